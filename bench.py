@@ -12,6 +12,9 @@ of the K moment rows, so the job is strong-scaled: `value` is the step rate of t
 
 Prints ONE JSON line on rank 0 with the driver's contract plus `roofline` (dominant kernel, HIP
 events on the engine's stream) and `cpu_baseline` (the oracle's C port on the host cores).
+
+`--dump-outputs DIR` also writes the posterior after the last timed step as DIR/<name>.npy (float64;
+same arguments, same inputs: two builds compare output for output).
 """
 from __future__ import annotations
 
@@ -26,12 +29,43 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def cpu_baseline(wl, seconds_budget: float = 20.0):
     """Time the oracle's fused C port (oracle/c/bb_port.c) on the same workload, same options."""
     from oracle import port
     return port.time_workload(wl, port.usable_cores(), seconds_budget)
+
+
+def dump_outputs(out_dir: str, eng, world: int, rank: int) -> None:
+    """--dump-outputs: what the timed path computed in its last step, as a caller of bb_run reads it back -- the posterior mean
+    (= mu), the posterior sigma (softplus(omega)) and omega -- one float64 DIR/<name>.npy each.  N > 1: every rank's own entries
+    are gathered onto rank 0 first (the replicated global latents are rank 0's copy).  Over DUMP_LIMIT_BYTES in all: the same
+    fixed, seeded sample of latents from every array, their flat indices in sample_index.npy."""
+    import numpy as np
+    mean, sigma = eng.posterior()
+    omega = eng.get_params()[1]
+    out = {"posterior_mean": mean, "posterior_sigma": sigma, "omega": omega}
+    if world > 1:
+        import torch.distributed as dist
+        ix = eng.owned()
+        parts = [None] * world
+        dist.all_gather_object(parts, (ix, [a[ix] for a in out.values()]))
+        for ix_r, vals in parts:
+            for a, v in zip(out.values(), vals):
+                a[ix_r] = v
+    if rank != 0:
+        return
+    D = mean.size
+    if len(out) * D * 8 > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - 4096) // (8 * (len(out) + 1))          # (4 KiB: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(D, size=k, replace=False))
+        out = {n: a[idx] for n, a in out.items()}
+        out["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in out.items():
+        np.save(os.path.join(out_dir, n + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def spawn_ranks(n: int) -> int:
@@ -94,6 +128,7 @@ def main():
     ap.add_argument("--timepoints", type=int, default=8)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-steps", type=int, default=200, help="eagerly launched steps timed per kernel for `roofline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the posterior they computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -172,6 +207,7 @@ def main():
             eng.run(args.warmup)
     else:
         eng.run(args.warmup)
+    steps_before = int(eng.stats()["steps_done"])
     fence()
     t0 = time.perf_counter()
     try:
@@ -189,6 +225,8 @@ def main():
         rank_ms = [round(x * 1e3, 4) for x in every]
         dt = float(t.item())
     st = eng.stats()
+    if int(st["steps_done"]) - steps_before != args.steps:
+        raise SystemExit(f"[rank {rank}] the timed region took {int(st['steps_done']) - steps_before} steps, --steps asked for {args.steps}")
     mu, sigma = eng.posterior()
     finite = bool(np.isfinite(mu).all() and np.isfinite(sigma).all())
     replicas_equal = None
@@ -200,6 +238,8 @@ def main():
         copies = [None] * world
         dist.all_gather_object(copies, (mu[glo:ghi].tobytes(), sigma[glo:ghi].tobytes()))
         replicas_equal = all(c == copies[0] for c in copies)
+    if args.dump_outputs:                # (before run_profiled below, which steps the engine on)
+        dump_outputs(args.dump_outputs, eng, world, rank)
 
     roofline = None
     if st["persistent_pairs"] > 0:      # (N > 1: rank 0's launch and rank 0's shard of the bytes -- a per-GPU figure)
