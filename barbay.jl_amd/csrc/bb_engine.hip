@@ -214,6 +214,60 @@ struct DevGuard {
 #endif
 #define BB_ENTER(h) DevGuard bb_dev_guard_((h)->o.device)
 
+// The environment switches, read once by bb_create and kept in the handle; a multi-device handle's shards get the
+// group's copy.  read_tuning says how each one is read.
+struct BBTuning {
+    bool no_hist_pack, no_host_tables, no_res, no_persist, no_stream, force_stream, any_parity, force_allreduce, p2p_self;
+    bool no_graph, graph_collective, no_regroup, no_reorder, nb_set, lead_set;
+    int nb, res_nb, ng, lead, pf, blocks_per_cu, nthr, row_l2;
+};
+
+static BBTuning read_tuning() {
+    auto set = [](const char* n) { return getenv(n) != nullptr; };
+    auto num = [](const char* n, int unset) { const char* v = getenv(n); return v ? atoi(v) : unset; };
+    auto on = [&](const char* n) { return num(n, 0) > 0; };
+    BBTuning t{};
+    t.no_hist_pack = on("BB_NO_HIST_PACK");
+    t.no_host_tables = on("BB_NO_HOST_TABLES");
+    t.no_res = on("BB_NO_RES");
+    t.no_persist = on("BB_NO_PERSIST");
+    t.no_stream = on("BB_NO_STREAM");
+    t.force_stream = on("BB_TUNE_STREAM");
+    t.any_parity = on("BB_TUNE_AP");
+    t.force_allreduce = on("BB_FORCE_ALLREDUCE");
+    t.p2p_self = on("BB_P2P_SELF");
+    t.no_graph = set("BB_NO_GRAPH");                  // (these four: set at all, "0" included)
+    t.graph_collective = set("BB_GRAPH_COLLECTIVE");
+    t.no_regroup = set("BB_NO_REGROUP");
+    t.no_reorder = set("BB_NO_REORDER");
+    t.nb_set = set("BB_TUNE_NB");                     // (odd: the resident tile map takes "set at all", the two-kernel map a value > 0)
+    t.nb = num("BB_TUNE_NB", 0);
+    t.res_nb = num("BB_TUNE_RES_NB", 0);              // (> 0: the resident launch's own tile size)
+    t.ng = num("BB_TUNE_NG", 0);                      // (try_resident takes 8, 16 or 32 where the shape allows)
+    t.lead_set = set("BB_TUNE_LEAD");
+    t.lead = num("BB_TUNE_LEAD", 65);
+    if (t.lead < 10 || t.lead > 100) t.lead = 100;
+    t.pf = num("BB_TUNE_PF", 1);
+    if (t.pf < 0 || t.pf > 3) t.pf = 0;
+    t.blocks_per_cu = std::max(num("BB_TUNE_BLOCKS_PER_CU", 1), 1);
+    t.nthr = num("BB_TUNE_NTHR", 0) >= 64 ? num("BB_TUNE_NTHR", 0) / 64 * 64 : 0;
+    t.row_l2 = num("BB_TUNE_ROW_L2", 1) == 0 ? 0 : 1;   // (odd: any value that reads as 0, "off" too, turns it off)
+    return t;
+}
+
+// What bb_run launches, planned by setup_persistent whenever the handle's shape or cross-GPU leg changes.
+enum { IMPL_TWO_KERNEL = 0, IMPL_PERSIST = 1, IMPL_RES = 2, IMPL_STREAM = 3 };     // (= bb_stats.resident_kernel)
+struct LaunchPlan {
+    int impl = IMPL_TWO_KERNEL;        // k_sample + k_update / k_persist (bb_persist.h) / k_res (bb_resident.h) / k_stream (bb_stream.h)
+    int P = 0;                         // pair slots per thread of the resident launch (0: none)
+    int NB = 0, NBL = 0, nblk = 0;     // its tile map: barcodes per tile, per leader tile (0: uniform), tiles (k_persist: the two-kernel map)
+    int ng = 8, pf = 0;                // k_res / k_stream: groups of the exchange's first hop (RunArgs.ng), window slot fetch (RunArgs.pf)
+    bool ms = false;                   // several samples per step or the ELBO trace (the MS instances)
+    const void* fn = nullptr;          // the resident kernel instance (none in the emulation)
+    std::string name;                  // ... as bb_kernel_name reports it
+    const char* why = nullptr;         // why no resident launch where one was wanted
+};
+
 struct bb_handle {
     DevModel M{};
     DevState S{};
@@ -222,11 +276,11 @@ struct bb_handle {
     std::vector<void*> owned;          // device allocations
     long long dev_bytes = 0;           // ... and their total size
     int NB = 0, nthr = 0, nblk = 0, ngeno_blk = 0;
+    int tile_cap = 0;                  // tiles the exchange, stamp, xsel and tile-table buffers hold: nblk + 8 (k_res's own map may need a few more)
     size_t lds_doubles = 0;            // dynamic LDS of the two-kernel path
     size_t lds_doubles_p0 = 0;         // ... of the resident launch (adds the lambda table)
     size_t lds_doubles_p = 0;          // ... plus the drawn-ahead normals and the cached counts (16 + 8 B per pair)
     long long b_lo = 0, b_hi = 0;      // barcode shard
-    int res_ng = 8;                    // k_res: groups of the exchange's first hop (RunArgs.ng)
     int cus = 256;                     // compute units of the device (one resident workgroup each)
     int g_lo = 0, g_hi = 0;            // genotype model: the genotypes whose theta this shard owns (all of them unless cut at genotype boundaries)
     std::vector<int> geno_ptr_h;       // genotype model: CSR offsets over genotypes (sorted geno_idx: first mutant of every genotype)
@@ -267,12 +321,9 @@ struct bb_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bb_ncclComm_t comm = nullptr;
 #endif
-    int persist_P = 0;                 // pairs per thread of the persistent launch (0 = not eligible)
-    int res_P = 0;                     // > 0: the launch is k_res (bb_resident.h, owner-computes) with this many pair slots per thread
-    int res_pf = 0;                    // ... when it fetches a step's window slot (RunArgs.pf)
-    bool res_stream = false;           // ... the launch is k_stream (bb_stream.h): res_P pair slots per thread, state streamed from memory
-    int res_NB = 0, res_NBL = 0, res_nblk = 0;   // ... its own tile map: barcodes per tile, per leader tile (0: uniform), tiles
-    BRLay Yh{};                        // its LDS carve-up (host copy) and device copy
+    BBTuning tune{};                   // the environment switches as bb_create found them
+    LaunchPlan plan;
+    BRLay Yh{};                        // k_res / k_stream: the LDS carve-up (host copy) and device copy
     BRLay* dY = nullptr;
     DevModel* dM = nullptr;            // device copies of the descriptors for the persistent launch
     DevState* dS = nullptr;
@@ -289,8 +340,7 @@ struct bb_handle {
     // cidx[i] = the caller's flat index of internal latent i (empty: identity); perm_m[m'] = the caller's mutant of internal mutant m'
     std::vector<long long> cidx;
     std::vector<int> perm_m;
-    bool force_reduce = false;         // BB_FORCE_ALLREDUCE=1: run the collective path even with one rank (tests)
-    bool use_reduce() const { return o.world_size > 1 || M.kind == BB_MODEL_GENOTYPE || force_reduce; }
+    bool use_reduce() const { return o.world_size > 1 || M.kind == BB_MODEL_GENOTYPE || tune.force_allreduce; }
 };
 
 template <class T>
@@ -376,8 +426,10 @@ static int upload_prior(bb_handle* h, int kind, const bb_prior* p, double dmean,
     return 0;
 }
 
-struct bb_handle;
-static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_handle** out);
+// what bb_create hands create_inner (and a multi-device handle's shards): the switches, and whether to lay the loglambda block out in
+// FRONT of the per-genotype / per-mutant blocks (the handle's internal order; the caller's stays the reference's source order)
+struct CreateCtx { BBTuning tune; bool loglambda_first; };
+static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out);
 // Rows of the TruncatedADAGrad window on a SHARDED handle (DevModel.Dh): the window is 2 x window doubles per latent -- a hundred
 // times everything else a handle holds -- and a shard only ever updates its own barcodes' latents, the replicated blocks and (genotype
 // model) the genotype block: one contiguous range of the flat vector per (block, replicate), the ranges every tile's segment table
@@ -389,8 +441,7 @@ static void hist_rows(bb_handle* h) {
     M.Dh = M.Dp;
     for (int k = 0; k < BK_COUNT; ++k) M.hd0[k] = M.hd1[k] = 0;
     for (int r = 0; r < BB_MAX_REP; ++r) M.hdl[r] = 0;
-    const char* ev = getenv("BB_NO_HIST_PACK");
-    if (h->o.world_size <= 1 || (ev && atoi(ev) > 0) || M.Dp >= (1ll << 31)) return;      // (a segment keeps its difference in an int)
+    if (h->o.world_size <= 1 || h->tune.no_hist_pack || M.Dp >= (1ll << 31)) return;      // (a segment keeps its difference in an int)
     const long long b0 = h->b_lo, nbt = h->b_hi - h->b_lo;
     const long long m0 = std::max(h->b_lo, M.nn) - M.nn, nmt = (std::max(h->b_hi, M.nn) - M.nn) - m0;
     long long c = 0;          // next free entry of the row
@@ -429,10 +480,7 @@ static void hist_rows(bb_handle* h) {
     M.Dh = Dh;
 }
 
-static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_handle** out);
-// bb_create -> create_inner (and the shards of a multi-device handle): lay the loglambda block out in FRONT of the per-genotype / per-mutant
-// blocks (the handle's internal order; the caller's stays the reference's source order) -- see bb_create
-static thread_local bool g_loglambda_first = false;
+static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out);
 static int ensure_scratch(bb_handle* h);
 static void owned_ranges(const bb_handle* sh, std::vector<std::pair<long long, long long>>& out);
 static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, bool apply, bool with_elbo);
@@ -455,6 +503,18 @@ static bb_persist_kernel persist_kernel(int kind, int P, int nthr, bool xg = fal
 #endif
 }
 #endif
+
+// f(std::integral_constant<int, KIND>{}) for the model kind: the host-side instances of templates over it
+template <class F>
+static void by_kind(int kind, F&& f) {
+    switch (kind) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{});
+    }
+}
 
 // the time-point count where all replicates share it (the compile-time-T instances), else 0
 static int uniform_T(const DevModel& M) {
@@ -529,9 +589,9 @@ static int sync_descriptors(bb_handle* h) {
     return h2d(h->dY, &h->Yh, sizeof(BRLay), h->stream);
 }
 
-// Genotype model: the tile table of k_res (br_tile_geno) -- tiles of at most NB barcodes (the first eight: NBL, if > 0) whose cuts
-// inside the mutants fall on genotype boundaries; tg[i] = first genotype tile i owns.  False if a genotype does not fit a tile.
-static bool build_geno_tiles(const bb_handle* h, int NB, int NBL, std::vector<long long>& tb, std::vector<int>& tg) {
+// Genotype model: the tile table of k_res (br_tile_geno) -- tiles of at most NB barcodes (the first ng, the leaders: NBL, if > 0) whose
+// cuts inside the mutants fall on genotype boundaries; tg[i] = first genotype tile i owns.  False if a genotype does not fit a tile.
+static bool build_geno_tiles(const bb_handle* h, int NB, int NBL, int ng, std::vector<long long>& tb, std::vector<int>& tg) {
     const DevModel& M = h->M;
     const std::vector<int>& ptr = h->geno_ptr_h;
     auto geno_of = [&](long long m) { return (int)(std::upper_bound(ptr.begin(), ptr.end(), (int)m) - ptr.begin()) - 1; };
@@ -540,7 +600,7 @@ static bool build_geno_tiles(const bb_handle* h, int NB, int NBL, std::vector<lo
     tg.clear();
     long long b = h->b_lo;
     while (b < h->b_hi) {
-        const int cap = (NBL > 0 && tb.size() < (size_t)h->res_ng) ? NBL : NB;
+        const int cap = (NBL > 0 && tb.size() < (size_t)ng) ? NBL : NB;
         long long e = std::min<long long>(b + cap, h->b_hi);
         if (e < h->b_hi && e > M.nn) {
             e = M.nn + ptr[(size_t)geno_of(e - M.nn)];       // back to the first mutant of the genotype the cut fell into
@@ -567,36 +627,29 @@ static bool build_geno_tiles(const bb_handle* h, int NB, int NBL, std::vector<lo
 // LDS tables another 1.8 us -- profiles/r03z_round3_final/fixed_cost.txt): per tile its segment table (br_build_segs, the same code),
 // once the tile-independent LDS tables (br_table_*).  BB_NO_HOST_TABLES=1: the kernels build them (A/B).
 template <int KIND>
-static void host_tables_kind(bb_handle* h, const RunArgs& A, const DevState& Sh, int nblk, int stride, std::vector<double>& tab) {
-    for (int b = 0; b < nblk; ++b) {
-        const BBTile t = KIND == 2 ? br_tile_geno(h->M, Sh, b, h->res_NB) : br_tile(h->M, A, b, h->res_NB);
+static void host_tables_kind(bb_handle* h, const RunArgs& A, const DevState& Sh, int NB, int stride, std::vector<double>& tab) {
+    for (int b = 0; b < A.nblk; ++b) {
+        const BBTile t = KIND == 2 ? br_tile_geno(h->M, Sh, b, NB) : br_tile(h->M, A, b, NB);
         const int g0 = KIND == 2 ? Sh.tile_g[b] : 0, g1 = KIND == 2 ? Sh.tile_g[b + 1] : 0;
         double* rec = tab.data() + (size_t)b * stride;
         const int n = br_build_segs<KIND>((BRSeg*)rec, h->M, h->Yh, t, b == 0, g0, g1);
         ((int*)(rec + stride - 1))[0] = n;
     }
 }
-static bool host_tables(bb_handle* h, const std::vector<long long>& tb, const std::vector<int>& tg) {
+static bool host_tables(bb_handle* h, const LaunchPlan& p, const std::vector<long long>& tb, const std::vector<int>& tg) {
     h->S.segtab = nullptr;
     h->S.ldstab = nullptr;
     h->S.segtab_stride = 0;
-    const char* ev = getenv("BB_NO_HOST_TABLES");
-    if (ev && atoi(ev) > 0) return true;
+    if (h->tune.no_host_tables) return true;
     const DevModel& M = h->M;
-    const int nblk = h->res_nblk, stride = BR_SEG_DOUBLES * (4 + 4 * M.R + 1) + 1;
+    const int stride = BR_SEG_DOUBLES * (4 + 4 * M.R + 1) + 1;
     RunArgs A = make_args(h, 0, 0, 1, true, false);
-    A.nblk = nblk; A.nbl = h->res_NBL; A.ng = h->res_ng;
+    A.nblk = p.nblk; A.nbl = p.NBL; A.ng = p.ng;
     DevState Sh = h->S;
     Sh.tile_b = tb.data();
     Sh.tile_g = tg.data();
-    std::vector<double> tab((size_t)nblk * stride, 0.0);
-    switch (M.kind) {
-    case 0: host_tables_kind<0>(h, A, Sh, nblk, stride, tab); break;
-    case 1: host_tables_kind<1>(h, A, Sh, nblk, stride, tab); break;
-    case 2: host_tables_kind<2>(h, A, Sh, nblk, stride, tab); break;
-    case 3: host_tables_kind<3>(h, A, Sh, nblk, stride, tab); break;
-    default: host_tables_kind<4>(h, A, Sh, nblk, stride, tab);
-    }
+    std::vector<double> tab((size_t)p.nblk * stride, 0.0);
+    by_kind(M.kind, [&](auto kindc) { host_tables_kind<decltype(kindc)::value>(h, A, Sh, p.NB, stride, tab); });
     const int K = M.K, Tt = M.Ttot, R = M.R;
     std::vector<int> img((size_t)3 * K + 4 * Tt + 4 * R + 4, 0);
     for (int j = 0; j < K; ++j) br_table_row(M, h->Yh, j, &img[2 * j], &img[2 * K + j]);
@@ -612,9 +665,10 @@ static bool host_tables(bb_handle* h, const std::vector<long long>& tb, const st
     return true;
 }
 
-static bool try_resident(bb_handle* h, bool any_parity) {
-    const char* ev = getenv("BB_NO_RES");
-    if (ev && atoi(ev) > 0) return false;
+// k_res or k_stream for this handle's shape, with its own tile map: true and `p` filled in where one fits
+static bool try_resident(bb_handle* h, bool any_parity, LaunchPlan& p) {
+    const BBTuning& tu = h->tune;
+    if (tu.no_res) return false;
     if (!br_eligible(h->M)) return false;
     if (!any_parity && br_any_parity(h->M)) return false;
     // tile map: leaders (tiles 0 .. 7) hold `frac` of a tile's barcodes (br_tile); BB_TUNE_LEAD=100 keeps all tiles alike
@@ -622,11 +676,10 @@ static bool try_resident(bb_handle* h, bool any_parity) {
     // The two-kernel step may run more tiles than the device has compute units (its tiles must fit LDS with ITS tables: config 5 on one
     // GPU runs 512 of them); a resident launch needs every tile resident -- one per compute unit: its own base map then
     int NB0 = h->NB, nblk0 = h->nblk;
-    if (nblk0 > h->cus && !getenv("BB_TUNE_NB")) { NB0 = (int)((nbar + h->cus - 1) / h->cus); nblk0 = (int)((nbar + NB0 - 1) / NB0); }
+    if (nblk0 > h->cus && !tu.nb_set) { NB0 = (int)((nbar + h->cus - 1) / h->cus); nblk0 = (int)((nbar + NB0 - 1) / NB0); }
     // BB_TUNE_RES_NB (tests): the resident launch's own tile size -- a cut of a BASELINE problem with the full-size tile geometry even where
     // the two-kernel step's tables would not fit such a tile (config 5 on one GPU: 782 barcodes per tile)
-    const char* res_nb = getenv("BB_TUNE_RES_NB");
-    if (res_nb && atoi(res_nb) > 0) { NB0 = atoi(res_nb); nblk0 = (int)((nbar + NB0 - 1) / NB0); }
+    if (tu.res_nb > 0) { NB0 = tu.res_nb; nblk0 = (int)((nbar + NB0 - 1) / NB0); }
     int NB = NB0, NBL = 0, nblk = nblk0;
     // Groups of the exchange's first hop.  Round 2: 16 on one GPU (a leader then fetched its 16 members' rows in one round of loads, the
     // consume ran on two thread groups).  Round 3, tagged rows + leaders that poll their members in chunks of eight on as many thread
@@ -634,31 +687,25 @@ static bool try_resident(bb_handle* h, bool any_parity) {
     // every tile's consume is one thread group's eight loads -- C2 82.7 -> 83.5 k steps/s, C4 94.1 -> 94.9 k, C3 57.1 -> 57.7 k against 16
     // (profiles/r03g_parallel_leaders).  The cross-GPU inbox protocol is laid out for 8.  BB_TUNE_NG overrides (8 or 16).
     if (h->M.K + 2 * h->M.nt1 > h->nthr) return false;      // (one thread per row entry: bbp_consume_tg / _tgx, the leaders' chunk sums)
-    {
-        const int KK = h->M.K + 2 * h->M.nt1;
-        const bool can16 = !h->p2p_on && nblk0 >= 64 && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128);
-        int ng = (can16 && !(BR_TG && BR_LEAD_PAR && h->nthr >= 4 * ((KK + 63) & ~63))) ? 16 : 8;
-        if ((ev = getenv("BB_TUNE_NG")) && (atoi(ev) == 8 || (atoi(ev) == 16 && !h->p2p_on && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128)))) ng = atoi(ev);
+    const int KK = h->M.K + 2 * h->M.nt1;
+    const bool can16 = !h->p2p_on && nblk0 >= 64 && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128);
+    int ng = (can16 && !(BR_TG && BR_LEAD_PAR && h->nthr >= 4 * ((KK + 63) & ~63))) ? 16 : 8;
+    if (tu.ng == 8 || (tu.ng == 16 && !h->p2p_on && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128))) ng = tu.ng;
 #if BR_TG
-        // self-validating rows: a leader takes its members' rows in batches of eight loads per lane -- 32 groups of 8 on a full grid:
-        // one batch, one round trip (the tile's consume then runs on four thread groups)
-        if (ev && atoi(ev) == 32 && !h->p2p_on && nblk0 >= 64 && h->nthr >= 4 * ((KK + 63) & ~63)) ng = 32;
+    // self-validating rows: a leader takes its members' rows in batches of eight loads per lane -- 32 groups of 8 on a full grid:
+    // one batch, one round trip (the tile's consume then runs on four thread groups)
+    if (tu.ng == 32 && !h->p2p_on && nblk0 >= 64 && h->nthr >= 4 * ((KK + 63) & ~63)) ng = 32;
 #endif
-        h->res_ng = ng;
-    }
-    const int NGh = h->res_ng;
-    int pct = (ev = getenv("BB_TUNE_LEAD")) ? atoi(ev) : 65;
-    if (pct < 10 || pct > 100) pct = 100;
-    const bool nb_fixed = getenv("BB_TUNE_NB") != nullptr || (res_nb && atoi(res_nb) > 0);
-    ev = getenv("BB_TUNE_LEAD");
-    if (pct < 100 && nblk0 >= 2 * NGh && (!nb_fixed || ev)) {
+    const int pct = tu.lead;
+    const bool nb_fixed = tu.nb_set || tu.res_nb > 0;
+    if (pct < 100 && nblk0 >= 2 * ng && (!nb_fixed || tu.lead_set)) {
         if (!nb_fixed) {
-            const double tiles = (double)nblk0 - (double)NGh * (1.0 - pct / 100.0);      // in units of a full tile
+            const double tiles = (double)nblk0 - (double)ng * (1.0 - pct / 100.0);      // in units of a full tile
             NB = (int)std::ceil((double)nbar / tiles);
         }
         NBL = std::max(1, (int)(NB * (pct / 100.0)));
-        const long long rest = nbar - (long long)NGh * NBL;
-        nblk = NGh + (int)((std::max<long long>(rest, 0) + NB - 1) / NB);
+        const long long rest = nbar - (long long)ng * NBL;
+        nblk = ng + (int)((std::max<long long>(rest, 0) + NB - 1) / NB);
         const long long p_uni = (br_tile_span(h->M, NB0, true) + h->nthr - 1) / h->nthr, p_new = (br_tile_span(h->M, NB, true) + h->nthr - 1) / h->nthr;
         // stay uniform where rounding pushed the map over the grid that fits, or the slightly larger tiles need another pair slot
         if (nblk > nblk0 + (nb_fixed ? 8 : 0) || p_new > p_uni) { NB = NB0; NBL = 0; nblk = nblk0; }
@@ -667,12 +714,12 @@ static bool try_resident(bb_handle* h, bool any_parity) {
     std::vector<int> tg;
     if (h->M.kind == BB_MODEL_GENOTYPE) {
         // cuts on genotype boundaries leave tiles partly empty: grow the tile until the map fits the grid again
-        const int limit = std::max(nblk0, std::min(nblk0 + 8, h->cus));      // (the exchange buffers hold nblk + 8 tiles)
+        const int limit = std::max(nblk0, std::min(nblk0 + 8, h->cus));
         bool ok = false;
         for (int grow = 0; grow <= NB / 2 + 8 && !ok; ++grow) {
             const int nb = NB + grow, nbl = NBL > 0 ? std::max(1, (int)((long long)NBL * nb / NB)) : 0;
-            if (build_geno_tiles(h, nb, nbl, tb, tg) && (int)tb.size() - 1 <= limit) { ok = true; NB = nb; NBL = nbl; }
-            else if (nb_fixed && NBL > 0 && build_geno_tiles(h, nb, 0, tb, tg) && (int)tb.size() - 1 <= limit) { ok = true; NB = nb; NBL = 0; }
+            if (build_geno_tiles(h, nb, nbl, ng, tb, tg) && (int)tb.size() - 1 <= limit) { ok = true; NB = nb; NBL = nbl; }
+            else if (nb_fixed && NBL > 0 && build_geno_tiles(h, nb, 0, ng, tb, tg) && (int)tb.size() - 1 <= limit) { ok = true; NB = nb; NBL = 0; }
         }
         if (!ok) return false;
         nblk = (int)tb.size() - 1;
@@ -681,76 +728,83 @@ static bool try_resident(bb_handle* h, bool any_parity) {
     if (!h->p2p_on && h->M.Dh != h->M.Dp) return false;      // (packed window rows: only the cross-GPU instances read the segments' differences)
     int P = (int)((br_tile_span(h->M, NB, true) + h->nthr - 1) / h->nthr);
     // more pair slots than the register file holds: k_stream (bb_stream.h) -- the same tile map, the per-pair state streamed
+    const int Pmax = h->nthr > 512 ? 2 : (h->nthr > 256 ? 3 : 4);
     bool stream = false;
-    const bool force_stream = (ev = getenv("BB_TUNE_STREAM")) && atoi(ev) > 0;        // (tests: small shapes through k_stream)
-    if (force_stream || P > (h->nthr > 512 ? 2 : (h->nthr > 256 ? 3 : 4))) {
+    if (tu.force_stream || P > Pmax) {        // (BB_TUNE_STREAM, tests: small shapes through k_stream)
         const int T0 = uniform_T(h->M);
-        const bool nostream = (ev = getenv("BB_NO_STREAM")) && atoi(ev) > 0;
         // every replicate the same even T (instances: 4, 6, 8), flat-index-aligned pairs, one GPU; several samples per step / the ELBO trace:
-        // the MS instances (T = 6, 8 at 1024 threads; tests: 512)
-        stream = !nostream && !br_any_parity(h->M) && (T0 == 8 || T0 == 6 || T0 == 4) && h->nthr % 64 == 0 && !h->p2p_on;
-        if (stream) {          // (a barcode takes a power-of-two number of lanes there: T = 6 four)
-            P = (int)((br_tile_span(h->M, NB, true, true) + h->nthr - 1) / h->nthr);
-            if (P > 64) stream = false;
-        }
-        if (!stream && !force_stream) return false;
-        if (!stream) { P = (int)((br_tile_span(h->M, NB, true) + h->nthr - 1) / h->nthr); if (P > (h->nthr > 512 ? 2 : (h->nthr > 256 ? 3 : 4))) return false; }
+        // the MS instances (T = 6, 8 at 1024 threads; tests: 512).  A barcode takes a power-of-two number of lanes there: T = 6 four.
+        const int Ps = (int)((br_tile_span(h->M, NB, true, true) + h->nthr - 1) / h->nthr);
+        stream = !tu.no_stream && !br_any_parity(h->M) && (T0 == 8 || T0 == 6 || T0 == 4) && h->nthr % 64 == 0 && !h->p2p_on && Ps <= 64;
+        if (stream) P = Ps;
+        else if (P > Pmax) return false;
     }
     // When the window slot is fetched (RunArgs.pf).  In the exchange's shadow (round 2) its 32 B per latent of HBM reads compete with
     // the exchange's own loads and stores: at the start of the S pass instead, C2 73.1 -> 77.7 k steps/s, C4 87.1 -> 89.1 k
     // (profiles/r03b_tagged_rows/prefetch_timing_on_lean_kernel.txt) -- where the slot buffer fits beside the moment contributions
-    int pf = (ev = getenv("BB_TUNE_PF")) ? atoi(ev) : 1;
-    if (pf < 0 || pf > 3 || h->o.optimizer != BB_OPT_TRUNCATED_ADAGRAD) pf = 0;
-    if (stream) pf = 0;
+    int pf = h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && !stream ? tu.pf : 0;
     BRLay Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, pf == 1 || pf == 2, stream);
     if (pf == 3) Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false);
     else if (pf != 0 && (size_t)Y.total * 8 > 160 * 1024) { pf = 0; Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false); }      // (no room for a slot buffer of its own: in the exchange's shadow; pf = 3, behind the exchange, measured 6% slower on C3)
     if ((size_t)Y.total * 8 > 160 * 1024) return false;
-#ifndef BB_EMU
-    const bool ms = h->o.samples_per_step != 1 || h->o.elbo_every != 0;
-    const void* k = stream ? (const void*)stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), nullptr, ms)
-                           : (const void*)res_kernel(h->M.kind, P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), ms);
+    const char* nm = "";
+    const void* k = nullptr;
+#ifdef BB_EMU
+    // (the emulation runs the block programs as host functions: it names the launch, the compile-time T / AP / MS are the product's)
+    char emu_nm[64];
+    if (stream) snprintf(emu_nm, sizeof emu_nm, "emu:k_stream<%d,%d,%d%s>", h->M.kind, h->nthr, uniform_T(h->M), p.ms ? ",true" : "");
+    else snprintf(emu_nm, sizeof emu_nm, "emu:k_res<%d,%d,%d,%s,*,%s,%s>", h->M.kind, P, h->nthr, h->p2p_on ? "true" : "false",
+                  br_any_parity(h->M) ? "true" : "false", p.ms ? "true" : "false");
+    nm = emu_nm;
+#else
+    k = stream ? (const void*)stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), &nm, p.ms)
+               : (const void*)res_kernel(h->M.kind, P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), p.ms, &nm);
     if (!k) return false;
     const int lds = Y.total * 8;
     if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
     int per_cu = 0;
-    hipDeviceProp_t pr;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, h->nthr, (size_t)lds) != hipSuccess ||
-        hipGetDeviceProperties(&pr, h->o.device) != hipSuccess || (long long)per_cu * pr.multiProcessorCount < nblk) return false;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, h->nthr, (size_t)lds) != hipSuccess || (long long)per_cu * h->cus < nblk) return false;
 #endif
+    if (nblk > h->tile_cap) return false;       // (more tiles than the exchange, stamp, xsel and tile-table buffers hold)
     if (h->M.kind == BB_MODEL_GENOTYPE) {
-        if (!h->d_tile_b && (dalloc(h, &h->d_tile_b, (size_t)h->nblk + 10) || dalloc(h, &h->d_tile_g, (size_t)h->nblk + 10))) return false;
+        if (!h->d_tile_b && (dalloc(h, &h->d_tile_b, (size_t)h->tile_cap + 2) || dalloc(h, &h->d_tile_g, (size_t)h->tile_cap + 2))) return false;
         if (h2d(h->d_tile_b, tb.data(), tb.size() * 8, h->stream) || h2d(h->d_tile_g, tg.data(), tg.size() * 4, h->stream)) return false;
         h->S.tile_b = h->d_tile_b;
         h->S.tile_g = h->d_tile_g;
     }
     h->Yh = Y;
-    h->res_P = P;
-    h->res_NB = NB;
-    h->res_NBL = NBL;
-    h->res_nblk = nblk;
-    h->res_pf = pf;
-    h->res_stream = stream;
-    if (stream && h->o.samples_per_step > 1 && ensure_scratch(h)) { h->res_P = 0; return false; }      // (the samples' gradient sums live in gacc_mu / gacc_om)
+    LaunchPlan r = p;
+    r.impl = stream ? IMPL_STREAM : IMPL_RES;
+    r.P = P; r.NB = NB; r.NBL = NBL; r.nblk = nblk; r.ng = ng; r.pf = pf; r.fn = k; r.name = nm;
+    if (stream && h->o.samples_per_step > 1 && ensure_scratch(h)) return false;      // (the samples' gradient sums live in gacc_mu / gacc_om)
     h->lds_doubles_p = (size_t)Y.total;
-    if (!host_tables(h, tb, tg)) { h->res_P = 0; return false; }
+    if (!host_tables(h, r, tb, tg)) return false;
+    p = r;
     return true;
 }
 
-static int setup_persistent(bb_handle* h) {
-    h->persist_P = 0;
-    const char* ev = getenv("BB_NO_PERSIST");
-    const bool want = h->o.launch_mode != 1 && !(ev && atoi(ev) > 0 && h->o.launch_mode == 0);
-    const char* why = nullptr;
+// h->plan for launch_mode `mode` (0: resident where possible, 1: two kernels, 2: resident or an error saying why not)
+static int setup_persistent(bb_handle* h, int mode) {
+    LaunchPlan& p = h->plan;
+    p = LaunchPlan{};
+    p.NB = h->NB;
+    p.nblk = h->nblk;
+#ifdef BB_EMU
+    p.name = "emu:k_sample + k_update";
+#else
+    p.name = "k_sample<" + std::to_string(h->M.kind) + "> + k_update<" + std::to_string(h->M.kind) + ">";
+#endif
     // several MC samples per step (Turing.ADVI(samples_per_step, ..), src/vi.jl:98) and ELBO recording: k_res's MS instances (round 4: sharded too --
     // every sample is an exchange of its own, the inbox epochs count exchanges)
-    const bool ms = h->o.samples_per_step != 1 || h->o.elbo_every != 0;
-    if (h->force_reduce || (h->o.world_size != 1 && !h->p2p_on)) why = "sharded run";
-    else if (h->p2p_on && h->nblk < 8) why = "fewer than 8 tiles on this rank";   // (k_res's own tile map never has fewer tiles than this one)
-    h->res_P = 0;
-    const bool ap_first = ms || h->M.kind == BB_MODEL_GENOTYPE || (getenv("BB_TUNE_AP") && atoi(getenv("BB_TUNE_AP")) > 0);
-    if (!why && want && try_resident(h, ap_first)) { h->persist_P = h->res_P; return 0; }
-    if (!why && ms) why = h->o.samples_per_step != 1 ? "samples_per_step != 1 and the shape has no owner-computes instance" : "ELBO recording is on and the shape has no owner-computes instance";
+    p.ms = h->o.samples_per_step != 1 || h->o.elbo_every != 0;
+    const bool want = mode != 1 && !(h->tune.no_persist && mode == 0);
+    // what rules out every resident launch (k_res's own tile map never has fewer tiles than this one)
+    const char* structural = (h->tune.force_allreduce || (h->o.world_size != 1 && !h->p2p_on)) ? "sharded run"
+                             : (h->p2p_on && h->nblk < 8) ? "fewer than 8 tiles on this rank" : nullptr;
+    const bool ap_first = p.ms || h->M.kind == BB_MODEL_GENOTYPE || h->tune.any_parity;
+    const char* why = structural;
+    if (!why && want && try_resident(h, ap_first, p)) return 0;
+    if (!why && p.ms) why = h->o.samples_per_step != 1 ? "samples_per_step != 1 and the shape has no owner-computes instance" : "ELBO recording is on and the shape has no owner-computes instance";
     if (!why && h->M.kind == BB_MODEL_GENOTYPE)
         why = h->M.geno_sorted ? "genotype model: no tile map with whole genotypes per tile fits the device" : "genotype model: geno_idx is not in consecutive runs (a tile must hold whole genotypes)";
     int P = 0;
@@ -761,35 +815,41 @@ static int setup_persistent(bb_handle* h) {
         if (h->p2p_on && P != 1) why = "sharded resident launch holds one pair per thread";
         h->lds_doubles_p = h->lds_doubles_p0 + (size_t)3 * P * h->nthr;        // drawn-ahead normals (16 B / pair) + cached counts (8 B)
     }
-#ifndef BB_EMU
+    const char* nm = "";
+    const void* k = nullptr;
+#ifdef BB_EMU
+    char emu_nm[48];
+    snprintf(emu_nm, sizeof emu_nm, "emu:k_persist<%d,%d,%d>", h->M.kind, P, h->nthr);
+    nm = emu_nm;
+#else
     if (!why && want) {
-        bb_persist_kernel k = persist_kernel(h->M.kind, P, h->nthr, h->p2p_on);
+        k = (const void*)persist_kernel(h->M.kind, P, h->nthr, h->p2p_on, &nm);
         const int lds = (int)(h->lds_doubles_p * 8);
+        int per_cu = 0;
         if (lds > 160 * 1024) why = "tile does not fit LDS with the lambda table";
         else if (!k) why = "no kernel instance";
-        else {
-            if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-                why = "cannot raise dynamic LDS";
-            int per_cu = 0, cus = 0;
-            hipDeviceProp_t pr;
-            if (!why && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k, h->nthr, (size_t)lds) == hipSuccess &&
-                hipGetDeviceProperties(&pr, h->o.device) == hipSuccess) {
-                cus = pr.multiProcessorCount;
-                if ((long long)per_cu * cus < h->nblk) why = "grid does not fit resident on the device";
-            } else if (!why) why = "occupancy query failed";
-        }
+        else if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) why = "cannot raise dynamic LDS";
+        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, h->nthr, (size_t)lds) != hipSuccess) why = "occupancy query failed";
+        else if ((long long)per_cu * h->cus < h->nblk) why = "grid does not fit resident on the device";
     }
 #endif
     if (why) {
         // k_persist cannot (tile too large for its state, no instance, sharded with more than one pair per thread ...): k_res's
         // any-parity instances as the second chance
-        const bool structural = ms || h->force_reduce || (h->o.world_size != 1 && !h->p2p_on) || (h->p2p_on && h->nblk < 8);
-        if (want && !structural && !ap_first && try_resident(h, true)) { h->persist_P = h->res_P; return 0; }
-        if (h->o.launch_mode == 2) return bb_fail(BB_ERR_UNSUPPORTED, "launch_mode = 2 (persistent) not possible: %s", why);
-        return 0;
+        if (want && !structural && !ap_first && try_resident(h, true, p)) return 0;
+        p.why = why;
+        return mode == 2 ? bb_fail(BB_ERR_UNSUPPORTED, "launch_mode = 2 (persistent) not possible: %s", why) : 0;
     }
-    if (want) h->persist_P = P;
+    if (want) { p.impl = IMPL_PERSIST; p.P = P; p.fn = k; p.name = nm; }
     return 0;
+}
+
+// the arguments of the planned resident launch: its tile map (k_persist's is the two-kernel one), every sample an exchange of its own
+// (k_persist runs one sample per step)
+static RunArgs resident_args(const bb_handle* h) {
+    RunArgs A = make_args(h, h->step, 0, h->o.samples_per_step, true, false);
+    A.nblk = h->plan.nblk; A.nbl = h->plan.NBL; A.ng = h->plan.ng; A.pf = h->plan.pf;
+    return A;
 }
 
 #ifdef BB_EMU
@@ -871,11 +931,11 @@ static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nste
     const int ring = A.elbo_every > 0 ? (int)((step / (unsigned long long)A.elbo_every) % BB_ELBO_RING) : 0;
     const bool xg = h->p2p_on;
     const BBSlot wslot = bb_slot_of(A, step);
-    for (int b = 0; b < (phase == 2 ? bbp_groups(A) : h->res_nblk); ++b) {
+    for (int b = 0; b < (phase == 2 ? bbp_groups(A) : h->plan.nblk); ++b) {
         BBCtx cx = cxof(b);
         BRSt<PP>* sb = st + (size_t)b * h->nthr;
         if (phase == 0) {
-            br_prologue<KIND, PP, AP>(cx, h->M, h->S, A, Y, h->res_NB, sb);
+            br_prologue<KIND, PP, AP>(cx, h->M, h->S, A, Y, h->plan.NB, sb);
             br_draw_ahead<KIND, PP, AP>(cx, A, Y, sb, (unsigned long long)h->step);
             if (A.pf == 2) br_prefetch_slot<PP>(cx, h->M, h->S, A, Y, sb, bb_slot_of(A, (unsigned long long)h->step).slot);
         } else if (phase == 1) {
@@ -894,10 +954,10 @@ static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nste
             else if (MSrun) br_xchg_consume<KIND, PP, false, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp, last ? wslot.slot : -1);
             else br_xchg_consume<KIND, PP, false, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, false, 0, 0, wslot.slot);
             // (the compile-time-T forms of the G pass where the product has them, so that the emulation covers that code too)
-            if (MSrun) br_update<KIND, PP, 0, AP, true>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->res_NB, smp, NS);
-            else if (!AP && uniform_T(h->M) == 8) br_update<KIND, PP, 8, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->res_NB);
-            else if (!AP && uniform_T(h->M) == 6) br_update<KIND, PP, 6, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->res_NB);
-            else br_update<KIND, PP, 0, AP>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->res_NB);
+            if (MSrun) br_update<KIND, PP, 0, AP, true>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB, smp, NS);
+            else if (!AP && uniform_T(h->M) == 8) br_update<KIND, PP, 8, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
+            else if (!AP && uniform_T(h->M) == 6) br_update<KIND, PP, 6, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
+            else br_update<KIND, PP, 0, AP>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
         } else {
             br_epilogue<KIND, PP, AP>(cx, h->S, sb, (unsigned long long)(h->step + nsteps), E.ok == 0);
         }
@@ -921,24 +981,24 @@ static void emu_stream_phase(EmuPersist& E, int phase, long long it, long long n
     const int ring = A.elbo_every > 0 ? (int)((step / (unsigned long long)A.elbo_every) % BB_ELBO_RING) : 0;
     const BSMs ms = MS ? bs_ms_of(A, step, smp, NS, want_el, rec(step + 1)) : bs_ms_plain((unsigned)step);
     BRSt<1>* nost = nullptr;
-    for (int b = 0; b < (phase == 2 ? bbp_groups(A) : h->res_nblk); ++b) {
+    for (int b = 0; b < (phase == 2 ? bbp_groups(A) : h->plan.nblk); ++b) {
         BBCtx cx = cxof(b);
         BSG* gb = gs + (size_t)b * h->nthr;
         int* bad_any = (int*)(cx.lds + Y.L.misc) + 3;
         if (phase == 0) {
-            br_tile_setup<KIND>(cx, h->M, h->S, A, Y, h->res_NB, KIND <= 2 ? h->nthr / 16 : h->nthr / 64);
+            br_tile_setup<KIND>(cx, h->M, h->S, A, Y, h->plan.NB, KIND <= 2 ? h->nthr / 16 : h->nthr / 64);
             *bad_any = 0;
             // (the launch's first sample; later ones: inside the G passes)
-            bs_sample0<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->res_NB, h->res_P, (unsigned)h->step, gb, (int)(((unsigned long long)h->step * (unsigned long long)NS) & 1ull), rec((unsigned long long)h->step));
+            bs_sample0<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)h->step, gb, (int)(((unsigned long long)h->step * (unsigned long long)NS) & 1ull), rec((unsigned long long)h->step));
         } else if (phase == 1) {
-            bs_moments<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->res_NB, h->res_P, (unsigned)step, gb, ms.buf, want_el);
+            bs_moments<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, gb, ms.buf, want_el);
             br_row_publish<1, true, MS>(cx, h->M, h->S, Y, nost, A.xepoch0 + (unsigned)(xc + 1), want_el);
         } else if (phase == 2) {
             br_xchg_lead<false>(cx, h->M, h->S, A, Y, xc, &E.ok);
         } else if (phase == 3) {
             br_xchg_consume<KIND, 1, false, MS>(cx, h->M, h->S, A, Y, nost, xc, &E.ok, want_el, ring, smp);
-            bs_update_l<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->res_NB, h->res_P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
-            bs_update_u<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->res_NB, h->res_P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
+            bs_update_l<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
+            bs_update_u<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
         } else {
             if (*bad_any) h->S.hstatus[1] = 1u;
             if (b == 0) { h->S.ctr[0] = (unsigned long long)(h->step + nsteps); h->S.ctr[1] = h->S.ctr[0]; }
@@ -947,59 +1007,43 @@ static void emu_stream_phase(EmuPersist& E, int phase, long long it, long long n
 }
 
 static void emu_persist_dispatch(EmuPersist& E, int phase, long long it, long long nsteps) {
-    if (E.h->res_P && E.h->res_stream) {
+    const LaunchPlan& p = E.h->plan;
+    if (p.impl == IMPL_STREAM) {
         const int T = uniform_T(E.h->M);
         auto byT = [&](auto kindc) {
             constexpr int KIND = decltype(kindc)::value;
-            const bool ms = E.h->o.samples_per_step != 1 || E.h->o.elbo_every != 0;
-            if (T == 8) ms ? emu_stream_phase<KIND, 8, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 8, false>(E, phase, it, nsteps);
-            else if (T == 6) ms ? emu_stream_phase<KIND, 6, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 6, false>(E, phase, it, nsteps);
-            else ms ? emu_stream_phase<KIND, 4, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 4, false>(E, phase, it, nsteps);
+            if (T == 8) p.ms ? emu_stream_phase<KIND, 8, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 8, false>(E, phase, it, nsteps);
+            else if (T == 6) p.ms ? emu_stream_phase<KIND, 6, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 6, false>(E, phase, it, nsteps);
+            else p.ms ? emu_stream_phase<KIND, 4, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 4, false>(E, phase, it, nsteps);
         };
-        switch (E.h->M.kind) {
-        case 0: byT(std::integral_constant<int, 0>{}); break;
-        case 1: byT(std::integral_constant<int, 1>{}); break;
-        case 2: byT(std::integral_constant<int, 2>{}); break;
-        case 3: byT(std::integral_constant<int, 3>{}); break;
-        default: byT(std::integral_constant<int, 4>{});
-        }
+        by_kind(E.h->M.kind, byT);
         return;
     }
-    if (E.h->res_P) {
+    if (p.impl == IMPL_RES) {
         const bool ap = br_any_parity(E.h->M);
         auto byP = [&](auto kindc) {
             constexpr int KIND = decltype(kindc)::value;
-            switch (E.h->res_P) {
+            switch (p.P) {
             case 1: ap ? emu_res_phase<KIND, 1, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 1, false>(E, phase, it, nsteps); break;
             case 2: ap ? emu_res_phase<KIND, 2, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 2, false>(E, phase, it, nsteps); break;
             case 3: ap ? emu_res_phase<KIND, 3, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 3, false>(E, phase, it, nsteps); break;
             default: ap ? emu_res_phase<KIND, 4, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 4, false>(E, phase, it, nsteps);
             }
         };
-        switch (E.h->M.kind) {
-        case 0: byP(std::integral_constant<int, 0>{}); break;
-        case 1: byP(std::integral_constant<int, 1>{}); break;
-        case 2: byP(std::integral_constant<int, 2>{}); break;
-        case 3: byP(std::integral_constant<int, 3>{}); break;
-        default: byP(std::integral_constant<int, 4>{});
-        }
+        by_kind(E.h->M.kind, byP);
         return;
     }
-    auto byP = [&](auto kindc) {
+    by_kind(E.h->M.kind, [&](auto kindc) {
         constexpr int KIND = decltype(kindc)::value;
-        switch (E.h->persist_P) {
-        case 1: emu_persist_phase<KIND, 1>(E, phase, it, nsteps); break;
-        case 2: emu_persist_phase<KIND, 2>(E, phase, it, nsteps); break;
-        case 3: emu_persist_phase<KIND, 3>(E, phase, it, nsteps); break;
-        default: emu_persist_phase<KIND, 4>(E, phase, it, nsteps);
+        if constexpr (KIND != BB_MODEL_GENOTYPE) {          // (the genotype model has no k_persist)
+            switch (p.P) {
+            case 1: emu_persist_phase<KIND, 1>(E, phase, it, nsteps); break;
+            case 2: emu_persist_phase<KIND, 2>(E, phase, it, nsteps); break;
+            case 3: emu_persist_phase<KIND, 3>(E, phase, it, nsteps); break;
+            default: emu_persist_phase<KIND, 4>(E, phase, it, nsteps);
+            }
         }
-    };
-    switch (E.h->M.kind) {
-    case 0: byP(std::integral_constant<int, 0>{}); break;
-    case 1: byP(std::integral_constant<int, 1>{}); break;
-    case 3: byP(std::integral_constant<int, 3>{}); break;
-    default: byP(std::integral_constant<int, 4>{});
-    }
+    });
 }
 
 static size_t emu_rst_bytes(int P) {
@@ -1013,14 +1057,14 @@ static int emu_run_group(bb_handle** hs, int n, long long nsteps) {
     std::vector<EmuPersist> es((size_t)n);
     for (int i = 0; i < n; ++i) {
         bb_handle* h = hs[i];
+        const LaunchPlan& p = h->plan;
         es[i].h = h;
-        es[i].A = make_args(h, h->step, 0, h->res_P ? h->o.samples_per_step : 1, true, false);
-        if (h->res_P) { es[i].A.nblk = h->res_nblk; es[i].A.nbl = h->res_NBL; es[i].A.ng = h->res_ng; es[i].A.pf = h->res_pf; }
-        es[i].lds.assign((size_t)std::max(h->nblk, h->res_nblk) * (h->lds_doubles_p + 64), 0.0);
-        es[i].st.assign((size_t)std::max(h->nblk, h->res_nblk) * h->nthr * (h->res_stream ? sizeof(BSG) : (h->res_P ? emu_rst_bytes(h->res_P) : emu_pst_bytes(h->persist_P))), 0);
+        es[i].A = resident_args(h);
+        es[i].lds.assign((size_t)std::max(h->nblk, p.nblk) * (h->lds_doubles_p + 64), 0.0);
+        es[i].st.assign((size_t)std::max(h->nblk, p.nblk) * h->nthr * (p.impl == IMPL_STREAM ? sizeof(BSG) : (p.impl == IMPL_RES ? emu_rst_bytes(p.P) : emu_pst_bytes(p.P))), 0);
         emu_persist_dispatch(es[i], 0, 0, nsteps);
     }
-    const long long NS = hs[0]->res_P ? std::max(hs[0]->o.samples_per_step, 1) : 1;
+    const long long NS = std::max(hs[0]->o.samples_per_step, 1);
     for (long long it = 0; it < nsteps * NS; ++it)
         for (int phase = 1; phase <= 3; ++phase)
             for (int i = 0; i < n; ++i) emu_persist_dispatch(es[i], phase, it, nsteps);
@@ -1037,7 +1081,7 @@ static int emu_run_group(bb_handle** hs, int n, long long nsteps) {
 extern "C" int bb_emu_run_group(bb_handle** hs, int32_t n, int64_t nsteps) {
     if (!hs || n < 1 || nsteps < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
     for (int i = 0; i < n; ++i)
-        if (!hs[i] || hs[i]->persist_P == 0) return bb_fail(BB_ERR_INVALID, "handle %d has no resident launch", i);
+        if (!hs[i] || hs[i]->plan.impl == IMPL_TWO_KERNEL) return bb_fail(BB_ERR_INVALID, "handle %d has no resident launch", i);
     for (int i = 0; i < n; ++i) hs[i]->req_steps += nsteps * std::max(hs[i]->o.samples_per_step, 1);
     int rc = emu_run_group(hs, n, nsteps);
     if (!rc) rc = theta_sync_local(hs, n);          // (genotype model: theta_g back from its owner, as bb_run does through RCCL)
@@ -1045,11 +1089,11 @@ extern "C" int bb_emu_run_group(bb_handle** hs, int32_t n, int64_t nsteps) {
 }
 #endif
 
-static bool res_ms(const bb_handle* h) { return h->res_P > 0 && (h->o.samples_per_step != 1 || h->o.elbo_every != 0); }
 static int launch_persistent(bb_handle* h, long long nsteps) {
-    RunArgs A = make_args(h, h->step, 0, h->res_P ? h->o.samples_per_step : 1, true, false);
+    const LaunchPlan& p = h->plan;
+    RunArgs A = resident_args(h);
     int rc = 0;
-    h->req_steps += nsteps * (h->res_P ? std::max(h->o.samples_per_step, 1) : 1);      // (exchanges asked: the rows' epochs count them)
+    h->req_steps += nsteps * std::max(h->o.samples_per_step, 1);      // (exchanges asked: the rows' epochs count them)
 #ifdef BB_EMU
     (void)A;
     if (h->p2p_on) return bb_fail(BB_ERR_UNSUPPORTED, "emulation: step the ranks of a sharded resident run with bb_emu_run_group");
@@ -1058,18 +1102,15 @@ static int launch_persistent(bb_handle* h, long long nsteps) {
     // No per-launch memsets: ready words carry base + step + 1 and only grow; the timeout word is sticky (a launch that finds it
     // set leaves at once, so a queue of launches behind a timed-out one neither runs nor skips steps); every launch takes its
     // first step from the device counter.
-    bb_persist_kernel k = h->res_P ? nullptr : persist_kernel(h->M.kind, h->persist_P, h->nthr, h->p2p_on);
-    bb_res_kernel kr = (h->res_P && !h->res_stream) ? res_kernel(h->M.kind, h->res_P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), res_ms(h)) : nullptr;
-    if (h->res_P) { A.nblk = h->res_nblk; A.nbl = h->res_NBL; A.ng = h->res_ng; A.pf = h->res_pf; }
     if (h->p2p_first && nsteps > 0) { A.spin_limit = 1u << 25; h->p2p_first = false; }   // launch skew between the ranks' processes
     do {                                                  // (nsteps == 0: one launch that only loads and stores the state)
         const int n = (int)std::min<long long>(nsteps, 4096);
         if (++h->launch_seq == 0u) h->launch_seq = 1u;
         A.launch_tag = h->launch_seq;
-        if (h->res_stream) hipLaunchKernelGGL(stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), nullptr, res_ms(h)), dim3(h->res_nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream,
-                                              (const DevModel*)h->dM, (const DevState*)h->dS, (const BRLay*)h->dY, A, h->res_NB, n, h->res_P);
-        else if (kr) hipLaunchKernelGGL(kr, dim3(h->res_nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, (const BRLay*)h->dY, A, h->res_NB, n);
-        else hipLaunchKernelGGL(k, dim3(h->nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, (const BBLds*)h->dL, A, h->NB, n);
+        if (p.impl == IMPL_STREAM) hipLaunchKernelGGL((bb_stream_kernel)p.fn, dim3(p.nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream,
+                                                      (const DevModel*)h->dM, (const DevState*)h->dS, (const BRLay*)h->dY, A, p.NB, n, p.P);
+        else if (p.impl == IMPL_RES) hipLaunchKernelGGL((bb_res_kernel)p.fn, dim3(p.nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, (const BRLay*)h->dY, A, p.NB, n);
+        else hipLaunchKernelGGL((bb_persist_kernel)p.fn, dim3(p.nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, (const BBLds*)h->dL, A, p.NB, n);
         rc = launch_check();
         h->step += n;
         nsteps -= n;
@@ -1103,7 +1144,7 @@ static int check_persistent(bb_handle* h) {
     return 0;
 }
 
-static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_handle** out) {
+static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out) {
     if (!md || !opts || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     *out = nullptr;
     if (md->kind < 0 || md->kind > 4) return bb_fail(BB_ERR_INVALID, "unknown model kind %d", md->kind);
@@ -1118,11 +1159,11 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
     if (opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD && opts->window < 1) return bb_fail(BB_ERR_INVALID, "window must be >= 1");
     if (opts->world_size < 1 || opts->rank < 0 || opts->rank >= opts->world_size)
         return bb_fail(BB_ERR_INVALID, "bad rank/world_size %d/%d", opts->rank, opts->world_size);
-    if (opts->n_devices > 1) return group_create(md, opts, out);
+    if (opts->n_devices > 1) return group_create(md, opts, cx, out);
 
     bb_handle* h = new bb_handle();
     h->o = *opts;
-    { const char* fr = getenv("BB_FORCE_ALLREDUCE"); h->force_reduce = fr && atoi(fr) > 0; }
+    h->tune = cx.tune;
     if (h->o.resum_every < 0) h->o.resum_every = 0;      // 0 = the default schedule (bb_slot_of)
     DevModel& M = h->M;
     M.kind = md->kind;
@@ -1197,13 +1238,13 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
         add_block(h, "logsigma_bc", BK_LS, M.nb * M.E, &off);
     } else {
         const long long E_ = M.kind == BB_MODEL_MULTIENV_REPLICATE ? M.E : 1;
-        if (g_loglambda_first) add_block(h, "loglambda", BK_L, n_l, &off);          // (internal order only: bb_create)
+        if (cx.loglambda_first) add_block(h, "loglambda", BK_L, n_l, &off);          // (internal order only: bb_create)
         add_block(h, "theta", BK_S, M.kind == BB_MODEL_GENOTYPE ? M.G : M.nb * E_, &off);
         add_block(h, "theta_tilde", BK_TT, M.nb * M.R * E_, &off);
         add_block(h, "logtau", BK_LT, M.nb * M.R * E_, &off);
         add_block(h, "logsigma_bc", BK_LS, M.nb * M.R * E_, &off);
     }
-    if (!(g_loglambda_first && M.kind >= BB_MODEL_GENOTYPE)) add_block(h, "loglambda", BK_L, n_l, &off);
+    if (!(cx.loglambda_first && M.kind >= BB_MODEL_GENOTYPE)) add_block(h, "loglambda", BK_L, n_l, &off);
     M.D = off;
     M.Dp = (off + 7) & ~7ll;
     for (int r = 0, o = 0; r < M.R; ++r) { M.off_l[r] = M.blk_lo[BK_L] + (long long)o * M.B; o += M.T[r]; }
@@ -1312,18 +1353,14 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
         // (16 waves per CU) working a tile's ~NB*(T+2) latents.  BB_TUNE_* env vars override for experiments.
         int maxT = 0;
         for (int r = 0; r < M.R; ++r) maxT = std::max(maxT, M.T[r]);
-        int cus = 256;
 #ifndef BB_EMU
-        { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, opts->device) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
+        { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, opts->device) == hipSuccess && pr.multiProcessorCount > 0) h->cus = pr.multiProcessorCount; }
 #endif
-        h->cus = cus;
-        const char* ev;
-        int bpc = (ev = getenv("BB_TUNE_BLOCKS_PER_CU")) ? atoi(ev) : 1;
-        if (bpc < 1) bpc = 1;
+        const int bpc = h->tune.blocks_per_cu;
         const long long nbar = std::max<long long>(h->b_hi - h->b_lo, 1);
-        long long target = (long long)cus * bpc;
+        long long target = (long long)h->cus * bpc;
         int NB = (int)std::max<long long>((nbar + target - 1) / target, 32);
-        if ((ev = getenv("BB_TUNE_NB")) && atoi(ev) > 0) NB = atoi(ev);
+        if (h->tune.nb > 0) NB = h->tune.nb;
         const size_t lds_cap = (size_t)160 * 1024 / (size_t)bpc;
         int nthr = 0;
         for (;;) {
@@ -1333,7 +1370,7 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
             // > 1 pair per thread: 512 threads (256-VGPR budget, up to 4 pairs) beat 1024 threads with spills (C3: 28.8k vs 18.8k steps/s)
             // (768 threads x 2 pairs was tried for C3: 138 spills at 168 VGPRs, 23.0k vs 28.8k steps/s for 512 x 3)
             nthr = pairs > 2048 ? 1024 : (pairs > 1024 ? 512 : (pairs > 512 ? 1024 : (pairs > 256 ? 512 : 256)));
-            if ((ev = getenv("BB_TUNE_NTHR")) && atoi(ev) >= 64) nthr = atoi(ev) / 64 * 64;
+            if (h->tune.nthr) nthr = h->tune.nthr;
             while (nthr < maxT) nthr <<= 1;
             const size_t need = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr).total * 8;
             if ((need <= lds_cap && (long long)NB * maxT < 65536) || NB <= 8) break;
@@ -1349,6 +1386,7 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
         h->lds_doubles = need / 8;
         h->lds_doubles_p0 = h->lds_doubles_p = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr, 1).total;
         h->nblk = (int)((nbar + NB - 1) / NB);
+        h->tile_cap = h->nblk + 8;
         h->ngeno_blk = M.G > 0 ? (int)std::min<long long>(((M.G + 1) / 2 + 255) / 256, 64) : 0;
 #ifndef BB_EMU
         if (need > 64 * 1024) {
@@ -1399,13 +1437,13 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
         S.hstatus = (unsigned*)dp;
     }
 #endif
-    BB_TRY(dalloc(h, &S.prow, (size_t)(h->nblk + 8) * (M.K + 2 * M.nt1)));      // (+ 8: k_res's own tile map may need a few tiles more)
+    BB_TRY(dalloc(h, &S.prow, (size_t)h->tile_cap * (M.K + 2 * M.nt1)));
     BB_TRY(dalloc(h, &S.xrow, (size_t)2 * BB_NG_MAX * (M.K + 2 * M.nt1)));
-    BB_TRY(dalloc(h, &S.grow, (size_t)(h->nblk + 8 + 16 * BB_NG_MAX) * bb_row_stride(M.K + 2 * M.nt1)));      // (+ 16 groups x 16: a leader's eight loads in flight run past its last member, bb_gran_poll8)
+    BB_TRY(dalloc(h, &S.grow, (size_t)(h->tile_cap + 16 * BB_NG_MAX) * bb_row_stride(M.K + 2 * M.nt1)));      // (+ 16 groups x 16: a leader's eight loads in flight run past its last member, bb_gran_poll8)
     BB_TRY(dalloc(h, &S.gxrow, (size_t)2 * BB_NG_MAX * (M.K + 2 * M.nt1)));
-    BB_TRY(dalloc(h, &S.rdy, (size_t)32 * (h->nblk + 8 + 2 * BB_NG_MAX)));
+    BB_TRY(dalloc(h, &S.rdy, (size_t)32 * (h->tile_cap + 2 * BB_NG_MAX)));
     BB_TRY(dalloc(h, &S.xtab, (size_t)BB_NG_MAX));
-    BB_TRY(dalloc(h, &S.xsel, (size_t)h->nblk + 8));
+    BB_TRY(dalloc(h, &S.xsel, (size_t)h->tile_cap));
     BB_TRY(dalloc(h, &S.ztheta, (size_t)std::max(M.G, 1)));
     BB_TRY(dalloc(h, &S.gsum, (size_t)std::max(M.G, 1)));
     BB_TRY(dalloc(h, &S.ds, (size_t)M.nb));
@@ -1413,7 +1451,7 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
     BB_TRY(dalloc(h, &S.elbo_ring, (size_t)BB_ELBO_RING));
     BB_TRY(dalloc(h, &S.elbo_sample, (size_t)opts->samples_per_step + 64));
     BB_TRY(dalloc(h, &S.ctr, (size_t)2));
-    BB_TRY(dalloc(h, &S.stamps, (size_t)(h->nblk + 8) * (32 + 64)));
+    BB_TRY(dalloc(h, &S.stamps, (size_t)h->tile_cap * (32 + 64)));
     S.eps_in = nullptr;
 
     // algorithmic bytes per step on this shard: theta r+w, optimiser state r+w, counts
@@ -1426,7 +1464,7 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
         const double optb = opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD ? 64.0 : 32.0;
         h->bytes_update = (int64_t)((16.0 + 16.0 + optb) * Dsh + cnts);
     }
-    BB_TRY(setup_persistent(h));
+    BB_TRY(setup_persistent(h, h->o.launch_mode));
     BB_TRY(sync_descriptors(h));
     BB_TRY(bb_init_meanfield(h));
     *out = h;
@@ -1454,7 +1492,8 @@ extern "C" int bb_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_h
     if (!md || !opts || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     const bool geno_ok = md->kind == BB_MODEL_GENOTYPE && md->geno_idx && md->n_bc > 1 && md->n_geno >= 1 && md->n_neutral >= 1 && md->n_time &&
                          md->counts && md->n_rep == 1 && md->n_time[0] >= 2 && md->n_time[0] <= 255;
-    bool regroup = geno_ok && !getenv("BB_NO_REGROUP");
+    CreateCtx cx{read_tuning(), false};
+    bool regroup = geno_ok && !cx.tune.no_regroup;
     if (regroup) {
         bool sorted = true, valid = true;
         for (long long m = 0; m < md->n_bc && valid; ++m) {
@@ -1468,8 +1507,8 @@ extern "C" int bb_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_h
     // the any-parity instances ran (two Philox draws in divergent lanes, 8-byte accesses, 40 spilled registers: C5's rank shape 14.95 against
     // 12.8 us).  The library owns an internal order anyway: it lays loglambda out right behind the two global blocks (offset 2 (T - 1): even
     // for even T) and presents the reference's order at every entry point, as for the regrouped mutants.  BB_NO_REORDER=1: as handed over.
-    const bool lfirst = geno_ok && !(md->n_time[0] & 1) && ((md->n_geno + md->n_bc) & 1) && !getenv("BB_NO_REORDER");
-    if (!regroup && !lfirst) return create_inner(md, opts, out);
+    cx.loglambda_first = geno_ok && !(md->n_time[0] & 1) && ((md->n_geno + md->n_bc) & 1) && !cx.tune.no_reorder;
+    if (!regroup && !cx.loglambda_first) return create_inner(md, opts, cx, out);
     const long long nn = md->n_neutral, nb = md->n_bc, B = nn + nb;
     const int T = md->n_time[0];
     std::vector<int> perm((size_t)nb);
@@ -1500,9 +1539,7 @@ extern "C" int bb_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_h
             md2.loglambda_prior.mean = llm.data(); md2.loglambda_prior.std = lls.data();
         }
     }
-    g_loglambda_first = lfirst;
-    int rc = create_inner(&md2, opts, out);
-    g_loglambda_first = false;
+    int rc = create_inner(&md2, opts, cx, out);
     if (rc) return rc;
     bb_handle* h = *out;
     const DevModel& M = h->M;
@@ -1606,9 +1643,9 @@ static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, 
     A.world = h->o.world_size;
     A.xepoch0 = h->epoch0;
     A.spin_limit = 1u << 23;                  // ~1 us per poll: seconds, not milliseconds
-    { const char* ev = getenv("BB_TUNE_ROW_L2"); A.row_l2 = (ev && atoi(ev) == 0) ? 0 : 1; }
+    A.row_l2 = h->tune.row_l2;
     A.nblk = h->nblk;
-    A.nblk_alloc = h->nblk;
+    A.nblk_alloc = h->tile_cap - 8;            // (the device adds the 8 back: BB_STAMP_WAVE)
     A.ng = 8;
     A.par = (int)(step & 1);
     A.sample = sample;
@@ -1724,7 +1761,7 @@ static int launch_geno_sum(bb_handle* h) {
 }
 
 static int allreduce(bb_handle* h, double* buf, size_t n) {
-    if (h->o.world_size == 1 && !h->force_reduce) return 0;
+    if (h->o.world_size == 1 && !h->tune.force_allreduce) return 0;
 #ifdef BB_EMU
     (void)buf; (void)n;
     return bb_fail(BB_ERR_COMM, "in-library collectives are not available in the emulation build");
@@ -1886,13 +1923,14 @@ static void group_destroy(bb_handle* g) {
     delete g;
 }
 
-static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_handle** out) {
+static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out) {
     const int n = opts->n_devices;
     if (n > BB_MAX_WORLD) return bb_fail(BB_ERR_UNSUPPORTED, "at most %d devices per handle", BB_MAX_WORLD);
     if (opts->world_size != 1 || opts->rank != 0) return bb_fail(BB_ERR_INVALID, "n_devices > 1 needs rank 0 / world_size 1 (the handle shards by itself)");
     bb_handle* g = new bb_handle();
     g->o = *opts;
     g->o.device = opts->device_ids ? opts->device_ids[0] : 0;
+    g->tune = cx.tune;
     int rc = 0;
     for (int i = 0; i < n && !rc; ++i) {
         bb_advi_opts o = *opts;
@@ -1903,8 +1941,10 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
         o.world_size = n;
         o.launch_mode = opts->launch_mode == 1 ? 1 : 0;      // (a shard alone cannot run resident before its inbox is wired: mode 2 is enforced below, on the group)
         bb_handle* sh = nullptr;
-        rc = create_inner(md, &o, &sh);
+        rc = create_inner(md, &o, cx, &sh);
         if (!rc) { sh->in_group = true; g->shards.push_back(sh); }
+        if (!rc && memcmp(sh->M.blk_lo, g->shards[0]->M.blk_lo, sizeof sh->M.blk_lo))
+            rc = bb_fail(BB_ERR_INVALID, "shard %d lays the latents out differently from shard 0", i);
     }
     if (rc) { group_destroy(g); return rc; }
     g->M = g->shards[0]->M;                      // (host-side copies of shapes and block ranges; the device pointers inside are shard 0's)
@@ -1944,7 +1984,7 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_ha
     }
     if (ok) for (int i = 0; i < n && ok; ++i) ok = bb_p2p_enable(g->shards[i], 1) == BB_OK;
     // the two resident kernels speak different inbox protocols (k_res: tagged entries, k_persist: rows + ready words): all shards the same one
-    if (ok) for (int i = 1; i < n && ok; ++i) ok = (g->shards[i]->res_P > 0) == (g->shards[0]->res_P > 0);
+    if (ok) for (int i = 1; i < n && ok; ++i) ok = (g->shards[i]->plan.impl >= IMPL_RES) == (g->shards[0]->plan.impl >= IMPL_RES);
     if (!ok) for (bb_handle* sh : g->shards) if (sh->p2p_ready) (void)bb_p2p_enable(sh, 0);
     g->group_resident = ok;
     if (!ok && opts->launch_mode == 2) {
@@ -1960,9 +2000,7 @@ static int group_run(bb_handle* g, int64_t n_steps) {
     int rc = 0;
     if (g->group_resident) {
 #ifdef BB_EMU
-        for (bb_handle* sh : g->shards) sh->req_steps += n_steps * std::max(sh->o.samples_per_step, 1);
-        rc = emu_run_group(g->shards.data(), (int)g->shards.size(), n_steps);      // the emulation steps the shards in lock step
-        if (!rc) rc = theta_sync_local(g->shards.data(), (int)g->shards.size());
+        rc = bb_emu_run_group(g->shards.data(), (int)g->shards.size(), n_steps);      // the emulation steps the shards in lock step
         g->step = g->shards[0]->step;
         return rc;
 #endif
@@ -2123,13 +2161,13 @@ static int run_enqueue(bb_handle* h, int64_t n_steps) {
     if (h->sample != 0) return bb_fail(BB_ERR_INVALID, "a split-phase step is in flight");
     int rc = 0;
     int64_t done = 0;
-    if (!(h->persist_P > 0) && (rc = ensure_scratch(h))) return rc;
+    if (h->plan.impl == IMPL_TWO_KERNEL && (rc = ensure_scratch(h))) return rc;
     if (h->hstatus) h->hstatus[1] = 0;          // divergence flag of THIS run (nothing of this handle is in flight here)
 #ifndef BB_EMU
     BB_HIP(hipEventRecord(h->ev0, h->stream));
 #endif
     h->launches_last_run = 0;
-    if (h->persist_P > 0 && n_steps > 0) {
+    if (h->plan.impl != IMPL_TWO_KERNEL && n_steps > 0) {
         if ((rc = launch_persistent(h, n_steps))) return rc;
         done = n_steps;
         h->launches_last_run = (int)((n_steps + 4095) / 4096);
@@ -2142,8 +2180,8 @@ static int run_enqueue(bb_handle* h, int64_t n_steps) {
     // A sharded step (with its RCCL all-reduce) can be captured too (BB_GRAPH_COLLECTIVE=1; equal results, no gain
     // measured: the step is GPU-bound), but multi-rank capture could not be exercised on the one-GPU boxes this was
     // developed on, so sharded runs launch eagerly by default.
-    const bool graph_ok = gs > 0 && h->o.elbo_every == 0 && !h->graph_failed && !getenv("BB_NO_GRAPH") &&
-                          ((h->o.world_size == 1 && !h->force_reduce) || getenv("BB_GRAPH_COLLECTIVE"));
+    const bool graph_ok = gs > 0 && h->o.elbo_every == 0 && !h->graph_failed && !h->tune.no_graph &&
+                          ((h->o.world_size == 1 && !h->tune.force_allreduce) || h->tune.graph_collective);
     if (graph_ok) {
         gs &= ~1;
         if (gs < 2) gs = 2;
@@ -2397,9 +2435,9 @@ extern "C" int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int
 extern "C" int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n) {
     if (!h || !out) return bb_fail(BB_ERR_INVALID, "bad argument");
     if (!h->shards.empty()) return bb_debug_stamps(h->shards[0], out, n);
-    if (n < 0) { out[0] = (uint64_t)(h->nblk + 8); return BB_OK; }     // rows of the block-stamp area (the per-wave area follows it)
+    if (n < 0) { out[0] = (uint64_t)h->tile_cap; return BB_OK; }     // rows of the block-stamp area (the per-wave area follows it)
     BB_ENTER(h);
-    const int64_t have = (int64_t)(h->nblk + 8) * (32 + 64);
+    const int64_t have = (int64_t)h->tile_cap * (32 + 64);
     int rc = dsync(h->stream);
     if (rc) return rc;
     return d2h(out, h->S.stamps, (size_t)std::min(n, have) * 8, h->stream);
@@ -2430,7 +2468,7 @@ static void p2p_release(bb_handle* h) {
 // this rank's inbox: fine-grained device memory (remote stores and local polls must meet in memory, not in either side's L2)
 static int p2p_alloc_inbox(bb_handle* h) {
     // (BB_P2P_SELF=1, diagnostics: a whole-problem handle runs the inbox protocol against its own inbox -- tools/xg_self.py)
-    if (h->o.world_size < 2 && !(getenv("BB_P2P_SELF") && atoi(getenv("BB_P2P_SELF")) > 0)) return bb_fail(BB_ERR_INVALID, "the cross-GPU leg needs a sharded handle (world_size > 1)");
+    if (h->o.world_size < 2 && !h->tune.p2p_self) return bb_fail(BB_ERR_INVALID, "the cross-GPU leg needs a sharded handle (world_size > 1)");
     if (h->o.world_size > BB_MAX_WORLD) return bb_fail(BB_ERR_UNSUPPORTED, "at most %d ranks", BB_MAX_WORLD);
     if (h->M.kind == BB_MODEL_GENOTYPE && !h->M.geno_sorted)
         return bb_fail(BB_ERR_UNSUPPORTED, "the genotype model's resident launch needs geno_idx in consecutive runs (shards must own whole genotypes)");
@@ -2573,15 +2611,12 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
     BB_ENTER(h);
     if (on && !h->p2p_ready) return bb_fail(BB_ERR_INVALID, "bb_p2p_import comes first");
     h->p2p_on = on != 0;
-    const int saved_mode = h->o.launch_mode;
-    if (h->p2p_on) h->o.launch_mode = 2;      // ask setup_persistent to say why not
-    int rc = setup_persistent(h);
-    h->o.launch_mode = saved_mode;
-    if (rc || (h->p2p_on && h->persist_P == 0)) {
+    int rc = setup_persistent(h, h->p2p_on ? 2 : h->o.launch_mode);      // (the cross-GPU leg needs a resident launch: an error says why not)
+    if (rc) {
         h->p2p_on = false;
-        (void)setup_persistent(h);
+        (void)setup_persistent(h, h->o.launch_mode);
         (void)sync_descriptors(h);
-        return rc ? rc : bb_fail(BB_ERR_UNSUPPORTED, "resident launch not possible on this shard");
+        return rc;
     }
     if ((rc = sync_descriptors(h))) return rc;
 #ifndef BB_EMU
@@ -2716,14 +2751,14 @@ extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
     s->last_run_ms = h->last_run_ms;
     s->avg_sample_ms = h->avg_sample_ms;
     s->avg_update_ms = h->avg_update_ms;
-    s->n_blocks = h->res_P ? h->res_nblk : h->nblk;
+    s->n_blocks = h->plan.nblk;
     s->block_threads = h->nthr;
-    s->lds_bytes = (int32_t)((h->persist_P > 0 ? h->lds_doubles_p : h->lds_doubles) * 8);
-    s->persistent_pairs = h->persist_P;
+    s->lds_bytes = (int32_t)((h->plan.impl != IMPL_TWO_KERNEL ? h->lds_doubles_p : h->lds_doubles) * 8);
+    s->persistent_pairs = h->plan.P;
     s->launches_last_run = h->launches_last_run;
-    s->resident_kernel = h->res_P > 0 ? (h->res_stream ? 3 : 2) : (h->persist_P > 0 ? 1 : 0);
-    if (h->res_P > 0 && h->res_nblk > 0) {          // (k_res / k_stream: what the tiles of the last launch decided about their row stores)
-        std::vector<int> sel((size_t)h->res_nblk);
+    s->resident_kernel = h->plan.impl;
+    if (h->plan.impl >= IMPL_RES) {          // (k_res / k_stream: what the tiles of the last launch decided about their row stores)
+        std::vector<int> sel((size_t)h->plan.nblk);
         int rc = d2h(sel.data(), h->S.xsel, sel.size() * sizeof(int), h->stream);
         if (rc) return rc;
         for (int v : sel) s->rows_same_xcd += v > 0 ? 1 : 0;
@@ -2737,23 +2772,7 @@ extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
 extern "C" int bb_kernel_name(bb_handle* h, char* buf, int64_t len) {
     if (!h || !buf || len < 2) return bb_fail(BB_ERR_INVALID, "null argument / no room");
     if (!h->shards.empty()) return bb_kernel_name(h->shards[0], buf, len);
-    const char* nm = "";
-    char tmp[96];
-#ifdef BB_EMU
-    // (the emulation runs the block programs as host functions: it names the launch, the compile-time T / AP / MS are the product's)
-    if (h->res_P && h->res_stream) snprintf(tmp, sizeof tmp, "emu:k_stream<%d,%d,%d%s>", h->M.kind, h->nthr, uniform_T(h->M), (h->o.samples_per_step != 1 || h->o.elbo_every != 0) ? ",true" : "");
-    else if (h->res_P) snprintf(tmp, sizeof tmp, "emu:k_res<%d,%d,%d,%s,*,%s,%s>", h->M.kind, h->res_P, h->nthr, h->p2p_on ? "true" : "false",
-                                br_any_parity(h->M) ? "true" : "false", (h->o.samples_per_step != 1 || h->o.elbo_every != 0) ? "true" : "false");
-    else if (h->persist_P) snprintf(tmp, sizeof tmp, "emu:k_persist<%d,%d,%d>", h->M.kind, h->persist_P, h->nthr);
-    else snprintf(tmp, sizeof tmp, "emu:k_sample + k_update");
-    nm = tmp;
-#else
-    if (h->res_P && h->res_stream) (void)stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), &nm, res_ms(h));
-    else if (h->res_P) (void)res_kernel(h->M.kind, h->res_P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), res_ms(h), &nm);
-    else if (h->persist_P) (void)persist_kernel(h->M.kind, h->persist_P, h->nthr, h->p2p_on, &nm);
-    else { snprintf(tmp, sizeof tmp, "k_sample<%d> + k_update<%d>", h->M.kind, h->M.kind); nm = tmp; }
-#endif
-    snprintf(buf, (size_t)len, "%s", nm);
+    snprintf(buf, (size_t)len, "%s", h->plan.name.c_str());
     return BB_OK;
 }
 

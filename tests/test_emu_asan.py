@@ -30,7 +30,9 @@ c.case_persistent_equals_two_kernel(lib, "multienv_replicate_R3", expect_kernel=
 c.case_persistent_equals_two_kernel(lib, "genotype_T8", expect_kernel=2)
 os.environ["BB_TUNE_NB"] = "40"; os.environ["BB_TUNE_NTHR"] = "128"        # two pair slots per thread, tiles ending inside a wave
 c.case_persistent_equals_two_kernel(lib, "fitness_T4", expect_kernel=2)
-del os.environ["BB_TUNE_NB"]; del os.environ["BB_TUNE_NTHR"]
+os.environ["BB_TUNE_NB"] = "16"; os.environ["BB_TUNE_NTHR"] = "512"; os.environ["BB_TUNE_RES_NB"] = "2"
+c.case_persistent_equals_two_kernel(lib, "fitness_T6")                  # 350 resident tiles against 44 + 8 in the exchange buffers: refused
+del os.environ["BB_TUNE_NB"]; del os.environ["BB_TUNE_NTHR"]; del os.environ["BB_TUNE_RES_NB"]
 c.case_hier_fitness(lib, "genotype")
 c.case_synth_grad(lib, "replicate_ragged")                                # the two-kernel block programs
 c.case_trajectory_exact(lib, "genotype", "TruncatedADAGrad", 2)

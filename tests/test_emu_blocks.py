@@ -146,6 +146,29 @@ def test_owner_computes_launch_geometries_hierarchical(emu_lib, monkeypatch, nb,
     c.case_persistent_equals_two_kernel(emu_lib, "multienv_replicate_T6", expect_kernel=2)
 
 
+@pytest.mark.parametrize("nb,nthr,res_nb", [(16, 512, 0), (16, 512, 2)])
+def test_resident_tile_map_fits_the_exchange_buffers(emu_lib, monkeypatch, nb, nthr, res_nb):
+    """The exchange, stamp and xsel buffers hold the two-kernel map's tiles + 8.  BB_TUNE_RES_NB=2 asks for a resident map of 350
+    tiles against 44 + 8: the plan refuses k_res for it, and whatever runs equals the two-kernel step."""
+    import math
+    from conftest import make_engine
+    monkeypatch.setenv("BB_TUNE_NB", str(nb))
+    monkeypatch.setenv("BB_TUNE_NTHR", str(nthr))
+    if res_nb:
+        monkeypatch.setenv("BB_TUNE_RES_NB", str(res_nb))
+    sp = c.synth("fitness_T6", seed=6)
+    outs = []
+    for mode in (1, 2):
+        with make_engine(sp, emu_lib, seed=13, window=6, resum_every=1, launch_mode=mode) as e:
+            st = e.stats()
+            if st["resident_kernel"] >= 2:
+                assert st["n_blocks"] <= math.ceil((sp.n_neutral + sp.n_bc) / nb) + 8, st
+            e.run(7)
+            e.run(10)
+            outs.append(e.get_params())
+    assert np.abs(outs[0][0] - outs[1][0]).max() < 1e-11 and np.abs(outs[0][1] - outs[1][1]).max() < 1e-11
+
+
 @pytest.mark.parametrize("lead", [50, 65, 13])
 def test_owner_computes_launch_smaller_leader_tiles(emu_lib, monkeypatch, lead):
     """k_res's own tile map: the exchange's group leaders (tiles 0 .. 7) hold fewer barcodes (neutral / mutant boundary inside
