@@ -27,6 +27,7 @@ EXPORTS = [
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
+    "bb_ppc_shape", "bb_ppc_bands",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -73,6 +74,13 @@ class bb_stats(C.Structure):
         ("geno_lo", C.c_int32), ("geno_hi", C.c_int32),
         ("device_bytes", C.c_int64), ("window_row", C.c_int64),
         ("rows_same_xcd", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class bb_ppc_opts(C.Structure):
+    _fields_ = [
+        ("n_samples", C.c_int32), ("n_ppc", C.c_int32), ("n_quantiles", C.c_int32), ("reserved0", C.c_int32),
+        ("quantiles", _dp), ("seed", C.c_uint64),
     ]
 
 
@@ -125,6 +133,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.bb_hier_units.argtypes = [vp]
     lib.bb_hier_units.restype = C.c_int64
     lib.bb_hier_fitness.argtypes = [vp, C.c_int32, C.c_uint64, _dp, _dp]
+    if hasattr(lib, "bb_ppc_bands"):            # (A/B builds of older sources, tools/xp.py)
+        lib.bb_ppc_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.bb_ppc_bands.argtypes = [vp, C.POINTER(bb_ppc_opts), _dp, C.POINTER(C.c_int64)]
     return lib
 
 
@@ -369,6 +380,28 @@ class Engine:
         med, sd = np.empty(n), np.empty(n)
         self._check(self._lib.bb_hier_fitness(self._h, n_samples, seed, _ptr(med), _ptr(sd)))
         return med, sd
+
+    def ppc_shape(self) -> Tuple[int, int]:
+        """(n_rows, n_steps) of `ppc_bands`: n_rep population-mean rows, then n_rep * n_bc mutant rows (replicate-major)."""
+        n, t = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.bb_ppc_shape(self._h, C.byref(n), C.byref(t)))
+        return int(n.value), int(t.value)
+
+    def ppc_bands(self, quantiles: Sequence[float], n_samples: int = 1000, n_ppc: int = 10, seed: int = 0,
+                  outside: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """Posterior predictive bands of the log-frequency ratios for every row (`bb_ppc_bands`): bands[n_rows, n_steps, n_q, 2]
+        (lower, upper; NaN past a shorter replicate's last step) and, with `outside`, the per-row count of observed ratios outside
+        the band of the largest q."""
+        q = _f64(np.atleast_1d(quantiles))
+        n_rows, n_steps = self.ppc_shape()
+        o = bb_ppc_opts()
+        o.n_samples, o.n_ppc, o.n_quantiles, o.seed = int(n_samples), int(n_ppc), int(q.shape[0]), int(seed)
+        o.quantiles = _ptr(q)
+        bands = np.empty((n_rows, n_steps, q.shape[0], 2))
+        nout = np.zeros(n_rows, dtype=np.int64) if outside else None
+        self._check(self._lib.bb_ppc_bands(self._h, C.byref(o), _ptr(bands),
+                                           nout.ctypes.data_as(C.POINTER(C.c_int64)) if outside else None))
+        return bands, nout
 
     # ---- cross-GPU leg of the resident launch (include/barbay_hip.h, bb_p2p_*) ----
     def p2p_export(self) -> bytes:

@@ -14,6 +14,7 @@
 #include "bb_stream.h"
 #include "bb_inst.h"
 #include "bb_hier.h"
+#include "bb_ppc.h"
 
 #include <algorithm>
 #include <cmath>
@@ -144,6 +145,14 @@ __global__ void __launch_bounds__(256) k_init(DevModel M, DevState S, unsigned l
 __global__ void __launch_bounds__(1024) k_hier(HierArgs H) {
     BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
     bb_block_hier(cx, H, (int)gridDim.x);
+}
+__global__ void __launch_bounds__(256) k_ppc_pop(PpcArgs P) {
+    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
+    bb_block_ppc_pop(cx, P, (int)gridDim.x);
+}
+__global__ void __launch_bounds__(1024) k_ppc(PpcArgs P) {
+    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
+    bb_block_ppc(cx, P, (int)gridDim.x);
 }
 // transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
 __global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {
@@ -309,6 +318,8 @@ struct bb_handle {
     size_t eps_cap = 0;
     double* dbg_buf = nullptr;
     size_t dbg_cap = 0;
+    double* ppc_buf = nullptr;         // bb_ppc_bands: parameters, tables, scratch and bands of the last call
+    size_t ppc_cap = 0;
     bbStream stream{};
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
     int launches_last_run = 0;
@@ -1616,6 +1627,7 @@ extern "C" void bb_destroy(bb_handle* h) {
     for (void* p : h->owned) dfree(p);
     if (h->eps_buf) dfree(h->eps_buf);
     if (h->dbg_buf) dfree(h->dbg_buf);
+    if (h->ppc_buf) dfree(h->ppc_buf);
 #ifndef BB_EMU
     if (h->stream) (void)hipStreamDestroy(h->stream);
 #endif
@@ -2711,6 +2723,164 @@ static int hier_fitness_raw(bb_handle* h, int32_t n_samples, uint64_t seed, doub
 #endif
     if ((rc = d2h(median, H.median_out, (size_t)n * 8, h->stream))) return rc;
     return d2h(stdv, H.std_out, (size_t)n * 8, h->stream);
+}
+
+// ---- posterior predictive bands (bb_ppc.h) ----------------------------------------------------------------------------------
+static long long ppc_rows(const bb_handle* h) { return (long long)h->M.R * (1 + h->M.nb); }
+static int ppc_steps(const bb_handle* h) {
+    int n = 0;
+    for (int r = 0; r < h->M.R; ++r) n = std::max(n, h->M.T[r] - 1);
+    return n;
+}
+// caller offset of a block of the reference's layout (h->blocks lists the caller's order), -1 if the model has none
+static long long ppc_block(const bb_handle* h, const char* name) {
+    for (const bb_block_range& b : h->blocks) if (!strcmp(b.name, name)) return b.lo;
+    return -1;
+}
+
+extern "C" int bb_ppc_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps) {
+    if (!h || !n_rows || !n_steps) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_rows = ppc_rows(h);
+    *n_steps = ppc_steps(h);
+    return BB_OK;
+}
+
+extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, int64_t* n_outside) {
+    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->n_quantiles < 1 || o->n_quantiles > BB_PPC_MAX_Q) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 1..%d", BB_PPC_MAX_Q);
+    for (int i = 0; i < o->n_quantiles; ++i)
+        if (!(o->quantiles[i] >= 0.0 && o->quantiles[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
+    if (o->n_samples < 1 || o->n_ppc < 1) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples and n_ppc must be >= 1");
+    const long long K = (long long)o->n_samples * o->n_ppc;
+    if (K < 2 || K > BB_PPC_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples * n_ppc = %lld must be in 2..%d", K, BB_PPC_MAX_K);
+    const size_t D = (size_t)h->M.D;
+    // the caller's parameters (a multi-device handle gathers them) -> mean / sigma = softplus(omega) in the caller's layout
+    std::vector<double> prm(2 * D);
+    int rc = bb_get_params(h, prm.data(), prm.data() + D);
+    if (rc) return rc;
+    for (size_t i = D; i < 2 * D; ++i) prm[i] = std::max(prm[i], 0.0) + log1p(exp(-fabs(prm[i])));
+    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // a group samples on shard 0 (as bb_hier_fitness)
+    BB_ENTER(dh);
+    const DevModel& M = dh->M;
+    PpcArgs P;
+    memset(&P, 0, sizeof P);
+    P.kind = M.kind;
+    P.R = M.R;
+    P.E = (M.kind == BB_MODEL_MULTIENV || M.kind == BB_MODEL_MULTIENV_REPLICATE) ? M.E : 1;
+    P.nt1 = M.nt1;
+    P.nb = M.nb;
+    P.n_rows = ppc_rows(h);
+    P.n_steps = ppc_steps(h);
+    P.n_samples = o->n_samples;
+    P.n_ppc = o->n_ppc;
+    P.K = (int)K;
+    P.n_q = o->n_quantiles;
+    P.seed = o->seed;
+    for (int r = 0; r < M.R; ++r) { P.T[r] = M.T[r]; P.off_t[r] = M.off_t[r]; P.tcum[r] = M.tcum[r]; }
+    const bool hier = M.kind >= BB_MODEL_GENOTYPE;
+    P.lo_spop = ppc_block(h, "s_pop");
+    P.lo_lspop = ppc_block(h, "logsigma_pop");
+    P.lo_s = ppc_block(h, hier ? "theta" : "s_bc");
+    P.lo_ls = ppc_block(h, "logsigma_bc");
+    P.lo_tt = hier ? ppc_block(h, "theta_tilde") : 0;
+    P.lo_lt = hier ? ppc_block(h, "logtau") : 0;
+    if (P.lo_spop < 0 || P.lo_lspop < 0 || P.lo_s < 0 || P.lo_ls < 0 || P.lo_tt < 0 || P.lo_lt < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    // order statistics of StatsBase.quantile (Statistics._quantile, alpha = beta = 1): aleph = K p + (1 - p), j = clamp(trunc(aleph), 1, K - 1),
+    // gamma = clamp(aleph - j, 0, 1), a + gamma (b - a) between the (1-based) order statistics j and j + 1
+    std::vector<int> lo(2 * (size_t)P.n_q), ranks;
+    for (int e = 0; e < 2 * P.n_q; ++e) {
+        const double q = o->quantiles[e >> 1];
+        const double p = (e & 1) ? 1.0 - (1.0 - q) / 2.0 : (1.0 - q) / 2.0;
+        const double aleph = (double)K * p + (1.0 - p);
+        const long long j = std::min<long long>(std::max<long long>((long long)aleph, 1), K - 1);
+        P.gam[e] = std::min(std::max(aleph - (double)j, 0.0), 1.0);
+        lo[(size_t)e] = (int)(j - 1);
+        ranks.push_back((int)(j - 1));
+        ranks.push_back((int)j);
+    }
+    std::sort(ranks.begin(), ranks.end());
+    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+    P.n_tgt = (int)ranks.size();
+    for (int x = 0; x < P.n_tgt; ++x) P.tgt[x] = ranks[(size_t)x];
+    for (int e = 0; e < 2 * P.n_q; ++e) P.plo[e] = (int)(std::lower_bound(ranks.begin(), ranks.end(), lo[(size_t)e]) - ranks.begin());
+    // grid: two workgroups per CU at most, the per-block scratch bounded to 256 MiB
+    const size_t ns = (size_t)P.n_samples;
+    long long nblk = std::min<long long>(P.n_rows, 2LL * dh->cus);
+    while (nblk > 1 && (size_t)nblk * P.E * 2 * ns * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    // device buffer: mean | sigma | pop [nt1][2][ns] | par [nblk][E][2][ns] | bands | geno_idx (caller order, ints)
+    const size_t nbands = (size_t)P.n_rows * P.n_steps * P.n_q * 2;
+    const size_t need = 2 * D + (size_t)P.nt1 * 2 * ns + (size_t)nblk * P.E * 2 * ns + nbands + ((size_t)M.nb + 1) / 2 + 8;
+    if (dh->ppc_cap < need) {
+        if (dh->ppc_buf) dfree(dh->ppc_buf);
+        dh->ppc_buf = nullptr;
+        dh->ppc_cap = 0;
+        void* p = nullptr;
+        if ((rc = dmalloc(&p, need * 8))) return rc;
+        dh->ppc_buf = (double*)p;
+        dh->ppc_cap = need;
+    }
+    double* b = dh->ppc_buf;
+    P.mean = b;
+    P.sigma = b + D;
+    P.pop = b + 2 * D;
+    P.par = P.pop + (size_t)P.nt1 * 2 * ns;
+    P.bands = P.par + (size_t)nblk * P.E * 2 * ns;
+    P.env_idx = M.env_idx;
+    if ((rc = h2d(b, prm.data(), 2 * D * 8, dh->stream))) return rc;
+    std::vector<int> geno;
+    if (M.kind == BB_MODEL_GENOTYPE) {
+        // geno_idx in the caller's mutant order (the handle keeps its own, regrouped one)
+        std::vector<int> gi((size_t)M.nb);
+        if ((rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, dh->stream))) return rc;
+        geno = gi;
+        if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
+        int* dg = (int*)(P.bands + nbands);
+        if ((rc = h2d(dg, geno.data(), (size_t)M.nb * 4, dh->stream))) return rc;
+        P.geno_idx = dg;
+    }
+    const int nthr = 1024;
+    const size_t lds = (size_t)bb_ppc_lds_doubles(P.K);
+    const int npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * P.n_samples + 255) / 256, 1024));
+#ifdef BB_EMU
+    emu_launch(npop, 256, 0, [&](BBCtx& cx) { bb_block_ppc_pop(cx, P, npop); });
+    emu_launch((int)nblk, nthr, lds, [&](BBCtx& cx) { bb_block_ppc(cx, P, (int)nblk); });
+#else
+    if (lds * 8 > 64 * 1024 && hipFuncSetAttribute((const void*)k_ppc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds * 8)) != hipSuccess)
+        return bb_fail(BB_ERR_DEVICE, "cannot raise dynamic LDS to %zu bytes", lds * 8);
+    hipLaunchKernelGGL(k_ppc_pop, dim3(npop), dim3(256), 0, dh->stream, P);
+    if ((rc = launch_check())) return rc;
+    hipLaunchKernelGGL(k_ppc, dim3((unsigned)nblk), dim3(nthr), lds * 8, dh->stream, P);
+    if ((rc = launch_check())) return rc;
+#endif
+    if ((rc = d2h(bands, P.bands, nbands * 8, dh->stream))) return rc;
+    if (!n_outside) return BB_OK;
+    // observed log-frequency ratios outside the band of the largest q (finite ratios only: both counts > 0); the handle's counts are in
+    // its own barcode order, the rows in the caller's
+    long long cnt = 0;
+    for (int r = 0; r < M.R; ++r) cnt += (long long)M.T[r] * M.B;
+    std::vector<unsigned> c((size_t)cnt);
+    if ((rc = d2h(c.data(), M.counts, (size_t)cnt * 4, dh->stream))) return rc;
+    int qx = 0;
+    for (int i = 1; i < P.n_q; ++i) if (o->quantiles[i] > o->quantiles[qx]) qx = i;
+    for (long long row = 0; row < P.n_rows; ++row) n_outside[row] = 0;
+    for (int r = 0; r < M.R; ++r) {
+        const int T = M.T[r];
+        const unsigned* cr = c.data() + M.cnt_off[r];
+        std::vector<double> n((size_t)T, 0.0);
+        for (long long bc = 0; bc < M.B; ++bc)
+            for (int t = 0; t < T; ++t) n[(size_t)t] += (double)cr[bc * T + t];
+        for (long long bc = 0; bc < M.B; ++bc) {
+            const long long row = bc < M.nn ? r : P.R + (long long)r * M.nb + (h->perm_m.empty() ? bc - M.nn : (long long)h->perm_m[(size_t)(bc - M.nn)]);
+            for (int t = 0; t + 1 < T; ++t) {
+                const unsigned c0 = cr[bc * T + t], c1 = cr[bc * T + t + 1];
+                if (!c0 || !c1) continue;
+                const double x = log((double)c1 / n[(size_t)t + 1]) - log((double)c0 / n[(size_t)t]);
+                const double* bd = bands + (((size_t)row * P.n_steps + t) * P.n_q + qx) * 2;
+                if (x < bd[0] || x > bd[1]) n_outside[row]++;
+            }
+        }
+    }
+    return BB_OK;
 }
 
 extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {

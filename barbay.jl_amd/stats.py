@@ -5,16 +5,24 @@
 
 Both are one-shot array passes over the tidy frame; their outputs (`s_pop_prior`, `logσ_pop_prior`, `logλ_prior`
 means) are what `docs/src/examples.md:122-140` stacks with a chosen std into the matrix-form priors that
-`bb_model_desc` takes per element.  The posterior-predictive helpers of src/stats.jl are outside SURVEY.md §8.
+`bb_model_desc` takes per element.
+
+The posterior-predictive checks of the reference's guide ("Validating the inference", docs/src/index.md:398-580) come in two forms:
+
+    matrix_quantile_range, freq_bc_ppc, logfreq_ratio_bc_ppc,    host numpy ports of src/stats.jl:55-1000, on a DataFrame of
+    logfreq_ratio_popmean_ppc, logfreq_ratio_multienv_ppc         posterior samples (numpy's Generator: Julia's stream is not matched)
+    logfreq_ratio_ppc_bands                                       the same bands for every barcode and time step in one device call
+                                                                  (`bb_ppc_bands`), from the ADVI frame itself
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import pandas as pd
 
 from . import utils
+from .model import BarBayError
 from .utils import _neutral_mask
 
 
@@ -84,3 +92,188 @@ def naive_prior(data: pd.DataFrame, *, id_col="barcode", time_col="time", count_
             loglam.append(np.log(R.astype(np.float64)).T.reshape(-1))              # column-major `[:]`
     return {"s_pop_prior": np.concatenate(s_pop), "logσ_pop_prior": np.concatenate(ls_pop),
             "logλ_prior": np.concatenate(loglam)}
+
+
+# ---- posterior predictive checks (src/stats.jl:55-1000) ------------------------------------------------------------------------
+def _quantile7(xs: np.ndarray, p: float) -> np.ndarray:
+    """StatsBase.quantile of the sorted last axis (Statistics._quantile, alpha = beta = 1: numpy's method="linear")."""
+    n = xs.shape[-1]
+    if n == 1:
+        return xs[..., 0].copy()
+    aleph = n * p + (1.0 - p)
+    j = min(max(int(aleph), 1), n - 1)
+    g = min(max(aleph - j, 0.0), 1.0)
+    a, b = xs[..., j - 1], xs[..., j]
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(a) & np.isfinite(b), a + g * (b - a), (1.0 - g) * a + g * b)
+
+
+def matrix_quantile_range(quantile: Sequence[float], matrix, *, dims: int = 2) -> np.ndarray:
+    """src/stats.jl:55-92: for every q the (1 - q) / 2 and 1 - (1 - q) / 2 quantiles of each slice along `dims` (2: every column,
+    1: every row), shape [size(matrix, dims), len(quantile), 2]."""
+    q = [float(x) for x in quantile]
+    if any(not (0.0 <= x <= 1) for x in q):
+        raise BarBayError("All quantiles must be between zero and one")
+    if dims not in (1, 2):
+        raise BarBayError("Dimensions should match a Matrix dimensiosn, i.e., 1 or 2")
+    m = np.asarray(matrix, dtype=np.float64)
+    xs = np.sort(m.T if dims == 2 else m, axis=-1)
+    out = np.empty((xs.shape[0], len(q), 2))
+    for i, x in enumerate(q):
+        out[:, i, 0] = _quantile7(xs, (1.0 - x) / 2.0)
+        out[:, i, 1] = _quantile7(xs, 1.0 - (1.0 - x) / 2.0)
+    return out
+
+
+def _sorted_vars(df: pd.DataFrame, pattern: str) -> List[str]:
+    """`sort(names(df)[occursin.(pattern, names(df))])`: substring match, then a LEXICOGRAPHIC sort -- as the reference has it,
+    `s̲ₜ[10]` comes before `s̲ₜ[2]`, so with 10 or more time steps the columns of the result are not in time order."""
+    return sorted(c for c in map(str, df.columns) if pattern in c)
+
+
+def _flat(x: np.ndarray, flatten: bool) -> np.ndarray:
+    """`vcat(eachslice(x, dims=3)...)`: the n_ppc slices stacked row-wise."""
+    return x.transpose(2, 0, 1).reshape(-1, x.shape[1]) if flatten else x
+
+
+def freq_bc_ppc(df: pd.DataFrame, n_ppc: int, *, param: Optional[Dict[str, str]] = None, model: str = "lognormal",
+                flatten: bool = True, rng: Optional[np.random.Generator] = None) -> np.ndarray:
+    """src/stats.jl:152-213: frequency trajectories f_{t+1} = f_t exp(s - sbar_t + noise), [n, n_steps + 1, n_ppc] (flattened:
+    [n_ppc n, n_steps + 1]).  model "lognormal": the std column is sigma; "normal": it is log sigma.  Column order: `_sorted_vars`."""
+    param = param or {"bc_mean_fitness": "s⁽ᵐ⁾", "bc_std_fitness": "σ⁽ᵐ⁾", "bc_freq": "f̲⁽ᵐ⁾[1]", "population_mean_fitness": "s̲ₜ"}
+    rng = rng or np.random.default_rng()
+    mean_vars = _sorted_vars(df, param["population_mean_fitness"])
+    f = np.empty((len(df), len(mean_vars) + 1, n_ppc))
+    f[:, 0, :] = df[param["bc_freq"]].to_numpy(dtype=np.float64)[:, None]
+    s = df[param["bc_mean_fitness"]].to_numpy(dtype=np.float64)
+    sd = df[param["bc_std_fitness"]].to_numpy(dtype=np.float64)
+    for i, var in enumerate(mean_vars):
+        if model == "lognormal":
+            scale = sd
+        elif model == "normal":
+            scale = np.exp(sd)
+        else:
+            raise BarBayError("model must be :normal or :lognormal")
+        mu = s - df[var].to_numpy(dtype=np.float64)
+        f[:, i + 1, :] = f[:, i, :] * np.exp(rng.normal(mu[:, None], scale[:, None], (len(df), n_ppc)))
+    return _flat(f, flatten)
+
+
+def logfreq_ratio_bc_ppc(df: pd.DataFrame, n_ppc: int, *, param: Optional[Dict[str, str]] = None, flatten: bool = True,
+                         rng: Optional[np.random.Generator] = None) -> np.ndarray:
+    """src/stats.jl:377-418: log(f_{t+1} / f_t) ~ N(s - sbar_t, exp(log sigma)) per sample row, [n, n_steps, n_ppc] (flattened:
+    [n_ppc n, n_steps]).  Column order: `_sorted_vars`."""
+    param = param or {"bc_mean_fitness": "s⁽ᵐ⁾", "bc_std_fitness": "σ⁽ᵐ⁾", "population_mean_fitness": "s̲ₜ"}
+    rng = rng or np.random.default_rng()
+    mean_vars = _sorted_vars(df, param["population_mean_fitness"])
+    out = np.empty((len(df), len(mean_vars), n_ppc))
+    s = df[param["bc_mean_fitness"]].to_numpy(dtype=np.float64)
+    sd = np.exp(df[param["bc_std_fitness"]].to_numpy(dtype=np.float64))
+    for i, var in enumerate(mean_vars):
+        mu = s - df[var].to_numpy(dtype=np.float64)
+        out[:, i, :] = rng.normal(mu[:, None], sd[:, None], (len(df), n_ppc))
+    return _flat(out, flatten)
+
+
+def logfreq_ratio_popmean_ppc(df: pd.DataFrame, n_ppc: int, *, param: Optional[Dict[str, str]] = None, flatten: bool = True,
+                              rng: Optional[np.random.Generator] = None) -> np.ndarray:
+    """src/stats.jl:571-621: neutral log(f_{t+1} / f_t) ~ N(-sbar_t, exp(log sigmabar_t)), [n, n_steps, n_ppc] (flattened:
+    [n_ppc n, n_steps]).  The default names are the reference's (`sₜ`, `σₜ`); column order: `_sorted_vars`."""
+    param = param or {"population_mean_fitness": "sₜ", "population_std_fitness": "σₜ"}
+    rng = rng or np.random.default_rng()
+    mean_vars = _sorted_vars(df, param["population_mean_fitness"])
+    std_vars = _sorted_vars(df, param["population_std_fitness"])
+    if len(mean_vars) != len(std_vars):
+        raise BarBayError("The number of mean and standard deviation variables does not match")
+    out = np.empty((len(df), len(mean_vars), n_ppc))
+    for i, var in enumerate(mean_vars):
+        mu = -df[var].to_numpy(dtype=np.float64)
+        sd = np.exp(df[std_vars[i]].to_numpy(dtype=np.float64))
+        out[:, i, :] = rng.normal(mu[:, None], sd[:, None], (len(df), n_ppc))
+    return _flat(out, flatten)
+
+
+def logfreq_ratio_multienv_ppc(df: pd.DataFrame, n_ppc: int, envs: Sequence, *, param: Optional[Dict[str, str]] = None,
+                               flatten: bool = True, rng: Optional[np.random.Generator] = None) -> np.ndarray:
+    """src/stats.jl:789-864: step t uses the fitness of the environment of the LATER time point, envs[t + 1].
+    [n, n_steps, n_ppc] (flattened: [n_ppc n, n_steps]).  Column order: `_sorted_vars`."""
+    param = param or {"bc_mean_fitness": "s̲⁽ᵐ⁾", "bc_std_fitness": "σ̲⁽ᵐ⁾", "population_mean_fitness": "s̲ₜ"}
+    rng = rng or np.random.default_rng()
+    envs = list(envs)
+    env_unique = list(dict.fromkeys(envs))
+    env_idx = [env_unique.index(e) for e in envs]
+    mean_vars = _sorted_vars(df, param["population_mean_fitness"])
+    s_vars = _sorted_vars(df, param["bc_mean_fitness"])
+    sd_vars = _sorted_vars(df, param["bc_std_fitness"])
+    if len(s_vars) != len(env_unique) or len(sd_vars) != len(env_unique):
+        raise BarBayError("# of mutant-related variables does not match # of environments")
+    if len(envs) != len(mean_vars) + 1:
+        raise BarBayError("Number of given environments does not match time points in chain")
+    out = np.empty((len(df), len(mean_vars), n_ppc))
+    for i, var in enumerate(mean_vars):
+        e = env_idx[i + 1]
+        mu = df[s_vars[e]].to_numpy(dtype=np.float64) - df[var].to_numpy(dtype=np.float64)
+        sd = np.exp(df[sd_vars[e]].to_numpy(dtype=np.float64))
+        out[:, i, :] = rng.normal(mu[:, None], sd[:, None], (len(df), n_ppc))
+    return _flat(out, flatten)
+
+
+def logfreq_ratio_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                            quantiles: Sequence[float] = (0.95, 0.675, 0.05), n_samples: int = 1000, n_ppc: int = 10, seed: int = 0,
+                            id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                            rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                            device: int = 0) -> pd.DataFrame:
+    """The guide's validation workflow (docs/src/index.md:398-580) for EVERY barcode and time step in one device call (`bb_ppc_bands`).
+
+    `df_advi` is what `vi.advi` returned for `data` and `model`: its first D rows (the variational parameters, in the model's
+    order) give the posterior N(mean, std).  Each (row, step) gets n_samples posterior draws x n_ppc predictive draws of the
+    log-frequency ratio; the bands are `matrix_quantile_range` of those K = n_samples n_ppc values (K <= 16384).
+
+    Returns a tidy frame, one line per (row, step, quantile): `id` ("neutral" for the population-mean row, else the barcode),
+    `rep` ("R1", ...), `env` (the later time point's environment; None without environments), `time` (the later time point's index,
+    1 .. T_r - 1), `quantile`, `lower`, `upper`, and `n_outside`: the row's finite observed ratios outside its widest band (per row,
+    repeated on its lines) -- sort by it to rank the barcodes the fit does not explain."""
+    from . import vi
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    mname = getattr(model, "__name__", str(model))
+    model_kwargs = dict(model_kwargs or {})
+    arrays = utils.data_to_arrays(data, **cols)
+    if "multienv" in mname:
+        model_kwargs = {"envs": arrays.envs, **model_kwargs}
+    if "genotype" in mname:
+        model_kwargs = {"genotypes": arrays.genotypes, **model_kwargs}
+    bayes_model = model(arrays.bc_count, arrays.bc_total, arrays.n_neutral, arrays.n_bc, **model_kwargs)
+    with vi.make_engine(bayes_model, vi.ADVI(), vi.TruncatedADAGrad(), seed, device) as e:
+        names = []
+        for sym, (_, lo, hi) in zip(bayes_model.var_symbols(), e.layout()):
+            names += [f"{sym}[{x}]" for x in range(1, hi - lo + 1)]
+        D = e.D
+        if len(df_advi) < D or list(df_advi["varname"].iloc[:D]) != names:
+            raise BarBayError("df_advi does not hold this model's variational parameters in its first rows (vi.advi on the same data and model)")
+        mu = df_advi["mean"].to_numpy(dtype=np.float64)[:D]
+        sd = np.maximum(df_advi["std"].to_numpy(dtype=np.float64)[:D], np.finfo(np.float64).tiny)
+        e.set_params(mu, sd + np.log(-np.expm1(-sd)))                   # omega = softplus^-1(std)
+        bands, nout = e.ppc_bands(quantiles, n_samples=n_samples, n_ppc=n_ppc, seed=seed)
+    n_rows, n_steps, n_q, _ = bands.shape
+    R, nb = len(bayes_model.counts), bayes_model.n_bc
+    envs = arrays.envs
+    has_env = "multienv" in mname
+    per_env = (envs if (has_env and isinstance(envs, list) and envs and isinstance(envs[0], (list, tuple))) else [envs] * R)
+    row = np.arange(n_rows)
+    rep = np.where(row < R, row, (row - R) // max(nb, 1))
+    ids = np.asarray(["neutral"] * R + [b for _ in range(R) for b in arrays.bc_ids], dtype=object)
+    rr, tt, qq = np.meshgrid(row, np.arange(n_steps), np.arange(n_q), indexing="ij")
+    keep = ~np.isnan(bands[..., 0])
+    rr, tt, qq = rr[keep], tt[keep], qq[keep]
+    out = pd.DataFrame({
+        "id": ids[rr],
+        "rep": [f"R{r + 1}" for r in rep[rr]],
+        "env": [per_env[r][t + 1] for r, t in zip(rep[rr], tt)] if has_env else None,
+        "time": tt + 1,
+        "quantile": np.asarray(quantiles, dtype=np.float64)[qq],
+        "lower": bands[..., 0][keep],
+        "upper": bands[..., 1][keep],
+        "n_outside": nout[rr],
+    })
+    return out

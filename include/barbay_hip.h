@@ -266,6 +266,48 @@ int bb_get_elbo_trace(bb_handle* h, int64_t first_step, int64_t n, double* out);
 int64_t bb_hier_units(const bb_handle* h);
 int bb_hier_fitness(bb_handle* h, int32_t n_samples, uint64_t seed, double* median, double* std);
 
+/* Posterior predictive bands of the log-frequency ratios ln(f_{t+1}/f_t) -- BarBay.stats.logfreq_ratio_popmean_ppc /
+ * logfreq_ratio_bc_ppc / logfreq_ratio_multienv_ppc followed by matrix_quantile_range (src/stats.jl:55-1000) -- for every row
+ * of the run at once, from the current mean-field posterior N(mu, softplus(omega)).
+ *
+ * Rows, in the caller's order (bb_ppc_shape: n_rows = n_rep (1 + n_bc), n_steps = max_r T_r - 1):
+ *   r < n_rep               population mean of replicate r: N(-sbar_t, exp(logsigmabar_t)) (model_fitness_normal.jl:250-257)
+ *   n_rep + r n_bc + m      mutant m (caller's order) in replicate r: N(s_{m,r,env(t+1)} - sbar_t, exp(logsigma_{m,r,env(t+1)})),
+ *                           s = s_bc (fitness / multienv) or theta + exp(logtau) theta_tilde (hierarchical kinds, the model's
+ *                           own indexing); env(t+1) = env of the later time point (stats.jl:843-852).
+ * sbar_t, logsigmabar_t are replicate r's own (no BB_FLAG_RAGGED_METHOD pairing here); steps t >= T_r - 1 of a shorter
+ * replicate are NaN.
+ *
+ * Draws: sample j < n_samples is one joint draw of the posterior; it gets n_ppc predictive draws per (row, step), so every
+ * (row, step) column holds K = n_samples n_ppc values.  With N(q, c, s) = bb_normal_pair(seed, q, c, s) (Philox4x32-10 counter
+ * (q_lo, q_hi, c, s), Box-Muller; an even index takes the cosine branch, an odd one the sine branch):
+ *   parameter draw j of latent i (the CALLER's flat index):  mu_i + sigma_i N(i, j >> 1, 0xFFFFFFE0)
+ *   predictive draw k' = j n_ppc + k of (row, t):            N(row | t << 32, k' >> 1, 0xFFFFFFE1)
+ * so a parameter draw is shared by every row and step that uses the latent (one row of the reference's sample frame), and
+ * nothing depends on the launch geometry, the handle's internal latent order or its device count.
+ *
+ * Bands: bands[row][t][i][0 / 1] = the (1 - q_i) / 2 and 1 - (1 - q_i) / 2 quantiles of the column, StatsBase.quantile's
+ * definition (type 7: h = (K - 1) p, linear between the order statistics floor(h) and floor(h) + 1), exact order statistics.
+ * n_outside[row] (may be NULL): finite observed ratios ln(R_{t+1,b} / n_{t+1}) - ln(R_{t,b} / n_t) (both counts > 0, n_t the
+ * totals the handle was created with) strictly outside the band of the largest q -- a mutant row counts its barcode's steps,
+ * a population-mean row those of every neutral barcode of its replicate.
+ *
+ * Limits: 1 <= n_quantiles <= 8 and every q in [0, 1], else BB_ERR_INVALID; n_samples, n_ppc >= 1 and 2 <= K <= 16384 (one
+ * column in LDS), else BB_ERR_UNSUPPORTED.  At K = 16384 the Monte-Carlo standard error of a 2.5 % quantile is about 0.02
+ * predictive standard deviations.  A multi-device handle (n_devices > 1) gathers the posterior onto its first device; a shard
+ * of a sharded run (world_size > 1) needs the gathered vector through bb_set_params first, as bb_hier_fitness. */
+typedef struct bb_ppc_opts {
+    int32_t n_samples;        /* posterior samples j                                   */
+    int32_t n_ppc;            /* predictive draws per sample, row and step             */
+    int32_t n_quantiles;      /* 1 .. 8                                                */
+    int32_t reserved0;
+    const double* quantiles;  /* [n_quantiles] band masses q                           */
+    uint64_t seed;            /* Philox key                                            */
+} bb_ppc_opts;
+int bb_ppc_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps);
+int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands /* [n_rows][n_steps][n_quantiles][2] */,
+                 int64_t* n_outside /* [n_rows] or NULL */);
+
 /* The engine's normal stream for (step, stream) over latents [lo, hi), for checks. */
 int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int64_t lo, int64_t hi, double* out);
 

@@ -179,4 +179,38 @@ function vi(model_name::String, R, n_t, n_neutral::Int, n_bc::Int;
     end
 end
 
+# Posterior predictive bands of the log-frequency ratios (bb_ppc_bands, include/barbay_hip.h): the device's
+# logfreq_ratio_popmean_ppc / logfreq_ratio_bc_ppc / logfreq_ratio_multienv_ppc + matrix_quantile_range for every row at once.
+# Field for field the Python binding's `bb_ppc_opts` (barbay.jl_amd/_capi.py).
+struct bb_ppc_opts
+    n_samples::Int32
+    n_ppc::Int32
+    n_quantiles::Int32
+    reserved0::Int32
+    quantiles::Ptr{Float64}
+    seed::UInt64
+end
+
+"""
+    ppc_bands(h, quantiles; n_samples=1000, n_ppc=10, seed=0, outside=true) -> (bands, n_outside)
+
+`h` a live `bb_handle` (e.g. the one `vi` drives, before `bb_destroy`).  `bands[q, side, t, row]` (Julia order of the
+C array [row][t][q][2]; side 1 lower, 2 upper; NaN past a shorter replicate's last step); rows: the n_rep population-mean
+rows, then mutant m of replicate r at n_rep + r n_bc + m (0-based).  `n_outside[row]`: finite observed ratios outside the
+band of the largest q, or `nothing`.
+"""
+function ppc_bands(h::Ptr{Cvoid}, quantiles::Vector{Float64}; n_samples::Int=1000, n_ppc::Int=10, seed::Integer=0,
+                   outside::Bool=true)
+    nr, nt = Ref{Int64}(0), Ref{Int32}(0)
+    check(ccall((:bb_ppc_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}), h, nr, nt))
+    bands = Array{Float64}(undef, 2, length(quantiles), nt[], nr[])
+    nout = outside ? zeros(Int64, nr[]) : nothing
+    GC.@preserve quantiles begin
+        o = bb_ppc_opts(Int32(n_samples), Int32(n_ppc), Int32(length(quantiles)), Int32(0), pointer(quantiles), UInt64(seed))
+        check(ccall((:bb_ppc_bands, LIB), Cint, (Ptr{Cvoid}, Ref{bb_ppc_opts}, Ptr{Float64}, Ptr{Int64}),
+                    h, o, bands, outside ? nout : C_NULL))
+    end
+    return bands, nout
+end
+
 end # module
