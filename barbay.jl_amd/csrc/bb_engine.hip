@@ -228,7 +228,7 @@ struct DevGuard {
 struct BBTuning {
     bool no_hist_pack, no_host_tables, no_res, no_persist, no_stream, force_stream, any_parity, force_allreduce, p2p_self;
     bool no_graph, graph_collective, no_regroup, no_reorder, nb_set, lead_set;
-    int nb, res_nb, ng, lead, pf, blocks_per_cu, nthr, row_l2;
+    int nb, res_nb, ng, lead, nthr, row_l2;
 };
 
 static BBTuning read_tuning() {
@@ -256,9 +256,6 @@ static BBTuning read_tuning() {
     t.lead_set = set("BB_TUNE_LEAD");
     t.lead = num("BB_TUNE_LEAD", 65);
     if (t.lead < 10 || t.lead > 100) t.lead = 100;
-    t.pf = num("BB_TUNE_PF", 1);
-    if (t.pf < 0 || t.pf > 3) t.pf = 0;
-    t.blocks_per_cu = std::max(num("BB_TUNE_BLOCKS_PER_CU", 1), 1);
     t.nthr = num("BB_TUNE_NTHR", 0) >= 64 ? num("BB_TUNE_NTHR", 0) / 64 * 64 : 0;
     t.row_l2 = num("BB_TUNE_ROW_L2", 1) == 0 ? 0 : 1;   // (odd: any value that reads as 0, "off" too, turns it off)
     return t;
@@ -270,7 +267,7 @@ struct LaunchPlan {
     int impl = IMPL_TWO_KERNEL;        // k_sample + k_update / k_persist (bb_persist.h) / k_res (bb_resident.h) / k_stream (bb_stream.h)
     int P = 0;                         // pair slots per thread of the resident launch (0: none)
     int NB = 0, NBL = 0, nblk = 0;     // its tile map: barcodes per tile, per leader tile (0: uniform), tiles (k_persist: the two-kernel map)
-    int ng = 8, pf = 0;                // k_res / k_stream: groups of the exchange's first hop (RunArgs.ng), window slot fetch (RunArgs.pf)
+    int ng = 8, pf = 0;                // k_res / k_stream: groups of the exchange's first hop (RunArgs.ng), window slot fetch (RunArgs.pf: 0 or 1)
     bool ms = false;                   // several samples per step or the ELBO trace (the MS instances)
     const void* fn = nullptr;          // the resident kernel instance (none in the emulation)
     std::string name;                  // ... as bb_kernel_name reports it
@@ -700,13 +697,11 @@ static bool try_resident(bb_handle* h, bool any_parity, LaunchPlan& p) {
     if (h->M.K + 2 * h->M.nt1 > h->nthr) return false;      // (one thread per row entry: bbp_consume_tg / _tgx, the leaders' chunk sums)
     const int KK = h->M.K + 2 * h->M.nt1;
     const bool can16 = !h->p2p_on && nblk0 >= 64 && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128);
-    int ng = (can16 && !(BR_TG && BR_LEAD_PAR && h->nthr >= 4 * ((KK + 63) & ~63))) ? 16 : 8;
+    int ng = (can16 && h->nthr < 4 * ((KK + 63) & ~63)) ? 16 : 8;
     if (tu.ng == 8 || (tu.ng == 16 && !h->p2p_on && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128))) ng = tu.ng;
-#if BR_TG
-    // self-validating rows: a leader takes its members' rows in batches of eight loads per lane -- 32 groups of 8 on a full grid:
-    // one batch, one round trip (the tile's consume then runs on four thread groups)
+    // a leader takes its members' rows in batches of eight loads per lane -- 32 groups of 8 on a full grid: one batch, one round trip
+    // (the tile's consume then runs on four thread groups)
     if (tu.ng == 32 && !h->p2p_on && nblk0 >= 64 && h->nthr >= 4 * ((KK + 63) & ~63)) ng = 32;
-#endif
     const int pct = tu.lead;
     const bool nb_fixed = tu.nb_set || tu.res_nb > 0;
     if (pct < 100 && nblk0 >= 2 * ng && (!nb_fixed || tu.lead_set)) {
@@ -752,11 +747,12 @@ static bool try_resident(bb_handle* h, bool any_parity, LaunchPlan& p) {
     }
     // When the window slot is fetched (RunArgs.pf).  In the exchange's shadow (round 2) its 32 B per latent of HBM reads compete with
     // the exchange's own loads and stores: at the start of the S pass instead, C2 73.1 -> 77.7 k steps/s, C4 87.1 -> 89.1 k
-    // (profiles/r03b_tagged_rows/prefetch_timing_on_lean_kernel.txt) -- where the slot buffer fits beside the moment contributions
-    int pf = h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && !stream ? tu.pf : 0;
-    BRLay Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, pf == 1 || pf == 2, stream);
-    if (pf == 3) Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false);
-    else if (pf != 0 && (size_t)Y.total * 8 > 160 * 1024) { pf = 0; Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false); }      // (no room for a slot buffer of its own: in the exchange's shadow; pf = 3, behind the exchange, measured 6% slower on C3)
+    // (profiles/r03b_tagged_rows/prefetch_timing_on_lean_kernel.txt) -- where the slot buffer fits beside the moment contributions.
+    // (At the end of the previous step's G pass instead: tied with the start of the S pass on C2 and C4, same file.  Behind the exchange,
+    //  where there is no room for a slot buffer of its own: 6 % slower on C3 than in the exchange's shadow.)
+    int pf = h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && !stream ? 1 : 0;
+    BRLay Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, pf == 1, stream);
+    if (pf != 0 && (size_t)Y.total * 8 > 160 * 1024) { pf = 0; Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false); }      // (no room for a slot buffer of its own: in the exchange's shadow)
     if ((size_t)Y.total * 8 > 160 * 1024) return false;
     const char* nm = "";
     const void* k = nullptr;
@@ -948,22 +944,21 @@ static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nste
         if (phase == 0) {
             br_prologue<KIND, PP, AP>(cx, h->M, h->S, A, Y, h->plan.NB, sb);
             br_draw_ahead<KIND, PP, AP>(cx, A, Y, sb, (unsigned long long)h->step);
-            if (A.pf == 2) br_prefetch_slot<PP>(cx, h->M, h->S, A, Y, sb, bb_slot_of(A, (unsigned long long)h->step).slot);
         } else if (phase == 1) {
             if (MSrun) br_sample<KIND, PP, true>(cx, h->M, h->S, A, Y, sb, buf, wslot.slot, last, want_el);
             else br_sample<KIND, PP, false>(cx, h->M, h->S, A, Y, sb, buf, wslot.slot);
             const unsigned epoch = A.xepoch0 + (unsigned)(xc + 1);
-            if (!BR_TG) { if (MSrun) br_moments<KIND, PP, false, true>(cx, h->M, h->S, Y, sb, buf, epoch, want_el); else br_moments<KIND, PP, false, false>(cx, h->M, h->S, Y, sb, buf, epoch); }
-            else { if (MSrun) br_moments<KIND, PP, true, true>(cx, h->M, h->S, Y, sb, buf, epoch, want_el); else br_moments<KIND, PP, true, false>(cx, h->M, h->S, Y, sb, buf, epoch); }
+            if (MSrun) br_moments<KIND, PP, true>(cx, h->M, h->S, Y, sb, buf, epoch, want_el);
+            else br_moments<KIND, PP, false>(cx, h->M, h->S, Y, sb, buf, epoch);
             br_xchg_publish<KIND, PP, AP>(cx, h->M, h->S, A, Y, sb, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
         } else if (phase == 2) {
             if (xg) br_xchg_lead<true>(cx, h->M, h->S, A, Y, xc, &E.ok);
             else br_xchg_lead<false>(cx, h->M, h->S, A, Y, xc, &E.ok);
         } else if (phase == 3) {
-            if (xg && MSrun) br_xchg_consume<KIND, PP, true, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp, last ? wslot.slot : -1);
-            else if (xg) br_xchg_consume<KIND, PP, true, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, false, 0, 0, wslot.slot);
-            else if (MSrun) br_xchg_consume<KIND, PP, false, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp, last ? wslot.slot : -1);
-            else br_xchg_consume<KIND, PP, false, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, false, 0, 0, wslot.slot);
+            if (xg && MSrun) br_xchg_consume<KIND, PP, true, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp);
+            else if (xg) br_xchg_consume<KIND, PP, true, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
+            else if (MSrun) br_xchg_consume<KIND, PP, false, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp);
+            else br_xchg_consume<KIND, PP, false, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
             // (the compile-time-T forms of the G pass where the product has them, so that the emulation covers that code too)
             if (MSrun) br_update<KIND, PP, 0, AP, true>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB, smp, NS);
             else if (!AP && uniform_T(h->M) == 8) br_update<KIND, PP, 8, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
@@ -1003,7 +998,7 @@ static void emu_stream_phase(EmuPersist& E, int phase, long long it, long long n
             bs_sample0<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)h->step, gb, (int)(((unsigned long long)h->step * (unsigned long long)NS) & 1ull), rec((unsigned long long)h->step));
         } else if (phase == 1) {
             bs_moments<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, gb, ms.buf, want_el);
-            br_row_publish<1, true, MS>(cx, h->M, h->S, Y, nost, A.xepoch0 + (unsigned)(xc + 1), want_el);
+            br_row_publish<1, MS>(cx, h->M, h->S, Y, nost, A.xepoch0 + (unsigned)(xc + 1), want_el);
         } else if (phase == 2) {
             br_xchg_lead<false>(cx, h->M, h->S, A, Y, xc, &E.ok);
         } else if (phase == 3) {
@@ -1367,12 +1362,10 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
 #ifndef BB_EMU
         { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, opts->device) == hipSuccess && pr.multiProcessorCount > 0) h->cus = pr.multiProcessorCount; }
 #endif
-        const int bpc = h->tune.blocks_per_cu;
         const long long nbar = std::max<long long>(h->b_hi - h->b_lo, 1);
-        long long target = (long long)h->cus * bpc;
-        int NB = (int)std::max<long long>((nbar + target - 1) / target, 32);
+        int NB = (int)std::max<long long>((nbar + h->cus - 1) / h->cus, 32);
         if (h->tune.nb > 0) NB = h->tune.nb;
-        const size_t lds_cap = (size_t)160 * 1024 / (size_t)bpc;
+        const size_t lds_cap = (size_t)160 * 1024;
         int nthr = 0;
         for (;;) {
             // one pair of latents per thread is the sweet spot; counted with the segments' rounding (tile_pairs_bound), the

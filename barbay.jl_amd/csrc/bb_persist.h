@@ -374,7 +374,7 @@ BB_DEV int br_xcc_id() {
 #endif
 }
 
-// ---- self-validating rows (k_res on one GPU, BR_TG) -------------------------------------------------------------------
+// ---- self-validating rows (k_res, k_stream) ---------------------------------------------------------------------------
 // A row entry travels as ONE 16-byte write-through store {lo32, tag, hi32, tag}: two 8-byte granules that each carry the step's
 // tag (= the ready words' epoch: base + step + 1, only ever growing).  A reader takes a value only when both tags match, so the
 // row needs no ready word: the producer neither drains its stores nor meets at a barrier nor stores a flag, and a reader's poll
@@ -384,9 +384,6 @@ BB_DEV int br_xcc_id() {
 // tag in each.  The loads are inline asm (no builtin gives a 16-byte sc1 load): the compiler does not know they are
 // asynchronous, so the wait behind them takes the destination registers as operands and nothing that reads them can move up.
 struct alignas(16) bb_gran { unsigned lo, t0, hi, t1; };
-#ifndef BR_TG
-#define BR_TG 1
-#endif
 #ifndef BB_EMU
 typedef unsigned bb_v4u __attribute__((ext_vector_type(4)));
 #endif
@@ -481,18 +478,15 @@ BB_DEV long long bbx_slot(const RunArgs& A, int par, int src, int g);
 // leader of group g = tile g: its members' rows (16 at most per batch of two polls), summed in member order, out as the group row.
 // XG: the first hop is the same (the members are this rank's own tiles); the group row then goes into EVERY rank's inbox as
 // tagged entries written with system-scope stores (bb_gran_st<true>): no drain, no meet, no ready words on the cross-GPU hop either.
-// PAR (the sharded instances: 8 groups, up to 33 members): the members go in chunks of eight to as many thread groups as the tile
-// has, all polling at once; the chunk sums cross through LDS and are added in chunk order -- one round of polls instead of four.
-#ifndef BR_LEAD_PAR
-#define BR_LEAD_PAR 1          /* 1: the one-GPU instances too (measured: C2 80.8 -> 82.6 k steps/s, C4 90.7 -> 93.9 k at 16 groups; 0 = round-3 form before) */
-#endif
+// Where the leader has several chunks of eight members and two thread groups or more, the chunks go to as many thread groups as
+// the tile has, all polling at once; the chunk sums cross through LDS and are added in chunk order -- one round of polls instead of
+// four for the sharded instances' 33 members (measured on one GPU as well: C2 80.8 -> 82.6 k steps/s, C4 90.7 -> 93.9 k at 16 groups).
 template <bool XG = false>
 BB_DEV void bbp_leader_reduce_tg(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BBLds& L, int par, unsigned epoch, int* ok) {
     const int KK = M.K + 2 * M.nt1, KS = bb_row_stride(KK), NG = bbp_groups(A), g = cx.block;
     const int members = (A.nblk - g + NG - 1) / NG;
-    constexpr bool PAR = XG || BR_LEAD_PAR;
     const int KKP = (KK + 63) & ~63, chunks = (members + 7) >> 3;
-    if (PAR && chunks > 1 && cx.nthr >= 2 * KKP) {
+    if (chunks > 1 && cx.nthr >= 2 * KKP) {
         double* lds = cx.lds;
         int NQ = cx.nthr / KKP;
         if (NQ > chunks) NQ = chunks;
@@ -739,75 +733,11 @@ BB_DEV void bbp_leader_reduce(BBCtx& cx, const DevModel& M, const DevState& S, c
 }
 
 // every tile: wait for the NG group rows, add them in group order -> totals in lds[L.wk], global samples in lds[L.zgl]
-// WIDE (k_res on one GPU): up to 16 groups, read by two thread groups of KKP = 64 or 128 lanes -- half h polls and reads groups
-// [8 h, 8 h + 8), eight loads in flight per lane as in the narrow form (sixteen would raise the kernel's register peak: measured,
-// the G pass doubled); half 1's partial sums cross through LDS and one workgroup barrier, half 0 adds them: (g0 + .. + g7) +
-// (g8 + .. + g15).  A leader then has 16 members: one round of loads instead of two.
-template <bool XG = false, bool WIDE = false>
+template <bool XG = false>
 BB_DEV void bbp_consume(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BBLds& L, int par,
                         unsigned epoch, int* ok, unsigned abs_epoch = 0u) {
     double* lds = cx.lds;
     const int KK = M.K + 2 * M.nt1, NG = bbp_groups(A);
-    if (WIDE && !XG) {
-        // (the host runs this form only where the tile has a thread per row entry, KK <= nthr, and asks for 16 groups only where
-        //  KK <= 128 and the tile has 2 KKP threads: try_resident.  A strided general form beside or instead of it costs the
-        //  C2 instance 3 %: the step loop is short of scalar registers as it is.)
-        const int KKP = KK <= 64 ? 64 : 128;
-        BB_PASS(cx, tid) {
-            const int half = tid / KKP, k = tid - half * KKP, g0 = 8 * half;
-            if (half < 2 && k < 8 && g0 + k < NG && !bb_wait_word(S.rdy + 32 * (A.nblk + par * NG + g0 + k), epoch, S.gbar + 1, A.spin_limit)) *ok = 0;
-        }
-        if (KK <= 64) {
-            // each half is one wave: it has left its poll loop before it loads (the wait also keeps the compiler from hoisting the loads)
-#ifndef BB_EMU
-            if (threadIdx.x < 128) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        } else {
-            BB_SYNC(cx);
-        }
-        BB_STAMP(cx, S, 1);
-        BB_PASS(cx, tid) {
-            const int half = tid / KKP, k = tid - half * KKP, g0 = 8 * half;
-            if (half == 1 && k < KK) {
-                double v[8];
-#pragma unroll
-                for (int g = 0; g < 8; ++g) v[g] = g0 + g < NG ? bb_ld<true>(S.xrow + ((long long)par * NG + g0 + g) * KK + k) : 0.0;
-                double s = 0.0;
-#pragma unroll
-                for (int g = 0; g < 8; ++g) s += v[g];
-                lds[L.red + k] = s;
-            }
-        }
-        double s0 = 0.0;
-        BB_PASS(cx, tid) {
-            if (tid < KK) {
-                double v[8];
-#pragma unroll
-                for (int g = 0; g < 8; ++g) v[g] = g < NG ? bb_ld<true>(S.xrow + ((long long)par * NG + g) * KK + tid) : 0.0;
-                double s = 0.0;
-#pragma unroll
-                for (int g = 0; g < 8; ++g) s += v[g];
-#ifdef BB_EMU
-                lds[L.red + KKP + tid] = s;
-#else
-                s0 = s;
-#endif
-            }
-        }
-        BB_SYNC(cx);
-        BB_PASS(cx, tid) {
-            if (tid < KK) {
-#ifdef BB_EMU
-                s0 = lds[L.red + KKP + tid];
-#endif
-                const double s = s0 + (NG > 8 ? lds[L.red + tid] : 0.0);
-                if (tid < M.K) bb_put_total(M, L, lds, tid, s);
-                else lds[L.zgl + (tid - M.K)] = s;
-            }
-        }
-        if (!(KK <= 64 && M.Ttot <= 64)) BB_SYNC(cx);
-        return;
-    }
     if (XG) {
         // the 8 x world rows of this rank's own inbox (slot order = (source rank, group) = summation order)
         const int rows = 8 * A.world;

@@ -45,20 +45,6 @@
 #define BR_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #endif
 #define BR_MAXT 16
-// BR_UNIT_PRIO: waves that hold unit pairs (s_bc, logsigma_bc, theta ...) raise their issue priority for the G pass (1) or for the G and the
-// following S pass (2).  Their G work is a chain of LDS round trips (a barcode's row per latent) that the SIMD's arbiter -- oldest wave first,
-// and they are the tile's youngest -- lets run only after the loglambda waves are done: they leave G last by far (per_wave_stamps.txt:
-// 8.3 k cycles against 3.4 - 5.5 k) and everybody waits for them at barrier 1.
-#ifndef BR_UNIT_PRIO
-#define BR_UNIT_PRIO 1
-#endif
-// BR_ROW_L2: a tile on its group leader's XCD stores its row with plain stores (br_row_publish); 0 = always write-through
-#ifndef BR_ROW_L2
-#define BR_ROW_L2 1
-#endif
-#ifndef BR_UNIT_PRIO_LEVEL
-#define BR_UNIT_PRIO_LEVEL 3
-#endif
 
 // (the prior of the segment's block travels with it: read per latent in the G pass, it must come from LDS -- fetched through the
 // model descriptor with a per-lane block index it was a chain of five dependent global loads per pair and step)
@@ -75,9 +61,8 @@ struct BRLay {
     int st[6], SU, nst;  // nst unit stage tables, each [2][SU]: fitness / multienv  0 = s, 1 = w = e^{-2 logsigma}, 2 = logsigma
                          //   hierarchical  0 = theta_tilde, 1 = e^logtau, 2 = w, 3 = theta, 4 = logtau, 5 = logsigma
     int eps;             // [P * NT] bb_d2: the next step's normals
-    int hbuf;            // [P][2][NT] bb_d2: this step's TruncatedADAGrad window slot, fetched by LDS-DMA while the exchange is in flight
-                         // (no registers held across the exchange); shares the moment contributions' region (dead by then) unless the
-                         // cross-GPU inbox staging needs it at the same time
+    int hbuf;            // [P][2][NT] bb_d2: this step's TruncatedADAGrad window slot, fetched by LDS-DMA (no registers held across the
+                         // exchange); shares the moment contributions' region (dead by then) where it is fetched in the exchange's shadow
     int racc;            // the moment contributions, transposed: per replicate r [12][rw[r] + 4] at racc_r[r], one column entry per lane
     int racc_r[BB_MAX_REP], rw[BB_MAX_REP];   // of the replicate's loglambda segment (rw = its lanes, whole waves; + 4: the 12 columns start in different banks)
     int rowmap;          // [K] int pairs: {lanes per barcode | used << 24, LDS offset of the entry's column (value v of time-pair class k of replicate r)}
@@ -219,12 +204,7 @@ BRLay br_layout(const DevModel& M, int NB, int NT, int P, int xg_rows, bool own_
         Y.rw[r] = r < M.R ? (stream ? (NT / (M.R == 1 ? 16 : 64)) * Y.lpb[r] : (int)(((long long)NB * Y.lpb[r] + 63) & ~63ll)) : 0;
         if (r < M.R) racc_total += BR_NCV * (Y.rw[r] + 4);
     }
-    // Staging of the cross-GPU inbox rows (bbp_consume<true>; xg_rows = 8 x world rows of KK entries, summed in chunks of whole rows):
-    // in use between the publish and the F pass, while the drawn-ahead normals (and, pf = 0, the window slot) wait in the transient
-    // region -- whatever that region has to spare behind them is the staging; only the missing part is added.
-    // (Only the ready-word form of the cross-GPU consume stages rows, bbp_consume<true>: builds with BR_TG = 0.  The tagged form polls
-    //  the inbox straight into registers, bbp_consume_tgx.)
-    const int xg_want = (!BR_TG && xg_rows > 0) ? (xg_rows * KK < (BB_NQ + 1) * NT ? xg_rows * KK : (BB_NQ + 1) * NT) : 0;
+    // (the cross-GPU inbox needs no staging here: bbp_consume_tgx polls its rows straight into registers)
     int busy;           // doubles of the transient region alive during the exchange
     if (stream) {
         // (no normals, no window slot in LDS: they go through registers.  hbuf = the units' sums (As, Qs) [SU] pairs, written by the loglambda
@@ -232,23 +212,21 @@ BRLay br_layout(const DevModel& M, int NB, int NT, int P, int xg_rows, bool own_
         Y.hbuf = Y.racc;
         busy = racc_total > 2 * Y.SU ? racc_total : 2 * Y.SU;
         o += busy;
-        Y.eps = o;     o += NT / 2;          // (4 bytes per thread: where the LDS-DMA touches of the first slot's lines land, bs_touch0)
+        Y.eps = o;     o += NT / 2;          // (4 bytes per thread, unused: kept while removing it would change which shapes fit LDS)
     } else if (own_hbuf) {
-        // the window slot is fetched while the moment contributions are alive (RunArgs.pf = 1, 2): a region of its own
+        // the window slot is fetched while the moment contributions are alive (RunArgs.pf = 1): a region of its own
         Y.eps = Y.racc;
         busy = 2 * P * NT;
-        { int need = racc_total > busy ? racc_total : busy; if (need < busy + xg_want) need = busy + xg_want; o += need; }
+        o += racc_total > busy ? racc_total : busy;
         o = (o + 1) & ~1;
         Y.hbuf = o;    o += 4 * P * NT;
     } else {
         Y.hbuf = Y.racc;
         Y.eps = Y.hbuf + 4 * P * NT;
         busy = 6 * P * NT;
-        { int need = racc_total > busy ? racc_total : busy; if (need < busy + xg_want) need = busy + xg_want; o += need; }
+        o += racc_total > busy ? racc_total : busy;
     }
-    L.acc = Y.racc + busy;
-    L.acc_cap = xg_want;
-    { const int nch = xg_rows / 8 > 5 ? xg_rows / 8 : 5;               // (bbp_consume<.., WIDE> / bbp_consume_tg: the other thread groups' partial sums; bbp_consume_tgx: one chunk sum per source rank)
+    { const int nch = xg_rows / 8 > 5 ? xg_rows / 8 : 5;               // (bbp_leader_reduce_tg / bbp_consume_tg: the other thread groups' partial sums; bbp_consume_tgx: one chunk sum per source rank)
       L.red = o;     o += 2 * 128 + nch * ((KK + 63) & ~63) + 16; }
     (void)lmax;
     L.total = Y.total = (o + 1) & ~1;
@@ -289,22 +267,9 @@ template <bool AP> BB_DEV bb_d2 br_load_pair(const double* base, long long i0, b
     if (a0 && a1 && br_pair_aligned<AP>(i0)) return *(const bb_d2*)(base + i0);
     return bb_d2{a0 ? base[i0] : 0.0, a1 ? base[i0 + 1] : 0.0};
 }
-// window slots are written once and read again a whole window (100 steps) later: BR_NT_STORE = 1 stores them non-temporally,
-// BR_NT_LOAD = 2 fetches them with the nt policy (experiment switches; defaults below)
-#ifndef BR_NT_LOAD
-#define BR_NT_LOAD 0
-#endif
-#ifndef BR_PUB_COALESCED
-#define BR_PUB_COALESCED 1
-#endif
-#ifndef BR_SKIP_EXP
-#define BR_SKIP_EXP 1
-#endif
-#ifndef BR_NT_STORE
-#define BR_NT_STORE 1
-#endif
+// window slots are written once and read again a whole window (100 steps) later: they are stored non-temporally
 template <bool AP> BB_DEV void br_store_pair_stream(double* base, long long i0, bool a0, bool a1, bb_d2 v) {
-#if !defined(BB_EMU) && BR_NT_STORE
+#ifndef BB_EMU
     if (a0 && a1 && br_pair_aligned<AP>(i0)) {
         typedef double bb_v2d __attribute__((ext_vector_type(2)));
         bb_v2d w = {v.x, v.y};
@@ -564,12 +529,12 @@ BB_DEV void br_tile_setup(BBCtx& cx, const DevModel& M, const DevState& S, const
         } else if (tid == 0) li[0] = br_build_segs<KIND>(sg, M, Y, t, cx.block == 0, g0, g1);
         if (tid == 0) { li[1] = bb_get_word(S.gbar + 1) == 0u ? 1 : 0; li[2] = ncol_or_neg < 0 ? t.nbt : ncol_or_neg; }
         if (tid == 0) {
-            // Same-XCD first hop (BR_ROW_L2): li[4] = 0 not known yet / 1 this tile runs on its group leader's XCD / -1 it does not;
-            // li[5] = own XCC id, li[6] = this launch's tag, li[7] = groups.  The leaders say where they run.
+            // Same-XCD first hop (br_row_publish): li[4] = 0 not known yet / 1 this tile runs on its group leader's XCD / -1 it does not
+            // (or RunArgs.row_l2 is off); li[5] = own XCC id, li[6] = this launch's tag, li[7] = groups.  The leaders say where they run.
             const int xcc = br_xcc_id(), NG = bbp_groups(A);
-            li[4] = (BR_ROW_L2 && A.row_l2) ? 0 : -1; li[5] = xcc; li[6] = (int)A.launch_tag; li[7] = NG;
+            li[4] = A.row_l2 ? 0 : -1; li[5] = xcc; li[6] = (int)A.launch_tag; li[7] = NG;
             S.xsel[cx.block] = li[4];
-            if (BR_ROW_L2 && cx.block < NG) bb_set_word64(S.xtab + cx.block, ((unsigned long long)A.launch_tag << 32) | (unsigned)xcc);
+            if (cx.block < NG) bb_set_word64(S.xtab + cx.block, ((unsigned long long)A.launch_tag << 32) | (unsigned)xcc);
         }
         for (int k = tid; k < KK; k += cx.nthr) lds[L.wk + k] = 0.0;
         for (int i = tid; i < Y.zlw * Y.NBT; i += cx.nthr) lds[Y.zl + i] = 0.0;
@@ -763,7 +728,7 @@ BB_DEV void br_sample(BBCtx& cx, const DevModel& M, const DevState& S, const Run
             // loglambda: lambda = e^z; logsigma_bc: precision w = e^{-2 z}; (others: unused)
             const int kd = st.meta[k] & 15;
             const double f = (kd == SK_LS_E || (KIND >= 2 && kd == SK_LS_R)) ? -2.0 : 1.0;      // logtau: e^{logtau}
-#if BR_SKIP_EXP && !defined(BB_EMU)
+#ifndef BB_EMU
             // a wave whose pairs are all s_bc / theta / theta_tilde -- nobody reads their e^z -- skips the chain (C2
             // 83.9 -> 84.7 k steps/s, C4 and C3 unchanged: profiles/r03g_parallel_leaders/skip_unused_exp.txt)
             if (__builtin_amdgcn_ballot_w64((st.meta[k] & BRM_VALID) && (kd == SK_L || (kd < SK_GS && br_stage_trn<KIND>(kd) >= 0))) == 0ull) st.lam[k] = bb_d2{0.0, 0.0};
@@ -826,9 +791,6 @@ BB_DEV void br_sample(BBCtx& cx, const DevModel& M, const DevState& S, const Run
         }
     }
     BB_STAMP_WAVE(cx, S, A, 0);
-#ifndef BB_EMU
-    if (BR_UNIT_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-#endif
     BB_SYNC(cx);                     // barrier 1: neighbours' z and the unit stages are visible
     BB_STAMP(cx, S, 21);
 }
@@ -855,8 +817,8 @@ __device__ __forceinline__ double br_row16_sum(double s) {
 // transposed into LDS; after the barrier 16 lanes per row entry walk their column and a DPP row sum finishes the entry, which
 // goes straight to the tile's published row ------------------------------------------------------------------------------------
 // ---- the tile's row from the transposed contributions (after barrier 2): 16 lanes per row entry walk their column, a DPP row sum
-// finishes the entry; the row goes out (self-validating entries: from LDS as whole lines; else sc1 stores + drain + ready word) ----
-template <int P, bool TG = false, bool MS = false>
+// finishes the entry; the row goes out from LDS as self-validating entries ----
+template <int P, bool MS = false>
 BB_DEV void br_row_publish(BBCtx& cx, const DevModel& M, const DevState& S, const BRLay& Y, BRSt<P>* stv, unsigned epoch, bool want_el = false) {
     double* lds = cx.lds;
     BB_STAMP(cx, S, 23);
@@ -875,9 +837,7 @@ BB_DEV void br_row_publish(BBCtx& cx, const DevModel& M, const DevState& S, cons
                 for (int w = 0; w < (cx.nthr >> 6); ++w) e += lds[Y.L.part + w];
 #endif
             }
-            if (TG && BR_PUB_COALESCED) lds[Y.L.wk + M.K - 2] = e;
-            else if (TG) bb_gran_st(S.grow + (long long)cx.block * KS + M.K - 2, e, epoch);
-            else bb_st<true>(S.prow + (long long)cx.block * KK + M.K - 2, e);
+            lds[Y.L.wk + M.K - 2] = e;
         }
         for (int j = tid >> 4; j < M.K; j += cx.nthr >> 4) {
             if (MS && j == M.K - 2) continue;
@@ -893,55 +853,38 @@ BB_DEV void br_row_publish(BBCtx& cx, const DevModel& M, const DevState& S, cons
             if (code >> 24) for (int e = c; e < nbt; e += 16) s += col[e * lpb];
             s = br_row16_sum(s);
 #endif
-            if (c == 0) {
-                if (TG && BR_PUB_COALESCED) lds[Y.L.wk + j] = s;
-                else if (TG) bb_gran_st(S.grow + (long long)cx.block * KS + j, s, epoch);
-                else bb_st<true>(S.prow + (long long)cx.block * KK + j, s);
-            }
-        }
-        if (!(TG && BR_PUB_COALESCED)) for (int j = M.K + tid; j < KK; j += cx.nthr) {
-            if (TG) bb_gran_st(S.grow + (long long)cx.block * KS + j, lds[Y.L.wk + j], epoch);
-            else bb_st<true>(S.prow + (long long)cx.block * KK + j, lds[Y.L.wk + j]);
+            if (c == 0) lds[Y.L.wk + j] = s;
         }
     }
     // (Measured and dropped, round 3, profiles/r03b_tagged_rows: a light "sentinel" first stage of the polls -- one entry per row until it carries the tag, then the sweep:
     //  C2 78.8 -> 75.2 k steps/s, the extra round trip costs more than the lighter polling saves.)
-    if (TG) {
-        // self-validating entries: no drain, no ready word.  The barrier stays for LDS alone: the contributions' region is about
-        // to take the next normals and the window slot
-        BB_SYNC(cx);
-        if (BR_PUB_COALESCED) {
-            // the row leaves as whole lines from the first waves (one store instruction per 64 entries) instead of one 16-byte
-            // partial line write per entry from a dozen waves
-            // Same-XCD first hop: a tile's row is read by ONE tile, its group's leader -- and the dispatcher deals workgroups to the XCDs in
-            // turn, so leader g and its members g + NG j (NG = 8, 16, 32) share an XCD and with it an L2.  A PLAIN store leaves the entry in
-            // that L2, where the leader's sc1 polls find it after an L2 round trip instead of a trip through the fabric: C2 11.35 -> 10.89 us per
-            // step (profiles/r04i_same_xcd_first_hop).  Nothing rests on the dispatch order: a member stores write-through (sc1) until it has
-            // read, from its leader's entry of this launch, that both run on the same XCC, and for good if they do not.
-            int* li = (int*)(lds + Y.L.misc);
-            BB_PASS(cx, tid) {
-                if (BR_ROW_L2 && li[4] > 0) { for (int j = tid; j < KK; j += cx.nthr) bb_gran_st_l2(S.grow + (long long)cx.block * KS + j, lds[Y.L.wk + j], epoch); }
-                else for (int j = tid; j < KK; j += cx.nthr) bb_gran_st(S.grow + (long long)cx.block * KS + j, lds[Y.L.wk + j], epoch);
-                if (BR_ROW_L2 && tid == 0 && li[4] == 0) {
-                    int g = cx.block;
-                    while (g >= li[7]) g -= li[7];          // (at most 31 rounds, the first steps of a launch only)
-                    const unsigned long long v = bb_get_word64(S.xtab + g);
-                    if ((unsigned)(v >> 32) == (unsigned)li[6]) { li[4] = (int)(unsigned)v == li[5] ? 1 : -1; S.xsel[cx.block] = li[4]; }
-                }
-            }
+    // self-validating entries: no drain, no ready word.  The barrier stays for LDS alone: the contributions' region is about
+    // to take the next normals and the window slot
+    BB_SYNC(cx);
+    // the row leaves as whole lines from the first waves (one store instruction per 64 entries) instead of one 16-byte
+    // partial line write per entry from a dozen waves
+    // Same-XCD first hop: a tile's row is read by ONE tile, its group's leader -- and the dispatcher deals workgroups to the XCDs in
+    // turn, so leader g and its members g + NG j (NG = 8, 16, 32) share an XCD and with it an L2.  A PLAIN store leaves the entry in
+    // that L2, where the leader's sc1 polls find it after an L2 round trip instead of a trip through the fabric: C2 11.35 -> 10.89 us per
+    // step (profiles/r04i_same_xcd_first_hop).  Nothing rests on the dispatch order: a member stores write-through (sc1) until it has
+    // read, from its leader's entry of this launch, that both run on the same XCC, and for good if they do not.
+    int* li = (int*)(lds + Y.L.misc);
+    BB_PASS(cx, tid) {
+        if (li[4] > 0) { for (int j = tid; j < KK; j += cx.nthr) bb_gran_st_l2(S.grow + (long long)cx.block * KS + j, lds[Y.L.wk + j], epoch); }
+        else for (int j = tid; j < KK; j += cx.nthr) bb_gran_st(S.grow + (long long)cx.block * KS + j, lds[Y.L.wk + j], epoch);
+        if (tid == 0 && li[4] == 0) {
+            int g = cx.block;
+            while (g >= li[7]) g -= li[7];          // (at most 31 rounds, the first steps of a launch only)
+            const unsigned long long v = bb_get_word64(S.xtab + g);
+            if ((unsigned)(v >> 32) == (unsigned)li[6]) { li[4] = (int)(unsigned)v == li[5] ? 1 : -1; S.xsel[cx.block] = li[4]; }
         }
-        BB_STAMP(cx, S, 24);
-        BB_STAMP_RT(cx, S, 29);
-        return;
     }
-    bb_drain_and_meet(cx);           // every storing wave has drained its write-through stores
     BB_STAMP(cx, S, 24);
     BB_STAMP_RT(cx, S, 29);
-    BB_PASS(cx, tid) { if (tid == 0) bb_set_word(S.rdy + 32 * cx.block, epoch); }
 }
 
 template <int KIND, int P, int TT> BB_DEV void br_theta_pre(BBCtx& cx, const DevModel& M, const BRLay& Y, BRSt<P>* stv, int buf);
-template <int KIND, int P, bool TG = false, bool MS = false>
+template <int KIND, int P, bool MS = false>
 BB_DEV void br_moments(BBCtx& cx, const DevModel& M, const DevState& S, const BRLay& Y, BRSt<P>* stv, int buf, unsigned epoch, bool want_el = false) {
     double* lds = cx.lds;
     // (genotype / replicate model: the units' terms of d/dtheta, by their theta_tilde threads -- idle in this pass -- in front of barrier 2, so
@@ -1003,7 +946,7 @@ BB_DEV void br_moments(BBCtx& cx, const DevModel& M, const DevState& S, const BR
         }
     }
     BB_SYNC(cx);                     // barrier 2: the contributions are in LDS
-    br_row_publish<P, TG, MS>(cx, M, S, Y, stv, epoch, want_el);
+    br_row_publish<P, MS>(cx, M, S, Y, stv, epoch, want_el);
 }
 
 // ---- window-slot prefetch (in the exchange's shadow): LDS-DMA, 16 bytes per lane straight into LDS, no register held across the
@@ -1025,7 +968,7 @@ BB_DEV void br_prefetch_slot(BBCtx& cx, const DevModel& M, const DevState& S, co
                 dst[tid] = bb_d2{src[0], src[1]};
 #else
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(dst + (tid & ~63)), 16, 0, BR_NT_LOAD);
+                                                 (__attribute__((address_space(3))) void*)(dst + (tid & ~63)), 16, 0, 0);
 #endif
             }
         }
@@ -1155,23 +1098,16 @@ BB_DEV void br_grad_pre(BBCtx& cx, const BRLay& Y, BRSt<P>* stv, int buf) {
 }
 // Genotype model, d/dtheta_g = sum over the genotype's mutants m of w_m As_m, As_m = sum_t r_t, r_t = (z_{t+1} - z_t) - s_eff - c_t:
 //   w As = w [(z_{T-1} - z_0) - (T - 1) s_eff]  -  w sum_t c_t
-// and only the c_t need the totals.  BR_TH_PRE = 1: every mutant's two terms w [..], w are formed IN THE EXCHANGE'S SHADOW (z rows and unit
-// forms are in LDS since barrier 1) and left in LDS; at the start of the G pass the theta thread adds its members' up, d/dtheta =
-// SA - SW sum_t c_t, and goes with all other pairs.  0 = round 3: the theta_tilde thread of every mutant leaves w As in LDS, one more
-// barrier, the theta threads add their members up and update in a second pass -- every wave waited for that chain at the next step's
-// barrier 1 (C5's rank shape, 25 000 x 8 / 626 genotypes: S 14.7 k cycles against C2's 10.0 k).
-#ifndef BR_TH_PRE
-#define BR_TH_PRE 1
-#endif
-// (replicate model, BR_TH_PRE3: the same for d/dtheta_m = sum over the replicates of w As of unit (m, r) -- the theta thread no longer walks
-//  R barcode rows, it adds R entries up)
-#ifndef BR_TH_PRE3
-#define BR_TH_PRE3 1
-#endif
-template <int KIND> BB_DEV constexpr bool br_th_pre() { return (KIND == 2 && BR_TH_PRE) || (KIND == 3 && BR_TH_PRE3); }
+// and only the c_t need the totals.  Every mutant's two terms w [..], w are formed IN THE EXCHANGE'S SHADOW (z rows and unit forms are
+// in LDS since barrier 1) and left in LDS; the theta thread adds its members' up (br_theta_sum), d/dtheta = SA - SW sum_t c_t, and goes
+// with all other pairs in the one G pass.  (Round 3 had the theta_tilde threads leave w As in the G pass, one more barrier and a second pass for the
+// theta threads: every wave waited for that chain at the next step's barrier 1 -- C5's rank shape, 25 000 x 8 / 626 genotypes: S 14.7 k
+// cycles against C2's 10.0 k.)
+// (replicate model: the same for d/dtheta_m = sum over the replicates of w As of unit (m, r) -- the theta thread does not walk R barcode
+//  rows, it adds R entries up)
 template <int KIND, int P, int TT>
 BB_DEV void br_theta_pre(BBCtx& cx, const DevModel& M, const BRLay& Y, BRSt<P>* stv, int buf) {
-    if (!br_th_pre<KIND>()) return;
+    if (KIND != 2 && KIND != 3) return;
     double* lds = cx.lds;
     BB_PASS(cx, tid) {
         BRSt<P>& st = BB_PSTATE(stv, tid);
@@ -1179,8 +1115,8 @@ BB_DEV void br_theta_pre(BBCtx& cx, const DevModel& M, const BRLay& Y, BRSt<P>* 
         for (int k = 0; k < P; ++k) {
             const int meta = st.meta[k];
             if ((meta & 15) != SK_TT_R || !(meta & BRM_VALID)) continue;
-            // the theta_tilde thread of a unit (idle here) leaves the unit's two terms; its theta thread adds its members' up at the start
-            // of the G pass (a theta thread walking its ~40 members' rows itself, here, took 12 k cycles and held its tile's exchange up:
+            // the theta_tilde thread of a unit (idle here) leaves the unit's two terms; its theta thread adds its members' up later
+            // (br_theta_sum / the G pass; a theta thread walking its ~40 members' rows itself, here, took 12 k cycles and held its tile's exchange up:
             // profiles/r04c_theta_pre)
             const int* rt = (const int*)(lds + Y.rtab) + 4 * (KIND == 2 ? 0 : st.pt[k]);          // (unit pairs: pt = replicate)
             const int T = TT ? TT : rt[2];
@@ -1199,16 +1135,13 @@ BB_DEV void br_theta_pre(BBCtx& cx, const DevModel& M, const BRLay& Y, BRSt<P>* 
     }
 }
 
-// ... and the theta threads add their members' entries up IN THE EXCHANGE'S SHADOW (BR_TH_SUM_F = 1): the entries are written during the M
+// ... and the genotype model's theta threads add their members' entries up IN THE EXCHANGE'S SHADOW: the entries are written during the M
 // pass (the theta_tilde threads are idle there) and visible since barrier 2; the sums wait in two register pairs (gp, lam: a theta pair
-// uses neither).  0: at the start of the G pass (C5's rank shape: S 13.7 k cycles -- the tile waits for that chain at barrier 1).
-// (Beside the F pass instead -- entries written in the shadow, summed behind the consume's barrier: F 1.5 k -> 3.3 k cycles, 12.77 -> 11.9 us.)
-#ifndef BR_TH_SUM_F
-#define BR_TH_SUM_F 1
-#endif
+// uses neither).  (At the start of the G pass instead, C5's rank shape: S 13.7 k cycles -- the tile waits for that chain at barrier 1.
+// Beside the F pass instead -- entries written in the shadow, summed behind the consume's barrier: F 1.5 k -> 3.3 k cycles, 12.77 -> 11.9 us.)
 template <int KIND, int P>
 BB_DEV void br_theta_sum(BBCtx& cx, const DevModel& M, const BRLay& Y, BRSt<P>* stv) {
-    if (!(KIND == 2 && BR_TH_PRE && BR_TH_SUM_F)) return;
+    if (KIND != 2) return;
     const double* lds = cx.lds;
     BB_PASS(cx, tid) {
         BRSt<P>& st = BB_PSTATE(stv, tid);
@@ -1290,18 +1223,18 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
     //  is bound by the SIMDs' total VALU work, not by the unit waves; C2 15.3 -> 15.5 us per step, C3 unchanged.)
     BB_STAMP_WAVE(cx, S, A, 2);
 #ifndef BB_EMU
-    if (BR_UNIT_PRIO) {
+    {
+        // Waves that hold unit pairs (s_bc, logsigma_bc, theta ...) raise their issue priority for the G pass.  Their G work is a chain of
+        // LDS round trips (a barcode's row per latent) that the SIMD's arbiter -- oldest wave first, and they are the tile's youngest --
+        // lets run only after the loglambda waves are done: they leave G last by far (per_wave_stamps.txt: 8.3 k cycles against
+        // 3.4 - 5.5 k) and everybody waits for them at barrier 1 (profiles/r04f_unit_wave_priority).
         bool u = false;
 #pragma unroll
         for (int k = 0; k < P; ++k) u = u || ((stv->meta[k] & BRM_VALID) && (stv->meta[k] & 15) != SK_L);
-        if (__builtin_amdgcn_ballot_w64(u) != 0ull) __builtin_amdgcn_s_setprio(BR_UNIT_PRIO_LEVEL);
+        if (__builtin_amdgcn_ballot_w64(u) != 0ull) __builtin_amdgcn_s_setprio(3);
     }
 #endif
     const double* zbuf = lds + Y.zl + buf * Y.NBT;
-    // Genotype model: two passes.  Pass 0 updates everything but theta, and the theta_tilde thread of every mutant leaves w As in
-    // LDS; after one more barrier the theta threads add up their genotypes' members (consecutive units of this tile) and update.
-    for (int pass = 0; pass < ((KIND == 2 && !BR_TH_PRE) ? 2 : 1); ++pass) {
-    if (pass) BB_SYNC(cx);
     BB_PASS(cx, tid) {
         BRSt<P>& st = BB_PSTATE(stv, tid);
         double* hs_m = nullptr;
@@ -1315,7 +1248,6 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
             const int meta = st.meta[k];
             if (!(meta & BRM_VALID)) continue;
             const int kind = meta & 15;
-            if (KIND == 2 && !BR_TH_PRE && (kind == SK_TH_R) != (pass == 1)) continue;
             const bool a0 = meta & BRM_A0, a1 = meta & BRM_A1;
             double pm0 = 0.0, pm1 = 0.0, iv0 = 0.0, iv1 = 0.0;       // (loglambda: the prior term is in st.gp already)
             if (kind != SK_L) br_pair_prior<KIND>(lds, Y, st, k, a0, a1, &pm0, &iv0, &pm1, &iv1);
@@ -1323,30 +1255,14 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
             if (kind == SK_L) {
                 br_l_grad<KIND, P, AP>(lds, Y, st, k, buf, &g0, &g1);
             } else if (KIND == 2 && kind == SK_TH_R) {
+                // (the members' sums came from br_theta_sum, in the exchange's shadow)
                 const double* stg = lds + buf * Y.SU;
                 double csum = 0.0;
-                if (BR_TH_PRE) { const int T = TT ? TT : M.T[0]; for (int tt = 0; tt < T - 1; ++tt) csum += lds[L.cc + tt]; }
+                { const int T = TT ? TT : M.T[0]; for (int tt = 0; tt < T - 1; ++tt) csum += lds[L.cc + tt]; }
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
                     if (!(x ? a1 : a0)) continue;
-                    double acc = 0.0;
-                    const int first = st.uo[k][x] & 0xffff, n = st.uo[k][x] >> 16;
-                    if (BR_TH_PRE && BR_TH_SUM_F) acc = (x ? st.gp[k].y : st.gp[k].x) - (x ? st.lam[k].y : st.lam[k].x) * csum;          // (br_theta_sum, beside the F pass)
-                    else if (BR_TH_PRE) {          // (br_theta_pre: the members' terms w [..] and w, left in LDS before the exchange's barriers)
-                        // (four 16-byte entries in flight per round trip: one after the other the ~40 members of a genotype are 40 LDS
-                        //  round trips, 5 k cycles, that the whole tile waits for at the next barrier)
-                        const bb_d2* ge = (const bb_d2*)(lds + Y.gas) + first;
-                        double sa = 0.0, sw = 0.0;
-                        int i = 0;
-                        for (; i + 4 <= n; i += 4) {
-                            const bb_d2 e0 = ge[i], e1 = ge[i + 1], e2 = ge[i + 2], e3 = ge[i + 3];
-                            sa += (e0.x + e1.x) + (e2.x + e3.x);
-                            sw += (e0.y + e1.y) + (e2.y + e3.y);
-                        }
-                        for (; i < n; ++i) { sa += ge[i].x; sw += ge[i].y; }
-                        acc = sa - sw * csum;
-                    } else for (int i = 0; i < n; ++i) acc += lds[Y.gas + first + i];
-                    (x ? g1 : g0) = acc;
+                    (x ? g1 : g0) = (x ? st.gp[k].y : st.gp[k].x) - (x ? st.lam[k].y : st.lam[k].x) * csum;
                     (x ? z1 : z0) = stg[BR_ST(Y, 3) + st.zoff[k] + x];
                 }
             } else if (kind < SK_GS) {
@@ -1366,7 +1282,7 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
                     zx[x] = stg[BR_ST(Y, br_stage_raw<KIND>(kind)) + j];
                     // replicates whose rows the latent's gradient sums over: its own; theta: all of them
                     const bool is_th = KIND >= 3 && kind == SK_TH_R;
-                    if (KIND == 3 && BR_TH_PRE3 && is_th) {          // (br_theta_pre: the units' terms w [..], w are in LDS since the exchange's shadow)
+                    if (KIND == 3 && is_th) {          // (br_theta_pre: the units' terms w [..], w are in LDS since the exchange's shadow)
                         double acc = 0.0;
                         for (int r = 0; r < M.R; ++r) {
                             const int* rt = (const int*)(lds + Y.rtab) + 4 * r;
@@ -1417,10 +1333,7 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
                         if (KIND <= 1) acc = kind == SK_S ? wv * As : wv * Qs - (double)nn;
                         else if (is_th) acc += wv * As;
                         else if (kind == SK_LS_R) acc = wv * Qs - (double)nn;
-                        else if (kind == SK_TT_R) {
-                            acc = wv * As * stg[BR_ST(Y, 1) + j];                                                // e^{logtau}
-                            if (KIND == 2 && !BR_TH_PRE) lds[Y.gas + j] = wv * As;                           // d/ds_eff: its genotype's theta sums these
-                        }
+                        else if (kind == SK_TT_R) acc = wv * As * stg[BR_ST(Y, 1) + j];                      // e^{logtau}
                         else acc = wv * As * stg[BR_ST(Y, 1) + j] * stg[BR_ST(Y, 0) + j];                            // logtau: e^{logtau} theta_tilde
                     }
                     gx[x] = acc;
@@ -1469,11 +1382,8 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
             if (hs_m) { br_store_pair_stream<AP>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<AP>(hs_o, ih, a0, a1, nho); }
         }
     }
-    }
-    // (the same thread has just read its entries of the slot buffer: its LDS-DMA of the next step's slot may overwrite them)
-    if (A.pf == 2) br_prefetch_slot<P, HD>(cx, M, S, A, Y, stv, wslot.slot + 1 == A.W ? 0 : wslot.slot + 1);
 #ifndef BB_EMU
-    if (BR_UNIT_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 #endif
     BB_STAMP_WAVE(cx, S, A, 3);
     BB_STAMP(cx, S, 28);
@@ -1526,21 +1436,14 @@ BB_DEV void br_xchg_lead(BBCtx& cx, const DevModel& M, const DevState& S, const 
     const unsigned epoch = A.xepoch0 + (unsigned)(xc + 1);
     // (fetching the members' rows in one round trip -- two waves, 16 members each, partial sums through LDS -- measured SLOWER,
     //  as round 1 had found for k_persist: 7.6 k cycles against 4.8 k for the leader's read + sum + publish)
-    if (cx.block < bbp_groups(A)) {
-        if (BR_TG) bbp_leader_reduce_tg<XG>(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
-        else bbp_leader_reduce<XG>(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot, epoch);
-    }
+    if (cx.block < bbp_groups(A)) bbp_leader_reduce_tg<XG>(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
 }
 template <int KIND, int P, bool XG, bool MS = false>
 BB_DEV void br_xchg_consume(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv,
-                            unsigned long long xc, int* ok_slot, bool want_el = false, int ring = 0, int smp = 0, int slot = -1) {
+                            unsigned long long xc, int* ok_slot, bool want_el = false, int ring = 0, int smp = 0) {
     const unsigned epoch = A.xepoch0 + (unsigned)(xc + 1);
-    if (XG && BR_TG) bbp_consume_tgx(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
-    else if (BR_TG) bbp_consume_tg(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
-    else bbp_consume<XG, !XG>(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot, epoch);
-    // pf = 3 (BB_TUNE_PF only): the window slot fetched HERE, behind the exchange and in front of the F pass and the first gradients.
-    // Measured on C3 (no LDS room for pf = 1): 52.7k steps/s against 56.3k with pf = 0 -- the fetch is exposed, not hidden
-    if (A.pf == 3 && slot >= 0) br_prefetch_slot<P, XG>(cx, M, S, A, Y, stv, slot);
+    if (XG) bbp_consume_tgx(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
+    else bbp_consume_tg(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
     br_finish<KIND, MS>(cx, M, S, Y, &A, want_el, ring, smp);
 }
 
@@ -1570,7 +1473,6 @@ __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, con
         br_draw_ahead<KIND, P, AP>(cx, A, Y, &st, step0);
         BB_STAMP_RT(cx, S, 4);
         BBSlotCtr sc = bb_slot_init(A, step0);
-        if (A.pf == 2) br_prefetch_slot<P, XG>(cx, M, S, A, Y, &st, sc.slot);
         const int NS = MS ? A.S : 1;
         // ELBO recording (MS): position inside the recording period and the ring slot, carried like the window slot
         int ec = (MS && A.elbo_every > 0) ? bb_uniform((int)(step0 % (unsigned long long)A.elbo_every)) : 1;
@@ -1594,10 +1496,10 @@ __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, con
                     for (int k = 0; k < P; ++k) asm volatile("" : "+v"(st.meta[k]));
                 }
                 br_sample<KIND, P, MS, XG>(cx, M, S, A, Y, &st, buf, wslot.slot, last, want_el);
-                br_moments<KIND, P, BR_TG != 0, MS>(cx, M, S, Y, &st, buf, A.xepoch0 + (unsigned)(xc + 1), want_el);      // (tagged rows on the first hop of the sharded instances too)
+                br_moments<KIND, P, MS>(cx, M, S, Y, &st, buf, A.xepoch0 + (unsigned)(xc + 1), want_el);      // (tagged rows on the first hop of the sharded instances too)
                 br_xchg_publish<KIND, P, AP, XG>(cx, M, S, A, Y, &st, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
                 br_xchg_lead<XG>(cx, M, S, A, Y, xc, ok_slot);
-                br_xchg_consume<KIND, P, XG, MS>(cx, M, S, A, Y, &st, xc, ok_slot, want_el, ring, smp, last ? wslot.slot : -1);
+                br_xchg_consume<KIND, P, XG, MS>(cx, M, S, A, Y, &st, xc, ok_slot, want_el, ring, smp);
                 if (*ok_slot == 0) { stop = true; break; }                 // uniform: read after barrier 3
                 br_update<KIND, P, TT, AP, MS, XG>(cx, M, S, A, Y, &st, wslot, buf, NB, smp, NS);
             }
@@ -1609,7 +1511,7 @@ __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, con
         }
     }
     BB_STAMP_RT(cx, S, 5);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (pf = 2: the slot fetched for a step this launch does not take has landed)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (every load of the step loop has landed before the state goes back to memory)
     br_epilogue<KIND, P, AP>(cx, S, &st, step0 + (unsigned long long)done, dead || *ok_slot == 0);
     BB_STAMP_RT(cx, S, 6);
 }

@@ -10,19 +10,18 @@
 // sampled, then, after the exchange, a G pass that read everything again: 80.6 us per step on C5, the memory system idle for the
 // 37 % of it that S, M and the exchange took).  A step:
 //
-//   M    the loglambda pairs' moment contributions from what the previous step's G pass left in LDS -- per pair the two forward
-//        differences (dm, dn) of ITS sample (thread-private entries, no barrier needed for them) and the units' staged forms
+//   M    the loglambda pairs' moment contributions from what the previous step's G pass left in LDS -- per pair its sample z (and
+//        the next pair's first one, for the forward difference behind it) and the units' staged forms
 //        (s, w = e^{-2 logsigma}, e^{logtau}, theta) -- summed per thread over its slots (a thread's pairs share their time-pair
 //        class: NT is a multiple of the lanes per barcode), then by class over the 16-lane rows of the wave (DPP), one LDS entry
 //        per (row, class, value)
 //   --   barrier -- row sums, publish, exchange, F pass: k_res's own code (br_row_publish, bbp_*_tg, br_finish)
-//   G-L  every loglambda pair slot, ONE pass over its state: mu, omega, accumulators, window slot in (56 B per latent); the step's
-//        draw AGAIN (Philox is a pure function of (seed, latent, step): nothing of the sample was kept but the differences), z = mu +
-//        sigma eps, the neighbour pairs' z through DPP (the lanes of a barcode are neighbours in a 16-lane row), lambda = e^z,
-//        gradient, optimiser, everything out (56 B per latent).  The lanes of a barcode add their residuals r, r^2 up (DPP) and
+//   G-L  every loglambda pair slot, ONE pass over its state: mu, omega, accumulators, window slot in (56 B per latent); the sample z
+//        kept in LDS and eps recovered from it (no second draw), the neighbour pairs' z through DPP (the lanes of a barcode are
+//        neighbours in a 16-lane row), lambda = e^z, gradient, optimiser, everything out (56 B per latent).  The lanes of a barcode add their residuals r, r^2 up (DPP) and
 //        leave the barcode's unit sums As = sum_t r, Qs = sum_t r^2 in LDS -- the unit threads no longer walk z rows, so no z row
-//        is staged at all.  THEN, in the same slot, the NEXT step's sample of the updated pair: draw, z' = mu' + sigma' eps', the
-//        neighbour's z' by DPP, (dm', dn') to the thread's private LDS entry, lambda' = e^{z'} onto the thread's running sums.
+//        is staged at all.  THEN, in the same slot, the NEXT step's sample of the updated pair: draw, z' = mu' + sigma' eps',
+//        z' to the pair's LDS entry, lambda' = e^{z'} onto the thread's running sums.
 //   --   barrier (As, Qs visible)
 //   G-U  the unit pair slots the same way: state in, the draw again, gradient from (As, Qs) and the staged forms of THIS step
 //        (buffer step & 1), optimiser, out; then the next step's sample, staged into buffer (step + 1) & 1.  Genotype model: theta
@@ -85,19 +84,9 @@ struct BSMs {
     unsigned nstep, nstream;     // step and stream of the next sample's draw
 };
 BB_DEV BSMs bs_ms_plain(unsigned step) { return BSMs{1, 0, (int)(step & 1u), true, false, step + 1u, 0u}; }
-// (inline in the G pass: the pair's state loads stay in flight behind it -- a call drains them first; C5 93.1 -> 91.4 us, round 3)
-#ifndef BS_G_INLINE_DRAW
-#define BS_G_INLINE_DRAW 1
-#endif
-// ... and the NEXT step's draw inside the same slot (the fused S part): 1 = inline, 0 = the out-of-line call
-#ifndef BS_S_INLINE_DRAW
-#define BS_S_INLINE_DRAW 1          /* (C5 63.9 -> 62.6 us) */
-#endif
-// BS_NT_HIST = 1: the window slot is read with the non-temporal policy (it is not touched again for a whole window; the state arrays,
-// re-read every step, keep the Infinity Cache): C5 90.8 -> 83.9 us (round 3)
-#ifndef BS_NT_HIST
-#define BS_NT_HIST 1
-#endif
+// The G passes draw inline (bs_draw_inline), not by the out-of-line bs_draw: the pair's state loads stay in flight behind the draw -- a
+// call drains them first (C5 93.1 -> 91.4 us, round 3); the same for the NEXT step's draw inside the same slot, the fused S part (C5 63.9
+// -> 62.6 us).
 
 // ---- lane exchanges: value of the previous / next lane of the 16-lane row, sum over the LPB lanes of a barcode ------------------------
 #ifndef BB_EMU
@@ -135,16 +124,13 @@ template <int LPB> static inline double bs_emu_tree(const double* v) {          
 #define BS_GROUP_SUM(LPB, gv, tid, F) ([&]() { double v_[8]; for (int i_ = 0; i_ < (LPB); ++i_) v_[i_] = (gv)[((tid) & ~((LPB) - 1)) + i_].F; return bs_emu_tree<LPB>(v_); }())
 #endif
 
-// BS_ZKEEP = 1: a loglambda pair's sample z' stays in its LDS entry from the pass that formed it (the G pass of the step before) -- the M pass
+// A loglambda pair's sample z' stays in its LDS entry from the pass that formed it (the G pass of the step before) -- the M pass
 // takes its differences from there (the next pair's first sample: the neighbour entry, behind the barrier that ends the G passes), and the
 // G pass does NOT draw again: with z, mu and softplus(omega) at hand eps = (z - mu) / softplus(omega), which is what d z / d omega =
 // eps sigmoid(omega) needs.  One Philox4x32-10 + Box-Muller less per pair and step (205 VALU instructions, 20 of them quarter-rate 64-bit
 // multiplies, of ~1 200) in the pass that is bound by instruction issue.  The recovered eps is not the draw bit for bit: its relative
 // error is ulp(z) / |sigma eps| -- 1e-16 at the start of a run, 1e-13 .. 1e-12 for a converged loglambda (mu ~ 10, sigma ~ 1e-3) -- in ONE
-// term of d ELBO / d omega; the sample z, lambda = e^z and everything else are the S pass's own numbers.  0: the draw again, bit for bit.
-#ifndef BS_ZKEEP
-#define BS_ZKEEP 1
-#endif
+// term of d ELBO / d omega; the sample z, lambda = e^z and everything else are the S pass's own numbers.
 
 // lanes per barcode (br_lpb_stream, as a constant)
 template <int TT> BB_DEV constexpr int bs_lpb() { return TT <= 2 ? 1 : (TT <= 4 ? 2 : (TT <= 8 ? 4 : 8)); }
@@ -154,36 +140,6 @@ BB_DEV int bs_lspan(const BRSeg* sg, int nseg) {
     int e = 0;
     for (int i = 0; i < nseg && sg[i].kind == SK_L; ++i) e = sg[i].tbeg + sg[i].span;
     return e;
-}
-
-// BS_PF0: between the M pass and the exchange -- the memory system idle until the G passes start -- the lines of the FIRST loglambda slot's
-// state are pulled towards the CU: 4 bytes per lane by LDS-DMA into a dump area (no register, nothing waits for them).  1 = the window
-// slot's lines (HBM: not touched for a whole window), 2 = all seven arrays.  (The same for the NEXT slot inside the G pass: measured
-// slower, 67.1 -> 68.8 / 72.6 us, profiles/r04b_stream_fused -- the pass is bound by the memory system itself.)
-#ifndef BS_PF0
-#define BS_PF0 0
-#endif
-template <int KIND, int TT>
-BB_DEV void bs_touch0(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, const BBSlot wslot) {
-#ifndef BB_EMU
-    if (!BS_PF0) return;
-    const BRSeg* sg = (const BRSeg*)(cx.lds + Y.seg);
-    const int nseg = ((const int*)(cx.lds + Y.L.misc))[0];
-    const int lspan = bs_lspan(sg, nseg), tid = threadIdx.x;
-    if (tid >= lspan || tid >= sg[0].tbeg + sg[0].span || TT != 2 * bs_lpb<TT>()) return;
-    const long long i0 = sg[0].lo + 2 * (long long)(tid - sg[0].tbeg), ih = i0 - sg[0].pad;
-    auto touch = [&](const void* p) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
-                                         (__attribute__((address_space(3))) void*)((float*)(cx.lds + Y.eps) + (tid & ~63)), 4, 0, 0);
-    };
-    if (A.opt == 0) {
-        touch(S.hist + ((long long)wslot.slot * 2 + 0) * M.Dh + ih);
-        touch(S.hist + ((long long)wslot.slot * 2 + 1) * M.Dh + ih);
-    }
-    if (BS_PF0 > 1) { touch(S.mu + i0); touch(S.om + i0); touch(S.acc_mu + i0); touch(S.acc_om + i0); touch(S.accl + 2 * i0); }
-#else
-    (void)cx; (void)M; (void)S; (void)A; (void)Y; (void)wslot;
-#endif
 }
 
 // pair slot p of the tile's loglambda segments (lane q = bl LPB + kk of replicate r's segment owns (b, 2 kk), (b, 2 kk + 1) of that
@@ -233,13 +189,11 @@ BB_DEV bb_d2 bs_z(const bb_d2 mu, const bb_d2 om, const bb_d2 e, bb_d2* sp, bb_d
     *sg = bb_d2{sg0, sg1};
     return bb_d2{fma(sp0, e.x, mu.x), fma(sp1, e.y, mu.y)};
 }
-// what a loglambda pair leaves for the NEXT step's M pass: its two forward differences in the thread's private LDS entry, lambda on the
-// thread's running sums (zn: the next pair's first sample, by DPP)
+// what a loglambda pair leaves for the NEXT step's M and G passes: its sample in its LDS entry, lambda on the thread's running sums
 template <int KIND>
-BB_DEV void bs_put_l(double* lds, const BRLay& Y, int zoff, int meta, const bb_d2 z, double zn, BSG& g) {
+BB_DEV void bs_put_l(double* lds, const BRLay& Y, int zoff, int meta, const bb_d2 z, BSG& g) {
     if (!(meta & BRM_VALID)) return;
-    const bool hn = meta & BRM_NEXT;
-    *(bb_d2*)(lds + Y.zl + zoff) = BS_ZKEEP ? z : bb_d2{z.y - z.x, hn ? zn - z.y : 0.0};
+    *(bb_d2*)(lds + Y.zl + zoff) = z;
     // (one replicate: a thread's pairs share their S_t rows, lambda joins running sums; several: the M pass takes e^z again, per replicate)
     if (KIND <= 2) { g.lam0 += bb_exp(z.x); g.lam1 += bb_exp(z.y); }
 }
@@ -329,9 +283,8 @@ BB_DEV void bs_sample0(BBCtx& cx, const DevModel& M, const DevState& S, const Ru
         }
         BB_PASS(cx, tid) {
             BSG& g = BB_PSTATE(gv, tid);
-            const double zn = BS_NEXT(gv, tid, z.x);
             const int p = tid + k * cx.nthr, meta = g.st.meta[0];
-            if (p < lspan) { if ((meta & 15) == SK_L) bs_put_l<KIND>(lds, Y, g.st.zoff[0], meta, g.z, zn, g); }
+            if (p < lspan) { if ((meta & 15) == SK_L) bs_put_l<KIND>(lds, Y, g.st.zoff[0], meta, g.z, g); }
             else bs_put_u<KIND>(lds, M, Y, A, g.st, buf0 >= 0 ? buf0 : (int)(step & 1u), g.z);
         }
     }
@@ -388,8 +341,7 @@ BB_DEV void bs_moments(BBCtx& cx, const DevModel& M, const DevState& S, const Ru
                 if ((meta & 15) != SK_L || !(meta & BRM_VALID)) continue;
                 const bb_d2 d = *(const bb_d2*)(lds + Y.zl + st.zoff[0]);
                 const bool hn = meta & BRM_NEXT, mut = meta & BRM_MUT;
-                double dm = d.x, dn = d.y;
-                if (BS_ZKEEP) { dm = d.y - d.x; dn = hn ? lds[Y.zl + st.zoff[0] + 2] - d.y : 0.0; }
+                double dm = d.y - d.x, dn = hn ? lds[Y.zl + st.zoff[0] + 2] - d.y : 0.0;
                 if (KIND >= 3) { g.cv[0] += bb_exp(d.x); g.cv[6] += bb_exp(d.y); }
                 if (mut) {
                     double sm, sn, wm, wn;
@@ -441,7 +393,9 @@ BB_DEV void bs_load_state(const DevModel& M, const DevState& S, const double* hs
     g.lo = bb_load_lo(S, i0, a0, a1);
     g.hm = g.ho = bb_d2{0, 0};
     if (hs_m) {
-#if !defined(BB_EMU) && BS_NT_HIST
+#ifndef BB_EMU
+        // the window slot is read with the non-temporal policy (it is not touched again for a whole window; the state arrays, re-read every
+        // step, keep the Infinity Cache): C5 90.8 -> 83.9 us (round 3)
         if (a0 && a1) {
             typedef double bs_v2d __attribute__((ext_vector_type(2)));
             const bs_v2d x = __builtin_nontemporal_load((const bs_v2d*)(hs_m + ih)), y = __builtin_nontemporal_load((const bs_v2d*)(hs_o + ih));
@@ -519,7 +473,7 @@ BB_DEV void bs_load_mu_om(const DevState& S, long long i0, bool a0, bool a1, BSG
     g.lo = bb_f4{0.f, 0.f, 0.f, 0.f};
 }
 
-// ---- G-L: every loglambda pair slot -- state in, the draw again, gradient, the barcode's unit sums, optimiser, out; the next sample ----
+// ---- G-L: every loglambda pair slot -- state in, eps from the kept sample, gradient, the barcode's unit sums, optimiser, out; the next sample ----
 template <int KIND, int TT, bool MS = false>
 BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, int NB, int P, unsigned step, const BBSlot wslot, int* bad_any, BSG* gv,
                         const BSMs ms_ = BSMs{1, 0, -1, true, false, 0u, 0u}) {
@@ -542,7 +496,7 @@ BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const R
     }
     double* aq = lds + Y.hbuf;            // [SU] pairs (As, Qs) per unit, in the moment contributions' region (dead since the row sums)
     for (int k = 0; k < PL; ++k) {
-        // A: state in, the step's draw again, the sample
+        // A: state in, the kept sample, eps
         BB_PASS(cx, tid) {
             BSG& g = BB_PSTATE(gv, tid);
             const int p = tid + k * cx.nthr;
@@ -556,20 +510,13 @@ BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const R
                     const long long i0 = g.st.i0[0];
                     if (MS && !ms.last) bs_load_mu_om(S, i0, true, true, g);
                     else bs_load_state(M, S, hs_m, hs_o, i0, i0 - sg[g.st.meta[0] >> 12].pad, true, true, g);
-                    if (BS_ZKEEP) {
-                        g.z = *(const bb_d2*)(lds + Y.zl + g.st.zoff[0]);
-                        double sp0, sg0, sp1, sg1;
-                        bb_softplus_sigmoid(g.om.x, &sp0, &sg0);
-                        bb_softplus_sigmoid(g.om.y, &sp1, &sg1);
-                        const double r0 = bb_rcp(sp0), r1 = bb_rcp(sp1);
-                        g.a = bb_d2{(g.z.x - g.mu.x) * r0 * sg0, (g.z.y - g.mu.y) * r1 * sg1};          // eps = (z - mu) / softplus(omega)
-                        g.h = bb_d2{sg0 * r0, sg1 * r1};
-                    } else {
-                        g.e = BS_G_INLINE_DRAW ? bs_draw_inline(A.seed, i0, step, (unsigned)ms.smp) : bs_draw(A.seed, i0, step, (unsigned)ms.smp);
-                        g.z = bs_z(g.mu, g.om, g.e, &g.sp, &g.sg);
-                        g.a = bb_d2{g.e.x * g.sg.x, g.e.y * g.sg.y};
-                        g.h = bb_d2{g.sg.x * bb_rcp(g.sp.x), g.sg.y * bb_rcp(g.sp.y)};
-                    }
+                    g.z = *(const bb_d2*)(lds + Y.zl + g.st.zoff[0]);
+                    double sp0, sg0, sp1, sg1;
+                    bb_softplus_sigmoid(g.om.x, &sp0, &sg0);
+                    bb_softplus_sigmoid(g.om.y, &sp1, &sg1);
+                    const double r0 = bb_rcp(sp0), r1 = bb_rcp(sp1);
+                    g.a = bb_d2{(g.z.x - g.mu.x) * r0 * sg0, (g.z.y - g.mu.y) * r1 * sg1};          // eps = (z - mu) / softplus(omega)
+                    g.h = bb_d2{sg0 * r0, sg1 * r1};
                 }
             }
         }
@@ -636,16 +583,14 @@ BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const R
             if (g.ok) {
                 const long long i0 = g.st.i0[0];
                 if (bs_finish_pair<MS>(M, S, A, wslot, hs_m, hs_o, i0, i0 - sg[g.st.meta[0] >> 12].pad, true, true, g.g0, g.g1, g, ms)) *bad_any = 1;
-                const bb_d2 en = BS_S_INLINE_DRAW ? bs_draw_inline(A.seed, i0, ms.nstep, ms.nstream) : bs_draw(A.seed, i0, ms.nstep, ms.nstream);
+                const bb_d2 en = bs_draw_inline(A.seed, i0, ms.nstep, ms.nstream);
                 g.z = bs_z(g.mu, g.om, en, &g.sp, &g.sg);
                 if (MS && ms.el_next) g.el += bs_el_pair<KIND, TT>(lds, M, Y, A, g.st, g.z, g.sp);
             }
         }
         BB_PASS(cx, tid) {
             BSG& g = BB_PSTATE(gv, tid);
-            const double zn = BS_NEXT(gv, tid, z.x);
-            const int p = tid + k * cx.nthr;
-            if (g.ok) bs_put_l<KIND>(lds, Y, g.st.zoff[0], g.st.meta[0], g.z, zn, g);
+            if (g.ok) bs_put_l<KIND>(lds, Y, g.st.zoff[0], g.st.meta[0], g.z, g);
         }
     }
     BB_STAMP(cx, S, 27);             // (no barrier here: the unit pass forms its first slot's sample before it meets the loglambda lanes)
@@ -666,7 +611,7 @@ BB_DEV bool bs_unit_a(const DevModel& M, const DevState& S, const RunArgs& A, co
     const long long i0 = st.i0[0];
     if (MS && !ms.last) bs_load_mu_om(S, i0, a0, a1, g);
     else bs_load_state(M, S, hs_m, hs_o, i0, i0 - sg[meta >> 12].pad, a0, a1, g);
-    g.e = BS_G_INLINE_DRAW ? bs_draw_inline(A.seed, i0, step, (unsigned)ms.smp) : bs_draw(A.seed, i0, step, (unsigned)ms.smp);
+    g.e = bs_draw_inline(A.seed, i0, step, (unsigned)ms.smp);
     g.z = bs_z(g.mu, g.om, g.e, &g.sp, &g.sg);          // the owner's own sample of this step, again
     g.a = bb_d2{g.e.x * g.sg.x, g.e.y * g.sg.y};
     g.h = bb_d2{g.sg.x * bb_rcp(g.sp.x), g.sg.y * bb_rcp(g.sp.y)};
@@ -750,7 +695,7 @@ BB_DEV bool bs_unit_b(const DevModel& M, const DevState& S, const RunArgs& A, co
     gl0 -= (zv0 - pm0) * iv0;
     gl1 -= (zv1 - pm1) * iv1;
     const bool bad = bs_finish_pair<MS>(M, S, A, wslot, hs_m, hs_o, i0, ih, a0, a1, gl0, gl1, g, ms);
-    const bb_d2 en = BS_S_INLINE_DRAW ? bs_draw_inline(A.seed, i0, ms.nstep, ms.nstream) : bs_draw(A.seed, i0, ms.nstep, ms.nstream);
+    const bb_d2 en = bs_draw_inline(A.seed, i0, ms.nstep, ms.nstream);
     const bb_d2 zn = bs_z(g.mu, g.om, en, &g.sp, &g.sg);
     bs_put_u<KIND>(lds, M, Y, A, st, nbuf, zn);
     if (MS && ms.el_next) g.el += bs_el_pair<KIND, TT>(lds, M, Y, A, st, zn, g.sp);
@@ -839,8 +784,7 @@ __global__ void __launch_bounds__(NT) k_stream(const DevModel* __restrict__ Mp, 
                 const BSMs ms = MS ? bs_ms_of(A, step, smp, NS, want_el, MS && A.elbo_every > 0 && ec1 == 0) : bs_ms_plain((unsigned)step);
                 const unsigned long long xc = MS ? step * (unsigned long long)NS + (unsigned long long)smp : step;
                 bs_moments<KIND, TT, MS>(cx, M, S, A, Y, NB, P, (unsigned)step, &g, ms.buf, want_el);
-                bs_touch0<KIND, TT>(cx, M, S, A, Y, wslot);
-                br_row_publish<1, true, MS>(cx, M, S, Y, nost, A.xepoch0 + (unsigned)(xc + 1), want_el);
+                br_row_publish<1, MS>(cx, M, S, Y, nost, A.xepoch0 + (unsigned)(xc + 1), want_el);
                 br_xchg_lead<false>(cx, M, S, A, Y, xc, ok_slot);
                 br_xchg_consume<KIND, 1, false, MS>(cx, M, S, A, Y, nost, xc, ok_slot, want_el, ring, smp);
                 if (*ok_slot == 0) { stop = true; break; }

@@ -88,7 +88,7 @@ struct DevState {
     unsigned *hstatus;                // host-mapped status words the host reads after a run without a copy: [0] timeout, [1] non-finite state
     double *prow;                     // [nblk][K + 2 nt1] rows of the tiles (persistent launch)
     double *xrow;                     // [2][8][K + 2 nt1] group rows, double-buffered by step parity
-    struct bb_gran *grow, *gxrow;     // k_res on one GPU: the same rows as self-validating 16-byte entries (bb_persist.h, BR_TG): [nblk][bb_row_stride(K + 2 nt1)], [2][16][K + 2 nt1]
+    struct bb_gran *grow, *gxrow;     // k_res / k_stream: the same rows as self-validating 16-byte entries (bb_persist.h, bb_gran): [nblk][bb_row_stride(K + 2 nt1)], [2][16][K + 2 nt1]
     unsigned *rdy;                    // [32 * (nblk + 16)] ready words, one 128-B line each: tiles, then [2][8] groups
     int *xsel;                        // [nblk + 8] what each tile of the last resident launch decided about its row stores: 1 plain (same XCD as its leader), -1 write-through, 0 not decided
     unsigned long long *xtab;         // [BB_NG_MAX] k_res / k_stream: where the group leaders run -- {launch tag << 32 | XCC id}, written by every leader at the start of
@@ -121,7 +121,7 @@ struct RunArgs {
     int nblk_alloc;                   // tiles the exchange / stamp buffers were sized for (+ 8)
     int ng;                           // groups of the exchange's first hop (8; k_res on one GPU: 16 where the tile has the threads for it)
     int pf;                           // k_res: when a step's TruncatedADAGrad window slot is fetched into LDS -- 0 in the exchange's shadow, 1 at the start of the
-                                      // step's S pass, 2 at the end of the previous step's G pass (1, 2: the slot buffer has an LDS region of its own)
+                                      // step's S pass (the slot buffer has an LDS region of its own)
     int nbl;                          // k_res: barcodes of each of the first min(8, nblk) tiles -- the exchange's group leaders get smaller tiles (0: all tiles alike)
     int par;                          // which ctr[] word holds the current step
     int sample, S;
