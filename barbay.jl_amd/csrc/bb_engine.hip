@@ -27,10 +27,6 @@
 #include <type_traits>
 #include <vector>
 
-#ifndef BB_EMU
-#include <dlfcn.h>
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // errors
 // ------------------------------------------------------------------------------------------------
@@ -43,184 +39,17 @@ static int bb_fail(int code, const char* fmt, ...) {
     return code;
 }
 extern "C" const char* bb_last_error(void) { return g_err; }
-extern "C" const char* bb_version(void) {
-#ifdef BB_EMU
-    return "barbay_hip 0.1 (host emulation, tests only)";
-#else
-    return "barbay_hip 0.1 (gfx950)";
-#endif
-}
 
-// ------------------------------------------------------------------------------------------------
-// backend: device memory + kernel launches
-// ------------------------------------------------------------------------------------------------
-#ifdef BB_EMU
-typedef int bbStream;
-#define BB_CHECK(x) (x)
-static int dmalloc(void** p, size_t n) { *p = calloc(1, n ? n : 1); return *p ? 0 : BB_ERR_DEVICE; }
-static void dfree(void* p) { free(p); }
-static int h2d(void* d, const void* h, size_t n, bbStream) { memcpy(d, h, n); return 0; }
-static int d2h(void* h, const void* d, size_t n, bbStream) { memcpy(h, d, n); return 0; }
-static int d2d(void* d, const void* s, size_t n, bbStream) { memcpy(d, s, n); return 0; }
-static int dzero(void* d, size_t n, bbStream) { memset(d, 0, n); return 0; }
-static int dsync(bbStream) { return 0; }
-template <class F>
-static void emu_launch(int nblocks, int nthr, size_t lds_doubles, F f) {
-    std::vector<double> lds(lds_doubles + 64);
-    for (int b = 0; b < nblocks; ++b) {
-        BBCtx cx{nthr, b, lds.data()};
-        f(cx);
-    }
-}
-#else
-typedef hipStream_t bbStream;
-#define BB_HIP(call)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) return bb_fail(BB_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(_e)); \
-    } while (0)
-static int dmalloc(void** p, size_t n) { BB_HIP(hipMalloc(p, n ? n : 1)); return 0; }
-static void dfree(void* p) { (void)hipFree(p); }
-static int h2d(void* d, const void* h, size_t n, bbStream s) {
-    BB_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s));
-    BB_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-static int d2h(void* h, const void* d, size_t n, bbStream s) {
-    BB_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s));
-    BB_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-static int d2d(void* d, const void* s_, size_t n, bbStream s) {
-    BB_HIP(hipMemcpyAsync(d, s_, n, hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-static int dzero(void* d, size_t n, bbStream s) { BB_HIP(hipMemsetAsync(d, 0, n, s)); return 0; }
-static int dsync(bbStream s) { BB_HIP(hipStreamSynchronize(s)); return 0; }
+// the backend: device memory, kernel launches, streams, peers, the communicator -- HIP or the host emulation; the small kernels
+#include "bb_backend.h"
 
-extern __shared__ __attribute__((aligned(16))) double bb_smem[];
-
-// (descriptors by pointer: scalar loads on demand; by value they cost dozens of SGPR spills per kernel)
-template <int KIND>
-__global__ void __launch_bounds__(1024) k_sample(const DevModel* __restrict__ Mp, const DevState* __restrict__ Sp, RunArgs A, int NB) {
-    const DevModel& M = *Mp;
-    const DevState& S = *Sp;
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_sample<KIND>(cx, M, S, A, NB);
-}
-template <int KIND>
-__global__ void __launch_bounds__(1024) k_update(const DevModel* __restrict__ Mp, const DevState* __restrict__ Sp, RunArgs A, int NB) {
-    const DevModel& M = *Mp;
-    const DevState& S = *Sp;
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_update<KIND>(cx, M, S, A, NB);
-}
-typedef void (*bb_step_kernel)(const DevModel*, const DevState*, RunArgs, int);
-static bb_step_kernel sample_kernel(int kind) {
-    switch (kind) { case 0: return k_sample<0>; case 1: return k_sample<1>; case 2: return k_sample<2>; case 3: return k_sample<3>; default: return k_sample<4>; }
-}
-static bb_step_kernel update_kernel(int kind) {
-    switch (kind) { case 0: return k_update<0>; case 1: return k_update<1>; case 2: return k_update<2>; case 3: return k_update<3>; default: return k_update<4>; }
-}
-__global__ void __launch_bounds__(256) k_geno(DevModel M, DevState S, RunArgs A, int do_update, int do_sample, int upd_par) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_geno(cx, M, S, A, (int)gridDim.x, do_update, do_sample, upd_par);
-}
-__global__ void __launch_bounds__(256) k_geno_sum(DevModel M, DevState S, long long m_lo, long long m_hi) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_geno_sum(cx, M, S, (int)gridDim.x, m_lo, m_hi);
-}
-__global__ void __launch_bounds__(256) k_reduce(DevModel M, DevState S, int nblk, int ngeno_blocks) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_reduce(cx, M, S, nblk, ngeno_blocks);
-}
-__global__ void __launch_bounds__(256) k_theta_pack(DevModel M, DevState S, double* buf, int g_lo, int g_hi, int W, int unpack) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_theta_pack(cx, M, S, buf, g_lo, g_hi, W, unpack, (int)gridDim.x);
-}
-__global__ void __launch_bounds__(256) k_init(DevModel M, DevState S, unsigned long long seed) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_init(cx, M, S, seed, (int)gridDim.x);
-}
-__global__ void __launch_bounds__(1024) k_hier(HierArgs H) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_hier(cx, H, (int)gridDim.x);
-}
-__global__ void __launch_bounds__(256) k_ppc_pop(PpcArgs P) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_ppc_pop(cx, P, (int)gridDim.x);
-}
-__global__ void __launch_bounds__(1024) k_ppc(PpcArgs P) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_ppc(cx, P, (int)gridDim.x);
-}
-// transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
-__global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {
-    const int r = threadIdx.x;
-    if (r < world) {
-        unsigned* out = S.xout_rdy[r] + probe_words_off + 32 * rank;
-        __hip_atomic_store(out, 0xB0000000u | (seq << 8) | (unsigned)rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const unsigned* in = S.xout_rdy[rank] + probe_words_off + 32 * r;
-        const unsigned want = 0xB0000000u | (seq << 8) | (unsigned)r;
-        unsigned seen = 0, spins = 0;
-        while ((seen = __hip_atomic_load(in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != want && ++spins < (1u << 22)) __builtin_amdgcn_s_sleep(2);
-        result[r] = seen == want ? 1u : 0u;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_normals(unsigned long long seed, unsigned step, unsigned stream, long long lo,
-                                                 long long hi, double* out) {
-    BBCtx cx{(int)blockDim.x, (int)blockIdx.x, bb_smem};
-    bb_block_normals(cx, seed, step, stream, lo, hi, out, (int)gridDim.x);
-}
-
-// ---- RCCL, bound at run time so that the library loads (and N = 1 runs) without it -------------
-typedef struct { char internal[128]; } bb_ncclUniqueId;
-typedef void* bb_ncclComm_t;
-struct RcclApi {
-    void* lib = nullptr;
-    int (*GetUniqueId)(bb_ncclUniqueId*) = nullptr;
-    int (*CommInitRank)(bb_ncclComm_t*, int, bb_ncclUniqueId, int) = nullptr;
-    int (*AllReduce)(const void*, void*, size_t, int, int, bb_ncclComm_t, hipStream_t) = nullptr;
-    int (*CommDestroy)(bb_ncclComm_t) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-};
-static RcclApi g_rccl;
-static int rccl_load() {
-    if (g_rccl.lib) return 0;
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (const char* n : names) {
-        g_rccl.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        if (g_rccl.lib) break;
-    }
-    if (!g_rccl.lib) return bb_fail(BB_ERR_COMM, "cannot load librccl: %s", dlerror());
-    g_rccl.GetUniqueId = (int (*)(bb_ncclUniqueId*))dlsym(g_rccl.lib, "ncclGetUniqueId");
-    g_rccl.CommInitRank = (int (*)(bb_ncclComm_t*, int, bb_ncclUniqueId, int))dlsym(g_rccl.lib, "ncclCommInitRank");
-    g_rccl.AllReduce = (int (*)(const void*, void*, size_t, int, int, bb_ncclComm_t, hipStream_t))dlsym(g_rccl.lib, "ncclAllReduce");
-    g_rccl.CommDestroy = (int (*)(bb_ncclComm_t))dlsym(g_rccl.lib, "ncclCommDestroy");
-    g_rccl.GetErrorString = (const char* (*)(int))dlsym(g_rccl.lib, "ncclGetErrorString");
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllReduce || !g_rccl.CommDestroy)
-        return bb_fail(BB_ERR_COMM, "librccl lacks a required symbol");
-    return 0;
-}
-#endif
+extern "C" const char* bb_version(void) { return BB_BACKEND_VERSION; }
 
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
 // Every entry point that takes a handle runs with the handle's device current and restores the caller's on exit: the
 // caller may have switched devices since bb_create (torch.cuda.set_device, other handles on other GPUs in this process).
-#ifdef BB_EMU
-struct DevGuard { explicit DevGuard(int) {} };
-#else
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
-    ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-    DevGuard(const DevGuard&) = delete;
-    DevGuard& operator=(const DevGuard&) = delete;
-};
-#endif
 #define BB_ENTER(h) DevGuard bb_dev_guard_((h)->o.device)
 
 // The environment switches, read once by bb_create and kept in the handle; a multi-device handle's shards get the
@@ -321,14 +150,7 @@ struct bb_handle {
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
     int launches_last_run = 0;
     int64_t bytes_sample = 0, bytes_update = 0;
-#ifndef BB_EMU
-    hipGraphExec_t graph = nullptr;
-    int graph_steps = 0;
-    unsigned launch_seq = 0;           // resident launches of this handle so far (RunArgs.launch_tag)
-    bool graph_failed = false;         // capture / instantiation failed once (e.g. a collective that cannot be captured): stay eager
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bb_ncclComm_t comm = nullptr;
-#endif
+    BackendState be;                   // the product's graph of the step loop, run timer and communicator
     BBTuning tune{};                   // the environment switches as bb_create found them
     LaunchPlan plan;
     BRLay Yh{};                        // k_res / k_stream: the LDS carve-up (host copy) and device copy
@@ -360,6 +182,20 @@ static int dalloc(bb_handle* h, T** p, size_t count) {
     h->dev_bytes += (long long)(count * sizeof(T));
     *p = (T*)q;
     return dzero(q, count * sizeof(T), h->stream);
+}
+
+// a buffer of the handle's that grows on demand and keeps no contents across calls (eps_buf, dbg_buf, ppc_buf; bb_destroy frees it)
+static int grow(double** buf, size_t* cap, size_t n) {
+    if (*cap >= n) return 0;
+    if (*buf) dfree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    void* p = nullptr;
+    int rc = dmalloc(&p, n * 8);
+    if (rc) return rc;
+    *buf = (double*)p;
+    *cap = n;
+    return 0;
 }
 
 extern "C" void bb_default_opts(bb_advi_opts* o) {
@@ -493,25 +329,13 @@ static int ensure_scratch(bb_handle* h);
 static void owned_ranges(const bb_handle* sh, std::vector<std::pair<long long, long long>>& out);
 static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, bool apply, bool with_elbo);
 static int theta_sync_local(bb_handle* const* hs, int n);
-#ifndef BB_EMU
-static int launch_check();
-#endif
+static int launch_persistent(bb_handle* h, long long nsteps);
+static int run_enqueue(bb_handle* h, int64_t n_steps);
+static int run_finish(bb_handle* h);
 
 // ------------------------------------------------------------------------------------------------
-// persistent launch (bb_persist.h)
+// resident launches (bb_persist.h, bb_resident.h, bb_stream.h): the plan
 // ------------------------------------------------------------------------------------------------
-#ifndef BB_EMU
-static bb_persist_kernel persist_kernel(int kind, int P, int nthr, bool xg = false, const char** nm = nullptr) {
-#ifdef BB_FAST_BUILD   /* experiment builds (tools/xp.py): only the instances the C2 / C4 workloads use, in this one translation unit */
-    if (nm) *nm = "(experiment build)";
-    if (!xg && nthr > 512 && P == 1 && kind == 0) return k_persist<0, 1, 1024>;
-    return nullptr;
-#else
-    return bb_persist_instance(kind, P, nthr, xg, nm);
-#endif
-}
-#endif
-
 // f(std::integral_constant<int, KIND>{}) for the model kind: the host-side instances of templates over it
 template <class F>
 static void by_kind(int kind, F&& f) {
@@ -530,7 +354,18 @@ static int uniform_T(const DevModel& M) {
     return M.T[0];
 }
 
+// The resident kernel instances (bb_inst.h) and their names; the emulation runs the block programs as host functions, so it only
+// names the launch (the compile-time T / AP / MS are the product's).
 #ifndef BB_EMU
+static bb_persist_kernel persist_kernel(int kind, int P, int nthr, bool xg = false, const char** nm = nullptr) {
+#ifdef BB_FAST_BUILD   /* experiment builds (tools/xp.py): only the instances the C2 / C4 workloads use, in this one translation unit */
+    if (nm) *nm = "(experiment build)";
+    if (!xg && nthr > 512 && P == 1 && kind == 0) return k_persist<0, 1, 1024>;
+    return nullptr;
+#else
+    return bb_persist_instance(kind, P, nthr, xg, nm);
+#endif
+}
 static bb_res_kernel res_kernel(int kind, int P, int nthr, bool xg, int T, bool ap, bool ms = false, const char** nm = nullptr) {
 #ifdef BB_FAST_BUILD
     if (nm) *nm = "(experiment build)";
@@ -557,9 +392,6 @@ static bb_res_kernel res_kernel(int kind, int P, int nthr, bool xg, int T, bool 
     }
 #endif
 }
-#endif
-
-#ifndef BB_EMU
 static bb_stream_kernel stream_kernel(int kind, int nthr, int T, const char** nm = nullptr, bool ms = false) {
 #ifdef BB_FAST_BUILD
     if (nm) *nm = "(experiment build)";
@@ -571,6 +403,35 @@ static bb_stream_kernel stream_kernel(int kind, int nthr, int T, const char** nm
 #else
     return ms ? bb_stream_instance_ms(kind, nthr, T, nm) : bb_stream_instance(kind, nthr, T, nm);
 #endif
+}
+// what try_resident / setup_persistent ask for: k_stream or k_res with P pair slots; k_persist
+static const void* resident_instance(const bb_handle* h, bool stream, int P, bool ms, std::string& name) {
+    const char* nm = "";
+    const void* k = stream ? (const void*)stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), &nm, ms)
+                           : (const void*)res_kernel(h->M.kind, P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), ms, &nm);
+    name = nm;
+    return k;
+}
+static const void* persist_instance(const bb_handle* h, int P, std::string& name) {
+    const char* nm = "";
+    const void* k = (const void*)persist_kernel(h->M.kind, P, h->nthr, h->p2p_on, &nm);
+    name = nm;
+    return k;
+}
+#else
+static const void* resident_instance(const bb_handle* h, bool stream, int P, bool ms, std::string& name) {
+    char nm[64];
+    if (stream) snprintf(nm, sizeof nm, "emu:k_stream<%d,%d,%d%s>", h->M.kind, h->nthr, uniform_T(h->M), ms ? ",true" : "");
+    else snprintf(nm, sizeof nm, "emu:k_res<%d,%d,%d,%s,*,%s,%s>", h->M.kind, P, h->nthr, h->p2p_on ? "true" : "false",
+                  br_any_parity(h->M) ? "true" : "false", ms ? "true" : "false");
+    name = nm;
+    return nullptr;
+}
+static const void* persist_instance(const bb_handle* h, int P, std::string& name) {
+    char nm[48];
+    snprintf(nm, sizeof nm, "emu:k_persist<%d,%d,%d>", h->M.kind, P, h->nthr);
+    name = nm;
+    return nullptr;
 }
 #endif
 
@@ -754,24 +615,9 @@ static bool try_resident(bb_handle* h, bool any_parity, LaunchPlan& p) {
     BRLay Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, pf == 1, stream);
     if (pf != 0 && (size_t)Y.total * 8 > 160 * 1024) { pf = 0; Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false); }      // (no room for a slot buffer of its own: in the exchange's shadow)
     if ((size_t)Y.total * 8 > 160 * 1024) return false;
-    const char* nm = "";
-    const void* k = nullptr;
-#ifdef BB_EMU
-    // (the emulation runs the block programs as host functions: it names the launch, the compile-time T / AP / MS are the product's)
-    char emu_nm[64];
-    if (stream) snprintf(emu_nm, sizeof emu_nm, "emu:k_stream<%d,%d,%d%s>", h->M.kind, h->nthr, uniform_T(h->M), p.ms ? ",true" : "");
-    else snprintf(emu_nm, sizeof emu_nm, "emu:k_res<%d,%d,%d,%s,*,%s,%s>", h->M.kind, P, h->nthr, h->p2p_on ? "true" : "false",
-                  br_any_parity(h->M) ? "true" : "false", p.ms ? "true" : "false");
-    nm = emu_nm;
-#else
-    k = stream ? (const void*)stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), &nm, p.ms)
-               : (const void*)res_kernel(h->M.kind, P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), p.ms, &nm);
-    if (!k) return false;
-    const int lds = Y.total * 8;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, h->nthr, (size_t)lds) != hipSuccess || (long long)per_cu * h->cus < nblk) return false;
-#endif
+    std::string nm;
+    const void* k = resident_instance(h, stream, P, p.ms, nm);
+    if (resident_fit(k, h->nthr, (size_t)Y.total * 8, nblk, h->cus)) return false;
     if (nblk > h->tile_cap) return false;       // (more tiles than the exchange, stamp, xsel and tile-table buffers hold)
     if (h->M.kind == BB_MODEL_GENOTYPE) {
         if (!h->d_tile_b && (dalloc(h, &h->d_tile_b, (size_t)h->tile_cap + 2) || dalloc(h, &h->d_tile_g, (size_t)h->tile_cap + 2))) return false;
@@ -796,11 +642,7 @@ static int setup_persistent(bb_handle* h, int mode) {
     p = LaunchPlan{};
     p.NB = h->NB;
     p.nblk = h->nblk;
-#ifdef BB_EMU
-    p.name = "emu:k_sample + k_update";
-#else
-    p.name = "k_sample<" + std::to_string(h->M.kind) + "> + k_update<" + std::to_string(h->M.kind) + ">";
-#endif
+    p.name = step_kernels_name(h->M.kind);
     // several MC samples per step (Turing.ADVI(samples_per_step, ..), src/vi.jl:98) and ELBO recording: k_res's MS instances (round 4: sharded too --
     // every sample is an exchange of its own, the inbox epochs count exchanges)
     p.ms = h->o.samples_per_step != 1 || h->o.elbo_every != 0;
@@ -822,24 +664,13 @@ static int setup_persistent(bb_handle* h, int mode) {
         if (h->p2p_on && P != 1) why = "sharded resident launch holds one pair per thread";
         h->lds_doubles_p = h->lds_doubles_p0 + (size_t)3 * P * h->nthr;        // drawn-ahead normals (16 B / pair) + cached counts (8 B)
     }
-    const char* nm = "";
+    std::string nm;
     const void* k = nullptr;
-#ifdef BB_EMU
-    char emu_nm[48];
-    snprintf(emu_nm, sizeof emu_nm, "emu:k_persist<%d,%d,%d>", h->M.kind, P, h->nthr);
-    nm = emu_nm;
-#else
     if (!why && want) {
-        k = (const void*)persist_kernel(h->M.kind, P, h->nthr, h->p2p_on, &nm);
-        const int lds = (int)(h->lds_doubles_p * 8);
-        int per_cu = 0;
-        if (lds > 160 * 1024) why = "tile does not fit LDS with the lambda table";
-        else if (!k) why = "no kernel instance";
-        else if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) why = "cannot raise dynamic LDS";
-        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, h->nthr, (size_t)lds) != hipSuccess) why = "occupancy query failed";
-        else if ((long long)per_cu * h->cus < h->nblk) why = "grid does not fit resident on the device";
+        k = persist_instance(h, P, nm);
+        const size_t lds = h->lds_doubles_p * 8;
+        why = lds > PERSIST_LDS_CAP ? "tile does not fit LDS with the lambda table" : resident_fit(k, h->nthr, lds, h->nblk, h->cus);
     }
-#endif
     if (why) {
         // k_persist cannot (tile too large for its state, no instance, sharded with more than one pair per thread ...): k_res's
         // any-parity instances as the second chance
@@ -859,6 +690,9 @@ static RunArgs resident_args(const bb_handle* h) {
     return A;
 }
 
+// ------------------------------------------------------------------------------------------------
+// resident launches: in the emulation
+// ------------------------------------------------------------------------------------------------
 #ifdef BB_EMU
 // Host emulation of the resident launch, phase by phase so that several handles (the ranks of a sharded run, all in
 // this process) can be stepped in lock step: phase 0 prologue, 1 sample + publish + draw-ahead, 2 leaders,
@@ -1093,26 +927,32 @@ extern "C" int bb_emu_run_group(bb_handle** hs, int32_t n, int64_t nsteps) {
     if (!rc) rc = theta_sync_local(hs, n);          // (genotype model: theta_g back from its owner, as bb_run does through RCCL)
     return rc;
 }
-#endif
 
-static int launch_persistent(bb_handle* h, long long nsteps) {
-    const LaunchPlan& p = h->plan;
-    RunArgs A = resident_args(h);
-    int rc = 0;
-    h->req_steps += nsteps * std::max(h->o.samples_per_step, 1);      // (exchanges asked: the rows' epochs count them)
-#ifdef BB_EMU
-    (void)A;
+static int resident_launch(bb_handle* h, RunArgs, long long nsteps) {
     if (h->p2p_on) return bb_fail(BB_ERR_UNSUPPORTED, "emulation: step the ranks of a sharded resident run with bb_emu_run_group");
-    rc = emu_run_group(&h, 1, nsteps);
+    return emu_run_group(&h, 1, nsteps);
+}
+static void resident_timeout_ack(bb_handle*) {}
+static int resident_warm(bb_handle*) { return BB_OK; }
+static int group_run_resident(bb_handle* g, int64_t n_steps) {      // the emulation steps the shards in lock step
+    return bb_emu_run_group(g->shards.data(), (int)g->shards.size(), n_steps);
+}
+
+// ------------------------------------------------------------------------------------------------
+// ... and on the device
+// ------------------------------------------------------------------------------------------------
 #else
+static int resident_launch(bb_handle* h, RunArgs A, long long nsteps) {
+    const LaunchPlan& p = h->plan;
+    int rc = 0;
     // No per-launch memsets: ready words carry base + step + 1 and only grow; the timeout word is sticky (a launch that finds it
     // set leaves at once, so a queue of launches behind a timed-out one neither runs nor skips steps); every launch takes its
     // first step from the device counter.
     if (h->p2p_first && nsteps > 0) { A.spin_limit = 1u << 25; h->p2p_first = false; }   // launch skew between the ranks' processes
     do {                                                  // (nsteps == 0: one launch that only loads and stores the state)
         const int n = (int)std::min<long long>(nsteps, 4096);
-        if (++h->launch_seq == 0u) h->launch_seq = 1u;
-        A.launch_tag = h->launch_seq;
+        if (++h->be.launch_seq == 0u) h->be.launch_seq = 1u;
+        A.launch_tag = h->be.launch_seq;
         if (p.impl == IMPL_STREAM) hipLaunchKernelGGL((bb_stream_kernel)p.fn, dim3(p.nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream,
                                                       (const DevModel*)h->dM, (const DevState*)h->dS, (const BRLay*)h->dY, A, p.NB, n, p.P);
         else if (p.impl == IMPL_RES) hipLaunchKernelGGL((bb_res_kernel)p.fn, dim3(p.nblk), dim3(h->nthr), h->lds_doubles_p * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, (const BRLay*)h->dY, A, p.NB, n);
@@ -1122,8 +962,37 @@ static int launch_persistent(bb_handle* h, long long nsteps) {
         nsteps -= n;
         A.spin_limit = 1u << 23;
     } while (nsteps > 0 && !rc);
-#endif
     return rc;
+}
+// a launch timed out: the steps that were completed, and the acknowledgement that lets later launches run again
+static void resident_timeout_ack(bb_handle* h) {
+    unsigned long long c[2];
+    if (!d2h(c, h->S.ctr, sizeof c, h->stream)) h->step = (long long)c[0];
+    if (!dzero(h->S.gbar, 32 * 10 * 4, h->stream)) (void)dsync(h->stream);
+}
+// a zero-step launch loads the kernel's code object now (seconds on a cold process), not while the peers already poll;
+// the first real launch still gets a longer poll limit (launch skew between the ranks' processes)
+static int resident_warm(bb_handle* h) {
+    h->p2p_first = true;
+    const long long keep = h->req_steps;
+    int rc = launch_persistent(h, 0);
+    h->req_steps = keep;
+    return rc ? rc : dsync(h->stream);
+}
+// the shards' launches are all enqueued before any is waited for
+static int group_run_resident(bb_handle* g, int64_t n_steps) {
+    int rc = 0, rc2 = 0;
+    for (bb_handle* sh : g->shards) { BB_ENTER(sh); if ((rc = run_enqueue(sh, n_steps))) break; }
+    for (bb_handle* sh : g->shards) { BB_ENTER(sh); const int r = run_finish(sh); if (r && !rc2) rc2 = r; }      // (wait for whatever was launched, also after an error)
+    if (!rc) rc = rc2;
+    if (!rc) rc = theta_sync_local(g->shards.data(), (int)g->shards.size());     // (genotype model: theta_g back from its owner)
+    return rc;
+}
+#endif
+
+static int launch_persistent(bb_handle* h, long long nsteps) {
+    h->req_steps += nsteps * std::max(h->o.samples_per_step, 1);      // (exchanges asked: the rows' epochs count them)
+    return resident_launch(h, resident_args(h), nsteps);
 }
 
 // after the stream has drained: the launches' status words (host-mapped, no copy)
@@ -1132,14 +1001,7 @@ static int check_persistent(bb_handle* h) {
     volatile unsigned* st = h->hstatus;
     if (st[0] != 0) {
         st[0] = 0;
-        int rc = 0;
-#ifndef BB_EMU
-        unsigned long long c[2];
-        if (!d2h(c, h->S.ctr, sizeof c, h->stream)) h->step = (long long)c[0];
-        rc = dzero(h->S.gbar, 32 * 10 * 4, h->stream);         // acknowledge: later launches may run again
-        if (!rc) rc = dsync(h->stream);
-#endif
-        (void)rc;
+        resident_timeout_ack(h);
         return bb_fail(BB_ERR_DEVICE, "an exchange of the resident launch timed out (not all %d workgroups resident -- device shared or masked? -- or a peer "
                                       "rank stalled); %lld steps completed; set launch_mode = 1 or re-initialise", h->nblk, h->step);
     }
@@ -1187,19 +1049,9 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
         if (rc) { bb_destroy(h); return rc; } \
     } while (0)
 
-#ifndef BB_EMU
-    {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || opts->device < 0 || opts->device >= ndev) { delete h; return bb_fail(BB_ERR_DEVICE, "device %d: no such HIP device (%d visible)", opts->device, ndev); }
-    }
+    if ((rc = dev_check(opts->device))) { delete h; return rc; }
     BB_ENTER(h);
-    {
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete h; return bb_fail(BB_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e)); }
-        (void)hipEventCreate(&h->ev0);
-        (void)hipEventCreate(&h->ev1);
-    }
-#endif
+    if ((rc = stream_open(&h->stream, h->be))) { delete h; return rc; }
 
     // ---- shapes -----------------------------------------------------------------------------
     long long n_l = 0, cnt = 0;
@@ -1359,9 +1211,7 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
         // (16 waves per CU) working a tile's ~NB*(T+2) latents.  BB_TUNE_* env vars override for experiments.
         int maxT = 0;
         for (int r = 0; r < M.R; ++r) maxT = std::max(maxT, M.T[r]);
-#ifndef BB_EMU
-        { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, opts->device) == hipSuccess && pr.multiProcessorCount > 0) h->cus = pr.multiProcessorCount; }
-#endif
+        h->cus = dev_cus(opts->device, h->cus);
         const long long nbar = std::max<long long>(h->b_hi - h->b_lo, 1);
         int NB = (int)std::max<long long>((nbar + h->cus - 1) / h->cus, 32);
         if (h->tune.nb > 0) NB = h->tune.nb;
@@ -1392,13 +1242,6 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
         h->nblk = (int)((nbar + NB - 1) / NB);
         h->tile_cap = h->nblk + 8;
         h->ngeno_blk = M.G > 0 ? (int)std::min<long long>(((M.G + 1) / 2 + 255) / 256, 64) : 0;
-#ifndef BB_EMU
-        if (need > 64 * 1024) {
-            hipError_t e1 = hipFuncSetAttribute((const void*)sample_kernel(M.kind), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            hipError_t e2 = hipFuncSetAttribute((const void*)update_kernel(M.kind), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            if (e1 != hipSuccess || e2 != hipSuccess) { bb_destroy(h); return bb_fail(BB_ERR_DEVICE, "cannot raise dynamic LDS to %zu bytes", need); }
-        }
-#endif
     }
 
     // ---- state ---------------------------------------------------------------------------------
@@ -1424,23 +1267,7 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
     BB_TRY(dalloc(h, &S.totals, (size_t)M.K));
     BB_TRY(dalloc(h, &S.zg, (size_t)2 * M.nt1));
     BB_TRY(dalloc(h, &S.gbar, (size_t)32 * 10));
-#ifdef BB_EMU
-    h->hstatus = (unsigned*)calloc(16, sizeof(unsigned));
-    S.hstatus = h->hstatus;
-#else
-    {
-        void* hp = nullptr;
-        void* dp = nullptr;
-        if (hipHostMalloc(&hp, 16 * sizeof(unsigned), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-            if (hp) (void)hipHostFree(hp);
-            bb_destroy(h);
-            return bb_fail(BB_ERR_DEVICE, "cannot allocate the host-mapped status words");
-        }
-        memset(hp, 0, 16 * sizeof(unsigned));
-        h->hstatus = (unsigned*)hp;
-        S.hstatus = (unsigned*)dp;
-    }
-#endif
+    BB_TRY(hostmap_alloc(&h->hstatus, &S.hstatus, 16));
     BB_TRY(dalloc(h, &S.prow, (size_t)h->tile_cap * (M.K + 2 * M.nt1)));
     BB_TRY(dalloc(h, &S.xrow, (size_t)2 * BB_NG_MAX * (M.K + 2 * M.nt1)));
     BB_TRY(dalloc(h, &S.grow, (size_t)(h->tile_cap + 16 * BB_NG_MAX) * bb_row_stride(M.K + 2 * M.nt1)));      // (+ 16 groups x 16: a leader's eight loads in flight run past its last member, bb_gran_poll8)
@@ -1604,26 +1431,14 @@ extern "C" void bb_destroy(bb_handle* h) {
     if (!h) return;
     if (!h->shards.empty()) { group_destroy(h); return; }
     BB_ENTER(h);
-#ifndef BB_EMU
-    (void)hipStreamSynchronize(h->stream);
-    if (h->graph) (void)hipGraphExecDestroy(h->graph);
-    if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-#endif
+    stream_quiesce(h->stream, h->be);
     p2p_release(h);
-#ifdef BB_EMU
-    free(h->hstatus);
-#else
-    if (h->hstatus) (void)hipHostFree(h->hstatus);
-#endif
+    hostmap_free(h->hstatus);
     for (void* p : h->owned) dfree(p);
     if (h->eps_buf) dfree(h->eps_buf);
     if (h->dbg_buf) dfree(h->dbg_buf);
     if (h->ppc_buf) dfree(h->ppc_buf);
-#ifndef BB_EMU
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-#endif
+    stream_close(h->stream);
     delete h;
 }
 
@@ -1675,17 +1490,6 @@ static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, 
     return A;
 }
 
-#ifdef BB_EMU
-#define LAUNCH_CHECK() 0
-#else
-static int launch_check() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bb_fail(BB_ERR_DEVICE, "kernel launch: %s", hipGetErrorString(e));
-    return 0;
-}
-#define LAUNCH_CHECK() launch_check()
-#endif
-
 // Per-sample scratch of the two-kernel step (z, eps sigmoid, sigmoid / softplus), the S > 1 / gradient-export accumulators and
 // bb_elbo_grad's saved parameters: 7 arrays of D doubles, allocated on first use -- every entry point that can reach the
 // two-kernel launchers calls this first (never from inside a stream capture); the resident launches use none of them.
@@ -1702,80 +1506,39 @@ static int ensure_scratch(bb_handle* h) {
     return h->dS ? h2d(h->dS, &h->S, sizeof(DevState), h->stream) : BB_OK;      // (kernels read the descriptor through its device copy)
 }
 
+// the small kernels of the two-kernel step (k_sample / k_update: the instance of the model kind, descriptors through pointers)
 static int launch_sample(bb_handle* h, const RunArgs& A) {
     if (!h->S.zsv) return bb_fail(BB_ERR_DEVICE, "internal: the two-kernel step's scratch arrays were not allocated (ensure_scratch)");
-#ifdef BB_EMU
-    emu_launch(h->nblk, h->nthr, h->lds_doubles, [&](BBCtx& cx) {
-        switch (h->M.kind) {
-        case 0: bb_block_sample<0>(cx, h->M, h->S, A, h->NB); break;
-        case 1: bb_block_sample<1>(cx, h->M, h->S, A, h->NB); break;
-        case 2: bb_block_sample<2>(cx, h->M, h->S, A, h->NB); break;
-        case 3: bb_block_sample<3>(cx, h->M, h->S, A, h->NB); break;
-        default: bb_block_sample<4>(cx, h->M, h->S, A, h->NB);
-        }
+    int rc = 0;
+    by_kind(h->M.kind, [&](auto kindc) {
+        rc = launch(h->stream, k_sample<decltype(kindc)::value>, h->nblk, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), desc_ptr(h->dS, &h->S), A, h->NB);
     });
-#else
-    hipLaunchKernelGGL(sample_kernel(h->M.kind), dim3(h->nblk), dim3(h->nthr), h->lds_doubles * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, A, h->NB);
-#endif
-    return LAUNCH_CHECK();
+    return rc;
 }
 static int launch_update(bb_handle* h, const RunArgs& A) {
     if (!h->S.zsv) return bb_fail(BB_ERR_DEVICE, "internal: the two-kernel step's scratch arrays were not allocated (ensure_scratch)");
-#ifdef BB_EMU
-    emu_launch(h->nblk, h->nthr, h->lds_doubles, [&](BBCtx& cx) {
-        switch (h->M.kind) {
-        case 0: bb_block_update<0>(cx, h->M, h->S, A, h->NB); break;
-        case 1: bb_block_update<1>(cx, h->M, h->S, A, h->NB); break;
-        case 2: bb_block_update<2>(cx, h->M, h->S, A, h->NB); break;
-        case 3: bb_block_update<3>(cx, h->M, h->S, A, h->NB); break;
-        default: bb_block_update<4>(cx, h->M, h->S, A, h->NB);
-        }
+    int rc = 0;
+    by_kind(h->M.kind, [&](auto kindc) {
+        rc = launch(h->stream, k_update<decltype(kindc)::value>, h->nblk, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), desc_ptr(h->dS, &h->S), A, h->NB);
     });
-#else
-    hipLaunchKernelGGL(update_kernel(h->M.kind), dim3(h->nblk), dim3(h->nthr), h->lds_doubles * 8, h->stream, (const DevModel*)h->dM, (const DevState*)h->dS, A, h->NB);
-#endif
-    return LAUNCH_CHECK();
+    return rc;
 }
 static int launch_reduce(bb_handle* h) {
-#ifdef BB_EMU
-    emu_launch(1, 256, (size_t)16 * h->M.K, [&](BBCtx& cx) { bb_block_reduce(cx, h->M, h->S, h->nblk, h->ngeno_blk); });
-#else
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), (size_t)16 * h->M.K * 8, h->stream, h->M, h->S, h->nblk, h->ngeno_blk);
-#endif
-    return LAUNCH_CHECK();
+    return launch(h->stream, k_reduce, 1, 256, (size_t)16 * h->M.K, h->M, h->S, h->nblk, h->ngeno_blk);
 }
 static int launch_geno(bb_handle* h, const RunArgs& A, int do_update, int do_sample, int upd_par) {
     if (!h->S.zsv) return bb_fail(BB_ERR_DEVICE, "internal: the two-kernel step's scratch arrays were not allocated (ensure_scratch)");
-#ifdef BB_EMU
-    emu_launch(h->ngeno_blk, 256, 256 + 64, [&](BBCtx& cx) { bb_block_geno(cx, h->M, h->S, A, h->ngeno_blk, do_update, do_sample, upd_par); });
-#else
-    hipLaunchKernelGGL(k_geno, dim3(h->ngeno_blk), dim3(256), (256 + 64) * 8, h->stream, h->M, h->S, A, do_update, do_sample, upd_par);
-#endif
-    return LAUNCH_CHECK();
+    return launch(h->stream, k_geno, h->ngeno_blk, 256, 256 + 64, h->M, h->S, A, do_update, do_sample, upd_par);
 }
 static int launch_geno_sum(bb_handle* h) {
     const long long m_lo = std::max(h->b_lo, h->M.nn) - h->M.nn, m_hi = std::max(h->b_hi, h->M.nn) - h->M.nn;
-#ifdef BB_EMU
     const int gsb = (int)std::min<long long>((h->M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block
-    emu_launch(gsb, 256, 256, [&](BBCtx& cx) { bb_block_geno_sum(cx, h->M, h->S, gsb, m_lo, m_hi); });
-#else
-    const int gsb = (int)std::min<long long>((h->M.G + 31) / 32, 1024);
-    hipLaunchKernelGGL(k_geno_sum, dim3(gsb), dim3(256), 256 * 8, h->stream, h->M, h->S, m_lo, m_hi);
-#endif
-    return LAUNCH_CHECK();
+    return launch(h->stream, k_geno_sum, gsb, 256, 256, h->M, h->S, m_lo, m_hi);
 }
 
 static int allreduce(bb_handle* h, double* buf, size_t n) {
     if (h->o.world_size == 1 && !h->tune.force_allreduce) return 0;
-#ifdef BB_EMU
-    (void)buf; (void)n;
-    return bb_fail(BB_ERR_COMM, "in-library collectives are not available in the emulation build");
-#else
-    if (!h->comm) return bb_fail(BB_ERR_COMM, "world_size = %d but bb_comm_init was not called (or use bb_step_moments/bb_step_apply)", h->o.world_size);
-    int rc = g_rccl.AllReduce(buf, buf, n, /*ncclFloat64*/ 8, /*ncclSum*/ 0, h->comm, h->stream);
-    if (rc) return bb_fail(BB_ERR_COMM, "ncclAllReduce: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error");
-    return 0;
-#endif
+    return comm_allreduce(h->be, h->stream, buf, n, h->o.world_size);
 }
 
 // Genotype model with the shards cut at genotype boundaries: a resident run updates theta_g on its owner only.  Gathering the
@@ -1788,12 +1551,7 @@ static int theta_pack(bb_handle* h, int unpack) {
     if (!h->theta_buf && (rc = dalloc(h, &h->theta_buf, n))) return rc;
     const int W = h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD ? h->o.window : 0;
     const int nb = (int)std::min<size_t>((n + 255) / 256, 512);
-#ifdef BB_EMU
-    emu_launch(nb, 256, 0, [&](BBCtx& cx) { bb_block_theta_pack(cx, h->M, h->S, h->theta_buf, h->g_lo, h->g_hi, W, unpack, nb); });
-#else
-    hipLaunchKernelGGL(k_theta_pack, dim3(nb), dim3(256), 0, h->stream, h->M, h->S, h->theta_buf, h->g_lo, h->g_hi, W, unpack);
-#endif
-    return LAUNCH_CHECK();
+    return launch(h->stream, k_theta_pack, nb, 256, 0, h->M, h->S, h->theta_buf, h->g_lo, h->g_hi, W, unpack);
 }
 // ranks of a multi-process run: through the RCCL communicator (collective: every rank is here after the same bb_run)
 static int theta_sync_comm(bb_handle* h) {
@@ -1900,8 +1658,6 @@ static int p2p_alloc_inbox(bb_handle* h);
 static int p2p_wire(bb_handle* h, void* const* bases);
 static int p2p_probe_launch(bb_handle* h, unsigned** res);
 static int p2p_probe_collect(bb_handle* h, unsigned* res, int32_t* ok);
-static int run_enqueue(bb_handle* h, int64_t n_steps);
-static int run_finish(bb_handle* h);
 static void owned_ranges(const bb_handle* sh, std::vector<std::pair<long long, long long>>& out) {
     const DevModel& M = sh->M;
     const long long b_lo = sh->b_lo, b_hi = sh->b_hi;
@@ -1958,19 +1714,11 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const
     g->b_hi = g->M.B;
     // resident launches with in-process peer-mapped inboxes, if every shard can (and the caller did not ask for two kernels)
     bool ok = opts->launch_mode != 1;
-#ifndef BB_EMU
     for (int i = 0; i < n && ok; ++i)
         for (int j = 0; j < n && ok; ++j) {
             const int di = g->shards[i]->o.device, dj = g->shards[j]->o.device;
-            if (di == dj) continue;
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, di, dj) != hipSuccess || !can) { ok = false; break; }
-            DevGuard guard(di);
-            hipError_t e = hipDeviceEnablePeerAccess(dj, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) ok = false;
-            (void)hipGetLastError();
+            if (di != dj && !peer_enable(di, dj)) ok = false;
         }
-#endif
     void* bases[BB_MAX_WORLD] = {};
     for (int i = 0; i < n && ok; ++i) {
         BB_ENTER(g->shards[i]);
@@ -2004,16 +1752,7 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const
 static int group_run(bb_handle* g, int64_t n_steps) {
     int rc = 0;
     if (g->group_resident) {
-#ifdef BB_EMU
-        rc = bb_emu_run_group(g->shards.data(), (int)g->shards.size(), n_steps);      // the emulation steps the shards in lock step
-        g->step = g->shards[0]->step;
-        return rc;
-#endif
-        for (bb_handle* sh : g->shards) { BB_ENTER(sh); if ((rc = run_enqueue(sh, n_steps))) break; }
-        int rc2 = 0;                              // (wait for whatever was launched, also after an error)
-        for (bb_handle* sh : g->shards) { BB_ENTER(sh); const int r = run_finish(sh); if (r && !rc2) rc2 = r; }
-        if (!rc) rc = rc2;
-        if (!rc) rc = theta_sync_local(g->shards.data(), (int)g->shards.size());     // (genotype model: theta_g back from its owner)
+        rc = group_run_resident(g, n_steps);
     } else {
         // the two-kernel step of every shard with the exchanges (K moments; per-genotype gradient sums of the genotype model)
         // summed on the host: enqueue_step with host reductions in place of the RCCL all-reduces
@@ -2080,14 +1819,8 @@ extern "C" int bb_init_meanfield(bb_handle* h) {
     BB_ENTER(h);
     h->theta_stale = false;
     const int nb = (int)std::min<long long>(((h->M.D + 1) / 2 + 255) / 256, 1024);
-#ifdef BB_EMU
-    emu_launch(nb, 256, 0, [&](BBCtx& cx) { bb_block_init(cx, h->M, h->S, h->o.seed, nb); });
-#else
-    hipLaunchKernelGGL(k_init, dim3(nb), dim3(256), 0, h->stream, h->M, h->S, (unsigned long long)h->o.seed);
-    int rc = launch_check();
-    if (rc) return rc;
-#endif
-    return reset_optimizer(h);
+    const int rc = launch(h->stream, k_init, nb, 256, 0, h->M, h->S, h->o.seed);
+    return rc ? rc : reset_optimizer(h);
 }
 
 extern "C" int bb_set_params(bb_handle* h, const double* mu, const double* omega) {
@@ -2138,10 +1871,14 @@ extern "C" int bb_get_posterior(bb_handle* h, double* mean, double* sigma) {
     return BB_OK;
 }
 
+// Captured graphs of the step loop: as many whole graphs of the remaining steps as fit, `done` moved past them.  Whole steps only,
+// starting on an even step (static ping-pong parity); the elbo_every pattern must repeat with the graph -> only when ELBO recording
+// is off; no collectives inside.  The emulation has none: every step is enqueued on its own.
 #ifndef BB_EMU
 static int build_graph(bb_handle* h, int steps) {
-    if (h->graph && h->graph_steps == steps) return 0;
-    if (h->graph) { (void)hipGraphExecDestroy(h->graph); h->graph = nullptr; }
+    BackendState& be = h->be;
+    if (be.graph && be.graph_steps == steps) return 0;
+    if (be.graph) { (void)hipGraphExecDestroy(be.graph); be.graph = nullptr; }
     hipGraph_t g = nullptr;
     BB_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     int rc = 0;
@@ -2150,15 +1887,39 @@ static int build_graph(bb_handle* h, int steps) {
     if (rc || e != hipSuccess) {
         if (g) (void)hipGraphDestroy(g);
         (void)hipGetLastError();
-        h->graph_failed = true;      // not an error: bb_run launches eagerly instead
+        be.graph_failed = true;      // not an error: bb_run launches eagerly instead
         return 0;
     }
-    e = hipGraphInstantiate(&h->graph, g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(&be.graph, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (e != hipSuccess) { h->graph = nullptr; (void)hipGetLastError(); h->graph_failed = true; return 0; }
-    h->graph_steps = steps;
+    if (e != hipSuccess) { be.graph = nullptr; (void)hipGetLastError(); be.graph_failed = true; return 0; }
+    be.graph_steps = steps;
     return 0;
 }
+static int run_graphs(bb_handle* h, int64_t n_steps, int64_t& done) {
+    int rc = 0;
+    int gs = h->o.steps_per_graph == 0 ? 50 : h->o.steps_per_graph;
+    // A sharded step (with its RCCL all-reduce) can be captured too (BB_GRAPH_COLLECTIVE=1; equal results, no gain
+    // measured: the step is GPU-bound), but multi-rank capture could not be exercised on the one-GPU boxes this was
+    // developed on, so sharded runs launch eagerly by default.
+    const bool graph_ok = gs > 0 && h->o.elbo_every == 0 && !h->be.graph_failed && !h->tune.no_graph &&
+                          ((h->o.world_size == 1 && !h->tune.force_allreduce) || h->tune.graph_collective);
+    if (!graph_ok) return 0;
+    gs &= ~1;
+    if (gs < 2) gs = 2;
+    if ((h->step & 1) && done < n_steps) { if ((rc = enqueue_step(h, h->step))) return rc; h->step++; done++; }
+    if (n_steps - done >= gs) {
+        if ((rc = build_graph(h, gs))) return rc;
+        while (h->be.graph && n_steps - done >= gs) {
+            BB_HIP(hipGraphLaunch(h->be.graph, h->stream));
+            h->step += gs;
+            done += gs;
+        }
+    }
+    return 0;
+}
+#else
+static int run_graphs(bb_handle*, int64_t, int64_t&) { return 0; }
 #endif
 
 // bb_run in two halves (a multi-device handle enqueues on all its shards before it waits for any)
@@ -2168,9 +1929,7 @@ static int run_enqueue(bb_handle* h, int64_t n_steps) {
     int64_t done = 0;
     if (h->plan.impl == IMPL_TWO_KERNEL && (rc = ensure_scratch(h))) return rc;
     if (h->hstatus) h->hstatus[1] = 0;          // divergence flag of THIS run (nothing of this handle is in flight here)
-#ifndef BB_EMU
-    BB_HIP(hipEventRecord(h->ev0, h->stream));
-#endif
+    if ((rc = timer_start(h->be, h->stream))) return rc;
     h->launches_last_run = 0;
     if (h->plan.impl != IMPL_TWO_KERNEL && n_steps > 0) {
         if ((rc = launch_persistent(h, n_steps))) return rc;
@@ -2178,46 +1937,16 @@ static int run_enqueue(bb_handle* h, int64_t n_steps) {
         h->launches_last_run = (int)((n_steps + 4095) / 4096);
         if (theta_partial(h)) h->theta_stale = true;         // only the owner's theta_g moved (bb_run / group_run gather it afterwards)
     } else if (h->theta_stale && n_steps > 0 && (rc = theta_sync_comm(h))) return rc;
-#ifndef BB_EMU
-    // graphs: whole steps only, starting on an even step (static ping-pong parity), elbo_every
-    // pattern must repeat with the graph -> only when ELBO recording is off; no collectives inside.
-    int gs = h->o.steps_per_graph == 0 ? 50 : h->o.steps_per_graph;
-    // A sharded step (with its RCCL all-reduce) can be captured too (BB_GRAPH_COLLECTIVE=1; equal results, no gain
-    // measured: the step is GPU-bound), but multi-rank capture could not be exercised on the one-GPU boxes this was
-    // developed on, so sharded runs launch eagerly by default.
-    const bool graph_ok = gs > 0 && h->o.elbo_every == 0 && !h->graph_failed && !h->tune.no_graph &&
-                          ((h->o.world_size == 1 && !h->tune.force_allreduce) || h->tune.graph_collective);
-    if (graph_ok) {
-        gs &= ~1;
-        if (gs < 2) gs = 2;
-        if ((h->step & 1) && done < n_steps) { if ((rc = enqueue_step(h, h->step))) return rc; h->step++; done++; }
-        if (n_steps - done >= gs) {
-            if ((rc = build_graph(h, gs))) return rc;
-            while (h->graph && n_steps - done >= gs) {
-                BB_HIP(hipGraphLaunch(h->graph, h->stream));
-                h->step += gs;
-                done += gs;
-            }
-        }
-    }
-#endif
+    if ((rc = run_graphs(h, n_steps, done))) return rc;
     for (; done < n_steps; ++done) {
         if ((rc = enqueue_step(h, h->step))) return rc;
         h->step++;
     }
-#ifndef BB_EMU
-    BB_HIP(hipEventRecord(h->ev1, h->stream));
-#endif
-    return BB_OK;
+    return timer_stop(h->be, h->stream);
 }
 static int run_finish(bb_handle* h) {
-#ifndef BB_EMU
-    BB_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0;
-    BB_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->last_run_ms = ms;
-#endif
-    return check_persistent(h);
+    int rc = timer_wait(h->be, h->stream, &h->last_run_ms);
+    return rc ? rc : check_persistent(h);
 }
 
 extern "C" int bb_run(bb_handle* h, int64_t n_steps) {
@@ -2242,8 +1971,7 @@ extern "C" int bb_run(bb_handle* h, int64_t n_steps) {
     auto us = [](const timespec& a, const timespec& b) { return (b.tv_sec - a.tv_sec) * 1e6 + (b.tv_nsec - a.tv_nsec) * 1e-3; };
     fprintf(stderr, "[bb_run %lld] device guard %.1f us, enqueue %.1f us, wait + status %.1f us, events %.1f us\n", (long long)n_steps, us(ht0, ht1), us(ht1, ht2), us(ht2, ht3), h->last_run_ms * 1e3);
 #endif
-#ifndef BB_EMU
-    if (h->theta_stale && h->comm) {
+    if (h->theta_stale && comm_ready(h->be)) {
         // Collective, so EVERY rank takes it whatever its own launch reported: the timeout word and the non-finite flag run_finish
         // looks at are this rank's alone, and a rank that returned early here would leave the clean ranks inside ncclAllReduce.
         // The rank's own error is reported afterwards (the gathered theta rows of a failed run mean nothing, but nobody hangs).
@@ -2252,17 +1980,14 @@ extern "C" int bb_run(bb_handle* h, int64_t n_steps) {
         if (rc) snprintf(g_err, sizeof g_err, "%s", why.c_str());
         else rc = rc2;
     }
-#endif
     return rc;
 }
 
-extern "C" int bb_run_profiled(bb_handle* h, int64_t n_steps) {
-    if (!h || n_steps < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
-    BB_GROUP_UNSUPPORTED(h, "bb_run_profiled");
-    BB_ENTER(h);
+// bb_run_profiled: every launch of the two-kernel step between events of its own (the emulation has no clock worth reading: a plain run)
 #ifdef BB_EMU
-    return bb_run(h, n_steps);
+static int run_profiled(bb_handle* h, int64_t n_steps) { return bb_run(h, n_steps); }
 #else
+static int run_profiled(bb_handle* h, int64_t n_steps) {
     if (h->use_reduce()) return bb_fail(BB_ERR_UNSUPPORTED, "bb_run_profiled covers the single-GPU two-kernel step only");
     { const int rcs = ensure_scratch(h); if (rcs) return rcs; }
     const int S = h->o.samples_per_step;
@@ -2294,7 +2019,13 @@ extern "C" int bb_run_profiled(bb_handle* h, int64_t n_steps) {
     for (auto& e : ev) (void)hipEventDestroy(e);
     if (nl) { h->avg_sample_ms = ts / nl; h->avg_update_ms = tu / nl; }
     return rc;
+}
 #endif
+extern "C" int bb_run_profiled(bb_handle* h, int64_t n_steps) {
+    if (!h || n_steps < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
+    BB_GROUP_UNSUPPORTED(h, "bb_run_profiled");
+    BB_ENTER(h);
+    return run_profiled(h, n_steps);
 }
 
 static int elbo_grad_raw(bb_handle* h, const double* mu, const double* omega, const double* eps, int32_t S,
@@ -2322,40 +2053,32 @@ static int elbo_grad_raw(bb_handle* h, const double* mu, const double* omega, co
     if (h->o.world_size > 1 && !eps) return bb_fail(BB_ERR_UNSUPPORTED, "bb_elbo_grad on a sharded handle needs explicit eps");
     const size_t D = (size_t)h->M.D;
     int rc;
+    // what can fail before the handle is touched: scratch, the copy of the parameters to put back, room for the draws, and for the
+    // per-sample ELBO values where S is more than the handle's own buffer holds
     if ((rc = ensure_scratch(h))) return rc;
-    if ((rc = d2d(h->bak_mu, h->S.mu, D * 8, h->stream))) return rc;
-    if ((rc = d2d(h->bak_om, h->S.om, D * 8, h->stream))) return rc;
-    if ((rc = h2d(h->S.mu, mu, D * 8, h->stream))) return rc;
-    if ((rc = h2d(h->S.om, omega, D * 8, h->stream))) return rc;
-    if (eps) {
-        if (h->eps_cap < (size_t)S * D) {
-            if (h->eps_buf) dfree(h->eps_buf);
-            h->eps_buf = nullptr;
-            void* p = nullptr;
-            if ((rc = dmalloc(&p, (size_t)S * D * 8))) return rc;
-            h->eps_buf = (double*)p;
-            h->eps_cap = (size_t)S * D;
-        }
-        if ((rc = h2d(h->eps_buf, eps, (size_t)S * D * 8, h->stream))) return rc;
-        h->S.eps_in = h->eps_buf;
-    }
-    double* es = nullptr;   // per-sample ELBO values
-    if (S > h->o.samples_per_step + 64) {
-        void* p = nullptr;
-        if ((rc = dmalloc(&p, (size_t)S * 8))) return rc;
-        es = (double*)p;
-    }
-    double* saved_es = h->S.elbo_sample;
-    if (es) h->S.elbo_sample = es;
-    if ((rc = sync_descriptors(h))) return rc;
-    for (int s = 0; s < S && !rc; ++s) {
-        RunArgs A = make_args(h, h->step, s, S, false, true);
-        rc = sample_half(h, A);
-        if (!rc) rc = allreduce(h, h->S.totals, (size_t)h->M.K);
-        if (!rc) rc = update_half(h, A);
-    }
+    if ((rc = d2d(h->bak_mu, h->S.mu, D * 8, h->stream)) || (rc = d2d(h->bak_om, h->S.om, D * 8, h->stream))) return rc;
+    if (eps && (rc = grow(&h->eps_buf, &h->eps_cap, (size_t)S * D))) return rc;
+    void* es = nullptr;
+    if (S > h->o.samples_per_step + 64 && (rc = dmalloc(&es, (size_t)S * 8))) return rc;
+    // from here on the handle holds the caller's point and buffers: every path goes through the restore below
+    double* const saved_es = h->S.elbo_sample;
     std::vector<double> ev((size_t)S);
-    if (!rc) rc = d2h(ev.data(), h->S.elbo_sample, (size_t)S * 8, h->stream);
+    auto eval = [&]() -> int {
+        int r;
+        if ((r = h2d(h->S.mu, mu, D * 8, h->stream)) || (r = h2d(h->S.om, omega, D * 8, h->stream))) return r;
+        if (eps) {
+            if ((r = h2d(h->eps_buf, eps, (size_t)S * D * 8, h->stream))) return r;
+            h->S.eps_in = h->eps_buf;
+        }
+        if (es) h->S.elbo_sample = (double*)es;
+        if ((r = sync_descriptors(h))) return r;
+        for (int s = 0; s < S; ++s) {
+            RunArgs A = make_args(h, h->step, s, S, false, true);
+            if ((r = sample_half(h, A)) || (r = allreduce(h, h->S.totals, (size_t)h->M.K)) || (r = update_half(h, A))) return r;
+        }
+        return d2h(ev.data(), h->S.elbo_sample, (size_t)S * 8, h->stream);
+    };
+    rc = eval();
     h->S.elbo_sample = saved_es;
     if (es) dfree(es);
     h->S.eps_in = nullptr;
@@ -2418,22 +2141,9 @@ extern "C" int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int
     const size_t n = (size_t)(hi - lo);
     if (n == 0) return BB_OK;
     int rc;
-    if (h->dbg_cap < n) {
-        if (h->dbg_buf) dfree(h->dbg_buf);
-        h->dbg_buf = nullptr;
-        void* p = nullptr;
-        if ((rc = dmalloc(&p, n * 8))) return rc;
-        h->dbg_buf = (double*)p;
-        h->dbg_cap = n;
-    }
+    if ((rc = grow(&h->dbg_buf, &h->dbg_cap, n))) return rc;
     const int nb = (int)std::min<size_t>((n / 2 + 256) / 256, 1024);
-#ifdef BB_EMU
-    emu_launch(nb, 256, 0, [&](BBCtx& cx) { bb_block_normals(cx, h->o.seed, (unsigned)step, stream, lo, hi, h->dbg_buf, nb); });
-#else
-    hipLaunchKernelGGL(k_normals, dim3(nb), dim3(256), 0, h->stream, (unsigned long long)h->o.seed, (unsigned)step, stream,
-                       (long long)lo, (long long)hi, h->dbg_buf);
-    if ((rc = launch_check())) return rc;
-#endif
+    if ((rc = launch(h->stream, k_normals, nb, 256, 0, h->o.seed, step, stream, lo, hi, h->dbg_buf))) return rc;
     return d2h(out, h->dbg_buf, n * 8, h->stream);
 }
 
@@ -2459,13 +2169,9 @@ static size_t p2p_rows_bytes(const bb_handle* h) {
 static size_t p2p_probe_words_off(const bb_handle* h) { return (size_t)32 * 2 * h->o.world_size * 8; }
 
 static void p2p_release(bb_handle* h) {
-#ifndef BB_EMU
     for (int r = 0; r < BB_MAX_WORLD; ++r)
-        if (h->p2p_peer[r] && r != h->o.rank && !h->in_group) (void)hipIpcCloseMemHandle(h->p2p_peer[r]);
-    if (h->p2p_inbox) (void)hipFree(h->p2p_inbox);
-#else
-    if (h->p2p_inbox) free(h->p2p_inbox);
-#endif
+        if (h->p2p_peer[r] && r != h->o.rank && !h->in_group) ipc_close(h->p2p_peer[r]);
+    finegrained_free(h->p2p_inbox);
     h->p2p_inbox = nullptr;
     h->p2p_ready = h->p2p_on = false;
 }
@@ -2481,15 +2187,7 @@ static int p2p_alloc_inbox(bb_handle* h) {
     h->p2p_rows_bytes = p2p_rows_bytes(h);
     h->p2p_gran_off = (h->p2p_rows_bytes + (p2p_probe_words_off(h) + (size_t)32 * h->o.world_size) * 4 + 255) & ~(size_t)255;
     h->p2p_bytes = h->p2p_gran_off + 2 * h->p2p_rows_bytes + 16 * 16 * (size_t)(h->M.K + 2 * h->M.nt1);      // (tagged rows: 16 B per entry; + the polls' eight-rows-in-flight slack)
-#ifdef BB_EMU
-    h->p2p_inbox = calloc(1, h->p2p_bytes);
-    if (!h->p2p_inbox) return bb_fail(BB_ERR_DEVICE, "out of memory");
-#else
-    BB_HIP(hipExtMallocWithFlags(&h->p2p_inbox, h->p2p_bytes, hipDeviceMallocFinegrained));
-    BB_HIP(hipMemsetAsync(h->p2p_inbox, 0, h->p2p_bytes, h->stream));
-    BB_HIP(hipStreamSynchronize(h->stream));
-#endif
-    return BB_OK;
+    return finegrained_alloc(&h->p2p_inbox, h->p2p_bytes, h->stream);
 }
 
 // every rank's inbox as seen from this rank (bases[own rank] = the local inbox)
@@ -2511,16 +2209,7 @@ extern "C" int bb_p2p_export(bb_handle* h, void* handle_out) {
     BB_ENTER(h);
     memset(handle_out, 0, BB_P2P_HANDLE_BYTES);
     int rc = p2p_alloc_inbox(h);
-    if (rc) return rc;
-#ifdef BB_EMU
-    memcpy(handle_out, &h->p2p_inbox, sizeof(void*));
-#else
-    static_assert(sizeof(hipIpcMemHandle_t) <= BB_P2P_HANDLE_BYTES, "IPC handle does not fit");
-    hipIpcMemHandle_t hnd;
-    BB_HIP(hipIpcGetMemHandle(&hnd, h->p2p_inbox));
-    memcpy(handle_out, &hnd, sizeof hnd);
-#endif
-    return BB_OK;
+    return rc ? rc : ipc_export(handle_out, h->p2p_inbox);
 }
 
 extern "C" int bb_p2p_import(bb_handle* h, const void* handles) {
@@ -2531,69 +2220,21 @@ extern "C" int bb_p2p_import(bb_handle* h, const void* handles) {
     const int W = h->o.world_size;
     void* bases[BB_MAX_WORLD] = {};
     for (int r = 0; r < W; ++r) {
-        void* base = nullptr;
-        if (r == h->o.rank) base = h->p2p_inbox;
-        else {
-            const char* src = (const char*)handles + (size_t)r * BB_P2P_HANDLE_BYTES;
-#ifdef BB_EMU
-            memcpy(&base, src, sizeof(void*));
-#else
-            if (!h->p2p_peer[r]) {
-                hipIpcMemHandle_t hnd;
-                memcpy(&hnd, src, sizeof hnd);
-                BB_HIP(hipIpcOpenMemHandle(&base, hnd, hipIpcMemLazyEnablePeerAccess));
-            } else base = h->p2p_peer[r];
-#endif
-        }
-        bases[r] = base;
+        int rc = 0;
+        if (r == h->o.rank) bases[r] = h->p2p_inbox;
+        else if ((rc = ipc_open(&bases[r], (const char*)handles + (size_t)r * BB_P2P_HANDLE_BYTES, h->p2p_peer[r]))) return rc;
     }
     return p2p_wire(h, bases);
-}
-
-static void dfree_probe(unsigned* res) {
-#ifndef BB_EMU
-    if (res) (void)hipFree(res);
-#else
-    (void)res;
-#endif
 }
 
 // transport probe in two halves, so that one host thread can run it on several devices at once: every rank's kernel waits for
 // the tokens of all the others
 static int p2p_probe_launch(bb_handle* h, unsigned** res) {
     *res = nullptr;
-    ++h->p2p_seq;
-#ifndef BB_EMU
-    BB_HIP(hipMalloc((void**)res, 64 * 4));
-    BB_HIP(hipMemsetAsync(*res, 0, 64 * 4, h->stream));
-    hipLaunchKernelGGL(k_p2p_probe_seq, dim3(1), dim3(64), 0, h->stream, h->S, h->o.rank, h->o.world_size, p2p_probe_words_off(h), h->p2p_seq, *res);
-    return launch_check();
-#else
-    return BB_OK;
-#endif
+    return probe_launch(h->stream, h->S, h->o.rank, h->o.world_size, p2p_probe_words_off(h), ++h->p2p_seq, res);
 }
 static int p2p_probe_collect(bb_handle* h, unsigned* res, int32_t* ok) {
-    const int W = h->o.world_size;
-    *ok = 0;
-#ifdef BB_EMU
-    (void)res;
-    // single address space: the "transport" is a pointer; check that every rank's inbox is distinct and writable
-    for (int r = 0; r < W; ++r) {
-        if (!h->S.xout_rdy[r]) return BB_OK;
-        for (int q = 0; q < r; ++q) if (h->S.xout_rdy[q] == h->S.xout_rdy[r]) return BB_OK;
-    }
-    *ok = 1;
-    return BB_OK;
-#else
-    unsigned host[64] = {0};
-    int rc = d2h(host, res, sizeof host, h->stream);
-    (void)hipFree(res);
-    if (rc) return rc;
-    int good = 1;
-    for (int r = 0; r < W; ++r) good &= host[r] == 1u;
-    *ok = good;
-    return BB_OK;
-#endif
+    return probe_collect(h->stream, res, h->S, h->o.world_size, ok);
 }
 
 extern "C" int bb_p2p_selftest(bb_handle* h, int32_t* ok) {
@@ -2606,7 +2247,7 @@ extern "C" int bb_p2p_selftest(bb_handle* h, int32_t* ok) {
     // (they do: the caller votes on the outcome), so a peer's token is predictable: replace the low byte.
     unsigned* res = nullptr;
     int rc = p2p_probe_launch(h, &res);
-    if (rc) { dfree_probe(res); return rc; }
+    if (rc) { probe_free(res); return rc; }
     return p2p_probe_collect(h, res, ok);
 }
 
@@ -2624,19 +2265,7 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
         return rc;
     }
     if ((rc = sync_descriptors(h))) return rc;
-#ifndef BB_EMU
-    if (h->p2p_on) {
-        // a zero-step launch loads the kernel's code object now (seconds on a cold process), not while the peers already poll;
-        // the first real launch still gets a longer poll limit (launch skew between the ranks' processes)
-        h->p2p_first = true;
-        const long long keep = h->req_steps;
-        rc = launch_persistent(h, 0);
-        h->req_steps = keep;
-        if (!rc) rc = dsync(h->stream);
-        if (rc) return rc;
-    }
-#endif
-    return BB_OK;
+    return h->p2p_on ? resident_warm(h) : BB_OK;
 }
 
 extern "C" int64_t bb_hier_units(const bb_handle* h) {
@@ -2706,14 +2335,7 @@ static int hier_fitness_raw(bb_handle* h, int32_t n_samples, uint64_t seed, doub
     const int nthr = H.n_pad >= 2048 ? 1024 : 256;
     const size_t lds = (size_t)H.n_pad + nthr + 8;
     const int nb = (int)std::min<long long>(n, 2048);
-#ifdef BB_EMU
-    emu_launch(nb, nthr, lds, [&](BBCtx& cx) { bb_block_hier(cx, H, nb); });
-#else
-    if (lds * 8 > 64 * 1024 && hipFuncSetAttribute((const void*)k_hier, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds * 8)) != hipSuccess)
-        return bb_fail(BB_ERR_DEVICE, "cannot raise dynamic LDS to %zu bytes", lds * 8);
-    hipLaunchKernelGGL(k_hier, dim3(nb), dim3(nthr), lds * 8, h->stream, H);
-    if ((rc = launch_check())) return rc;
-#endif
+    if ((rc = launch(h->stream, k_hier, nb, nthr, lds, H))) return rc;
     if ((rc = d2h(median, H.median_out, (size_t)n * 8, h->stream))) return rc;
     return d2h(stdv, H.std_out, (size_t)n * 8, h->stream);
 }
@@ -2803,15 +2425,7 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
     // device buffer: mean | sigma | pop [nt1][2][ns] | par [nblk][E][2][ns] | bands | geno_idx (caller order, ints)
     const size_t nbands = (size_t)P.n_rows * P.n_steps * P.n_q * 2;
     const size_t need = 2 * D + (size_t)P.nt1 * 2 * ns + (size_t)nblk * P.E * 2 * ns + nbands + ((size_t)M.nb + 1) / 2 + 8;
-    if (dh->ppc_cap < need) {
-        if (dh->ppc_buf) dfree(dh->ppc_buf);
-        dh->ppc_buf = nullptr;
-        dh->ppc_cap = 0;
-        void* p = nullptr;
-        if ((rc = dmalloc(&p, need * 8))) return rc;
-        dh->ppc_buf = (double*)p;
-        dh->ppc_cap = need;
-    }
+    if ((rc = grow(&dh->ppc_buf, &dh->ppc_cap, need))) return rc;
     double* b = dh->ppc_buf;
     P.mean = b;
     P.sigma = b + D;
@@ -2834,17 +2448,8 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
     const int nthr = 1024;
     const size_t lds = (size_t)bb_ppc_lds_doubles(P.K);
     const int npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * P.n_samples + 255) / 256, 1024));
-#ifdef BB_EMU
-    emu_launch(npop, 256, 0, [&](BBCtx& cx) { bb_block_ppc_pop(cx, P, npop); });
-    emu_launch((int)nblk, nthr, lds, [&](BBCtx& cx) { bb_block_ppc(cx, P, (int)nblk); });
-#else
-    if (lds * 8 > 64 * 1024 && hipFuncSetAttribute((const void*)k_ppc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds * 8)) != hipSuccess)
-        return bb_fail(BB_ERR_DEVICE, "cannot raise dynamic LDS to %zu bytes", lds * 8);
-    hipLaunchKernelGGL(k_ppc_pop, dim3(npop), dim3(256), 0, dh->stream, P);
-    if ((rc = launch_check())) return rc;
-    hipLaunchKernelGGL(k_ppc, dim3((unsigned)nblk), dim3(nthr), lds * 8, dh->stream, P);
-    if ((rc = launch_check())) return rc;
-#endif
+    if ((rc = launch(dh->stream, k_ppc_pop, npop, 256, 0, P))) return rc;
+    if ((rc = launch(dh->stream, k_ppc, (int)nblk, nthr, lds, P))) return rc;
     if ((rc = d2h(bands, P.bands, nbands * 8, dh->stream))) return rc;
     if (!n_outside) return BB_OK;
     // observed log-frequency ratios outside the band of the largest q (finite ratios only: both counts > 0); the handle's counts are in
@@ -2944,35 +2549,14 @@ extern "C" int bb_kernel_name(bb_handle* h, char* buf, int64_t len) {
 // ------------------------------------------------------------------------------------------------
 extern "C" int bb_comm_make_id(void* id_out) {
     if (!id_out) return bb_fail(BB_ERR_INVALID, "null argument");
-#ifdef BB_EMU
-    return bb_fail(BB_ERR_COMM, "no RCCL in the emulation build");
-#else
-    int rc = rccl_load();
-    if (rc) return rc;
-    bb_ncclUniqueId id;
-    rc = g_rccl.GetUniqueId(&id);
-    if (rc) return bb_fail(BB_ERR_COMM, "ncclGetUniqueId: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error");
-    memcpy(id_out, &id, sizeof id);
-    return BB_OK;
-#endif
+    return comm_make_id(id_out);
 }
 
 extern "C" int bb_comm_init(bb_handle* h, const void* id_in) {
     if (!h || !id_in) return bb_fail(BB_ERR_INVALID, "null argument");
     BB_GROUP_UNSUPPORTED(h, "bb_comm_init");
     BB_ENTER(h);
-#ifdef BB_EMU
-    return bb_fail(BB_ERR_COMM, "no RCCL in the emulation build");
-#else
-    int rc = rccl_load();
-    if (rc) return rc;
-    BB_HIP(hipSetDevice(h->o.device));
-    bb_ncclUniqueId id;
-    memcpy(&id, id_in, sizeof id);
-    rc = g_rccl.CommInitRank(&h->comm, h->o.world_size, id, h->o.rank);
-    if (rc) { h->comm = nullptr; return bb_fail(BB_ERR_COMM, "ncclCommInitRank: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error"); }
-    return BB_OK;
-#endif
+    return comm_init(h->be, id_in, h->o.device, h->o.world_size, h->o.rank);
 }
 
 extern "C" int bb_step_moments(bb_handle* h, double* partial) {

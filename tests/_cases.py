@@ -360,6 +360,38 @@ def case_logdensity(lib, name):
         assert (mu0 == mu1).all() and (om0 == om1).all()      # the variational state is untouched
 
 
+def case_elbo_grad_sample_counts(lib, name="fitness_T2", seed=11):
+    """bb_elbo_grad with S = 1, then 3 (the device copy of the draws grows), then 66 on the smallest fitness shape of SYNTH: with
+    samples_per_step = 1 the handle's per-sample ELBO buffer holds 65 values, so 66 is the smallest S that takes the temporary one.
+    Every multi-sample ELBO and gradient is the mean of the single-sample calls on the same draws -- to 1e-12 of the largest term:
+    an fp64 sum of 66 terms is off by at most about 66 * 2^-53 * sum|g_s| ~ 1e-14 * 66 * max|g|, a hundredth of that bound -- and the
+    calls leave the handle as they found it: parameters bitwise, and the run that follows bitwise that of a fresh handle."""
+    sp = synth(name)
+    with make_engine(sp, lib, seed=seed) as e:
+        mu0, om0 = e.get_params()
+        mu, om = mu0 * 0.2 + 3, om0 * 0.5 - 2               # (not the handle's own parameters: the calls must put those back)
+        eps = np.stack([rng.normals(seed, 4, s, sp.D) for s in range(66)])
+        one = [e.elbo_grad(mu, om, eps[s:s + 1]) for s in range(66)]
+        for S in (3, 66):
+            el, gm, go = e.elbo_grad(mu, om, eps[:S])
+            el1 = np.array([o[0] for o in one[:S]])
+            gm1, go1 = np.stack([o[1] for o in one[:S]]), np.stack([o[2] for o in one[:S]])
+            d_el, d_gm, d_go = abs(el - el1.mean()), np.abs(gm - gm1.mean(0)).max(), np.abs(go - go1.mean(0)).max()
+            print(f"S = {S}: |dELBO| {d_el:.3e} of {np.abs(el1).max():.3e}, |dgrad_mu| {d_gm:.3e} of {np.abs(gm1).max():.3e}, "
+                  f"|dgrad_omega| {d_go:.3e} of {np.abs(go1).max():.3e}")
+            assert d_el <= 1e-12 * np.abs(el1).max()
+            assert d_gm <= 1e-12 * np.abs(gm1).max()
+            assert d_go <= 1e-12 * np.abs(go1).max()
+        mu1, om1 = e.get_params()
+        assert np.array_equal(mu0, mu1) and np.array_equal(om0, om1)
+        e.run(5)
+        got = e.get_params()
+    with make_engine(sp, lib, seed=seed) as e:
+        e.run(5)
+        ref = e.get_params()
+    assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
+
+
 def case_p2p_resident(lib, name, world, steps=7, **ekw):
     """Sharded resident launch (bb_p2p_*): `world` handles of one process, stepped in lock step by the emulation's
     bb_emu_run_group, against the unsharded run -- rows cross ranks through the inboxes exactly as on xGMI.

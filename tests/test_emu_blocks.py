@@ -389,6 +389,10 @@ def test_logdensity_grad(emu_lib, name):
     c.case_logdensity(emu_lib, name)
 
 
+def test_elbo_grad_sample_counts(emu_lib):
+    c.case_elbo_grad_sample_counts(emu_lib)
+
+
 @pytest.mark.parametrize("name,world", [("fitness_multi_tile", 2), ("fitness_multi_tile", 3), ("multienv", 2), ("replicate_ragged", 2),
                                         ("multienv_replicate", 2), ("fitness_T6", 2), ("fitness_T6", 3), ("multienv_T8", 2),
                                         ("replicate_R3", 2), ("multienv_replicate_R3", 2)])

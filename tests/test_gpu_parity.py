@@ -212,6 +212,10 @@ def test_logdensity_grad(hip_lib, name):
     c.case_logdensity(hip_lib, name)
 
 
+def test_elbo_grad_sample_counts(hip_lib):
+    c.case_elbo_grad_sample_counts(hip_lib)
+
+
 @pytest.mark.parametrize("mode", [1, 2])
 def test_runs_are_bit_reproducible(hip_lib, mode):
     """Every cross-thread and cross-workgroup sum has a fixed order (no floating-point atomics anywhere): two runs of the same
