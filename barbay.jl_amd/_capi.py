@@ -27,7 +27,7 @@ EXPORTS = [
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
-    "bb_ppc_shape", "bb_ppc_bands",
+    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -84,6 +84,16 @@ class bb_ppc_opts(C.Structure):
     ]
 
 
+BB_FREQ_MODE = {"trajectory": 0, "posterior": 1}
+
+
+class bb_freq_opts(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32), ("n_samples", C.c_int32), ("n_ppc", C.c_int32), ("n_quantiles", C.c_int32),
+        ("quantiles", _dp), ("seed", C.c_uint64),
+    ]
+
+
 class BarBayHipError(RuntimeError):
     """Raised for any non-zero status of the C ABI (the reference throws ErrorException)."""
 
@@ -136,6 +146,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_ppc_bands"):            # (A/B builds of older sources, tools/xp.py)
         lib.bb_ppc_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.bb_ppc_bands.argtypes = [vp, C.POINTER(bb_ppc_opts), _dp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "bb_freq_bands"):
+        lib.bb_freq_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.bb_freq_bands.argtypes = [vp, C.POINTER(bb_freq_opts), _dp, C.POINTER(C.c_int64)]
     return lib
 
 
@@ -401,6 +414,31 @@ class Engine:
         nout = np.zeros(n_rows, dtype=np.int64) if outside else None
         self._check(self._lib.bb_ppc_bands(self._h, C.byref(o), _ptr(bands),
                                            nout.ctypes.data_as(C.POINTER(C.c_int64)) if outside else None))
+        return bands, nout
+
+    def freq_shape(self) -> Tuple[int, int]:
+        """(n_rows, n_cols) of `freq_bands`: n_rep * (n_neutral + n_bc) rows (replicate-major, data columns: neutrals first) and
+        max_r T_r time points."""
+        n, t = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.bb_freq_shape(self._h, C.byref(n), C.byref(t)))
+        return int(n.value), int(t.value)
+
+    def freq_bands(self, quantiles: Sequence[float], mode="trajectory", n_samples: int = 1000, n_ppc: int = 10, seed: int = 0,
+                   outside: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """Bands of the frequency of every barcode at every time point (`bb_freq_bands`): bands[n_rows, n_cols, n_q, 2] (lower, upper;
+        NaN past a shorter replicate's last time point) and, with `outside`, the per-row count of observed frequencies outside the
+        band of the largest q.  mode "trajectory": the predictive trajectories f_{t+1} = f_t exp(N(s - sbar_t, sigma)) from the draws'
+        initial frequencies; "posterior" (n_ppc = 1): the posterior of the model's own frequencies exp(loglambda) / sum."""
+        q = _f64(np.atleast_1d(quantiles))
+        n_rows, n_cols = self.freq_shape()
+        o = bb_freq_opts()
+        o.mode = BB_FREQ_MODE[mode] if isinstance(mode, str) else int(mode)
+        o.n_samples, o.n_ppc, o.n_quantiles, o.seed = int(n_samples), int(n_ppc), int(q.shape[0]), int(seed)
+        o.quantiles = _ptr(q)
+        bands = np.empty((n_rows, n_cols, q.shape[0], 2))
+        nout = np.zeros(n_rows, dtype=np.int64) if outside else None
+        self._check(self._lib.bb_freq_bands(self._h, C.byref(o), _ptr(bands),
+                                            nout.ctypes.data_as(C.POINTER(C.c_int64)) if outside else None))
         return bands, nout
 
     # ---- cross-GPU leg of the resident launch (include/barbay_hip.h, bb_p2p_*) ----

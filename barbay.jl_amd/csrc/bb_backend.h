@@ -382,6 +382,18 @@ BB_KERNEL(1024, k_ppc, PpcArgs P) {
     BB_CTX;
     bb_block_ppc(cx, P, BB_GRID);
 }
+BB_KERNEL(256, k_freq_zpart, FreqArgs F) {
+    BB_CTX;
+    bb_block_freq_zpart(cx, F, BB_GRID);
+}
+BB_KERNEL(256, k_freq_zsum, FreqArgs F) {
+    BB_CTX;
+    bb_block_freq_zsum(cx, F, BB_GRID);
+}
+BB_KERNEL(1024, k_freq, FreqArgs F) {
+    BB_CTX;
+    bb_block_freq(cx, F, BB_GRID);
+}
 #ifndef BB_EMU
 // transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
 __global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {

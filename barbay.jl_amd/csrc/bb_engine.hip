@@ -15,6 +15,7 @@
 #include "bb_inst.h"
 #include "bb_hier.h"
 #include "bb_ppc.h"
+#include "bb_freq.h"
 
 #include <algorithm>
 #include <cmath>
@@ -144,7 +145,7 @@ struct bb_handle {
     size_t eps_cap = 0;
     double* dbg_buf = nullptr;
     size_t dbg_cap = 0;
-    double* ppc_buf = nullptr;         // bb_ppc_bands: parameters, tables, scratch and bands of the last call
+    double* ppc_buf = nullptr;         // bb_ppc_bands / bb_freq_bands: parameters, tables, scratch and bands of the last call
     size_t ppc_cap = 0;
     bbStream stream{};
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
@@ -2360,37 +2361,39 @@ extern "C" int bb_ppc_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_step
     return BB_OK;
 }
 
-extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, int64_t* n_outside) {
-    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
-    if (o->n_quantiles < 1 || o->n_quantiles > BB_PPC_MAX_Q) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 1..%d", BB_PPC_MAX_Q);
-    for (int i = 0; i < o->n_quantiles; ++i)
-        if (!(o->quantiles[i] >= 0.0 && o->quantiles[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
-    if (o->n_samples < 1 || o->n_ppc < 1) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples and n_ppc must be >= 1");
-    const long long K = (long long)o->n_samples * o->n_ppc;
-    if (K < 2 || K > BB_PPC_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples * n_ppc = %lld must be in 2..%d", K, BB_PPC_MAX_K);
+// option checks shared by bb_ppc_bands and bb_freq_bands; *K = n_samples n_ppc
+static int ppc_check(int32_t n_samples, int32_t n_ppc, int32_t n_q, const double* q, long long* K) {
+    if (n_q < 1 || n_q > BB_PPC_MAX_Q) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 1..%d", BB_PPC_MAX_Q);
+    for (int i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
+    if (n_samples < 1 || n_ppc < 1) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples and n_ppc must be >= 1");
+    *K = (long long)n_samples * n_ppc;
+    if (*K < 2 || *K > BB_PPC_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples * n_ppc = %lld must be in 2..%d", *K, BB_PPC_MAX_K);
+    return BB_OK;
+}
+// the caller's parameters (a multi-device handle gathers them) -> mean | sigma = softplus(omega) in the caller's layout
+static int ppc_posterior(bb_handle* h, std::vector<double>& prm) {
     const size_t D = (size_t)h->M.D;
-    // the caller's parameters (a multi-device handle gathers them) -> mean / sigma = softplus(omega) in the caller's layout
-    std::vector<double> prm(2 * D);
+    prm.resize(2 * D);
     int rc = bb_get_params(h, prm.data(), prm.data() + D);
     if (rc) return rc;
     for (size_t i = D; i < 2 * D; ++i) prm[i] = std::max(prm[i], 0.0) + log1p(exp(-fabs(prm[i])));
-    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // a group samples on shard 0 (as bb_hier_fitness)
-    BB_ENTER(dh);
-    const DevModel& M = dh->M;
-    PpcArgs P;
+    return BB_OK;
+}
+// everything of PpcArgs but the row / step counts and the device pointers: the model's shape, the blocks' caller offsets, the targets
+static int ppc_fill(const bb_handle* h, const DevModel& M, int32_t n_samples, int32_t n_ppc, long long K, int32_t n_q, const double* quantiles,
+                    uint64_t seed, PpcArgs& P) {
     memset(&P, 0, sizeof P);
     P.kind = M.kind;
     P.R = M.R;
     P.E = (M.kind == BB_MODEL_MULTIENV || M.kind == BB_MODEL_MULTIENV_REPLICATE) ? M.E : 1;
     P.nt1 = M.nt1;
     P.nb = M.nb;
-    P.n_rows = ppc_rows(h);
-    P.n_steps = ppc_steps(h);
-    P.n_samples = o->n_samples;
-    P.n_ppc = o->n_ppc;
+    P.n_samples = n_samples;
+    P.n_ppc = n_ppc;
     P.K = (int)K;
-    P.n_q = o->n_quantiles;
-    P.seed = o->seed;
+    P.n_q = n_q;
+    P.seed = seed;
     for (int r = 0; r < M.R; ++r) { P.T[r] = M.T[r]; P.off_t[r] = M.off_t[r]; P.tcum[r] = M.tcum[r]; }
     const bool hier = M.kind >= BB_MODEL_GENOTYPE;
     P.lo_spop = ppc_block(h, "s_pop");
@@ -2404,7 +2407,7 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
     // gamma = clamp(aleph - j, 0, 1), a + gamma (b - a) between the (1-based) order statistics j and j + 1
     std::vector<int> lo(2 * (size_t)P.n_q), ranks;
     for (int e = 0; e < 2 * P.n_q; ++e) {
-        const double q = o->quantiles[e >> 1];
+        const double q = quantiles[e >> 1];
         const double p = (e & 1) ? 1.0 - (1.0 - q) / 2.0 : (1.0 - q) / 2.0;
         const double aleph = (double)K * p + (1.0 - p);
         const long long j = std::min<long long>(std::max<long long>((long long)aleph, 1), K - 1);
@@ -2418,6 +2421,45 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
     P.n_tgt = (int)ranks.size();
     for (int x = 0; x < P.n_tgt; ++x) P.tgt[x] = ranks[(size_t)x];
     for (int e = 0; e < 2 * P.n_q; ++e) P.plo[e] = (int)(std::lower_bound(ranks.begin(), ranks.end(), lo[(size_t)e]) - ranks.begin());
+    return BB_OK;
+}
+// genotype model: geno_idx in the caller's mutant order (the handle keeps its own, regrouped one) into dg [nb] on the device
+static int ppc_geno(const bb_handle* h, bb_handle* dh, int* dg, PpcArgs& P) {
+    const DevModel& M = dh->M;
+    if (M.kind != BB_MODEL_GENOTYPE) return BB_OK;
+    int rc;
+    std::vector<int> gi((size_t)M.nb);
+    if ((rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, dh->stream))) return rc;
+    std::vector<int> geno = gi;
+    if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
+    if ((rc = h2d(dg, geno.data(), (size_t)M.nb * 4, dh->stream))) return rc;
+    P.geno_idx = dg;
+    return BB_OK;
+}
+// the handle's counts (its own barcode order: [B][T_r] per replicate at M.cnt_off[r])
+static int ppc_counts(bb_handle* dh, std::vector<unsigned>& c) {
+    const DevModel& M = dh->M;
+    long long cnt = 0;
+    for (int r = 0; r < M.R; ++r) cnt += (long long)M.T[r] * M.B;
+    c.resize((size_t)cnt);
+    return d2h(c.data(), M.counts, (size_t)cnt * 4, dh->stream);
+}
+
+extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, int64_t* n_outside) {
+    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
+    long long K;
+    int rc = ppc_check(o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, &K);
+    if (rc) return rc;
+    const size_t D = (size_t)h->M.D;
+    std::vector<double> prm;
+    if ((rc = ppc_posterior(h, prm))) return rc;
+    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // a group samples on shard 0 (as bb_hier_fitness)
+    BB_ENTER(dh);
+    const DevModel& M = dh->M;
+    PpcArgs P;
+    if ((rc = ppc_fill(h, M, o->n_samples, o->n_ppc, K, o->n_quantiles, o->quantiles, o->seed, P))) return rc;
+    P.n_rows = ppc_rows(h);
+    P.n_steps = ppc_steps(h);
     // grid: two workgroups per CU at most, the per-block scratch bounded to 256 MiB
     const size_t ns = (size_t)P.n_samples;
     long long nblk = std::min<long long>(P.n_rows, 2LL * dh->cus);
@@ -2434,17 +2476,7 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
     P.bands = P.par + (size_t)nblk * P.E * 2 * ns;
     P.env_idx = M.env_idx;
     if ((rc = h2d(b, prm.data(), 2 * D * 8, dh->stream))) return rc;
-    std::vector<int> geno;
-    if (M.kind == BB_MODEL_GENOTYPE) {
-        // geno_idx in the caller's mutant order (the handle keeps its own, regrouped one)
-        std::vector<int> gi((size_t)M.nb);
-        if ((rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, dh->stream))) return rc;
-        geno = gi;
-        if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
-        int* dg = (int*)(P.bands + nbands);
-        if ((rc = h2d(dg, geno.data(), (size_t)M.nb * 4, dh->stream))) return rc;
-        P.geno_idx = dg;
-    }
+    if ((rc = ppc_geno(h, dh, (int*)(P.bands + nbands), P))) return rc;
     const int nthr = 1024;
     const size_t lds = (size_t)bb_ppc_lds_doubles(P.K);
     const int npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * P.n_samples + 255) / 256, 1024));
@@ -2454,10 +2486,8 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
     if (!n_outside) return BB_OK;
     // observed log-frequency ratios outside the band of the largest q (finite ratios only: both counts > 0); the handle's counts are in
     // its own barcode order, the rows in the caller's
-    long long cnt = 0;
-    for (int r = 0; r < M.R; ++r) cnt += (long long)M.T[r] * M.B;
-    std::vector<unsigned> c((size_t)cnt);
-    if ((rc = d2h(c.data(), M.counts, (size_t)cnt * 4, dh->stream))) return rc;
+    std::vector<unsigned> c;
+    if ((rc = ppc_counts(dh, c))) return rc;
     int qx = 0;
     for (int i = 1; i < P.n_q; ++i) if (o->quantiles[i] > o->quantiles[qx]) qx = i;
     for (long long row = 0; row < P.n_rows; ++row) n_outside[row] = 0;
@@ -2476,6 +2506,113 @@ extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, i
                 const double* bd = bands + (((size_t)row * P.n_steps + t) * P.n_q + qx) * 2;
                 if (x < bd[0] || x > bd[1]) n_outside[row]++;
             }
+        }
+    }
+    return BB_OK;
+}
+
+// ---- frequency-trajectory bands (bb_freq.h) -----------------------------------------------------------------------------------
+static_assert(BB_FREQ_TRAJECTORY == BB_FREQ_MODE_TRAJECTORY && BB_FREQ_POSTERIOR == BB_FREQ_MODE_POSTERIOR, "mode numbering");
+static int freq_cols(const bb_handle* h) {
+    int n = 0;
+    for (int r = 0; r < h->M.R; ++r) n = std::max(n, h->M.T[r]);
+    return n;
+}
+
+extern "C" int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols) {
+    if (!h || !n_rows || !n_cols) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_rows = (long long)h->M.R * h->M.B;
+    *n_cols = freq_cols(h);
+    return BB_OK;
+}
+
+extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands, int64_t* n_outside) {
+    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->mode != BB_FREQ_TRAJECTORY && o->mode != BB_FREQ_POSTERIOR) return bb_fail(BB_ERR_INVALID, "mode must be BB_FREQ_TRAJECTORY or BB_FREQ_POSTERIOR");
+    long long K;
+    int rc = ppc_check(o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, &K);
+    if (rc) return rc;
+    if (o->mode == BB_FREQ_POSTERIOR && o->n_ppc != 1) return bb_fail(BB_ERR_INVALID, "BB_FREQ_POSTERIOR takes n_ppc = 1");
+    const size_t D = (size_t)h->M.D;
+    std::vector<double> prm;
+    if ((rc = ppc_posterior(h, prm))) return rc;
+    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // a group samples on shard 0 (as bb_ppc_bands)
+    BB_ENTER(dh);
+    const DevModel& M = dh->M;
+    FreqArgs F;
+    memset(&F, 0, sizeof F);
+    PpcArgs& P = F.P;
+    if ((rc = ppc_fill(h, M, o->n_samples, o->n_ppc, K, o->n_quantiles, o->quantiles, o->seed, P))) return rc;
+    P.n_rows = (long long)M.R * M.B;
+    P.n_steps = freq_cols(h);
+    F.mode = o->mode;
+    F.B = M.B;
+    F.nn = M.nn;
+    F.nchunks = (int)((M.B + BB_FREQ_CHUNK - 1) / BB_FREQ_CHUNK);
+    F.nz = o->mode == BB_FREQ_TRAJECTORY ? M.R : M.Ttot;
+    const long long lo_l = ppc_block(h, "loglambda");
+    if (lo_l < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    for (int r = 0; r < M.R; ++r) F.off_l[r] = lo_l + (long long)M.tcum[r] * M.B;
+    // grid of the row program: as k_ppc; normaliser rows in flight: their chunk partials bounded to 256 MiB
+    const size_t ns = (size_t)P.n_samples;
+    long long nblk = std::min<long long>(P.n_rows, 2LL * dh->cus);
+    while (nblk > 1 && (size_t)nblk * P.E * 2 * ns * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    int zb = F.nz;
+    while (zb > 1 && (size_t)F.nchunks * zb * ns * 8 > ((size_t)256 << 20)) zb = (zb + 1) / 2;
+    // device buffer: mean | sigma | pop [nt1][2][ns] | par [nblk][E][2][ns] | Z [Ttot][ns] | zpart [nchunks][zb][ns] | bands | geno_idx (ints)
+    const size_t nbands = (size_t)P.n_rows * P.n_steps * P.n_q * 2;
+    const size_t need = 2 * D + (size_t)P.nt1 * 2 * ns + (size_t)nblk * P.E * 2 * ns + (size_t)M.Ttot * ns + (size_t)F.nchunks * zb * ns + nbands +
+                        ((size_t)M.nb + 1) / 2 + 8;
+    if ((rc = grow(&dh->ppc_buf, &dh->ppc_cap, need))) return rc;
+    double* b = dh->ppc_buf;
+    P.mean = b;
+    P.sigma = b + D;
+    P.pop = b + 2 * D;
+    P.par = P.pop + (size_t)P.nt1 * 2 * ns;
+    F.Z = P.par + (size_t)nblk * P.E * 2 * ns;
+    F.zpart = F.Z + (size_t)M.Ttot * ns;
+    P.bands = F.zpart + (size_t)F.nchunks * zb * ns;
+    P.env_idx = M.env_idx;
+    if ((rc = h2d(b, prm.data(), 2 * D * 8, dh->stream))) return rc;
+    if ((rc = ppc_geno(h, dh, (int*)(P.bands + nbands), P))) return rc;
+    const size_t np2 = (ns + 1) / 2;
+    for (F.z0 = 0; F.z0 < F.nz; F.z0 = F.z1) {
+        F.z1 = std::min(F.nz, F.z0 + zb);
+        const size_t nzb = (size_t)(F.z1 - F.z0);
+        const int g1 = (int)std::max<size_t>(1, std::min<size_t>(((size_t)F.nchunks * nzb * np2 + 255) / 256, 65536));
+        const int g2 = (int)std::max<size_t>(1, std::min<size_t>((nzb * ns + 255) / 256, 4096));
+        if ((rc = launch(dh->stream, k_freq_zpart, g1, 256, 0, F))) return rc;
+        if ((rc = launch(dh->stream, k_freq_zsum, g2, 256, 0, F))) return rc;
+    }
+    if (o->mode == BB_FREQ_TRAJECTORY) {
+        const int npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * P.n_samples + 255) / 256, 1024));
+        if ((rc = launch(dh->stream, k_ppc_pop, npop, 256, 0, P))) return rc;
+    }
+    if ((rc = launch(dh->stream, k_freq, (int)nblk, 1024, (size_t)bb_ppc_lds_doubles(P.K), F))) return rc;
+    if ((rc = d2h(bands, P.bands, nbands * 8, dh->stream))) return rc;
+    if (!n_outside) return BB_OK;
+    // observed frequencies R_{t,b} / n_t (zero counts included) outside the band of the largest q; the handle's counts are in its own
+    // barcode order, the rows in the caller's
+    std::vector<unsigned> c;
+    if ((rc = ppc_counts(dh, c))) return rc;
+    int qx = 0;
+    for (int i = 1; i < P.n_q; ++i) if (o->quantiles[i] > o->quantiles[qx]) qx = i;
+    for (int r = 0; r < M.R; ++r) {
+        const int T = M.T[r];
+        const unsigned* cr = c.data() + M.cnt_off[r];
+        std::vector<double> n((size_t)T, 0.0);
+        for (long long bc = 0; bc < M.B; ++bc)
+            for (int t = 0; t < T; ++t) n[(size_t)t] += (double)cr[bc * T + t];
+        for (long long bc = 0; bc < M.B; ++bc) {
+            const long long col = bc < M.nn || h->perm_m.empty() ? bc : M.nn + (long long)h->perm_m[(size_t)(bc - M.nn)];
+            const long long row = (long long)r * M.B + col;
+            int64_t cnt = 0;
+            for (int t = 0; t < T; ++t) {
+                const double x = (double)cr[bc * T + t] / n[(size_t)t];
+                const double* bd = bands + (((size_t)row * P.n_steps + t) * P.n_q + qx) * 2;
+                if (x < bd[0] || x > bd[1]) cnt++;
+            }
+            n_outside[row] = cnt;
         }
     }
     return BB_OK;

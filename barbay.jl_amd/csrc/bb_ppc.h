@@ -17,6 +17,7 @@
 //                      LDS histogram (16-bit bins, two per word) per distinct prefix among the targets -- all targets resolve in the same
 //                      passes; a target whose bucket holds one element is fetched by one more pass.  Quantiles as StatsBase.quantile
 //                      (type 7): h = (K - 1) p, a + gamma (b - a) between the order statistics floor(h), floor(h) + 1.
+// The selection (bb_ppc_select) and the row's parameter table (bb_ppc_row_par) are functions of their own: bb_block_freq (bb_freq.h) calls them too.
 // Written as barrier-separated passes like the step programs, so the host emulation (BB_EMU) runs the same source.
 #pragma once
 #include "bb_block.h"
@@ -82,46 +83,158 @@ BB_DEV void bb_block_ppc_pop(BBCtx& cx, const PpcArgs& P, int nblocks) {
     }
 }
 
-// LDS: col[K] doubles | hist [BB_PPC_MAX_TGT][BB_PPC_HWORDS] u32 | state (see below)
+// LDS: col[K] doubles | hist [BB_PPC_MAX_TGT][BB_PPC_HWORDS] u32 | state (PpcSel)
 BB_HD long long bb_ppc_lds_doubles(int K) { return (long long)K + BB_PPC_MAX_TGT * BB_PPC_HWORDS / 2 + 6 * BB_PPC_MAX_TGT + 8; }
+
+// the select's LDS state behind the column
+struct PpcSel {
+    unsigned* hist;
+    unsigned long long* tpre;      // target: key prefix so far
+    unsigned long long* gpre;      // group: prefix
+    double* tval;                  // target: value once resolved
+    int* trank;                    // target: rank inside its prefix bucket
+    int* tgrp;                     // target: its group, -1 resolved
+    int* tst;                      // target: 0 active, 1 unique in its bucket (fetch), 2 whole key known
+    int* tsh;                      // target: shift its prefix ends at
+    int* sc;                       // [0] groups, [1] shift of the next digit, [2] all resolved, [3] any fetch
+};
+BB_DEV PpcSel bb_ppc_sel(double* lds, int K) {
+    PpcSel S;
+    S.hist = (unsigned*)(lds + K);
+    S.tpre = (unsigned long long*)(lds + K + BB_PPC_MAX_TGT * BB_PPC_HWORDS / 2);
+    S.gpre = S.tpre + BB_PPC_MAX_TGT;
+    S.tval = (double*)(S.gpre + BB_PPC_MAX_TGT);
+    S.trank = (int*)(S.tval + BB_PPC_MAX_TGT);
+    S.tgrp = S.trank + BB_PPC_MAX_TGT;
+    S.tst = S.tgrp + BB_PPC_MAX_TGT;
+    S.tsh = S.tst + BB_PPC_MAX_TGT;
+    S.sc = S.tsh + BB_PPC_MAX_TGT;
+    return S;
+}
+// start of a column's selection; called by every thread inside the pass that fills the column (the barrier after it is the caller's)
+BB_DEV void bb_ppc_select_reset(const PpcArgs& P, const PpcSel& S, int tid) {
+    if (tid < P.n_tgt) { S.tpre[tid] = 0; S.trank[tid] = P.tgt[tid]; S.tgrp[tid] = 0; S.tst[tid] = 0; }
+    if (tid == 0) { S.gpre[0] = 0; S.sc[0] = 1; S.sc[1] = 56; S.sc[2] = 0; S.sc[3] = 0; }
+}
+
+// The band ends out[n_q][2] of the column col[P.K] (LDS; read, never written): the order statistics P.tgt by radix select, then
+// StatsBase.quantile's interpolation.  Shared by bb_block_ppc and bb_block_freq (bb_freq.h).  Ends with a barrier.
+BB_DEV void bb_ppc_select(BBCtx& cx, const PpcArgs& P, const PpcSel& S, const double* col, double* out) {
+    unsigned* hist = S.hist;
+    unsigned long long *tpre = S.tpre, *gpre = S.gpre;
+    double* tval = S.tval;
+    int *trank = S.trank, *tgrp = S.tgrp, *tst = S.tst, *tsh = S.tsh, *sc = S.sc;
+#ifdef BB_PPC_DRAW_ONLY
+    // diagnostic build (tools/ppc_time.py, the draw-only floor): no selection, the targets read unordered entries
+    BB_PASS(cx, tid) { if (tid < P.n_tgt) tval[tid] = col[P.tgt[tid]]; }
+    BB_SYNC(cx);
+#else
+    // radix select, 8-bit digits from the top
+    for (;;) {
+        const int ng = sc[0], sh = sc[1];
+        BB_PASS(cx, tid) { for (int w = tid; w < ng * BB_PPC_HWORDS; w += cx.nthr) hist[w] = 0; }
+        BB_SYNC(cx);
+        BB_PASS(cx, tid) {
+            for (int i = tid; i < P.K; i += cx.nthr) {
+                const unsigned long long k = bb_ppc_key(col[i]);
+                const unsigned long long pre = sh == 56 ? 0ull : k >> (sh + 8);
+                int gi = 0;
+                while (gi < ng && gpre[gi] != pre) ++gi;
+                if (gi < ng) {
+                    const unsigned d = (unsigned)(k >> sh) & 255u;
+                    BB_LDS_ADD_U32(&hist[gi * BB_PPC_HWORDS + (d >> 1)], 1u << (16 * (d & 1)));
+                }
+            }
+        }
+        BB_SYNC(cx);
+        BB_PASS(cx, tid) {
+            if (tid < P.n_tgt && tst[tid] == 0) {
+                const unsigned* hg = hist + tgrp[tid] * BB_PPC_HWORDS;
+                int rk = trank[tid], d = 0;
+                unsigned c = 0;
+                for (; d < 256; ++d) {
+                    c = (hg[d >> 1] >> (16 * (d & 1))) & 0xFFFFu;
+                    if (rk < (int)c) break;
+                    rk -= (int)c;
+                }
+                trank[tid] = rk;
+                tpre[tid] = (tpre[tid] << 8) | (unsigned long long)d;
+                tsh[tid] = sh;
+                if (sh == 0) { tst[tid] = 2; tval[tid] = bb_ppc_unkey(tpre[tid]); }
+                else if (c == 1) tst[tid] = 1;
+            }
+        }
+        BB_SYNC(cx);
+        BB_PASS(cx, tid) {
+            if (tid == 0) {
+                int n = 0, fetch = 0;
+                for (int x = 0; x < P.n_tgt; ++x) {
+                    if (tst[x] != 0) { tgrp[x] = -1; fetch |= tst[x] == 1; continue; }
+                    int gi = 0;
+                    while (gi < n && gpre[gi] != tpre[x]) ++gi;
+                    if (gi == n) gpre[n++] = tpre[x];
+                    tgrp[x] = gi;
+                }
+                sc[0] = n; sc[1] = sh - 8; sc[2] = n == 0; sc[3] = fetch;
+            }
+        }
+        BB_SYNC(cx);
+        if (sc[2]) break;
+    }
+    // targets alone in their bucket: the one element with that prefix
+    if (sc[3]) {
+        BB_PASS(cx, tid) {
+            for (int i = tid; i < P.K; i += cx.nthr) {
+                const unsigned long long k = bb_ppc_key(col[i]);
+                for (int x = 0; x < P.n_tgt; ++x)
+                    if (tst[x] == 1 && (k >> tsh[x]) == tpre[x]) tval[x] = col[i];
+            }
+        }
+        BB_SYNC(cx);
+    }
+#endif
+    // band ends: StatsBase.quantile's interpolation between the two order statistics
+    BB_PASS(cx, tid) {
+        if (tid < 2 * P.n_q) {
+            const double a = tval[P.plo[tid]], b = tval[P.plo[tid] + 1], gm = P.gam[tid];
+            out[tid] = (isfinite(a) && isfinite(b)) ? a + gm * (b - a) : (1.0 - gm) * a + gm * b;
+        }
+    }
+    BB_SYNC(cx);
+}
+
+// per-sample parameters (s_j, exp(logsigma_j)) of mutant m in replicate r, every environment, into the block's scratch slice par[E][2][n_samples]
+BB_DEV void bb_ppc_row_par(BBCtx& cx, const PpcArgs& P, double* par, int r, long long m) {
+    const int ns = P.n_samples, E = P.E;
+    BB_PASS(cx, tid) {
+        for (int x = tid; x < E * ns; x += cx.nthr) {
+            const int e = x / ns, j = x % ns;
+            double s, ls;
+            if (P.kind == 0) { s = bb_ppc_param(P, P.lo_s + m, j); ls = bb_ppc_param(P, P.lo_ls + m, j); }
+            else if (P.kind == 1) { s = bb_ppc_param(P, P.lo_s + e + (long long)E * m, j); ls = bb_ppc_param(P, P.lo_ls + e + (long long)E * m, j); }
+            else {
+                const long long th = P.kind == 2 ? P.geno_idx[m] : e + (long long)E * m;
+                const long long u = P.kind == 2 ? m : e + (long long)E * m + (long long)E * P.nb * r;
+                s = bb_ppc_param(P, P.lo_s + th, j) + bb_exp(bb_ppc_param(P, P.lo_lt + u, j)) * bb_ppc_param(P, P.lo_tt + u, j);
+                ls = bb_ppc_param(P, P.lo_ls + u, j);
+            }
+            par[(long long)(2 * e) * ns + j] = s;
+            par[(long long)(2 * e + 1) * ns + j] = bb_exp(ls);
+        }
+    }
+    BB_SYNC(cx);
+}
 
 BB_DEV void bb_block_ppc(BBCtx& cx, const PpcArgs& P, int nblocks) {
     double* col = cx.lds;
-    unsigned* hist = (unsigned*)(cx.lds + P.K);
-    unsigned long long* tpre = (unsigned long long*)(cx.lds + P.K + BB_PPC_MAX_TGT * BB_PPC_HWORDS / 2);   // target: key prefix so far
-    unsigned long long* gpre = tpre + BB_PPC_MAX_TGT;          // group: prefix
-    double* tval = (double*)(gpre + BB_PPC_MAX_TGT);           // target: value once resolved
-    int* trank = (int*)(tval + BB_PPC_MAX_TGT);                // target: rank inside its prefix bucket
-    int* tgrp = trank + BB_PPC_MAX_TGT;                        // target: its group, -1 resolved
-    int* tst = tgrp + BB_PPC_MAX_TGT;                          // target: 0 active, 1 unique in its bucket (fetch), 2 whole key known
-    int* tsh = tst + BB_PPC_MAX_TGT;                           // target: shift its prefix ends at
-    int* sc = tsh + BB_PPC_MAX_TGT;                            // [0] groups, [1] shift of the next digit, [2] all resolved, [3] any fetch
+    const PpcSel S = bb_ppc_sel(cx.lds, P.K);
     const int ns = P.n_samples, E = P.E;
     double* par = P.par + (long long)cx.block * E * 2 * ns;
     for (long long row = cx.block; row < P.n_rows; row += nblocks) {
         const bool popr = row < P.R;
         const int r = popr ? (int)row : (int)((row - P.R) / P.nb);
         const long long m = popr ? 0 : (row - P.R) % P.nb;
-        // per-sample parameters of the row, every environment
-        if (!popr) {
-            BB_PASS(cx, tid) {
-                for (int x = tid; x < E * ns; x += cx.nthr) {
-                    const int e = x / ns, j = x % ns;
-                    double s, ls;
-                    if (P.kind == 0) { s = bb_ppc_param(P, P.lo_s + m, j); ls = bb_ppc_param(P, P.lo_ls + m, j); }
-                    else if (P.kind == 1) { s = bb_ppc_param(P, P.lo_s + e + (long long)E * m, j); ls = bb_ppc_param(P, P.lo_ls + e + (long long)E * m, j); }
-                    else {
-                        const long long th = P.kind == 2 ? P.geno_idx[m] : e + (long long)E * m;
-                        const long long u = P.kind == 2 ? m : e + (long long)E * m + (long long)E * P.nb * r;
-                        s = bb_ppc_param(P, P.lo_s + th, j) + bb_exp(bb_ppc_param(P, P.lo_lt + u, j)) * bb_ppc_param(P, P.lo_tt + u, j);
-                        ls = bb_ppc_param(P, P.lo_ls + u, j);
-                    }
-                    par[(long long)(2 * e) * ns + j] = s;
-                    par[(long long)(2 * e + 1) * ns + j] = bb_exp(ls);
-                }
-            }
-            BB_SYNC(cx);
-        }
+        if (!popr) bb_ppc_row_par(cx, P, par, r, m);
         for (int t = 0; t < P.n_steps; ++t) {
             double* out = P.bands + (row * P.n_steps + t) * P.n_q * 2;
             if (t >= P.T[r] - 1) {           // ragged replicate: no such step
@@ -145,87 +258,10 @@ BB_DEV void bb_block_ppc(BBCtx& cx, const PpcArgs& P, int nblocks) {
                         if (kk + 1 < k1) col[kk + 1] = fma(sd, b, mu);
                     }
                 }
-                if (tid < P.n_tgt) { tpre[tid] = 0; trank[tid] = P.tgt[tid]; tgrp[tid] = 0; tst[tid] = 0; }
-                if (tid == 0) { gpre[0] = 0; sc[0] = 1; sc[1] = 56; sc[2] = 0; sc[3] = 0; }
+                bb_ppc_select_reset(P, S, tid);
             }
             BB_SYNC(cx);
-#ifdef BB_PPC_DRAW_ONLY
-            // diagnostic build (tools/ppc_time.py, the draw-only floor): no selection, the targets read unordered entries
-            BB_PASS(cx, tid) { if (tid < P.n_tgt) tval[tid] = col[P.tgt[tid]]; }
-            BB_SYNC(cx);
-#else
-            // radix select, 8-bit digits from the top
-            for (;;) {
-                const int ng = sc[0], sh = sc[1];
-                BB_PASS(cx, tid) { for (int w = tid; w < ng * BB_PPC_HWORDS; w += cx.nthr) hist[w] = 0; }
-                BB_SYNC(cx);
-                BB_PASS(cx, tid) {
-                    for (int i = tid; i < P.K; i += cx.nthr) {
-                        const unsigned long long k = bb_ppc_key(col[i]);
-                        const unsigned long long pre = sh == 56 ? 0ull : k >> (sh + 8);
-                        int gi = 0;
-                        while (gi < ng && gpre[gi] != pre) ++gi;
-                        if (gi < ng) {
-                            const unsigned d = (unsigned)(k >> sh) & 255u;
-                            BB_LDS_ADD_U32(&hist[gi * BB_PPC_HWORDS + (d >> 1)], 1u << (16 * (d & 1)));
-                        }
-                    }
-                }
-                BB_SYNC(cx);
-                BB_PASS(cx, tid) {
-                    if (tid < P.n_tgt && tst[tid] == 0) {
-                        const unsigned* hg = hist + tgrp[tid] * BB_PPC_HWORDS;
-                        int rk = trank[tid], d = 0;
-                        unsigned c = 0;
-                        for (; d < 256; ++d) {
-                            c = (hg[d >> 1] >> (16 * (d & 1))) & 0xFFFFu;
-                            if (rk < (int)c) break;
-                            rk -= (int)c;
-                        }
-                        trank[tid] = rk;
-                        tpre[tid] = (tpre[tid] << 8) | (unsigned long long)d;
-                        tsh[tid] = sh;
-                        if (sh == 0) { tst[tid] = 2; tval[tid] = bb_ppc_unkey(tpre[tid]); }
-                        else if (c == 1) tst[tid] = 1;
-                    }
-                }
-                BB_SYNC(cx);
-                BB_PASS(cx, tid) {
-                    if (tid == 0) {
-                        int n = 0, fetch = 0;
-                        for (int x = 0; x < P.n_tgt; ++x) {
-                            if (tst[x] != 0) { tgrp[x] = -1; fetch |= tst[x] == 1; continue; }
-                            int gi = 0;
-                            while (gi < n && gpre[gi] != tpre[x]) ++gi;
-                            if (gi == n) gpre[n++] = tpre[x];
-                            tgrp[x] = gi;
-                        }
-                        sc[0] = n; sc[1] = sh - 8; sc[2] = n == 0; sc[3] = fetch;
-                    }
-                }
-                BB_SYNC(cx);
-                if (sc[2]) break;
-            }
-            // targets alone in their bucket: the one element with that prefix
-            if (sc[3]) {
-                BB_PASS(cx, tid) {
-                    for (int i = tid; i < P.K; i += cx.nthr) {
-                        const unsigned long long k = bb_ppc_key(col[i]);
-                        for (int x = 0; x < P.n_tgt; ++x)
-                            if (tst[x] == 1 && (k >> tsh[x]) == tpre[x]) tval[x] = col[i];
-                    }
-                }
-                BB_SYNC(cx);
-            }
-#endif
-            // band ends: StatsBase.quantile's interpolation between the two order statistics
-            BB_PASS(cx, tid) {
-                if (tid < 2 * P.n_q) {
-                    const double a = tval[P.plo[tid]], b = tval[P.plo[tid] + 1], gm = P.gam[tid];
-                    out[tid] = (isfinite(a) && isfinite(b)) ? a + gm * (b - a) : (1.0 - gm) * a + gm * b;
-                }
-            }
-            BB_SYNC(cx);
+            bb_ppc_select(cx, P, S, col, out);
         }
     }
 }

@@ -13,9 +13,12 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
     logfreq_ratio_popmean_ppc, logfreq_ratio_multienv_ppc         posterior samples (numpy's Generator: Julia's stream is not matched)
     logfreq_ratio_ppc_bands                                       the same bands for every barcode and time step in one device call
                                                                   (`bb_ppc_bands`), from the ADVI frame itself
+    freq_ppc_bands                                                the bands of the frequency trajectories (freq_bc_ppc) of every barcode,
+                                                                  neutrals included, in one device call (`bb_freq_bands`)
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -218,24 +221,11 @@ def logfreq_ratio_multienv_ppc(df: pd.DataFrame, n_ppc: int, envs: Sequence, *, 
     return _flat(out, flatten)
 
 
-def logfreq_ratio_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
-                            quantiles: Sequence[float] = (0.95, 0.675, 0.05), n_samples: int = 1000, n_ppc: int = 10, seed: int = 0,
-                            id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
-                            rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
-                            device: int = 0) -> pd.DataFrame:
-    """The guide's validation workflow (docs/src/index.md:398-580) for EVERY barcode and time step in one device call (`bb_ppc_bands`).
-
-    `df_advi` is what `vi.advi` returned for `data` and `model`: its first D rows (the variational parameters, in the model's
-    order) give the posterior N(mean, std).  Each (row, step) gets n_samples posterior draws x n_ppc predictive draws of the
-    log-frequency ratio; the bands are `matrix_quantile_range` of those K = n_samples n_ppc values (K <= 16384).
-
-    Returns a tidy frame, one line per (row, step, quantile): `id` ("neutral" for the population-mean row, else the barcode),
-    `rep` ("R1", ...), `env` (the later time point's environment; None without environments), `time` (the later time point's index,
-    1 .. T_r - 1), `quantile`, `lower`, `upper`, and `n_outside`: the row's finite observed ratios outside its widest band (per row,
-    repeated on its lines) -- sort by it to rank the barcodes the fit does not explain."""
+@contextmanager
+def _engine_at_fit(data: pd.DataFrame, df_advi: pd.DataFrame, model, model_kwargs: Optional[Dict], seed: int, device: int, cols: Dict):
+    """An engine for `model` on `data` holding the variational parameters of `df_advi` (what `vi.advi` returned for the same data and
+    model: its first D rows, in the model's order): (engine, model instance, DataArrays, model name)."""
     from . import vi
-    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
-                env_col=env_col, genotype_col=genotype_col)
     mname = getattr(model, "__name__", str(model))
     model_kwargs = dict(model_kwargs or {})
     arrays = utils.data_to_arrays(data, **cols)
@@ -254,12 +244,37 @@ def logfreq_ratio_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model,
         mu = df_advi["mean"].to_numpy(dtype=np.float64)[:D]
         sd = np.maximum(df_advi["std"].to_numpy(dtype=np.float64)[:D], np.finfo(np.float64).tiny)
         e.set_params(mu, sd + np.log(-np.expm1(-sd)))                   # omega = softplus^-1(std)
+        yield e, bayes_model, arrays, mname
+
+
+def _envs_per_rep(arrays, mname: str, R: int):
+    envs = arrays.envs
+    has_env = "multienv" in mname
+    return has_env, (envs if (has_env and isinstance(envs, list) and envs and isinstance(envs[0], (list, tuple))) else [envs] * R)
+
+
+def logfreq_ratio_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                            quantiles: Sequence[float] = (0.95, 0.675, 0.05), n_samples: int = 1000, n_ppc: int = 10, seed: int = 0,
+                            id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                            rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                            device: int = 0) -> pd.DataFrame:
+    """The guide's validation workflow (docs/src/index.md:398-580) for EVERY barcode and time step in one device call (`bb_ppc_bands`).
+
+    `df_advi` is what `vi.advi` returned for `data` and `model`: its first D rows (the variational parameters, in the model's
+    order) give the posterior N(mean, std).  Each (row, step) gets n_samples posterior draws x n_ppc predictive draws of the
+    log-frequency ratio; the bands are `matrix_quantile_range` of those K = n_samples n_ppc values (K <= 16384).
+
+    Returns a tidy frame, one line per (row, step, quantile): `id` ("neutral" for the population-mean row, else the barcode),
+    `rep` ("R1", ...), `env` (the later time point's environment; None without environments), `time` (the later time point's index,
+    1 .. T_r - 1), `quantile`, `lower`, `upper`, and `n_outside`: the row's finite observed ratios outside its widest band (per row,
+    repeated on its lines) -- sort by it to rank the barcodes the fit does not explain."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
         bands, nout = e.ppc_bands(quantiles, n_samples=n_samples, n_ppc=n_ppc, seed=seed)
     n_rows, n_steps, n_q, _ = bands.shape
     R, nb = len(bayes_model.counts), bayes_model.n_bc
-    envs = arrays.envs
-    has_env = "multienv" in mname
-    per_env = (envs if (has_env and isinstance(envs, list) and envs and isinstance(envs[0], (list, tuple))) else [envs] * R)
+    has_env, per_env = _envs_per_rep(arrays, mname, R)
     row = np.arange(n_rows)
     rep = np.where(row < R, row, (row - R) // max(nb, 1))
     ids = np.asarray(["neutral"] * R + [b for _ in range(R) for b in arrays.bc_ids], dtype=object)
@@ -277,3 +292,56 @@ def logfreq_ratio_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model,
         "n_outside": nout[rr],
     })
     return out
+
+
+def freq_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, mode: str = "trajectory", model_kwargs: Optional[Dict] = None,
+                   quantiles: Sequence[float] = (0.95, 0.675, 0.05), n_samples: int = 1000, n_ppc: Optional[int] = None, seed: int = 0,
+                   id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                   rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                   device: int = 0) -> pd.DataFrame:
+    """The observed frequency trajectory of EVERY barcode, neutrals included, against what the fit predicts (`bb_freq_bands`).
+
+    mode "trajectory": `freq_bc_ppc` (src/stats.jl:152-213) for all barcodes at once -- from each of n_samples posterior draws the
+    initial frequency exp(loglambda) / sum exp(loglambda) of the draw, then n_ppc (default 10) trajectories
+    f_{t+1} = f_t exp(N(s - sbar_t, sigma)); the errors accumulate over time, so a barcode may leave these bands while every single
+    step stays inside its `logfreq_ratio_ppc_bands` band.  mode "posterior" (n_ppc = 1): the posterior of the model's own frequencies
+    at every time point.  `df_advi` as for `logfreq_ratio_ppc_bands`; K = n_samples n_ppc <= 16384.
+
+    Returns a tidy frame, one line per (barcode, time point, quantile): `id`, `neutral`, `rep` ("R1", ...), `env` (the time point's
+    environment; None without environments), `time` (0-based index of the time point), `quantile`, `lower`, `upper`, `observed`
+    (count / total of the time point) and `n_outside`: the barcode's time points whose observed frequency lies outside its widest band
+    (per barcode and replicate, repeated on its lines) -- sort by it to rank the barcodes the fit does not explain."""
+    if mode not in ("trajectory", "posterior"):
+        raise BarBayError('mode must be "trajectory" or "posterior"')
+    if n_ppc is None:
+        n_ppc = 10 if mode == "trajectory" else 1
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        bands, nout = e.freq_bands(quantiles, mode=mode, n_samples=n_samples, n_ppc=n_ppc, seed=seed)
+    n_rows, n_cols, n_q, _ = bands.shape
+    R, nn = len(bayes_model.counts), arrays.n_neutral
+    B = n_rows // R
+    has_env, per_env = _envs_per_rep(arrays, mname, R)
+    ids = np.asarray(list(arrays.neutral_ids) + list(arrays.bc_ids), dtype=object)      # the data columns: neutrals first
+    obs = np.full((n_rows, n_cols), np.nan)
+    for r, (c, n) in enumerate(zip(bayes_model.counts, bayes_model.totals)):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            obs[r * B:(r + 1) * B, :c.shape[0]] = (np.asarray(c, dtype=np.float64) / np.asarray(n, dtype=np.float64)[:, None]).T
+    rr, tt, qq = np.meshgrid(np.arange(n_rows), np.arange(n_cols), np.arange(n_q), indexing="ij")
+    keep = np.broadcast_to((np.arange(n_cols)[None, :] < np.repeat([c.shape[0] for c in bayes_model.counts], B)[:, None])[..., None],
+                           rr.shape)
+    rr, tt, qq = rr[keep], tt[keep], qq[keep]
+    rep, col = rr // B, rr % B
+    return pd.DataFrame({
+        "id": ids[col],
+        "neutral": col < nn,
+        "rep": [f"R{r + 1}" for r in rep],
+        "env": [per_env[r][t] for r, t in zip(rep, tt)] if has_env else None,
+        "time": tt,
+        "quantile": np.asarray(quantiles, dtype=np.float64)[qq],
+        "lower": bands[..., 0][keep],
+        "upper": bands[..., 1][keep],
+        "observed": obs[rr, tt],
+        "n_outside": nout[rr],
+    })

@@ -308,6 +308,54 @@ int bb_ppc_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps);
 int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands /* [n_rows][n_steps][n_quantiles][2] */,
                  int64_t* n_outside /* [n_rows] or NULL */);
 
+/* Posterior predictive bands of the frequency TRAJECTORIES f_{t+1} = f_t exp(N(s - sbar_t, sigma)) -- BarBay.stats.freq_bc_ppc
+ * (src/stats.jl:152-213) followed by matrix_quantile_range -- and the posterior bands of the frequencies the model itself returns,
+ * F = Lambda ./ sum(Lambda, dims=2) with Lambda = exp.(logLambda) (src/model_fitness_normal.jl:209-212), for every barcode of the
+ * run at once, neutral barcodes included, from the current mean-field posterior.
+ *
+ * Rows, in the caller's order (bb_freq_shape: n_rows = n_rep (n_neutral + n_bc), n_cols = max_r T_r):
+ *   row = r B + b, B = n_neutral + n_bc, b the data column: neutrals first, then the mutants as the caller handed them over (also
+ *   where the library regrouped a genotype model).  Columns are TIME POINTS t < T_r, not steps; columns t >= T_r of a shorter
+ *   replicate are NaN.
+ *
+ * Sample j < n_samples is the joint posterior draw of bb_ppc_bands: latent i (the caller's flat index) is
+ * mu_i + sigma_i N(i, j >> 1, 0xFFFFFFE0), so at equal seed the two calls share their parameter draws.  Frequency of a draw:
+ *   F_{r,t,b,j} = exp(ll_{r,t,b,j}) / Z_{r,t,j},   Z_{r,t,j} = sum_{b' < B} exp(ll_{r,t,b',j}),
+ * ll the loglambda latent of (r, t, b) in the layout bb_get_layout reports.  Z is summed in chunks of 256 consecutive data columns,
+ * each in index order, the chunk sums then added in chunk order: the order is a function of B alone and nothing depends on the launch
+ * geometry, the launch mode, the handle's internal latent order or its device count.
+ *
+ * BB_FREQ_POSTERIOR:  column t holds the K = n_samples values F_{r,t,b,j}; n_ppc must be 1, else BB_ERR_INVALID.
+ * BB_FREQ_TRAJECTORY: K = n_samples n_ppc, k' = j n_ppc + k.  Column 0 is f_0[k'] = F_{r,0,b,j}; column t + 1 is
+ *   f_{t+1}[k'] = f_t[k'] exp(mu_j + sd_j N(row | t << 32, k' >> 1, 0xFFFFFFE2)), the product carried in f as the reference multiplies.
+ *   A neutral row has mu = -sbar_{r,t}, sd = exp(logsigmabar_{r,t}); a mutant row the (s - sbar_{r,t}, sigma) of its bb_ppc_bands row:
+ *   the environment of the later time point, theta + exp(logtau) theta_tilde for the hierarchical kinds.  sbar is replicate r's own
+ *   (no BB_FLAG_RAGGED_METHOD pairing, as in bb_ppc_bands).  A trajectory may underflow to 0 or overflow to +Inf; that is reported as
+ *   is.  Where the carried product then meets 0 * Inf the value is NaN: it orders above +Inf in its column (as numpy's sort has it),
+ *   and the band ends that touch it are NaN by the non-finite rule.
+ *
+ * Bands: bands[row][t][i][0 / 1] = the (1 - q_i) / 2 and 1 - (1 - q_i) / 2 quantiles of the column; definition, interpolation and
+ * non-finite rule as bb_ppc_bands (exact order statistics).  n_outside[row] (may be NULL): the time points t < T_r whose observed
+ * frequency R_{t,b} / n_t (zero counts included; n_t the totals the handle was created with) lies strictly outside the band of the
+ * largest q.
+ *
+ * Limits as bb_ppc_bands: 1 <= n_quantiles <= 8 and every q in [0, 1], else BB_ERR_INVALID; n_samples, n_ppc >= 1 and
+ * 2 <= K <= 16384, else BB_ERR_UNSUPPORTED; an unknown mode is BB_ERR_INVALID.  A multi-device handle (n_devices > 1) gathers the
+ * posterior onto its first device; a shard of a sharded run (world_size > 1) needs the gathered vector through bb_set_params first. */
+#define BB_FREQ_TRAJECTORY 0
+#define BB_FREQ_POSTERIOR 1
+typedef struct bb_freq_opts {
+    int32_t mode;             /* BB_FREQ_*                                             */
+    int32_t n_samples;        /* posterior samples j                                   */
+    int32_t n_ppc;            /* predictive trajectories per sample and row            */
+    int32_t n_quantiles;      /* 1 .. 8                                                */
+    const double* quantiles;  /* [n_quantiles] band masses q                           */
+    uint64_t seed;            /* Philox key                                            */
+} bb_freq_opts;
+int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols);
+int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands /* [n_rows][n_cols][n_quantiles][2] */,
+                  int64_t* n_outside /* [n_rows] or NULL */);
+
 /* The engine's normal stream for (step, stream) over latents [lo, hi), for checks. */
 int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int64_t lo, int64_t hi, double* out);
 

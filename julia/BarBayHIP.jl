@@ -213,4 +213,40 @@ function ppc_bands(h::Ptr{Cvoid}, quantiles::Vector{Float64}; n_samples::Int=100
     return bands, nout
 end
 
+# Frequency-trajectory bands (bb_freq_bands, include/barbay_hip.h): the device's freq_bc_ppc + matrix_quantile_range for every
+# barcode at once, neutrals included, or the posterior of the model's own frequencies exp(loglambda) / sum.
+# Field for field the Python binding's `bb_freq_opts` (barbay.jl_amd/_capi.py).
+const BB_FREQ_TRAJECTORY = Int32(0)
+const BB_FREQ_POSTERIOR = Int32(1)
+struct bb_freq_opts
+    mode::Int32
+    n_samples::Int32
+    n_ppc::Int32
+    n_quantiles::Int32
+    quantiles::Ptr{Float64}
+    seed::UInt64
+end
+
+"""
+    freq_bands(h, quantiles; mode=BB_FREQ_TRAJECTORY, n_samples=1000, n_ppc=10, seed=0, outside=true) -> (bands, n_outside)
+
+`h` a live `bb_handle`.  `bands[side, q, t, row]` (Julia order of the C array [row][t][q][2]; side 1 lower, 2 upper; NaN past a
+shorter replicate's last time point); rows: data column b of replicate r at r (n_neutral + n_bc) + b (0-based), neutrals first;
+columns: time points.  `mode=BB_FREQ_POSTERIOR` takes `n_ppc=1`.  `n_outside[row]`: time points whose observed frequency lies
+outside the band of the largest q, or `nothing`.
+"""
+function freq_bands(h::Ptr{Cvoid}, quantiles::Vector{Float64}; mode::Integer=BB_FREQ_TRAJECTORY, n_samples::Int=1000,
+                    n_ppc::Int=10, seed::Integer=0, outside::Bool=true)
+    nr, nt = Ref{Int64}(0), Ref{Int32}(0)
+    check(ccall((:bb_freq_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}), h, nr, nt))
+    bands = Array{Float64}(undef, 2, length(quantiles), nt[], nr[])
+    nout = outside ? zeros(Int64, nr[]) : nothing
+    GC.@preserve quantiles begin
+        o = bb_freq_opts(Int32(mode), Int32(n_samples), Int32(n_ppc), Int32(length(quantiles)), pointer(quantiles), UInt64(seed))
+        check(ccall((:bb_freq_bands, LIB), Cint, (Ptr{Cvoid}, Ref{bb_freq_opts}, Ptr{Float64}, Ptr{Int64}),
+                    h, o, bands, outside ? nout : C_NULL))
+    end
+    return bands, nout
+end
+
 end # module
