@@ -19,13 +19,14 @@ BB_OPT_TRUNCATED_ADAGRAD = 0
 BB_OPT_DECAYED_ADAGRAD = 1
 BB_COMM_ID_BYTES = 128
 BB_P2P_HANDLE_BYTES = 64
+BB_LOGP_MAX_BATCH = 64
 BB_ERR_UNSUPPORTED = -4
 BB_ERR_NONFINITE = -5
 
 EXPORTS = [
     "bb_version", "bb_last_error", "bb_default_opts", "bb_create", "bb_destroy", "bb_num_latents",
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
-    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_get_stats", "bb_kernel_name",
+    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands",
 ]
@@ -126,6 +127,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.bb_get_posterior.argtypes = [vp, _dp, _dp]
     lib.bb_elbo_grad.argtypes = [vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]
     lib.bb_logdensity_grad.argtypes = [vp, _dp, _dp, _dp]
+    lib.bb_logdensity_grad_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     lib.bb_get_elbo_trace.argtypes = [vp, C.c_int64, C.c_int64, _dp]
     lib.bb_debug_normals.argtypes = [vp, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _dp]
     lib.bb_get_stats.argtypes = [vp, C.POINTER(bb_stats)]
@@ -382,6 +384,19 @@ class Engine:
         g = np.empty(self.D)
         self._check(self._lib.bb_logdensity_grad(self._h, _ptr(z), C.byref(lp), _ptr(g)))
         return lp.value, g
+
+    def logdensity_grad_batch(self, Z) -> Tuple[np.ndarray, np.ndarray]:
+        """log p(data, z_w) and its gradient at W <= BB_LOGP_MAX_BATCH points in one call (`bb_logdensity_grad_batch`): Z is
+        [W, D], or [D] for one point; returns (logp[W], grad[W, D]).  Each row's result is a function of that row alone."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.ndim == 1:
+            Z = Z[None, :]
+        assert Z.ndim == 2 and Z.shape[1] == self.D
+        W = Z.shape[0]
+        lp = np.empty(W)
+        g = np.empty((W, self.D))
+        self._check(self._lib.bb_logdensity_grad_batch(self._h, W, _ptr(Z), _ptr(lp), _ptr(g)))
+        return lp, g
 
     def hier_units(self) -> int:
         """Length of the theta_tilde block (0 for the non-hierarchical models)."""

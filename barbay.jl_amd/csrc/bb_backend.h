@@ -394,6 +394,24 @@ BB_KERNEL(1024, k_freq, FreqArgs F) {
     BB_CTX;
     bb_block_freq(cx, F, BB_GRID);
 }
+// bb_logdensity_grad_batch (bb_logp.h): grid = tile + n_tiles * point
+template <int KIND>
+BB_KERNEL(1024, k_logp_moments, const DevModel* __restrict__ Mp, LogpArgs B, RunArgs A, int NB) {
+    const DevModel& M = *Mp;
+    BB_CTX;
+    bb_block_logp_moments<KIND>(cx, M, B, A, NB);
+}
+template <int KIND>
+BB_KERNEL(1024, k_logp_grad, const DevModel* __restrict__ Mp, LogpArgs B, RunArgs A, int NB) {
+    const DevModel& M = *Mp;
+    BB_CTX;
+    bb_block_logp_grad<KIND>(cx, M, B, A, NB);
+}
+BB_KERNEL(256, k_logp_geno, const DevModel* __restrict__ Mp, LogpArgs B, int gsb) {
+    const DevModel& M = *Mp;
+    BB_CTX;
+    bb_block_logp_geno(cx, M, B, gsb);
+}
 #ifndef BB_EMU
 // transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
 __global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {

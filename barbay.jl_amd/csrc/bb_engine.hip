@@ -16,6 +16,7 @@
 #include "bb_hier.h"
 #include "bb_ppc.h"
 #include "bb_freq.h"
+#include "bb_logp.h"
 
 #include <algorithm>
 #include <cmath>
@@ -147,6 +148,9 @@ struct bb_handle {
     size_t dbg_cap = 0;
     double* ppc_buf = nullptr;         // bb_ppc_bands / bb_freq_bands: parameters, tables, scratch and bands of the last call
     size_t ppc_cap = 0;
+    double* logp_buf = nullptr;        // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
+    size_t logp_cap = 0;
+    std::vector<double> logp_host;     // ... and its host staging (rows padded to an even length, the handle's latent order)
     bbStream stream{};
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
     int launches_last_run = 0;
@@ -1439,6 +1443,7 @@ extern "C" void bb_destroy(bb_handle* h) {
     if (h->eps_buf) dfree(h->eps_buf);
     if (h->dbg_buf) dfree(h->dbg_buf);
     if (h->ppc_buf) dfree(h->ppc_buf);
+    if (h->logp_buf) dfree(h->logp_buf);
     stream_close(h->stream);
     delete h;
 }
@@ -2112,6 +2117,71 @@ extern "C" int bb_logdensity_grad(bb_handle* h, const double* z, double* logp, d
     int rc = bb_elbo_grad(h, z, h->ld_omega.data(), h->ld_zero.data(), 1, &elbo, grad, nullptr);
     if (rc) return rc;
     if (logp) *logp = elbo - 0.5 * (double)D * (1.0 + BB_LOG2PI) - (double)D * log(log1p(exp(om1)));
+    return BB_OK;
+}
+
+// log-joint and gradient at n_points points in one call (bb_logp.h): three launches on buffers of the handle's own, the
+// variational state untouched.  Caller's order <-> the handle's order once per batch, on the host.
+extern "C" int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z, double* logp, double* grad) {
+    if (!h || !z) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (n_points < 1 || n_points > BB_LOGP_MAX_BATCH) return bb_fail(BB_ERR_INVALID, "n_points = %d is outside 1 .. %d", (int)n_points, BB_LOGP_MAX_BATCH);
+    BB_GROUP_UNSUPPORTED(h, "bb_logdensity_grad_batch");
+    if (h->o.world_size > 1) return bb_fail(BB_ERR_UNSUPPORTED, "bb_logdensity_grad_batch is not available on a sharded handle (world_size > 1)");
+    BB_ENTER(h);
+    const DevModel& M = h->M;
+    const size_t W = (size_t)n_points, D = (size_t)M.D, Dz = (D + 1) & ~(size_t)1, Wp = (W + 1) & ~(size_t)1;
+    const bool geno = M.kind == BB_MODEL_GENOTYPE;
+    const size_t nbs = geno ? ((size_t)M.nb + 1) & ~(size_t)1 : 0, Gs = geno ? ((size_t)M.G + 1) & ~(size_t)1 : 0;
+    const size_t n_part = (W * (size_t)M.K * (size_t)h->nblk + 1) & ~(size_t)1, n_zg = W * 2 * (size_t)M.nt1;
+    int rc;
+    if ((rc = grow(&h->logp_buf, &h->logp_cap, 2 * W * Dz + Wp + n_part + n_zg + W * (nbs + Gs)))) return rc;
+    double* dz = h->logp_buf;
+    LogpArgs B{};
+    B.z = dz;
+    B.grad = dz + W * Dz;
+    B.logp = B.grad + W * Dz;                          // (behind the gradients: one copy brings both back)
+    B.part = B.logp + Wp;
+    B.zg = B.part + n_part;
+    B.ds = B.zg + n_zg;
+    B.gsum = B.ds + W * nbs;
+    B.Dz = (long long)Dz; B.nbs = (long long)nbs; B.Gs = (long long)Gs;
+    B.nt = h->nblk; B.W = n_points;
+    B.c0 = h->elbo_const - 0.5 * (double)M.D * (1.0 + BB_LOG2PI);      // (the ELBO's constant carries the entropy's: not part of the log-joint)
+    const bool direct = h->cidx.empty() && Dz == D;    // rows can be copied as they are
+    if (!direct) {
+        h->logp_host.resize(W * Dz + Wp);
+        for (size_t w = 0; w < W; ++w) {
+            double* row = h->logp_host.data() + w * Dz;
+            if (h->cidx.empty()) memcpy(row, z + w * D, D * 8);
+            else perm_gather(h, z + w * D, row);
+            if (Dz > D) row[D] = 0.0;
+        }
+    }
+    if ((rc = h2d(dz, direct ? z : h->logp_host.data(), W * Dz * 8, h->stream))) return rc;
+    const RunArgs A = make_args(h, 0, 0, 1, false, true);
+    const int grid = h->nblk * n_points;
+    by_kind(M.kind, [&](auto kindc) {
+        constexpr int KIND = decltype(kindc)::value;
+        rc = launch(h->stream, k_logp_moments<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
+        if (!rc) rc = launch(h->stream, k_logp_grad<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
+    });
+    if (rc) return rc;
+    if (geno) {
+        const int gsb = (int)std::min<long long>((M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block (as k_geno_sum)
+        if ((rc = launch(h->stream, k_logp_geno, gsb * n_points, 256, 256, desc_ptr(h->dM, &h->M), B, gsb))) return rc;
+    }
+    if (!grad) return logp ? d2h(logp, B.logp, W * 8, h->stream) : dsync(h->stream);
+    if (direct) {
+        if ((rc = d2h(grad, B.grad, W * D * 8, h->stream))) return rc;
+        return logp ? d2h(logp, B.logp, W * 8, h->stream) : BB_OK;
+    }
+    if ((rc = d2h(h->logp_host.data(), B.grad, (W * Dz + Wp) * 8, h->stream))) return rc;
+    for (size_t w = 0; w < W; ++w) {
+        const double* row = h->logp_host.data() + w * Dz;
+        if (h->cidx.empty()) memcpy(grad + w * D, row, D * 8);
+        else perm_scatter(h, row, grad + w * D);
+    }
+    if (logp) memcpy(logp, h->logp_host.data() + W * Dz, W * 8);
     return BB_OK;
 }
 

@@ -3,7 +3,8 @@
 The reference samples the Turing model with NUTS (`Turing.NUTS(0.65)`, `Turing.sample(model, sampler, ensemble,
 n_steps, n_walkers)`) and saves the chain.  Here the sampler is a host-side NUTS (Hoffman & Gelman 2014, algorithm 6:
 slice variant, dual-averaging step size, diagonal metric) whose every leapfrog asks the engine for
-log p(data, z) and its gradient (`bb_logdensity_grad`: the same fused kernels as the ADVI step, draw pinned to z).
+log p(data, z) and its gradient (`bb_logdensity_grad`: the same fused kernels as the ADVI step, draw pinned to z; with
+`ensemble="batched"` the walkers run in lock-step on `bb_logdensity_grad_batch`, one call per round for all of them).
 The metric and the start point come from a short ADVI run on the same handle (q's sigma^2 and mean): the
 variational fit costs a few thousand device steps and spares NUTS its longest warm-up phase.
 
@@ -16,21 +17,25 @@ from __future__ import annotations
 
 import logging
 import os
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, Optional, Sequence
 
 import numpy as np
 
 from . import utils
 from . import vi as _vi
+from ._capi import BB_LOGP_MAX_BATCH
 from .model import BarBayError, BayesModel
 
 log = logging.getLogger("barbay")
 
 
-def _leapfrog(f, z, r, g, eps, minv):
+# The sampler asks for the log-density at one point at a time.  Its body is written as generators that YIELD the point and are
+# resumed with (logp, grad): `nuts` answers each request at once, `nuts_ensemble` collects the requests of all its walkers and
+# answers them with one batched evaluation per round.  Both run the same arithmetic in the same order.
+def _leapfrog(z, r, g, eps, minv):
     r = r + 0.5 * eps * g
     z = z + eps * minv * r
-    lp, g = f(z)
+    lp, g = yield z
     r = r + 0.5 * eps * g
     return z, r, lp, g
 
@@ -40,35 +45,35 @@ def _energy(lp, r, minv):
     return h if np.isfinite(h) else -np.inf
 
 
-def _find_step(f, z, lp, g, minv, rng):
+def _find_step(z, lp, g, minv, rng):
     """Heuristic initial step size (Hoffman & Gelman, algorithm 4)."""
     eps = 1.0
     r = rng.standard_normal(z.shape[0]) / np.sqrt(minv)
     h0 = _energy(lp, r, minv)
-    _, r1, lp1, _ = _leapfrog(f, z, r, g, eps, minv)
+    _, r1, lp1, _ = yield from _leapfrog(z, r, g, eps, minv)
     a = 1.0 if _energy(lp1, r1, minv) - h0 > np.log(0.5) else -1.0
     for _ in range(60):
-        _, r1, lp1, _ = _leapfrog(f, z, r, g, eps, minv)
+        _, r1, lp1, _ = yield from _leapfrog(z, r, g, eps, minv)
         if a * (_energy(lp1, r1, minv) - h0) <= -a * np.log(2.0):
             break
         eps *= 2.0 ** a
     return eps
 
 
-def _build_tree(f, z, r, g, logu, v, j, eps, h0, minv, rng):
+def _build_tree(z, r, g, logu, v, j, eps, h0, minv, rng):
     if j == 0:
-        z1, r1, lp1, g1 = _leapfrog(f, z, r, g, v * eps, minv)
+        z1, r1, lp1, g1 = yield from _leapfrog(z, r, g, v * eps, minv)
         h1 = _energy(lp1, r1, minv)
         n1 = int(logu <= h1)
         s1 = logu < 1000.0 + h1
         alpha = min(1.0, float(np.exp(min(0.0, h1 - h0)))) if np.isfinite(h1) else 0.0
         return z1, r1, g1, z1, r1, g1, z1, lp1, g1, n1, s1, alpha, 1
-    zm, rm, gm, zp, rp, gp, z1, lp1, g1, n1, s1, a1, na1 = _build_tree(f, z, r, g, logu, v, j - 1, eps, h0, minv, rng)
+    zm, rm, gm, zp, rp, gp, z1, lp1, g1, n1, s1, a1, na1 = yield from _build_tree(z, r, g, logu, v, j - 1, eps, h0, minv, rng)
     if s1:
         if v < 0:
-            zm, rm, gm, _, _, _, z2, lp2, g2, n2, s2, a2, na2 = _build_tree(f, zm, rm, gm, logu, v, j - 1, eps, h0, minv, rng)
+            zm, rm, gm, _, _, _, z2, lp2, g2, n2, s2, a2, na2 = yield from _build_tree(zm, rm, gm, logu, v, j - 1, eps, h0, minv, rng)
         else:
-            _, _, _, zp, rp, gp, z2, lp2, g2, n2, s2, a2, na2 = _build_tree(f, zp, rp, gp, logu, v, j - 1, eps, h0, minv, rng)
+            _, _, _, zp, rp, gp, z2, lp2, g2, n2, s2, a2, na2 = yield from _build_tree(zp, rp, gp, logu, v, j - 1, eps, h0, minv, rng)
         if n2 > 0 and rng.random() < n2 / max(n1 + n2, 1):
             z1, lp1, g1 = z2, lp2, g2
         dz = zp - zm
@@ -79,19 +84,17 @@ def _build_tree(f, z, r, g, logu, v, j, eps, h0, minv, rng):
     return zm, rm, gm, zp, rp, gp, z1, lp1, g1, n1, s1, a1, na1
 
 
-def nuts(f: Callable, z0: np.ndarray, n_steps: int, n_adapt: int, *, target_accept: float = 0.65,
-         minv: Optional[np.ndarray] = None, rng: Optional[np.random.Generator] = None, max_depth: int = 10):
-    """One NUTS chain on `f(z) -> (logp, grad)`.  Returns (chain[n_steps, D], logp[n_steps], info); the n_adapt
-    warm-up draws (step-size dual averaging towards `target_accept`) are not part of the returned chain, as with
-    `Turing.NUTS` (`discard_adapt = true`)."""
+def _walker(z0, n_steps, n_adapt, target_accept, minv, rng, max_depth):
+    """One NUTS chain as a generator: yields the point it needs the log-density at, is resumed with (logp, grad), and returns
+    what `nuts` returns."""
     rng = rng or np.random.default_rng()
     z = np.array(z0, dtype=np.float64)
     D = z.shape[0]
     minv = np.ones(D) if minv is None else np.asarray(minv, dtype=np.float64)
-    lp, g = f(z)
+    lp, g = yield z
     if not np.isfinite(lp):
         raise BarBayError("log density is not finite at the initial point")
-    eps = _find_step(f, z, lp, g, minv, rng)
+    eps = yield from _find_step(z, lp, g, minv, rng)
     mu, eps_bar, h_bar, gamma, t0, kappa = np.log(10.0 * eps), 1.0, 0.0, 0.05, 10.0, 0.75
     chain = np.empty((n_steps, D))
     lps = np.empty(n_steps)
@@ -108,9 +111,9 @@ def nuts(f: Callable, z0: np.ndarray, n_steps: int, n_adapt: int, *, target_acce
         while s and j < max_depth:
             v = -1 if rng.random() < 0.5 else 1
             if v < 0:
-                zm, rm, gm, _, _, _, z1, lp1, g1, n1, s1, alpha, n_alpha = _build_tree(f, zm, rm, gm, logu, v, j, eps, h0, minv, rng)
+                zm, rm, gm, _, _, _, z1, lp1, g1, n1, s1, alpha, n_alpha = yield from _build_tree(zm, rm, gm, logu, v, j, eps, h0, minv, rng)
             else:
-                _, _, _, zp, rp, gp, z1, lp1, g1, n1, s1, alpha, n_alpha = _build_tree(f, zp, rp, gp, logu, v, j, eps, h0, minv, rng)
+                _, _, _, zp, rp, gp, z1, lp1, g1, n1, s1, alpha, n_alpha = yield from _build_tree(zp, rp, gp, logu, v, j, eps, h0, minv, rng)
             if s1 and rng.random() < min(1.0, n1 / n):
                 z, lp, g = z1, lp1, g1
             n += n1
@@ -132,14 +135,59 @@ def nuts(f: Callable, z0: np.ndarray, n_steps: int, n_adapt: int, *, target_acce
     return chain, lps, {"step_size": eps, "mean_tree_depth": float(np.mean(depths)) if depths else 0.0, "n_grad": n_grad}
 
 
+def nuts(f: Callable, z0: np.ndarray, n_steps: int, n_adapt: int, *, target_accept: float = 0.65,
+         minv: Optional[np.ndarray] = None, rng: Optional[np.random.Generator] = None, max_depth: int = 10):
+    """One NUTS chain on `f(z) -> (logp, grad)`.  Returns (chain[n_steps, D], logp[n_steps], info); the n_adapt
+    warm-up draws (step-size dual averaging towards `target_accept`) are not part of the returned chain, as with
+    `Turing.NUTS` (`discard_adapt = true`)."""
+    walker = _walker(z0, n_steps, n_adapt, target_accept, minv, rng, max_depth)
+    try:
+        z = next(walker)
+        while True:
+            z = walker.send(f(z))
+    except StopIteration as done:
+        return done.value
+
+
+def nuts_ensemble(fbatch: Callable, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Generator], target_accept: float = 0.65,
+                  minv: Optional[np.ndarray] = None, max_depth: int = 10):
+    """len(z0s) NUTS chains stepped in lock-step on `fbatch(Z[W, D]) -> (logp[W], grad[W, D])`: every round collects the point
+    each unfinished walker waits for, evaluates them in ONE call and resumes the walkers.  Walkers drop out as they finish, so
+    the batch shrinks.  Walker w draws from rngs[w] only and is resumed with row w's result only, so its chain is the one
+    `nuts(f, z0s[w], ..., rng=rngs[w])` returns wherever f agrees with fbatch row by row.  `n_steps` / `n_adapt` may be sequences,
+    one value per walker.  Returns a list of `nuts` results, one per walker."""
+    W = len(z0s)
+    if len(rngs) != W:
+        raise BarBayError("nuts_ensemble needs one random generator per walker")
+    per = lambda v, w: int(v[w]) if np.ndim(v) else int(v)
+    walkers = [_walker(z0s[w], per(n_steps, w), per(n_adapt, w), target_accept, minv, rngs[w], max_depth) for w in range(W)]
+    results = [None] * W
+    pending = {w: next(walkers[w]) for w in range(W)}
+    while pending:
+        order = sorted(pending)
+        lp, g = fbatch(np.stack([pending[w] for w in order]))
+        for i, w in enumerate(order):
+            try:
+                pending[w] = walkers[w].send((float(lp[i]), np.array(g[i], dtype=np.float64)))
+            except StopIteration as done:
+                results[w] = done.value
+                del pending[w]
+    return results
+
+
 def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str], model: Callable,
                 model_kwargs: Optional[Dict] = None, id_col="barcode", time_col="time", count_col="count",
                 neutral_col="neutral", rep_col: Optional[str] = None, env_col: Optional[str] = None,
                 genotype_col: Optional[str] = None, rm_T0: bool = False, target_accept: float = 0.65,
                 n_adapt: Optional[int] = None, advi_steps: int = 3000, verbose: bool = True, seed: int = 0, device: int = 0,
-                engine_kwargs: Optional[Dict] = None):
-    """src/mcmc.jl:86-160.  `sampler = Turing.NUTS(0.65)` becomes `target_accept`; `ensemble` is serial (one device).
+                engine_kwargs: Optional[Dict] = None, ensemble: str = "serial"):
+    """src/mcmc.jl:86-160.  `sampler = Turing.NUTS(0.65)` becomes `target_accept`.  `ensemble` (the reference's
+    `MCMCSerial()` / `MCMCThreads()` / `MCMCDistributed()`, all on one device here): "serial" runs the walkers one after another,
+    all drawing from `default_rng(seed)`; "batched" steps them in lock-step, walker w drawing from `default_rng([seed, w])`, every
+    round's log-densities in one `Engine.logdensity_grad_batch` call (chunks of BB_LOGP_MAX_BATCH walkers).
     `advi_steps` > 0 preconditions NUTS with a mean-field fit on the same handle (0: unit metric, prior-mean start)."""
+    if ensemble not in ("serial", "batched"):
+        raise BarBayError(f"ensemble must be 'serial' or 'batched', not {ensemble!r}")
     fname = None if outputname is None else f"{outputname}.npz"
     if fname is not None and os.path.isfile(fname):                                # :104-106
         raise BarBayError(f"{fname} was already processed")
@@ -177,9 +225,21 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
             mean, _ = e.posterior()
             mean, minv = np.zeros_like(mean), np.ones_like(mean)
         chains, lps, infos = [], [], []
+        spread = 0.1 if advi_steps > 0 else 0.0
+        batched = []
+        if ensemble == "batched":
+            rngs = [np.random.default_rng([seed, w]) for w in range(n_walkers)]
+            z0s = [mean + np.sqrt(minv) * r.standard_normal(mean.shape[0]) * spread for r in rngs]
+            for lo in range(0, n_walkers, BB_LOGP_MAX_BATCH):
+                hi = min(lo + BB_LOGP_MAX_BATCH, n_walkers)
+                batched += nuts_ensemble(e.logdensity_grad_batch, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi],
+                                         target_accept=target_accept, minv=minv)
         for w in range(n_walkers):
-            z0 = mean + np.sqrt(minv) * rng.standard_normal(mean.shape[0]) * (0.1 if advi_steps > 0 else 0.0)
-            c, lp, info = nuts(e.logdensity_grad, z0, n_steps, n_adapt, target_accept=target_accept, minv=minv, rng=rng)
+            if ensemble == "batched":
+                c, lp, info = batched[w]
+            else:
+                z0 = mean + np.sqrt(minv) * rng.standard_normal(mean.shape[0]) * spread
+                c, lp, info = nuts(e.logdensity_grad, z0, n_steps, n_adapt, target_accept=target_accept, minv=minv, rng=rng)
             chains.append(c)
             lps.append(lp)
             infos.append(info)

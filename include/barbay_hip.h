@@ -253,6 +253,26 @@ int bb_p2p_enable(bb_handle* h, int32_t on);
  * On a sharded handle the gradient is this shard's part (global blocks replicated). */
 int bb_logdensity_grad(bb_handle* h, const double* z, double* logp, double* grad);
 
+/* The same service for n_points points in one call -- what an ensemble sampler that steps its walkers in lock-step needs
+ * (the reference's `ensemble` argument of Turing.sample, src/mcmc.jl:78-82, 151-153).  Kernels of its own (csrc/bb_logp.h)
+ * evaluate the log-joint directly at the points, on buffers of the handle's own.
+ *  - logp[w] and grad[w] are the model's log-joint, normalisers included, and its gradient at z[w]: the quantities
+ *    bb_logdensity_grad documents.  Either output may be NULL.
+ *  - They are a function of z[w] alone: bit-identical for every n_points, every slot w, every launch mode the handle was
+ *    created with, and whatever else is in the batch.  No atomics: every sum over barcodes or tiles runs in an order fixed
+ *    by the model shape and the handle's tile map (a tile's partial sums, then the tiles in tile order).
+ *  - The handle's mu, omega, optimiser state, step counter and RNG position are untouched, bitwise: a bb_run after the
+ *    call equals one on a fresh handle.
+ *  - A point whose log-joint is not finite returns that value (-Inf / NaN) in logp[w]; it is not an error and does not
+ *    disturb the other points.
+ *  - n_points outside 1 .. BB_LOGP_MAX_BATCH, or a null h / z: BB_ERR_INVALID.
+ *  - Sharded handles (world_size > 1) and multi-device handles (n_devices > 1): BB_ERR_UNSUPPORTED.
+ * All model kinds run batched, the genotype model included (its theta block in a third launch over genotypes x points);
+ * where the handle regrouped a genotype model's mutants, the points and gradients are permuted once per batch on the host. */
+#define BB_LOGP_MAX_BATCH 64
+int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z /* [n_points][D], caller's order */,
+                             double* logp /* [n_points] or NULL */, double* grad /* [n_points][D] or NULL */);
+
 /* ELBO estimates recorded by bb_run (elbo_every > 0): values of steps
  * first_step, first_step + elbo_every, ... ; NaN where not recorded/kept. */
 int bb_get_elbo_trace(bb_handle* h, int64_t first_step, int64_t n, double* out);

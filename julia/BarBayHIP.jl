@@ -249,4 +249,24 @@ function freq_bands(h::Ptr{Cvoid}, quantiles::Vector{Float64}; mode::Integer=BB_
     return bands, nout
 end
 
+# Log-joint and gradient at several points in one call (bb_logdensity_grad_batch, include/barbay_hip.h): what a sampler that
+# steps an ensemble of walkers in lock-step asks of the model (`LogDensityProblems.logdensity_and_gradient`, W points at once).
+const BB_LOGP_MAX_BATCH = 64
+"""
+    logdensity_grad_batch(h, Z) -> (logp, grad)
+
+`Z` is D x W (one point per COLUMN: Julia's column-major D x W is the ABI's [W][D]), W <= BB_LOGP_MAX_BATCH, or a vector (W = 1).
+Returns `logp` (W) and `grad` (D x W).  Column w's result is a function of `Z[:, w]` alone; the handle's variational state is untouched.
+"""
+function logdensity_grad_batch(h::Ptr{Cvoid}, Z::AbstractVecOrMat{Float64})
+    Zc = Z isa AbstractVector ? reshape(collect(Z), :, 1) : Matrix{Float64}(Z)
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    size(Zc, 1) == D || error("logdensity_grad_batch: Z must have $D rows")
+    W = size(Zc, 2)
+    logp, grad = Vector{Float64}(undef, W), Matrix{Float64}(undef, D, W)
+    check(ccall((:bb_logdensity_grad_batch, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h, W, Zc, logp, grad))
+    return logp, grad
+end
+
 end # module
