@@ -20,6 +20,9 @@ BB_OPT_DECAYED_ADAGRAD = 1
 BB_COMM_ID_BYTES = 128
 BB_P2P_HANDLE_BYTES = 64
 BB_LOGP_MAX_BATCH = 64
+BB_CHAIN_MAX_K = 16384
+BB_CHAIN_MAX_Q = 8
+BB_CHAIN_LAG_BATCH = 32
 BB_ERR_UNSUPPORTED = -4
 BB_ERR_NONFINITE = -5
 
@@ -28,7 +31,7 @@ EXPORTS = [
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
-    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands",
+    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_chain_summary",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -95,6 +98,20 @@ class bb_freq_opts(C.Structure):
     ]
 
 
+class bb_chain_opts(C.Structure):
+    _fields_ = [
+        ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("n_quantiles", C.c_int32), ("max_lag", C.c_int32),
+        ("probs", _dp), ("slab_cols", C.c_int64),
+    ]
+
+
+class bb_chain_out(C.Structure):
+    _fields_ = [
+        ("mean", _dp), ("sd", _dp), ("mcse", _dp), ("ess", _dp), ("rhat", _dp), ("quantiles", _dp),
+        ("n_lags", C.POINTER(C.c_int32)),
+    ]
+
+
 class BarBayHipError(RuntimeError):
     """Raised for any non-zero status of the C ABI (the reference throws ErrorException)."""
 
@@ -151,6 +168,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_freq_bands"):
         lib.bb_freq_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.bb_freq_bands.argtypes = [vp, C.POINTER(bb_freq_opts), _dp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "bb_chain_summary"):
+        lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     return lib
 
 
@@ -455,6 +474,33 @@ class Engine:
         self._check(self._lib.bb_freq_bands(self._h, C.byref(o), _ptr(bands),
                                             nout.ctypes.data_as(C.POINTER(C.c_int64)) if outside else None))
         return bands, nout
+
+    def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,
+                      slab_cols: int = 0) -> Dict[str, np.ndarray]:
+        """Chain diagnostics of every column of a host chain (`bb_chain_summary`): `chain` is [W, N, D], or [N, D] for one chain;
+        D need not be the model's latent count.  Returns mean, sd, mcse, ess (Geyer's initial monotone sequence), rhat (split-R-hat),
+        each [D]; quantiles [D, len(probs)] (StatsBase.quantile of the pooled draws at the probabilities `probs`); n_lags [D] (int32,
+        the lags that entered the ESS sum).  `max_lag` > 0 bounds that sum; `slab_cols` > 0 sets the columns uploaded per slab."""
+        x = np.ascontiguousarray(chain, dtype=np.float64)
+        if x.ndim == 2:
+            x = x[None, :, :]
+        if x.ndim != 3:
+            raise BarBayHipError("chain must be [n_chains, n_draws, n_cols] or [n_draws, n_cols]")
+        W, N, D = x.shape
+        p = _f64(np.atleast_1d(probs)).reshape(-1)
+        o = bb_chain_opts()
+        o.n_chains, o.n_draws, o.n_quantiles, o.max_lag, o.slab_cols = W, N, int(p.shape[0]), int(max_lag), int(slab_cols)
+        o.probs = _ptr(p) if p.shape[0] else None
+        res = {k: np.empty(D) for k in ("mean", "sd", "mcse", "ess", "rhat")}
+        res["quantiles"] = np.empty((D, p.shape[0]))
+        res["n_lags"] = np.empty(D, dtype=np.int32)
+        out = bb_chain_out()
+        for k in ("mean", "sd", "mcse", "ess", "rhat"):
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.n_lags = res["n_lags"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_chain_summary(self._h, C.byref(o), D, _ptr(x), C.byref(out)))
+        return res
 
     # ---- cross-GPU leg of the resident launch (include/barbay_hip.h, bb_p2p_*) ----
     def p2p_export(self) -> bytes:

@@ -17,6 +17,11 @@ static int dmalloc(void** p, size_t n) { *p = calloc(1, n ? n : 1); return *p ? 
 static void dfree(void* p) { free(p); }
 static int h2d(void* d, const void* h, size_t n, bbStream) { memcpy(d, h, n); return 0; }
 static int d2h(void* h, const void* d, size_t n, bbStream) { memcpy(h, d, n); return 0; }
+// `rows` rows of `width` bytes, pitches in bytes
+static int h2d_2d(void* d, size_t dpitch, const void* h, size_t hpitch, size_t width, size_t rows, bbStream) {
+    for (size_t r = 0; r < rows; ++r) memcpy((char*)d + r * dpitch, (const char*)h + r * hpitch, width);
+    return 0;
+}
 static int d2d(void* d, const void* s, size_t n, bbStream) { memcpy(d, s, n); return 0; }
 static int dzero(void* d, size_t n, bbStream) { memset(d, 0, n); return 0; }
 static int dsync(bbStream) { return 0; }
@@ -125,6 +130,12 @@ static int h2d(void* d, const void* h, size_t n, bbStream s) {
 }
 static int d2h(void* h, const void* d, size_t n, bbStream s) {
     BB_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s));
+    BB_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+// `rows` rows of `width` bytes, pitches in bytes
+static int h2d_2d(void* d, size_t dpitch, const void* h, size_t hpitch, size_t width, size_t rows, bbStream s) {
+    BB_HIP(hipMemcpy2DAsync(d, dpitch, h, hpitch, width, rows, hipMemcpyHostToDevice, s));
     BB_HIP(hipStreamSynchronize(s));
     return 0;
 }
@@ -393,6 +404,14 @@ BB_KERNEL(256, k_freq_zsum, FreqArgs F) {
 BB_KERNEL(1024, k_freq, FreqArgs F) {
     BB_CTX;
     bb_block_freq(cx, F, BB_GRID);
+}
+BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
+    BB_CTX;
+    bb_block_chain_transpose(cx, C, BB_GRID);
+}
+BB_KERNEL(BB_CHAIN_NT, k_chain_stats, ChainArgs C) {
+    BB_CTX;
+    bb_block_chain_stats(cx, C, BB_GRID);
 }
 // bb_logdensity_grad_batch (bb_logp.h): grid = tile + n_tiles * point
 template <int KIND>

@@ -16,6 +16,7 @@
 #include "bb_hier.h"
 #include "bb_ppc.h"
 #include "bb_freq.h"
+#include "bb_chain.h"
 #include "bb_logp.h"
 
 #include <algorithm>
@@ -150,6 +151,8 @@ struct bb_handle {
     size_t ppc_cap = 0;
     double* logp_buf = nullptr;        // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
     size_t logp_cap = 0;
+    double* chain_buf = nullptr;       // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
+    size_t chain_cap = 0;
     std::vector<double> logp_host;     // ... and its host staging (rows padded to an even length, the handle's latent order)
     bbStream stream{};
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
@@ -1444,6 +1447,7 @@ extern "C" void bb_destroy(bb_handle* h) {
     if (h->dbg_buf) dfree(h->dbg_buf);
     if (h->ppc_buf) dfree(h->ppc_buf);
     if (h->logp_buf) dfree(h->logp_buf);
+    if (h->chain_buf) dfree(h->chain_buf);
     stream_close(h->stream);
     delete h;
 }
@@ -2685,6 +2689,100 @@ extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands,
             n_outside[row] = cnt;
         }
     }
+    return BB_OK;
+}
+
+// ---- chain diagnostics (bb_chain.h) --------------------------------------------------------------------------------------------
+static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRIDE && BB_CHAIN_LAG_BATCH == BB_CHAIN_LAGS &&
+              2 * BB_CHAIN_MAX_Q <= BB_PPC_MAX_TGT, "bb_chain_summary limits");
+
+extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols, const double* chain, const bb_chain_out* out) {
+    if (!h || !o || !chain || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (n_cols < 1) return bb_fail(BB_ERR_INVALID, "n_cols must be >= 1");
+    if (o->n_chains < 1 || o->n_draws < 4) return bb_fail(BB_ERR_INVALID, "n_chains must be >= 1 and n_draws >= 4");
+    const int nq = o->n_quantiles;
+    if (nq < 0 || nq > BB_CHAIN_MAX_Q || (nq > 0 && !o->probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_CHAIN_MAX_Q);
+    for (int i = 0; i < nq; ++i)
+        if (!(o->probs[i] >= 0.0 && o->probs[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
+    if (o->max_lag < 0 || o->slab_cols < 0) return bb_fail(BB_ERR_INVALID, "max_lag and slab_cols must be >= 0");
+    const long long K = (long long)o->n_chains * o->n_draws;
+    if (K > BB_CHAIN_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_chains * n_draws = %lld must be <= %d", K, BB_CHAIN_MAX_K);
+    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // nothing of the model is read: a group works on its first device
+    BB_ENTER(dh);
+    ChainArgs C;
+    memset(&C, 0, sizeof C);
+    PpcArgs& P = C.P;
+    P.K = (int)K;
+    C.W = o->n_chains;
+    C.N = o->n_draws;
+    C.lag_max = o->max_lag ? std::min(o->max_lag, o->n_draws - 1) : o->n_draws - 1;
+    C.ess_cap = (double)K * log10((double)K);
+    // the select takes the order statistics and forms no bands (n_q = 0); per probability the pair of StatsBase.quantile as in
+    // ppc_fill: aleph = K p + (1 - p), j = clamp(trunc(aleph), 1, K - 1), gamma = clamp(aleph - j, 0, 1)
+    C.nq = nq;
+    std::vector<int> lo((size_t)nq), ranks;
+    for (int e = 0; e < nq; ++e) {
+        const double p = o->probs[e];
+        const double aleph = (double)K * p + (1.0 - p);
+        const long long j = std::min<long long>(std::max<long long>((long long)aleph, 1), K - 1);
+        P.gam[e] = std::min(std::max(aleph - (double)j, 0.0), 1.0);
+        lo[(size_t)e] = (int)(j - 1);
+        ranks.push_back((int)(j - 1));
+        ranks.push_back((int)j);
+    }
+    std::sort(ranks.begin(), ranks.end());
+    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+    P.n_tgt = (int)ranks.size();
+    for (int x = 0; x < P.n_tgt; ++x) P.tgt[x] = ranks[(size_t)x];
+    for (int e = 0; e < nq; ++e) P.plo[e] = (int)(std::lower_bound(ranks.begin(), ranks.end(), lo[(size_t)e]) - ranks.begin());
+    // slab: the caller's column count, or what BB_CHAIN_SLAB_BYTES of uploaded rows hold (whole transpose tiles)
+    long long ld = o->slab_cols;
+    if (!ld) {
+        ld = std::max<long long>(1, (long long)BB_CHAIN_SLAB_BYTES / (8 * K));
+        if (ld >= BB_CHAIN_TILE) ld -= ld % BB_CHAIN_TILE;
+    }
+    ld = std::min<long long>(ld, n_cols);
+    // device buffer: slab [K][ld] | transpose [ld][K] | mean, sd, mcse, ess, rhat [5][ld] | quantiles [ld][8] | n_lags [ld] (ints)
+    const size_t nres = (size_t)(5 + BB_CHAIN_QSTRIDE) * ld + ((size_t)ld + 1) / 2;
+    int rc = grow(&dh->chain_buf, &dh->chain_cap, 2 * (size_t)K * ld + nres);
+    if (rc) return rc;
+    double* slab = dh->chain_buf;
+    C.slab = slab;
+    C.colT = slab + (size_t)K * ld;
+    C.stat = C.colT + (size_t)K * ld;
+    C.quant = C.stat + 5 * ld;
+    C.nlags = (int*)(C.quant + (size_t)BB_CHAIN_QSTRIDE * ld);
+    C.ld = ld;
+    std::vector<double> res(nres);
+    double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
+#ifdef BB_CHAIN_TIMES          // diagnostics (tools/chain_summary_rate.py): the call's phases, each drained before the next starts
+    timespec ct[5];
+    double cms[4] = {0, 0, 0, 0};
+    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int) {};
+#endif
+    for (long long c0 = 0; c0 < n_cols; c0 += ld) {
+        C.sc = std::min<long long>(ld, n_cols - c0);
+        lap(0);
+        if ((rc = h2d_2d(slab, (size_t)ld * 8, chain + c0, (size_t)n_cols * 8, (size_t)C.sc * 8, (size_t)K, dh->stream))) return rc;
+        lap(1);
+        const long long tiles = ((C.sc + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE) * ((K + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE);
+        if ((rc = launch(dh->stream, k_chain_transpose, (int)std::min<long long>(tiles, 1 << 16), BB_CHAIN_TNT, BB_CHAIN_TILE * (BB_CHAIN_TILE + 1), C))) return rc;
+        lap(2);
+        if ((rc = launch(dh->stream, k_chain_stats, (int)std::min<long long>(C.sc, 1 << 20), BB_CHAIN_NT, (size_t)bb_chain_lds_doubles(P.K), C))) return rc;
+        lap(3);
+        if ((rc = d2h(res.data(), C.stat, nres * 8, dh->stream))) return rc;
+        lap(4);
+        for (int s = 0; s < 5; ++s)
+            if (outs[s]) memcpy(outs[s] + c0, res.data() + (size_t)s * ld, (size_t)C.sc * 8);
+        if (out->quantiles && nq)
+            for (long long c = 0; c < C.sc; ++c) memcpy(out->quantiles + (size_t)(c0 + c) * nq, res.data() + 5 * ld + c * BB_CHAIN_QSTRIDE, (size_t)nq * 8);
+        if (out->n_lags) memcpy(out->n_lags + c0, res.data() + (size_t)(5 + BB_CHAIN_QSTRIDE) * ld, (size_t)C.sc * 4);
+    }
+#ifdef BB_CHAIN_TIMES
+    fprintf(stderr, "[bb_chain_summary %lld x %lld, slabs of %lld] upload %.3f ms, transpose %.3f ms, stats %.3f ms, download %.3f ms\n", K, (long long)n_cols, ld, cms[0], cms[1], cms[2], cms[3]);
+#endif
     return BB_OK;
 }
 

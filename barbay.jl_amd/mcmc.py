@@ -11,7 +11,9 @@ variational fit costs a few thousand device steps and spares NUTS its longest wa
 The reference's entry point is stale (it indexes the `data_to_arrays` result as a Dict and passes `rm_T0` / `verbose`
 kwargs that function no longer has, src/mcmc.jl:120-129, 143-146); the argument list is kept, `rm_T0` is applied here.
 Output: `<outputname>.npz` with `ids`, `var_names`, `chain` (n_walkers x n_steps x D), `logp` (the reference
-writes `ids` and an MCMCChains object to `<outputname>.jld2`).
+writes `ids` and an MCMCChains object to `<outputname>.jld2`).  What MCMCChains' `summarystats` / `quantile` report for that
+object -- mean, std, MCSE, ESS, R-hat and quantiles of every parameter -- comes from the device (`bb_chain_summary`):
+`mcmc_sample(..., summary=True)` adds it to the output, `summarize` turns an output into the table.
 """
 from __future__ import annotations
 
@@ -23,7 +25,7 @@ import numpy as np
 
 from . import utils
 from . import vi as _vi
-from ._capi import BB_LOGP_MAX_BATCH
+from ._capi import BB_CHAIN_MAX_K, BB_LOGP_MAX_BATCH, Engine
 from .model import BarBayError, BayesModel
 
 log = logging.getLogger("barbay")
@@ -175,19 +177,76 @@ def nuts_ensemble(fbatch: Callable, z0s, n_steps, n_adapt, *, rngs: Sequence[np.
     return results
 
 
+SUMMARY_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)                  # MCMCChains.quantile's default q
+_SUMMARY_KEYS = (("mean", "mean"), ("std", "sd"), ("mcse", "mcse"), ("ess", "ess"), ("rhat", "rhat"))
+
+
+def _summary_arrays(engine, chain, probs, max_lag=0) -> Dict[str, np.ndarray]:
+    """`Engine.chain_summary` under the `summary_*` keys of `mcmc_sample`'s output."""
+    r = engine.chain_summary(chain, probs, max_lag=max_lag)
+    out = {f"summary_{k}": r[src] for k, src in _SUMMARY_KEYS}
+    out.update(summary_quantiles=r["quantiles"], summary_probs=np.asarray(probs, dtype=np.float64), summary_n_lags=r["n_lags"])
+    return out
+
+
+def _stream_engine(device: int = 0, _lib=None) -> Engine:
+    """The smallest handle `bb_create` accepts (a fitness model of two barcodes, one neutral, three time points), for
+    `summarize` without an engine of the caller's: `bb_chain_summary` takes its device and stream from a handle and reads nothing of
+    the handle's model, so the counts below never reach a result."""
+    return Engine("fitness", [np.array([[10, 12, 9], [11, 13, 8]], dtype=np.int64)], 2, 1, device=device, _lib=_lib)
+
+
+def summarize(out_or_path, engine: Optional[Engine] = None, *, probs: Optional[Sequence[float]] = None, max_lag: int = 0,
+              device: int = 0, _lib=None):
+    """MCMCChains' `summarystats` + `quantile` of a chain as one table: one row per `var_names` entry, columns `parameters, mean,
+    std, mcse, ess, rhat` and one `q<100 p>` per probability (`q2.5 ... q97.5`).  `out_or_path`: what `mcmc_sample` returned, or the
+    `.npz` it wrote.  `probs` None: the output's own `summary_probs`, or SUMMARY_PROBS.  The `summary_*` arrays an output carries
+    (`mcmc_sample(summary=True)`: `summary_probs`, no lag bound) are tabulated as they are where they answer the call -- `probs` None
+    or equal to `summary_probs`, `max_lag` 0; otherwise the statistics are computed from `chain` on the device
+    (`Engine.chain_summary`) through `engine`, or through a minimal handle of its own on `device`."""
+    import pandas as pd
+    out = out_or_path
+    if isinstance(out, (str, os.PathLike)):
+        path = os.fspath(out)
+        with np.load(path if os.path.isfile(path) else path + ".npz", allow_pickle=True) as z:
+            out = {k: z[k] for k in z.files}
+    stored = "summary_mean" in out and max_lag == 0 and (
+        probs is None or np.array_equal(np.asarray(probs, dtype=np.float64), np.asarray(out["summary_probs"], dtype=np.float64)))
+    probs = SUMMARY_PROBS if probs is None else probs
+    if stored:
+        s = out
+    elif engine is not None:
+        s = _summary_arrays(engine, out["chain"], probs, max_lag)
+    else:
+        with _stream_engine(device, _lib) as e:
+            s = _summary_arrays(e, out["chain"], probs, max_lag)
+    cols = {"parameters": [str(v) for v in out["var_names"]]}
+    cols.update({k: np.asarray(s[f"summary_{k}"]) for k, _ in _SUMMARY_KEYS})
+    for i, p in enumerate(np.asarray(s["summary_probs"], dtype=np.float64)):
+        cols[f"q{100.0 * p:g}"] = np.asarray(s["summary_quantiles"])[:, i]
+    return pd.DataFrame(cols)
+
+
 def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str], model: Callable,
                 model_kwargs: Optional[Dict] = None, id_col="barcode", time_col="time", count_col="count",
                 neutral_col="neutral", rep_col: Optional[str] = None, env_col: Optional[str] = None,
                 genotype_col: Optional[str] = None, rm_T0: bool = False, target_accept: float = 0.65,
                 n_adapt: Optional[int] = None, advi_steps: int = 3000, verbose: bool = True, seed: int = 0, device: int = 0,
-                engine_kwargs: Optional[Dict] = None, ensemble: str = "serial"):
+                engine_kwargs: Optional[Dict] = None, ensemble: str = "serial", summary: bool = False):
     """src/mcmc.jl:86-160.  `sampler = Turing.NUTS(0.65)` becomes `target_accept`.  `ensemble` (the reference's
     `MCMCSerial()` / `MCMCThreads()` / `MCMCDistributed()`, all on one device here): "serial" runs the walkers one after another,
     all drawing from `default_rng(seed)`; "batched" steps them in lock-step, walker w drawing from `default_rng([seed, w])`, every
     round's log-densities in one `Engine.logdensity_grad_batch` call (chunks of BB_LOGP_MAX_BATCH walkers).
-    `advi_steps` > 0 preconditions NUTS with a mean-field fit on the same handle (0: unit metric, prior-mean start)."""
+    `advi_steps` > 0 preconditions NUTS with a mean-field fit on the same handle (0: unit metric, prior-mean start).
+    `summary` adds the chain diagnostics of every parameter (`Engine.chain_summary` on the same handle) to the output under
+    `summary_mean, summary_std, summary_mcse, summary_ess, summary_rhat, summary_quantiles` (at `summary_probs`), `summary_n_lags`;
+    `summarize` tabulates them.  It needs n_steps >= 4 and n_walkers * n_steps <= 16384 (BB_CHAIN_MAX_K: one pooled column in
+    LDS), which is checked before anything is sampled."""
     if ensemble not in ("serial", "batched"):
         raise BarBayError(f"ensemble must be 'serial' or 'batched', not {ensemble!r}")
+    if summary and (n_walkers < 1 or n_steps < 4 or n_walkers * n_steps > BB_CHAIN_MAX_K):
+        raise BarBayError(f"summary=True needs n_walkers >= 1, n_steps >= 4 and n_walkers * n_steps <= {BB_CHAIN_MAX_K}, not "
+                          f"{n_walkers} x {n_steps}: sample with summary=False and summarize fewer draws")
     fname = None if outputname is None else f"{outputname}.npz"
     if fname is not None and os.path.isfile(fname):                                # :104-106
         raise BarBayError(f"{fname} was already processed")
@@ -246,11 +305,12 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
             if verbose:
                 log.info("walker %d: step size %.3g, mean tree depth %.2f, %d gradients", w + 1, info["step_size"],
                          info["mean_tree_depth"], info["n_grad"])
+        summ = _summary_arrays(e, np.stack(chains), SUMMARY_PROBS) if summary else {}
     var_names = []
     for sym, (lo, hi) in zip(bayes_model.var_symbols(), ranges):
         var_names += [f"{sym}[{x}]" for x in range(1, hi - lo + 1)]
     out = {"ids": np.asarray(arrays.bc_ids, dtype=object), "var_names": np.asarray(var_names, dtype=object),
-           "chain": np.stack(chains), "logp": np.stack(lps), "step_size": np.asarray([i["step_size"] for i in infos])}
+           "chain": np.stack(chains), "logp": np.stack(lps), "step_size": np.asarray([i["step_size"] for i in infos]), **summ}
     if fname is None:
         return out
     if verbose:

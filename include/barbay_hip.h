@@ -376,6 +376,65 @@ int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols);
 int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands /* [n_rows][n_cols][n_quantiles][2] */,
                   int64_t* n_outside /* [n_rows] or NULL */);
 
+/* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
+ * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array
+ * chain[n_chains][n_draws][n_cols] (what mcmc_sample of the host layer writes).  n_cols is any positive count, not necessarily
+ * bb_num_latents(h): derived quantities can be summarised too.  The handle supplies the device and the stream; nothing of the model
+ * is read.
+ *
+ * Per column, with x_{c,n} the draws of chain c < W = n_chains, n < N = n_draws, and K = W N:
+ *   mean, sd   pooled mean, and the corrected (/ (K - 1)) standard deviation about it, two-pass and centred (a column
+ *              1e6 + 1e-3 noise keeps its digits).
+ *   autocovariance, with m_c the mean of chain c:  a_c(t) = (1/N) sum_{n < N - t} (x_{c,n} - m_c)(x_{c,n+t} - m_c)   (biased)
+ *   variances  s2_c = a_c(0) N / (N - 1);  Wbar = mean_c s2_c;  var+ = (N - 1)/N Wbar + [W > 1] Var_c(m_c), the variance of the
+ *              chain means taken with W - 1.
+ *   ess        Geyer's initial monotone sequence (BDA3 section 11.5, Vehtari et al. 2021):
+ *              rho_t = 1 - (Wbar - mean_c a_c(t)) / var+;  P_k = rho_{2k} + rho_{2k+1};  the sum runs over k = 0, 1, ... while
+ *              P_k > 0, 2k + 1 <= N - 1 and 2k + 1 <= max_lag (max_lag = 0 means N - 1); before P_k is added it is replaced by
+ *              min(P_k, P_{k-1});  tau = -1 + 2 sum P_k;  ess = min(K / tau, K log10(K)).
+ *   n_lags     2 x (number of P_k summed).
+ *   mcse       sd / sqrt(ess).
+ *   rhat       split-R-hat: N' = floor(N / 2), every chain gives the halves [0, N') and [N - N', N) (an odd N drops the middle
+ *              draw); rhat = sqrt(var+ / Wbar) computed over those 2W chains of length N'.
+ *   quantiles  StatsBase.quantile (type 7) of the pooled K draws at each probs[i] (probabilities, NOT band masses): exact order
+ *              statistics; interpolation and non-finite rule as bb_ppc_bands (a NaN orders above +Inf).
+ *   A constant column reports its value as mean, sd = 0 exactly, ess = mcse = rhat = NaN and n_lags = 0.  A column holding a
+ *   non-finite value reports NaN for the five moment statistics and n_lags = 0, its quantiles by the non-finite rule; it
+ *   disturbs no other column and is not an error.
+ *
+ * The autocovariances are computed BB_CHAIN_LAG_BATCH lags at a time and only up to the batch that holds the truncation.
+ * Columns are uploaded in slabs of slab_cols columns (0: as many as BB_CHAIN_SLAB_BYTES of uploaded doubles hold, in whole
+ * multiples of 32) and transposed on the device.  The byte budget bounds the library's choice only: an explicit slab_cols is taken
+ * as it is (at most n_cols) and the handle then keeps 2 x 8 K slab_cols bytes of device memory for the slab and its transpose --
+ * 256 KiB a column at K = BB_CHAIN_MAX_K; what the device cannot allocate fails as BB_ERR_DEVICE and computes nothing.
+ *
+ * A column's results are a function of its K values, n_chains, n_draws, max_lag and probs alone: bit-identical whatever n_cols,
+ * the column's position, slab_cols, the grid or the other columns.  No atomics on doubles; every sum runs in an order fixed by
+ * (W, N).  The handle's mu, omega, optimiser state, step counter and RNG position are untouched, bitwise.
+ * BB_ERR_INVALID: a null h / o / chain / out; n_cols < 1; n_chains < 1; n_draws < 4; n_quantiles outside 0 .. BB_CHAIN_MAX_Q (or
+ * probs null with n_quantiles > 0); a prob outside [0, 1] or NaN; a negative max_lag or slab_cols.  BB_ERR_UNSUPPORTED:
+ * n_chains n_draws > BB_CHAIN_MAX_K (one pooled column in LDS).  A multi-device handle (n_devices > 1) works on its first device;
+ * a shard of a sharded run works as any other handle. */
+#define BB_CHAIN_MAX_K 16384
+#define BB_CHAIN_MAX_Q 8
+#define BB_CHAIN_LAG_BATCH 32
+#define BB_CHAIN_SLAB_BYTES (64 << 20)
+typedef struct bb_chain_opts {
+    int32_t n_chains;         /* W >= 1                                                */
+    int32_t n_draws;          /* N >= 4 per chain; W N <= BB_CHAIN_MAX_K               */
+    int32_t n_quantiles;      /* 0 .. BB_CHAIN_MAX_Q                                   */
+    int32_t max_lag;          /* 0 = N - 1; else the Geyer sum stops at lag <= max_lag */
+    const double* probs;      /* [n_quantiles] probabilities in [0, 1]                 */
+    int64_t slab_cols;        /* 0 = library's choice; else columns per slab, as given */
+} bb_chain_opts;
+typedef struct bb_chain_out {     /* every pointer may be NULL; [n_cols] unless noted  */
+    double *mean, *sd, *mcse, *ess, *rhat;
+    double* quantiles;        /* [n_cols][n_quantiles]                                 */
+    int32_t* n_lags;          /* lags that entered the ESS sum                         */
+} bb_chain_out;
+int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols,
+                     const double* chain /* host, [n_chains][n_draws][n_cols] */, const bb_chain_out* out);
+
 /* The engine's normal stream for (step, stream) over latents [lo, hi), for checks. */
 int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int64_t lo, int64_t hi, double* out);
 

@@ -269,4 +269,52 @@ function logdensity_grad_batch(h::Ptr{Cvoid}, Z::AbstractVecOrMat{Float64})
     return logp, grad
 end
 
+# Chain diagnostics (bb_chain_summary, include/barbay_hip.h): MCMCChains' summarystats + quantile of a host chain, on the device.
+# Field for field the Python binding's `bb_chain_opts` / `bb_chain_out` (barbay.jl_amd/_capi.py).
+const BB_CHAIN_MAX_K = 16384
+const BB_CHAIN_MAX_Q = 8
+struct bb_chain_opts
+    n_chains::Int32
+    n_draws::Int32
+    n_quantiles::Int32
+    max_lag::Int32
+    probs::Ptr{Float64}
+    slab_cols::Int64
+end
+struct bb_chain_out
+    mean::Ptr{Float64}
+    sd::Ptr{Float64}
+    mcse::Ptr{Float64}
+    ess::Ptr{Float64}
+    rhat::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    n_lags::Ptr{Int32}
+end
+
+"""
+    chain_summary(h, chain; probs=[0.025, 0.25, 0.5, 0.75, 0.975], max_lag=0, slab_cols=0) -> NamedTuple
+
+`h` a live `bb_handle` (it lends its device; nothing of its model is read).  `chain` is D x N x W (Julia order of the C array
+[n_chains][n_draws][n_cols]), or D x N for one chain; W N <= BB_CHAIN_MAX_K.  Returns `mean, sd, mcse, ess, rhat` (D each),
+`quantiles` (length(probs) x D) and `n_lags` (D): pooled mean and std, MCSE, ESS by Geyer's initial monotone sequence, split-R-hat
+and StatsBase type-7 quantiles of every column.
+"""
+function chain_summary(h::Ptr{Cvoid}, chain::AbstractArray{Float64}; probs::Vector{Float64}=[0.025, 0.25, 0.5, 0.75, 0.975],
+                       max_lag::Integer=0, slab_cols::Integer=0)
+    x = Array{Float64}(ndims(chain) == 2 ? reshape(chain, size(chain, 1), size(chain, 2), 1) : chain)
+    D, N, W = size(x)
+    nq = length(probs)
+    mean, sd, mcse, ess, rhat = (Vector{Float64}(undef, D) for _ in 1:5)
+    q = Matrix{Float64}(undef, nq, D)
+    nl = Vector{Int32}(undef, D)
+    GC.@preserve probs mean sd mcse ess rhat q nl begin
+        o = bb_chain_opts(Int32(W), Int32(N), Int32(nq), Int32(max_lag), nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL), Int64(slab_cols))
+        out = bb_chain_out(pointer(mean), pointer(sd), pointer(mcse), pointer(ess), pointer(rhat),
+                           nq > 0 ? pointer(q) : Ptr{Float64}(C_NULL), pointer(nl))
+        check(ccall((:bb_chain_summary, LIB), Cint, (Ptr{Cvoid}, Ref{bb_chain_opts}, Int64, Ptr{Float64}, Ref{bb_chain_out}),
+                    h, o, D, x, out))
+    end
+    return (mean=mean, sd=sd, mcse=mcse, ess=ess, rhat=rhat, quantiles=q, n_lags=nl)
+end
+
 end # module
