@@ -29,7 +29,7 @@ BB_ERR_NONFINITE = -5
 EXPORTS = [
     "bb_version", "bb_last_error", "bb_default_opts", "bb_create", "bb_destroy", "bb_num_latents",
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
-    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_get_stats", "bb_kernel_name",
+    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_chain_summary",
 ]
@@ -151,6 +151,7 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_kernel_name"):          # (A/B builds of older sources, tools/xp.py)
         lib.bb_kernel_name.argtypes = [vp, C.c_char_p, C.c_int64]
     lib.bb_debug_stamps.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64]
+    lib.bb_debug_graph_launches.argtypes = [vp]
     lib.bb_comm_make_id.argtypes = [C.c_void_p]
     lib.bb_comm_init.argtypes = [vp, C.c_void_p]
     lib.bb_step_moments.argtypes = [vp, _dp]
@@ -383,6 +384,10 @@ class Engine:
         if not per_wave:
             return raw[:nb * 32].reshape(nb, 32).copy()
         return raw[rows * 32:rows * 32 + nb * 64].reshape(nb, 4, 16).copy()
+
+    def graph_launches(self) -> int:
+        """hipGraphLaunch calls of the last `run` (`bb_debug_graph_launches`); 0 on a resident launch, an eager run and the emulation."""
+        return int(self._lib.bb_debug_graph_launches(self._h))
 
     def stats(self) -> Dict[str, float]:
         s = bb_stats()

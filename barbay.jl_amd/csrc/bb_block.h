@@ -522,6 +522,11 @@ BB_DEV void bb_update_pair(const DevModel& M, const DevState& S, const RunArgs& 
         S.acc_mu[i] = a0 ? am.x : am.y; S.acc_om[i] = a0 ? ao.x : ao.y;
         if (hs_m) { hs_m[i] = a0 ? nhm.x : nhm.y; hs_o[i] = a0 ? nho.x : nho.y; }
     }
+    // divergence flag, the authoritative one of the two-kernel step: on the parameters as stored, like the resident launches' epilogues.
+    // The moment totals (bb_block_update) do not see every one of them: softplus(NaN) is finite here, so a NaN omega samples a finite z
+    // and never reaches a moment.
+    const double chk = (a0 ? mu.x + om.x : 0.0) + (a1 ? mu.y + om.y : 0.0);
+    if (!(chk - chk == 0.0)) S.hstatus[1] = 1u;
 }
 
 // Deterministic sum of one LDS row of n entries: 16 partial sums, then one thread.
@@ -1075,7 +1080,8 @@ BB_DEV void bb_block_update(BBCtx& cx, const DevModel& M, const DevState& S, con
             }
             if (A.last_sample && A.apply) {
                 S.ctr[1 - A.par] = step + 1;
-                // divergence flag: a NaN / Inf anywhere in theta reaches the exchanged moment totals
+                // divergence flag on the exchanged moment totals.  Subsumed by bb_update_pair's check of the stored
+                // parameters, which a non-finite total reaches in this same step; kept, at no cost, until a change of its own retires it
                 double chk = 0.0;
                 for (int k = 0; k < M.K - 2; ++k) chk += lds[L.wk + k];
                 if (!(chk - chk == 0.0)) S.hstatus[1] = 1u;

@@ -157,6 +157,7 @@ struct bb_handle {
     bbStream stream{};
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
     int launches_last_run = 0;
+    int graph_launches = 0;            // hipGraphLaunch calls of the last bb_run (bb_debug_graph_launches)
     int64_t bytes_sample = 0, bytes_update = 0;
     BackendState be;                   // the product's graph of the step loop, run timer and communicator
     BBTuning tune{};                   // the environment switches as bb_create found them
@@ -1922,6 +1923,7 @@ static int run_graphs(bb_handle* h, int64_t n_steps, int64_t& done) {
         if ((rc = build_graph(h, gs))) return rc;
         while (h->be.graph && n_steps - done >= gs) {
             BB_HIP(hipGraphLaunch(h->be.graph, h->stream));
+            h->graph_launches++;
             h->step += gs;
             done += gs;
         }
@@ -1941,6 +1943,7 @@ static int run_enqueue(bb_handle* h, int64_t n_steps) {
     if (h->hstatus) h->hstatus[1] = 0;          // divergence flag of THIS run (nothing of this handle is in flight here)
     if ((rc = timer_start(h->be, h->stream))) return rc;
     h->launches_last_run = 0;
+    h->graph_launches = 0;
     if (h->plan.impl != IMPL_TWO_KERNEL && n_steps > 0) {
         if ((rc = launch_persistent(h, n_steps))) return rc;
         done = n_steps;
@@ -2231,6 +2234,12 @@ extern "C" int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n) {
     int rc = dsync(h->stream);
     if (rc) return rc;
     return d2h(out, h->S.stamps, (size_t)std::min(n, have) * 8, h->stream);
+}
+
+extern "C" int bb_debug_graph_launches(bb_handle* h) {
+    if (!h) return 0;
+    if (!h->shards.empty()) return bb_debug_graph_launches(h->shards[0]);
+    return h->graph_launches;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ bb_stream_kernel bb_stream_instance_ms(int kind, int nthr, int T, const char** n
     BS_CASE(0, 1024, 8) BS_CASE(1, 1024, 8) BS_CASE(2, 1024, 8) BS_CASE(3, 1024, 8) BS_CASE(4, 1024, 8)
     BS_CASE(0, 1024, 6) BS_CASE(1, 1024, 6) BS_CASE(2, 1024, 6) BS_CASE(3, 1024, 6) BS_CASE(4, 1024, 6)
     BS_CASE(2, 512, 8) BS_CASE(3, 512, 6)
+    BS_CASE(0, 1024, 4)
 #undef BS_CASE
     return nullptr;
 }

@@ -442,6 +442,10 @@ int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int64_t lo, in
  * the library was built with -DBB_STAMPS (diagnostic build, never the shipped one). */
 int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n);
 
+/* hipGraphLaunch calls of the last bb_run on this handle: 0 when the run was a resident launch or went eagerly (ELBO recording on,
+ * steps_per_graph < 0, fewer steps than one graph, or a capture that failed), and always 0 in the emulation. */
+int bb_debug_graph_launches(bb_handle* h);
+
 int bb_get_stats(bb_handle* h, bb_stats* out);
 /* The kernel bb_run launches on this handle, as text: the selected template instance with its arguments in declaration order --
  * "k_res<KIND,P,NT,XG,TT,AP,MS>" (bb_resident.h), "k_stream<KIND,NT,TT>" (bb_stream.h), "k_persist<KIND,P,NT[,XG]>" (bb_persist.h) --
