@@ -615,6 +615,7 @@ BB_DEV void bb_pass_moments(BBCtx& cx, const DevModel& M, const DevState& S, con
                 const int blq = (int)bb_umulhi((unsigned)tid, M.Tmagic[r]);
                 const int tt = tid - blq * T;
                 const int x = (tt < T - 1) ? bb_xof<KIND>(M, r, tt) : 0;
+                const double pv = (tt < T - 1) ? M.piv[M.tcum[r] + tt] : 0.0;      // the step's pivot (DevModel::piv)
                 for (int bl = blq; bl < t.nbt; bl += bstride) {
                     const double z = zl[bl * T + tt];
                     const double lam = bb_exp(z);
@@ -622,7 +623,7 @@ BB_DEV void bb_pass_moments(BBCtx& cx, const DevModel& M, const DevState& S, con
                     aS += lam;
                     if (we) el += (double)M.counts[M.cnt_off[r] + (t.b0 + bl) * T + tt] * z - lam;
                     if (tt < T - 1) {
-                        const double d = zl[bl * T + tt + 1] - z;
+                        const double d = (zl[bl * T + tt + 1] - z) - pv;
                         if (bl >= t.nshift) {
                             const double a = d - lds[L.seff + bl * X + x];
                             const double w = lds[L.weff + bl * X + x];
@@ -682,9 +683,10 @@ BB_DEV void bb_pass_moments(BBCtx& cx, const DevModel& M, const DevState& S, con
                     if (lo < t.b0) lo = t.b0;
                     if (hi > t.b0 + t.nshift) hi = t.b0 + t.nshift;
                     double s1 = 0.0, s2 = 0.0;
+                    const double pv = M.piv[M.tcum[r] + tt];
                     for (long long bb = lo; bb < hi; ++bb) {
                         const int bl = (int)(bb - t.b0);
-                        const double d = zl[bl * T + tt + 1] - zl[bl * T + tt];
+                        const double d = (zl[bl * T + tt + 1] - zl[bl * T + tt]) - pv;
                         s1 += d; s2 += d * d;
                     }
                     lds[L.wk + M.kqa[r] + 2 * w] = s1;
@@ -822,6 +824,15 @@ BB_DEV void bb_finalize_sum(BBCtx& cx, const DevModel& M, const DevState& S, con
     BB_SYNC(cx);
 }
 
+// L_{t+1} - L_t as the log of the totals' ratio: the difference of the two logs carries an absolute error of ~ u |L_t| (L_t ~ 10 .. 20),
+// which enters c_t and with it EVERY residual of the step with the same sign -- in d logp / d s_pop it adds up over all barcodes, 10 - 30
+// times what the literal oracle's log(F[t+1] / F[t]) loses (tests/_accuracy_cases.py).  The ratio S[t+1] * (1 / S[t]) is
+// good to ~ 1.5 u relative (bb_rcp, one multiply), so its log to ~ 1.5 u + u |log ratio| absolute: about a tenth of u |L_t|.
+BB_DEV double bb_dlog(const double* lds, const DevModel& M, const BBLds& L, int r, int tt) {
+    const double* S = lds + L.wk + M.kq[r] + tt;
+    return bb_log(S[1] * lds[L.invS + M.tcum[r] + tt]);
+}
+
 // Everything that depends on the totals in lds[L.wk] and the sampled global latents in lds[L.zgl] (tiny).
 template <int KIND>
 BB_DEV void bb_finalize_finish(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BBLds& L) {
@@ -840,7 +851,8 @@ BB_DEV void bb_finalize_finish(BBCtx& cx, const DevModel& M, const DevState& S, 
                 const double M0 = mm[0], M1 = mm[1], M2 = mm[2], N1 = mm[3], N2 = mm[4];
                 const double sbar = lds[L.zgl + M.off_t[r] + tt], ls = lds[L.zgl + M.nt1 + M.off_t[r] + tt];
                 const double wb = bb_exp(-2.0 * ls);
-                const double c = lds[L.Lt + j + 1] - lds[L.Lt + j] - sbar;
+                // (c_t less the step's pivot: the moments were formed from a - piv[t], DevModel::piv; r = a - c is unchanged)
+                const double c = (bb_dlog(lds, M, L, r, tt) - M.piv[j]) - sbar;
                 const double quadM = M2 - 2.0 * c * M1 + c * c * M0;
                 lds[L.cc + j] = c;
                 lds[L.wbar + j] = wb;
@@ -854,7 +866,7 @@ BB_DEV void bb_finalize_finish(BBCtx& cx, const DevModel& M, const DevState& S, 
                     // ragged method: this thread is time step tt for D_t (neutral element (tt, b) pairs index jq) and
                     // population index tt for the global gradients (pairs (t', tt) over all t')
                     const int T1 = T - 1;
-                    const double cL = lds[L.Lt + j + 1] - lds[L.Lt + j];
+                    const double cL = bb_dlog(lds, M, L, r, tt) - M.piv[j];
                     double Dn = 0.0, gs = 0.0, gls = 0.0, en = 0.0;
                     for (int q = 0; q < T1; ++q) {
                         long long lo, hi;
@@ -869,7 +881,7 @@ BB_DEV void bb_finalize_finish(BBCtx& cx, const DevModel& M, const DevState& S, 
                             bb_qrange(M, T1, q, tt, &lo, &hi);
                             const double n = (double)(hi - lo);
                             const double* aa = lds + L.wk + M.kqa[r] + 2 * (q * T1 + tt);
-                            const double cq = (lds[L.Lt + M.tcum[r] + q + 1] - lds[L.Lt + M.tcum[r] + q]) - sbar;
+                            const double cq = (bb_dlog(lds, M, L, r, q) - M.piv[M.tcum[r] + q]) - sbar;
                             const double R1 = aa[0] - n * cq, R2 = aa[1] - 2.0 * cq * aa[0] + n * cq * cq;
                             gs -= wb * R1;
                             gls += wb * R2 - n;
@@ -916,7 +928,7 @@ BB_DEV double bb_residual(const double* lds, const DevModel& M, const BBLds& L, 
     const int T = M.T[r], tc = M.tcum[r];
     if (TABLE && !(KIND == 3 && M.quirk)) return lds[L.res + NB * tc + bl * T + tt] - lds[L.cc + tc + tt];
     const double* zl = lds + L.zl + NB * tc + bl * T + tt;
-    double a = zl[1] - zl[0];
+    double a = (zl[1] - zl[0]) - M.piv[tc + tt];
     if (bl >= t.nshift) a -= lds[L.seff + bl * X + bb_xof<KIND>(M, r, tt)];
     else if (KIND == 3 && M.quirk)   // ragged method: residual against -s_pop[jq] instead of -s_pop[tt]
         a += lds[L.zgl + M.off_t[r] + bb_qj(M, T - 1, tt, t.b0 + bl)] - lds[L.zgl + M.off_t[r] + tt];

@@ -1147,6 +1147,29 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
     BB_TRY(h2d(dcounts, c32.data(), (size_t)cnt * 4, h->stream));
     M.counts = dcounts;
 
+    // the moment pivot (DevModel::piv): a function of the whole problem's counts, the same on every shard
+    std::vector<double> piv((size_t)M.Ttot, 0.0);
+    {
+        long long co = 0;
+        for (int r = 0; r < M.R; ++r) {
+            const int T = M.T[r];
+            const long long nb_ = M.nn > 0 ? M.nn : M.B;        // (no neutrals: all barcodes)
+            for (int t = 0; t + 1 < T; ++t) {
+                double s = 0.0;
+                for (long long b = 0; b < nb_; ++b)
+                    s += log((double)md->counts[co + b * T + t + 1] + 0.5) - log((double)md->counts[co + b * T + t] + 0.5);
+                piv[(size_t)(M.tcum[r] + t)] = s / (double)nb_;
+            }
+            co += (long long)T * M.B;
+        }
+    }
+    {
+        double* d = nullptr;
+        BB_TRY(dalloc(h, &d, (size_t)M.Ttot));
+        BB_TRY(h2d(d, piv.data(), (size_t)M.Ttot * 8, h->stream));
+        M.piv = d;
+    }
+
     if (has_env) {
         int* d = nullptr;
         BB_TRY(dalloc(h, &d, (size_t)M.Ttot));

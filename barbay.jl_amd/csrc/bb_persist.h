@@ -197,7 +197,7 @@ BB_DEV void bbp_residual_ahead(BBCtx& cx, const DevModel& M, int NB, const RunAr
             for (int i = tid; i < t.nbt * T; i += cx.nthr) {
                 const int bl = (int)bb_umulhi((unsigned)i, M.Tmagic[r]), tt = i - bl * T;
                 if (tt < T - 1) {
-                    double a = zl[i + 1] - zl[i];
+                    double a = (zl[i + 1] - zl[i]) - M.piv[tc + tt];
                     if (bl >= t.nshift) a -= lds[L.seff + bl * X + bb_xof<KIND>(M, r, tt)];
                     lds[L.res + NB * tc + i] = a;
                 }

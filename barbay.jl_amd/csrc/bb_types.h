@@ -57,6 +57,12 @@ struct DevModel {
     int geno_sorted;                  // 1 = geno_idx is non-decreasing: a genotype's mutants are consecutive, so tiles / shards cut at genotype
                                       // boundaries own their genotypes' theta outright (the resident launch of the genotype model needs it)
     const unsigned* counts;           // device, uint32, same indexing as loglambda minus blk_lo
+    // device [Ttot]: per (replicate, time step) the neutrals' mean log count ratio, mean_b log((R[t+1,b] + 1/2) / (R[t,b] + 1/2)) (0 at
+    // t = T - 1) -- a constant of the data close to c_t wherever the model fits it.  The block programs of bb_block.h (two-kernel step,
+    // k_persist, bb_logp.h) form a_tb - piv[t] and c_t - piv[t] instead of a_tb and c_t: the residual a - c is the same number, but the
+    // moments M1, M2, N1, N2 and the polynomials in c built from them are then of the residuals' own size instead of cancelling by
+    // |a| / sigma.  Computed from ALL neutrals in bb_create, so every shard of a problem holds the same values.
+    const double* piv;
 };
 
 #define BB_MAX_WORLD 16               // ranks of one resident multi-GPU run (one xGMI hive holds 8)

@@ -250,6 +250,9 @@ int bb_p2p_enable(bb_handle* h, int32_t on);
  * of the flat latent vector -- the `logdensity_and_gradient` service an HMC / NUTS
  * sampler needs (the reference's MCMC entry, src/mcmc.jl:86-160, samples the same
  * Turing model).  logp / grad may be NULL.  Does not touch the variational state.
+ * Accuracy: logp is good to a few 2^-53 of the SUM OF THE MAGNITUDES of its addends (R*l, lambda,
+ * lgamma(R+1), every quadratic and normaliser), not of |logp|: at posterior-like points of deep
+ * data |logp| is orders of magnitude below that sum.
  * On a sharded handle the gradient is this shard's part (global blocks replicated). */
 int bb_logdensity_grad(bb_handle* h, const double* z, double* logp, double* grad);
 

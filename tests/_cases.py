@@ -57,6 +57,12 @@ def caller_normals(e, seed, step, stream, D):
     return out
 
 
+def block_rel(got, ref, sp):
+    """(block, max|got - ref| over the block / max|ref| over the block) of the block where that figure is largest: what the
+    max-norm over the whole vector cannot show (reported next to it, not asserted; tests/_accuracy_cases.py asserts per block)."""
+    return max(((float(np.abs(got[lo:hi] - ref[lo:hi]).max() / np.abs(ref[lo:hi]).max()), n) for n, (lo, hi) in sp.offsets().items()))[::-1]
+
+
 def check_grad(e, sp, mu, om, eps):
     el, gm, go = literal.elbo_and_grad(mu, om, eps, sp)
     el2, gm2, go2 = e.elbo_grad(mu, om, eps)
@@ -354,6 +360,8 @@ def case_logdensity(lib, name):
             z = g.normal(0.0, scale, sp.D)
             lp, gr = e.logdensity_grad(z)
             lp2, gr2 = literal.logjoint_and_grad(z, sp)
+            print(name, scale, "logp rel", abs(lp - lp2) / abs(lp2), "grad rel", np.abs(gr - gr2).max() / np.abs(gr2).max(),
+                  "worst block", block_rel(gr, gr2, sp))
             assert abs(lp - lp2) <= 1e-11 * abs(lp2), (lp, lp2)
             assert np.abs(gr - gr2).max() <= 1e-9 * np.abs(gr2).max()
         mu1, om1 = e.get_params()

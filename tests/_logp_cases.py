@@ -49,7 +49,8 @@ def case_oracle(lib, name):
         assert lp.shape == (3,) and gr.shape == (3, sp.D)
         for w in range(3):
             lp2, gr2 = ref[w]
-            print(name, w, "logp rel", abs(lp[w] - lp2) / abs(lp2), "grad rel", np.abs(gr[w] - gr2).max() / np.abs(gr2).max())
+            print(name, w, "logp rel", abs(lp[w] - lp2) / abs(lp2), "grad rel", np.abs(gr[w] - gr2).max() / np.abs(gr2).max(),
+                  "worst block", _cases.block_rel(gr[w], gr2, sp))
             assert abs(lp[w] - lp2) <= 1e-11 * abs(lp2), (lp[w], lp2)
             assert np.abs(gr[w] - gr2).max() <= 1e-9 * np.abs(gr2).max()
             lp1, gr1 = e.logdensity_grad(Z[w])

@@ -48,3 +48,4 @@ def test_product_does_not_import_oracle():
             if f.endswith(".py"):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert "import oracle" not in txt and "from oracle" not in txt and "libbb_emu" not in txt, f
+                assert "mp_literal" not in txt and "mpmath" not in txt, f      # (the 50-digit reference is test infrastructure too)

@@ -22,7 +22,9 @@ def sample(lib, **kw):
 
 @pytest.fixture(scope="module")
 def run(emu_lib):
-    return sample(emu_lib, n_walkers=2, n_steps=150, outputname=None, advi_steps=1500, summary=True)
+    # 400 draws a walker: at 150 the largest R-hat of this unconverged run moved between 2.4 and 3.5 with the last bits of the gradient
+    # (another seed, or a rounding-level change in bb_logdensity_grad), around the 3.0 asserted below; at 400 it is 1.4
+    return sample(emu_lib, n_walkers=2, n_steps=400, outputname=None, advi_steps=1500, summary=True)
 
 
 def test_default_output_keys_are_unchanged(emu_lib, tmp_path):
@@ -45,8 +47,8 @@ def test_summary_arrays_equal_chain_summary(run, emu_lib):
     assert np.array_equal(run["summary_probs"], [0.025, 0.25, 0.5, 0.75, 0.975])
     D = run["chain"].shape[2]
     assert run["summary_quantiles"].shape == (D, 5) and run["summary_n_lags"].dtype == np.int32
-    assert np.isfinite(run["summary_ess"]).all() and (run["summary_ess"] > 1).all() and (run["summary_ess"] <= 300 * np.log10(300)).all()
-    assert (run["summary_rhat"] > 0.9).all() and (run["summary_rhat"] < 3.0).all()        # 150 draws a walker: not converged, but sane
+    assert np.isfinite(run["summary_ess"]).all() and (run["summary_ess"] > 1).all() and (run["summary_ess"] <= 800 * np.log10(800)).all()
+    assert (run["summary_rhat"] > 0.9).all() and (run["summary_rhat"] < 3.0).all()        # 400 draws a walker: not converged, but sane
     assert np.allclose(run["summary_mean"], run["chain"].reshape(-1, D).mean(0), rtol=1e-10, atol=1e-12)
 
 
