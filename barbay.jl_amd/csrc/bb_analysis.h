@@ -1,0 +1,503 @@
+// bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h) and bb_chain_summary (bb_chain.h).  None of them touches the step loop.
+// Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
+// hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
+
+// the handle whose device, stream and buffers a post-fit call works on: a group samples on its first shard
+static bb_handle* sampling_handle(bb_handle* h) { return h->shards.empty() ? h : h->shards[0]; }
+
+// One statement of a device buffer's layout.  A layout is a function that names every sub-buffer once, in order, as the pointer it
+// lands in and its length in doubles (an int array behind the doubles: its length rounded up to whole doubles); carve() runs it
+// once to size the buffer and once more, after the buffer has grown, to place the pointers.
+struct Carve {
+    double* base;              // nullptr: the sizing pass
+    size_t n = 0;              // doubles taken so far
+    template <class T>
+    void operator()(T*& p, size_t doubles) {
+        if (base) p = (T*)(base + n);
+        n += doubles;
+    }
+};
+template <class L>
+static int carve(DevBuf& b, L&& layout) {
+    Carve size{nullptr};
+    layout(size);
+    int rc = b.grow(size.n);
+    if (rc) return rc;
+    Carve place{b.p};
+    layout(place);
+    return BB_OK;
+}
+
+// The order statistics StatsBase.quantile takes (Statistics._quantile, alpha = beta = 1) for n probabilities of a column of K:
+// aleph = K p + (1 - p), j = clamp(trunc(aleph), 1, K - 1), gamma = clamp(aleph - j, 0, 1), a + gamma (b - a) between the (1-based)
+// order statistics j and j + 1.  P.gam[e] = gamma, P.tgt[0 .. n_tgt) = the distinct 0-based ranks in ascending order, P.plo[e] = the
+// index into tgt of entry e's lower order statistic.
+static void quantile_plan(long long K, const double* probs, int n, PpcArgs& P) {
+    std::vector<int> lo((size_t)n), ranks;
+    for (int e = 0; e < n; ++e) {
+        const double p = probs[e];
+        const double aleph = (double)K * p + (1.0 - p);
+        const long long j = std::min<long long>(std::max<long long>((long long)aleph, 1), K - 1);
+        P.gam[e] = std::min(std::max(aleph - (double)j, 0.0), 1.0);
+        lo[(size_t)e] = (int)(j - 1);
+        ranks.push_back((int)(j - 1));
+        ranks.push_back((int)j);
+    }
+    std::sort(ranks.begin(), ranks.end());
+    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+    P.n_tgt = (int)ranks.size();
+    for (int x = 0; x < P.n_tgt; ++x) P.tgt[x] = ranks[(size_t)x];
+    for (int e = 0; e < n; ++e) P.plo[e] = (int)(std::lower_bound(ranks.begin(), ranks.end(), lo[(size_t)e]) - ranks.begin());
+}
+
+// ---- derived fitness of the hierarchical models (bb_hier.h) ---------------------------------------------------------------------
+extern "C" int64_t bb_hier_units(const bb_handle* h) {
+    if (!h || h->M.kind < BB_MODEL_GENOTYPE) return 0;
+    return h->M.blk_hi[BK_TT] - h->M.blk_lo[BK_TT];
+}
+
+static int hier_fitness_raw(bb_handle* h, int32_t n_samples, uint64_t seed, double* median, double* stdv) {
+    if (!h->shards.empty()) {
+        // the whole posterior onto shard 0 (entries it does not own are dead weight there: never read by its tiles), then its sampler
+        bb_handle* s0 = h->shards[0];
+        const size_t D = (size_t)h->M.D;
+        std::vector<double> mu(D), om(D);
+        int rc = group_get_params(h, mu.data(), om.data());
+        BB_ENTER(s0);
+        if (!rc) rc = h2d(s0->S.mu, mu.data(), D * 8, s0->stream);
+        if (!rc) rc = h2d(s0->S.om, om.data(), D * 8, s0->stream);
+        return rc ? rc : hier_fitness_raw(s0, n_samples, seed, median, stdv);
+    }
+    BB_ENTER(h);
+    if (h->M.kind < BB_MODEL_GENOTYPE) return bb_fail(BB_ERR_INVALID, "bb_hier_fitness applies to the hierarchical models only");
+    if (n_samples < 2 || n_samples > 16384) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in 2..16384");
+    // (a shard of a sharded run keeps full-length parameter arrays but only its own barcodes' entries are current: the caller makes them
+    //  whole first -- bb_set_params with the gathered vector, as barbay.jl_amd.vi does -- the draws are then those of a whole-problem handle)
+    const long long n = bb_hier_units(h);
+    const size_t D = (size_t)h->M.D;
+    int rc;
+    if ((rc = ensure_scratch(h))) return rc;
+    // posterior sigma = softplus(omega) into the (free between steps) z scratch array
+    std::vector<double> om(D);
+    if ((rc = dsync(h->stream)) || (rc = d2h(om.data(), h->S.om, D * 8, h->stream))) return rc;
+    for (size_t i = 0; i < D; ++i) om[i] = host_softplus(om[i]);
+    if ((rc = h2d(h->S.zsv, om.data(), D * 8, h->stream))) return rc;
+    HierArgs H;
+    memset(&H, 0, sizeof H);
+    H.mean = h->S.mu;
+    H.sigma = h->S.zsv;
+    H.median_out = h->S.asv;           // n <= D: scratch arrays are free between steps
+    H.std_out = h->S.hsv;
+    H.n_units = n;
+    H.lo_theta = h->M.blk_lo[BK_S];
+    H.lo_tt = h->M.blk_lo[BK_TT];
+    H.lo_lt = h->M.blk_lo[BK_LT];
+    H.theta_mod = h->M.kind == BB_MODEL_GENOTYPE ? 0 : (h->M.blk_hi[BK_S] - h->M.blk_lo[BK_S]);
+    H.geno_idx = h->M.geno_idx;
+    H.n_samples = n_samples;
+    H.n_pad = 2;
+    while (H.n_pad < n_samples) H.n_pad <<= 1;
+    H.seed = seed;
+    const int nthr = H.n_pad >= 2048 ? 1024 : 256;
+    const size_t lds = (size_t)H.n_pad + nthr + 8;
+    const int nb = (int)std::min<long long>(n, 2048);
+    if ((rc = launch(h->stream, k_hier, nb, nthr, lds, H))) return rc;
+    if ((rc = d2h(median, H.median_out, (size_t)n * 8, h->stream))) return rc;
+    return d2h(stdv, H.std_out, (size_t)n * 8, h->stream);
+}
+extern "C" int bb_hier_fitness(bb_handle* h, int32_t n_samples, uint64_t seed, double* median, double* stdv) {
+    if (!h || !median || !stdv) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (h->perm_m.empty()) return hier_fitness_raw(h, n_samples, seed, median, stdv);
+    const size_t n = h->perm_m.size();          // (genotype model: one unit per mutant)
+    std::vector<double> a(n), b(n);
+    int rc = hier_fitness_raw(h, n_samples, seed, a.data(), b.data());
+    if (rc) return rc;
+    for (size_t m = 0; m < n; ++m) { median[(size_t)h->perm_m[m]] = a[m]; stdv[(size_t)h->perm_m[m]] = b[m]; }
+    return BB_OK;
+}
+
+// ---- log-joint and gradient at a batch of points (bb_logp.h) --------------------------------------------------------------------
+// n_points points in one call: three launches on buffers of the handle's own, the variational state untouched.  Caller's order <->
+// the handle's order once per batch, on the host.
+extern "C" int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z, double* logp, double* grad) {
+    if (!h || !z) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (n_points < 1 || n_points > BB_LOGP_MAX_BATCH) return bb_fail(BB_ERR_INVALID, "n_points = %d is outside 1 .. %d", (int)n_points, BB_LOGP_MAX_BATCH);
+    BB_GROUP_UNSUPPORTED(h, "bb_logdensity_grad_batch");
+    if (h->o.world_size > 1) return bb_fail(BB_ERR_UNSUPPORTED, "bb_logdensity_grad_batch is not available on a sharded handle (world_size > 1)");
+    BB_ENTER(h);
+    const DevModel& M = h->M;
+    const size_t W = (size_t)n_points, D = (size_t)M.D, Dz = (D + 1) & ~(size_t)1, Wp = (W + 1) & ~(size_t)1;
+    const bool geno = M.kind == BB_MODEL_GENOTYPE;
+    const size_t nbs = geno ? ((size_t)M.nb + 1) & ~(size_t)1 : 0, Gs = geno ? ((size_t)M.G + 1) & ~(size_t)1 : 0;
+    int rc;
+    LogpArgs B{};
+    double* dz = nullptr;
+    rc = carve(h->buf[BUF_LOGP], [&](Carve& c) {      // (every length even: pairs stay 16-byte aligned)
+        c(dz, W * Dz);
+        c(B.grad, W * Dz);
+        c(B.logp, Wp);                                 // (behind the gradients: one copy brings both back)
+        c(B.part, (W * (size_t)M.K * (size_t)h->nblk + 1) & ~(size_t)1);
+        c(B.zg, W * 2 * (size_t)M.nt1);
+        c(B.ds, W * nbs);
+        c(B.gsum, W * Gs);
+    });
+    if (rc) return rc;
+    B.z = dz;
+    B.Dz = (long long)Dz; B.nbs = (long long)nbs; B.Gs = (long long)Gs;
+    B.nt = h->nblk; B.W = n_points;
+    B.c0 = h->elbo_const - 0.5 * (double)M.D * (1.0 + BB_LOG2PI);      // (the ELBO's constant carries the entropy's: not part of the log-joint)
+    const bool direct = h->cidx.empty() && Dz == D;    // rows can be copied as they are
+    if (!direct) {
+        h->logp_host.resize(W * Dz + Wp);
+        for (size_t w = 0; w < W; ++w) {
+            double* row = h->logp_host.data() + w * Dz;
+            if (h->cidx.empty()) memcpy(row, z + w * D, D * 8);
+            else perm_gather(h, z + w * D, row);
+            if (Dz > D) row[D] = 0.0;
+        }
+    }
+    if ((rc = h2d(dz, direct ? z : h->logp_host.data(), W * Dz * 8, h->stream))) return rc;
+    const RunArgs A = make_args(h, 0, 0, 1, false, true);
+    const int grid = h->nblk * n_points;
+    by_kind(M.kind, [&](auto kindc) {
+        constexpr int KIND = decltype(kindc)::value;
+        rc = launch(h->stream, k_logp_moments<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
+        if (!rc) rc = launch(h->stream, k_logp_grad<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
+    });
+    if (rc) return rc;
+    if (geno) {
+        const int gsb = (int)std::min<long long>((M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block (as k_geno_sum)
+        if ((rc = launch(h->stream, k_logp_geno, gsb * n_points, 256, 256, desc_ptr(h->dM, &h->M), B, gsb))) return rc;
+    }
+    if (!grad) return logp ? d2h(logp, B.logp, W * 8, h->stream) : dsync(h->stream);
+    if (direct) {
+        if ((rc = d2h(grad, B.grad, W * D * 8, h->stream))) return rc;
+        return logp ? d2h(logp, B.logp, W * 8, h->stream) : BB_OK;
+    }
+    if ((rc = d2h(h->logp_host.data(), B.grad, (W * Dz + Wp) * 8, h->stream))) return rc;
+    for (size_t w = 0; w < W; ++w) {
+        const double* row = h->logp_host.data() + w * Dz;
+        if (h->cidx.empty()) memcpy(grad + w * D, row, D * 8);
+        else perm_scatter(h, row, grad + w * D);
+    }
+    if (logp) memcpy(logp, h->logp_host.data() + W * Dz, W * 8);
+    return BB_OK;
+}
+
+// ---- posterior predictive bands (bb_ppc.h) ----------------------------------------------------------------------------------
+static long long ppc_rows(const bb_handle* h) { return (long long)h->M.R * (1 + h->M.nb); }
+// time points of the longest replicate: the columns of the frequency bands, one more than the steps of the ratio bands
+static int freq_cols(const bb_handle* h) {
+    int n = 0;
+    for (int r = 0; r < h->M.R; ++r) n = std::max(n, h->M.T[r]);
+    return n;
+}
+static int ppc_steps(const bb_handle* h) { return freq_cols(h) - 1; }
+// caller offset of a block of the reference's layout (h->blocks lists the caller's order), -1 if the model has none
+static long long ppc_block(const bb_handle* h, const char* name) {
+    for (const bb_block_range& b : h->blocks) if (!strcmp(b.name, name)) return b.lo;
+    return -1;
+}
+
+extern "C" int bb_ppc_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps) {
+    if (!h || !n_rows || !n_steps) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_rows = ppc_rows(h);
+    *n_steps = ppc_steps(h);
+    return BB_OK;
+}
+
+// option checks shared by bb_ppc_bands and bb_freq_bands; *K = n_samples n_ppc
+static int ppc_check(int32_t n_samples, int32_t n_ppc, int32_t n_q, const double* q, long long* K) {
+    if (n_q < 1 || n_q > BB_PPC_MAX_Q) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 1..%d", BB_PPC_MAX_Q);
+    for (int i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
+    if (n_samples < 1 || n_ppc < 1) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples and n_ppc must be >= 1");
+    *K = (long long)n_samples * n_ppc;
+    if (*K < 2 || *K > BB_PPC_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples * n_ppc = %lld must be in 2..%d", *K, BB_PPC_MAX_K);
+    return BB_OK;
+}
+// What bb_ppc_bands and bb_freq_bands share.  The sampling handle's device is current for as long as this lives.
+struct BandsCall {
+    bb_handle* dh;                 // the handle that samples
+    DevGuard guard;
+    std::vector<double> prm;       // mean | sigma = softplus(omega), the caller's layout
+    size_t nbands = 0;             // doubles of the result
+    long long nblk = 0;            // grid of the row program (k_ppc / k_freq, 1024 threads)
+    int npop = 0;                  // grid of k_ppc_pop
+    explicit BandsCall(bb_handle* h) : dh(sampling_handle(h)), guard(dh->o.device) {}
+};
+// The front of a band call: the options checked, the posterior gathered, everything of P but the device pointers (the model's shape,
+// the blocks' caller offsets, the targets of n_rows x n_steps bands), the grids.
+static int bands_prologue(bb_handle* h, int32_t n_samples, int32_t n_ppc, int32_t n_q, const double* quantiles, uint64_t seed,
+                          long long n_rows, int n_steps, PpcArgs& P, BandsCall& B) {
+    long long K;
+    int rc = ppc_check(n_samples, n_ppc, n_q, quantiles, &K);
+    if (rc) return rc;
+    const DevModel& M = B.dh->M;
+    const size_t D = (size_t)h->M.D;
+    B.prm.resize(2 * D);           // (a multi-device handle gathers its parameters)
+    if ((rc = bb_get_params(h, B.prm.data(), B.prm.data() + D))) return rc;
+    for (size_t i = D; i < 2 * D; ++i) B.prm[i] = host_softplus(B.prm[i]);
+    memset(&P, 0, sizeof P);
+    P.kind = M.kind;
+    P.R = M.R;
+    P.E = (M.kind == BB_MODEL_MULTIENV || M.kind == BB_MODEL_MULTIENV_REPLICATE) ? M.E : 1;
+    P.nt1 = M.nt1;
+    P.nb = M.nb;
+    P.n_samples = n_samples;
+    P.n_ppc = n_ppc;
+    P.K = (int)K;
+    P.n_q = n_q;
+    P.seed = seed;
+    P.n_rows = n_rows;
+    P.n_steps = n_steps;
+    P.env_idx = M.env_idx;
+    for (int r = 0; r < M.R; ++r) { P.T[r] = M.T[r]; P.off_t[r] = M.off_t[r]; P.tcum[r] = M.tcum[r]; }
+    const bool hier = M.kind >= BB_MODEL_GENOTYPE;
+    P.lo_spop = ppc_block(h, "s_pop");
+    P.lo_lspop = ppc_block(h, "logsigma_pop");
+    P.lo_s = ppc_block(h, hier ? "theta" : "s_bc");
+    P.lo_ls = ppc_block(h, "logsigma_bc");
+    P.lo_tt = hier ? ppc_block(h, "theta_tilde") : 0;
+    P.lo_lt = hier ? ppc_block(h, "logtau") : 0;
+    if (P.lo_spop < 0 || P.lo_lspop < 0 || P.lo_s < 0 || P.lo_ls < 0 || P.lo_tt < 0 || P.lo_lt < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    // band end e = 2 qi + upper of the central mass q: the tail probabilities (1 - q) / 2 and 1 - (1 - q) / 2
+    double probs[2 * BB_PPC_MAX_Q];
+    for (int e = 0; e < 2 * n_q; ++e) {
+        const double q = quantiles[e >> 1];
+        probs[e] = (e & 1) ? 1.0 - (1.0 - q) / 2.0 : (1.0 - q) / 2.0;
+    }
+    quantile_plan(K, probs, 2 * n_q, P);
+    B.nbands = (size_t)n_rows * n_steps * n_q * 2;
+    // row program: two workgroups per CU at most, the per-block scratch (P.par) bounded to 256 MiB
+    B.nblk = std::min<long long>(n_rows, 2LL * B.dh->cus);
+    while (B.nblk > 1 && (size_t)B.nblk * P.E * 2 * (size_t)n_samples * 8 > ((size_t)256 << 20)) B.nblk = (B.nblk + 1) / 2;
+    B.npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * n_samples + 255) / 256, 1024));
+    return BB_OK;
+}
+// The device buffer of a band call, `extra` naming what the call puts between the row scratch and the bands; then what needs the
+// pointers: mean | sigma uploaded and, genotype model, geno_idx in the caller's mutant order (the handle keeps its own, regrouped one).
+template <class X>
+static int bands_buffers(const bb_handle* h, PpcArgs& P, BandsCall& B, X&& extra) {
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    const size_t D = (size_t)h->M.D, ns = (size_t)P.n_samples;
+    double* post = nullptr;
+    int* dg = nullptr;
+    int rc = carve(dh->buf[BUF_BANDS], [&](Carve& c) {
+        c(post, 2 * D);                                // mean | sigma
+        c(P.pop, (size_t)P.nt1 * 2 * ns);              // [nt1][2][ns]
+        c(P.par, (size_t)B.nblk * P.E * 2 * ns);       // [nblk][E][2][ns]
+        extra(c);
+        c(P.bands, B.nbands);
+        c(dg, ((size_t)M.nb + 1) / 2 + 8);             // [nb] ints
+    });
+    if (rc) return rc;
+    P.mean = post;
+    P.sigma = post + D;
+    if ((rc = h2d(post, B.prm.data(), 2 * D * 8, dh->stream)) || M.kind != BB_MODEL_GENOTYPE) return rc;
+    std::vector<int> gi((size_t)M.nb);
+    if ((rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, dh->stream))) return rc;
+    std::vector<int> geno = gi;
+    if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
+    P.geno_idx = dg;
+    return h2d(dg, geno.data(), (size_t)M.nb * 4, dh->stream);
+}
+
+// The walk over the observed counts that both n_outside computations make.  The handle's counts are in its own barcode order ([B][T_r]
+// per replicate at M.cnt_off[r]), the bands' rows in the caller's: for every replicate r (T time points) and barcode,
+// f(r, T, col, c, n, outside) gets the caller's data column col (neutrals first; a mutant through perm_m), the barcode's counts c[T],
+// the replicate's totals n[T] and outside(row, t, x): does x lie outside the band of the largest q at (row, t)?
+template <class F>
+static int observed_walk(const bb_handle* h, const BandsCall& B, const PpcArgs& P, const double* quantiles, const double* bands, F&& f) {
+    const DevModel& M = B.dh->M;
+    long long cnt = 0;
+    for (int r = 0; r < M.R; ++r) cnt += (long long)M.T[r] * M.B;
+    std::vector<unsigned> c((size_t)cnt);
+    int rc = d2h(c.data(), M.counts, (size_t)cnt * 4, B.dh->stream);
+    if (rc) return rc;
+    int qx = 0;
+    for (int i = 1; i < P.n_q; ++i) if (quantiles[i] > quantiles[qx]) qx = i;
+    auto outside = [&](long long row, int t, double x) {
+        const double* bd = bands + (((size_t)row * P.n_steps + t) * P.n_q + qx) * 2;
+        return x < bd[0] || x > bd[1];
+    };
+    for (int r = 0; r < M.R; ++r) {
+        const int T = M.T[r];
+        const unsigned* cr = c.data() + M.cnt_off[r];
+        std::vector<double> n((size_t)T, 0.0);
+        for (long long bc = 0; bc < M.B; ++bc)
+            for (int t = 0; t < T; ++t) n[(size_t)t] += (double)cr[bc * T + t];
+        for (long long bc = 0; bc < M.B; ++bc) {
+            const long long col = bc < M.nn || h->perm_m.empty() ? bc : M.nn + (long long)h->perm_m[(size_t)(bc - M.nn)];
+            f(r, T, col, cr + bc * T, n.data(), outside);
+        }
+    }
+    return BB_OK;
+}
+
+extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, int64_t* n_outside) {
+    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    PpcArgs P;
+    int rc = bands_prologue(h, o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, o->seed, ppc_rows(h), ppc_steps(h), P, B);
+    if (rc || (rc = bands_buffers(h, P, B, [](Carve&) {}))) return rc;
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    if ((rc = launch(dh->stream, k_ppc, (int)B.nblk, 1024, (size_t)bb_ppc_lds_doubles(P.K), P))) return rc;
+    if ((rc = d2h(bands, P.bands, B.nbands * 8, dh->stream))) return rc;
+    if (!n_outside) return BB_OK;
+    // observed log-frequency ratios outside the band of the largest q (finite ratios only: both counts > 0); a replicate's neutrals
+    // all count into its population-mean row
+    for (long long row = 0; row < P.n_rows; ++row) n_outside[row] = 0;
+    return observed_walk(h, B, P, o->quantiles, bands, [&](int r, int T, long long col, const unsigned* c, const double* n, auto& outside) {
+        const long long row = col < M.nn ? r : P.R + (long long)r * M.nb + (col - M.nn);
+        for (int t = 0; t + 1 < T; ++t) {
+            if (!c[t] || !c[t + 1]) continue;
+            if (outside(row, t, log((double)c[t + 1] / n[t + 1]) - log((double)c[t] / n[t]))) n_outside[row]++;
+        }
+    });
+}
+
+// ---- frequency-trajectory bands (bb_freq.h) -----------------------------------------------------------------------------------
+static_assert(BB_FREQ_TRAJECTORY == BB_FREQ_MODE_TRAJECTORY && BB_FREQ_POSTERIOR == BB_FREQ_MODE_POSTERIOR, "mode numbering");
+extern "C" int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols) {
+    if (!h || !n_rows || !n_cols) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_rows = (long long)h->M.R * h->M.B;
+    *n_cols = freq_cols(h);
+    return BB_OK;
+}
+
+extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands, int64_t* n_outside) {
+    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->mode != BB_FREQ_TRAJECTORY && o->mode != BB_FREQ_POSTERIOR) return bb_fail(BB_ERR_INVALID, "mode must be BB_FREQ_TRAJECTORY or BB_FREQ_POSTERIOR");
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    FreqArgs F;
+    memset(&F, 0, sizeof F);
+    PpcArgs& P = F.P;
+    int rc = bands_prologue(h, o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, o->seed, (long long)M.R * M.B, freq_cols(h), P, B);
+    if (rc) return rc;
+    if (o->mode == BB_FREQ_POSTERIOR && o->n_ppc != 1) return bb_fail(BB_ERR_INVALID, "BB_FREQ_POSTERIOR takes n_ppc = 1");      // (the shared checks report first)
+    F.mode = o->mode;
+    F.B = M.B;
+    F.nn = M.nn;
+    F.nchunks = (int)((M.B + BB_FREQ_CHUNK - 1) / BB_FREQ_CHUNK);
+    F.nz = o->mode == BB_FREQ_TRAJECTORY ? M.R : M.Ttot;
+    const long long lo_l = ppc_block(h, "loglambda");
+    if (lo_l < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    for (int r = 0; r < M.R; ++r) F.off_l[r] = lo_l + (long long)M.tcum[r] * M.B;
+    // normaliser rows in flight: their chunk partials bounded to 256 MiB
+    const size_t ns = (size_t)P.n_samples;
+    int zb = F.nz;
+    while (zb > 1 && (size_t)F.nchunks * zb * ns * 8 > ((size_t)256 << 20)) zb = (zb + 1) / 2;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * ns);                   // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * ns);       // [nchunks][zb][ns]
+    });
+    if (rc) return rc;
+    const size_t np2 = (ns + 1) / 2;
+    for (F.z0 = 0; F.z0 < F.nz; F.z0 = F.z1) {
+        F.z1 = std::min(F.nz, F.z0 + zb);
+        const size_t nzb = (size_t)(F.z1 - F.z0);
+        const int g1 = (int)std::max<size_t>(1, std::min<size_t>(((size_t)F.nchunks * nzb * np2 + 255) / 256, 65536));
+        const int g2 = (int)std::max<size_t>(1, std::min<size_t>((nzb * ns + 255) / 256, 4096));
+        if ((rc = launch(dh->stream, k_freq_zpart, g1, 256, 0, F))) return rc;
+        if ((rc = launch(dh->stream, k_freq_zsum, g2, 256, 0, F))) return rc;
+    }
+    if (o->mode == BB_FREQ_TRAJECTORY && (rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    if ((rc = launch(dh->stream, k_freq, (int)B.nblk, 1024, (size_t)bb_ppc_lds_doubles(P.K), F))) return rc;
+    if ((rc = d2h(bands, P.bands, B.nbands * 8, dh->stream))) return rc;
+    if (!n_outside) return BB_OK;
+    // observed frequencies R_{t,b} / n_t (zero counts included) outside the band of the largest q
+    return observed_walk(h, B, P, o->quantiles, bands, [&](int r, int T, long long col, const unsigned* c, const double* n, auto& outside) {
+        const long long row = (long long)r * M.B + col;
+        int64_t cnt = 0;
+        for (int t = 0; t < T; ++t) cnt += outside(row, t, (double)c[t] / n[t]);
+        n_outside[row] = cnt;
+    });
+}
+
+// ---- chain diagnostics (bb_chain.h) --------------------------------------------------------------------------------------------
+static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRIDE && BB_CHAIN_LAG_BATCH == BB_CHAIN_LAGS &&
+              2 * BB_CHAIN_MAX_Q <= BB_PPC_MAX_TGT, "bb_chain_summary limits");
+
+extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols, const double* chain, const bb_chain_out* out) {
+    if (!h || !o || !chain || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (n_cols < 1) return bb_fail(BB_ERR_INVALID, "n_cols must be >= 1");
+    if (o->n_chains < 1 || o->n_draws < 4) return bb_fail(BB_ERR_INVALID, "n_chains must be >= 1 and n_draws >= 4");
+    const int nq = o->n_quantiles;
+    if (nq < 0 || nq > BB_CHAIN_MAX_Q || (nq > 0 && !o->probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_CHAIN_MAX_Q);
+    for (int i = 0; i < nq; ++i)
+        if (!(o->probs[i] >= 0.0 && o->probs[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
+    if (o->max_lag < 0 || o->slab_cols < 0) return bb_fail(BB_ERR_INVALID, "max_lag and slab_cols must be >= 0");
+    const long long K = (long long)o->n_chains * o->n_draws;
+    if (K > BB_CHAIN_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_chains * n_draws = %lld must be <= %d", K, BB_CHAIN_MAX_K);
+    bb_handle* dh = sampling_handle(h);      // (nothing of the model is read)
+    BB_ENTER(dh);
+    ChainArgs C;
+    memset(&C, 0, sizeof C);
+    PpcArgs& P = C.P;
+    P.K = (int)K;
+    C.W = o->n_chains;
+    C.N = o->n_draws;
+    C.lag_max = o->max_lag ? std::min(o->max_lag, o->n_draws - 1) : o->n_draws - 1;
+    C.ess_cap = (double)K * log10((double)K);
+    // the select takes the order statistics and forms no bands (n_q = 0): one pair per probability
+    C.nq = nq;
+    quantile_plan(K, o->probs, nq, P);
+    // slab: the caller's column count, or what BB_CHAIN_SLAB_BYTES of uploaded rows hold (whole transpose tiles)
+    long long ld = o->slab_cols;
+    if (!ld) {
+        ld = std::max<long long>(1, (long long)BB_CHAIN_SLAB_BYTES / (8 * K));
+        if (ld >= BB_CHAIN_TILE) ld -= ld % BB_CHAIN_TILE;
+    }
+    ld = std::min<long long>(ld, n_cols);
+    // the slab's results lie together and come back in one copy: stat | quant | nlags
+    const size_t n_stat = 5 * (size_t)ld, n_quant = (size_t)BB_CHAIN_QSTRIDE * ld, n_lags = ((size_t)ld + 1) / 2, nres = n_stat + n_quant + n_lags;
+    double* slab = nullptr;
+    int rc = carve(dh->buf[BUF_CHAIN], [&](Carve& c) {
+        c(slab, (size_t)K * ld);                       // [K][ld] as uploaded
+        c(C.colT, (size_t)K * ld);                     // [ld][K]
+        c(C.stat, n_stat);                             // mean, sd, mcse, ess, rhat [5][ld]
+        c(C.quant, n_quant);                           // [ld][BB_CHAIN_QSTRIDE]
+        c(C.nlags, n_lags);                            // [ld] ints
+    });
+    if (rc) return rc;
+    C.slab = slab;
+    C.ld = ld;
+    std::vector<double> res(nres);
+    double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
+#ifdef BB_CHAIN_TIMES          // diagnostics (tools/chain_summary_rate.py): the call's phases, each drained before the next starts
+    timespec ct[5];
+    double cms[4] = {0, 0, 0, 0};
+    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int) {};
+#endif
+    for (long long c0 = 0; c0 < n_cols; c0 += ld) {
+        C.sc = std::min<long long>(ld, n_cols - c0);
+        lap(0);
+        if ((rc = h2d_2d(slab, (size_t)ld * 8, chain + c0, (size_t)n_cols * 8, (size_t)C.sc * 8, (size_t)K, dh->stream))) return rc;
+        lap(1);
+        const long long tiles = ((C.sc + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE) * ((K + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE);
+        if ((rc = launch(dh->stream, k_chain_transpose, (int)std::min<long long>(tiles, 1 << 16), BB_CHAIN_TNT, BB_CHAIN_TILE * (BB_CHAIN_TILE + 1), C))) return rc;
+        lap(2);
+        if ((rc = launch(dh->stream, k_chain_stats, (int)std::min<long long>(C.sc, 1 << 20), BB_CHAIN_NT, (size_t)bb_chain_lds_doubles(P.K), C))) return rc;
+        lap(3);
+        if ((rc = d2h(res.data(), C.stat, nres * 8, dh->stream))) return rc;
+        lap(4);
+        for (int s = 0; s < 5; ++s)
+            if (outs[s]) memcpy(outs[s] + c0, res.data() + (size_t)s * ld, (size_t)C.sc * 8);
+        if (out->quantiles && nq)
+            for (long long c = 0; c < C.sc; ++c) memcpy(out->quantiles + (size_t)(c0 + c) * nq, res.data() + n_stat + c * BB_CHAIN_QSTRIDE, (size_t)nq * 8);
+        if (out->n_lags) memcpy(out->n_lags + c0, res.data() + n_stat + n_quant, (size_t)C.sc * 4);
+    }
+#ifdef BB_CHAIN_TIMES
+    fprintf(stderr, "[bb_chain_summary %lld x %lld, slabs of %lld] upload %.3f ms, transpose %.3f ms, stats %.3f ms, download %.3f ms\n", K, (long long)n_cols, ld, cms[0], cms[1], cms[2], cms[3]);
+#endif
+    return BB_OK;
+}

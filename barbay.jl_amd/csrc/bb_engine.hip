@@ -1,4 +1,5 @@
-// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h.
+// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the step loop and its launch plans; the
+// post-fit entry points (hier fitness, log-density batch, predictive bands, chain summary) are in bb_analysis.h, included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -106,6 +107,30 @@ struct LaunchPlan {
     const char* why = nullptr;         // why no resident launch where one was wanted
 };
 
+// A device buffer of the handle's that grows on demand and keeps no contents across calls; bb_destroy frees them all.
+struct DevBuf {
+    double* p = nullptr;
+    size_t cap = 0;                    // doubles
+    int grow(size_t n) {
+        if (cap >= n) return 0;
+        if (p) dfree(p);
+        p = nullptr;
+        cap = 0;
+        void* q = nullptr;
+        int rc = dmalloc(&q, n * 8);
+        if (!rc) { p = (double*)q; cap = n; }
+        return rc;
+    }
+};
+enum {
+    BUF_EPS,       // bb_elbo_grad: device copy of caller-supplied draws
+    BUF_DBG,       // bb_debug_normals
+    BUF_BANDS,     // bb_ppc_bands / bb_freq_bands: parameters, tables, scratch and bands of the last call
+    BUF_LOGP,      // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
+    BUF_CHAIN,     // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
+    BUF_COUNT
+};
+
 struct bb_handle {
     DevModel M{};
     DevState S{};
@@ -143,17 +168,8 @@ struct bb_handle {
     unsigned* hstatus = nullptr;             // host-mapped status words (DevState.hstatus is their device address)
     double* bak_mu = nullptr;          // bb_elbo_grad: saved parameters
     double* bak_om = nullptr;
-    double* eps_buf = nullptr;         // device copy of caller-supplied draws
-    size_t eps_cap = 0;
-    double* dbg_buf = nullptr;
-    size_t dbg_cap = 0;
-    double* ppc_buf = nullptr;         // bb_ppc_bands / bb_freq_bands: parameters, tables, scratch and bands of the last call
-    size_t ppc_cap = 0;
-    double* logp_buf = nullptr;        // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
-    size_t logp_cap = 0;
-    double* chain_buf = nullptr;       // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
-    size_t chain_cap = 0;
-    std::vector<double> logp_host;     // ... and its host staging (rows padded to an even length, the handle's latent order)
+    DevBuf buf[BUF_COUNT];             // the calls' own device buffers (BUF_*)
+    std::vector<double> logp_host;     // bb_logdensity_grad_batch: host staging (rows padded to an even length, the handle's latent order)
     bbStream stream{};
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
     int launches_last_run = 0;
@@ -191,20 +207,6 @@ static int dalloc(bb_handle* h, T** p, size_t count) {
     h->dev_bytes += (long long)(count * sizeof(T));
     *p = (T*)q;
     return dzero(q, count * sizeof(T), h->stream);
-}
-
-// a buffer of the handle's that grows on demand and keeps no contents across calls (eps_buf, dbg_buf, ppc_buf; bb_destroy frees it)
-static int grow(double** buf, size_t* cap, size_t n) {
-    if (*cap >= n) return 0;
-    if (*buf) dfree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    void* p = nullptr;
-    int rc = dmalloc(&p, n * 8);
-    if (rc) return rc;
-    *buf = (double*)p;
-    *cap = n;
-    return 0;
 }
 
 extern "C" void bb_default_opts(bb_advi_opts* o) {
@@ -1467,11 +1469,7 @@ extern "C" void bb_destroy(bb_handle* h) {
     p2p_release(h);
     hostmap_free(h->hstatus);
     for (void* p : h->owned) dfree(p);
-    if (h->eps_buf) dfree(h->eps_buf);
-    if (h->dbg_buf) dfree(h->dbg_buf);
-    if (h->ppc_buf) dfree(h->ppc_buf);
-    if (h->logp_buf) dfree(h->logp_buf);
-    if (h->chain_buf) dfree(h->chain_buf);
+    for (DevBuf& b : h->buf) if (b.p) dfree(b.p);
     stream_close(h->stream);
     delete h;
 }
@@ -1893,15 +1891,14 @@ extern "C" int bb_get_params(bb_handle* h, double* mu, double* omega) {
     return BB_OK;
 }
 
+static double host_softplus(double om) { return std::max(om, 0.0) + log1p(exp(-fabs(om))); }
+
 extern "C" int bb_get_posterior(bb_handle* h, double* mean, double* sigma) {
     if (!h || !mean || !sigma) return bb_fail(BB_ERR_INVALID, "null argument");
     BB_ENTER(h);
     int rc = bb_get_params(h, mean, sigma);
     if (rc) return rc;
-    for (long long i = 0; i < h->M.D; ++i) {   // sigma = softplus(omega), O(D) once at the end
-        const double om = sigma[i];
-        sigma[i] = std::max(om, 0.0) + log1p(exp(-fabs(om)));
-    }
+    for (long long i = 0; i < h->M.D; ++i) sigma[i] = host_softplus(sigma[i]);   // sigma = softplus(omega), O(D) once at the end
     return BB_OK;
 }
 
@@ -2093,7 +2090,7 @@ static int elbo_grad_raw(bb_handle* h, const double* mu, const double* omega, co
     // per-sample ELBO values where S is more than the handle's own buffer holds
     if ((rc = ensure_scratch(h))) return rc;
     if ((rc = d2d(h->bak_mu, h->S.mu, D * 8, h->stream)) || (rc = d2d(h->bak_om, h->S.om, D * 8, h->stream))) return rc;
-    if (eps && (rc = grow(&h->eps_buf, &h->eps_cap, (size_t)S * D))) return rc;
+    if (eps && (rc = h->buf[BUF_EPS].grow((size_t)S * D))) return rc;
     void* es = nullptr;
     if (S > h->o.samples_per_step + 64 && (rc = dmalloc(&es, (size_t)S * 8))) return rc;
     // from here on the handle holds the caller's point and buffers: every path goes through the restore below
@@ -2103,8 +2100,8 @@ static int elbo_grad_raw(bb_handle* h, const double* mu, const double* omega, co
         int r;
         if ((r = h2d(h->S.mu, mu, D * 8, h->stream)) || (r = h2d(h->S.om, omega, D * 8, h->stream))) return r;
         if (eps) {
-            if ((r = h2d(h->eps_buf, eps, (size_t)S * D * 8, h->stream))) return r;
-            h->S.eps_in = h->eps_buf;
+            if ((r = h2d(h->buf[BUF_EPS].p, eps, (size_t)S * D * 8, h->stream))) return r;
+            h->S.eps_in = h->buf[BUF_EPS].p;
         }
         if (es) h->S.elbo_sample = (double*)es;
         if ((r = sync_descriptors(h))) return r;
@@ -2150,71 +2147,6 @@ extern "C" int bb_logdensity_grad(bb_handle* h, const double* z, double* logp, d
     return BB_OK;
 }
 
-// log-joint and gradient at n_points points in one call (bb_logp.h): three launches on buffers of the handle's own, the
-// variational state untouched.  Caller's order <-> the handle's order once per batch, on the host.
-extern "C" int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z, double* logp, double* grad) {
-    if (!h || !z) return bb_fail(BB_ERR_INVALID, "null argument");
-    if (n_points < 1 || n_points > BB_LOGP_MAX_BATCH) return bb_fail(BB_ERR_INVALID, "n_points = %d is outside 1 .. %d", (int)n_points, BB_LOGP_MAX_BATCH);
-    BB_GROUP_UNSUPPORTED(h, "bb_logdensity_grad_batch");
-    if (h->o.world_size > 1) return bb_fail(BB_ERR_UNSUPPORTED, "bb_logdensity_grad_batch is not available on a sharded handle (world_size > 1)");
-    BB_ENTER(h);
-    const DevModel& M = h->M;
-    const size_t W = (size_t)n_points, D = (size_t)M.D, Dz = (D + 1) & ~(size_t)1, Wp = (W + 1) & ~(size_t)1;
-    const bool geno = M.kind == BB_MODEL_GENOTYPE;
-    const size_t nbs = geno ? ((size_t)M.nb + 1) & ~(size_t)1 : 0, Gs = geno ? ((size_t)M.G + 1) & ~(size_t)1 : 0;
-    const size_t n_part = (W * (size_t)M.K * (size_t)h->nblk + 1) & ~(size_t)1, n_zg = W * 2 * (size_t)M.nt1;
-    int rc;
-    if ((rc = grow(&h->logp_buf, &h->logp_cap, 2 * W * Dz + Wp + n_part + n_zg + W * (nbs + Gs)))) return rc;
-    double* dz = h->logp_buf;
-    LogpArgs B{};
-    B.z = dz;
-    B.grad = dz + W * Dz;
-    B.logp = B.grad + W * Dz;                          // (behind the gradients: one copy brings both back)
-    B.part = B.logp + Wp;
-    B.zg = B.part + n_part;
-    B.ds = B.zg + n_zg;
-    B.gsum = B.ds + W * nbs;
-    B.Dz = (long long)Dz; B.nbs = (long long)nbs; B.Gs = (long long)Gs;
-    B.nt = h->nblk; B.W = n_points;
-    B.c0 = h->elbo_const - 0.5 * (double)M.D * (1.0 + BB_LOG2PI);      // (the ELBO's constant carries the entropy's: not part of the log-joint)
-    const bool direct = h->cidx.empty() && Dz == D;    // rows can be copied as they are
-    if (!direct) {
-        h->logp_host.resize(W * Dz + Wp);
-        for (size_t w = 0; w < W; ++w) {
-            double* row = h->logp_host.data() + w * Dz;
-            if (h->cidx.empty()) memcpy(row, z + w * D, D * 8);
-            else perm_gather(h, z + w * D, row);
-            if (Dz > D) row[D] = 0.0;
-        }
-    }
-    if ((rc = h2d(dz, direct ? z : h->logp_host.data(), W * Dz * 8, h->stream))) return rc;
-    const RunArgs A = make_args(h, 0, 0, 1, false, true);
-    const int grid = h->nblk * n_points;
-    by_kind(M.kind, [&](auto kindc) {
-        constexpr int KIND = decltype(kindc)::value;
-        rc = launch(h->stream, k_logp_moments<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
-        if (!rc) rc = launch(h->stream, k_logp_grad<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
-    });
-    if (rc) return rc;
-    if (geno) {
-        const int gsb = (int)std::min<long long>((M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block (as k_geno_sum)
-        if ((rc = launch(h->stream, k_logp_geno, gsb * n_points, 256, 256, desc_ptr(h->dM, &h->M), B, gsb))) return rc;
-    }
-    if (!grad) return logp ? d2h(logp, B.logp, W * 8, h->stream) : dsync(h->stream);
-    if (direct) {
-        if ((rc = d2h(grad, B.grad, W * D * 8, h->stream))) return rc;
-        return logp ? d2h(logp, B.logp, W * 8, h->stream) : BB_OK;
-    }
-    if ((rc = d2h(h->logp_host.data(), B.grad, (W * Dz + Wp) * 8, h->stream))) return rc;
-    for (size_t w = 0; w < W; ++w) {
-        const double* row = h->logp_host.data() + w * Dz;
-        if (h->cidx.empty()) memcpy(grad + w * D, row, D * 8);
-        else perm_scatter(h, row, grad + w * D);
-    }
-    if (logp) memcpy(logp, h->logp_host.data() + W * Dz, W * 8);
-    return BB_OK;
-}
-
 extern "C" int bb_get_elbo_trace(bb_handle* h, int64_t first_step, int64_t n, double* out) {
     if (!h || !out || n < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
     if (!h->shards.empty()) return bb_get_elbo_trace(h->shards[0], first_step, n, out);      // (every shard forms the same estimate from the same totals)
@@ -2242,10 +2174,11 @@ extern "C" int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int
     const size_t n = (size_t)(hi - lo);
     if (n == 0) return BB_OK;
     int rc;
-    if ((rc = grow(&h->dbg_buf, &h->dbg_cap, n))) return rc;
+    DevBuf& dbg = h->buf[BUF_DBG];
+    if ((rc = dbg.grow(n))) return rc;
     const int nb = (int)std::min<size_t>((n / 2 + 256) / 256, 1024);
-    if ((rc = launch(h->stream, k_normals, nb, 256, 0, h->o.seed, step, stream, lo, hi, h->dbg_buf))) return rc;
-    return d2h(out, h->dbg_buf, n * 8, h->stream);
+    if ((rc = launch(h->stream, k_normals, nb, 256, 0, h->o.seed, step, stream, lo, hi, dbg.p))) return rc;
+    return d2h(out, dbg.p, n * 8, h->stream);
 }
 
 extern "C" int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n) {
@@ -2375,448 +2308,8 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
     return h->p2p_on ? resident_warm(h) : BB_OK;
 }
 
-extern "C" int64_t bb_hier_units(const bb_handle* h) {
-    if (!h || h->M.kind < BB_MODEL_GENOTYPE) return 0;
-    return h->M.blk_hi[BK_TT] - h->M.blk_lo[BK_TT];
-}
-
-static int hier_fitness_raw(bb_handle* h, int32_t n_samples, uint64_t seed, double* median, double* stdv);
-extern "C" int bb_hier_fitness(bb_handle* h, int32_t n_samples, uint64_t seed, double* median, double* stdv) {
-    if (!h || !median || !stdv) return bb_fail(BB_ERR_INVALID, "null argument");
-    if (h->perm_m.empty()) return hier_fitness_raw(h, n_samples, seed, median, stdv);
-    const size_t n = h->perm_m.size();          // (genotype model: one unit per mutant)
-    std::vector<double> a(n), b(n);
-    int rc = hier_fitness_raw(h, n_samples, seed, a.data(), b.data());
-    if (rc) return rc;
-    for (size_t m = 0; m < n; ++m) { median[(size_t)h->perm_m[m]] = a[m]; stdv[(size_t)h->perm_m[m]] = b[m]; }
-    return BB_OK;
-}
-static int hier_fitness_raw(bb_handle* h, int32_t n_samples, uint64_t seed, double* median, double* stdv) {
-    if (!h || !median || !stdv) return bb_fail(BB_ERR_INVALID, "null argument");
-    if (!h->shards.empty()) {
-        // the whole posterior onto shard 0 (entries it does not own are dead weight there: never read by its tiles), then its sampler
-        bb_handle* s0 = h->shards[0];
-        const size_t D = (size_t)h->M.D;
-        std::vector<double> mu(D), om(D);
-        int rc = group_get_params(h, mu.data(), om.data());
-        BB_ENTER(s0);
-        if (!rc) rc = h2d(s0->S.mu, mu.data(), D * 8, s0->stream);
-        if (!rc) rc = h2d(s0->S.om, om.data(), D * 8, s0->stream);
-        if (rc) return rc;
-        const int ws = s0->o.world_size;
-        s0->o.world_size = 1;
-        rc = hier_fitness_raw(s0, n_samples, seed, median, stdv);
-        s0->o.world_size = ws;
-        return rc;
-    }
-    BB_ENTER(h);
-    if (h->M.kind < BB_MODEL_GENOTYPE) return bb_fail(BB_ERR_INVALID, "bb_hier_fitness applies to the hierarchical models only");
-    if (n_samples < 2 || n_samples > 16384) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in 2..16384");
-    // (a shard of a sharded run keeps full-length parameter arrays but only its own barcodes' entries are current: the caller makes them
-    //  whole first -- bb_set_params with the gathered vector, as barbay.jl_amd.vi does -- the draws are then those of a whole-problem handle)
-    const long long n = bb_hier_units(h);
-    const size_t D = (size_t)h->M.D;
-    int rc;
-    if ((rc = ensure_scratch(h))) return rc;
-    // posterior sigma = softplus(omega) into the (free between steps) z scratch array
-    std::vector<double> om(D);
-    if ((rc = dsync(h->stream)) || (rc = d2h(om.data(), h->S.om, D * 8, h->stream))) return rc;
-    for (size_t i = 0; i < D; ++i) om[i] = std::max(om[i], 0.0) + log1p(exp(-fabs(om[i])));
-    if ((rc = h2d(h->S.zsv, om.data(), D * 8, h->stream))) return rc;
-    HierArgs H;
-    memset(&H, 0, sizeof H);
-    H.mean = h->S.mu;
-    H.sigma = h->S.zsv;
-    H.median_out = h->S.asv;           // n <= D: scratch arrays are free between steps
-    H.std_out = h->S.hsv;
-    H.n_units = n;
-    H.lo_theta = h->M.blk_lo[BK_S];
-    H.lo_tt = h->M.blk_lo[BK_TT];
-    H.lo_lt = h->M.blk_lo[BK_LT];
-    H.theta_mod = h->M.kind == BB_MODEL_GENOTYPE ? 0 : (h->M.blk_hi[BK_S] - h->M.blk_lo[BK_S]);
-    H.geno_idx = h->M.geno_idx;
-    H.n_samples = n_samples;
-    H.n_pad = 2;
-    while (H.n_pad < n_samples) H.n_pad <<= 1;
-    H.seed = seed;
-    const int nthr = H.n_pad >= 2048 ? 1024 : 256;
-    const size_t lds = (size_t)H.n_pad + nthr + 8;
-    const int nb = (int)std::min<long long>(n, 2048);
-    if ((rc = launch(h->stream, k_hier, nb, nthr, lds, H))) return rc;
-    if ((rc = d2h(median, H.median_out, (size_t)n * 8, h->stream))) return rc;
-    return d2h(stdv, H.std_out, (size_t)n * 8, h->stream);
-}
-
-// ---- posterior predictive bands (bb_ppc.h) ----------------------------------------------------------------------------------
-static long long ppc_rows(const bb_handle* h) { return (long long)h->M.R * (1 + h->M.nb); }
-static int ppc_steps(const bb_handle* h) {
-    int n = 0;
-    for (int r = 0; r < h->M.R; ++r) n = std::max(n, h->M.T[r] - 1);
-    return n;
-}
-// caller offset of a block of the reference's layout (h->blocks lists the caller's order), -1 if the model has none
-static long long ppc_block(const bb_handle* h, const char* name) {
-    for (const bb_block_range& b : h->blocks) if (!strcmp(b.name, name)) return b.lo;
-    return -1;
-}
-
-extern "C" int bb_ppc_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps) {
-    if (!h || !n_rows || !n_steps) return bb_fail(BB_ERR_INVALID, "null argument");
-    *n_rows = ppc_rows(h);
-    *n_steps = ppc_steps(h);
-    return BB_OK;
-}
-
-// option checks shared by bb_ppc_bands and bb_freq_bands; *K = n_samples n_ppc
-static int ppc_check(int32_t n_samples, int32_t n_ppc, int32_t n_q, const double* q, long long* K) {
-    if (n_q < 1 || n_q > BB_PPC_MAX_Q) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 1..%d", BB_PPC_MAX_Q);
-    for (int i = 0; i < n_q; ++i)
-        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
-    if (n_samples < 1 || n_ppc < 1) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples and n_ppc must be >= 1");
-    *K = (long long)n_samples * n_ppc;
-    if (*K < 2 || *K > BB_PPC_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples * n_ppc = %lld must be in 2..%d", *K, BB_PPC_MAX_K);
-    return BB_OK;
-}
-// the caller's parameters (a multi-device handle gathers them) -> mean | sigma = softplus(omega) in the caller's layout
-static int ppc_posterior(bb_handle* h, std::vector<double>& prm) {
-    const size_t D = (size_t)h->M.D;
-    prm.resize(2 * D);
-    int rc = bb_get_params(h, prm.data(), prm.data() + D);
-    if (rc) return rc;
-    for (size_t i = D; i < 2 * D; ++i) prm[i] = std::max(prm[i], 0.0) + log1p(exp(-fabs(prm[i])));
-    return BB_OK;
-}
-// everything of PpcArgs but the row / step counts and the device pointers: the model's shape, the blocks' caller offsets, the targets
-static int ppc_fill(const bb_handle* h, const DevModel& M, int32_t n_samples, int32_t n_ppc, long long K, int32_t n_q, const double* quantiles,
-                    uint64_t seed, PpcArgs& P) {
-    memset(&P, 0, sizeof P);
-    P.kind = M.kind;
-    P.R = M.R;
-    P.E = (M.kind == BB_MODEL_MULTIENV || M.kind == BB_MODEL_MULTIENV_REPLICATE) ? M.E : 1;
-    P.nt1 = M.nt1;
-    P.nb = M.nb;
-    P.n_samples = n_samples;
-    P.n_ppc = n_ppc;
-    P.K = (int)K;
-    P.n_q = n_q;
-    P.seed = seed;
-    for (int r = 0; r < M.R; ++r) { P.T[r] = M.T[r]; P.off_t[r] = M.off_t[r]; P.tcum[r] = M.tcum[r]; }
-    const bool hier = M.kind >= BB_MODEL_GENOTYPE;
-    P.lo_spop = ppc_block(h, "s_pop");
-    P.lo_lspop = ppc_block(h, "logsigma_pop");
-    P.lo_s = ppc_block(h, hier ? "theta" : "s_bc");
-    P.lo_ls = ppc_block(h, "logsigma_bc");
-    P.lo_tt = hier ? ppc_block(h, "theta_tilde") : 0;
-    P.lo_lt = hier ? ppc_block(h, "logtau") : 0;
-    if (P.lo_spop < 0 || P.lo_lspop < 0 || P.lo_s < 0 || P.lo_ls < 0 || P.lo_tt < 0 || P.lo_lt < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
-    // order statistics of StatsBase.quantile (Statistics._quantile, alpha = beta = 1): aleph = K p + (1 - p), j = clamp(trunc(aleph), 1, K - 1),
-    // gamma = clamp(aleph - j, 0, 1), a + gamma (b - a) between the (1-based) order statistics j and j + 1
-    std::vector<int> lo(2 * (size_t)P.n_q), ranks;
-    for (int e = 0; e < 2 * P.n_q; ++e) {
-        const double q = quantiles[e >> 1];
-        const double p = (e & 1) ? 1.0 - (1.0 - q) / 2.0 : (1.0 - q) / 2.0;
-        const double aleph = (double)K * p + (1.0 - p);
-        const long long j = std::min<long long>(std::max<long long>((long long)aleph, 1), K - 1);
-        P.gam[e] = std::min(std::max(aleph - (double)j, 0.0), 1.0);
-        lo[(size_t)e] = (int)(j - 1);
-        ranks.push_back((int)(j - 1));
-        ranks.push_back((int)j);
-    }
-    std::sort(ranks.begin(), ranks.end());
-    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
-    P.n_tgt = (int)ranks.size();
-    for (int x = 0; x < P.n_tgt; ++x) P.tgt[x] = ranks[(size_t)x];
-    for (int e = 0; e < 2 * P.n_q; ++e) P.plo[e] = (int)(std::lower_bound(ranks.begin(), ranks.end(), lo[(size_t)e]) - ranks.begin());
-    return BB_OK;
-}
-// genotype model: geno_idx in the caller's mutant order (the handle keeps its own, regrouped one) into dg [nb] on the device
-static int ppc_geno(const bb_handle* h, bb_handle* dh, int* dg, PpcArgs& P) {
-    const DevModel& M = dh->M;
-    if (M.kind != BB_MODEL_GENOTYPE) return BB_OK;
-    int rc;
-    std::vector<int> gi((size_t)M.nb);
-    if ((rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, dh->stream))) return rc;
-    std::vector<int> geno = gi;
-    if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
-    if ((rc = h2d(dg, geno.data(), (size_t)M.nb * 4, dh->stream))) return rc;
-    P.geno_idx = dg;
-    return BB_OK;
-}
-// the handle's counts (its own barcode order: [B][T_r] per replicate at M.cnt_off[r])
-static int ppc_counts(bb_handle* dh, std::vector<unsigned>& c) {
-    const DevModel& M = dh->M;
-    long long cnt = 0;
-    for (int r = 0; r < M.R; ++r) cnt += (long long)M.T[r] * M.B;
-    c.resize((size_t)cnt);
-    return d2h(c.data(), M.counts, (size_t)cnt * 4, dh->stream);
-}
-
-extern "C" int bb_ppc_bands(bb_handle* h, const bb_ppc_opts* o, double* bands, int64_t* n_outside) {
-    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
-    long long K;
-    int rc = ppc_check(o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, &K);
-    if (rc) return rc;
-    const size_t D = (size_t)h->M.D;
-    std::vector<double> prm;
-    if ((rc = ppc_posterior(h, prm))) return rc;
-    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // a group samples on shard 0 (as bb_hier_fitness)
-    BB_ENTER(dh);
-    const DevModel& M = dh->M;
-    PpcArgs P;
-    if ((rc = ppc_fill(h, M, o->n_samples, o->n_ppc, K, o->n_quantiles, o->quantiles, o->seed, P))) return rc;
-    P.n_rows = ppc_rows(h);
-    P.n_steps = ppc_steps(h);
-    // grid: two workgroups per CU at most, the per-block scratch bounded to 256 MiB
-    const size_t ns = (size_t)P.n_samples;
-    long long nblk = std::min<long long>(P.n_rows, 2LL * dh->cus);
-    while (nblk > 1 && (size_t)nblk * P.E * 2 * ns * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
-    // device buffer: mean | sigma | pop [nt1][2][ns] | par [nblk][E][2][ns] | bands | geno_idx (caller order, ints)
-    const size_t nbands = (size_t)P.n_rows * P.n_steps * P.n_q * 2;
-    const size_t need = 2 * D + (size_t)P.nt1 * 2 * ns + (size_t)nblk * P.E * 2 * ns + nbands + ((size_t)M.nb + 1) / 2 + 8;
-    if ((rc = grow(&dh->ppc_buf, &dh->ppc_cap, need))) return rc;
-    double* b = dh->ppc_buf;
-    P.mean = b;
-    P.sigma = b + D;
-    P.pop = b + 2 * D;
-    P.par = P.pop + (size_t)P.nt1 * 2 * ns;
-    P.bands = P.par + (size_t)nblk * P.E * 2 * ns;
-    P.env_idx = M.env_idx;
-    if ((rc = h2d(b, prm.data(), 2 * D * 8, dh->stream))) return rc;
-    if ((rc = ppc_geno(h, dh, (int*)(P.bands + nbands), P))) return rc;
-    const int nthr = 1024;
-    const size_t lds = (size_t)bb_ppc_lds_doubles(P.K);
-    const int npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * P.n_samples + 255) / 256, 1024));
-    if ((rc = launch(dh->stream, k_ppc_pop, npop, 256, 0, P))) return rc;
-    if ((rc = launch(dh->stream, k_ppc, (int)nblk, nthr, lds, P))) return rc;
-    if ((rc = d2h(bands, P.bands, nbands * 8, dh->stream))) return rc;
-    if (!n_outside) return BB_OK;
-    // observed log-frequency ratios outside the band of the largest q (finite ratios only: both counts > 0); the handle's counts are in
-    // its own barcode order, the rows in the caller's
-    std::vector<unsigned> c;
-    if ((rc = ppc_counts(dh, c))) return rc;
-    int qx = 0;
-    for (int i = 1; i < P.n_q; ++i) if (o->quantiles[i] > o->quantiles[qx]) qx = i;
-    for (long long row = 0; row < P.n_rows; ++row) n_outside[row] = 0;
-    for (int r = 0; r < M.R; ++r) {
-        const int T = M.T[r];
-        const unsigned* cr = c.data() + M.cnt_off[r];
-        std::vector<double> n((size_t)T, 0.0);
-        for (long long bc = 0; bc < M.B; ++bc)
-            for (int t = 0; t < T; ++t) n[(size_t)t] += (double)cr[bc * T + t];
-        for (long long bc = 0; bc < M.B; ++bc) {
-            const long long row = bc < M.nn ? r : P.R + (long long)r * M.nb + (h->perm_m.empty() ? bc - M.nn : (long long)h->perm_m[(size_t)(bc - M.nn)]);
-            for (int t = 0; t + 1 < T; ++t) {
-                const unsigned c0 = cr[bc * T + t], c1 = cr[bc * T + t + 1];
-                if (!c0 || !c1) continue;
-                const double x = log((double)c1 / n[(size_t)t + 1]) - log((double)c0 / n[(size_t)t]);
-                const double* bd = bands + (((size_t)row * P.n_steps + t) * P.n_q + qx) * 2;
-                if (x < bd[0] || x > bd[1]) n_outside[row]++;
-            }
-        }
-    }
-    return BB_OK;
-}
-
-// ---- frequency-trajectory bands (bb_freq.h) -----------------------------------------------------------------------------------
-static_assert(BB_FREQ_TRAJECTORY == BB_FREQ_MODE_TRAJECTORY && BB_FREQ_POSTERIOR == BB_FREQ_MODE_POSTERIOR, "mode numbering");
-static int freq_cols(const bb_handle* h) {
-    int n = 0;
-    for (int r = 0; r < h->M.R; ++r) n = std::max(n, h->M.T[r]);
-    return n;
-}
-
-extern "C" int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols) {
-    if (!h || !n_rows || !n_cols) return bb_fail(BB_ERR_INVALID, "null argument");
-    *n_rows = (long long)h->M.R * h->M.B;
-    *n_cols = freq_cols(h);
-    return BB_OK;
-}
-
-extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands, int64_t* n_outside) {
-    if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
-    if (o->mode != BB_FREQ_TRAJECTORY && o->mode != BB_FREQ_POSTERIOR) return bb_fail(BB_ERR_INVALID, "mode must be BB_FREQ_TRAJECTORY or BB_FREQ_POSTERIOR");
-    long long K;
-    int rc = ppc_check(o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, &K);
-    if (rc) return rc;
-    if (o->mode == BB_FREQ_POSTERIOR && o->n_ppc != 1) return bb_fail(BB_ERR_INVALID, "BB_FREQ_POSTERIOR takes n_ppc = 1");
-    const size_t D = (size_t)h->M.D;
-    std::vector<double> prm;
-    if ((rc = ppc_posterior(h, prm))) return rc;
-    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // a group samples on shard 0 (as bb_ppc_bands)
-    BB_ENTER(dh);
-    const DevModel& M = dh->M;
-    FreqArgs F;
-    memset(&F, 0, sizeof F);
-    PpcArgs& P = F.P;
-    if ((rc = ppc_fill(h, M, o->n_samples, o->n_ppc, K, o->n_quantiles, o->quantiles, o->seed, P))) return rc;
-    P.n_rows = (long long)M.R * M.B;
-    P.n_steps = freq_cols(h);
-    F.mode = o->mode;
-    F.B = M.B;
-    F.nn = M.nn;
-    F.nchunks = (int)((M.B + BB_FREQ_CHUNK - 1) / BB_FREQ_CHUNK);
-    F.nz = o->mode == BB_FREQ_TRAJECTORY ? M.R : M.Ttot;
-    const long long lo_l = ppc_block(h, "loglambda");
-    if (lo_l < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
-    for (int r = 0; r < M.R; ++r) F.off_l[r] = lo_l + (long long)M.tcum[r] * M.B;
-    // grid of the row program: as k_ppc; normaliser rows in flight: their chunk partials bounded to 256 MiB
-    const size_t ns = (size_t)P.n_samples;
-    long long nblk = std::min<long long>(P.n_rows, 2LL * dh->cus);
-    while (nblk > 1 && (size_t)nblk * P.E * 2 * ns * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
-    int zb = F.nz;
-    while (zb > 1 && (size_t)F.nchunks * zb * ns * 8 > ((size_t)256 << 20)) zb = (zb + 1) / 2;
-    // device buffer: mean | sigma | pop [nt1][2][ns] | par [nblk][E][2][ns] | Z [Ttot][ns] | zpart [nchunks][zb][ns] | bands | geno_idx (ints)
-    const size_t nbands = (size_t)P.n_rows * P.n_steps * P.n_q * 2;
-    const size_t need = 2 * D + (size_t)P.nt1 * 2 * ns + (size_t)nblk * P.E * 2 * ns + (size_t)M.Ttot * ns + (size_t)F.nchunks * zb * ns + nbands +
-                        ((size_t)M.nb + 1) / 2 + 8;
-    if ((rc = grow(&dh->ppc_buf, &dh->ppc_cap, need))) return rc;
-    double* b = dh->ppc_buf;
-    P.mean = b;
-    P.sigma = b + D;
-    P.pop = b + 2 * D;
-    P.par = P.pop + (size_t)P.nt1 * 2 * ns;
-    F.Z = P.par + (size_t)nblk * P.E * 2 * ns;
-    F.zpart = F.Z + (size_t)M.Ttot * ns;
-    P.bands = F.zpart + (size_t)F.nchunks * zb * ns;
-    P.env_idx = M.env_idx;
-    if ((rc = h2d(b, prm.data(), 2 * D * 8, dh->stream))) return rc;
-    if ((rc = ppc_geno(h, dh, (int*)(P.bands + nbands), P))) return rc;
-    const size_t np2 = (ns + 1) / 2;
-    for (F.z0 = 0; F.z0 < F.nz; F.z0 = F.z1) {
-        F.z1 = std::min(F.nz, F.z0 + zb);
-        const size_t nzb = (size_t)(F.z1 - F.z0);
-        const int g1 = (int)std::max<size_t>(1, std::min<size_t>(((size_t)F.nchunks * nzb * np2 + 255) / 256, 65536));
-        const int g2 = (int)std::max<size_t>(1, std::min<size_t>((nzb * ns + 255) / 256, 4096));
-        if ((rc = launch(dh->stream, k_freq_zpart, g1, 256, 0, F))) return rc;
-        if ((rc = launch(dh->stream, k_freq_zsum, g2, 256, 0, F))) return rc;
-    }
-    if (o->mode == BB_FREQ_TRAJECTORY) {
-        const int npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * P.n_samples + 255) / 256, 1024));
-        if ((rc = launch(dh->stream, k_ppc_pop, npop, 256, 0, P))) return rc;
-    }
-    if ((rc = launch(dh->stream, k_freq, (int)nblk, 1024, (size_t)bb_ppc_lds_doubles(P.K), F))) return rc;
-    if ((rc = d2h(bands, P.bands, nbands * 8, dh->stream))) return rc;
-    if (!n_outside) return BB_OK;
-    // observed frequencies R_{t,b} / n_t (zero counts included) outside the band of the largest q; the handle's counts are in its own
-    // barcode order, the rows in the caller's
-    std::vector<unsigned> c;
-    if ((rc = ppc_counts(dh, c))) return rc;
-    int qx = 0;
-    for (int i = 1; i < P.n_q; ++i) if (o->quantiles[i] > o->quantiles[qx]) qx = i;
-    for (int r = 0; r < M.R; ++r) {
-        const int T = M.T[r];
-        const unsigned* cr = c.data() + M.cnt_off[r];
-        std::vector<double> n((size_t)T, 0.0);
-        for (long long bc = 0; bc < M.B; ++bc)
-            for (int t = 0; t < T; ++t) n[(size_t)t] += (double)cr[bc * T + t];
-        for (long long bc = 0; bc < M.B; ++bc) {
-            const long long col = bc < M.nn || h->perm_m.empty() ? bc : M.nn + (long long)h->perm_m[(size_t)(bc - M.nn)];
-            const long long row = (long long)r * M.B + col;
-            int64_t cnt = 0;
-            for (int t = 0; t < T; ++t) {
-                const double x = (double)cr[bc * T + t] / n[(size_t)t];
-                const double* bd = bands + (((size_t)row * P.n_steps + t) * P.n_q + qx) * 2;
-                if (x < bd[0] || x > bd[1]) cnt++;
-            }
-            n_outside[row] = cnt;
-        }
-    }
-    return BB_OK;
-}
-
-// ---- chain diagnostics (bb_chain.h) --------------------------------------------------------------------------------------------
-static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRIDE && BB_CHAIN_LAG_BATCH == BB_CHAIN_LAGS &&
-              2 * BB_CHAIN_MAX_Q <= BB_PPC_MAX_TGT, "bb_chain_summary limits");
-
-extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols, const double* chain, const bb_chain_out* out) {
-    if (!h || !o || !chain || !out) return bb_fail(BB_ERR_INVALID, "null argument");
-    if (n_cols < 1) return bb_fail(BB_ERR_INVALID, "n_cols must be >= 1");
-    if (o->n_chains < 1 || o->n_draws < 4) return bb_fail(BB_ERR_INVALID, "n_chains must be >= 1 and n_draws >= 4");
-    const int nq = o->n_quantiles;
-    if (nq < 0 || nq > BB_CHAIN_MAX_Q || (nq > 0 && !o->probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_CHAIN_MAX_Q);
-    for (int i = 0; i < nq; ++i)
-        if (!(o->probs[i] >= 0.0 && o->probs[i] <= 1.0)) return bb_fail(BB_ERR_INVALID, "All quantiles must be between zero and one");
-    if (o->max_lag < 0 || o->slab_cols < 0) return bb_fail(BB_ERR_INVALID, "max_lag and slab_cols must be >= 0");
-    const long long K = (long long)o->n_chains * o->n_draws;
-    if (K > BB_CHAIN_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_chains * n_draws = %lld must be <= %d", K, BB_CHAIN_MAX_K);
-    bb_handle* dh = h->shards.empty() ? h : h->shards[0];      // nothing of the model is read: a group works on its first device
-    BB_ENTER(dh);
-    ChainArgs C;
-    memset(&C, 0, sizeof C);
-    PpcArgs& P = C.P;
-    P.K = (int)K;
-    C.W = o->n_chains;
-    C.N = o->n_draws;
-    C.lag_max = o->max_lag ? std::min(o->max_lag, o->n_draws - 1) : o->n_draws - 1;
-    C.ess_cap = (double)K * log10((double)K);
-    // the select takes the order statistics and forms no bands (n_q = 0); per probability the pair of StatsBase.quantile as in
-    // ppc_fill: aleph = K p + (1 - p), j = clamp(trunc(aleph), 1, K - 1), gamma = clamp(aleph - j, 0, 1)
-    C.nq = nq;
-    std::vector<int> lo((size_t)nq), ranks;
-    for (int e = 0; e < nq; ++e) {
-        const double p = o->probs[e];
-        const double aleph = (double)K * p + (1.0 - p);
-        const long long j = std::min<long long>(std::max<long long>((long long)aleph, 1), K - 1);
-        P.gam[e] = std::min(std::max(aleph - (double)j, 0.0), 1.0);
-        lo[(size_t)e] = (int)(j - 1);
-        ranks.push_back((int)(j - 1));
-        ranks.push_back((int)j);
-    }
-    std::sort(ranks.begin(), ranks.end());
-    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
-    P.n_tgt = (int)ranks.size();
-    for (int x = 0; x < P.n_tgt; ++x) P.tgt[x] = ranks[(size_t)x];
-    for (int e = 0; e < nq; ++e) P.plo[e] = (int)(std::lower_bound(ranks.begin(), ranks.end(), lo[(size_t)e]) - ranks.begin());
-    // slab: the caller's column count, or what BB_CHAIN_SLAB_BYTES of uploaded rows hold (whole transpose tiles)
-    long long ld = o->slab_cols;
-    if (!ld) {
-        ld = std::max<long long>(1, (long long)BB_CHAIN_SLAB_BYTES / (8 * K));
-        if (ld >= BB_CHAIN_TILE) ld -= ld % BB_CHAIN_TILE;
-    }
-    ld = std::min<long long>(ld, n_cols);
-    // device buffer: slab [K][ld] | transpose [ld][K] | mean, sd, mcse, ess, rhat [5][ld] | quantiles [ld][8] | n_lags [ld] (ints)
-    const size_t nres = (size_t)(5 + BB_CHAIN_QSTRIDE) * ld + ((size_t)ld + 1) / 2;
-    int rc = grow(&dh->chain_buf, &dh->chain_cap, 2 * (size_t)K * ld + nres);
-    if (rc) return rc;
-    double* slab = dh->chain_buf;
-    C.slab = slab;
-    C.colT = slab + (size_t)K * ld;
-    C.stat = C.colT + (size_t)K * ld;
-    C.quant = C.stat + 5 * ld;
-    C.nlags = (int*)(C.quant + (size_t)BB_CHAIN_QSTRIDE * ld);
-    C.ld = ld;
-    std::vector<double> res(nres);
-    double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
-#ifdef BB_CHAIN_TIMES          // diagnostics (tools/chain_summary_rate.py): the call's phases, each drained before the next starts
-    timespec ct[5];
-    double cms[4] = {0, 0, 0, 0};
-    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int) {};
-#endif
-    for (long long c0 = 0; c0 < n_cols; c0 += ld) {
-        C.sc = std::min<long long>(ld, n_cols - c0);
-        lap(0);
-        if ((rc = h2d_2d(slab, (size_t)ld * 8, chain + c0, (size_t)n_cols * 8, (size_t)C.sc * 8, (size_t)K, dh->stream))) return rc;
-        lap(1);
-        const long long tiles = ((C.sc + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE) * ((K + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE);
-        if ((rc = launch(dh->stream, k_chain_transpose, (int)std::min<long long>(tiles, 1 << 16), BB_CHAIN_TNT, BB_CHAIN_TILE * (BB_CHAIN_TILE + 1), C))) return rc;
-        lap(2);
-        if ((rc = launch(dh->stream, k_chain_stats, (int)std::min<long long>(C.sc, 1 << 20), BB_CHAIN_NT, (size_t)bb_chain_lds_doubles(P.K), C))) return rc;
-        lap(3);
-        if ((rc = d2h(res.data(), C.stat, nres * 8, dh->stream))) return rc;
-        lap(4);
-        for (int s = 0; s < 5; ++s)
-            if (outs[s]) memcpy(outs[s] + c0, res.data() + (size_t)s * ld, (size_t)C.sc * 8);
-        if (out->quantiles && nq)
-            for (long long c = 0; c < C.sc; ++c) memcpy(out->quantiles + (size_t)(c0 + c) * nq, res.data() + 5 * ld + c * BB_CHAIN_QSTRIDE, (size_t)nq * 8);
-        if (out->n_lags) memcpy(out->n_lags + c0, res.data() + (size_t)(5 + BB_CHAIN_QSTRIDE) * ld, (size_t)C.sc * 4);
-    }
-#ifdef BB_CHAIN_TIMES
-    fprintf(stderr, "[bb_chain_summary %lld x %lld, slabs of %lld] upload %.3f ms, transpose %.3f ms, stats %.3f ms, download %.3f ms\n", K, (long long)n_cols, ld, cms[0], cms[1], cms[2], cms[3]);
-#endif
-    return BB_OK;
-}
+// the post-fit entry points: bb_hier_fitness, bb_logdensity_grad_batch, bb_ppc_bands, bb_freq_bands, bb_chain_summary
+#include "bb_analysis.h"
 
 extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
     if (!h || !s) return bb_fail(BB_ERR_INVALID, "null argument");

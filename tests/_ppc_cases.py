@@ -136,3 +136,64 @@ def case_ppc(lib, name, Ks=((1000, 1), (111, 7))):
         for r, T in enumerate(sp.n_time):
             rows = [r] + list(sp.n_rep + r * sp.n_bc + np.arange(sp.n_bc))
             assert np.all(np.isnan(bands[rows, T - 1:])) and not np.any(np.isnan(bands[rows, :T - 1]))
+
+
+def _bits(res):
+    """The raw bytes of a call's results: (bands, n_outside) or chain_summary's dict."""
+    vals = list(res.values()) if isinstance(res, dict) else list(res)
+    return [np.ascontiguousarray(v).tobytes() for v in vals]
+
+
+def _handle(lib, sp, mu, om, **kw):
+    e = make_engine(sp, lib, seed=4, **kw)
+    e.set_params(mu, om)
+    return e
+
+
+def case_buffer_reuse(lib):
+    """The calls' device buffers across calls and sizes on ONE handle: bands, frequency bands and a chain summary in turn, a call
+    that regrows the bands' buffer, a small call on the large stale buffer, the first call again.  Every result, n_outside included,
+    is byte for byte what the same call gives on a fresh handle."""
+    sp = spec("fitness")
+    qs = (0.95, 0.675, 0.05)
+    with make_engine(sp, lib, seed=4) as e:
+        e.run(3)
+        mu, om = e.get_params()
+    om = np.minimum(om, -2.0)                                  # (a fitted sigma: finite trajectories, as _freq_cases.tame)
+    chain = np.random.default_rng(12).standard_normal((2, 5, 6))
+    calls = [lambda e: e.ppc_bands(qs, n_samples=111, n_ppc=7, seed=11),
+             lambda e: e.freq_bands(qs, mode="trajectory", n_samples=111, n_ppc=7, seed=11),
+             lambda e: e.chain_summary(chain),
+             lambda e: e.ppc_bands(qs, n_samples=1000, n_ppc=1, seed=11),
+             lambda e: e.freq_bands(qs, mode="posterior", n_samples=2, n_ppc=1, seed=11),
+             lambda e: e.ppc_bands(qs, n_samples=111, n_ppc=7, seed=11)]
+    with _handle(lib, sp, mu, om) as e:
+        got = [_bits(f(e)) for f in calls]
+    for i, f in enumerate(calls):
+        with _handle(lib, sp, mu, om) as e:
+            assert got[i] == _bits(f(e)), i
+    assert got[0] == got[5]
+
+
+GROUP_CASES = ("fitness", "genotype_regrouped", "replicate_ragged")
+
+
+def group_results(lib, name, **kw):
+    """bb_ppc_bands, bb_freq_bands in both modes and (hierarchical kinds) bb_hier_fitness of a handle of the case at fixed parameters."""
+    sp = spec(name)
+    qs = (0.95, 0.675, 0.05)
+    g = np.random.default_rng(5)
+    mu, om = g.normal(0.0, 1.0, sp.D), g.normal(-3.0, 0.3, sp.D)
+    with _handle(lib, sp, mu, om, **kw) as e:
+        out = _bits(e.ppc_bands(qs, n_samples=111, n_ppc=7, seed=11))
+        out += _bits(e.freq_bands(qs, mode="trajectory", n_samples=111, n_ppc=7, seed=11))
+        out += _bits(e.freq_bands(qs, mode="posterior", n_samples=200, n_ppc=1, seed=11))
+        if e.hier_units() > 0:
+            out += _bits(e.hier_fitness(777, seed=21))
+    return out
+
+
+def case_group_handle(lib, name):
+    """A multi-device handle (n_devices = 2, both shards on device 0, as `_cases.case_multi_device_handle`) against a single-device
+    handle at the same parameters: the post-fit calls sample on shard 0 from the gathered posterior, byte for byte the same."""
+    assert group_results(lib, name, device_ids=[0, 0]) == group_results(lib, name)

@@ -12,6 +12,15 @@ def test_ppc_bands_match_restatement(emu_lib, name):
     pc.case_ppc(emu_lib, name)
 
 
+def test_buffer_reuse_across_calls_and_sizes(emu_lib):
+    pc.case_buffer_reuse(emu_lib)
+
+
+@pytest.mark.parametrize("name", pc.GROUP_CASES)
+def test_group_handle_equals_single_device(emu_lib, name):
+    pc.case_group_handle(emu_lib, name)
+
+
 def test_ppc_rows_subset_and_outside_flag(emu_lib):
     sp = pc.spec("fitness")
     with make_engine(sp, emu_lib, seed=2) as e:

@@ -20,6 +20,10 @@ def test_ppc_bands_match_restatement(hip_lib, name):
     pc.case_ppc(hip_lib, name)
 
 
+def test_buffer_reuse_across_calls_and_sizes(hip_lib):
+    pc.case_buffer_reuse(hip_lib)
+
+
 @pytest.fixture(scope="module")
 def c2(hip_lib):
     import barbay_jl_amd as bb
