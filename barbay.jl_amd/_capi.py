@@ -23,6 +23,7 @@ BB_LOGP_MAX_BATCH = 64
 BB_CHAIN_MAX_K = 16384
 BB_CHAIN_MAX_Q = 8
 BB_CHAIN_LAG_BATCH = 32
+BB_SCORE_MAX_SAMPLES = 16384
 BB_ERR_UNSUPPORTED = -4
 BB_ERR_NONFINITE = -5
 
@@ -31,7 +32,7 @@ EXPORTS = [
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
-    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_chain_summary",
+    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -96,6 +97,18 @@ class bb_freq_opts(C.Structure):
         ("mode", C.c_int32), ("n_samples", C.c_int32), ("n_ppc", C.c_int32), ("n_quantiles", C.c_int32),
         ("quantiles", _dp), ("seed", C.c_uint64),
     ]
+
+
+class bb_score_opts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64)]
+
+
+SCORE_CELLS = ("observed", "pred_mean", "pred_sd", "lpd", "p_waic", "pit", "pit_upper")
+SCORE_ROWS = ("row_lpd", "row_p_waic")
+
+
+class bb_score_out(C.Structure):
+    _fields_ = [(k, _dp) for k in SCORE_CELLS + SCORE_ROWS] + [("n_scored", C.POINTER(C.c_int32))]
 
 
 class bb_chain_opts(C.Structure):
@@ -169,6 +182,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_freq_bands"):
         lib.bb_freq_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.bb_freq_bands.argtypes = [vp, C.POINTER(bb_freq_opts), _dp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "bb_ppc_score"):
+        lib.bb_score_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.bb_ppc_score.argtypes = [vp, C.POINTER(bb_score_opts), C.POINTER(bb_score_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     return lib
@@ -479,6 +495,30 @@ class Engine:
         self._check(self._lib.bb_freq_bands(self._h, C.byref(o), _ptr(bands),
                                             nout.ctypes.data_as(C.POINTER(C.c_int64)) if outside else None))
         return bands, nout
+
+    def score_shape(self) -> Tuple[int, int]:
+        """(n_rows, n_steps) of `ppc_score`: the rows of `freq_bands` (n_rep * (n_neutral + n_bc), replicate-major, data columns:
+        neutrals first) and max_r T_r - 1 steps."""
+        n, t = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.bb_score_shape(self._h, C.byref(n), C.byref(t)))
+        return int(n.value), int(t.value)
+
+    def ppc_score(self, n_samples: int = 1000, seed: int = 0) -> Dict[str, np.ndarray]:
+        """Predictive log score and PIT of every observed log-frequency ratio (`bb_ppc_score`), the predictive density and CDF
+        averaged over the posterior draws in closed form.  Returns observed, pred_mean, pred_sd, lpd, p_waic, pit, pit_upper, each
+        [n_rows, n_steps] (NaN: no such step, or a zero count), and row_lpd, row_p_waic, n_scored (int32), each [n_rows]."""
+        n_rows, n_steps = self.score_shape()
+        o = bb_score_opts()
+        o.n_samples, o.seed = int(n_samples), int(seed)
+        res = {k: np.empty((n_rows, n_steps)) for k in SCORE_CELLS}
+        res.update({k: np.empty(n_rows) for k in SCORE_ROWS})
+        res["n_scored"] = np.empty(n_rows, dtype=np.int32)
+        out = bb_score_out()
+        for k in SCORE_CELLS + SCORE_ROWS:
+            setattr(out, k, _ptr(res[k]))
+        out.n_scored = res["n_scored"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_ppc_score(self._h, C.byref(o), C.byref(out)))
+        return res
 
     def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,
                       slab_cols: int = 0) -> Dict[str, np.ndarray]:

@@ -1,5 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
-// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h) and bb_chain_summary (bb_chain.h).  None of them touches the step loop.
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h) and bb_chain_summary (bb_chain.h).  None of them
+// touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -419,6 +420,79 @@ extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands,
         for (int t = 0; t < T; ++t) cnt += outside(row, t, (double)c[t] / n[t]);
         n_outside[row] = cnt;
     });
+}
+
+// ---- predictive log score and PIT of the observed ratios (bb_score.h) -----------------------------------------------------------
+static_assert(BB_SCORE_MAX_SAMPLES == BB_PPC_MAX_K, "bb_ppc_score limits");
+extern "C" int bb_score_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps) {
+    if (!h || !n_rows || !n_steps) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_rows = (long long)h->M.R * h->M.B;
+    *n_steps = ppc_steps(h);
+    return BB_OK;
+}
+
+extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->n_samples < 2 || o->n_samples > BB_SCORE_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in 2..%d", BB_SCORE_MAX_SAMPLES);
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    ScoreArgs A;
+    memset(&A, 0, sizeof A);
+    PpcArgs& P = A.P;
+    const long long n_rows = (long long)M.R * M.B;
+    const int n_steps = ppc_steps(h);
+    const double no_band = 0.0;              // (the shared prologue plans one band; nothing selects here)
+    int rc = bands_prologue(h, o->n_samples, 1, 1, &no_band, o->seed, n_rows, n_steps, P, B);
+    if (rc) return rc;
+    B.nbands = 0;
+    A.B = M.B;
+    A.nn = M.nn;
+#ifdef BB_SCORE_TIMES          // diagnostics (tools/ppc_score_rate.py): the call's phases, each drained before the next starts
+    timespec ct[6];
+    double cms[5] = {0, 0, 0, 0, 0};
+    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] = (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int) {};
+#endif
+    lap(0);
+    // the observed ratios, formed once here exactly as n_outside's walk forms them; NaN: a zero count, or no such step
+    const size_t ncell = (size_t)n_rows * n_steps;
+    std::vector<double> y(ncell, (double)NAN);
+    rc = observed_walk(h, B, P, &no_band, nullptr, [&](int r, int T, long long col, const unsigned* c, const double* n, auto&) {
+        double* yr = y.data() + ((size_t)r * M.B + col) * n_steps;
+        for (int t = 0; t + 1 < T; ++t)
+            if (c[t] && c[t + 1]) yr[t] = log((double)c[t + 1] / n[t + 1]) - log((double)c[t] / n[t]);
+    });
+    if (rc) return rc;
+    lap(1);
+    double* dy = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(dy, ncell);                                  // [n_rows][n_steps]
+        c(A.cell, BB_SCORE_CELLS * ncell);             // [6][n_rows][n_steps]
+        c(A.rowsum, 2 * (size_t)n_rows);               // [2][n_rows]
+        c(A.n_scored, ((size_t)n_rows + 1) / 2);       // [n_rows] ints
+    });
+    if (rc || (rc = h2d(dy, y.data(), ncell * 8, dh->stream))) return rc;
+    A.y = dy;
+    lap(2);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    lap(3);
+    if ((rc = launch(dh->stream, k_score, (int)B.nblk, BB_SCORE_NT, (size_t)bb_score_lds_doubles(P.n_samples), A))) return rc;
+    lap(4);
+    if (out->observed) memcpy(out->observed, y.data(), ncell * 8);
+    double* cells[BB_SCORE_CELLS] = {out->pred_mean, out->pred_sd, out->lpd, out->p_waic, out->pit, out->pit_upper};
+    for (int k = 0; k < BB_SCORE_CELLS; ++k)
+        if (cells[k] && (rc = d2h(cells[k], A.cell + (size_t)k * ncell, ncell * 8, dh->stream))) return rc;
+    if (out->row_lpd && (rc = d2h(out->row_lpd, A.rowsum, (size_t)n_rows * 8, dh->stream))) return rc;
+    if (out->row_p_waic && (rc = d2h(out->row_p_waic, A.rowsum + n_rows, (size_t)n_rows * 8, dh->stream))) return rc;
+    if (out->n_scored && (rc = d2h(out->n_scored, A.n_scored, (size_t)n_rows * 4, dh->stream))) return rc;
+    rc = dsync(dh->stream);
+    lap(5);
+#ifdef BB_SCORE_TIMES
+    fprintf(stderr, "[bb_ppc_score %lld x %d, %d samples] observed %.3f ms, upload %.3f ms, pop %.3f ms, score %.3f ms, download %.3f ms\n", n_rows, n_steps, (int)o->n_samples, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
 }
 
 // ---- chain diagnostics (bb_chain.h) --------------------------------------------------------------------------------------------

@@ -405,6 +405,10 @@ BB_KERNEL(1024, k_freq, FreqArgs F) {
     BB_CTX;
     bb_block_freq(cx, F, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_score, ScoreArgs A) {
+    BB_CTX;
+    bb_block_score(cx, A, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

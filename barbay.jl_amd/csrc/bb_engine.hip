@@ -17,6 +17,7 @@
 #include "bb_hier.h"
 #include "bb_ppc.h"
 #include "bb_freq.h"
+#include "bb_score.h"
 #include "bb_chain.h"
 #include "bb_logp.h"
 

@@ -15,6 +15,9 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
                                                                   (`bb_ppc_bands`), from the ADVI frame itself
     freq_ppc_bands                                                the bands of the frequency trajectories (freq_bc_ppc) of every barcode,
                                                                   neutrals included, in one device call (`bb_freq_bands`)
+    logfreq_ratio_ppc_scores, pit_histogram                       the log predictive density and PIT of every observed ratio, the
+                                                                  draws averaged in closed form (`bb_ppc_score`), and the calibration
+                                                                  histogram of the PITs (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -344,4 +347,66 @@ def freq_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, mode: st
         "upper": bands[..., 1][keep],
         "observed": obs[rr, tt],
         "n_outside": nout[rr],
+    })
+
+
+def logfreq_ratio_ppc_scores(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                             n_samples: int = 1000, seed: int = 0,
+                             id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                             rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                             device: int = 0) -> pd.DataFrame:
+    """How well the fit predicts EVERY observed log-frequency ratio, neutrals included, in one device call (`bb_ppc_score`): the
+    log predictive density of the ratio and its probability integral transform (PIT), the normal predictive of each of n_samples
+    posterior draws averaged in closed form -- no predictive draws, so the scores rank barcodes that `n_outside` cannot tell apart
+    and do not depend on a quantile.  `df_advi` as for `logfreq_ratio_ppc_bands`; n_samples <= 16384; at equal seed the draws are
+    those of the band calls.
+
+    Returns a tidy frame, one line per (barcode, replicate, step) that exists: `id`, `neutral`, `rep` ("R1", ...), `env` (the later
+    time point's environment; None without environments), `time` (the later time point's index, 1 .. T_r - 1), `observed` (the
+    ratio; NaN, as every score of the line, where either count is 0), `pred_mean`, `pred_sd`, `lpd`, `p_waic`, `pit`, `pit_upper`
+    (the predictive CDF at the ratio and its complement, each accurate where it is tiny), and per barcode and replicate, repeated
+    on its lines, `row_lpd` (the sum of its scored steps' lpd: sort ascending to rank the barcodes the fit does not explain) and
+    `n_scored`.  `pit_histogram` of the frame shows the calibration."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        res = e.ppc_score(n_samples=n_samples, seed=seed)
+    n_rows, n_steps = res["lpd"].shape
+    R, nn = len(bayes_model.counts), arrays.n_neutral
+    B = n_rows // R
+    has_env, per_env = _envs_per_rep(arrays, mname, R)
+    ids = np.asarray(list(arrays.neutral_ids) + list(arrays.bc_ids), dtype=object)      # the data columns: neutrals first
+    rr, tt = np.meshgrid(np.arange(n_rows), np.arange(n_steps), indexing="ij")
+    keep = np.arange(n_steps)[None, :] < np.repeat([c.shape[0] - 1 for c in bayes_model.counts], B)[:, None]
+    rr, tt = rr[keep], tt[keep]
+    rep, col = rr // B, rr % B
+    out = {
+        "id": ids[col],
+        "neutral": col < nn,
+        "rep": [f"R{r + 1}" for r in rep],
+        "env": [per_env[r][t + 1] for r, t in zip(rep, tt)] if has_env else None,
+        "time": tt + 1,
+    }
+    for k in ("observed", "pred_mean", "pred_sd", "lpd", "p_waic", "pit", "pit_upper"):
+        out[k] = res[k][keep]
+    out["row_lpd"] = res["row_lpd"][rr]
+    out["n_scored"] = res["n_scored"][rr]
+    return pd.DataFrame(out)
+
+
+def pit_histogram(scores: pd.DataFrame, bins: int = 10) -> pd.DataFrame:
+    """Calibration of the predictive: counts of the `pit` column of `logfreq_ratio_ppc_scores` in `bins` equal bins of [0, 1], for
+    the neutral and the mutant barcodes separately (unscored lines left out).  Flat: calibrated; U-shaped: the predictive is too
+    narrow (how mean-field ADVI fails); a hump: too wide.  Returns one line per bin: `lower`, `upper`, `neutral`, `mutant`."""
+    if bins < 1:
+        raise BarBayError("bins must be >= 1")
+    edges = np.linspace(0.0, 1.0, bins + 1)
+    pit = scores["pit"].to_numpy(dtype=np.float64)
+    neu = scores["neutral"].to_numpy(dtype=bool)
+    ok = ~np.isnan(pit)
+    return pd.DataFrame({
+        "lower": edges[:-1],
+        "upper": edges[1:],
+        "neutral": np.histogram(pit[ok & neu], bins=edges)[0],
+        "mutant": np.histogram(pit[ok & ~neu], bins=edges)[0],
     })

@@ -379,6 +379,55 @@ int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols);
 int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands /* [n_rows][n_cols][n_quantiles][2] */,
                   int64_t* n_outside /* [n_rows] or NULL */);
 
+/* Predictive log score and probability integral transform (PIT) of every OBSERVED log-frequency ratio, per barcode and step, from
+ * the current mean-field posterior -- the per-barcode verdict the bands' n_outside only counts.  No reference counterpart.  The
+ * predictive of a step given posterior draw j is N(mu_j, sigma_j), so its density and CDF at the observed ratio are averaged over
+ * the draws in closed form: no predictive draws, no selection, no Monte-Carlo error from the predictive layer.
+ *
+ * Rows (bb_score_shape: n_rows = n_rep (n_neutral + n_bc), n_steps = max_r T_r - 1) are the barcode rows of bb_freq_bands:
+ *   row = r B + b, B = n_neutral + n_bc, b the data column: neutrals first, then the mutants as the caller handed them over (also
+ *   where the library regrouped a genotype model).  Cells t >= T_r - 1 of a shorter replicate are NaN in every output.
+ *
+ * Cell (row, t).  Observed ratio y = ln(R_{t+1,b} / n_{t+1}) - ln(R_{t,b} / n_t), formed once on the host as bb_ppc_bands forms it
+ * for n_outside; where either count is 0 the cell is unscored and every output of the cell is NaN.  Per-draw parameters, j < n_samples:
+ *   a neutral barcode has (mu_j, sigma_j) = (-sbar_{r,t,j}, exp(logsigmabar_{r,t,j}));
+ *   a mutant exactly the (s - sbar_t, sigma) of its bb_ppc_bands row n_rep + r n_bc + m: the environment of the later time point,
+ *   theta + exp(logtau) theta_tilde for the hierarchical kinds.
+ * Draw j of latent i (the caller's flat index) is mu_i + sigma_i N(i, j >> 1, 0xFFFFFFE0), the draw of bb_ppc_bands: at equal seed
+ * the three post-fit calls share their joint draws.  With z_j = (y - mu_j) / sigma_j, l_j = -z_j^2 / 2 - ln sigma_j - ln(2 pi) / 2
+ * and n = n_samples:
+ *   observed   y, the value that was scored
+ *   pred_mean  mean_j mu_j
+ *   pred_sd    sqrt(mean_j sigma_j^2 + mean_j (mu_j - pred_mean)^2), two-pass and centred
+ *   lpd        the log predictive density  m + ln sum_j exp(l_j - m) - ln n,  m = max_j l_j
+ *   p_waic     sum_j (l_j - lbar)^2 / (n - 1), lbar = mean_j l_j, two-pass and centred (the cell's term of WAIC's penalty)
+ *   pit        mean_j erfc(-z_j / sqrt 2) / 2, the predictive CDF at y
+ *   pit_upper  mean_j erfc( z_j / sqrt 2) / 2, the upper tail; both through erfc, never as 1 - the other: each keeps its relative
+ *              accuracy where it is tiny, and a calibrated predictive has both uniform on (0, 1)
+ * Per row: row_lpd and row_p_waic are the sums over the row's scored cells in step order, n_scored their number.
+ * Non-finite parameters propagate by IEEE rules into the cells that use them (a NaN l_j makes m, and with it lpd, NaN); that is
+ * not an error and disturbs no other cell.
+ *
+ * A cell's results are a function of y, the handle's (mu, sigma), n_samples and seed alone: every sum runs in an order fixed by
+ * n_samples, bit-identical whatever the grid, the launch mode, the handle's internal latent order, the device count or the calls
+ * made on the handle before; no atomics on doubles.  The handle's mu, omega, optimiser state, step counter and RNG position are
+ * untouched, bitwise.  BB_ERR_INVALID: a null h, o or out; BB_ERR_UNSUPPORTED: n_samples outside 2 .. BB_SCORE_MAX_SAMPLES (a
+ * step's log densities in LDS).  A multi-device handle (n_devices > 1) gathers the posterior onto its first device; a shard of a
+ * sharded run (world_size > 1) needs the gathered vector through bb_set_params first, as bb_ppc_bands. */
+#define BB_SCORE_MAX_SAMPLES 16384
+typedef struct bb_score_opts {
+    int32_t n_samples;        /* posterior samples j, 2 .. BB_SCORE_MAX_SAMPLES        */
+    int32_t reserved0;
+    uint64_t seed;            /* Philox key                                            */
+} bb_score_opts;
+typedef struct bb_score_out {     /* every pointer may be NULL                         */
+    double *observed, *pred_mean, *pred_sd, *lpd, *p_waic, *pit, *pit_upper;      /* [n_rows][n_steps] */
+    double *row_lpd, *row_p_waic;    /* [n_rows]                                       */
+    int32_t* n_scored;        /* [n_rows]                                              */
+} bb_score_out;
+int bb_score_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps);
+int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
+
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array
  * chain[n_chains][n_draws][n_cols] (what mcmc_sample of the host layer writes).  n_cols is any positive count, not necessarily

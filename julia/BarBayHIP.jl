@@ -249,6 +249,53 @@ function freq_bands(h::Ptr{Cvoid}, quantiles::Vector{Float64}; mode::Integer=BB_
     return bands, nout
 end
 
+# Predictive log score and PIT of every observed log-frequency ratio (bb_ppc_score, include/barbay_hip.h): the per-barcode verdict
+# beside the bands.  Field for field the Python binding's `bb_score_opts` / `bb_score_out` (barbay.jl_amd/_capi.py).
+# Like the rest of this file it remains unexecuted (no `julia` where this repository is built and tested).
+const BB_SCORE_MAX_SAMPLES = 16384
+struct bb_score_opts
+    n_samples::Int32
+    reserved0::Int32
+    seed::UInt64
+end
+struct bb_score_out
+    observed::Ptr{Float64}
+    pred_mean::Ptr{Float64}
+    pred_sd::Ptr{Float64}
+    lpd::Ptr{Float64}
+    p_waic::Ptr{Float64}
+    pit::Ptr{Float64}
+    pit_upper::Ptr{Float64}
+    row_lpd::Ptr{Float64}
+    row_p_waic::Ptr{Float64}
+    n_scored::Ptr{Int32}
+end
+
+"""
+    ppc_score(h; n_samples=1000, seed=0) -> NamedTuple
+
+`h` a live `bb_handle`.  Returns `observed, pred_mean, pred_sd, lpd, p_waic, pit, pit_upper` (each n_steps x n_rows: Julia order of
+the C array [row][t]; NaN where the replicate has no such step or a count is 0) and `row_lpd, row_p_waic, n_scored` (n_rows each);
+rows: data column b of replicate r at r (n_neutral + n_bc) + b (0-based), neutrals first, as `freq_bands`.  The log predictive
+density and both tails of the predictive CDF at every observed log-frequency ratio, the n_samples posterior draws (those of
+`ppc_bands` at equal seed) averaged in closed form; 2 <= n_samples <= BB_SCORE_MAX_SAMPLES.
+"""
+function ppc_score(h::Ptr{Cvoid}; n_samples::Int=1000, seed::Integer=0)
+    nr, nt = Ref{Int64}(0), Ref{Int32}(0)
+    check(ccall((:bb_score_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}), h, nr, nt))
+    observed, pred_mean, pred_sd, lpd, p_waic, pit, pit_upper = (Matrix{Float64}(undef, nt[], nr[]) for _ in 1:7)
+    row_lpd, row_p_waic = Vector{Float64}(undef, nr[]), Vector{Float64}(undef, nr[])
+    n_scored = Vector{Int32}(undef, nr[])
+    GC.@preserve observed pred_mean pred_sd lpd p_waic pit pit_upper row_lpd row_p_waic n_scored begin
+        o = bb_score_opts(Int32(n_samples), Int32(0), UInt64(seed))
+        out = bb_score_out(pointer(observed), pointer(pred_mean), pointer(pred_sd), pointer(lpd), pointer(p_waic), pointer(pit),
+                           pointer(pit_upper), pointer(row_lpd), pointer(row_p_waic), pointer(n_scored))
+        check(ccall((:bb_ppc_score, LIB), Cint, (Ptr{Cvoid}, Ref{bb_score_opts}, Ref{bb_score_out}), h, o, out))
+    end
+    return (observed=observed, pred_mean=pred_mean, pred_sd=pred_sd, lpd=lpd, p_waic=p_waic, pit=pit, pit_upper=pit_upper,
+            row_lpd=row_lpd, row_p_waic=row_p_waic, n_scored=n_scored)
+end
+
 # Log-joint and gradient at several points in one call (bb_logdensity_grad_batch, include/barbay_hip.h): what a sampler that
 # steps an ensemble of walkers in lock-step asks of the model (`LogDensityProblems.logdensity_and_gradient`, W points at once).
 const BB_LOGP_MAX_BATCH = 64
