@@ -24,13 +24,15 @@ BB_CHAIN_MAX_K = 16384
 BB_CHAIN_MAX_Q = 8
 BB_CHAIN_LAG_BATCH = 32
 BB_SCORE_MAX_SAMPLES = 16384
+BB_MATH_FN = {"exp": 0, "log": 1, "rcp": 2, "div": 3, "sqrt": 4, "softplus_sigmoid": 5, "sincospi": 6, "exp_nonpos": 7, "log_1to2": 8,
+              "box_muller": 9}
 BB_ERR_UNSUPPORTED = -4
 BB_ERR_NONFINITE = -5
 
 EXPORTS = [
     "bb_version", "bb_last_error", "bb_default_opts", "bb_create", "bb_destroy", "bb_num_latents",
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
-    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
+    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
 ]
@@ -160,6 +162,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.bb_logdensity_grad_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     lib.bb_get_elbo_trace.argtypes = [vp, C.c_int64, C.c_int64, _dp]
     lib.bb_debug_normals.argtypes = [vp, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _dp]
+    if hasattr(lib, "bb_debug_math"):           # (A/B builds of older sources, tools/xp.py)
+        lib.bb_debug_math.argtypes = [vp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp]
     lib.bb_get_stats.argtypes = [vp, C.POINTER(bb_stats)]
     if hasattr(lib, "bb_kernel_name"):          # (A/B builds of older sources, tools/xp.py)
         lib.bb_kernel_name.argtypes = [vp, C.c_char_p, C.c_int64]
@@ -388,6 +392,23 @@ class Engine:
         out = np.empty(hi - lo)
         self._check(self._lib.bb_debug_normals(self._h, step, stream, lo, hi, _ptr(out)))
         return out
+
+    def debug_math(self, fn, x, y=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """One function of the kernels' fp64 math header, or the Box-Muller step, on the device at the arguments x (and y), for
+        accuracy checks (`bb_debug_math`): fn is a name of BB_MATH_FN or its number.  Returns (out0, out1), out1 None for the
+        functions of one result.  box_muller takes the two 64-bit words as uint64 arrays."""
+        code = BB_MATH_FN[fn] if isinstance(fn, str) else int(fn)
+        words = code == BB_MATH_FN["box_muller"]
+        x = np.ascontiguousarray(x, dtype=np.uint64).view(np.float64) if words else _f64(x)
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.uint64).view(np.float64) if words else _f64(y)
+            assert y.shape == x.shape
+        assert x.ndim == 1
+        out0 = np.empty(x.shape[0])
+        out1 = np.empty(x.shape[0]) if code in (BB_MATH_FN["softplus_sigmoid"], BB_MATH_FN["sincospi"], BB_MATH_FN["box_muller"]) else None
+        self._check(self._lib.bb_debug_math(self._h, code, x.shape[0], _ptr(x), _ptr(y) if y is not None else None, _ptr(out0),
+                                            _ptr(out1) if out1 is not None else None))
+        return out0, out1
 
     def stamps(self, per_wave: bool = False) -> np.ndarray:
         """Diagnostic build only: [tiles][32] block stamps, or with per_wave [tiles][4 events][16 waves]."""

@@ -454,3 +454,7 @@ BB_KERNEL(256, k_normals, unsigned long long seed, unsigned step, unsigned strea
     BB_CTX;
     bb_block_normals(cx, seed, step, stream, lo, hi, out, BB_GRID);
 }
+BB_KERNEL(256, k_math, int fn, long long n, const double* x, const double* y, double* out0, double* out1) {
+    BB_CTX;
+    bb_block_math(cx, fn, n, x, y, out0, out1, BB_GRID);
+}

@@ -111,12 +111,8 @@ BB_DEV void bb_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
 
-BB_DEV void bb_normal_pair(unsigned long long seed, unsigned long long q, unsigned step, unsigned stream,
-                           double* n0, double* n1) {
-    unsigned o[4];
-    bb_philox4x32_10((unsigned)q, (unsigned)(q >> 32), step, stream, (unsigned)seed, (unsigned)(seed >> 32), o);
-    unsigned long long a = ((unsigned long long)o[1] << 32) | o[0];
-    unsigned long long b = ((unsigned long long)o[3] << 32) | o[2];
+// Box-Muller on the two 64-bit words of one Philox output (apart from the draw: bb_debug_math feeds it chosen words)
+BB_DEV void bb_box_muller(unsigned long long a, unsigned long long b, double* n0, double* n1) {
     double u1 = ((double)(a >> 11) + 1.0) * 0x1.0p-53;   // (0, 1]
     double u2 = (double)(b >> 11) * 0x1.0p-53;           // [0, 1)
     double r = bb_sqrt(-2.0 * bb_log(u1));
@@ -124,6 +120,15 @@ BB_DEV void bb_normal_pair(unsigned long long seed, unsigned long long q, unsign
     bb_sincospi_02(2.0 * u2, &s, &c);
     *n0 = r * c;
     *n1 = r * s;
+}
+
+BB_DEV void bb_normal_pair(unsigned long long seed, unsigned long long q, unsigned step, unsigned stream,
+                           double* n0, double* n1) {
+    unsigned o[4];
+    bb_philox4x32_10((unsigned)q, (unsigned)(q >> 32), step, stream, (unsigned)seed, (unsigned)(seed >> 32), o);
+    unsigned long long a = ((unsigned long long)o[1] << 32) | o[0];
+    unsigned long long b = ((unsigned long long)o[3] << 32) | o[2];
+    bb_box_muller(a, b, n0, n1);
 }
 
 BB_DEV void bb_softplus_sigmoid(double om, double* sp, double* sig) { bb_softplus_sigmoid_fast(om, sp, sig); }

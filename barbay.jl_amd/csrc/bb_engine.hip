@@ -20,6 +20,7 @@
 #include "bb_score.h"
 #include "bb_chain.h"
 #include "bb_logp.h"
+#include "bb_mathprobe.h"
 
 #include <algorithm>
 #include <cmath>
@@ -125,7 +126,7 @@ struct DevBuf {
 };
 enum {
     BUF_EPS,       // bb_elbo_grad: device copy of caller-supplied draws
-    BUF_DBG,       // bb_debug_normals
+    BUF_DBG,       // bb_debug_normals, bb_debug_math
     BUF_BANDS,     // bb_ppc_bands / bb_freq_bands: parameters, tables, scratch and bands of the last call
     BUF_LOGP,      // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
     BUF_CHAIN,     // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
@@ -2180,6 +2181,28 @@ extern "C" int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int
     const int nb = (int)std::min<size_t>((n / 2 + 256) / 256, 1024);
     if ((rc = launch(h->stream, k_normals, nb, 256, 0, h->o.seed, step, stream, lo, hi, dbg.p))) return rc;
     return d2h(out, dbg.p, n * 8, h->stream);
+}
+
+// operands, results and the kernel of bb_block_math (bb_mathprobe.h) in BUF_DBG: x, y, out0, out1, n doubles each
+extern "C" int bb_debug_math(bb_handle* h, int32_t fn, int64_t n, const double* x, const double* y, double* out0, double* out1) {
+    if (!h || fn < 0 || fn >= BB_MATH_COUNT || n < 0 || !x || !out0) return bb_fail(BB_ERR_INVALID, "bad argument");
+    const bool two_in = fn == BB_MATH_DIV || fn == BB_MATH_BOX_MULLER;
+    const bool two_out = fn == BB_MATH_SOFTPLUS_SIGMOID || fn == BB_MATH_SINCOSPI || fn == BB_MATH_BOX_MULLER;
+    if ((two_in && !y) || (two_out && !out1)) return bb_fail(BB_ERR_INVALID, "function %d takes two operands / gives two results", (int)fn);
+    if (!h->shards.empty()) return bb_debug_math(h->shards[0], fn, n, x, y, out0, out1);
+    BB_ENTER(h);
+    if (n == 0) return BB_OK;
+    const size_t m = (size_t)n;
+    int rc;
+    DevBuf& dbg = h->buf[BUF_DBG];
+    if ((rc = dbg.grow(4 * m))) return rc;
+    double *dx = dbg.p, *dy = dbg.p + m, *d0 = dbg.p + 2 * m, *d1 = dbg.p + 3 * m;
+    if ((rc = h2d(dx, x, m * 8, h->stream))) return rc;
+    if (two_in && (rc = h2d(dy, y, m * 8, h->stream))) return rc;
+    const int nb = (int)std::min<size_t>((m + 255) / 256, 1024);
+    if ((rc = launch(h->stream, k_math, nb, 256, 0, (int)fn, (long long)n, dx, two_in ? dy : nullptr, d0, two_out ? d1 : nullptr))) return rc;
+    if ((rc = d2h(out0, d0, m * 8, h->stream))) return rc;
+    return two_out ? d2h(out1, d1, m * 8, h->stream) : BB_OK;
 }
 
 extern "C" int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n) {

@@ -5,7 +5,9 @@
 // (profiles/r01*: 59 % of k_sample in "draw"); the library forms carry full special-case handling
 // and IEEE-exact divide / sqrt expansions (div_scale / div_fmas / div_fixup).  These use the hardware
 // seeds v_rcp_f64 / v_rsq_f64 with Newton steps and short fma polynomials.  Compiles for the host
-// too (emulation build, accuracy tests in tests/test_bb_math.py).
+// too (emulation build, accuracy tests in tests/test_bb_math.py).  The device build -- these seeds, the
+// asm Horner blocks, the constant tables, the device ldexp / frexp -- is tested function by function on
+// the GPU against 50-digit values: tests/test_gpu_math.py through bb_debug_math (bb_mathprobe.h).
 #pragma once
 #include <math.h>
 
@@ -87,15 +89,23 @@ BB_DEV double bb_div(double a, double b) {
 
 // sqrt(x), x >= 0 (0 -> 0): rsq seed, ONE coupled Newton (Goldschmidt) iteration + final residual correction -- measured on
 // gfx950 (tools/probe/seed_accuracy.hip): the seed is good to 2^-24.2, the iteration squares that and the correction leaves 1.1e-16,
-// the same as with a second iteration.
-BB_DEV double bb_sqrt(double x) {
-    if (!(x > 0.0)) return x == 0.0 ? 0.0 : sqrt(x);
+// the same as with a second iteration.  The correction's residual x - g^2 is ~2^-47 x: below x = 2^-1022 it has no bits left (it
+// rounds to a multiple of 2^-1074) and the iteration's own error stays, 4.4e-16 measured on gfx950 (tests/test_gpu_math.py; the
+// host's exact seed hides it).  So x < 2^-900, subnormals included, takes the same steps on 2^256 x -- both scalings are exact.
+BB_DEV double bb_sqrt_normal(double x) {
     const double y = BB_RSQ_SEED(x);
     double g = x * y, h = 0.5 * y;
     const double r = fma(-h, g, 0.5);
     g = fma(g, r, g);
     h = fma(h, r, h);
     return fma(fma(-g, g, x), h, g);
+}
+BB_DEV double bb_sqrt(double x) {
+    if (!(x >= 0x1.0p-900)) {
+        if (!(x > 0.0)) return x == 0.0 ? 0.0 : sqrt(x);
+        return 0x1.0p-128 * bb_sqrt_normal(0x1.0p256 * x);
+    }
+    return bb_sqrt_normal(x);
 }
 
 // exp(x): k = rint(x log2 e), r = x - k ln2 (two-piece), degree-13 Taylor on |r| <= 0.347, ldexp.

@@ -490,6 +490,30 @@ int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols,
 /* The engine's normal stream for (step, stream) over latents [lo, hi), for checks. */
 int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int64_t lo, int64_t hi, double* out);
 
+/* One fp64 function of the kernels' math header (csrc/bb_math.h), or the Box-Muller step of the normal stream, evaluated on the
+ * device at n caller-chosen arguments, for accuracy checks: out0[i] (and out1[i]) = fn(x[i] (, y[i])).  Arguments outside a
+ * function's stated domain give what the kernels would get.
+ *   fn                          operands                                   results
+ *   BB_MATH_EXP, _LOG, _RCP, _SQRT, _EXP_NONPOS, _LOG_1TO2    x            out0
+ *   BB_MATH_DIV                 x / y                                      out0
+ *   BB_MATH_SOFTPLUS_SIGMOID    x                                          out0 = softplus, out1 = sigmoid
+ *   BB_MATH_SINCOSPI            x in [0, 2)                                out0 = sin(pi x), out1 = cos(pi x)
+ *   BB_MATH_BOX_MULLER          the two 64-bit words of a Philox output,   out0, out1 = the pair of normals (cosine, sine branch)
+ *                               as the bit patterns of x[i] and y[i]
+ * y and out1 may be NULL where fn does not use them.  BB_ERR_INVALID: unknown fn, n < 0, a NULL pointer fn needs.  n = 0: no launch. */
+#define BB_MATH_EXP 0
+#define BB_MATH_LOG 1
+#define BB_MATH_RCP 2
+#define BB_MATH_DIV 3
+#define BB_MATH_SQRT 4
+#define BB_MATH_SOFTPLUS_SIGMOID 5
+#define BB_MATH_SINCOSPI 6
+#define BB_MATH_EXP_NONPOS 7
+#define BB_MATH_LOG_1TO2 8
+#define BB_MATH_BOX_MULLER 9
+#define BB_MATH_COUNT 10
+int bb_debug_math(bb_handle* h, int32_t fn, int64_t n, const double* x, const double* y, double* out0, double* out1);
+
 /* s_memtime stamps at the pass boundaries of the last launches, [n_blocks][32]; all zero unless
  * the library was built with -DBB_STAMPS (diagnostic build, never the shipped one). */
 int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n);
