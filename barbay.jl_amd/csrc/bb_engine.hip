@@ -243,6 +243,21 @@ static void add_block(bb_handle* h, const char* name, int kind, long long n, lon
     *off += n;
 }
 
+// every mean finite, every std finite and > 0; the message names the prior and, Matrix form, the element in the CALLER's order
+static int check_prior(const bb_prior* p, const char* name) {
+    if (!p || !p->mean || !p->std || p->n == 0) return 0;
+    if (p->n == 1) {
+        if (!(p->std[0] > 0) || !std::isfinite(p->std[0])) return bb_fail(BB_ERR_INVALID, "%s: std must be > 0 and finite", name);
+        if (!std::isfinite(p->mean[0])) return bb_fail(BB_ERR_INVALID, "%s: mean must be finite", name);
+        return 0;
+    }
+    for (long long i = 0; i < (long long)p->n; ++i) {
+        if (!(p->std[i] > 0) || !std::isfinite(p->std[i])) return bb_fail(BB_ERR_INVALID, "%s: std[%lld] must be > 0 and finite", name, i);
+        if (!std::isfinite(p->mean[i])) return bb_fail(BB_ERR_INVALID, "%s: mean[%lld] must be finite", name, i);
+    }
+    return 0;
+}
+
 static int upload_prior(bb_handle* h, int kind, const bb_prior* p, double dmean, double dstd, const char* name,
                         bool vector_only, double* sum_log_std) {
     const long long n = h->M.blk_hi[kind] - h->M.blk_lo[kind];
@@ -256,7 +271,7 @@ static int upload_prior(bb_handle* h, int kind, const bb_prior* p, double dmean,
         return 0;
     }
     if (p->n == 1 || (n == 1 && p->n == 1)) {
-        if (!(p->std[0] > 0)) return bb_fail(BB_ERR_INVALID, "%s: std must be > 0", name);
+        if (int rc = check_prior(p, name)) return rc;
         dp.mean = p->mean[0];
         dp.inv_var = 1.0 / (p->std[0] * p->std[0]);
         *sum_log_std += (double)n * log(p->std[0]);
@@ -264,9 +279,9 @@ static int upload_prior(bb_handle* h, int kind, const bb_prior* p, double dmean,
     }
     if (vector_only) return bb_fail(BB_ERR_INVALID, "%s accepts only the Vector form [mean, std]", name);
     if (p->n != n) return bb_fail(BB_ERR_INVALID, "%s: Matrix form needs %lld rows, got %lld", name, n, (long long)p->n);
+    if (int rc = check_prior(p, name)) return rc;
     std::vector<double> iv((size_t)n);
     for (long long i = 0; i < n; ++i) {
-        if (!(p->std[i] > 0)) return bb_fail(BB_ERR_INVALID, "%s: std[%lld] must be > 0", name, i);
         iv[(size_t)i] = 1.0 / (p->std[i] * p->std[i]);
         *sum_log_std += log(p->std[i]);
     }
@@ -1038,6 +1053,11 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
     if (opts->optimizer != BB_OPT_TRUNCATED_ADAGRAD && opts->optimizer != BB_OPT_DECAYED_ADAGRAD)
         return bb_fail(BB_ERR_INVALID, "unknown optimizer %d", opts->optimizer);
     if (opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD && opts->window < 1) return bb_fail(BB_ERR_INVALID, "window must be >= 1");
+    // the optimiser constants go to the kernels as they are (DevState.optc): any sign (eta = 0 freezes a run), but finite
+    if (!std::isfinite(opts->eta)) return bb_fail(BB_ERR_INVALID, "eta must be finite");
+    if (!std::isfinite(opts->tau)) return bb_fail(BB_ERR_INVALID, "tau must be finite");
+    if (!std::isfinite(opts->pre)) return bb_fail(BB_ERR_INVALID, "pre must be finite");
+    if (!std::isfinite(opts->post)) return bb_fail(BB_ERR_INVALID, "post must be finite");
     if (opts->world_size < 1 || opts->rank < 0 || opts->rank >= opts->world_size)
         return bb_fail(BB_ERR_INVALID, "bad rank/world_size %d/%d", opts->rank, opts->world_size);
     if (opts->n_devices > 1) return group_create(md, opts, cx, out);
@@ -1393,7 +1413,10 @@ extern "C" int bb_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_h
         for (long long m = 0; m < nb; ++m) geno2[(size_t)m] = md->geno_idx[perm[(size_t)m]];
         md2.counts = counts2.data();
         md2.geno_idx = geno2.data();
-        // Matrix-form priors of the per-mutant and per-(time, barcode) blocks move with their barcodes
+        // Matrix-form priors of the per-mutant and per-(time, barcode) blocks move with their barcodes (checked first: a message names
+        // the element where the caller put it)
+        if (md->logsigma_bc_prior.n == nb && check_prior(&md->logsigma_bc_prior, "logsigma_bc_prior")) return BB_ERR_INVALID;
+        if (md->loglambda_prior.n == (int64_t)B * T && check_prior(&md->loglambda_prior, "loglambda_prior")) return BB_ERR_INVALID;
         if (md->logsigma_bc_prior.mean && md->logsigma_bc_prior.std && md->logsigma_bc_prior.n == nb && nb > 1) {
             lsm.resize((size_t)nb); lss.resize((size_t)nb);
             for (long long m = 0; m < nb; ++m) { lsm[(size_t)m] = md->logsigma_bc_prior.mean[perm[(size_t)m]]; lss[(size_t)m] = md->logsigma_bc_prior.std[perm[(size_t)m]]; }

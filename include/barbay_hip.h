@@ -58,8 +58,14 @@ extern "C" {
 #define BB_OPT_DECAYED_ADAGRAD 1
 
 /* A prior argument of a model (`VecOrMat{Float64}`, model_fitness_normal.jl:125-129):
+ * n == 0 or a null pointer: the reference's default for the block;
  * n == 1  : Vector form [mean, std] shared by the block;
- * n == len: Matrix form, mean[i], std[i] per element of the block. */
+ * n == len: Matrix form, mean[i], std[i] per element of the block, in the block's own order as the CALLER lays it out (loglambda:
+ *           t fastest per barcode, replicate-major; the per-mutant blocks of the multienv / replicate kinds: one element per
+ *           (mutant, environment) / (mutant, replicate)).  Where the library regroups a genotype model's mutants or moves a block
+ *           (bb_get_permutation) the elements move with their latents.
+ * Every mean must be finite and every std finite and > 0, else bb_create returns BB_ERR_INVALID and bb_last_error names the prior
+ * (Matrix form: and the element, "s_pop_prior: std[3] ..."); any other n is BB_ERR_INVALID too ("Matrix form needs <len> rows"). */
 typedef struct bb_prior {
     const double* mean;
     const double* std;
@@ -87,15 +93,18 @@ typedef struct bb_model_desc {
     bb_prior s_bc_prior;         /* default [0,2]; theta prior for the hierarchical models */
     bb_prior logsigma_bc_prior;  /* default [0,1] */
     bb_prior loglambda_prior;    /* default [3,3] */
-    bb_prior logtau_prior;       /* default [-2,1]; Vector form only (as in the reference) */
+    bb_prior logtau_prior;       /* default [-2,1]; Vector form only (as in the reference): n > 1 is BB_ERR_INVALID */
     int32_t flags;               /* BB_FLAG_*                                              */
 } bb_model_desc;
 
-/* Turing.ADVI(samples_per_step, max_iters) + optimiser + engine options. */
+/* Turing.ADVI(samples_per_step, max_iters) + optimiser + engine options.
+ * eta, tau, pre, post are the handle's own: they are copied into a device table at bb_create and every launch of the handle (two-kernel
+ * step, resident launches, split-phase step) reads them from there, so handles with different constants can live side by side.  Each
+ * must be finite, else BB_ERR_INVALID; no sign is imposed (eta = 0 takes the steps and leaves the parameters where they are). */
 typedef struct bb_advi_opts {
     int32_t samples_per_step; /* S >= 1                                                  */
     int32_t optimizer;        /* BB_OPT_*                                                */
-    double eta;               /* both optimisers, default 0.1                            */
+    double eta;               /* both optimisers, default 0.1: step = eta / (tau + sqrt(s)) or eta / (sqrt(acc) + 1e-8) */
     double tau;               /* TruncatedADAGrad, default 40                            */
     int32_t window;           /* TruncatedADAGrad n, default 100                         */
     int32_t resum_every;      /* TruncatedADAGrad: 1 = re-add the whole window every step
@@ -111,7 +120,7 @@ typedef struct bb_advi_opts {
                                  3e-11 at 1 000, 7e-8 at 5 000, 3e-8 at 10 000 (relative,
                                  worst latent); the step size eta / (tau + sqrt(s)) moves
                                  by at most 1e-8 of itself.  k > 1 bounds it.             */
-    double pre;               /* DecayedADAGrad, default 1.0                             */
+    double pre;               /* DecayedADAGrad, default 1.0: acc = post acc + pre g^2   */
     double post;              /* DecayedADAGrad, default 0.9                             */
     uint64_t seed;            /* Philox key (DESIGN.md "RNG stream")                     */
     int32_t device;           /* HIP device ordinal                                      */

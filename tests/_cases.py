@@ -122,12 +122,20 @@ def case_normals(lib):
         assert abs(big.mean()) < 0.01 and abs(big.std() - 1) < 0.01
 
 
+def oracle_optimizer(optname, **ekw):
+    """The oracle's optimiser with the constants the engine was given: eta, tau / pre, post and the window found in the engine's
+    keywords (the defaults of both sides are the reference's)."""
+    if optname == "TruncatedADAGrad":
+        return advi.TruncatedADAGrad(n=ekw.get("window", 100), **{k: ekw[k] for k in ("eta", "tau") if k in ekw})
+    return advi.DecayedADAGrad(**{k: ekw[k] for k in ("eta", "pre", "post") if k in ekw})
+
+
 def _trajectory(lib, sp, nsteps, S, optname, seed=11, use_priors=False, **ekw):
     e = make_engine(sp, lib, use_priors=use_priors, seed=seed, samples_per_step=S, optimizer=optname, **ekw)
     mu0, om0 = e.get_params()
     e.run(nsteps)
     mu, om = e.get_params()
-    opt = advi.TruncatedADAGrad(n=ekw.get("window", 100)) if optname == "TruncatedADAGrad" else advi.DecayedADAGrad()
+    opt = oracle_optimizer(optname, **ekw)
     f = lambda m, o, eps: literal.elbo_and_grad(m, o, eps, sp)
     eps_fn = lambda i: np.stack([caller_normals(e, seed, i, s, sp.D) for s in range(S)])
     m2, o2, tr = advi.run_advi(sp, f, mu0, om0, nsteps, S, opt, seed, eps_fn=eps_fn)
@@ -197,6 +205,12 @@ def case_sharded_split_phase(lib, name, W=3, S=2, nsteps=5):
     assert np.abs(mu - m1).max() < 1e-10 and np.abs(om - o1).max() < 1e-10
 
 
+def dataclass_with_priors(sp, **pri):
+    """`sp` with the named priors replaced (the others as they are)."""
+    import dataclasses
+    return dataclasses.replace(sp, priors={**sp.priors, **pri})
+
+
 def case_errors(lib):
     import barbay_jl_amd as bb
     import pytest
@@ -213,6 +227,59 @@ def case_errors(lib):
         bb.Engine("multienv", sp.counts, sp.n_neutral, sp.n_bc, _lib=lib)   # env_idx missing
     with pytest.raises(bb.BarBayHipError):
         bb.Engine("fitness", sp.counts, sp.n_neutral, sp.n_bc, samples_per_step=0, _lib=lib)
+    # non-finite priors: refused at bb_create, by name (Matrix form: with the element), not met later as BB_ERR_NONFINITE
+    nt1 = sp.n_time[0] - 1
+    ones, zeros = np.ones(nt1), np.zeros(nt1)
+
+    def at(a, i, v):
+        a = a.copy()
+        a[i] = v
+        return a
+    for pri, match in [({"s_bc_prior": (0.0, np.inf)}, r"s_bc_prior: std"),
+                       ({"loglambda_prior": (np.nan, 3.0)}, r"loglambda_prior: mean"),
+                       ({"s_pop_prior": (np.inf, 2.0)}, r"s_pop_prior: mean"),
+                       ({"logsigma_pop_prior": (0.0, np.nan)}, r"logsigma_pop_prior: std"),
+                       ({"s_pop_prior": (zeros, at(ones, nt1 - 1, np.inf))}, rf"s_pop_prior: std\[{nt1 - 1}\]"),
+                       ({"s_pop_prior": (zeros, at(ones, 1, 0.0))}, r"s_pop_prior: std\[1\]"),
+                       ({"logsigma_pop_prior": (at(zeros, 2, np.nan), ones)}, r"logsigma_pop_prior: mean\[2\]"),
+                       ({"s_bc_prior": (at(np.zeros(sp.n_bc), sp.n_bc - 1, -np.inf), np.ones(sp.n_bc))}, rf"s_bc_prior: mean\[{sp.n_bc - 1}\]")]:
+        with pytest.raises(bb.BarBayHipError, match=match) as ei:
+            bb.Engine(sp.kind, sp.counts, sp.n_neutral, sp.n_bc, priors=pri, _lib=lib)
+        assert "error -1:" in str(ei.value), ei.value          # BB_ERR_INVALID
+    # the optimiser constants: finite, of any sign (eta = 0 freezes a run)
+    for k in ("eta", "tau", "pre", "post"):
+        for v in (np.nan, np.inf, -np.inf):
+            with pytest.raises(bb.BarBayHipError, match=rf"{k} must be finite") as ei:
+                bb.Engine(sp.kind, sp.counts, sp.n_neutral, sp.n_bc, _lib=lib, **{k: v})
+            assert "error -1:" in str(ei.value), ei.value
+    for kw in (dict(eta=0.0), dict(eta=-0.1, tau=-1.0), dict(optimizer="DecayedADAGrad", pre=0.0, post=-0.5)):
+        bb.Engine(sp.kind, sp.counts, sp.n_neutral, sp.n_bc, _lib=lib, **kw).close()
+    # logtau_prior has only the Vector form (as in the reference)
+    sg = fixtures.load("data004_multigen")
+    with pytest.raises(bb.BarBayHipError, match="logtau_prior accepts only the Vector form"):
+        make_engine(dataclass_with_priors(sg, logtau_prior=(np.full(sg.n_bc, -2.0), np.ones(sg.n_bc))), lib, use_priors=True)
+    # ... whose mutants come scattered: the library regroups them, and still names the element where the caller put it
+    sg = synth("genotype")
+    assert not np.all(np.diff(sg.geno_idx) >= 0)
+    nl = sg.n_time[0] * sg.B
+    for pri, match in [(dict(loglambda_prior=(np.full(nl, 3.0), at(np.full(nl, 3.0), nl - 1, np.inf))), rf"loglambda_prior: std\[{nl - 1}\]"),
+                       (dict(logsigma_bc_prior=(at(np.zeros(sg.n_bc), sg.n_bc - 1, np.nan), np.ones(sg.n_bc))), rf"logsigma_bc_prior: mean\[{sg.n_bc - 1}\]")]:
+        with pytest.raises(bb.BarBayHipError, match=match):
+            make_engine(dataclass_with_priors(sg, **pri), lib, use_priors=True)
+    with pytest.raises(bb.BarBayHipError, match="logtau_prior: std"):
+        make_engine(dataclass_with_priors(sg, logtau_prior=(-2.0, np.inf)), lib, use_priors=True)
+    # a Matrix prior of the wrong length: per (mutant, environment) / per (mutant, replicate), not per mutant
+    sm = fixtures.load("data003_multienv")
+    assert sm.n_env > 1
+    with pytest.raises(bb.BarBayHipError, match=rf"s_bc_prior: Matrix form needs {sm.n_bc * sm.n_env} rows, got {sm.n_bc}"):
+        make_engine(dataclass_with_priors(sm, s_bc_prior=(np.zeros(sm.n_bc), np.ones(sm.n_bc))), lib, use_priors=True)
+    sr = fixtures.load("data002_hier-rep")
+    assert sr.n_rep > 1
+    with pytest.raises(bb.BarBayHipError, match=rf"logsigma_bc_prior: Matrix form needs {sr.n_bc * sr.n_rep} rows, got {sr.n_bc}"):
+        make_engine(dataclass_with_priors(sr, logsigma_bc_prior=(np.zeros(sr.n_bc), np.ones(sr.n_bc))), lib, use_priors=True)
+    nl = sum(sr.n_time) * sr.B
+    with pytest.raises(bb.BarBayHipError, match=rf"loglambda_prior: Matrix form needs {nl} rows, got {sr.n_time[0] * sr.B}"):
+        make_engine(dataclass_with_priors(sr, loglambda_prior=(np.zeros(sr.n_time[0] * sr.B), np.ones(sr.n_time[0] * sr.B))), lib, use_priors=True)
 
 
 def case_persistent_equals_two_kernel(lib, name, tol=1e-11, expect_kernel=None, **geom):
@@ -237,38 +304,62 @@ def case_persistent_equals_two_kernel(lib, name, tol=1e-11, expect_kernel=None, 
     assert a < 1e-10 and b < 1e-10, (a, b)
 
 
-def case_genotype_regrouped(lib, name="genotype_runs", seed=6):
-    """geno_idx as the reference hands it over (barcodes in order of appearance, a genotype's mutants scattered;
-    utils.data_to_arrays, src/utils.jl:692-731): the library groups the mutants itself, runs the resident launch and presents the
-    caller's order.  The scatter here interleaves the genotype runs and keeps every genotype's mutants in their relative order, so
-    that the library's stable grouping restores exactly the sorted problem: same draws, bit-equal results after mapping back."""
+def scatter_genotypes(sp, priors=None):
+    """The genotype problem `sp` (mutants in runs) as the reference hands it over: the genotype runs interleaved by a random merge that
+    keeps every genotype's mutants in their relative order, so that the library's stable grouping restores exactly `sp`.  Returns the
+    scattered problem and `cols` (scattered column j is column cols[j] of `sp`).  priors: a function ModelSpec -> ModelSpec that gives
+    the SCATTERED problem its priors, in the caller's order; a third value is then returned, `sp` with those priors carried to its own
+    order (per-mutant and per-(barcode, time) elements move with their barcodes; per-time and per-genotype elements stay)."""
     import dataclasses
-    sp = synth(name, seed=seed)
     g = np.random.default_rng(3)
     gi = np.asarray(sp.geno_idx)
-    order = np.argsort(g.random(sp.n_bc) + 1e-9 * np.arange(sp.n_bc), kind="stable")       # a random merge ...
-    keys = np.sort(g.random(sp.n_bc))
-    # ... that keeps each genotype's mutants in order: give mutant m the m-th smallest key among its genotype's draws
-    shuffled = np.empty(sp.n_bc, dtype=np.int64)       # shuffled[j] = sorted-problem mutant at caller position j
+    g.random(sp.n_bc), g.random(sp.n_bc)          # (two draws the first version of this merge made and did not use: the stream's position is kept)
+    # give mutant m the m-th smallest key among its genotype's draws
     pos_keys = g.random(sp.n_bc)
     for gg in np.unique(gi):
         mem = np.nonzero(gi == gg)[0]
         pos_keys[mem] = np.sort(pos_keys[mem])
-    shuffled = np.argsort(pos_keys, kind="stable")
+    shuffled = np.argsort(pos_keys, kind="stable")       # shuffled[j] = sorted-problem mutant at caller position j
     nn = sp.n_neutral
     cols = np.concatenate([np.arange(nn), nn + shuffled])
     sp2 = dataclasses.replace(sp, counts=[c[:, cols] for c in sp.counts], geno_idx=gi[shuffled])
     assert not np.all(np.diff(np.asarray(sp2.geno_idx)) >= 0)
+    if priors is None:
+        return sp2, cols
+    sp2 = priors(sp2)
+    T, pri = sp.n_time[0], dict(sp2.priors)
+    for pname, idx in (("logsigma_bc_prior", shuffled), ("loglambda_prior", (cols[:, None] * T + np.arange(T)[None, :]).reshape(-1))):
+        m, sd = (np.asarray(x, dtype=np.float64) for x in pri[pname])
+        if m.ndim == 1:
+            ms, ss = np.empty_like(m), np.empty_like(sd)
+            ms[idx], ss[idx] = m, sd
+            pri[pname] = (ms, ss)
+    return sp2, cols, dataclasses.replace(sp, priors=pri)
+
+
+def case_genotype_regrouped(lib, name="genotype_runs", seed=6, priors=None, expect_kernel=2):
+    """geno_idx as the reference hands it over (barcodes in order of appearance, a genotype's mutants scattered;
+    utils.data_to_arrays, src/utils.jl:692-731): the library groups the mutants itself, runs the resident launch and presents the
+    caller's order.  The scatter here interleaves the genotype runs and keeps every genotype's mutants in their relative order, so
+    that the library's stable grouping restores exactly the sorted problem: same draws, bit-equal results after mapping back.
+    priors: a function that gives the scattered problem Matrix-form priors in the caller's order (scatter_genotypes); the sorted
+    problem gets the same priors sorted with its barcodes, and the trajectory is checked in launch_mode 1 too."""
+    sp = synth(name, seed=seed)
+    if priors is None:
+        sp2, _ = scatter_genotypes(sp)
+    else:
+        sp2, _, sp = scatter_genotypes(sp, priors)
+    up = priors is not None
     kw = dict(seed=13, window=6, resum_every=1)
-    with make_engine(sp, lib, launch_mode=2, **kw) as e:
+    with make_engine(sp, lib, use_priors=up, launch_mode=2, **kw) as e:
         e.run(11)
         ref = e.get_params()
         cidx_ref = e.permutation()
         # nothing to regroup here; the library's internal order still differs from the caller's where loglambda would start at an odd
         # flat index (n_geno + n_bc odd): it then sits in front of the theta block (bb_create)
         assert (cidx_ref == np.arange(sp.D)).all() == (sp.offsets()["loglambda"][0] % 2 == 0)
-    with make_engine(sp2, lib, launch_mode=2, **kw) as e:
-        assert e.stats()["resident_kernel"] == 2
+    with make_engine(sp2, lib, use_priors=up, launch_mode=2, **kw) as e:
+        assert e.stats()["resident_kernel"] == expect_kernel
         cidx = e.permutation()
         mu0, om0 = e.get_params()
         # gradient at a fixed point with explicit draws, in the caller's order, against the literal oracle on the scattered problem
@@ -281,15 +372,17 @@ def case_genotype_regrouped(lib, name="genotype_runs", seed=6):
     assert (got[0][cidx] == ref[0][cidx_ref]).all() and (got[1][cidx] == ref[1][cidx_ref]).all()
     off = sp.offsets()
     lo_tt = off["theta_tilde"][0]
-    with make_engine(sp, lib, launch_mode=2, **kw) as e:
+    with make_engine(sp, lib, use_priors=up, launch_mode=2, **kw) as e:
         e.run(11)
         med1, sd1 = e.hier_fitness(300, seed=4)
     pu = cidx[(cidx >= lo_tt) & (cidx < lo_tt + sp.n_bc)] - lo_tt          # (the theta_tilde block in internal order)
     assert (med[pu] == med1).all() and (sd[pu] == sd1).all()
     # trajectory against the oracle loop on the scattered problem (draws mapped through the permutation)
-    e, a, b, _ = _trajectory(lib, sp2, 9, 1, "TruncatedADAGrad", seed=13, window=4, resum_every=1, launch_mode=2)
-    e.close()
-    assert a < 1e-10 and b < 1e-10, (a, b)
+    for mode in ((2, 1) if up else (2,)):
+        e, a, b, _ = _trajectory(lib, sp2, 9, 1, "TruncatedADAGrad", seed=13, use_priors=up, window=4, resum_every=1, launch_mode=mode)
+        e.close()
+        print(f"regrouped {name} launch_mode {mode}: against the oracle loop |dmu| {a:.3e} |domega| {b:.3e}")
+        assert a < 1e-10 and b < 1e-10, (a, b)
 
 
 def case_ragged_method(lib, launch_mode=0):
@@ -501,3 +594,47 @@ def case_multi_device_handle(lib, name, n=2, steps=9, expect_resident=True, **ek
         e1b.run(2)
         assert np.abs(e.get_params()[0] - e1b.get_params()[0]).max() < 1e-9
         e1b.close()
+
+
+# The kernel instance a BASELINE workload runs at full size, on a cut of the problem with the full-size tile geometry (barcodes per tile,
+# threads): fixtures.synthetic's arguments, BB_TUNE_NB, BB_TUNE_NTHR, the instance bb_kernel_name must report (a prefix), further
+# environment, steps.
+BASELINE_INSTANCES = {
+    # 50 000 barcodes / 256 tiles, 65 % leaders
+    "C2_fitness": (("fitness", dict(B=2000, T=8, n_neutral=40, seed=42)), 198, 1024, "k_res<0,1,1024,false,8,false,false>", {}, 10),
+    # 20 000 barcodes / 256 tiles, 65 % leaders
+    "C3_replicate": (("replicate", dict(B=2000, T=6, n_rep=3, n_neutral=40, seed=43)), 79, 512, "k_res<3,3,512,false,6,false,false>", {}, 10),
+    "C4_multienv": (("multienv", dict(B=2000, T=6, n_env=4, n_neutral=40, seed=44)), 79, 1024, "k_res<1,1,1024,false,6,false,false>", {}, 10),
+    # 25 000 barcodes of 625 genotypes over ~216 tiles: ~117 barcodes, three genotypes of ~39 mutants per tile
+    "C5_rank": (("genotype", dict(B=2400, T=8, n_geno=60, n_neutral=48, seed=45, geno_runs=True)), 125, 1024,
+                "k_res<2,1,1024,false,8,false,false>", {}, 10),
+    # 200 000 barcodes over 256 tiles: 782 barcodes and ~4 300 pairs per tile -- five pair slots per thread, the state streamed
+    # (256: the two-kernel step's own tile; the resident launch's: BB_TUNE_RES_NB)
+    "C5_stream": (("genotype", dict(B=6256, T=8, n_geno=160, n_neutral=126, seed=45, geno_runs=True)), 256, 1024, "k_stream<2,1024,8>",
+                  {"BB_TUNE_RES_NB": "800"}, 8),
+    "multienv_replicate_even": (("multienv_replicate", dict(B=1500, T=6, n_rep=2, n_env=3, n_neutral=30, seed=46)), 60, 512, "k_res<4,", {}, 10),
+}
+
+
+def case_baseline_instance(lib, monkeypatch, cfg, priors=None, **ekw):
+    """One row of BASELINE_INSTANCES against the LITERAL oracle's ADVI loop (exact window), the instance by the library's own word
+    (bb_kernel_name).  priors: a function ModelSpec -> ModelSpec that gives the problem its priors; ekw: further engine settings
+    (optimiser constants: they go to the oracle's optimiser too)."""
+    (kind, skw), nb, nthr, inst, env, steps = BASELINE_INSTANCES[cfg]
+    sp = fixtures.synthetic(kind, **skw)
+    if priors is not None:
+        sp = priors(sp)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("BB_TUNE_NB", str(nb))
+    monkeypatch.setenv("BB_TUNE_NTHR", str(nthr))
+    e, a, b, _ = _trajectory(lib, sp, steps, 1, "TruncatedADAGrad", seed=13, use_priors=priors is not None, window=4, resum_every=1,
+                             launch_mode=2, **ekw)
+    st, name = e.stats(), e.kernel_name()
+    e.close()
+    print(f"baseline {cfg}: {name}: against the oracle loop |dmu| {a:.3e} |domega| {b:.3e}")
+    assert name.startswith(inst), name
+    assert st["block_threads"] == nthr and st["resident_kernel"] == (3 if cfg == "C5_stream" else 2), st
+    if cfg == "C5_stream":
+        assert st["n_blocks"] >= 8 and st["persistent_pairs"] >= 5, st
+    assert a < 1e-10 and b < 1e-10, (a, b)

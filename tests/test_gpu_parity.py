@@ -287,41 +287,7 @@ def test_baseline_kernel_instance_against_the_oracle_loop(hip_lib, monkeypatch, 
     barcodes per tile, 8 tiles -- each on a cut of the problem with the full-size tile geometry (barcodes per tile, threads), against the
     LITERAL oracle's ADVI loop (exact window), not only against the two-kernel step.  The instance is the library's own word
     (bb_kernel_name), not inferred from bb_stats."""
-    from conftest import make_engine
-    from oracle import fixtures
-    steps = 10
-    if cfg == "C2_fitness":
-        sp = fixtures.synthetic("fitness", B=2000, T=8, n_neutral=40, seed=42)
-        nb, nthr, inst = 198, 1024, "k_res<0,1,1024,false,8,false,false>"          # 50 000 barcodes / 256 tiles, 65 % leaders
-    elif cfg == "C3_replicate":
-        sp = fixtures.synthetic("replicate", B=2000, T=6, n_rep=3, n_neutral=40, seed=43)
-        nb, nthr, inst = 79, 512, "k_res<3,3,512,false,6,false,false>"             # 20 000 barcodes / 256 tiles, 65 % leaders
-    elif cfg == "C4_multienv":
-        sp = fixtures.synthetic("multienv", B=2000, T=6, n_env=4, n_neutral=40, seed=44)
-        nb, nthr, inst = 79, 1024, "k_res<1,1,1024,false,6,false,false>"
-    elif cfg == "C5_rank":
-        # 25 000 barcodes of 625 genotypes over ~216 tiles: ~117 barcodes, three genotypes of ~39 mutants per tile
-        sp = fixtures.synthetic("genotype", B=2400, T=8, n_geno=60, n_neutral=48, seed=45, geno_runs=True)
-        nb, nthr, inst = 125, 1024, "k_res<2,1,1024,false,8,false,false>"
-    elif cfg == "C5_stream":
-        # 200 000 barcodes over 256 tiles: 782 barcodes and ~4 300 pairs per tile -- five pair slots per thread, the state streamed
-        sp = fixtures.synthetic("genotype", B=6256, T=8, n_geno=160, n_neutral=126, seed=45, geno_runs=True)
-        nb, nthr, inst = 256, 1024, "k_stream<2,1024,8>"          # (the two-kernel step's own tile; the resident launch's: BB_TUNE_RES_NB)
-        monkeypatch.setenv("BB_TUNE_RES_NB", "800")
-        steps = 8
-    else:
-        sp = fixtures.synthetic("multienv_replicate", B=1500, T=6, n_rep=2, n_env=3, n_neutral=30, seed=46)
-        nb, nthr, inst = 60, 512, "k_res<4,"
-    monkeypatch.setenv("BB_TUNE_NB", str(nb))
-    monkeypatch.setenv("BB_TUNE_NTHR", str(nthr))
-    e, a, b, _ = c._trajectory(hip_lib, sp, steps, 1, "TruncatedADAGrad", seed=13, window=4, resum_every=1, launch_mode=2)
-    st, name = e.stats(), e.kernel_name()
-    e.close()
-    assert name.startswith(inst), name
-    assert st["block_threads"] == nthr and st["resident_kernel"] == (3 if cfg == "C5_stream" else 2), st
-    if cfg == "C5_stream":
-        assert st["n_blocks"] >= 8 and st["persistent_pairs"] >= 5, st
-    assert a < 1e-10 and b < 1e-10, (a, b)
+    c.case_baseline_instance(hip_lib, monkeypatch, cfg)          # (the table: _cases.BASELINE_INSTANCES)
 
 
 @pytest.mark.parametrize("nb,nthr", [(100, 256), (24, 128), (150, 512), (40, 128), (9, 64), (96, 1024)])
