@@ -1,5 +1,6 @@
-// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the step loop and its launch plans; the
-// post-fit entry points (hier fitness, log-density batch, predictive bands, chain summary) are in bb_analysis.h, included below.
+// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the step loop and its launch plans; handle
+// creation (bb_create) is in bb_create.h and the post-fit entry points (hier fitness, log-density batch, predictive bands, chain
+// summary) are in bb_analysis.h, both included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -173,6 +174,7 @@ struct bb_handle {
     DevBuf buf[BUF_COUNT];             // the calls' own device buffers (BUF_*)
     std::vector<double> logp_host;     // bb_logdensity_grad_batch: host staging (rows padded to an even length, the handle's latent order)
     bbStream stream{};
+    bool opened = false;               // the stream is open (bb_create sets it: until then the handle holds nothing on a device)
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
     int launches_last_run = 0;
     int graph_launches = 0;            // hipGraphLaunch calls of the last bb_run (bb_debug_graph_launches)
@@ -211,150 +213,7 @@ static int dalloc(bb_handle* h, T** p, size_t count) {
     return dzero(q, count * sizeof(T), h->stream);
 }
 
-extern "C" void bb_default_opts(bb_advi_opts* o) {
-    memset(o, 0, sizeof *o);
-    o->samples_per_step = 1;
-    o->optimizer = BB_OPT_TRUNCATED_ADAGRAD;
-    o->eta = 0.1;
-    o->tau = 40.0;
-    o->window = 100;
-    o->resum_every = 0;
-    o->pre = 1.0;
-    o->post = 0.9;
-    o->seed = 0;
-    o->device = 0;
-    o->rank = 0;
-    o->world_size = 1;
-    o->steps_per_graph = 0;
-    o->elbo_every = 0;
-    o->n_devices = 1;
-    o->device_ids = nullptr;
-}
-
-static void add_block(bb_handle* h, const char* name, int kind, long long n, long long* off) {
-    bb_block_range b;
-    memset(&b, 0, sizeof b);
-    snprintf(b.name, sizeof b.name, "%s", name);
-    b.lo = *off;
-    b.hi = *off + n;
-    h->blocks.push_back(b);
-    h->M.blk_lo[kind] = b.lo;
-    h->M.blk_hi[kind] = b.hi;
-    *off += n;
-}
-
-// every mean finite, every std finite and > 0; the message names the prior and, Matrix form, the element in the CALLER's order
-static int check_prior(const bb_prior* p, const char* name) {
-    if (!p || !p->mean || !p->std || p->n == 0) return 0;
-    if (p->n == 1) {
-        if (!(p->std[0] > 0) || !std::isfinite(p->std[0])) return bb_fail(BB_ERR_INVALID, "%s: std must be > 0 and finite", name);
-        if (!std::isfinite(p->mean[0])) return bb_fail(BB_ERR_INVALID, "%s: mean must be finite", name);
-        return 0;
-    }
-    for (long long i = 0; i < (long long)p->n; ++i) {
-        if (!(p->std[i] > 0) || !std::isfinite(p->std[i])) return bb_fail(BB_ERR_INVALID, "%s: std[%lld] must be > 0 and finite", name, i);
-        if (!std::isfinite(p->mean[i])) return bb_fail(BB_ERR_INVALID, "%s: mean[%lld] must be finite", name, i);
-    }
-    return 0;
-}
-
-static int upload_prior(bb_handle* h, int kind, const bb_prior* p, double dmean, double dstd, const char* name,
-                        bool vector_only, double* sum_log_std) {
-    const long long n = h->M.blk_hi[kind] - h->M.blk_lo[kind];
-    DevPrior& dp = h->M.pri[kind];
-    dp.mean_e = nullptr;
-    dp.inv_var_e = nullptr;
-    if (!p || !p->mean || !p->std || p->n == 0) {
-        dp.mean = dmean;
-        dp.inv_var = 1.0 / (dstd * dstd);
-        *sum_log_std += (double)n * log(dstd);
-        return 0;
-    }
-    if (p->n == 1 || (n == 1 && p->n == 1)) {
-        if (int rc = check_prior(p, name)) return rc;
-        dp.mean = p->mean[0];
-        dp.inv_var = 1.0 / (p->std[0] * p->std[0]);
-        *sum_log_std += (double)n * log(p->std[0]);
-        return 0;
-    }
-    if (vector_only) return bb_fail(BB_ERR_INVALID, "%s accepts only the Vector form [mean, std]", name);
-    if (p->n != n) return bb_fail(BB_ERR_INVALID, "%s: Matrix form needs %lld rows, got %lld", name, n, (long long)p->n);
-    if (int rc = check_prior(p, name)) return rc;
-    std::vector<double> iv((size_t)n);
-    for (long long i = 0; i < n; ++i) {
-        iv[(size_t)i] = 1.0 / (p->std[i] * p->std[i]);
-        *sum_log_std += log(p->std[i]);
-    }
-    double *dm = nullptr, *di = nullptr;
-    int rc;
-    if ((rc = dalloc(h, &dm, (size_t)n))) return rc;
-    if ((rc = dalloc(h, &di, (size_t)n))) return rc;
-    if ((rc = h2d(dm, p->mean, (size_t)n * 8, h->stream))) return rc;
-    if ((rc = h2d(di, iv.data(), (size_t)n * 8, h->stream))) return rc;
-    dp.mean = 0;
-    dp.inv_var = 0;
-    dp.mean_e = dm;
-    dp.inv_var_e = di;
-    return 0;
-}
-
-// what bb_create hands create_inner (and a multi-device handle's shards): the switches, and whether to lay the loglambda block out in
-// FRONT of the per-genotype / per-mutant blocks (the handle's internal order; the caller's stays the reference's source order)
-struct CreateCtx { BBTuning tune; bool loglambda_first; };
-static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out);
-// Rows of the TruncatedADAGrad window on a SHARDED handle (DevModel.Dh): the window is 2 x window doubles per latent -- a hundred
-// times everything else a handle holds -- and a shard only ever updates its own barcodes' latents, the replicated blocks and (genotype
-// model) the genotype block: one contiguous range of the flat vector per (block, replicate), the ranges every tile's segment table
-// is cut from (bb_build_segs / br_build_segs).  A row packs those ranges one after the other; a segment carries the difference
-// between a latent's flat index and its entry (bb_hdelta), so the kernels pay one subtraction per pair.  Differences are even: pairs
-// stay whole and 16-byte aligned.  BB_NO_HIST_PACK=1 keeps full rows.
-static void hist_rows(bb_handle* h) {
-    DevModel& M = h->M;
-    M.Dh = M.Dp;
-    for (int k = 0; k < BK_COUNT; ++k) M.hd0[k] = M.hd1[k] = 0;
-    for (int r = 0; r < BB_MAX_REP; ++r) M.hdl[r] = 0;
-    if (h->o.world_size <= 1 || h->tune.no_hist_pack || M.Dp >= (1ll << 31)) return;      // (a segment keeps its difference in an int)
-    const long long b0 = h->b_lo, nbt = h->b_hi - h->b_lo;
-    const long long m0 = std::max(h->b_lo, M.nn) - M.nn, nmt = (std::max(h->b_hi, M.nn) - M.nn) - m0;
-    long long c = 0;          // next free entry of the row
-    // one range [a, a + len): starts on an entry of a's parity; two entries of slack (an edge pair's other half is read, never used)
-    auto place = [&](long long a, long long len) { const long long at = c + ((a - c) & 1); c = at + len + 2; return a - at; };
-    // R ranges of one block, `stride` apart in the flat vector, `len` long: packed `lp` apart with lp of the stride's parity
-    auto place_r = [&](int blk, long long a0, long long stride, long long len, int R) {
-        const long long lp = len + 2 + ((stride - (len + 2)) & 1);
-        const long long at = c + ((a0 - c) & 1);
-        M.hd0[blk] = a0 - at;
-        M.hd1[blk] = stride - lp;
-        c = at + (long long)R * lp;
-    };
-    M.hd0[BK_SPOP] = place(M.blk_lo[BK_SPOP], M.blk_hi[BK_SPOP] - M.blk_lo[BK_SPOP]);
-    M.hd0[BK_LSPOP] = place(M.blk_lo[BK_LSPOP], M.blk_hi[BK_LSPOP] - M.blk_lo[BK_LSPOP]);
-    if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {
-        M.hd0[BK_S] = place(M.blk_lo[BK_S] + m0 * M.E, nmt * M.E);
-        M.hd0[BK_LS] = place(M.blk_lo[BK_LS] + m0 * M.E, nmt * M.E);
-    } else if (M.kind == BB_MODEL_GENOTYPE) {
-        M.hd0[BK_S] = place(M.blk_lo[BK_S], M.G);      // (every rank updates every theta_g on the all-reduce step; the resident launch only its own)
-        M.hd0[BK_TT] = place(M.blk_lo[BK_TT] + m0, nmt);
-        M.hd0[BK_LT] = place(M.blk_lo[BK_LT] + m0, nmt);
-        M.hd0[BK_LS] = place(M.blk_lo[BK_LS] + m0, nmt);
-    } else {
-        const long long E_ = M.kind == BB_MODEL_MULTIENV_REPLICATE ? M.E : 1;
-        M.hd0[BK_S] = place(M.blk_lo[BK_S] + m0 * E_, nmt * E_);
-        for (int blk : {BK_TT, BK_LT, BK_LS}) place_r(blk, M.blk_lo[blk] + m0 * E_, M.nb * E_, nmt * E_, M.R);
-    }
-    for (int r = 0; r < M.R; ++r) M.hdl[r] = place(M.off_l[r] + b0 * M.T[r], nbt * M.T[r]);
-    const long long Dh = (c + 7) & ~7ll;
-    if (Dh >= M.Dp) {          // nothing gained (a shard that owns almost everything): full rows, no differences
-        for (int k = 0; k < BK_COUNT; ++k) M.hd0[k] = M.hd1[k] = 0;
-        for (int r = 0; r < BB_MAX_REP; ++r) M.hdl[r] = 0;
-        return;
-    }
-    M.Dh = Dh;
-}
-
-static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out);
 static int ensure_scratch(bb_handle* h);
-static void owned_ranges(const bb_handle* sh, std::vector<std::pair<long long, long long>>& out);
 static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, bool apply, bool with_elbo);
 static int theta_sync_local(bb_handle* const* hs, int n);
 static int launch_persistent(bb_handle* h, long long nsteps);
@@ -1040,429 +899,7 @@ static int check_persistent(bb_handle* h) {
     return 0;
 }
 
-static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out) {
-    if (!md || !opts || !out) return bb_fail(BB_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (md->kind < 0 || md->kind > 4) return bb_fail(BB_ERR_INVALID, "unknown model kind %d", md->kind);
-    if (md->n_rep < 1 || md->n_rep > BB_MAX_REP) return bb_fail(BB_ERR_INVALID, "n_rep must be in 1..%d", BB_MAX_REP);
-    if (md->kind != BB_MODEL_REPLICATE && md->kind != BB_MODEL_MULTIENV_REPLICATE && md->n_rep != 1)
-        return bb_fail(BB_ERR_INVALID, "only the replicate models take n_rep > 1");
-    if (md->n_neutral < 1 || md->n_bc < 1) return bb_fail(BB_ERR_INVALID, "need at least one neutral and one mutant barcode");
-    if (!md->n_time || !md->counts || !md->totals) return bb_fail(BB_ERR_INVALID, "n_time/counts/totals missing");
-    if (opts->samples_per_step < 1) return bb_fail(BB_ERR_INVALID, "samples_per_step must be >= 1");
-    if (opts->optimizer != BB_OPT_TRUNCATED_ADAGRAD && opts->optimizer != BB_OPT_DECAYED_ADAGRAD)
-        return bb_fail(BB_ERR_INVALID, "unknown optimizer %d", opts->optimizer);
-    if (opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD && opts->window < 1) return bb_fail(BB_ERR_INVALID, "window must be >= 1");
-    // the optimiser constants go to the kernels as they are (DevState.optc): any sign (eta = 0 freezes a run), but finite
-    if (!std::isfinite(opts->eta)) return bb_fail(BB_ERR_INVALID, "eta must be finite");
-    if (!std::isfinite(opts->tau)) return bb_fail(BB_ERR_INVALID, "tau must be finite");
-    if (!std::isfinite(opts->pre)) return bb_fail(BB_ERR_INVALID, "pre must be finite");
-    if (!std::isfinite(opts->post)) return bb_fail(BB_ERR_INVALID, "post must be finite");
-    if (opts->world_size < 1 || opts->rank < 0 || opts->rank >= opts->world_size)
-        return bb_fail(BB_ERR_INVALID, "bad rank/world_size %d/%d", opts->rank, opts->world_size);
-    if (opts->n_devices > 1) return group_create(md, opts, cx, out);
-
-    bb_handle* h = new bb_handle();
-    h->o = *opts;
-    h->tune = cx.tune;
-    if (h->o.resum_every < 0) h->o.resum_every = 0;      // 0 = the default schedule (bb_slot_of)
-    DevModel& M = h->M;
-    M.kind = md->kind;
-    M.R = md->n_rep;
-    M.E = (md->kind == BB_MODEL_MULTIENV || md->kind == BB_MODEL_MULTIENV_REPLICATE) ? md->n_env : 1;
-    M.G = md->kind == BB_MODEL_GENOTYPE ? md->n_geno : 0;
-    M.nn = md->n_neutral;
-    M.nb = md->n_bc;
-    M.B = M.nn + M.nb;
-    M.quirk = (md->kind == BB_MODEL_REPLICATE && (md->flags & BB_FLAG_RAGGED_METHOD)) ? 1 : 0;
-    int rc = 0;
-#define BB_TRY(x)                  \
-    do {                           \
-        rc = (x);                  \
-        if (rc) { bb_destroy(h); return rc; } \
-    } while (0)
-
-    if ((rc = dev_check(opts->device))) { delete h; return rc; }
-    BB_ENTER(h);
-    if ((rc = stream_open(&h->stream, h->be))) { delete h; return rc; }
-
-    // ---- shapes -----------------------------------------------------------------------------
-    long long n_l = 0, cnt = 0;
-    M.Ttot = 0; M.nt1 = 0; M.K = 0;
-    for (int r = 0; r < M.R; ++r) {
-        const int T = md->n_time[r];
-        if (T < 2 || T > 255) { bb_destroy(h); return bb_fail(BB_ERR_INVALID, "n_time[%d] = %d outside 2..255", r, T); }
-        M.T[r] = T;
-        M.Tmagic[r] = (unsigned)(0x100000000ull / (unsigned)T) + 1u;
-        M.Tmagic1[r] = T > 2 ? (unsigned)(0x100000000ull / (unsigned)(T - 1)) + 1u : 0u;   // T - 1 == 1: no division
-        M.off_t[r] = M.nt1;
-        M.cnt_off[r] = cnt;
-        M.kq[r] = M.K;
-        M.kqa[r] = M.K + T + 5 * (T - 1);
-        M.tcum[r] = M.Ttot;
-        M.Ttot += T;
-        M.nt1 += T - 1;
-        M.K += 6 * T - 5 + (M.quirk ? 2 * (T - 1) * (T - 1) : 0);
-        n_l += (long long)T * M.B;
-        cnt += (long long)T * M.B;
-    }
-    M.K += 2;
-    const bool has_env = md->kind == BB_MODEL_MULTIENV || md->kind == BB_MODEL_MULTIENV_REPLICATE;
-    if (has_env) {
-        if (md->n_env < 1 || !md->env_idx) { bb_destroy(h); return bb_fail(BB_ERR_INVALID, "multienv models need n_env >= 1 and env_idx"); }
-        for (int t = 0; t < M.Ttot; ++t)
-            if (md->env_idx[t] < 0 || md->env_idx[t] >= md->n_env) { bb_destroy(h); return bb_fail(BB_ERR_INVALID, "env_idx[%d] out of range", t); }
-    }
-    if (md->kind == BB_MODEL_GENOTYPE) {
-        if (md->n_geno < 1 || !md->geno_idx) { bb_destroy(h); return bb_fail(BB_ERR_INVALID, "genotype model needs n_geno >= 1 and geno_idx"); }
-        for (long long m = 0; m < M.nb; ++m)
-            if (md->geno_idx[m] < 0 || md->geno_idx[m] >= md->n_geno) { bb_destroy(h); return bb_fail(BB_ERR_INVALID, "geno_idx[%lld] out of range", m); }
-    }
-
-    // ---- flat layout, source order (model_*.jl `~` statements) -----------------
-    long long off = 0;
-    for (int k = 0; k < BK_COUNT; ++k) M.blk_lo[k] = M.blk_hi[k] = 0;
-    add_block(h, "s_pop", BK_SPOP, M.nt1, &off);
-    add_block(h, "logsigma_pop", BK_LSPOP, M.nt1, &off);
-    if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {
-        add_block(h, "s_bc", BK_S, M.nb * M.E, &off);
-        add_block(h, "logsigma_bc", BK_LS, M.nb * M.E, &off);
-    } else {
-        const long long E_ = M.kind == BB_MODEL_MULTIENV_REPLICATE ? M.E : 1;
-        if (cx.loglambda_first) add_block(h, "loglambda", BK_L, n_l, &off);          // (internal order only: bb_create)
-        add_block(h, "theta", BK_S, M.kind == BB_MODEL_GENOTYPE ? M.G : M.nb * E_, &off);
-        add_block(h, "theta_tilde", BK_TT, M.nb * M.R * E_, &off);
-        add_block(h, "logtau", BK_LT, M.nb * M.R * E_, &off);
-        add_block(h, "logsigma_bc", BK_LS, M.nb * M.R * E_, &off);
-    }
-    if (!(cx.loglambda_first && M.kind >= BB_MODEL_GENOTYPE)) add_block(h, "loglambda", BK_L, n_l, &off);
-    M.D = off;
-    M.Dp = (off + 7) & ~7ll;
-    for (int r = 0, o = 0; r < M.R; ++r) { M.off_l[r] = M.blk_lo[BK_L] + (long long)o * M.B; o += M.T[r]; }
-
-    // ---- counts: validate totals == row sums (Multinomial support, Distributions.jl), to uint32
-    std::vector<unsigned> c32((size_t)cnt);
-    double sum_lgamma = 0.0;
-    {
-        long long co = 0, to = 0;
-        for (int r = 0; r < M.R; ++r) {
-            const int T = M.T[r];
-            for (int t = 0; t < T; ++t) {
-                long long s = 0;
-                for (long long b = 0; b < M.B; ++b) {
-                    const int64_t v = md->counts[co + b * T + t];
-                    if (v < 0 || v > 0xFFFFFFFFll) { bb_destroy(h); return bb_fail(BB_ERR_INVALID, "count out of range at rep %d t %d barcode %lld", r, t, b); }
-                    c32[(size_t)(co + b * T + t)] = (unsigned)v;
-                    s += v;
-                    sum_lgamma += lgamma((double)v + 1.0);
-                }
-                if (s != md->totals[to + t]) {
-                    bb_destroy(h);
-                    return bb_fail(BB_ERR_INVALID, "totals[rep %d, t %d] = %lld but the counts sum to %lld (the reference's Multinomial term is -Inf there)",
-                                   r, t, (long long)md->totals[to + t], s);
-                }
-            }
-            co += (long long)T * M.B;
-            to += T;
-        }
-    }
-    unsigned* dcounts = nullptr;
-    BB_TRY(dalloc(h, &dcounts, (size_t)cnt));
-    BB_TRY(h2d(dcounts, c32.data(), (size_t)cnt * 4, h->stream));
-    M.counts = dcounts;
-
-    // the moment pivot (DevModel::piv): a function of the whole problem's counts, the same on every shard
-    std::vector<double> piv((size_t)M.Ttot, 0.0);
-    {
-        long long co = 0;
-        for (int r = 0; r < M.R; ++r) {
-            const int T = M.T[r];
-            const long long nb_ = M.nn > 0 ? M.nn : M.B;        // (no neutrals: all barcodes)
-            for (int t = 0; t + 1 < T; ++t) {
-                double s = 0.0;
-                for (long long b = 0; b < nb_; ++b)
-                    s += log((double)md->counts[co + b * T + t + 1] + 0.5) - log((double)md->counts[co + b * T + t] + 0.5);
-                piv[(size_t)(M.tcum[r] + t)] = s / (double)nb_;
-            }
-            co += (long long)T * M.B;
-        }
-    }
-    {
-        double* d = nullptr;
-        BB_TRY(dalloc(h, &d, (size_t)M.Ttot));
-        BB_TRY(h2d(d, piv.data(), (size_t)M.Ttot * 8, h->stream));
-        M.piv = d;
-    }
-
-    if (has_env) {
-        int* d = nullptr;
-        BB_TRY(dalloc(h, &d, (size_t)M.Ttot));
-        BB_TRY(h2d(d, md->env_idx, (size_t)M.Ttot * 4, h->stream));
-        M.env_idx = d;
-    }
-    if (md->kind == BB_MODEL_GENOTYPE) {
-        int *d = nullptr, *dp = nullptr, *dm = nullptr;
-        BB_TRY(dalloc(h, &d, (size_t)M.nb));
-        BB_TRY(h2d(d, md->geno_idx, (size_t)M.nb * 4, h->stream));
-        M.geno_idx = d;
-        std::vector<int> ptr((size_t)M.G + 1, 0), mem((size_t)M.nb);
-        for (long long m = 0; m < M.nb; ++m) ptr[(size_t)md->geno_idx[m] + 1]++;
-        for (int g = 0; g < M.G; ++g) ptr[(size_t)g + 1] += ptr[(size_t)g];
-        std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-        for (long long m = 0; m < M.nb; ++m) mem[(size_t)fill[(size_t)md->geno_idx[m]]++] = (int)m;
-        BB_TRY(dalloc(h, &dp, (size_t)M.G + 1));
-        BB_TRY(dalloc(h, &dm, (size_t)M.nb));
-        BB_TRY(h2d(dp, ptr.data(), ((size_t)M.G + 1) * 4, h->stream));
-        BB_TRY(h2d(dm, mem.data(), (size_t)M.nb * 4, h->stream));
-        M.geno_ptr = dp;
-        M.geno_mem = dm;
-        M.geno_sorted = 1;
-        for (long long m = 1; m < M.nb; ++m) if (md->geno_idx[m] < md->geno_idx[m - 1]) { M.geno_sorted = 0; break; }
-        h->geno_ptr_h = ptr;
-    }
-
-    // ---- priors (defaults: model_fitness_normal.jl:125-129, ..._genotypes.jl:162) -------------
-    double sum_log_std = 0.0;
-    BB_TRY(upload_prior(h, BK_SPOP, &md->s_pop_prior, 0.0, 2.0, "s_pop_prior", false, &sum_log_std));
-    BB_TRY(upload_prior(h, BK_LSPOP, &md->logsigma_pop_prior, 0.0, 1.0, "logsigma_pop_prior", false, &sum_log_std));
-    BB_TRY(upload_prior(h, BK_S, &md->s_bc_prior, 0.0, 2.0, "s_bc_prior", false, &sum_log_std));
-    BB_TRY(upload_prior(h, BK_LS, &md->logsigma_bc_prior, 0.0, 1.0, "logsigma_bc_prior", false, &sum_log_std));
-    BB_TRY(upload_prior(h, BK_L, &md->loglambda_prior, 3.0, 3.0, "loglambda_prior", false, &sum_log_std));
-    if (M.kind >= BB_MODEL_GENOTYPE) {
-        BB_TRY(upload_prior(h, BK_TT, nullptr, 0.0, 1.0, "theta_tilde", true, &sum_log_std));
-        BB_TRY(upload_prior(h, BK_LT, &md->logtau_prior, -2.0, 1.0, "logtau_prior", true, &sum_log_std));
-    }
-    // constant part of the ELBO: prior normalisers, likelihood normalisers, lgamma terms, entropy constant
-    {
-        double nlik = 0.0;
-        for (int r = 0; r < M.R; ++r) nlik += (double)(M.T[r] - 1) * (double)M.B;
-        h->elbo_const = -sum_log_std - 0.5 * BB_LOG2PI * (double)M.D - sum_lgamma - 0.5 * BB_LOG2PI * nlik +
-                        0.5 * (double)M.D * (1.0 + BB_LOG2PI);
-    }
-
-    // ---- shard + launch geometry -------------------------------------------------------------
-    h->b_lo = M.B * opts->rank / opts->world_size;
-    h->b_hi = M.B * (opts->rank + 1) / opts->world_size;
-    h->g_lo = 0;
-    h->g_hi = M.G;
-    if (M.kind == BB_MODEL_GENOTYPE && M.geno_sorted && opts->world_size > 1) {
-        // Genotypes in consecutive runs: cut the shards at genotype boundaries, so that every rank holds ALL mutants of the
-        // genotypes it owns -- d/dtheta_g is then a rank-local sum.  The cut moves back to the first mutant
-        // of the genotype it fell into; genotypes without mutants go with the one before.
-        auto snap = [&](long long b, int* g) {
-            if (b <= 0) { *g = 0; return (long long)0; }
-            if (b >= M.B) { *g = M.G; return M.B; }
-            if (b <= M.nn) { *g = 0; return b; }
-            const int gg = md->geno_idx[b - M.nn];
-            *g = gg;
-            return M.nn + (long long)h->geno_ptr_h[(size_t)gg];
-        };
-        h->b_lo = snap(h->b_lo, &h->g_lo);
-        h->b_hi = snap(h->b_hi, &h->g_hi);
-        if (h->b_lo <= M.nn) h->g_lo = 0;          // (genotype ranges tile [0, G): whoever owns the first mutant also owns the empty ones before it)
-    }
-    {
-        // One workgroup per CU (XCD-agnostic: every tile is independent), sized so that the whole
-        // shard is resident at once: NB = ceil(barcodes / CUs) barcodes per tile, up to 1024 threads
-        // (16 waves per CU) working a tile's ~NB*(T+2) latents.  BB_TUNE_* env vars override for experiments.
-        int maxT = 0;
-        for (int r = 0; r < M.R; ++r) maxT = std::max(maxT, M.T[r]);
-        h->cus = dev_cus(opts->device, h->cus);
-        const long long nbar = std::max<long long>(h->b_hi - h->b_lo, 1);
-        int NB = (int)std::max<long long>((nbar + h->cus - 1) / h->cus, 32);
-        if (h->tune.nb > 0) NB = h->tune.nb;
-        const size_t lds_cap = (size_t)160 * 1024;
-        int nthr = 0;
-        for (;;) {
-            // one pair of latents per thread is the sweet spot; counted with the segments' rounding (tile_pairs_bound), the
-            // number the resident launch sizes its per-thread state by (a tile of 257 pairs on 256 threads would need two)
-            const long long pairs = tile_pairs_bound(M, NB);
-            // > 1 pair per thread: 512 threads (256-VGPR budget, up to 4 pairs) beat 1024 threads with spills (C3: 28.8k vs 18.8k steps/s)
-            // (768 threads x 2 pairs was tried for C3: 138 spills at 168 VGPRs, 23.0k vs 28.8k steps/s for 512 x 3)
-            nthr = pairs > 2048 ? 1024 : (pairs > 1024 ? 512 : (pairs > 512 ? 1024 : (pairs > 256 ? 512 : 256)));
-            if (h->tune.nthr) nthr = h->tune.nthr;
-            while (nthr < maxT) nthr <<= 1;
-            const size_t need = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr).total * 8;
-            if ((need <= lds_cap && (long long)NB * maxT < 65536) || NB <= 8) break;
-            NB = (NB + 1) / 2;
-        }
-        const size_t need = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr).total * 8;
-        if (need > 160 * 1024 || nthr > 1024 || (long long)NB * maxT >= 65536) {
-            bb_destroy(h);
-            return bb_fail(BB_ERR_UNSUPPORTED, "a tile of %d barcodes needs %zu bytes of LDS / %d threads (n_time or n_rep too large for this build)", NB, need, nthr);
-        }
-        h->NB = NB;
-        h->nthr = nthr;
-        h->lds_doubles = need / 8;
-        h->lds_doubles_p0 = h->lds_doubles_p = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr, 1).total;
-        h->nblk = (int)((nbar + NB - 1) / NB);
-        h->tile_cap = h->nblk + 8;
-        h->ngeno_blk = M.G > 0 ? (int)std::min<long long>(((M.G + 1) / 2 + 255) / 256, 64) : 0;
-    }
-
-    // ---- state ---------------------------------------------------------------------------------
-    DevState& S = h->S;
-    const size_t D = (size_t)M.D;
-    BB_TRY(dalloc(h, &S.mu, D + 2));
-    BB_TRY(dalloc(h, &S.om, D + 2));
-    BB_TRY(dalloc(h, &S.acc_mu, D + 2));
-    BB_TRY(dalloc(h, &S.acc_om, D + 2));
-    BB_TRY(dalloc(h, &S.accl, 2 * D + 8));
-    {
-        double* oc = nullptr;
-        const double v[8] = {opts->eta, opts->tau, opts->pre, opts->post, 0, 0, 0, 0};
-        BB_TRY(dalloc(h, &oc, 8));
-        BB_TRY(h2d(oc, v, sizeof v, h->stream));
-        S.optc = oc;
-    }
-    // (zsv, asv, hsv, gacc_*, bak_*: per-sample scratch of the two-kernel step and of bb_elbo_grad -- ensure_scratch, on first use: a
-    //  shard that only ever runs the resident launch never pays their 7 x 8 D bytes)
-    hist_rows(h);
-    if (opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD) BB_TRY(dalloc(h, &S.hist, (size_t)opts->window * 2 * (size_t)M.Dh + 8));   // (+ 8: an edge pair's prefetch reads both halves)
-    BB_TRY(dalloc(h, &S.partials, (size_t)M.K * (size_t)h->nblk));
-    BB_TRY(dalloc(h, &S.totals, (size_t)M.K));
-    BB_TRY(dalloc(h, &S.zg, (size_t)2 * M.nt1));
-    BB_TRY(dalloc(h, &S.gbar, (size_t)32 * 10));
-    BB_TRY(hostmap_alloc(&h->hstatus, &S.hstatus, 16));
-    BB_TRY(dalloc(h, &S.prow, (size_t)h->tile_cap * (M.K + 2 * M.nt1)));
-    BB_TRY(dalloc(h, &S.xrow, (size_t)2 * BB_NG_MAX * (M.K + 2 * M.nt1)));
-    BB_TRY(dalloc(h, &S.grow, (size_t)(h->tile_cap + 16 * BB_NG_MAX) * bb_row_stride(M.K + 2 * M.nt1)));      // (+ 16 groups x 16: a leader's eight loads in flight run past its last member, bb_gran_poll8)
-    BB_TRY(dalloc(h, &S.gxrow, (size_t)2 * BB_NG_MAX * (M.K + 2 * M.nt1)));
-    BB_TRY(dalloc(h, &S.rdy, (size_t)32 * (h->tile_cap + 2 * BB_NG_MAX)));
-    BB_TRY(dalloc(h, &S.xtab, (size_t)BB_NG_MAX));
-    BB_TRY(dalloc(h, &S.xsel, (size_t)h->tile_cap));
-    BB_TRY(dalloc(h, &S.ztheta, (size_t)std::max(M.G, 1)));
-    BB_TRY(dalloc(h, &S.gsum, (size_t)std::max(M.G, 1)));
-    BB_TRY(dalloc(h, &S.ds, (size_t)M.nb));
-    BB_TRY(dalloc(h, &S.geno_el, (size_t)std::max(h->ngeno_blk, 1)));
-    BB_TRY(dalloc(h, &S.elbo_ring, (size_t)BB_ELBO_RING));
-    BB_TRY(dalloc(h, &S.elbo_sample, (size_t)opts->samples_per_step + 64));
-    BB_TRY(dalloc(h, &S.ctr, (size_t)2));
-    BB_TRY(dalloc(h, &S.stamps, (size_t)h->tile_cap * (32 + 64)));
-    S.eps_in = nullptr;
-
-    // algorithmic bytes per step on this shard: theta r+w, optimiser state r+w, counts
-    {
-        const long long nb_sh = h->b_hi - h->b_lo;
-        double frac = (double)nb_sh / (double)M.B;
-        const double Dsh = (double)M.D * frac;
-        const double cnts = 4.0 * (double)cnt * frac;
-        h->bytes_sample = (int64_t)(16.0 * Dsh + cnts);
-        const double optb = opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD ? 64.0 : 32.0;
-        h->bytes_update = (int64_t)((16.0 + 16.0 + optb) * Dsh + cnts);
-    }
-    BB_TRY(setup_persistent(h, h->o.launch_mode));
-    BB_TRY(sync_descriptors(h));
-    BB_TRY(bb_init_meanfield(h));
-    *out = h;
-    return BB_OK;
-}
-
-
-// ---- caller's order <-> the handle's order (genotype model with geno_idx not in runs) ------------------------------------------
-static void perm_gather(const bb_handle* h, const double* caller, double* internal) {
-    const size_t D = h->cidx.size();
-    for (size_t i = 0; i < D; ++i) internal[i] = caller[(size_t)h->cidx[i]];
-}
-static void perm_scatter(const bb_handle* h, const double* internal, double* caller) {
-    const size_t D = h->cidx.size();
-    for (size_t i = 0; i < D; ++i) caller[(size_t)h->cidx[i]] = internal[i];
-}
-
-// The reference hands barcodes over in order of appearance (utils.data_to_arrays, src/utils.jl:692-731), so a genotype's mutants
-// are scattered; the resident launch and genotype-aligned shards need them in consecutive runs (a tile / shard owns whole
-// genotypes and their theta).  The library groups them itself -- a stable sort of the mutants by genotype -- works in that order
-// and presents the caller's at every entry point that takes or returns a latent vector (bb_get_params / posterior / set_params /
-// elbo_grad / logdensity_grad / hier_fitness; bb_get_permutation tells the mapping).  The engine's normal stream is keyed by the
-// INTERNAL index (bb_debug_normals likewise).
-extern "C" int bb_create(const bb_model_desc* md, const bb_advi_opts* opts, bb_handle** out) {
-    if (!md || !opts || !out) return bb_fail(BB_ERR_INVALID, "null argument");
-    const bool geno_ok = md->kind == BB_MODEL_GENOTYPE && md->geno_idx && md->n_bc > 1 && md->n_geno >= 1 && md->n_neutral >= 1 && md->n_time &&
-                         md->counts && md->n_rep == 1 && md->n_time[0] >= 2 && md->n_time[0] <= 255;
-    CreateCtx cx{read_tuning(), false};
-    bool regroup = geno_ok && !cx.tune.no_regroup;
-    if (regroup) {
-        bool sorted = true, valid = true;
-        for (long long m = 0; m < md->n_bc && valid; ++m) {
-            if (md->geno_idx[m] < 0 || md->geno_idx[m] >= md->n_geno) valid = false;
-            else if (m > 0 && md->geno_idx[m] < md->geno_idx[m - 1]) sorted = false;
-        }
-        regroup = valid && !sorted;      // (anything invalid: create_inner says what)
-    }
-    // Round 4: the genotype model's flat vector s_pop | logsigma_pop | theta (G) | theta_tilde | logtau | logsigma_bc (n_bc each) | loglambda puts
-    // loglambda at an ODD index whenever G + n_bc is odd; k_res's pairs (b, 2k), (b, 2k+1) are then not pairs (2q, 2q+1) of the flat index and
-    // the any-parity instances ran (two Philox draws in divergent lanes, 8-byte accesses, 40 spilled registers: C5's rank shape 14.95 against
-    // 12.8 us).  The library owns an internal order anyway: it lays loglambda out right behind the two global blocks (offset 2 (T - 1): even
-    // for even T) and presents the reference's order at every entry point, as for the regrouped mutants.  BB_NO_REORDER=1: as handed over.
-    cx.loglambda_first = geno_ok && !(md->n_time[0] & 1) && ((md->n_geno + md->n_bc) & 1) && !cx.tune.no_reorder;
-    if (!regroup && !cx.loglambda_first) return create_inner(md, opts, cx, out);
-    const long long nn = md->n_neutral, nb = md->n_bc, B = nn + nb;
-    const int T = md->n_time[0];
-    std::vector<int> perm((size_t)nb);
-    for (long long m = 0; m < nb; ++m) perm[(size_t)m] = (int)m;
-    if (regroup) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return md->geno_idx[a] < md->geno_idx[b]; });
-    auto src = [&](long long b) { return b < nn ? b : nn + perm[(size_t)(b - nn)]; };
-    bb_model_desc md2 = *md;
-    std::vector<int64_t> counts2;
-    std::vector<int32_t> geno2;
-    std::vector<double> lsm, lss, llm, lls;
-    if (regroup) {
-        counts2.resize((size_t)B * T);
-        for (long long b = 0; b < B; ++b) memcpy(&counts2[(size_t)b * T], md->counts + src(b) * T, (size_t)T * sizeof(int64_t));
-        geno2.resize((size_t)nb);
-        for (long long m = 0; m < nb; ++m) geno2[(size_t)m] = md->geno_idx[perm[(size_t)m]];
-        md2.counts = counts2.data();
-        md2.geno_idx = geno2.data();
-        // Matrix-form priors of the per-mutant and per-(time, barcode) blocks move with their barcodes (checked first: a message names
-        // the element where the caller put it)
-        if (md->logsigma_bc_prior.n == nb && check_prior(&md->logsigma_bc_prior, "logsigma_bc_prior")) return BB_ERR_INVALID;
-        if (md->loglambda_prior.n == (int64_t)B * T && check_prior(&md->loglambda_prior, "loglambda_prior")) return BB_ERR_INVALID;
-        if (md->logsigma_bc_prior.mean && md->logsigma_bc_prior.std && md->logsigma_bc_prior.n == nb && nb > 1) {
-            lsm.resize((size_t)nb); lss.resize((size_t)nb);
-            for (long long m = 0; m < nb; ++m) { lsm[(size_t)m] = md->logsigma_bc_prior.mean[perm[(size_t)m]]; lss[(size_t)m] = md->logsigma_bc_prior.std[perm[(size_t)m]]; }
-            md2.logsigma_bc_prior.mean = lsm.data(); md2.logsigma_bc_prior.std = lss.data();
-        }
-        if (md->loglambda_prior.mean && md->loglambda_prior.std && md->loglambda_prior.n == (int64_t)B * T && B * T > 1) {
-            llm.resize((size_t)B * T); lls.resize((size_t)B * T);
-            for (long long b = 0; b < B; ++b)
-                for (int t = 0; t < T; ++t) { llm[(size_t)b * T + t] = md->loglambda_prior.mean[src(b) * T + t]; lls[(size_t)b * T + t] = md->loglambda_prior.std[src(b) * T + t]; }
-            md2.loglambda_prior.mean = llm.data(); md2.loglambda_prior.std = lls.data();
-        }
-    }
-    int rc = create_inner(&md2, opts, cx, out);
-    if (rc) return rc;
-    bb_handle* h = *out;
-    const DevModel& M = h->M;
-    if (regroup) h->perm_m = perm;
-    // the caller's layout: the reference's source order (what bb_get_layout reports), and the map internal -> caller
-    const int order[BK_COUNT] = {BK_SPOP, BK_LSPOP, BK_S, BK_TT, BK_LT, BK_LS, BK_L};
-    long long clo[BK_COUNT] = {0};
-    {
-        std::vector<bb_block_range> cb;
-        long long off = 0;
-        for (int k : order) {
-            bb_block_range b;
-            memset(&b, 0, sizeof b);
-            for (const bb_block_range& ib : h->blocks) if (ib.lo == M.blk_lo[k] && ib.hi == M.blk_hi[k] && ib.hi > ib.lo) snprintf(b.name, sizeof b.name, "%s", ib.name);
-            clo[k] = off;
-            b.lo = off;
-            b.hi = off + (M.blk_hi[k] - M.blk_lo[k]);
-            off = b.hi;
-            cb.push_back(b);
-        }
-        h->blocks = cb;
-    }
-    h->cidx.resize((size_t)M.D);
-    for (int k : order)
-        for (long long j = 0; j < M.blk_hi[k] - M.blk_lo[k]; ++j) h->cidx[(size_t)(M.blk_lo[k] + j)] = clo[k] + j;
-    if (regroup) {
-        for (int k : {BK_TT, BK_LT, BK_LS})
-            for (long long m = 0; m < nb; ++m) h->cidx[(size_t)(M.blk_lo[k] + m)] = clo[k] + perm[(size_t)m];
-        for (long long b = nn; b < B; ++b)
-            for (int t = 0; t < T; ++t) h->cidx[(size_t)(M.blk_lo[BK_L] + b * T + t)] = clo[BK_L] + src(b) * T + t;
-    }
-    return BB_OK;
-}
+#include "bb_create.h"      // handle creation: bb_default_opts, create_inner and its stages, the caller's order, bb_create; hist_rows, owned_ranges
 
 // caller indices of the latents THIS handle owns on a sharded run (its barcodes' latents; genotype model: theta of its own genotypes) -- what
 // a gather of the ranks' posteriors takes from this rank.  The replicated global blocks are not in the list.  idx: [bb_num_latents(h)].
@@ -1489,6 +926,7 @@ static void group_destroy(bb_handle* g);
 extern "C" void bb_destroy(bb_handle* h) {
     if (!h) return;
     if (!h->shards.empty()) { group_destroy(h); return; }
+    if (!h->opened) { delete h; return; }      // under construction, refused before its stream was open (or a group without a shard yet)
     BB_ENTER(h);
     stream_quiesce(h->stream, h->be);
     p2p_release(h);
@@ -1715,26 +1153,6 @@ static int p2p_alloc_inbox(bb_handle* h);
 static int p2p_wire(bb_handle* h, void* const* bases);
 static int p2p_probe_launch(bb_handle* h, unsigned** res);
 static int p2p_probe_collect(bb_handle* h, unsigned* res, int32_t* ok);
-static void owned_ranges(const bb_handle* sh, std::vector<std::pair<long long, long long>>& out) {
-    const DevModel& M = sh->M;
-    const long long b_lo = sh->b_lo, b_hi = sh->b_hi;
-    const long long m_lo = std::max(b_lo, M.nn) - M.nn, m_hi = std::max(b_hi, M.nn) - M.nn;
-    for (int r = 0; r < M.R; ++r) out.push_back({M.off_l[r] + b_lo * M.T[r], M.off_l[r] + b_hi * M.T[r]});
-    if (M.kind == BB_MODEL_GENOTYPE && sh->g_hi > sh->g_lo) out.push_back({M.blk_lo[BK_S] + sh->g_lo, M.blk_lo[BK_S] + sh->g_hi});   // theta of its own genotypes
-    if (m_hi <= m_lo) return;
-    if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {
-        out.push_back({M.blk_lo[BK_S] + m_lo * M.E, M.blk_lo[BK_S] + m_hi * M.E});
-        out.push_back({M.blk_lo[BK_LS] + m_lo * M.E, M.blk_lo[BK_LS] + m_hi * M.E});
-    } else if (M.kind == BB_MODEL_GENOTYPE) {      // (theta: above -- sharded by genotype where the cuts allow, else all shards hold all of it)
-        for (int k : {BK_TT, BK_LT, BK_LS}) out.push_back({M.blk_lo[k] + m_lo, M.blk_lo[k] + m_hi});
-    } else {
-        const long long E_ = M.kind == BB_MODEL_MULTIENV_REPLICATE ? M.E : 1;
-        out.push_back({M.blk_lo[BK_S] + m_lo * E_, M.blk_lo[BK_S] + m_hi * E_});
-        for (int r = 0; r < M.R; ++r)
-            for (int k : {BK_TT, BK_LT, BK_LS}) out.push_back({M.blk_lo[k] + (r * M.nb + m_lo) * E_, M.blk_lo[k] + (r * M.nb + m_hi) * E_});
-    }
-}
-
 static void group_destroy(bb_handle* g) {
     for (bb_handle* sh : g->shards) bb_destroy(sh);
     g->shards.clear();
@@ -1742,10 +1160,9 @@ static void group_destroy(bb_handle* g) {
 }
 
 static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const CreateCtx& cx, bb_handle** out) {
-    const int n = opts->n_devices;
-    if (n > BB_MAX_WORLD) return bb_fail(BB_ERR_UNSUPPORTED, "at most %d devices per handle", BB_MAX_WORLD);
-    if (opts->world_size != 1 || opts->rank != 0) return bb_fail(BB_ERR_INVALID, "n_devices > 1 needs rank 0 / world_size 1 (the handle shards by itself)");
-    bb_handle* g = new bb_handle();
+    const int n = opts->n_devices;          // (2..BB_MAX_WORLD, rank 0 of 1: check_request)
+    HandleOwner own(new bb_handle());
+    bb_handle* g = own.get();
     g->o = *opts;
     g->o.device = opts->device_ids ? opts->device_ids[0] : 0;
     g->tune = cx.tune;
@@ -1764,7 +1181,7 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const
         if (!rc && memcmp(sh->M.blk_lo, g->shards[0]->M.blk_lo, sizeof sh->M.blk_lo))
             rc = bb_fail(BB_ERR_INVALID, "shard %d lays the latents out differently from shard 0", i);
     }
-    if (rc) { group_destroy(g); return rc; }
+    if (rc) return rc;
     g->M = g->shards[0]->M;                      // (host-side copies of shapes and block ranges; the device pointers inside are shard 0's)
     g->blocks = g->shards[0]->blocks;
     g->b_lo = 0;
@@ -1799,10 +1216,9 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const
     g->group_resident = ok;
     if (!ok && opts->launch_mode == 2) {
         const std::string why(g_err);                 // (bb_fail formats INTO g_err: the message must not be its own argument)
-        group_destroy(g);
         return bb_fail(BB_ERR_UNSUPPORTED, "launch_mode = 2: the shards cannot run resident launches with peer-mapped inboxes: %s", why.c_str());
     }
-    *out = g;
+    *out = own.release();
     return BB_OK;
 }
 
