@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
-// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h) and bb_chain_summary (bb_chain.h).  None of them
-// touches the step loop.
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb (bb_rb.h) and bb_chain_summary
+// (bb_chain.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -229,11 +229,12 @@ struct BandsCall {
     explicit BandsCall(bb_handle* h) : dh(sampling_handle(h)), guard(dh->o.device) {}
 };
 // The front of a band call: the options checked, the posterior gathered, everything of P but the device pointers (the model's shape,
-// the blocks' caller offsets, the targets of n_rows x n_steps bands), the grids.
+// the blocks' caller offsets, the targets of n_rows x n_steps bands), the grids.  quantiles == nullptr: the front of a call that takes
+// the same draws but forms no bands (bb_fitness_rb): no band options to check, no targets, K = n_samples n_ppc >= 1 as its caller checked.
 static int bands_prologue(bb_handle* h, int32_t n_samples, int32_t n_ppc, int32_t n_q, const double* quantiles, uint64_t seed,
                           long long n_rows, int n_steps, PpcArgs& P, BandsCall& B) {
-    long long K;
-    int rc = ppc_check(n_samples, n_ppc, n_q, quantiles, &K);
+    long long K = (long long)n_samples * n_ppc;
+    int rc = quantiles ? ppc_check(n_samples, n_ppc, n_q, quantiles, &K) : BB_OK;
     if (rc) return rc;
     const DevModel& M = B.dh->M;
     const size_t D = (size_t)h->M.D;
@@ -264,13 +265,15 @@ static int bands_prologue(bb_handle* h, int32_t n_samples, int32_t n_ppc, int32_
     P.lo_lt = hier ? ppc_block(h, "logtau") : 0;
     if (P.lo_spop < 0 || P.lo_lspop < 0 || P.lo_s < 0 || P.lo_ls < 0 || P.lo_tt < 0 || P.lo_lt < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
     // band end e = 2 qi + upper of the central mass q: the tail probabilities (1 - q) / 2 and 1 - (1 - q) / 2
-    double probs[2 * BB_PPC_MAX_Q];
-    for (int e = 0; e < 2 * n_q; ++e) {
-        const double q = quantiles[e >> 1];
-        probs[e] = (e & 1) ? 1.0 - (1.0 - q) / 2.0 : (1.0 - q) / 2.0;
+    if (quantiles) {
+        double probs[2 * BB_PPC_MAX_Q];
+        for (int e = 0; e < 2 * n_q; ++e) {
+            const double q = quantiles[e >> 1];
+            probs[e] = (e & 1) ? 1.0 - (1.0 - q) / 2.0 : (1.0 - q) / 2.0;
+        }
+        quantile_plan(K, probs, 2 * n_q, P);
+        B.nbands = (size_t)n_rows * n_steps * n_q * 2;
     }
-    quantile_plan(K, probs, 2 * n_q, P);
-    B.nbands = (size_t)n_rows * n_steps * n_q * 2;
     // row program: two workgroups per CU at most, the per-block scratch (P.par) bounded to 256 MiB
     B.nblk = std::min<long long>(n_rows, 2LL * B.dh->cus);
     while (B.nblk > 1 && (size_t)B.nblk * P.E * 2 * (size_t)n_samples * 8 > ((size_t)256 << 20)) B.nblk = (B.nblk + 1) / 2;
@@ -371,6 +374,36 @@ extern "C" int bb_freq_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_col
     return BB_OK;
 }
 
+// The normalisers' side of F (F.P filled by bands_prologue): the shape, the loglambda offsets and *zb, the normaliser rows in flight
+// (their chunk partials bounded to 256 MiB).  Shared by bb_freq_bands and bb_fitness_rb.
+static int freq_plan(const bb_handle* h, const DevModel& M, int mode, FreqArgs& F, int* zb) {
+    F.mode = mode;
+    F.B = M.B;
+    F.nn = M.nn;
+    F.nchunks = (int)((M.B + BB_FREQ_CHUNK - 1) / BB_FREQ_CHUNK);
+    F.nz = mode == BB_FREQ_TRAJECTORY ? M.R : M.Ttot;
+    const long long lo_l = ppc_block(h, "loglambda");
+    if (lo_l < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    for (int r = 0; r < M.R; ++r) F.off_l[r] = lo_l + (long long)M.tcum[r] * M.B;
+    *zb = F.nz;
+    while (*zb > 1 && (size_t)F.nchunks * *zb * (size_t)F.P.n_samples * 8 > ((size_t)256 << 20)) *zb = (*zb + 1) / 2;
+    return BB_OK;
+}
+// F.Z filled, zb normaliser rows at a time (F.Z and F.zpart placed by the caller's layout)
+static int freq_normalisers(bb_handle* dh, FreqArgs& F, int zb) {
+    const size_t ns = (size_t)F.P.n_samples, np2 = (ns + 1) / 2;
+    int rc;
+    for (F.z0 = 0; F.z0 < F.nz; F.z0 = F.z1) {
+        F.z1 = std::min(F.nz, F.z0 + zb);
+        const size_t nzb = (size_t)(F.z1 - F.z0);
+        const int g1 = (int)std::max<size_t>(1, std::min<size_t>(((size_t)F.nchunks * nzb * np2 + 255) / 256, 65536));
+        const int g2 = (int)std::max<size_t>(1, std::min<size_t>((nzb * ns + 255) / 256, 4096));
+        if ((rc = launch(dh->stream, k_freq_zpart, g1, 256, 0, F))) return rc;
+        if ((rc = launch(dh->stream, k_freq_zsum, g2, 256, 0, F))) return rc;
+    }
+    return BB_OK;
+}
+
 extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands, int64_t* n_outside) {
     if (!h || !o || !bands || !o->quantiles) return bb_fail(BB_ERR_INVALID, "null argument");
     if (o->mode != BB_FREQ_TRAJECTORY && o->mode != BB_FREQ_POSTERIOR) return bb_fail(BB_ERR_INVALID, "mode must be BB_FREQ_TRAJECTORY or BB_FREQ_POSTERIOR");
@@ -383,32 +416,14 @@ extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands,
     int rc = bands_prologue(h, o->n_samples, o->n_ppc, o->n_quantiles, o->quantiles, o->seed, (long long)M.R * M.B, freq_cols(h), P, B);
     if (rc) return rc;
     if (o->mode == BB_FREQ_POSTERIOR && o->n_ppc != 1) return bb_fail(BB_ERR_INVALID, "BB_FREQ_POSTERIOR takes n_ppc = 1");      // (the shared checks report first)
-    F.mode = o->mode;
-    F.B = M.B;
-    F.nn = M.nn;
-    F.nchunks = (int)((M.B + BB_FREQ_CHUNK - 1) / BB_FREQ_CHUNK);
-    F.nz = o->mode == BB_FREQ_TRAJECTORY ? M.R : M.Ttot;
-    const long long lo_l = ppc_block(h, "loglambda");
-    if (lo_l < 0) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
-    for (int r = 0; r < M.R; ++r) F.off_l[r] = lo_l + (long long)M.tcum[r] * M.B;
-    // normaliser rows in flight: their chunk partials bounded to 256 MiB
+    int zb;
+    if ((rc = freq_plan(h, M, o->mode, F, &zb))) return rc;
     const size_t ns = (size_t)P.n_samples;
-    int zb = F.nz;
-    while (zb > 1 && (size_t)F.nchunks * zb * ns * 8 > ((size_t)256 << 20)) zb = (zb + 1) / 2;
     rc = bands_buffers(h, P, B, [&](Carve& c) {
         c(F.Z, (size_t)M.Ttot * ns);                   // [Ttot][ns]
         c(F.zpart, (size_t)F.nchunks * zb * ns);       // [nchunks][zb][ns]
     });
-    if (rc) return rc;
-    const size_t np2 = (ns + 1) / 2;
-    for (F.z0 = 0; F.z0 < F.nz; F.z0 = F.z1) {
-        F.z1 = std::min(F.nz, F.z0 + zb);
-        const size_t nzb = (size_t)(F.z1 - F.z0);
-        const int g1 = (int)std::max<size_t>(1, std::min<size_t>(((size_t)F.nchunks * nzb * np2 + 255) / 256, 65536));
-        const int g2 = (int)std::max<size_t>(1, std::min<size_t>((nzb * ns + 255) / 256, 4096));
-        if ((rc = launch(dh->stream, k_freq_zpart, g1, 256, 0, F))) return rc;
-        if ((rc = launch(dh->stream, k_freq_zsum, g2, 256, 0, F))) return rc;
-    }
+    if (rc || (rc = freq_normalisers(dh, F, zb))) return rc;
     if (o->mode == BB_FREQ_TRAJECTORY && (rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
     if ((rc = launch(dh->stream, k_freq, (int)B.nblk, 1024, (size_t)bb_ppc_lds_doubles(P.K), F))) return rc;
     if ((rc = d2h(bands, P.bands, B.nbands * 8, dh->stream))) return rc;
@@ -491,6 +506,100 @@ extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score
     lap(5);
 #ifdef BB_SCORE_TIMES
     fprintf(stderr, "[bb_ppc_score %lld x %d, %d samples] observed %.3f ms, upload %.3f ms, pop %.3f ms, score %.3f ms, download %.3f ms\n", n_rows, n_steps, (int)o->n_samples, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
+}
+
+// ---- Rao-Blackwellised fitness marginals (bb_rb.h) ----------------------------------------------------------------------------------
+static_assert(BB_RB_MAX_SAMPLES == BB_RB_SAMPLES_CAP && BB_RB_MAX_SAMPLES <= BB_PPC_MAX_K, "bb_fitness_rb limits");
+static long long rb_units(const bb_handle* h) {
+    const DevModel& M = h->M;
+    const int E = (M.kind == BB_MODEL_MULTIENV || M.kind == BB_MODEL_MULTIENV_REPLICATE) ? M.E : 1;
+    return (long long)M.R * M.nb * E;
+}
+extern "C" int bb_fitness_rb_shape(const bb_handle* h, int64_t* n_units) {
+    if (!h || !n_units) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_units = rb_units(h);
+    return BB_OK;
+}
+
+extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    if (nq < 0 || nq > BB_RB_MAX_Q || (nq > 0 && !o->probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_RB_MAX_Q);
+    for (int i = 0; i < nq; ++i)
+        if (!(o->probs[i] > 0.0 && o->probs[i] < 1.0)) return bb_fail(BB_ERR_INVALID, "every prob must lie strictly between zero and one");
+    if (!std::isfinite(o->threshold)) return bb_fail(BB_ERR_INVALID, "threshold must be finite");
+    const int ns_lo = o->draws ? 1 : 2;
+    if (ns < ns_lo || ns > BB_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_RB_MAX_SAMPLES);
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    RbArgs A;
+    memset(&A, 0, sizeof A);
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const long long n_units = rb_units(h);
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
+    if (rc) return rc;
+    int zb;
+    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {         // (no regrouping for these kinds: the handle's order is the caller's)
+        const DevPrior& dp = M.pri[BK_S];
+        P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    }
+    A.nq = nq;
+    A.threshold = o->threshold;
+    A.n_units = n_units;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+#ifdef BB_RB_TIMES             // diagnostics (tools/fitness_rb_rate.py): the call's phases, each drained before the next starts
+    timespec ct[6];
+    double cms[5] = {0, 0, 0, 0, 0};
+    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] = (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int) {};
+#endif
+    lap(0);
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, nu = (size_t)n_units;
+    double* ddraws = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {        // (P.par, [nblk][E][2][ns], holds the [nblk][E + 1][ns] table of bb_block_rb)
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(A.unit, BB_RB_OUT * nu);                     // [6][n_units]
+        c(A.quant, BB_RB_MAX_Q * nu);                  // [n_units][8]
+        c(A.n_steps, (nu + 1) / 2);                    // [n_units] ints
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    A.ytab = P.par;
+    if (o->draws) {
+        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
+        P.draws = ddraws;
+        P.D = (long long)D;
+    }
+    lap(1);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    lap(2);
+    if ((rc = freq_normalisers(dh, F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
+    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z: every row of a replicate reads the same ones)
+    lap(3);
+    if ((rc = launch(dh->stream, k_rb, (int)B.nblk, BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), A))) return rc;
+    lap(4);
+    double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
+    for (int k = 0; k < BB_RB_OUT; ++k)
+        if (units[k] && (rc = d2h(units[k], A.unit + (size_t)k * nu, nu * 8, dh->stream))) return rc;
+    if (out->quantiles && nq) {
+        std::vector<double> q(BB_RB_MAX_Q * nu);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
+        for (size_t u = 0; u < nu; ++u) memcpy(out->quantiles + u * nq, q.data() + u * BB_RB_MAX_Q, (size_t)nq * 8);
+    }
+    if (out->n_steps && (rc = d2h(out->n_steps, A.n_steps, nu * 4, dh->stream))) return rc;
+    rc = dsync(dh->stream);
+    lap(5);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_fitness_rb %lld units, %d samples, %d quantiles] upload %.3f ms, pop %.3f ms, normalisers %.3f ms, rb %.3f ms, download %.3f ms\n", n_units, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
 #endif
     return rc;
 }

@@ -409,6 +409,14 @@ BB_KERNEL(BB_SCORE_NT, k_score, ScoreArgs A) {
     BB_CTX;
     bb_block_score(cx, A, BB_GRID);
 }
+BB_KERNEL(256, k_rb_logz, RbArgs A) {
+    BB_CTX;
+    bb_block_rb_logz(cx, A, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_rb, RbArgs A) {
+    BB_CTX;
+    bb_block_rb(cx, A, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

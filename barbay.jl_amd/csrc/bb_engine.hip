@@ -1,6 +1,6 @@
 // bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the step loop and its launch plans; handle
-// creation (bb_create) is in bb_create.h and the post-fit entry points (hier fitness, log-density batch, predictive bands, chain
-// summary) are in bb_analysis.h, both included below.
+// creation (bb_create) is in bb_create.h and the post-fit entry points (hier fitness, log-density batch, predictive bands and scores,
+// Rao-Blackwellised fitness marginals, chain summary) are in bb_analysis.h, both included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -19,6 +19,7 @@
 #include "bb_ppc.h"
 #include "bb_freq.h"
 #include "bb_score.h"
+#include "bb_rb.h"
 #include "bb_chain.h"
 #include "bb_logp.h"
 #include "bb_mathprobe.h"

@@ -66,13 +66,22 @@ BB_DEV void bb_block_freq_zpart(BBCtx& cx, const FreqArgs& F, int nblocks) {
             const int T = P.T[r];
             const long long b0 = (long long)c * BB_FREQ_CHUNK, b1 = b0 + BB_FREQ_CHUNK < F.B ? b0 + BB_FREQ_CHUNK : F.B;
             double s0 = 0.0, s1 = 0.0;
-            for (long long b = b0; b < b1; ++b) {
-                const long long i = F.off_l[r] + b * T + t;
-                double e0, e1;
-                bb_normal_pair(P.seed, (unsigned long long)i, (unsigned)jp, BB_STREAM_PPC_PARAM, &e0, &e1);
-                const double m = P.mean[i], sg = P.sigma[i];
-                s0 += bb_exp(fma(sg, e0, m));
-                s1 += bb_exp(fma(sg, e1, m));
+            if (P.draws) {                   // explicit draws (bb_fitness_rb): the same chunk, the same order
+                const int j1 = 2 * jp + 1 < ns ? 2 * jp + 1 : 2 * jp;
+                for (long long b = b0; b < b1; ++b) {
+                    const long long i = F.off_l[r] + b * T + t;
+                    s0 += bb_exp(bb_ppc_param(P, i, 2 * jp));
+                    s1 += bb_exp(bb_ppc_param(P, i, j1));
+                }
+            } else {
+                for (long long b = b0; b < b1; ++b) {
+                    const long long i = F.off_l[r] + b * T + t;
+                    double e0, e1;
+                    bb_normal_pair(P.seed, (unsigned long long)i, (unsigned)jp, BB_STREAM_PPC_PARAM, &e0, &e1);
+                    const double m = P.mean[i], sg = P.sigma[i];
+                    s0 += bb_exp(fma(sg, e0, m));
+                    s1 += bb_exp(fma(sg, e1, m));
+                }
             }
             double* o = F.zpart + ci * ns;
             o[2 * jp] = s0;

@@ -51,10 +51,17 @@ struct PpcArgs {
     int plo[2 * BB_PPC_MAX_Q];               // band end e (= 2 qi + upper): index into tgt of its lower order statistic (upper: +1)
     double gam[2 * BB_PPC_MAX_Q];            // ... and its interpolation weight
     unsigned long long seed;
+    // bb_fitness_rb (bb_rb.h) only; all zero in every other call, which then runs exactly as before
+    const double* draws;      // [n_samples][D] explicit draws in the caller's order, read in place of the Philox draw; nullptr: none
+    long long D;              // ... and their row length
+    const double* pri_mean_e; // s_bc prior, Matrix form (device, caller order = the handle's for the kinds that have one): mean,
+    const double* pri_ivar_e; // 1 / std^2; nullptr: the Vector form below
+    double pri_mean, pri_ivar;
 };
 
 // parameter draw j of the caller's latent i
 BB_DEV double bb_ppc_param(const PpcArgs& P, long long i, int j) {
+    if (P.draws) return P.draws[(long long)j * P.D + i];      // (a strided read: sample-major rows, as a chain comes)
     double a, b;
     bb_normal_pair(P.seed, (unsigned long long)i, (unsigned)(j >> 1), BB_STREAM_PPC_PARAM, &a, &b);
     return fma(P.sigma[i], (j & 1) ? b : a, P.mean[i]);

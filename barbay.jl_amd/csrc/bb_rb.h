@@ -1,0 +1,231 @@
+// bb_rb.h -- Rao-Blackwellised marginals of the mutants' fitness on the device.  Entry point bb_fitness_rb (include/barbay_hip.h,
+// where the formulas are); no reference counterpart.
+//
+// Given everything else, a mutant's fitness s_u enters the log-joint through a Gaussian prior and Gaussian log-frequency-ratio terms
+// only (model_fitness_normal.jl:262-270 and its four siblings), so its full conditional is N(m, sd) in closed form.  A sample
+// j < n_samples is the joint posterior draw of bb_ppc.h (same keying, BB_STREAM_PPC_PARAM) or row j of the caller's draws; the
+// conditionals N(m_j, sd_j) of a unit u = (r, m, e) are averaged over j: moments, both tails at a threshold, quantiles of the mixture.
+//
+// Phases of a call (bb_analysis.h): bb_block_ppc_pop (sbar_{t,j}), bb_block_freq_zpart / _zsum (Z_{r,t,j}, every time point, summed by
+// bb_freq.h's rule), bb_block_rb_logz (ln Z in place, once: the rows of a replicate all read the same ones), then the row program:
+//   bb_block_rb : one workgroup of BB_SCORE_NT threads per mutant row (r, m), row += nblocks.
+//     Y  per draw one walk over the row's T_r loglambda draws: gamma_t = (ll_{t+1} - ll_t) - (log Z_{t+1} - log Z_t) and
+//        y_e += gamma_t + sbar_t for e = env(t + 1), ascending t.  The E running sums of a draw live in the block's slice of a global
+//        table ytab[E + 1][n_samples] (row E: the unit's s_j), not in a per-thread array: indexed by a run-time environment such an
+//        array would be scratch memory.  A draw j is always lane j mod NT's, so every table entry is read by the thread that wrote it.
+//     per environment e (unit u = e + E m + E nb r):
+//     A  s_j, m_j, sd_j (m, sd kept in LDS)            -> sum s, sum m, sum sd^2
+//     B  centred second moments                        -> sum (s - q_mean)^2, sum (m - rb_mean)^2, max m
+//     C  both tails at the threshold, through erfc     -> their sums, max -m
+//     D  (n_quantiles > 0)                             -> max sd
+//     Q  bisection of the mixture CDF, 64 iterations: the reduction has three slots, so one sweep over the draws advances up to three
+//        quantiles, ceil(n_q / 3) sweeps per iteration; every quantile of the unit moves in the same iteration.
+// Sums and maxima in bb_score_reduce's order (bb_score.h): a function of n_samples alone, no atomics.  exp, log, erfc, sqrt are the
+// platform's (ocml on the device, libm in the emulation), as in bb_score.h: non-finite parameters propagate by IEEE rules into the
+// units that use them (bb_exp, which clamps, is used only where bb_ppc.h / bb_freq.h use it: the tables this file reads as they are).
+// Barrier-separated passes, so the host emulation (BB_EMU) runs the same source.
+#pragma once
+#include "bb_freq.h"
+#include "bb_score.h"
+
+#define BB_RB_MAX_Q 8
+#define BB_RB_OUT 6                        // per-unit results on the device: q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg
+#define BB_RB_ITER 64                      // bisection steps
+#define BB_RB_SCALARS 64                   // st[]: 0 .. 11 the reductions A .. D, 12 .. 14 a sweep's CDF sums, 15 bracket finite,
+                                           // 16 .. 23 lo, 24 .. 31 hi (the rest: padding to a whole 512 bytes)
+// LDS: m[n_samples] | sd[n_samples] | three arrays of BB_SCORE_NT partials (bb_score_reduce's layout) | scalars
+#define BB_RB_LDS_DOUBLES(ns) (2 * (long long)(ns) + 3 * BB_SCORE_NT + BB_RB_SCALARS)
+// the largest n_samples whose layout fits the 160 KiB of LDS a workgroup can have
+#define BB_RB_SAMPLES_CAP ((160 * 1024 / 8 - 3 * BB_SCORE_NT - BB_RB_SCALARS) / 2)
+static_assert(BB_RB_LDS_DOUBLES(BB_RB_SAMPLES_CAP) * 8 <= 160 * 1024 && BB_RB_LDS_DOUBLES(BB_RB_SAMPLES_CAP + 1) * 8 > 160 * 1024,
+              "BB_RB_SAMPLES_CAP is the largest count that fits");
+static_assert(BB_RB_SAMPLES_CAP == 8672, "2 x 8672 doubles of (m, sd) + 24 KiB of partials + 512 B of scalars = 160 KiB exactly");
+
+struct RbArgs {
+    FreqArgs F;               // posterior mode, every normaliser row; F.P: n_rows = R nb (the mutant rows), nb = the mutants, n_ppc = 1
+    double* ytab;             // [gridDim][E + 1][n_samples] per-block scratch: y_{e,j}, then s_j of the unit being worked
+    double* unit;             // [BB_RB_OUT][n_units]
+    double* quant;            // [n_units][BB_RB_MAX_Q]
+    int* n_steps;             // [n_units]
+    double probs[BB_RB_MAX_Q];
+    double threshold;
+    long long n_units;
+    int nq;
+    int n_z;                  // rows of F.Z: every time point of every replicate
+};
+
+// the normalisers F.Z[Ttot][n_samples] replaced by their logarithms, once per call: every mutant row of a replicate reads the same ones
+BB_DEV void bb_block_rb_logz(BBCtx& cx, const RbArgs& A, int nblocks) {
+    const long long n = (long long)A.n_z * A.F.P.n_samples;
+    BB_PASS(cx, tid) {
+        for (long long x = (long long)cx.block * cx.nthr + tid; x < n; x += (long long)nblocks * cx.nthr) A.F.Z[x] = log(A.F.Z[x]);
+    }
+}
+
+BB_DEV void bb_block_rb(BBCtx& cx, const RbArgs& A, int nblocks) {
+    const FreqArgs& F = A.F;
+    const PpcArgs& P = F.P;
+    const int ns = P.n_samples, E = P.E, nq = A.nq;
+    double* mj = cx.lds;
+    double* sdj = cx.lds + ns;
+    double* red = cx.lds + 2 * (long long)ns;
+    double* st = red + 3 * BB_SCORE_NT;
+    double* ytab = A.ytab + (long long)cx.block * (E + 1) * ns;
+    double* sj = ytab + (long long)E * ns;
+    const bool hier = P.kind >= 2, menv = P.kind == 1 || P.kind == 4;
+    const double rsqrt2 = 0.70710678118654752440, s0 = A.threshold;
+    for (long long row = cx.block; row < P.n_rows; row += nblocks) {
+        const int r = (int)(row / P.nb);
+        const long long m = row % P.nb;
+        const int T = P.T[r];
+        const long long ll = F.off_l[r] + (F.nn + m) * T;
+        const double* Z = F.Z + (long long)P.tcum[r] * ns;      // ln Z (bb_block_rb_logz)
+        const double* sbar = P.pop + (long long)(2 * P.off_t[r]) * ns;
+        // pass Y: every environment's y_j in one walk over the row's loglambda draws
+        BB_PASS(cx, tid) {
+            for (int j = tid; j < ns; j += BB_SCORE_NT) {
+                for (int e = 0; e < E; ++e) ytab[(long long)e * ns + j] = 0.0;
+                double l0 = bb_ppc_param(P, ll, j), z0 = Z[j];
+                for (int t = 0; t + 1 < T; ++t) {
+                    const double l1 = bb_ppc_param(P, ll + t + 1, j), z1 = Z[(long long)(t + 1) * ns + j];
+                    const int e = menv ? P.env_idx[P.tcum[r] + t + 1] : 0;
+                    ytab[(long long)e * ns + j] += ((l1 - l0) - (z1 - z0)) + sbar[(long long)(2 * t) * ns + j];
+                    l0 = l1;
+                    z0 = z1;
+                }
+            }
+        }
+        for (int e = 0; e < E; ++e) {
+            const long long em = e + (long long)E * m, u = em + (long long)E * P.nb * r;
+            int nu = 0;
+            for (int t = 0; t + 1 < T; ++t) nu += !menv || P.env_idx[P.tcum[r] + t + 1] == e;
+            const double* y = ytab + (long long)e * ns;
+            // sweep A: the conditionals into LDS; first moments
+            BB_PASS(cx, tid) {
+                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+                for (int j = tid; j < ns; j += BB_SCORE_NT) {
+                    double s, a, ib2, ls, tau = 0.0;
+                    if (!hier) {
+                        s = bb_ppc_param(P, P.lo_s + em, j);
+                        ls = bb_ppc_param(P, P.lo_ls + em, j);
+                        a = P.pri_mean_e ? P.pri_mean_e[em] : P.pri_mean;
+                        ib2 = P.pri_ivar_e ? P.pri_ivar_e[em] : P.pri_ivar;
+                    } else {
+                        const long long th = P.kind == 2 ? P.geno_idx[m] : em, uu = P.kind == 2 ? m : u;
+                        a = bb_ppc_param(P, P.lo_s + th, j);
+                        tau = exp(bb_ppc_param(P, P.lo_lt + uu, j));
+                        s = a + tau * bb_ppc_param(P, P.lo_tt + uu, j);
+                        ib2 = 1.0 / (tau * tau);
+                        ls = bb_ppc_param(P, P.lo_ls + uu, j);
+                    }
+                    double mm, sd;
+                    if (nu == 0) {           // no step uses the unit: the conditional is the prior
+                        mm = a;
+                        sd = hier ? tau : 1.0 / sqrt(ib2);
+                    } else {
+                        const double w = exp(-2.0 * ls), Pj = ib2 + (double)nu * w;
+                        mm = (a * ib2 + w * y[j]) / Pj;
+                        sd = 1.0 / sqrt(Pj);
+                    }
+                    sj[j] = s;
+                    mj[j] = mm;
+                    sdj[j] = sd;
+                    a0 += s;
+                    a1 += mm;
+                    a2 += sd * sd;
+                }
+                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = a2;
+            }
+            BB_SYNC(cx);
+            bb_score_reduce(cx, red, st, false);
+            // sweep B: centred second moments; the largest mean
+            BB_PASS(cx, tid) {
+                const double qm = st[0] / ns, rm = st[1] / ns;
+                double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
+                for (int j = tid; j < ns; j += BB_SCORE_NT) {
+                    const double ds = sj[j] - qm, dm = mj[j] - rm;
+                    a0 += ds * ds;
+                    a1 += dm * dm;
+                    mx = bb_score_max(mx, mj[j]);
+                }
+                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
+            }
+            BB_SYNC(cx);
+            bb_score_reduce(cx, red, st + 3, true);
+            // sweep C: both tails at the threshold; the smallest mean (as the largest of -m)
+            BB_PASS(cx, tid) {
+                double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
+                for (int j = tid; j < ns; j += BB_SCORE_NT) {
+                    const double v = (mj[j] - s0) / sdj[j] * rsqrt2;
+                    a0 += 0.5 * erfc(-v);
+                    a1 += 0.5 * erfc(v);
+                    mx = bb_score_max(mx, -mj[j]);
+                }
+                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
+            }
+            BB_SYNC(cx);
+            bb_score_reduce(cx, red, st + 6, true);
+            if (nq > 0) {
+                // sweep D: the largest sd
+                BB_PASS(cx, tid) {
+                    double mx = -INFINITY;
+                    for (int j = tid; j < ns; j += BB_SCORE_NT) mx = bb_score_max(mx, sdj[j]);
+                    red[tid] = 0.0; red[BB_SCORE_NT + tid] = 0.0; red[2 * BB_SCORE_NT + tid] = mx;
+                }
+                BB_SYNC(cx);
+                bb_score_reduce(cx, red, st + 9, true);
+            }
+            BB_PASS(cx, tid) {
+                if (tid == 0) {
+                    A.unit[0 * A.n_units + u] = st[0] / ns;
+                    A.unit[1 * A.n_units + u] = sqrt(st[3] / ns);
+                    A.unit[2 * A.n_units + u] = st[1] / ns;
+                    A.unit[3 * A.n_units + u] = sqrt(st[2] / ns + st[4] / ns);
+                    A.unit[4 * A.n_units + u] = st[6] / ns;
+                    A.unit[5 * A.n_units + u] = st[7] / ns;
+                    A.n_steps[u] = nu;
+                    const double lo = -st[8] - 40.0 * st[11], hi = st[5] + 40.0 * st[11];
+                    st[15] = (nq > 0 && isfinite(lo) && isfinite(hi)) ? 1.0 : 0.0;
+                    for (int i = 0; i < nq; ++i) { st[16 + i] = lo; st[24 + i] = hi; }
+                }
+            }
+            BB_SYNC(cx);
+            if (nq > 0 && st[15] == 0.0) {   // a non-finite m_j or sd_j: no bracket
+                BB_PASS(cx, tid) { if (tid < nq) A.quant[u * BB_RB_MAX_Q + tid] = NAN; }
+            } else if (nq > 0) {
+                for (int it = 0; it < BB_RB_ITER; ++it) {
+                    for (int q0 = 0; q0 < nq; q0 += 3) {
+                        // sweep Q: the mixture CDF at the midpoints of up to three brackets
+                        BB_PASS(cx, tid) {
+                            const int i1 = q0 + 1 < nq ? q0 + 1 : q0, i2 = q0 + 2 < nq ? q0 + 2 : q0;
+                            const double x0 = st[16 + q0] + (st[24 + q0] - st[16 + q0]) / 2.0;
+                            const double x1 = st[16 + i1] + (st[24 + i1] - st[16 + i1]) / 2.0;
+                            const double x2 = st[16 + i2] + (st[24 + i2] - st[16 + i2]) / 2.0;
+                            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+                            for (int j = tid; j < ns; j += BB_SCORE_NT) {
+                                const double mm = mj[j], sd = sdj[j];
+                                a0 += 0.5 * erfc(-((x0 - mm) / sd * rsqrt2));
+                                if (q0 + 1 < nq) a1 += 0.5 * erfc(-((x1 - mm) / sd * rsqrt2));
+                                if (q0 + 2 < nq) a2 += 0.5 * erfc(-((x2 - mm) / sd * rsqrt2));
+                            }
+                            red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = a2;
+                        }
+                        BB_SYNC(cx);
+                        bb_score_reduce(cx, red, st + 12, false);
+                        BB_PASS(cx, tid) {
+                            if (tid < 3 && q0 + tid < nq) {
+                                const int i = q0 + tid;
+                                const double x = st[16 + i] + (st[24 + i] - st[16 + i]) / 2.0;
+                                if (st[12 + tid] / ns < A.probs[i]) st[16 + i] = x;
+                                else st[24 + i] = x;
+                            }
+                        }
+                        BB_SYNC(cx);
+                    }
+                }
+                BB_PASS(cx, tid) { if (tid < nq) A.quant[u * BB_RB_MAX_Q + tid] = st[16 + tid] + (st[24 + tid] - st[16 + tid]) / 2.0; }
+            }
+            BB_SYNC(cx);                     // (the next unit's sweep A overwrites what this one read)
+        }
+    }
+}

@@ -18,6 +18,9 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
     logfreq_ratio_ppc_scores, pit_histogram                       the log predictive density and PIT of every observed ratio, the
                                                                   draws averaged in closed form (`bb_ppc_score`), and the calibration
                                                                   histogram of the PITs (no reference counterpart)
+    fitness_marginals                                             the Rao-Blackwellised marginal of every mutant's fitness beside the
+                                                                  mean-field one (`bb_fitness_rb`): how far the fit's +- can be trusted
+                                                                  (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -391,6 +394,62 @@ def logfreq_ratio_ppc_scores(data: pd.DataFrame, df_advi: pd.DataFrame, *, model
         out[k] = res[k][keep]
     out["row_lpd"] = res["row_lpd"][rr]
     out["n_scored"] = res["n_scored"][rr]
+    return pd.DataFrame(out)
+
+
+def fitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                      n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
+                      id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                      rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                      device: int = 0, chain=None) -> pd.DataFrame:
+    """Can the +- on a mutant's fitness be trusted?  Mean-field ADVI underestimates posterior standard deviations, and the fitness
+    `vi.advi` reports is q's own mean and sd.  Given everything else a mutant's fitness has an exactly Gaussian full conditional;
+    averaging it over n_samples joint draws of everything else gives the Rao-Blackwellised (RB) marginal, one exact Gibbs half-step
+    away from q (`bb_fitness_rb`, one device call).  Were q the true posterior the two would agree; `sd_ratio` = rb_sd / q_sd says,
+    per mutant, how much of the uncertainty mean-field cut away comes back.  `df_advi` as for `logfreq_ratio_ppc_bands`; at equal
+    seed the draws are those of the band and score calls.  `chain`: the `chain` array of `mcmc.mcmc_sample` ([walkers, steps, D],
+    or [draws, D]) -- its draws, pooled over the walkers, replace q's (at most 8672 of them): the same call then Rao-Blackwellises
+    the chain's fitness estimates, and q_mean / q_sd are the chain's own.
+
+    Returns one line per fitness unit (replicate, mutant, environment): `id`, `rep` ("R1", ...), `env` (None without environments),
+    `n_steps` (the time steps that inform the unit; 0: its conditional is the prior), `q_mean`, `q_sd` (the draws' own fitness),
+    `rb_mean`, `rb_sd`, `sd_ratio`, `p_pos`, `p_neg` (the RB probability of a fitness above / below `threshold`, each accurate
+    where it is tiny) and one column per probability of `probs`, named q2.5, q50, q97.5, ...: the quantiles of the RB marginal."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        res = e.fitness_rb(n_samples=n_samples, probs=probs, threshold=threshold, seed=seed, draws=draws)
+    R, nb = len(bayes_model.counts), bayes_model.n_bc
+    n_units = res["rb_mean"].shape[0]
+    E = n_units // max(R * nb, 1)
+    has_env, per_env = _envs_per_rep(arrays, mname, R)
+    labels: List = []
+    if has_env:
+        for env in (x for r in range(R) for x in per_env[r]):            # first appearance over the replicates' time points, as the model indexes them
+            if env not in labels:
+                labels.append(env)
+    u = np.arange(n_units)
+    rep, m, env = u // max(E * nb, 1), (u // max(E, 1)) % max(nb, 1), u % max(E, 1)
+    out = {
+        "id": np.asarray(list(arrays.bc_ids), dtype=object)[m],
+        "rep": [f"R{r + 1}" for r in rep],
+        "env": [labels[x] for x in env] if has_env else None,
+        "n_steps": res["n_steps"],
+    }
+    for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"] / res["q_sd"]
+    out["p_pos"], out["p_neg"] = res["p_pos"], res["p_neg"]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
     return pd.DataFrame(out)
 
 

@@ -437,6 +437,82 @@ typedef struct bb_score_out {     /* every pointer may be NULL                  
 int bb_score_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps);
 int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
 
+/* Rao-Blackwellised (RB) marginals of the mutants' fitness -- how far the "+-" of the mean-field posterior can be trusted, per
+ * mutant.  No reference counterpart.  Given everything else, a mutant's fitness enters the log-joint only through a Gaussian prior
+ * and Gaussian log-frequency-ratio terms (model_fitness_normal.jl:262-270 and its four siblings), so its full conditional is
+ * exactly N(m, sd) in all five model kinds.  Averaging that conditional over joint draws of everything else gives the RB marginal:
+ * one exact Gibbs half-step away from q.  Were q the true posterior the RB marginal would equal q's own; where mean-field has cut
+ * the coupling of a fitness to its loglambda row, sbar_t, logsigma, theta and tau, the RB marginal has that uncertainty back in it,
+ * and rb_sd / q_sd says by how much.  Given the draws of an MCMC chain instead, the same call Rao-Blackwellises the chain's
+ * fitness estimates.
+ *
+ * Units (bb_fitness_rb_shape: n_units): u = (r, m, e), replicate, mutant in the caller's order, environment, numbered in the order
+ * of the caller's s_bc block (kinds FITNESS, MULTIENV) or theta_tilde block (hierarchical kinds): u = e + E m + E n_bc r, E = n_env
+ * for the multi-environment kinds and 1 otherwise; the genotype model has u = m (the order of bb_hier_fitness).  The steps of a
+ * unit are T_u = { t < T_r - 1 : env_r(t + 1) = e } (the later time point's environment, as in bb_ppc_bands), n_u their number.
+ *
+ * Per draw j < n = n_samples, with ll the loglambda draw of (r, t, b), b = n_neutral + m, and Z_{r,t,j} = sum_b' exp(ll_{r,t,b',j})
+ * summed by bb_freq_bands' rule (chunks of 256 consecutive data columns in index order, then the chunks in chunk order):
+ *   gamma_{t,j} = (ll_{r,t+1,b,j} - ll_{r,t,b,j}) - (ln Z_{r,t+1,j} - ln Z_{r,t,j})
+ *   y_j  = sum_{t in T_u} (gamma_{t,j} + sbar_{r,t,j}), in ascending t
+ *   w_j  = exp(-2 logsigma_{u,j}), logsigma_u the unit's logsigma_bc entry
+ *   (a_j, b_j), the prior of s_u given the rest: FITNESS, MULTIENV: the s_bc prior (mean, std) of the element as the handle holds
+ *          it (Vector or Matrix form; the handle holds 1 / std^2, which is what enters below), the same for every draw;
+ *          hierarchical kinds: (theta_j, exp(logtau_{u,j})), theta the unit's hyper-fitness: theta[geno_idx[m]] for the genotype
+ *          model, theta[e + E m] for the replicate kinds
+ *   P_j  = 1 / b_j^2 + n_u w_j;   m_j = (a_j / b_j^2 + w_j y_j) / P_j;   sd_j = 1 / sqrt(P_j)
+ *   s_j  = the unit's fitness in draw j: the s_bc draw, or theta_j + exp(logtau_j) theta_tilde_j.
+ * A unit with n_u = 0 (an environment that never occurs as a later time point) has the prior as its conditional: m_j = a_j and
+ * sd_j = b_j, taken as they are (for the s_bc prior: 1 / sqrt(1 / std^2)).
+ * The identity all this rests on, at any point z:  P (m - s_u) = dlogp/ds_u (FITNESS, MULTIENV);  exp(logtau_u) P (m - s_u) =
+ * dlogp/dtheta_tilde_u (hierarchical kinds).  BB_FLAG_RAGGED_METHOD alters the neutral term only, so flagged handles are served alike.
+ *
+ * Outputs per unit (every pointer may be NULL):
+ *   n_steps    n_u
+ *   q_mean, q_sd     mean and sd of s_j over the draws: two-pass, centred, divisor n
+ *   rb_mean    mean_j m_j
+ *   rb_sd      sqrt(mean_j sd_j^2 + mean_j (m_j - rb_mean)^2), two-pass and centred
+ *   p_pos      mean_j erfc(-(m_j - s0) / (sd_j sqrt 2)) / 2, the RB probability of s_u > s0 = threshold
+ *   p_neg      mean_j erfc(+(m_j - s0) / (sd_j sqrt 2)) / 2; both through erfc, never as 1 - the other (bb_ppc_score's rule)
+ *   quantiles  quantiles[u][i], the probs[i] quantile of the mixture F(x) = mean_j erfc(-(x - m_j) / (sd_j sqrt 2)) / 2 by
+ *              bisection: lo = min_j m_j - 40 max_j sd_j, hi = max_j m_j + 40 max_j sd_j; 64 times x = lo + (hi - lo) / 2,
+ *              F(x) < p ? lo = x : hi = x; the result is the last bracket's midpoint.  A unit with a non-finite m_j or sd_j reports
+ *              NaN quantiles.
+ * Non-finite parameters propagate by IEEE rules into the units that use them; they disturb no other unit and are not an error.
+ *
+ * Draws.  draws == NULL: the joint draw of bb_ppc_bands, latent i (the caller's flat index) = mu_i + sigma_i N(i, j >> 1,
+ * 0xFFFFFFE0): at equal seed all four post-fit calls share their draws; n_samples in 2 .. BB_RB_MAX_SAMPLES.  draws != NULL: a host
+ * array [n_samples][D] in the caller's order (an MCMC chain, say), uploaded whole and read in place of the Philox draw; n_samples
+ * in 1 .. BB_RB_MAX_SAMPLES, and with n_samples = 1 the outputs are the conditional at that point (rb_mean = m, rb_sd = sd).  What
+ * the device cannot allocate is BB_ERR_DEVICE, and nothing is computed.  This path is no hot path: a latent's draws lie D doubles
+ * apart and are read with that stride.  BB_RB_MAX_SAMPLES is the largest count for which a unit's (m_j, sd_j) and the reductions'
+ * partials fit the 160 KiB of LDS (derived next to the layout, csrc/bb_rb.h).
+ *
+ * A unit's results are a function of the handle's (mu, sigma) (or the supplied draws), the s_bc priors, n_samples, seed, threshold
+ * and probs: bit-identical whatever the grid, the launch mode, the handle's internal latent order, the device count, n_units or
+ * the calls made before.  No atomics on doubles; every sum over the draws runs in bb_ppc_score's order.  The handle's mu, omega,
+ * optimiser state, step counter and RNG position are untouched, bitwise.  BB_ERR_INVALID: a null h, o or out; n_quantiles outside
+ * 0 .. 8; probs null with n_quantiles > 0; a prob outside (0, 1) or NaN; a non-finite threshold.  BB_ERR_UNSUPPORTED: n_samples
+ * outside its range.  Multi-device and sharded handles: as bb_ppc_bands (the first device works on the gathered posterior; a shard
+ * needs bb_set_params first).
+ * Out of scope: the conditionals of sbar_t, theta, tau and logsigma; any change to what the fit or an MCMC run report by default. */
+#define BB_RB_MAX_SAMPLES 8672
+typedef struct bb_rb_opts {
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
+    int32_t n_quantiles;      /* 0 .. 8                                                */
+    const double* probs;      /* [n_quantiles] probabilities in (0, 1)                 */
+    double threshold;         /* s0 of p_pos / p_neg                                   */
+    uint64_t seed;            /* Philox key (draws == NULL)                            */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL   */
+} bb_rb_opts;
+typedef struct bb_rb_out {        /* every pointer may be NULL; [n_units] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
+    double* quantiles;        /* [n_units][n_quantiles]                                */
+    int32_t* n_steps;         /* n_u                                                   */
+} bb_rb_out;
+int bb_fitness_rb_shape(const bb_handle* h, int64_t* n_units);
+int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out);
+
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array
  * chain[n_chains][n_draws][n_cols] (what mcmc_sample of the host layer writes).  n_cols is any positive count, not necessarily

@@ -296,6 +296,71 @@ function ppc_score(h::Ptr{Cvoid}; n_samples::Int=1000, seed::Integer=0)
             row_lpd=row_lpd, row_p_waic=row_p_waic, n_scored=n_scored)
 end
 
+# Rao-Blackwellised marginals of the mutants' fitness (bb_fitness_rb, include/barbay_hip.h): every unit's exact Gaussian full
+# conditional averaged over joint draws of everything else -- how far the mean-field +- can be trusted, per mutant.  Field for
+# field the Python binding's `bb_rb_opts` / `bb_rb_out` (barbay.jl_amd/_capi.py).
+# Like the rest of this file it remains unexecuted (no `julia` where this repository is built and tested).
+const BB_RB_MAX_SAMPLES = 8672
+struct bb_rb_opts
+    n_samples::Int32
+    n_quantiles::Int32
+    probs::Ptr{Float64}
+    threshold::Float64
+    seed::UInt64
+    draws::Ptr{Float64}
+end
+struct bb_rb_out
+    q_mean::Ptr{Float64}
+    q_sd::Ptr{Float64}
+    rb_mean::Ptr{Float64}
+    rb_sd::Ptr{Float64}
+    p_pos::Ptr{Float64}
+    p_neg::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    n_steps::Ptr{Int32}
+end
+
+"""
+    fitness_rb_shape(h) -> Int
+
+Fitness units of `fitness_rb`: u = e + E m + E n_bc r (0-based: replicate r, mutant m in the caller's order, environment e), the
+order of the s_bc block (fitness, multienv) or the theta_tilde block (hierarchical kinds).
+"""
+function fitness_rb_shape(h::Ptr{Cvoid})
+    n = Ref{Int64}(0)
+    check(ccall((:bb_fitness_rb_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), h, n))
+    return Int(n[])
+end
+
+"""
+    fitness_rb(h; n_samples=1000, probs=[0.025, 0.5, 0.975], threshold=0.0, seed=0, draws=nothing) -> NamedTuple
+
+`h` a live `bb_handle`.  Returns `n_steps, q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg` (n_units each) and `quantiles`
+(length(probs) x n_units: Julia order of the C array [unit][i]).  `draws`: a D x n matrix (one draw per COLUMN: Julia's
+column-major D x n is the ABI's [n][D]), an MCMC chain say, read in place of the posterior's own draws; n_samples is then its
+column count.  2 (1 with draws) <= n_samples <= BB_RB_MAX_SAMPLES; every prob strictly inside (0, 1).
+"""
+function fitness_rb(h::Ptr{Cvoid}; n_samples::Int=1000, probs::Vector{Float64}=[0.025, 0.5, 0.975], threshold::Real=0.0,
+                    seed::Integer=0, draws::Union{Nothing,Matrix{Float64}}=nothing)
+    nu, nq = fitness_rb_shape(h), length(probs)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("fitness_rb: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg = (Vector{Float64}(undef, nu) for _ in 1:6)
+    quantiles = Matrix{Float64}(undef, nq, nu)
+    n_steps = Vector{Int32}(undef, nu)
+    GC.@preserve probs draws q_mean q_sd rb_mean rb_sd p_pos p_neg quantiles n_steps begin
+        o = bb_rb_opts(Int32(n_samples), Int32(nq), nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL), Float64(threshold), UInt64(seed),
+                       draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws))
+        out = bb_rb_out(pointer(q_mean), pointer(q_sd), pointer(rb_mean), pointer(rb_sd), pointer(p_pos), pointer(p_neg),
+                        nq > 0 ? pointer(quantiles) : Ptr{Float64}(C_NULL), pointer(n_steps))
+        check(ccall((:bb_fitness_rb, LIB), Cint, (Ptr{Cvoid}, Ref{bb_rb_opts}, Ref{bb_rb_out}), h, o, out))
+    end
+    return (n_steps=n_steps, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, p_pos=p_pos, p_neg=p_neg, quantiles=quantiles)
+end
+
 # Log-joint and gradient at several points in one call (bb_logdensity_grad_batch, include/barbay_hip.h): what a sampler that
 # steps an ensemble of walkers in lock-step asks of the model (`LogDensityProblems.logdensity_and_gradient`, W points at once).
 const BB_LOGP_MAX_BATCH = 64
