@@ -404,7 +404,7 @@ static int pick_geometry(bb_handle* h) {
     h->NB = NB;
     h->nthr = nthr;
     h->lds_doubles = need / 8;
-    h->lds_doubles_p0 = h->lds_doubles_p = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr, 1).total;
+    h->lds_doubles_p0 = (size_t)bb_lds_layout(M.R, M.E, M.kind, M.Ttot, M.nt1, M.K, NB, nthr, 1).total;
     h->nblk = (int)((nbar + NB - 1) / NB);
     h->tile_cap = h->nblk + 8;
     h->ngeno_blk = M.G > 0 ? (int)std::min<long long>(((M.G + 1) / 2 + 255) / 256, 64) : 0;
@@ -470,7 +470,10 @@ static int create_inner(const bb_model_desc* md, const bb_advi_opts* opts, const
     const double Dsh = (double)M.D * frac, cnts = 4.0 * (double)n_cells(M) * frac;
     h->bytes_sample = (int64_t)(16.0 * Dsh + cnts);
     h->bytes_update = (int64_t)((16.0 + 16.0 + (opts->optimizer == BB_OPT_TRUNCATED_ADAGRAD ? 64.0 : 32.0)) * Dsh + cnts);
-    if ((rc = setup_persistent(h, h->o.launch_mode)) || (rc = sync_descriptors(h)) || (rc = bb_init_meanfield(h))) return rc;
+    Planned plan;
+    if ((rc = plan_or_refuse(h, h->o.launch_mode, false, plan))) return rc;
+    (void)install_plan(h, plan);      // (an allocation or copy that fails there leaves the two-kernel plan: the handle is created with it)
+    if ((rc = sync_descriptors(h)) || (rc = bb_init_meanfield(h))) return rc;
     *out = own.release();
     return BB_OK;
 }

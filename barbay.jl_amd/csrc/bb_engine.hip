@@ -1,6 +1,6 @@
-// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the step loop and its launch plans; handle
-// creation (bb_create) is in bb_create.h and the post-fit entry points (hier fitness, log-density batch, predictive bands and scores,
-// Rao-Blackwellised fitness marginals, chain summary) are in bb_analysis.h, both included below.
+// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle and the step loop; the launch plan (plan_launch,
+// install_plan) is in bb_plan.h, handle creation (bb_create) in bb_create.h and the post-fit entry points (hier fitness, log-density
+// batch, predictive bands and scores, Rao-Blackwellised fitness marginals, chain summary) in bb_analysis.h, all three included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -89,7 +89,7 @@ static BBTuning read_tuning() {
     t.nb_set = set("BB_TUNE_NB");                     // (odd: the resident tile map takes "set at all", the two-kernel map a value > 0)
     t.nb = num("BB_TUNE_NB", 0);
     t.res_nb = num("BB_TUNE_RES_NB", 0);              // (> 0: the resident launch's own tile size)
-    t.ng = num("BB_TUNE_NG", 0);                      // (try_resident takes 8, 16 or 32 where the shape allows)
+    t.ng = num("BB_TUNE_NG", 0);                      // (first_hop_groups takes 8, 16 or 32 where the shape allows)
     t.lead_set = set("BB_TUNE_LEAD");
     t.lead = num("BB_TUNE_LEAD", 65);
     if (t.lead < 10 || t.lead > 100) t.lead = 100;
@@ -98,7 +98,7 @@ static BBTuning read_tuning() {
     return t;
 }
 
-// What bb_run launches, planned by setup_persistent whenever the handle's shape or cross-GPU leg changes.
+// What bb_run launches, planned by plan_launch (bb_plan.h) whenever the handle's shape or cross-GPU leg changes.
 enum { IMPL_TWO_KERNEL = 0, IMPL_PERSIST = 1, IMPL_RES = 2, IMPL_STREAM = 3 };     // (= bb_stats.resident_kernel)
 struct LaunchPlan {
     int impl = IMPL_TWO_KERNEL;        // k_sample + k_update / k_persist (bb_persist.h) / k_res (bb_resident.h) / k_stream (bb_stream.h)
@@ -160,7 +160,7 @@ struct bb_handle {
     // cross-GPU leg of the resident launch (bb_p2p_*)
     void* p2p_inbox = nullptr;               // this rank's inbox (fine-grained device memory)
     size_t p2p_rows_bytes = 0, p2p_bytes = 0, p2p_gran_off = 0;
-    double* d_segtab = nullptr;        // host-built tables of the resident launches (host_tables)
+    double* d_segtab = nullptr;        // host-built tables of the resident launches (host_tables, install_plan)
     int* d_ldstab = nullptr;
     size_t segtab_cap = 0, ldstab_cap = 0;
     void* p2p_peer[BB_MAX_WORLD] = {};       // peers' inboxes as mapped here
@@ -221,9 +221,6 @@ static int launch_persistent(bb_handle* h, long long nsteps);
 static int run_enqueue(bb_handle* h, int64_t n_steps);
 static int run_finish(bb_handle* h);
 
-// ------------------------------------------------------------------------------------------------
-// resident launches (bb_persist.h, bb_resident.h, bb_stream.h): the plan
-// ------------------------------------------------------------------------------------------------
 // f(std::integral_constant<int, KIND>{}) for the model kind: the host-side instances of templates over it
 template <class F>
 static void by_kind(int kind, F&& f) {
@@ -236,347 +233,9 @@ static void by_kind(int kind, F&& f) {
     }
 }
 
-// the time-point count where all replicates share it (the compile-time-T instances), else 0
-static int uniform_T(const DevModel& M) {
-    for (int r = 1; r < M.R; ++r) if (M.T[r] != M.T[0]) return 0;
-    return M.T[0];
-}
-
-// The resident kernel instances (bb_inst.h) and their names; the emulation runs the block programs as host functions, so it only
-// names the launch (the compile-time T / AP / MS are the product's).
-#ifndef BB_EMU
-static bb_persist_kernel persist_kernel(int kind, int P, int nthr, bool xg = false, const char** nm = nullptr) {
-#ifdef BB_FAST_BUILD   /* experiment builds (tools/xp.py): only the instances the C2 / C4 workloads use, in this one translation unit */
-    if (nm) *nm = "(experiment build)";
-    if (!xg && nthr > 512 && P == 1 && kind == 0) return k_persist<0, 1, 1024>;
-    return nullptr;
-#else
-    return bb_persist_instance(kind, P, nthr, xg, nm);
-#endif
-}
-static bb_res_kernel res_kernel(int kind, int P, int nthr, bool xg, int T, bool ap, bool ms = false, const char** nm = nullptr) {
-#ifdef BB_FAST_BUILD
-    if (nm) *nm = "(experiment build)";
-    if (xg || ms) return nullptr;
-    if (ap) {
-        if (nthr > 512 && P == 1 && kind == 0) return k_res<0, 1, 1024, false, 0, true>;
-        if (nthr > 256 && nthr <= 512 && P == 3 && kind == 3) return k_res<3, 3, 512, false, 0, true>;
-        return nullptr;
-    }
-    if (nthr > 512 && P == 1 && kind == 0) return T == 8 ? k_res<0, 1, 1024, false, 8> : k_res<0, 1, 1024, false>;
-    if (nthr > 512 && P == 1 && kind == 1) return T == 6 ? k_res<1, 1, 1024, false, 6> : k_res<1, 1, 1024, false>;
-    if (nthr > 256 && nthr <= 512 && P == 2 && kind == 0) return T == 8 ? k_res<0, 2, 512, false, 8> : k_res<0, 2, 512, false>;
-    if (nthr > 256 && nthr <= 512 && P == 3 && kind == 3) return T == 6 ? k_res<3, 3, 512, false, 6> : k_res<3, 3, 512, false>;
-    if (nthr > 256 && nthr <= 512 && P == 2 && kind == 3) return T == 6 ? k_res<3, 2, 512, false, 6> : k_res<3, 2, 512, false>;
-    if (nthr > 512 && P == 1 && kind == 2) return T == 8 ? k_res<2, 1, 1024, false, 8> : k_res<2, 1, 1024, false>;
-    return nullptr;
-#else
-    switch (kind) {
-    case 0: return bb_res_instance_k0(P, nthr, xg, T, ap, ms, nm);
-    case 1: return bb_res_instance_k1(P, nthr, xg, T, ap, ms, nm);
-    case 2: return bb_res_instance_k2(P, nthr, xg, T, ap, ms, nm);
-    case 3: return bb_res_instance_k3(P, nthr, xg, T, ap, ms, nm);
-    default: return bb_res_instance_k4(P, nthr, xg, T, ap, ms, nm);
-    }
-#endif
-}
-static bb_stream_kernel stream_kernel(int kind, int nthr, int T, const char** nm = nullptr, bool ms = false) {
-#ifdef BB_FAST_BUILD
-    if (nm) *nm = "(experiment build)";
-    if (ms) return nullptr;
-    if (nthr == 1024 && kind == 0 && T == 8) return k_stream<0, 1024, 8>;
-    if (nthr == 1024 && kind == 2 && T == 8) return k_stream<2, 1024, 8>;
-    if (nthr == 1024 && kind == 3 && T == 6) return k_stream<3, 1024, 6>;
-    return nullptr;
-#else
-    return ms ? bb_stream_instance_ms(kind, nthr, T, nm) : bb_stream_instance(kind, nthr, T, nm);
-#endif
-}
-// what try_resident / setup_persistent ask for: k_stream or k_res with P pair slots; k_persist
-static const void* resident_instance(const bb_handle* h, bool stream, int P, bool ms, std::string& name) {
-    const char* nm = "";
-    const void* k = stream ? (const void*)stream_kernel(h->M.kind, h->nthr, uniform_T(h->M), &nm, ms)
-                           : (const void*)res_kernel(h->M.kind, P, h->nthr, h->p2p_on, uniform_T(h->M), br_any_parity(h->M), ms, &nm);
-    name = nm;
-    return k;
-}
-static const void* persist_instance(const bb_handle* h, int P, std::string& name) {
-    const char* nm = "";
-    const void* k = (const void*)persist_kernel(h->M.kind, P, h->nthr, h->p2p_on, &nm);
-    name = nm;
-    return k;
-}
-#else
-static const void* resident_instance(const bb_handle* h, bool stream, int P, bool ms, std::string& name) {
-    char nm[64];
-    if (stream) snprintf(nm, sizeof nm, "emu:k_stream<%d,%d,%d%s>", h->M.kind, h->nthr, uniform_T(h->M), ms ? ",true" : "");
-    else snprintf(nm, sizeof nm, "emu:k_res<%d,%d,%d,%s,*,%s,%s>", h->M.kind, P, h->nthr, h->p2p_on ? "true" : "false",
-                  br_any_parity(h->M) ? "true" : "false", ms ? "true" : "false");
-    name = nm;
-    return nullptr;
-}
-static const void* persist_instance(const bb_handle* h, int P, std::string& name) {
-    char nm[48];
-    snprintf(nm, sizeof nm, "emu:k_persist<%d,%d,%d>", h->M.kind, P, h->nthr);
-    name = nm;
-    return nullptr;
-}
-#endif
-
-// pairs a tile can hold: every segment contributes count/2 + 1 at most
-static long long tile_pairs_bound(const DevModel& M, long long NB) {
-    long long p = 0;
-    for (int r = 0; r < M.R; ++r) p += NB * M.T[r] / 2 + 1;
-    if (M.kind == 0 || M.kind == 1) p += 2 * (NB * M.E / 2 + 1);
-    else if (M.kind == 2) p += 3 * (NB / 2 + 1);
-    else if (M.kind == 3) p += (NB / 2 + 1) + 3ll * M.R * (NB / 2 + 1);
-    else p += (NB * M.E / 2 + 1) + 3ll * M.R * (NB * M.E / 2 + 1);
-    p += 2 * (M.nt1 / 2 + 1);
-    return p;
-}
-
-// device copies of the descriptors (kernels read them through pointers); re-sent whenever the host copy changes
-static int sync_descriptors(bb_handle* h) {
-    int rc;
-    if (!h->dM && ((rc = dalloc(h, &h->dM, 1)) || (rc = dalloc(h, &h->dS, 1)) || (rc = dalloc(h, &h->dL, 1)))) return rc;
-    if ((rc = h2d(h->dM, &h->M, sizeof(DevModel), h->stream)) || (rc = h2d(h->dS, &h->S, sizeof(DevState), h->stream))) return rc;
-    h->Lp = bb_lds_layout(h->M.R, h->M.E, h->M.kind, h->M.Ttot, h->M.nt1, h->M.K, h->NB, h->nthr, 1);   // the resident launch's carve-up
-    if ((rc = h2d(h->dL, &h->Lp, sizeof(BBLds), h->stream))) return rc;
-    if (!h->dY && (rc = dalloc(h, &h->dY, 1))) return rc;
-    return h2d(h->dY, &h->Yh, sizeof(BRLay), h->stream);
-}
-
-// Genotype model: the tile table of k_res (br_tile_geno) -- tiles of at most NB barcodes (the first ng, the leaders: NBL, if > 0) whose
-// cuts inside the mutants fall on genotype boundaries; tg[i] = first genotype tile i owns.  False if a genotype does not fit a tile.
-static bool build_geno_tiles(const bb_handle* h, int NB, int NBL, int ng, std::vector<long long>& tb, std::vector<int>& tg) {
-    const DevModel& M = h->M;
-    const std::vector<int>& ptr = h->geno_ptr_h;
-    auto geno_of = [&](long long m) { return (int)(std::upper_bound(ptr.begin(), ptr.end(), (int)m) - ptr.begin()) - 1; };
-    auto gcut = [&](long long b) { return (b <= M.nn || b <= h->b_lo) ? h->g_lo : (b >= h->b_hi ? h->g_hi : geno_of(b - M.nn)); };
-    tb.clear();
-    tg.clear();
-    long long b = h->b_lo;
-    while (b < h->b_hi) {
-        const int cap = (NBL > 0 && tb.size() < (size_t)ng) ? NBL : NB;
-        long long e = std::min<long long>(b + cap, h->b_hi);
-        if (e < h->b_hi && e > M.nn) {
-            e = M.nn + ptr[(size_t)geno_of(e - M.nn)];       // back to the first mutant of the genotype the cut fell into
-            if (e <= b) return false;
-        }
-        tb.push_back(b);
-        tg.push_back(gcut(b));
-        b = e;
-    }
-    if (tb.empty()) { tb.push_back(h->b_lo); tg.push_back(h->g_lo); }
-    tb.push_back(h->b_hi);
-    tg.push_back(h->g_hi);
-    for (size_t i = 0; i + 1 < tg.size(); ++i) if (tg[i + 1] - tg[i] > NB) return false;      // (theta stage table: NB entries)
-    return NB < 32768;
-}
-
-// the owner-computes launch (bb_resident.h) where the shape allows it; BB_NO_RES=1 keeps k_persist (A/B runs)
-// any_parity: also the AP instances (odd time-point counts, odd loglambda offset).  Measured (C2-sized fitness_normal with 7 / 5
-// time points, the fifth model): they are 1 - 5 % SLOWER than k_persist -- parity is a run-time property of every pair there,
-// 45 spilled registers and two Philox draws in divergent lanes -- so setup_persistent asks for them only where k_persist cannot
-// run: the genotype model (whose other choice is the two-kernel step) or after k_persist has refused the shape.
-// The tables a tile of k_res / k_stream needs before its first step, built HERE instead of in every launch's prologue (where
-// thread 0 of each tile spent 3.4 us on its segment table behind a chain of scalar loads, and the per-lane descriptor loads of the
-// LDS tables another 1.8 us -- profiles/r03z_round3_final/fixed_cost.txt): per tile its segment table (br_build_segs, the same code),
-// once the tile-independent LDS tables (br_table_*).  BB_NO_HOST_TABLES=1: the kernels build them (A/B).
-template <int KIND>
-static void host_tables_kind(bb_handle* h, const RunArgs& A, const DevState& Sh, int NB, int stride, std::vector<double>& tab) {
-    for (int b = 0; b < A.nblk; ++b) {
-        const BBTile t = KIND == 2 ? br_tile_geno(h->M, Sh, b, NB) : br_tile(h->M, A, b, NB);
-        const int g0 = KIND == 2 ? Sh.tile_g[b] : 0, g1 = KIND == 2 ? Sh.tile_g[b + 1] : 0;
-        double* rec = tab.data() + (size_t)b * stride;
-        const int n = br_build_segs<KIND>((BRSeg*)rec, h->M, h->Yh, t, b == 0, g0, g1);
-        ((int*)(rec + stride - 1))[0] = n;
-    }
-}
-static bool host_tables(bb_handle* h, const LaunchPlan& p, const std::vector<long long>& tb, const std::vector<int>& tg) {
-    h->S.segtab = nullptr;
-    h->S.ldstab = nullptr;
-    h->S.segtab_stride = 0;
-    if (h->tune.no_host_tables) return true;
-    const DevModel& M = h->M;
-    const int stride = BR_SEG_DOUBLES * (4 + 4 * M.R + 1) + 1;
-    RunArgs A = make_args(h, 0, 0, 1, true, false);
-    A.nblk = p.nblk; A.nbl = p.NBL; A.ng = p.ng;
-    DevState Sh = h->S;
-    Sh.tile_b = tb.data();
-    Sh.tile_g = tg.data();
-    std::vector<double> tab((size_t)p.nblk * stride, 0.0);
-    by_kind(M.kind, [&](auto kindc) { host_tables_kind<decltype(kindc)::value>(h, A, Sh, p.NB, stride, tab); });
-    const int K = M.K, Tt = M.Ttot, R = M.R;
-    std::vector<int> img((size_t)3 * K + 4 * Tt + 4 * R + 4, 0);
-    for (int j = 0; j < K; ++j) br_table_row(M, h->Yh, j, &img[2 * j], &img[2 * K + j]);
-    for (int j = 0; j < Tt; ++j) br_table_time(M, h->Yh.L, j, &img[3 * K + 4 * j]);
-    for (int r = 0; r < R; ++r) br_table_rep(M, h->Yh, r, &img[3 * K + 4 * Tt + 4 * r]);
-    // (the handle keeps one buffer of each, sized for the largest tile map it has seen)
-    if (tab.size() > h->segtab_cap) { double* d = nullptr; if (dalloc(h, &d, tab.size())) return false; h->d_segtab = d; h->segtab_cap = tab.size(); }
-    if (img.size() > h->ldstab_cap) { int* d = nullptr; if (dalloc(h, &d, img.size())) return false; h->d_ldstab = d; h->ldstab_cap = img.size(); }
-    if (h2d(h->d_segtab, tab.data(), tab.size() * 8, h->stream) || h2d(h->d_ldstab, img.data(), img.size() * 4, h->stream)) return false;
-    h->S.segtab = h->d_segtab;
-    h->S.segtab_stride = stride;
-    h->S.ldstab = h->d_ldstab;
-    return true;
-}
-
-// k_res or k_stream for this handle's shape, with its own tile map: true and `p` filled in where one fits
-static bool try_resident(bb_handle* h, bool any_parity, LaunchPlan& p) {
-    const BBTuning& tu = h->tune;
-    if (tu.no_res) return false;
-    if (!br_eligible(h->M)) return false;
-    if (!any_parity && br_any_parity(h->M)) return false;
-    // tile map: leaders (tiles 0 .. 7) hold `frac` of a tile's barcodes (br_tile); BB_TUNE_LEAD=100 keeps all tiles alike
-    const long long nbar = std::max<long long>(h->b_hi - h->b_lo, 1);
-    // The two-kernel step may run more tiles than the device has compute units (its tiles must fit LDS with ITS tables: config 5 on one
-    // GPU runs 512 of them); a resident launch needs every tile resident -- one per compute unit: its own base map then
-    int NB0 = h->NB, nblk0 = h->nblk;
-    if (nblk0 > h->cus && !tu.nb_set) { NB0 = (int)((nbar + h->cus - 1) / h->cus); nblk0 = (int)((nbar + NB0 - 1) / NB0); }
-    // BB_TUNE_RES_NB (tests): the resident launch's own tile size -- a cut of a BASELINE problem with the full-size tile geometry even where
-    // the two-kernel step's tables would not fit such a tile (config 5 on one GPU: 782 barcodes per tile)
-    if (tu.res_nb > 0) { NB0 = tu.res_nb; nblk0 = (int)((nbar + NB0 - 1) / NB0); }
-    int NB = NB0, NBL = 0, nblk = nblk0;
-    // Groups of the exchange's first hop.  Round 2: 16 on one GPU (a leader then fetched its 16 members' rows in one round of loads, the
-    // consume ran on two thread groups).  Round 3, tagged rows + leaders that poll their members in chunks of eight on as many thread
-    // groups as the tile has (bbp_leader_reduce_tg, PAR): 8 groups of 32 are ONE round of polls where the tile has four thread groups, and
-    // every tile's consume is one thread group's eight loads -- C2 82.7 -> 83.5 k steps/s, C4 94.1 -> 94.9 k, C3 57.1 -> 57.7 k against 16
-    // (profiles/r03g_parallel_leaders).  The cross-GPU inbox protocol is laid out for 8.  BB_TUNE_NG overrides (8 or 16).
-    if (h->M.K + 2 * h->M.nt1 > h->nthr) return false;      // (one thread per row entry: bbp_consume_tg / _tgx, the leaders' chunk sums)
-    const int KK = h->M.K + 2 * h->M.nt1;
-    const bool can16 = !h->p2p_on && nblk0 >= 64 && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128);
-    int ng = (can16 && h->nthr < 4 * ((KK + 63) & ~63)) ? 16 : 8;
-    if (tu.ng == 8 || (tu.ng == 16 && !h->p2p_on && KK <= 128 && h->nthr >= 2 * (KK <= 64 ? 64 : 128))) ng = tu.ng;
-    // a leader takes its members' rows in batches of eight loads per lane -- 32 groups of 8 on a full grid: one batch, one round trip
-    // (the tile's consume then runs on four thread groups)
-    if (tu.ng == 32 && !h->p2p_on && nblk0 >= 64 && h->nthr >= 4 * ((KK + 63) & ~63)) ng = 32;
-    const int pct = tu.lead;
-    const bool nb_fixed = tu.nb_set || tu.res_nb > 0;
-    if (pct < 100 && nblk0 >= 2 * ng && (!nb_fixed || tu.lead_set)) {
-        if (!nb_fixed) {
-            const double tiles = (double)nblk0 - (double)ng * (1.0 - pct / 100.0);      // in units of a full tile
-            NB = (int)std::ceil((double)nbar / tiles);
-        }
-        NBL = std::max(1, (int)(NB * (pct / 100.0)));
-        const long long rest = nbar - (long long)ng * NBL;
-        nblk = ng + (int)((std::max<long long>(rest, 0) + NB - 1) / NB);
-        const long long p_uni = (br_tile_span(h->M, NB0, true) + h->nthr - 1) / h->nthr, p_new = (br_tile_span(h->M, NB, true) + h->nthr - 1) / h->nthr;
-        // stay uniform where rounding pushed the map over the grid that fits, or the slightly larger tiles need another pair slot
-        if (nblk > nblk0 + (nb_fixed ? 8 : 0) || p_new > p_uni) { NB = NB0; NBL = 0; nblk = nblk0; }
-    }
-    std::vector<long long> tb;
-    std::vector<int> tg;
-    if (h->M.kind == BB_MODEL_GENOTYPE) {
-        // cuts on genotype boundaries leave tiles partly empty: grow the tile until the map fits the grid again
-        const int limit = std::max(nblk0, std::min(nblk0 + 8, h->cus));
-        bool ok = false;
-        for (int grow = 0; grow <= NB / 2 + 8 && !ok; ++grow) {
-            const int nb = NB + grow, nbl = NBL > 0 ? std::max(1, (int)((long long)NBL * nb / NB)) : 0;
-            if (build_geno_tiles(h, nb, nbl, ng, tb, tg) && (int)tb.size() - 1 <= limit) { ok = true; NB = nb; NBL = nbl; }
-            else if (nb_fixed && NBL > 0 && build_geno_tiles(h, nb, 0, ng, tb, tg) && (int)tb.size() - 1 <= limit) { ok = true; NB = nb; NBL = 0; }
-        }
-        if (!ok) return false;
-        nblk = (int)tb.size() - 1;
-        if (h->p2p_on && nblk < 8) return false;
-    }
-    if (!h->p2p_on && h->M.Dh != h->M.Dp) return false;      // (packed window rows: only the cross-GPU instances read the segments' differences)
-    int P = (int)((br_tile_span(h->M, NB, true) + h->nthr - 1) / h->nthr);
-    // more pair slots than the register file holds: k_stream (bb_stream.h) -- the same tile map, the per-pair state streamed
-    const int Pmax = h->nthr > 512 ? 2 : (h->nthr > 256 ? 3 : 4);
-    bool stream = false;
-    if (tu.force_stream || P > Pmax) {        // (BB_TUNE_STREAM, tests: small shapes through k_stream)
-        const int T0 = uniform_T(h->M);
-        // every replicate the same even T (instances: 4, 6, 8), flat-index-aligned pairs, one GPU; several samples per step / the ELBO trace:
-        // the MS instances (T = 6, 8 at 1024 threads; tests: 512).  A barcode takes a power-of-two number of lanes there: T = 6 four.
-        const int Ps = (int)((br_tile_span(h->M, NB, true, true) + h->nthr - 1) / h->nthr);
-        stream = !tu.no_stream && !br_any_parity(h->M) && (T0 == 8 || T0 == 6 || T0 == 4) && h->nthr % 64 == 0 && !h->p2p_on && Ps <= 64;
-        if (stream) P = Ps;
-        else if (P > Pmax) return false;
-    }
-    // When the window slot is fetched (RunArgs.pf).  In the exchange's shadow (round 2) its 32 B per latent of HBM reads compete with
-    // the exchange's own loads and stores: at the start of the S pass instead, C2 73.1 -> 77.7 k steps/s, C4 87.1 -> 89.1 k
-    // (profiles/r03b_tagged_rows/prefetch_timing_on_lean_kernel.txt) -- where the slot buffer fits beside the moment contributions.
-    // (At the end of the previous step's G pass instead: tied with the start of the S pass on C2 and C4, same file.  Behind the exchange,
-    //  where there is no room for a slot buffer of its own: 6 % slower on C3 than in the exchange's shadow.)
-    int pf = h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && !stream ? 1 : 0;
-    BRLay Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, pf == 1, stream);
-    if (pf != 0 && (size_t)Y.total * 8 > 160 * 1024) { pf = 0; Y = br_layout(h->M, NB, h->nthr, P, h->p2p_on ? 8 * h->o.world_size : 0, false); }      // (no room for a slot buffer of its own: in the exchange's shadow)
-    if ((size_t)Y.total * 8 > 160 * 1024) return false;
-    std::string nm;
-    const void* k = resident_instance(h, stream, P, p.ms, nm);
-    if (resident_fit(k, h->nthr, (size_t)Y.total * 8, nblk, h->cus)) return false;
-    if (nblk > h->tile_cap) return false;       // (more tiles than the exchange, stamp, xsel and tile-table buffers hold)
-    if (h->M.kind == BB_MODEL_GENOTYPE) {
-        if (!h->d_tile_b && (dalloc(h, &h->d_tile_b, (size_t)h->tile_cap + 2) || dalloc(h, &h->d_tile_g, (size_t)h->tile_cap + 2))) return false;
-        if (h2d(h->d_tile_b, tb.data(), tb.size() * 8, h->stream) || h2d(h->d_tile_g, tg.data(), tg.size() * 4, h->stream)) return false;
-        h->S.tile_b = h->d_tile_b;
-        h->S.tile_g = h->d_tile_g;
-    }
-    h->Yh = Y;
-    LaunchPlan r = p;
-    r.impl = stream ? IMPL_STREAM : IMPL_RES;
-    r.P = P; r.NB = NB; r.NBL = NBL; r.nblk = nblk; r.ng = ng; r.pf = pf; r.fn = k; r.name = nm;
-    if (stream && h->o.samples_per_step > 1 && ensure_scratch(h)) return false;      // (the samples' gradient sums live in gacc_mu / gacc_om)
-    h->lds_doubles_p = (size_t)Y.total;
-    if (!host_tables(h, r, tb, tg)) return false;
-    p = r;
-    return true;
-}
-
-// h->plan for launch_mode `mode` (0: resident where possible, 1: two kernels, 2: resident or an error saying why not)
-static int setup_persistent(bb_handle* h, int mode) {
-    LaunchPlan& p = h->plan;
-    p = LaunchPlan{};
-    p.NB = h->NB;
-    p.nblk = h->nblk;
-    p.name = step_kernels_name(h->M.kind);
-    // several MC samples per step (Turing.ADVI(samples_per_step, ..), src/vi.jl:98) and ELBO recording: k_res's MS instances (round 4: sharded too --
-    // every sample is an exchange of its own, the inbox epochs count exchanges)
-    p.ms = h->o.samples_per_step != 1 || h->o.elbo_every != 0;
-    const bool want = mode != 1 && !(h->tune.no_persist && mode == 0);
-    // what rules out every resident launch (k_res's own tile map never has fewer tiles than this one)
-    const char* structural = (h->tune.force_allreduce || (h->o.world_size != 1 && !h->p2p_on)) ? "sharded run"
-                             : (h->p2p_on && h->nblk < 8) ? "fewer than 8 tiles on this rank" : nullptr;
-    const bool ap_first = p.ms || h->M.kind == BB_MODEL_GENOTYPE || h->tune.any_parity;
-    const char* why = structural;
-    if (!why && want && try_resident(h, ap_first, p)) return 0;
-    if (!why && p.ms) why = h->o.samples_per_step != 1 ? "samples_per_step != 1 and the shape has no owner-computes instance" : "ELBO recording is on and the shape has no owner-computes instance";
-    if (!why && h->M.kind == BB_MODEL_GENOTYPE)
-        why = h->M.geno_sorted ? "genotype model: no tile map with whole genotypes per tile fits the device" : "genotype model: geno_idx is not in consecutive runs (a tile must hold whole genotypes)";
-    int P = 0;
-    if (!why) {
-        P = (int)((tile_pairs_bound(h->M, h->NB) + h->nthr - 1) / h->nthr);
-        if (P == 3 && h->nthr > 512) P = 4;      // (no 3-pair instance at 1024 threads; 4 is refused just below)
-        if (P > (h->nthr > 512 ? 2 : 4)) why = "tile too large for the register-resident state";
-        if (h->p2p_on && P != 1) why = "sharded resident launch holds one pair per thread";
-        h->lds_doubles_p = h->lds_doubles_p0 + (size_t)3 * P * h->nthr;        // drawn-ahead normals (16 B / pair) + cached counts (8 B)
-    }
-    std::string nm;
-    const void* k = nullptr;
-    if (!why && want) {
-        k = persist_instance(h, P, nm);
-        const size_t lds = h->lds_doubles_p * 8;
-        why = lds > PERSIST_LDS_CAP ? "tile does not fit LDS with the lambda table" : resident_fit(k, h->nthr, lds, h->nblk, h->cus);
-    }
-    if (why) {
-        // k_persist cannot (tile too large for its state, no instance, sharded with more than one pair per thread ...): k_res's
-        // any-parity instances as the second chance
-        if (want && !structural && !ap_first && try_resident(h, true, p)) return 0;
-        p.why = why;
-        return mode == 2 ? bb_fail(BB_ERR_UNSUPPORTED, "launch_mode = 2 (persistent) not possible: %s", why) : 0;
-    }
-    if (want) { p.impl = IMPL_PERSIST; p.P = P; p.fn = k; p.name = nm; }
-    return 0;
-}
-
-// the arguments of the planned resident launch: its tile map (k_persist's is the two-kernel one), every sample an exchange of its own
-// (k_persist runs one sample per step)
-static RunArgs resident_args(const bb_handle* h) {
-    RunArgs A = make_args(h, h->step, 0, h->o.samples_per_step, true, false);
-    A.nblk = h->plan.nblk; A.nbl = h->plan.NBL; A.ng = h->plan.ng; A.pf = h->plan.pf;
-    return A;
-}
+// resident launches (bb_persist.h, bb_resident.h, bb_stream.h), the plan: the kernel lookup, plan_launch and its stages (the decision),
+// install_plan (the one place that changes the handle), sync_descriptors, resident_args
+#include "bb_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // resident launches: in the emulation
@@ -1760,15 +1419,15 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
     BB_GROUP_UNSUPPORTED(h, "bb_p2p_enable");
     BB_ENTER(h);
     if (on && !h->p2p_ready) return bb_fail(BB_ERR_INVALID, "bb_p2p_import comes first");
+    Planned plan;
+    int rc = plan_or_refuse(h, on ? 2 : h->o.launch_mode, on != 0, plan);      // (the cross-GPU leg needs a resident launch: an error says why not)
+    // ... and the handle was never touched.  (Switching the leg OFF is never refused: without the leg the handle plans as it did in
+    // bb_create, which a launch_mode = 2 handle has passed.)
+    if (rc) return rc;
     h->p2p_on = on != 0;
-    int rc = setup_persistent(h, h->p2p_on ? 2 : h->o.launch_mode);      // (the cross-GPU leg needs a resident launch: an error says why not)
-    if (rc) {
-        h->p2p_on = false;
-        (void)setup_persistent(h, h->o.launch_mode);
-        (void)sync_descriptors(h);
-        return rc;
-    }
-    if ((rc = sync_descriptors(h))) return rc;
+    if ((rc = install_plan(h, plan))) h->p2p_on = false;      // (what install_plan leaves then, the two-kernel step, runs without the cross-GPU leg)
+    { const int rcs = sync_descriptors(h); if (!rc) rc = rcs; }
+    if (rc) return rc;
     return h->p2p_on ? resident_warm(h) : BB_OK;
 }
 

@@ -99,7 +99,7 @@ struct DevState {
     int *xsel;                        // [nblk + 8] what each tile of the last resident launch decided about its row stores: 1 plain (same XCD as its leader), -1 write-through, 0 not decided
     unsigned long long *xtab;         // [BB_NG_MAX] k_res / k_stream: where the group leaders run -- {launch tag << 32 | XCC id}, written by every leader at the start of
                                       //   a launch; a member whose own XCC id is the leader's stores its row with plain stores (br_row_publish)
-    const double *segtab;             // k_res / k_stream: the tiles' segment tables, built on the host (bb_engine.hip, host_tables): [tiles][segtab_stride] doubles,
+    const double *segtab;             // k_res / k_stream: the tiles' segment tables, built on the host (bb_plan.h, host_tables): [tiles][segtab_stride] doubles,
     int segtab_stride;                //   each = (4 + 4 R + 1) BRSeg records + one word with their count; nullptr: thread 0 of a tile builds its own
     const int *ldstab;                // ... and the tile-independent LDS descriptor tables [rowmap 2 K | tmap K | ftab 4 Ttot | rtab 4 R]
     const long long *tile_b;          // genotype model, k_res: [tiles + 1] first barcode of every tile (cuts fall on genotype boundaries)

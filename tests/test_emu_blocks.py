@@ -114,7 +114,7 @@ def test_same_xcd_row_stores_switch(emu_lib, monkeypatch, name):
 
 @pytest.mark.parametrize("name", ["fitness_T6", "multienv_T8", "replicate_R3", "multienv_replicate_T6", "genotype_runs"])
 def test_host_built_tables_equal_the_kernels_own(emu_lib, monkeypatch, name):
-    """The tiles' segment tables and the LDS descriptor tables come from the host (bb_engine.hip, host_tables); BB_NO_HOST_TABLES=1
+    """The tiles' segment tables and the LDS descriptor tables come from the host (bb_plan.h, host_tables); BB_NO_HOST_TABLES=1
     makes every tile build them in its prologue, as before: the runs must agree bit for bit."""
     import numpy as np
     from conftest import make_engine
