@@ -115,7 +115,7 @@ struct BackendState {
 };
 struct DevGuard {
     int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
+    explicit DevGuard(int d) : dev(d) { if (d < 0) return; if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }      // (d < 0: no guard)
     ~DevGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
     DevGuard(const DevGuard&) = delete;
     DevGuard& operator=(const DevGuard&) = delete;

@@ -1,6 +1,6 @@
-// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle and the step loop; the launch plan (plan_launch,
-// install_plan) is in bb_plan.h, handle creation (bb_create) in bb_create.h and the post-fit entry points (hier fitness, log-density
-// batch, predictive bands and scores, Rao-Blackwellised fitness marginals, chain summary) in bb_analysis.h, all three included below.
+// bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the resident launchers, groups and the cross-GPU
+// leg; what a step launches is in bb_step.h, the launch plan in bb_plan.h, handle creation in bb_create.h, the run path (bb_run and its
+// kin) in bb_run.h and the post-fit entry points (hier fitness, log-density batch, bands, scores, chain summary) in bb_analysis.h, all included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -59,6 +59,8 @@ extern "C" const char* bb_version(void) { return BB_BACKEND_VERSION; }
 // Every entry point that takes a handle runs with the handle's device current and restores the caller's on exit: the
 // caller may have switched devices since bb_create (torch.cuda.set_device, other handles on other GPUs in this process).
 #define BB_ENTER(h) DevGuard bb_dev_guard_((h)->o.device)
+#define BB_GROUP_UNSUPPORTED(h, what) \
+    do { if (!(h)->shards.empty()) return bb_fail(BB_ERR_UNSUPPORTED, what " is not available on a multi-device handle (n_devices > 1)"); } while (0)
 
 // The environment switches, read once by bb_create and kept in the handle; a multi-device handle's shards get the
 // group's copy.  read_tuning says how each one is read.
@@ -214,13 +216,6 @@ static int dalloc(bb_handle* h, T** p, size_t count) {
     return dzero(q, count * sizeof(T), h->stream);
 }
 
-static int ensure_scratch(bb_handle* h);
-static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, bool apply, bool with_elbo);
-static int theta_sync_local(bb_handle* const* hs, int n);
-static int launch_persistent(bb_handle* h, long long nsteps);
-static int run_enqueue(bb_handle* h, int64_t n_steps);
-static int run_finish(bb_handle* h);
-
 // f(std::integral_constant<int, KIND>{}) for the model kind: the host-side instances of templates over it
 template <class F>
 static void by_kind(int kind, F&& f) {
@@ -232,6 +227,9 @@ static void by_kind(int kind, F&& f) {
     default: f(std::integral_constant<int, 4>{});
     }
 }
+
+// what one step launches: make_args, ensure_scratch, the launchers, the two exchanges, step_sample and its stages; theta gather; set_step, reset_optimizer
+#include "bb_step.h"
 
 // resident launches (bb_persist.h, bb_resident.h, bb_stream.h), the plan: the kernel lookup, plan_launch and its stages (the decision),
 // install_plan (the one place that changes the handle), sync_descriptors, resident_args
@@ -480,10 +478,6 @@ static int resident_launch(bb_handle* h, RunArgs, long long nsteps) {
     return emu_run_group(&h, 1, nsteps);
 }
 static void resident_timeout_ack(bb_handle*) {}
-static int resident_warm(bb_handle*) { return BB_OK; }
-static int group_run_resident(bb_handle* g, int64_t n_steps) {      // the emulation steps the shards in lock step
-    return bb_emu_run_group(g->shards.data(), (int)g->shards.size(), n_steps);
-}
 
 // ------------------------------------------------------------------------------------------------
 // ... and on the device
@@ -517,29 +511,25 @@ static void resident_timeout_ack(bb_handle* h) {
     if (!d2h(c, h->S.ctr, sizeof c, h->stream)) h->step = (long long)c[0];
     if (!dzero(h->S.gbar, 32 * 10 * 4, h->stream)) (void)dsync(h->stream);
 }
-// a zero-step launch loads the kernel's code object now (seconds on a cold process), not while the peers already poll;
-// the first real launch still gets a longer poll limit (launch skew between the ranks' processes)
-static int resident_warm(bb_handle* h) {
-    h->p2p_first = true;
-    const long long keep = h->req_steps;
-    int rc = launch_persistent(h, 0);
-    h->req_steps = keep;
-    return rc ? rc : dsync(h->stream);
-}
-// the shards' launches are all enqueued before any is waited for
-static int group_run_resident(bb_handle* g, int64_t n_steps) {
-    int rc = 0, rc2 = 0;
-    for (bb_handle* sh : g->shards) { BB_ENTER(sh); if ((rc = run_enqueue(sh, n_steps))) break; }
-    for (bb_handle* sh : g->shards) { BB_ENTER(sh); const int r = run_finish(sh); if (r && !rc2) rc2 = r; }      // (wait for whatever was launched, also after an error)
-    if (!rc) rc = rc2;
-    if (!rc) rc = theta_sync_local(g->shards.data(), (int)g->shards.size());     // (genotype model: theta_g back from its owner)
-    return rc;
-}
 #endif
 
 static int launch_persistent(bb_handle* h, long long nsteps) {
     h->req_steps += nsteps * std::max(h->o.samples_per_step, 1);      // (exchanges asked: the rows' epochs count them)
     return resident_launch(h, resident_args(h), nsteps);
+}
+
+// a zero-step launch loads the kernel's code object now (seconds on a cold process), not while the peers already poll;
+// the first real launch still gets a longer poll limit (launch skew between the ranks' processes)
+static int resident_warm(bb_handle* h) {
+#ifdef BB_EMU
+    return BB_OK;
+#else
+    h->p2p_first = true;
+    const long long keep = h->req_steps;
+    int rc = launch_persistent(h, 0);
+    h->req_steps = keep;
+    return rc ? rc : dsync(h->stream);
+#endif
 }
 
 // after the stream has drained: the launches' status words (host-mapped, no copy)
@@ -560,6 +550,9 @@ static int check_persistent(bb_handle* h) {
 }
 
 #include "bb_create.h"      // handle creation: bb_default_opts, create_inner and its stages, the caller's order, bb_create; hist_rows, owned_ranges
+
+// how steps are strung together: graphs, run_enqueue / run_finish, bb_run, bb_run_profiled, bb_elbo_grad, bb_logdensity_grad, the ELBO trace, split-phase steps
+#include "bb_run.h"
 
 // caller indices of the latents THIS handle owns on a sharded run (its barcodes' latents; genotype model: theta of its own genotypes) -- what
 // a gather of the ranks' posteriors takes from this rank.  The replicated global blocks are not in the list.  idx: [bb_num_latents(h)].
@@ -605,202 +598,6 @@ extern "C" int bb_get_layout(const bb_handle* h, bb_block_range* blocks, int32_t
     for (size_t i = 0; i < h->blocks.size(); ++i) blocks[i] = h->blocks[i];
     return BB_OK;
 }
-
-// ------------------------------------------------------------------------------------------------
-// launches
-// ------------------------------------------------------------------------------------------------
-static RunArgs make_args(const bb_handle* h, long long step, int sample, int S, bool apply, bool with_elbo) {
-    RunArgs A;
-    memset(&A, 0, sizeof A);
-    A.b_lo = h->b_lo;
-    A.b_hi = h->b_hi;
-    A.rank = h->o.rank;
-    A.world = h->o.world_size;
-    A.xepoch0 = h->epoch0;
-    A.spin_limit = 1u << 23;                  // ~1 us per poll: seconds, not milliseconds
-    A.row_l2 = h->tune.row_l2;
-    A.nblk = h->nblk;
-    A.nblk_alloc = h->tile_cap - 8;            // (the device adds the 8 back: BB_STAMP_WAVE)
-    A.ng = 8;
-    A.par = (int)(step & 1);
-    A.sample = sample;
-    A.S = S;
-    A.first_sample = sample == 0;
-    A.last_sample = sample == S - 1;
-    A.apply = apply ? 1 : 0;
-    A.with_elbo = with_elbo ? 1 : 0;
-    A.count_globals = h->o.rank == 0;
-    A.opt = h->o.optimizer;
-    A.W = h->o.window;
-    A.resum_every = h->o.resum_every;
-    A.elbo_every = h->o.elbo_every;
-    A.eta = h->o.eta;
-    A.tau = h->o.tau;
-    A.pre = h->o.pre;
-    A.post = h->o.post;
-    A.seed = h->o.seed;
-    A.elbo_const = h->elbo_const;
-    if (h->use_reduce()) { A.red = h->S.totals; A.nred = 1; }
-    else { A.red = h->S.partials; A.nred = h->nblk; }
-    return A;
-}
-
-// Per-sample scratch of the two-kernel step (z, eps sigmoid, sigmoid / softplus), the S > 1 / gradient-export accumulators and
-// bb_elbo_grad's saved parameters: 7 arrays of D doubles, allocated on first use -- every entry point that can reach the
-// two-kernel launchers calls this first (never from inside a stream capture); the resident launches use none of them.
-static int ensure_scratch(bb_handle* h) {
-    if (h->S.zsv) return BB_OK;
-    // ONE slab carved into the seven arrays: a failed allocation leaves nothing behind (seven separate ones left the earlier arrays
-    // in h->owned with stale pointers in S, and a retry allocated them all again -- ADVICE r03)
-    const size_t D = (size_t)h->M.D, n = (D + 2 + 1) & ~(size_t)1;
-    double* slab = nullptr;
-    int rc = dalloc(h, &slab, 7 * n);
-    if (rc) return rc;
-    h->S.zsv = slab; h->S.asv = slab + n; h->S.hsv = slab + 2 * n; h->S.gacc_mu = slab + 3 * n; h->S.gacc_om = slab + 4 * n;
-    h->bak_mu = slab + 5 * n; h->bak_om = slab + 6 * n;
-    return h->dS ? h2d(h->dS, &h->S, sizeof(DevState), h->stream) : BB_OK;      // (kernels read the descriptor through its device copy)
-}
-
-// the small kernels of the two-kernel step (k_sample / k_update: the instance of the model kind, descriptors through pointers)
-static int launch_sample(bb_handle* h, const RunArgs& A) {
-    if (!h->S.zsv) return bb_fail(BB_ERR_DEVICE, "internal: the two-kernel step's scratch arrays were not allocated (ensure_scratch)");
-    int rc = 0;
-    by_kind(h->M.kind, [&](auto kindc) {
-        rc = launch(h->stream, k_sample<decltype(kindc)::value>, h->nblk, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), desc_ptr(h->dS, &h->S), A, h->NB);
-    });
-    return rc;
-}
-static int launch_update(bb_handle* h, const RunArgs& A) {
-    if (!h->S.zsv) return bb_fail(BB_ERR_DEVICE, "internal: the two-kernel step's scratch arrays were not allocated (ensure_scratch)");
-    int rc = 0;
-    by_kind(h->M.kind, [&](auto kindc) {
-        rc = launch(h->stream, k_update<decltype(kindc)::value>, h->nblk, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), desc_ptr(h->dS, &h->S), A, h->NB);
-    });
-    return rc;
-}
-static int launch_reduce(bb_handle* h) {
-    return launch(h->stream, k_reduce, 1, 256, (size_t)16 * h->M.K, h->M, h->S, h->nblk, h->ngeno_blk);
-}
-static int launch_geno(bb_handle* h, const RunArgs& A, int do_update, int do_sample, int upd_par) {
-    if (!h->S.zsv) return bb_fail(BB_ERR_DEVICE, "internal: the two-kernel step's scratch arrays were not allocated (ensure_scratch)");
-    return launch(h->stream, k_geno, h->ngeno_blk, 256, 256 + 64, h->M, h->S, A, do_update, do_sample, upd_par);
-}
-static int launch_geno_sum(bb_handle* h) {
-    const long long m_lo = std::max(h->b_lo, h->M.nn) - h->M.nn, m_hi = std::max(h->b_hi, h->M.nn) - h->M.nn;
-    const int gsb = (int)std::min<long long>((h->M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block
-    return launch(h->stream, k_geno_sum, gsb, 256, 256, h->M, h->S, m_lo, m_hi);
-}
-
-static int allreduce(bb_handle* h, double* buf, size_t n) {
-    if (h->o.world_size == 1 && !h->tune.force_allreduce) return 0;
-    return comm_allreduce(h->be, h->stream, buf, n, h->o.world_size);
-}
-
-// Genotype model with the shards cut at genotype boundaries: a resident run updates theta_g on its owner only.  Gathering the
-// owners' copies (parameters, optimiser accumulators, window rows) = summing rows that hold zeros for what a shard does not own.
-static size_t theta_rows(const bb_handle* h) { return 6 + (h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD ? 2 * (size_t)h->o.window : 0); }
-static bool theta_partial(const bb_handle* h) { return h->M.kind == BB_MODEL_GENOTYPE && (h->g_lo > 0 || h->g_hi < h->M.G); }
-static int theta_pack(bb_handle* h, int unpack) {
-    const size_t n = theta_rows(h) * (size_t)h->M.G;
-    int rc;
-    if (!h->theta_buf && (rc = dalloc(h, &h->theta_buf, n))) return rc;
-    const int W = h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD ? h->o.window : 0;
-    const int nb = (int)std::min<size_t>((n + 255) / 256, 512);
-    return launch(h->stream, k_theta_pack, nb, 256, 0, h->M, h->S, h->theta_buf, h->g_lo, h->g_hi, W, unpack);
-}
-// ranks of a multi-process run: through the RCCL communicator (collective: every rank is here after the same bb_run)
-static int theta_sync_comm(bb_handle* h) {
-    int rc;
-    if ((rc = theta_pack(h, 0))) return rc;
-    if ((rc = allreduce(h, h->theta_buf, theta_rows(h) * (size_t)h->M.G))) return rc;
-    if ((rc = theta_pack(h, 1))) return rc;
-    h->theta_stale = false;
-    return dsync(h->stream);
-}
-// handles of one process (the shards of a multi-device handle; the emulation's ranks): summed on the host
-static int theta_sync_local(bb_handle* const* hs, int n) {
-    if (n < 2 || !theta_partial(hs[0])) return 0;
-    const size_t len = theta_rows(hs[0]) * (size_t)hs[0]->M.G;
-    std::vector<double> part(len), total(len, 0.0);
-    int rc;
-    for (int i = 0; i < n; ++i) {
-        BB_ENTER(hs[i]);
-        if ((rc = theta_pack(hs[i], 0)) || (rc = d2h(part.data(), hs[i]->theta_buf, len * 8, hs[i]->stream))) return rc;
-        for (size_t k = 0; k < len; ++k) total[k] += part[k];
-    }
-    for (int i = 0; i < n; ++i) {
-        BB_ENTER(hs[i]);
-        if ((rc = h2d(hs[i]->theta_buf, total.data(), len * 8, hs[i]->stream)) || (rc = theta_pack(hs[i], 1)) || (rc = dsync(hs[i]->stream))) return rc;
-        hs[i]->theta_stale = false;
-    }
-    return 0;
-}
-
-// first half of one MC sample: draw + moments (+ reduce to totals when sharded / genotype)
-static int sample_half(bb_handle* h, const RunArgs& A) {
-    int rc;
-    if (h->M.kind == BB_MODEL_GENOTYPE && (rc = launch_geno(h, A, 0, 1, 0))) return rc;
-    if ((rc = launch_sample(h, A))) return rc;
-    if (h->use_reduce() && (rc = launch_reduce(h))) return rc;
-    return 0;
-}
-// second half: gradient + update (+ the genotype block's exchange and update)
-static int update_half(bb_handle* h, const RunArgs& A) {
-    int rc;
-    if ((rc = launch_update(h, A))) return rc;
-    if (h->M.kind == BB_MODEL_GENOTYPE) {
-        if ((rc = launch_geno_sum(h))) return rc;
-        if ((rc = allreduce(h, h->S.gsum, (size_t)h->M.G))) return rc;
-        if ((rc = launch_geno(h, A, 1, 0, A.par))) return rc;
-    }
-    return 0;
-}
-
-static bool elbo_wanted(const bb_handle* h, long long step) {
-    return h->o.elbo_every > 0 && step % h->o.elbo_every == 0;
-}
-
-static int enqueue_step(bb_handle* h, long long step) {
-    const int S = h->o.samples_per_step;
-    int rc;
-    for (int s = 0; s < S; ++s) {
-        RunArgs A = make_args(h, step, s, S, true, elbo_wanted(h, step));
-        if ((rc = sample_half(h, A))) return rc;
-        if ((rc = allreduce(h, h->S.totals, (size_t)h->M.K))) return rc;
-        if ((rc = update_half(h, A))) return rc;
-    }
-    return 0;
-}
-
-static int set_step(bb_handle* h, long long step) {
-    unsigned long long c[2] = {(unsigned long long)step, (unsigned long long)step};
-    h->step = step;
-    h->sample = 0;
-    return h2d(h->S.ctr, c, sizeof c, h->stream);
-}
-
-static int reset_optimizer(bb_handle* h) {
-    const size_t D = (size_t)h->M.D;
-    int rc;
-    if ((rc = dzero(h->S.accl, (2 * D + 8) * 4, h->stream))) return rc;
-    if (h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD) {
-        if ((rc = dzero(h->S.hist, (size_t)h->o.window * 2 * (size_t)h->M.Dh * 8, h->stream))) return rc;
-        if ((rc = dzero(h->S.acc_mu, D * 8, h->stream))) return rc;
-        if ((rc = dzero(h->S.acc_om, D * 8, h->stream))) return rc;
-    } else {
-        std::vector<double> a(D, 1e-8);   // AdvancedVI: acc = fill(1e-8, size(x))
-        if ((rc = h2d(h->S.acc_mu, a.data(), D * 8, h->stream))) return rc;
-        if ((rc = h2d(h->S.acc_om, a.data(), D * 8, h->stream))) return rc;
-    }
-    std::vector<double> nanv(BB_ELBO_RING, NAN);
-    if ((rc = h2d(h->S.elbo_ring, nanv.data(), nanv.size() * 8, h->stream))) return rc;
-    // ready / inbox words never repeat, also across restarts: the base moves by the steps ASKED of the resident launch since
-    // the last restart -- the same number on every rank of a sharded run, wherever a timeout may have stopped each of them
-    h->epoch0 += (unsigned)h->req_steps + 1u;
-    h->req_steps = 0;
-    return set_step(h, 0);
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // single-process multi-device handle (bb_advi_opts.n_devices > 1; SURVEY.md 8b: "multi-GPU is driven inside the library by
@@ -882,42 +679,33 @@ static int group_create(const bb_model_desc* md, const bb_advi_opts* opts, const
     return BB_OK;
 }
 
+// resident: the shards' launches are all enqueued before any is waited for (the emulation steps them in lock step)
+static int group_run_resident(bb_handle* g, int64_t n_steps) {
+#ifdef BB_EMU
+    return bb_emu_run_group(g->shards.data(), (int)g->shards.size(), n_steps);
+#else
+    int rc = 0, rc2 = 0;
+    for (bb_handle* sh : g->shards) { BB_ENTER(sh); if ((rc = run_enqueue(sh, n_steps))) break; }
+    for (bb_handle* sh : g->shards) { BB_ENTER(sh); const int r = run_finish(sh); if (r && !rc2) rc2 = r; }      // (wait for whatever was launched, also after an error)
+    if (!rc) rc = rc2;
+    if (!rc) rc = theta_sync_local(g->shards.data(), (int)g->shards.size());     // (genotype model: theta_g back from its owner)
+    return rc;
+#endif
+}
+
 static int group_run(bb_handle* g, int64_t n_steps) {
     int rc = 0;
     if (g->group_resident) {
         rc = group_run_resident(g, n_steps);
     } else {
-        // the two-kernel step of every shard with the exchanges (K moments; per-genotype gradient sums of the genotype model)
-        // summed on the host: enqueue_step with host reductions in place of the RCCL all-reduces
-        const int S = g->o.samples_per_step < 1 ? 1 : g->o.samples_per_step;
-        const size_t K = (size_t)g->shards[0]->M.K, G = (size_t)g->shards[0]->M.G;
-        const bool geno = g->shards[0]->M.kind == BB_MODEL_GENOTYPE;
-        std::vector<double> part(std::max(K, G)), total(std::max(K, G));
+        // the two-kernel step over all shards, the exchanges summed on the host in place of the RCCL all-reduces
+        const int S = g->o.samples_per_step < 1 ? 1 : g->o.samples_per_step, n = (int)g->shards.size();
+        std::vector<RunArgs> As((size_t)n);
         for (bb_handle* sh : g->shards) { BB_ENTER(sh); if ((rc = ensure_scratch(sh))) return rc; }
-        auto exchange = [&](size_t n, double* DevState::*buf) -> int {
-            std::fill(total.begin(), total.begin() + n, 0.0);
-            for (bb_handle* sh : g->shards) {
-                BB_ENTER(sh);
-                int r = d2h(part.data(), sh->S.*buf, n * 8, sh->stream);
-                if (r) return r;
-                for (size_t k = 0; k < n; ++k) total[k] += part[k];
-            }
-            for (bb_handle* sh : g->shards) { BB_ENTER(sh); int r = h2d(sh->S.*buf, total.data(), n * 8, sh->stream); if (r) return r; }
-            return 0;
-        };
         for (int64_t it = 0; it < n_steps && !rc; ++it) {
             for (int smp = 0; smp < S && !rc; ++smp) {
-                std::vector<RunArgs> As;
-                for (bb_handle* sh : g->shards) As.push_back(make_args(sh, sh->step, smp, S, true, elbo_wanted(sh, sh->step)));
-                for (size_t i = 0; i < g->shards.size() && !rc; ++i) { BB_ENTER(g->shards[i]); rc = sample_half(g->shards[i], As[i]); }
-                if (!rc) rc = exchange(K, &DevState::totals);
-                for (size_t i = 0; i < g->shards.size() && !rc; ++i) {
-                    BB_ENTER(g->shards[i]);
-                    rc = launch_update(g->shards[i], As[i]);
-                    if (!rc && geno) rc = launch_geno_sum(g->shards[i]);
-                }
-                if (!rc && geno) rc = exchange(G, &DevState::gsum);
-                for (size_t i = 0; i < g->shards.size() && !rc && geno; ++i) { BB_ENTER(g->shards[i]); rc = launch_geno(g->shards[i], As[i], 1, 0, As[i].par); }
+                for (int i = 0; i < n; ++i) { const bb_handle* sh = g->shards[i]; As[i] = make_args(sh, sh->step, smp, S, true, elbo_wanted(sh, sh->step)); }
+                rc = step_sample(g->shards.data(), n, As.data(), host_sum_exchange);
             }
             for (bb_handle* sh : g->shards) sh->step++;
         }
@@ -942,9 +730,6 @@ static int group_get_params(bb_handle* g, double* mu, double* omega) {
     }
     return rc;
 }
-
-#define BB_GROUP_UNSUPPORTED(h, what) \
-    do { if (!(h)->shards.empty()) return bb_fail(BB_ERR_UNSUPPORTED, what " is not available on a multi-device handle (n_devices > 1)"); } while (0)
 
 extern "C" int bb_init_meanfield(bb_handle* h) {
     if (!h) return bb_fail(BB_ERR_INVALID, "null handle");
@@ -1000,271 +785,6 @@ extern "C" int bb_get_posterior(bb_handle* h, double* mean, double* sigma) {
     int rc = bb_get_params(h, mean, sigma);
     if (rc) return rc;
     for (long long i = 0; i < h->M.D; ++i) sigma[i] = host_softplus(sigma[i]);   // sigma = softplus(omega), O(D) once at the end
-    return BB_OK;
-}
-
-// Captured graphs of the step loop: as many whole graphs of the remaining steps as fit, `done` moved past them.  Whole steps only,
-// starting on an even step (static ping-pong parity); the elbo_every pattern must repeat with the graph -> only when ELBO recording
-// is off; no collectives inside.  The emulation has none: every step is enqueued on its own.
-#ifndef BB_EMU
-static int build_graph(bb_handle* h, int steps) {
-    BackendState& be = h->be;
-    if (be.graph && be.graph_steps == steps) return 0;
-    if (be.graph) { (void)hipGraphExecDestroy(be.graph); be.graph = nullptr; }
-    hipGraph_t g = nullptr;
-    BB_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    for (int i = 0; i < steps && !rc; ++i) rc = enqueue_step(h, i);   // parity of i == parity of the real step (even start)
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (rc || e != hipSuccess) {
-        if (g) (void)hipGraphDestroy(g);
-        (void)hipGetLastError();
-        be.graph_failed = true;      // not an error: bb_run launches eagerly instead
-        return 0;
-    }
-    e = hipGraphInstantiate(&be.graph, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) { be.graph = nullptr; (void)hipGetLastError(); be.graph_failed = true; return 0; }
-    be.graph_steps = steps;
-    return 0;
-}
-static int run_graphs(bb_handle* h, int64_t n_steps, int64_t& done) {
-    int rc = 0;
-    int gs = h->o.steps_per_graph == 0 ? 50 : h->o.steps_per_graph;
-    // A sharded step (with its RCCL all-reduce) can be captured too (BB_GRAPH_COLLECTIVE=1; equal results, no gain
-    // measured: the step is GPU-bound), but multi-rank capture could not be exercised on the one-GPU boxes this was
-    // developed on, so sharded runs launch eagerly by default.
-    const bool graph_ok = gs > 0 && h->o.elbo_every == 0 && !h->be.graph_failed && !h->tune.no_graph &&
-                          ((h->o.world_size == 1 && !h->tune.force_allreduce) || h->tune.graph_collective);
-    if (!graph_ok) return 0;
-    gs &= ~1;
-    if (gs < 2) gs = 2;
-    if ((h->step & 1) && done < n_steps) { if ((rc = enqueue_step(h, h->step))) return rc; h->step++; done++; }
-    if (n_steps - done >= gs) {
-        if ((rc = build_graph(h, gs))) return rc;
-        while (h->be.graph && n_steps - done >= gs) {
-            BB_HIP(hipGraphLaunch(h->be.graph, h->stream));
-            h->graph_launches++;
-            h->step += gs;
-            done += gs;
-        }
-    }
-    return 0;
-}
-#else
-static int run_graphs(bb_handle*, int64_t, int64_t&) { return 0; }
-#endif
-
-// bb_run in two halves (a multi-device handle enqueues on all its shards before it waits for any)
-static int run_enqueue(bb_handle* h, int64_t n_steps) {
-    if (h->sample != 0) return bb_fail(BB_ERR_INVALID, "a split-phase step is in flight");
-    int rc = 0;
-    int64_t done = 0;
-    if (h->plan.impl == IMPL_TWO_KERNEL && (rc = ensure_scratch(h))) return rc;
-    if (h->hstatus) h->hstatus[1] = 0;          // divergence flag of THIS run (nothing of this handle is in flight here)
-    if ((rc = timer_start(h->be, h->stream))) return rc;
-    h->launches_last_run = 0;
-    h->graph_launches = 0;
-    if (h->plan.impl != IMPL_TWO_KERNEL && n_steps > 0) {
-        if ((rc = launch_persistent(h, n_steps))) return rc;
-        done = n_steps;
-        h->launches_last_run = (int)((n_steps + 4095) / 4096);
-        if (theta_partial(h)) h->theta_stale = true;         // only the owner's theta_g moved (bb_run / group_run gather it afterwards)
-    } else if (h->theta_stale && n_steps > 0 && (rc = theta_sync_comm(h))) return rc;
-    if ((rc = run_graphs(h, n_steps, done))) return rc;
-    for (; done < n_steps; ++done) {
-        if ((rc = enqueue_step(h, h->step))) return rc;
-        h->step++;
-    }
-    return timer_stop(h->be, h->stream);
-}
-static int run_finish(bb_handle* h) {
-    int rc = timer_wait(h->be, h->stream, &h->last_run_ms);
-    return rc ? rc : check_persistent(h);
-}
-
-extern "C" int bb_run(bb_handle* h, int64_t n_steps) {
-    if (!h || n_steps < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
-    if (!h->shards.empty()) return group_run(h, n_steps);
-#ifdef BB_HOST_TIMES          // diagnostics (tools/launch_probe.py): where the host's share of a run goes
-    timespec ht0, ht1, ht2, ht3;
-    clock_gettime(CLOCK_MONOTONIC, &ht0);
-#endif
-    BB_ENTER(h);
-#ifdef BB_HOST_TIMES
-    clock_gettime(CLOCK_MONOTONIC, &ht1);
-#endif
-    int rc = run_enqueue(h, n_steps);
-    if (rc) return rc;
-#ifdef BB_HOST_TIMES
-    clock_gettime(CLOCK_MONOTONIC, &ht2);
-#endif
-    rc = run_finish(h);
-#ifdef BB_HOST_TIMES
-    clock_gettime(CLOCK_MONOTONIC, &ht3);
-    auto us = [](const timespec& a, const timespec& b) { return (b.tv_sec - a.tv_sec) * 1e6 + (b.tv_nsec - a.tv_nsec) * 1e-3; };
-    fprintf(stderr, "[bb_run %lld] device guard %.1f us, enqueue %.1f us, wait + status %.1f us, events %.1f us\n", (long long)n_steps, us(ht0, ht1), us(ht1, ht2), us(ht2, ht3), h->last_run_ms * 1e3);
-#endif
-    if (h->theta_stale && comm_ready(h->be)) {
-        // Collective, so EVERY rank takes it whatever its own launch reported: the timeout word and the non-finite flag run_finish
-        // looks at are this rank's alone, and a rank that returned early here would leave the clean ranks inside ncclAllReduce.
-        // The rank's own error is reported afterwards (the gathered theta rows of a failed run mean nothing, but nobody hangs).
-        const std::string why(g_err);
-        const int rc2 = theta_sync_comm(h);
-        if (rc) snprintf(g_err, sizeof g_err, "%s", why.c_str());
-        else rc = rc2;
-    }
-    return rc;
-}
-
-// bb_run_profiled: every launch of the two-kernel step between events of its own (the emulation has no clock worth reading: a plain run)
-#ifdef BB_EMU
-static int run_profiled(bb_handle* h, int64_t n_steps) { return bb_run(h, n_steps); }
-#else
-static int run_profiled(bb_handle* h, int64_t n_steps) {
-    if (h->use_reduce()) return bb_fail(BB_ERR_UNSUPPORTED, "bb_run_profiled covers the single-GPU two-kernel step only");
-    { const int rcs = ensure_scratch(h); if (rcs) return rcs; }
-    const int S = h->o.samples_per_step;
-    const size_t nl = (size_t)n_steps * S;
-    std::vector<hipEvent_t> ev(3 * nl);
-    for (auto& e : ev) BB_HIP(hipEventCreate(&e));
-    int rc = 0;
-    for (int64_t i = 0; i < n_steps && !rc; ++i) {
-        for (int s = 0; s < S && !rc; ++s) {
-            RunArgs A = make_args(h, h->step, s, S, true, elbo_wanted(h, h->step));
-            const size_t k = 3 * ((size_t)i * S + s);
-            BB_HIP(hipEventRecord(ev[k], h->stream));
-            rc = launch_sample(h, A);
-            BB_HIP(hipEventRecord(ev[k + 1], h->stream));
-            if (!rc) rc = launch_update(h, A);
-            BB_HIP(hipEventRecord(ev[k + 2], h->stream));
-        }
-        h->step++;
-    }
-    BB_HIP(hipStreamSynchronize(h->stream));
-    double ts = 0, tu = 0;
-    for (size_t k = 0; k < nl; ++k) {
-        float a = 0, b = 0;
-        BB_HIP(hipEventElapsedTime(&a, ev[3 * k], ev[3 * k + 1]));
-        BB_HIP(hipEventElapsedTime(&b, ev[3 * k + 1], ev[3 * k + 2]));
-        ts += a;
-        tu += b;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (nl) { h->avg_sample_ms = ts / nl; h->avg_update_ms = tu / nl; }
-    return rc;
-}
-#endif
-extern "C" int bb_run_profiled(bb_handle* h, int64_t n_steps) {
-    if (!h || n_steps < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
-    BB_GROUP_UNSUPPORTED(h, "bb_run_profiled");
-    BB_ENTER(h);
-    return run_profiled(h, n_steps);
-}
-
-static int elbo_grad_raw(bb_handle* h, const double* mu, const double* omega, const double* eps, int32_t S,
-                         double* elbo, double* grad_mu, double* grad_omega);
-extern "C" int bb_elbo_grad(bb_handle* h, const double* mu, const double* omega, const double* eps, int32_t S,
-                            double* elbo, double* grad_mu, double* grad_omega) {
-    if (!h || !mu || !omega || S < 1) return bb_fail(BB_ERR_INVALID, "bad argument");
-    if (h->cidx.empty()) return elbo_grad_raw(h, mu, omega, eps, S, elbo, grad_mu, grad_omega);
-    const size_t D = h->cidx.size();
-    std::vector<double> pm(D), po(D), pe, gm(D), go(D);
-    perm_gather(h, mu, pm.data());
-    perm_gather(h, omega, po.data());
-    if (eps) { pe.resize((size_t)S * D); for (int s = 0; s < S; ++s) perm_gather(h, eps + (size_t)s * D, pe.data() + (size_t)s * D); }
-    int rc = elbo_grad_raw(h, pm.data(), po.data(), eps ? pe.data() : nullptr, S, elbo, grad_mu ? gm.data() : nullptr, grad_omega ? go.data() : nullptr);
-    if (rc) return rc;
-    if (grad_mu) perm_scatter(h, gm.data(), grad_mu);
-    if (grad_omega) perm_scatter(h, go.data(), grad_omega);
-    return BB_OK;
-}
-static int elbo_grad_raw(bb_handle* h, const double* mu, const double* omega, const double* eps, int32_t S,
-                         double* elbo, double* grad_mu, double* grad_omega) {
-    if (!h || !mu || !omega || S < 1) return bb_fail(BB_ERR_INVALID, "bad argument");
-    BB_GROUP_UNSUPPORTED(h, "bb_elbo_grad");
-    BB_ENTER(h);
-    if (h->o.world_size > 1 && !eps) return bb_fail(BB_ERR_UNSUPPORTED, "bb_elbo_grad on a sharded handle needs explicit eps");
-    const size_t D = (size_t)h->M.D;
-    int rc;
-    // what can fail before the handle is touched: scratch, the copy of the parameters to put back, room for the draws, and for the
-    // per-sample ELBO values where S is more than the handle's own buffer holds
-    if ((rc = ensure_scratch(h))) return rc;
-    if ((rc = d2d(h->bak_mu, h->S.mu, D * 8, h->stream)) || (rc = d2d(h->bak_om, h->S.om, D * 8, h->stream))) return rc;
-    if (eps && (rc = h->buf[BUF_EPS].grow((size_t)S * D))) return rc;
-    void* es = nullptr;
-    if (S > h->o.samples_per_step + 64 && (rc = dmalloc(&es, (size_t)S * 8))) return rc;
-    // from here on the handle holds the caller's point and buffers: every path goes through the restore below
-    double* const saved_es = h->S.elbo_sample;
-    std::vector<double> ev((size_t)S);
-    auto eval = [&]() -> int {
-        int r;
-        if ((r = h2d(h->S.mu, mu, D * 8, h->stream)) || (r = h2d(h->S.om, omega, D * 8, h->stream))) return r;
-        if (eps) {
-            if ((r = h2d(h->buf[BUF_EPS].p, eps, (size_t)S * D * 8, h->stream))) return r;
-            h->S.eps_in = h->buf[BUF_EPS].p;
-        }
-        if (es) h->S.elbo_sample = (double*)es;
-        if ((r = sync_descriptors(h))) return r;
-        for (int s = 0; s < S; ++s) {
-            RunArgs A = make_args(h, h->step, s, S, false, true);
-            if ((r = sample_half(h, A)) || (r = allreduce(h, h->S.totals, (size_t)h->M.K)) || (r = update_half(h, A))) return r;
-        }
-        return d2h(ev.data(), h->S.elbo_sample, (size_t)S * 8, h->stream);
-    };
-    rc = eval();
-    h->S.elbo_sample = saved_es;
-    if (es) dfree(es);
-    h->S.eps_in = nullptr;
-    { int rcs = sync_descriptors(h); if (!rc) rc = rcs; }
-    if (!rc && grad_mu) rc = d2h(grad_mu, h->S.gacc_mu, D * 8, h->stream);
-    if (!rc && grad_omega) rc = d2h(grad_omega, h->S.gacc_om, D * 8, h->stream);
-    int rc2 = d2d(h->S.mu, h->bak_mu, D * 8, h->stream);
-    int rc3 = d2d(h->S.om, h->bak_om, D * 8, h->stream);
-    int rc4 = dsync(h->stream);
-    if (rc) return rc;
-    if (rc2 || rc3 || rc4) return rc2 ? rc2 : (rc3 ? rc3 : rc4);
-    if (elbo) {
-        double v = 0;
-        for (int s = 0; s < S; ++s) v += ev[(size_t)s];
-        *elbo = v / S;
-    }
-    return BB_OK;
-}
-
-// log-joint density and its gradient at a point of the unconstrained latent space: the ELBO machinery with the
-// draw pinned to the mean (eps = 0) and sigma = softplus(omega) = 1, minus the entropy terms -- what an HMC / NUTS
-// sampler asks of a model (`LogDensityProblems.logdensity_and_gradient`; the reference's src/mcmc.jl:86-160 path)
-extern "C" int bb_logdensity_grad(bb_handle* h, const double* z, double* logp, double* grad) {
-    if (!h || !z) return bb_fail(BB_ERR_INVALID, "null argument");
-    BB_ENTER(h);
-    const size_t D = (size_t)h->M.D;
-    const double om1 = 0.54132485461291810;                  // log(e - 1): softplus = 1
-    if (h->ld_omega.size() != D) { h->ld_omega.assign(D, om1); h->ld_zero.assign(D, 0.0); }
-    double elbo = 0.0;
-    int rc = bb_elbo_grad(h, z, h->ld_omega.data(), h->ld_zero.data(), 1, &elbo, grad, nullptr);
-    if (rc) return rc;
-    if (logp) *logp = elbo - 0.5 * (double)D * (1.0 + BB_LOG2PI) - (double)D * log(log1p(exp(om1)));
-    return BB_OK;
-}
-
-extern "C" int bb_get_elbo_trace(bb_handle* h, int64_t first_step, int64_t n, double* out) {
-    if (!h || !out || n < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
-    if (!h->shards.empty()) return bb_get_elbo_trace(h->shards[0], first_step, n, out);      // (every shard forms the same estimate from the same totals)
-    BB_ENTER(h);
-    if (h->o.elbo_every <= 0) return bb_fail(BB_ERR_INVALID, "ELBO recording is off (elbo_every = 0)");
-    std::vector<double> ring(BB_ELBO_RING);
-    int rc = dsync(h->stream);
-    if (rc) return rc;
-    if ((rc = d2h(ring.data(), h->S.elbo_ring, ring.size() * 8, h->stream))) return rc;
-    const int64_t ev = h->o.elbo_every;
-    const int64_t newest = h->step > 0 ? (h->step - 1) / ev : -1;
-    for (int64_t k = 0; k < n; ++k) {
-        const int64_t st = first_step + k * ev;
-        const int64_t idx = st / ev;
-        const bool have = st % ev == 0 && st >= 0 && st < h->step && idx > newest - BB_ELBO_RING;
-        out[k] = have ? ring[(size_t)(idx % BB_ELBO_RING)] : NAN;
-    }
     return BB_OK;
 }
 
@@ -1510,38 +1030,4 @@ extern "C" int bb_comm_init(bb_handle* h, const void* id_in) {
     BB_GROUP_UNSUPPORTED(h, "bb_comm_init");
     BB_ENTER(h);
     return comm_init(h->be, id_in, h->o.device, h->o.world_size, h->o.rank);
-}
-
-extern "C" int bb_step_moments(bb_handle* h, double* partial) {
-    if (!h || !partial) return bb_fail(BB_ERR_INVALID, "null argument");
-    BB_GROUP_UNSUPPORTED(h, "bb_step_moments");
-    BB_ENTER(h);
-    if (h->M.kind == BB_MODEL_GENOTYPE && h->o.world_size > 1)
-        return bb_fail(BB_ERR_UNSUPPORTED, "split-phase stepping of the sharded genotype model needs a second exchange; use bb_comm_init + bb_run");
-    const int S = h->o.samples_per_step;
-    int rc;
-    if ((rc = ensure_scratch(h))) return rc;
-    RunArgs A = make_args(h, h->step, h->sample, S, true, elbo_wanted(h, h->step));
-    A.red = h->S.totals;   // the caller-reduced totals come back through bb_step_apply
-    A.nred = 1;
-    if (h->M.kind == BB_MODEL_GENOTYPE && (rc = launch_geno(h, A, 0, 1, 0))) return rc;
-    if ((rc = launch_sample(h, A))) return rc;
-    if ((rc = launch_reduce(h))) return rc;
-    return d2h(partial, h->S.totals, (size_t)h->M.K * 8, h->stream);
-}
-
-extern "C" int bb_step_apply(bb_handle* h, const double* total) {
-    if (!h || !total) return bb_fail(BB_ERR_INVALID, "null argument");
-    BB_GROUP_UNSUPPORTED(h, "bb_step_apply");
-    BB_ENTER(h);
-    const int S = h->o.samples_per_step;
-    RunArgs A = make_args(h, h->step, h->sample, S, true, elbo_wanted(h, h->step));
-    A.red = h->S.totals;
-    A.nred = 1;
-    int rc;
-    if ((rc = ensure_scratch(h))) return rc;
-    if ((rc = h2d(h->S.totals, total, (size_t)h->M.K * 8, h->stream))) return rc;
-    if ((rc = update_half(h, A))) return rc;
-    if (++h->sample == S) { h->sample = 0; h->step++; }
-    return dsync(h->stream);
 }

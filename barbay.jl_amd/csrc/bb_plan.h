@@ -1,7 +1,7 @@
 // bb_plan.h -- resident launches (bb_persist.h, bb_resident.h, bb_stream.h): the plan.  Which of the four step implementations bb_run
 // launches and with what tile map is DECIDED first -- plan_launch, a function of the handle and a launch mode that changes no handle
 // field and allocates or copies nothing on the device -- and INSTALLED once: install_plan, the one place that writes the plan's handle
-// fields and device tables.  Included by bb_engine.hip (after the handle, before the launchers).
+// fields and device tables.  Included by bb_engine.hip (after the handle and bb_step.h, before the resident launchers).
 
 // the time-point count where all replicates share it (the compile-time-T instances), else 0
 static int uniform_T(const DevModel& M) {

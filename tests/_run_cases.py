@@ -244,7 +244,45 @@ def case_graph_replay(lib, name, g, S, optname):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# D. the non-finite status
+# D. bb_run_profiled: bb_run's two-kernel step with events between the two launches
+# ---------------------------------------------------------------------------------------------------------------------------
+def case_run_profiled(lib, row, gpu):
+    """run_profiled(7) launches the kernels run(7) launches, with the same arguments in the same order: parameters, step count and ELBO
+    trace are equal bit for bit (as test_graph_equals_eager holds graph replay to eager).  On the GPU it leaves the two launches' mean
+    times in bb_stats.  A multi-device handle is refused, and on the GPU a handle that reduces (world_size = 2) too; the emulation has no
+    clock, runs bb_run in its place and so has nothing to refuse there."""
+    import barbay_jl_amd as bb
+    path, r = PATHS["two_kernel"], ROWS[row]
+    sp = _sp(path["shape"])
+    kw = dict(seed=SEED, samples_per_step=r["S"], optimizer=r["opt"], window=WINDOW, elbo_every=r["ev"], **r["kw"], **path["kw"])
+    n = math.ceil(7 / r["ev"])
+    outs = []
+    for profiled in (False, True):
+        with make_engine(sp, lib, **kw) as e:
+            check_instance(e, path)
+            outs.append([e.get_params()])
+            (e.run_profiled if profiled else e.run)(7)
+            st = e.stats()
+            outs[-1] += [e.get_params(), st["steps_done"], e.elbo_trace(0, n)]
+    (p0, p1, done, tr), (q0, q1, qdone, qtr) = outs
+    assert np.array_equal(p0[0], q0[0]) and np.array_equal(p0[1], q0[1])          # the same initial state
+    assert not np.array_equal(p0[0], p1[0])          # ... which the seven steps moved
+    assert np.array_equal(p1[0], q1[0]) and np.array_equal(p1[1], q1[1])
+    assert done == qdone == 7
+    assert np.isfinite(tr).all() and np.array_equal(tr, qtr), (tr, qtr)
+    print(f"run_profiled row {row}: avg_sample_ms {st['avg_sample_ms']:.4f} avg_update_ms {st['avg_update_ms']:.4f}")
+    if gpu:
+        assert st["avg_sample_ms"] > 0 and st["avg_update_ms"] > 0, st
+        with make_engine(sp, lib, rank=0, world_size=2, **kw) as e:
+            with pytest.raises(bb.BarBayHipError, match="single-GPU two-kernel step only"):
+                e.run_profiled(7)
+    with make_engine(sp, lib, device_ids=[0, 0], **kw) as e:
+        with pytest.raises(bb.BarBayHipError, match="not available on a multi-device handle"):
+            e.run_profiled(7)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# E. the non-finite status
 # ---------------------------------------------------------------------------------------------------------------------------
 def case_nonfinite(lib, pname):
     """A NaN / Inf planted in any block of the parameters makes bb_run return BB_ERR_NONFINITE -- after taking its steps, with the state

@@ -22,6 +22,11 @@ def test_frozen_run_wraps_the_elbo_ring(emu_lib, monkeypatch, path):
     r.case_frozen_ring(emu_lib, path)
 
 
+@pytest.mark.parametrize("row", [1, 2])
+def test_run_profiled(emu_lib, row):
+    r.case_run_profiled(emu_lib, row, gpu=False)
+
+
 @pytest.mark.parametrize("path", list(r.PATHS))
 def test_nonfinite_status(emu_lib, monkeypatch, path):
     r.set_env(monkeypatch, r.PATHS[path])

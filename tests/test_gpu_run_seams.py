@@ -29,6 +29,11 @@ def test_graph_replay(hip_lib, name, g, S, opt):
     r.case_graph_replay(hip_lib, name, g, S, opt)
 
 
+@pytest.mark.parametrize("row", [1, 2])
+def test_run_profiled(hip_lib, row):
+    r.case_run_profiled(hip_lib, row, gpu=True)
+
+
 @pytest.mark.parametrize("path", list(r.PATHS))
 def test_nonfinite_status(hip_lib, monkeypatch, path):
     r.set_env(monkeypatch, r.PATHS[path])
