@@ -26,6 +26,7 @@ BB_CHAIN_LAG_BATCH = 32
 BB_SCORE_MAX_SAMPLES = 16384
 BB_RB_MAX_SAMPLES = 8672
 BB_RB_MAX_Q = 8
+BB_THETA_RB_CHUNK = 64
 BB_MATH_FN = {"exp": 0, "log": 1, "rcp": 2, "div": 3, "sqrt": 4, "softplus_sigmoid": 5, "sincospi": 6, "exp_nonpos": 7, "log_1to2": 8,
               "box_muller": 9}
 BB_ERR_UNSUPPORTED = -4
@@ -37,7 +38,7 @@ EXPORTS = [
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
-    "bb_fitness_rb_shape", "bb_fitness_rb",
+    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -128,6 +129,10 @@ class bb_rb_out(C.Structure):
     _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("n_steps", C.POINTER(C.c_int32))]
 
 
+class bb_theta_rb_out(C.Structure):
+    _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("n_members", C.POINTER(C.c_int32)), ("n_steps", C.POINTER(C.c_int32))]
+
+
 class bb_chain_opts(C.Structure):
     _fields_ = [
         ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("n_quantiles", C.c_int32), ("max_lag", C.c_int32),
@@ -207,6 +212,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_fitness_rb"):
         lib.bb_fitness_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_fitness_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_rb_out)]
+    if hasattr(lib, "bb_theta_rb"):
+        lib.bb_theta_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
+        lib.bb_theta_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_theta_rb_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     return lib
@@ -574,18 +582,7 @@ class Engine:
         q_mean, q_sd (the draws' own fitness), rb_mean, rb_sd, p_pos, p_neg (the RB probability of a fitness above / below
         `threshold`), each [n_units], and quantiles [n_units, len(probs)] of the RB mixture at the probabilities `probs`."""
         n_units = self.fitness_rb_shape()
-        p = _f64(np.atleast_1d(probs)).reshape(-1)
-        o = bb_rb_opts()
-        o.n_samples, o.n_quantiles, o.threshold, o.seed = int(n_samples), int(p.shape[0]), float(threshold), int(seed)
-        o.probs = _ptr(p) if p.shape[0] else None
-        if draws is not None:
-            x = np.ascontiguousarray(draws, dtype=np.float64)
-            if x.ndim == 1:
-                x = x[None, :]
-            if x.ndim != 2 or x.shape[1] != self.D:
-                raise BarBayHipError(f"draws must be [n_samples, {self.D}]")
-            o.n_samples = x.shape[0]
-            o.draws = _ptr(x)
+        o, p, _x = self._rb_opts(n_samples, probs, threshold, seed, draws)
         res = {k: np.empty(n_units) for k in RB_UNITS}
         res["quantiles"] = np.empty((n_units, p.shape[0]))
         res["n_steps"] = np.empty(n_units, dtype=np.int32)
@@ -595,6 +592,51 @@ class Engine:
         out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
         out.n_steps = res["n_steps"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_fitness_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def _rb_opts(self, n_samples, probs, threshold, seed, draws):
+        """(bb_rb_opts, probs, draws): the arrays the options point into must outlive the call."""
+        p = _f64(np.atleast_1d(probs)).reshape(-1)
+        o = bb_rb_opts()
+        o.n_samples, o.n_quantiles, o.threshold, o.seed = int(n_samples), int(p.shape[0]), float(threshold), int(seed)
+        o.probs = _ptr(p) if p.shape[0] else None
+        x = None
+        if draws is not None:
+            x = np.ascontiguousarray(draws, dtype=np.float64)
+            if x.ndim == 1:
+                x = x[None, :]
+            if x.ndim != 2 or x.shape[1] != self.D:
+                raise BarBayHipError(f"draws must be [n_samples, {self.D}]")
+            o.n_samples = x.shape[0]
+            o.draws = _ptr(x)
+        return o, p, x
+
+    def theta_rb_shape(self) -> int:
+        """Groups of `theta_rb`: the length of the theta block (genotypes; e + E m for the replicate kinds); 0 for the
+        non-hierarchical kinds."""
+        n = C.c_int64(0)
+        self._check(self._lib.bb_theta_rb_shape(self._h, C.byref(n)))
+        return int(n.value)
+
+    def theta_rb(self, n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
+                 draws=None) -> Dict[str, np.ndarray]:
+        """Rao-Blackwellised marginal of every hyper-fitness theta_g of a hierarchical model (`bb_theta_rb`): its exact Gaussian
+        full conditional -- the prior and the log-frequency-ratio terms of the group's members, a genotype's mutants or a mutant's
+        replicates -- averaged over the draws of `fitness_rb` (same arguments).  Returns what `fitness_rb` returns, per group
+        (n_steps: the members' steps together), plus n_members (int32)."""
+        n_groups = self.theta_rb_shape()
+        o, p, _x = self._rb_opts(n_samples, probs, threshold, seed, draws)
+        res = {k: np.empty(n_groups) for k in RB_UNITS}
+        res["quantiles"] = np.empty((n_groups, p.shape[0]))
+        res["n_steps"] = np.empty(n_groups, dtype=np.int32)
+        res["n_members"] = np.empty(n_groups, dtype=np.int32)
+        out = bb_theta_rb_out()
+        for k in RB_UNITS:
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.n_steps = res["n_steps"].ctypes.data_as(C.POINTER(C.c_int32))
+        out.n_members = res["n_members"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_theta_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,

@@ -1,5 +1,5 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
-// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb (bb_rb.h) and bb_chain_summary
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb (bb_rb.h) and bb_chain_summary
 // (bb_chain.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
@@ -223,6 +223,7 @@ struct BandsCall {
     bb_handle* dh;                 // the handle that samples
     DevGuard guard;
     std::vector<double> prm;       // mean | sigma = softplus(omega), the caller's layout
+    std::vector<int> geno;         // genotype model: geno_idx in the caller's mutant order (caller_geno), once it has been fetched
     size_t nbands = 0;             // doubles of the result
     long long nblk = 0;            // grid of the row program (k_ppc / k_freq, 1024 threads)
     int npop = 0;                  // grid of k_ppc_pop
@@ -280,6 +281,17 @@ static int bands_prologue(bb_handle* h, int32_t n_samples, int32_t n_ppc, int32_
     B.npop = (int)std::max<long long>(1, std::min<long long>(((long long)P.nt1 * n_samples + 255) / 256, 1024));
     return BB_OK;
 }
+// B.geno: geno_idx in the caller's mutant order (the handle keeps its own, regrouped one), fetched once per call
+static int caller_geno(const bb_handle* h, BandsCall& B) {
+    const DevModel& M = B.dh->M;
+    if (!B.geno.empty() || M.nb == 0) return BB_OK;
+    std::vector<int> gi((size_t)M.nb);
+    int rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, B.dh->stream);
+    if (rc) return rc;
+    B.geno = gi;
+    if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) B.geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
+    return BB_OK;
+}
 // The device buffer of a band call, `extra` naming what the call puts between the row scratch and the bands; then what needs the
 // pointers: mean | sigma uploaded and, genotype model, geno_idx in the caller's mutant order (the handle keeps its own, regrouped one).
 template <class X>
@@ -301,12 +313,9 @@ static int bands_buffers(const bb_handle* h, PpcArgs& P, BandsCall& B, X&& extra
     P.mean = post;
     P.sigma = post + D;
     if ((rc = h2d(post, B.prm.data(), 2 * D * 8, dh->stream)) || M.kind != BB_MODEL_GENOTYPE) return rc;
-    std::vector<int> gi((size_t)M.nb);
-    if ((rc = d2h(gi.data(), M.geno_idx, (size_t)M.nb * 4, dh->stream))) return rc;
-    std::vector<int> geno = gi;
-    if (!h->perm_m.empty()) for (long long m = 0; m < M.nb; ++m) geno[(size_t)h->perm_m[(size_t)m]] = gi[(size_t)m];
+    if ((rc = caller_geno(h, B))) return rc;
     P.geno_idx = dg;
-    return h2d(dg, geno.data(), (size_t)M.nb * 4, dh->stream);
+    return h2d(dg, B.geno.data(), (size_t)M.nb * 4, dh->stream);
 }
 
 // The walk over the observed counts that both n_outside computations make.  The handle's counts are in its own barcode order ([B][T_r]
@@ -523,8 +532,8 @@ extern "C" int bb_fitness_rb_shape(const bb_handle* h, int64_t* n_units) {
     return BB_OK;
 }
 
-extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out) {
-    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+// the option checks bb_fitness_rb and bb_theta_rb share
+static int rb_check(const bb_rb_opts* o) {
     const int nq = o->n_quantiles, ns = o->n_samples;
     if (nq < 0 || nq > BB_RB_MAX_Q || (nq > 0 && !o->probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_RB_MAX_Q);
     for (int i = 0; i < nq; ++i)
@@ -532,6 +541,13 @@ extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out*
     if (!std::isfinite(o->threshold)) return bb_fail(BB_ERR_INVALID, "threshold must be finite");
     const int ns_lo = o->draws ? 1 : 2;
     if (ns < ns_lo || ns > BB_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_RB_MAX_SAMPLES);
+    return BB_OK;
+}
+
+extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    if (int rc = rb_check(o)) return rc;
     BandsCall B(h);
     bb_handle* dh = B.dh;
     const DevModel& M = dh->M;
@@ -600,6 +616,193 @@ extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out*
     lap(5);
 #ifdef BB_RB_TIMES
     fprintf(stderr, "[bb_fitness_rb %lld units, %d samples, %d quantiles] upload %.3f ms, pop %.3f ms, normalisers %.3f ms, rb %.3f ms, download %.3f ms\n", n_units, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
+}
+
+// ---- Rao-Blackwellised hyper-fitness marginals (bb_rb.h) -------------------------------------------------------------------------
+static_assert(BB_THETA_RB_CHUNK == BB_THETA_CHUNK, "bb_theta_rb chunk");
+static long long theta_groups(const bb_handle* h) {
+    return h->M.kind < BB_MODEL_GENOTYPE ? 0 : h->M.blk_hi[BK_S] - h->M.blk_lo[BK_S];
+}
+extern "C" int bb_theta_rb_shape(const bb_handle* h, int64_t* n_groups) {
+    if (!h || !n_groups) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_groups = theta_groups(h);
+    return BB_OK;
+}
+
+// The chunk map of bb_block_theta_part / bb_block_theta, in the caller's order: a group's members ascending (genotype: the caller's
+// mutants m with geno_idx[m] == g; replicate kinds: r = 0 .. R - 1), cut into chunks of BB_THETA_CHUNK consecutive members.
+struct ThetaMap {
+    std::vector<int> grp_c0, grp_nst, grp_nmem, chk_grp, chk_m0, mem_row, mem_nu;
+};
+static int theta_map(const bb_handle* h, BandsCall& B, int E, ThetaMap& tm) {
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    const long long G = theta_groups(h), nb = M.nb;
+    const bool geno = M.kind == BB_MODEL_GENOTYPE;
+    int rc;
+    // n_u of (replicate, environment)
+    std::vector<int> env;
+    if (E > 1) {
+        env.resize((size_t)M.Ttot);
+        if ((rc = d2h(env.data(), M.env_idx, (size_t)M.Ttot * 4, dh->stream))) return rc;
+    }
+    std::vector<int> nu((size_t)M.R * E, 0);
+    for (int r = 0; r < M.R; ++r)
+        for (int t = 0; t + 1 < M.T[r]; ++t) nu[(size_t)r * E + (E > 1 ? env[(size_t)(M.tcum[r] + t + 1)] : 0)]++;
+    // members: first member of every group, then the rows
+    std::vector<long long> m0((size_t)G + 1, 0);
+    if (geno) {
+        if ((rc = caller_geno(h, B))) return rc;
+        const std::vector<int>& gi = B.geno;
+        for (long long m = 0; m < nb; ++m) m0[(size_t)gi[(size_t)m] + 1]++;
+        for (long long g = 0; g < G; ++g) m0[(size_t)g + 1] += m0[(size_t)g];
+        tm.mem_row.resize((size_t)nb);
+        std::vector<long long> at(m0.begin(), m0.end() - 1);
+        for (long long m = 0; m < nb; ++m) tm.mem_row[(size_t)at[(size_t)gi[(size_t)m]]++] = (int)m;
+    } else {
+        if ((long long)M.R * nb * E > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_theta_rb: more than 2^31 members");
+        tm.mem_row.resize((size_t)(G * M.R));
+        for (long long g = 0; g < G; ++g) {
+            m0[(size_t)g + 1] = (g + 1) * M.R;
+            for (int r = 0; r < M.R; ++r) tm.mem_row[(size_t)(g * M.R + r)] = (int)(r * nb + g / E);
+        }
+    }
+    tm.mem_nu.assign(tm.mem_row.size(), 0);
+    tm.grp_c0.assign((size_t)G + 1, 0);
+    tm.grp_nst.assign((size_t)G, 0);
+    tm.grp_nmem.assign((size_t)G, 0);
+    tm.chk_grp.clear();
+    tm.chk_m0.clear();
+    for (long long g = 0; g < G; ++g) {
+        const long long a = m0[(size_t)g], b = m0[(size_t)g + 1];
+        tm.grp_c0[(size_t)g] = (int)tm.chk_grp.size();
+        tm.grp_nmem[(size_t)g] = (int)(b - a);
+        for (long long x = a; x < b; x += BB_THETA_CHUNK) { tm.chk_grp.push_back((int)g); tm.chk_m0.push_back((int)x); }
+        long long nst = 0;
+        for (long long x = a; x < b; ++x) {
+            tm.mem_nu[(size_t)x] = nu[(size_t)(tm.mem_row[(size_t)x] / nb) * E + (geno ? 0 : g % E)];
+            nst += tm.mem_nu[(size_t)x];
+        }
+        tm.grp_nst[(size_t)g] = (int)nst;
+    }
+    tm.grp_c0[(size_t)G] = (int)tm.chk_grp.size();
+    tm.chk_m0.push_back((int)m0[(size_t)G]);
+    return BB_OK;
+}
+
+extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    if (int rc = rb_check(o)) return rc;
+    if (h->M.kind < BB_MODEL_GENOTYPE)
+        return bb_fail(BB_ERR_UNSUPPORTED, "bb_theta_rb applies to the hierarchical models only: model kind %d (%s) has no theta", (int)h->M.kind,
+                       h->M.kind == BB_MODEL_FITNESS ? "BB_MODEL_FITNESS" : "BB_MODEL_MULTIENV");
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    ThetaArgs H;
+    memset(&H, 0, sizeof H);
+    RbArgs& A = H.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const long long n_groups = theta_groups(h);
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
+    if (rc) return rc;
+    int zb;
+    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    {   // the prior of theta: the block is never regrouped (a genotype keeps its number, the replicate kinds keep the caller's order),
+        // so a Matrix form lies in the handle as the caller gave it, indexed by g
+        const DevPrior& dp = M.pri[BK_S];
+        P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    }
+    A.nq = nq;
+    A.threshold = o->threshold;
+    A.n_units = n_groups;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+#ifdef BB_RB_TIMES             // diagnostics (tools/theta_rb_rate.py): the call's phases, each drained before the next starts
+    timespec ct[8];
+    double cms[7] = {0, 0, 0, 0, 0, 0, 0};
+    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int, int) {};
+#endif
+    lap(0, -1);
+    ThetaMap tm;
+    if ((rc = theta_map(h, B, P.E, tm))) return rc;
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ng = (size_t)n_groups, nchk = tm.chk_grp.size(), nmem = tm.mem_row.size();
+    // the groups in flight: their chunk partials bounded to 256 MiB (a single group is worked whole whatever it takes)
+    const size_t cap = std::max<size_t>(1, ((size_t)256 << 20) / (2 * nsz * 8));
+    size_t slab_chunks = 1;
+    std::vector<size_t> cut{0};                       // slab s: the groups [cut[s], cut[s + 1])
+    while (cut.back() < ng) {
+        const size_t g0 = cut.back();
+        size_t g1 = g0 + 1;
+        while (g1 < ng && (size_t)(tm.grp_c0[g1 + 1] - tm.grp_c0[g0]) <= cap) ++g1;
+        slab_chunks = std::max(slab_chunks, (size_t)(tm.grp_c0[g1] - tm.grp_c0[g0]));
+        cut.push_back(g1);
+    }
+    const int nblk = (int)std::max<long long>(1, std::min<long long>(n_groups, B.nblk));      // (P.par holds a [nblk][ns] table of theta_j)
+    double* ddraws = nullptr;
+    int* dmap = nullptr;
+    const size_t nmap = (ng + 1) + ng + nchk + (nchk + 1) + 2 * nmem;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(H.part, slab_chunks * 2 * nsz);              // [chunks in flight][2][ns]
+        c(A.unit, BB_RB_OUT * ng);                     // [6][n_groups]
+        c(A.quant, BB_RB_MAX_Q * ng);                  // [n_groups][8]
+        c(dmap, (nmap + 1) / 2);                       // the chunk map: ints
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    A.ytab = P.par;
+    {
+        std::vector<int> hm;
+        hm.reserve(nmap);
+        int* p = dmap;
+        auto put = [&](const int*& dst, const std::vector<int>& v) { dst = p; p += v.size(); hm.insert(hm.end(), v.begin(), v.end()); };
+        put(H.grp_c0, tm.grp_c0); put(H.grp_nst, tm.grp_nst); put(H.chk_grp, tm.chk_grp); put(H.chk_m0, tm.chk_m0); put(H.mem_row, tm.mem_row); put(H.mem_nu, tm.mem_nu);
+        if ((rc = h2d(dmap, hm.data(), nmap * 4, dh->stream))) return rc;
+    }
+    if (o->draws) {
+        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
+        P.draws = ddraws;
+        P.D = (long long)D;
+    }
+    lap(1, 0);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    lap(2, 1);
+    if ((rc = freq_normalisers(dh, F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
+    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
+    lap(3, 2);
+    for (size_t sl = 0; sl + 1 < cut.size(); ++sl) {
+        const size_t g0 = cut[sl], g1 = cut[sl + 1];
+        H.g0 = (long long)g0; H.g1 = (long long)g1;
+        H.c0 = tm.grp_c0[g0]; H.c1 = tm.grp_c0[g1];
+        lap(4, -1);
+        if (H.c1 > H.c0 && (rc = launch(dh->stream, k_rb_theta_part, std::min(H.c1 - H.c0, 1 << 20), BB_SCORE_NT, 0, H))) return rc;
+        lap(5, 3);
+        if ((rc = launch(dh->stream, k_rb_theta, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), H))) return rc;
+        lap(6, 4);
+    }
+    double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
+    for (int k = 0; k < BB_RB_OUT; ++k)
+        if (units[k] && (rc = d2h(units[k], A.unit + (size_t)k * ng, ng * 8, dh->stream))) return rc;
+    if (out->quantiles && nq) {
+        std::vector<double> q(BB_RB_MAX_Q * ng);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
+        for (size_t g = 0; g < ng; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
+    }
+    if (out->n_members) memcpy(out->n_members, tm.grp_nmem.data(), ng * 4);
+    if (out->n_steps) memcpy(out->n_steps, tm.grp_nst.data(), ng * 4);
+    rc = dsync(dh->stream);
+    lap(7, 5);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_theta_rb %lld groups, %zu members, %zu chunks, %d samples, %d quantiles] map+upload %.3f ms, pop %.3f ms, normalisers %.3f ms, part %.3f ms, theta %.3f ms, download %.3f ms\n", n_groups, nmem, nchk, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4], cms[5]);
 #endif
     return rc;
 }

@@ -417,6 +417,14 @@ BB_KERNEL(BB_SCORE_NT, k_rb, RbArgs A) {
     BB_CTX;
     bb_block_rb(cx, A, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_rb_theta_part, ThetaArgs H) {
+    BB_CTX;
+    bb_block_theta_part(cx, H, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_rb_theta, ThetaArgs H) {
+    BB_CTX;
+    bb_block_theta(cx, H, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

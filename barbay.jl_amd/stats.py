@@ -21,6 +21,9 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
     fitness_marginals                                             the Rao-Blackwellised marginal of every mutant's fitness beside the
                                                                   mean-field one (`bb_fitness_rb`): how far the fit's +- can be trusted
                                                                   (no reference counterpart)
+    hyperfitness_marginals                                        the same for the hyper-fitness theta of the hierarchical models -- a
+                                                                  genotype's fitness, a mutant's across its replicates -- whose
+                                                                  conditional sums over the group's members (`bb_theta_rb`)
 """
 from __future__ import annotations
 
@@ -259,6 +262,17 @@ def _envs_per_rep(arrays, mname: str, R: int):
     return has_env, (envs if (has_env and isinstance(envs, list) and envs and isinstance(envs[0], (list, tuple))) else [envs] * R)
 
 
+def _env_labels(arrays, mname: str, R: int):
+    """(has environments, their labels in the model's numbering: first appearance over the replicates' time points)."""
+    has_env, per_env = _envs_per_rep(arrays, mname, R)
+    labels: List = []
+    if has_env:
+        for env in (x for r in range(R) for x in per_env[r]):
+            if env not in labels:
+                labels.append(env)
+    return has_env, labels
+
+
 def logfreq_ratio_ppc_bands(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
                             quantiles: Sequence[float] = (0.95, 0.675, 0.05), n_samples: int = 1000, n_ppc: int = 10, seed: int = 0,
                             id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
@@ -429,12 +443,7 @@ def fitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model
     R, nb = len(bayes_model.counts), bayes_model.n_bc
     n_units = res["rb_mean"].shape[0]
     E = n_units // max(R * nb, 1)
-    has_env, per_env = _envs_per_rep(arrays, mname, R)
-    labels: List = []
-    if has_env:
-        for env in (x for r in range(R) for x in per_env[r]):            # first appearance over the replicates' time points, as the model indexes them
-            if env not in labels:
-                labels.append(env)
+    has_env, labels = _env_labels(arrays, mname, R)
     u = np.arange(n_units)
     rep, m, env = u // max(E * nb, 1), (u // max(E, 1)) % max(nb, 1), u % max(E, 1)
     out = {
@@ -443,6 +452,58 @@ def fitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model
         "env": [labels[x] for x in env] if has_env else None,
         "n_steps": res["n_steps"],
     }
+    for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"] / res["q_sd"]
+    out["p_pos"], out["p_neg"] = res["p_pos"], res["p_neg"]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
+    return pd.DataFrame(out)
+
+
+def hyperfitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                           n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
+                           id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                           rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                           device: int = 0, chain=None) -> pd.DataFrame:
+    """`fitness_marginals` for the number a hierarchical fit is made for: the hyper-fitness theta, the fitness of a genotype
+    (`genotype_fitness_normal`) or of a mutant across its replicates (`replicate_fitness_normal`,
+    `multienv_replicate_fitness_normal`) -- the `bc_hyperfitness` rows of the fit's frame.  q factorises theta away from the
+    theta_tilde, logtau and logsigma of every member of its group and from their loglambda rows, so its +- is the least to be
+    trusted; given everything else theta's full conditional is exactly Gaussian (the prior and the members' log-frequency-ratio
+    terms), and averaging it over n_samples joint draws of everything else gives the Rao-Blackwellised marginal (`bb_theta_rb`,
+    one device call).  Arguments as for `fitness_marginals`; a model without a theta raises `BarBayError`.
+
+    Returns one line per theta entry, in the order and with the labels of the frame's `bc_hyperfitness` rows: `genotype` (genotype
+    model, else None), `id` and `env` (replicate kinds, else None; `env` None without environments), `n_members` (the group's
+    mutants or replicates), `n_steps` (the time steps of all of them that inform theta; 0: its conditional is the prior), `q_mean`,
+    `q_sd`, `rb_mean`, `rb_sd`, `sd_ratio`, `p_pos`, `p_neg` and one column per probability of `probs`, as `fitness_marginals`."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        n_groups = e.theta_rb_shape()
+        if n_groups == 0:
+            raise BarBayError(f"{mname} has no hyper-fitness: hyperfitness_marginals applies to the hierarchical models (fitness_marginals serves every model)")
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        res = e.theta_rb(n_samples=n_samples, probs=probs, threshold=threshold, seed=seed, draws=draws)
+    R, nb = len(bayes_model.counts), bayes_model.n_bc
+    none = np.full(n_groups, None, dtype=object)
+    if "genotype" in mname:
+        out = {"genotype": np.asarray(list(dict.fromkeys(arrays.genotypes)), dtype=object), "id": none, "env": none}
+    else:
+        E = n_groups // max(nb, 1)
+        has_env, labels = _env_labels(arrays, mname, R)
+        g = np.arange(n_groups)
+        out = {"genotype": none, "id": np.asarray(list(arrays.bc_ids), dtype=object)[g // max(E, 1)],
+               "env": np.asarray(labels, dtype=object)[g % max(E, 1)] if has_env else none}
+    out["n_members"], out["n_steps"] = res["n_members"], res["n_steps"]
     for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
         out[k] = res[k]
     with np.errstate(divide="ignore", invalid="ignore"):

@@ -495,7 +495,8 @@ int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
  * 0 .. 8; probs null with n_quantiles > 0; a prob outside (0, 1) or NaN; a non-finite threshold.  BB_ERR_UNSUPPORTED: n_samples
  * outside its range.  Multi-device and sharded handles: as bb_ppc_bands (the first device works on the gathered posterior; a shard
  * needs bb_set_params first).
- * Out of scope: the conditionals of sbar_t, theta, tau and logsigma; any change to what the fit or an MCMC run report by default. */
+ * The conditional of theta, the hyper-fitness of the hierarchical kinds: bb_theta_rb, below.  Out of scope: the conditionals of
+ * sbar_t, tau and logsigma; any change to what the fit or an MCMC run report by default. */
 #define BB_RB_MAX_SAMPLES 8672
 typedef struct bb_rb_opts {
     int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
@@ -512,6 +513,62 @@ typedef struct bb_rb_out {        /* every pointer may be NULL; [n_units] unless
 } bb_rb_out;
 int bb_fitness_rb_shape(const bb_handle* h, int64_t* n_units);
 int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out);
+
+/* Rao-Blackwellised marginals of the hyper-fitness theta -- the fitness of a genotype (BB_MODEL_GENOTYPE) or of a mutant across its
+ * replicates (BB_MODEL_REPLICATE, BB_MODEL_MULTIENV_REPLICATE): the number a hierarchical fit is made for, and the one whose
+ * mean-field "+-" is least to be trusted, since q factorises theta_g away from the theta_tilde, logtau and logsigma of every member
+ * and from their loglambda rows and sbar_t.  No reference counterpart.  The models are non-centred, s_u = theta_g(u) +
+ * exp(logtau_u) theta_tilde_u: theta_g enters the log-joint through its Gaussian prior (s_bc_prior, Vector or Matrix form) and,
+ * linearly, through the Gaussian log-frequency-ratio terms of its members, so its full conditional given everything else is
+ * N(m, sd) in closed form, and bb_fitness_rb's averaging over joint draws applies as it stands.
+ *
+ * Groups (bb_theta_rb_shape: n_groups = the length of the caller's theta block; 0 for BB_MODEL_FITNESS / BB_MODEL_MULTIENV):
+ *   BB_MODEL_GENOTYPE: g is the genotype; its members are the mutants m with geno_idx[m] == g in ascending caller's m; a member's
+ *          unit (bb_fitness_rb's numbering) is u = m.
+ *   BB_MODEL_REPLICATE / _MULTIENV_REPLICATE: g = e + E m, the theta block's own order; its members are the replicates
+ *          r = 0 .. n_rep - 1, ascending; a member's unit is u = g + E n_bc r.
+ *
+ * Per draw j and member with unit u: n_u, y_{u,j} and w_{u,j} = exp(-2 logsigma_{u,j}) are exactly bb_fitness_rb's (the same gamma,
+ * the same ln Z by the 256-column rule, ascending t, the later time point's environment).  With tau = exp(logtau_{u,j}) and
+ * theta_tilde_{u,j}:
+ *   cP = n_u w;   cN = w (y - n_u (tau theta_tilde))
+ * A member with n_u = 0 is skipped, not multiplied by zero: the log-joint has no term for it, and a non-finite logsigma of such a
+ * member does not reach the group.
+ * Order of the sums: a group's members are cut into chunks of BB_THETA_RB_CHUNK consecutive members; a chunk's (SP, SN) start at 0.0
+ * and take their members' (cP, cN) in order; the group's (SP_j, SN_j) start at 0.0 and take the chunks in chunk order.  No atomics
+ * on doubles.
+ * Conditional, with (a, 1 / b^2) the s_bc_prior element of theta[g] as the handle holds it (the same for every draw):
+ *   P_j = 1 / b^2 + SP_j;   m_j = (a / b^2 + SN_j) / P_j;   sd_j = 1 / sqrt(P_j)
+ * A group with no contributing member (none, or every n_u = 0) has the prior as its conditional: m_j = a, sd_j = 1 / sqrt(1 / b^2)
+ * (bb_fitness_rb's n_u = 0 rule).  theta_j is the draw of theta[g] itself.
+ * The identity all this rests on, at any point z:  P (m - theta_g) = dlogp/dtheta_g.  BB_FLAG_RAGGED_METHOD alters the neutral term
+ * only, so flagged handles are served alike.
+ *
+ * Outputs per group (every pointer may be NULL):
+ *   n_members  the members of the group;   n_steps  the sum of n_u over them
+ *   q_mean, q_sd     mean and sd of theta_j over the draws, as bb_fitness_rb's of s_j
+ *   rb_mean, rb_sd, p_pos, p_neg, quantiles    from (m_j, sd_j) by bb_fitness_rb's formulas word for word, the 64-step bisection
+ *              and its bracket included; a group with a non-finite m_j or sd_j reports NaN quantiles.
+ * Non-finite parameters propagate by IEEE rules into the groups that use them; they disturb no other group and are not an error.
+ *
+ * The options are bb_fitness_rb's, with the same meaning and limits (draws, seed and keying included; BB_RB_MAX_SAMPLES because a
+ * group's (m_j, sd_j) live in LDS as a unit's do).  A group's results are a function of the handle's (mu, sigma) (or the supplied
+ * draws), the s_bc prior, geno_idx, n_samples, seed, threshold and probs: bit-identical whatever the grid, the launch mode, the
+ * handle's internal latent order (the library regroups a genotype model's mutants), the device count or the calls made before.
+ * The handle's mu, omega, optimiser state, step counter and RNG position are untouched, bitwise.  BB_ERR_INVALID /
+ * BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb; BB_ERR_UNSUPPORTED, the message naming the model kind, for
+ * BB_MODEL_FITNESS / BB_MODEL_MULTIENV.  The chunk partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB
+ * (the groups are worked in slabs; a single group is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
+ * Out of scope: the conditionals of sbar_t, tau and logsigma. */
+#define BB_THETA_RB_CHUNK 64
+typedef struct bb_theta_rb_out {  /* every pointer may be NULL; [n_groups] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
+    double* quantiles;            /* [n_groups][n_quantiles]                           */
+    int32_t* n_members;           /* members of the group                              */
+    int32_t* n_steps;             /* sum of n_u over the members                       */
+} bb_theta_rb_out;
+int bb_theta_rb_shape(const bb_handle* h, int64_t* n_groups);
+int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out);
 
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array
