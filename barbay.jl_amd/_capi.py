@@ -23,6 +23,7 @@ BB_LOGP_MAX_BATCH = 64
 BB_CHAIN_MAX_K = 16384
 BB_CHAIN_MAX_Q = 8
 BB_CHAIN_LAG_BATCH = 32
+BB_TRACE_MAX_SNAPSHOTS = 16384
 BB_SCORE_MAX_SAMPLES = 16384
 BB_RB_MAX_SAMPLES = 8672
 BB_RB_MAX_Q = 8
@@ -39,6 +40,7 @@ EXPORTS = [
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb",
+    "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -147,6 +149,31 @@ class bb_chain_out(C.Structure):
     ]
 
 
+class bb_trace_opts(C.Structure):
+    _fields_ = [("every", C.c_int32), ("capacity", C.c_int32)]
+
+
+class bb_trace_sum_opts(C.Structure):
+    _fields_ = [
+        ("first", C.c_int64), ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("max_lag", C.c_int32), ("reserved0", C.c_int32),
+        ("slab_cols", C.c_int64), ("rhat_max", C.c_double),
+    ]
+
+
+TRACE_COLS = ("mean", "sd", "mcse", "ess", "rhat")
+TRACE_BLOCK_COUNTS = ("n_cols", "n_nonfinite", "n_const", "n_above")
+TRACE_BLOCK_VALUES = ("max_rhat", "min_ess", "max_mcse_rel")
+
+
+class bb_trace_block(C.Structure):
+    _fields_ = ([("name", C.c_char * 24), ("part", C.c_int32), ("reserved0", C.c_int32)] + [(k, C.c_int64) for k in TRACE_BLOCK_COUNTS]
+                + [(k, C.c_double) for k in TRACE_BLOCK_VALUES])
+
+
+class bb_trace_sum_out(C.Structure):
+    _fields_ = [(k, _dp) for k in TRACE_COLS] + [("n_lags", C.POINTER(C.c_int32)), ("blocks", C.POINTER(bb_trace_block))]
+
+
 class BarBayHipError(RuntimeError):
     """Raised for any non-zero status of the C ABI (the reference throws ErrorException)."""
 
@@ -217,6 +244,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.bb_theta_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_theta_rb_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
+    if hasattr(lib, "bb_trace_begin"):
+        lib.bb_trace_begin.argtypes = [vp, C.POINTER(bb_trace_opts)]
+        lib.bb_trace_end.argtypes = [vp]
+        lib.bb_trace_count.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.bb_trace_get.argtypes = [vp, C.c_int64, C.c_int64, _dp, _dp]
+        lib.bb_trace_summary.argtypes = [vp, C.POINTER(bb_trace_sum_opts), C.POINTER(bb_trace_sum_out)]
     return lib
 
 
@@ -664,6 +697,62 @@ class Engine:
         out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
         out.n_lags = res["n_lags"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_chain_summary(self._h, C.byref(o), D, _ptr(x), C.byref(out)))
+        return res
+
+    # ---- the iterate trace (include/barbay_hip.h, bb_trace_*) ----
+    def trace_begin(self, every: int, capacity: int):
+        """Keep (mu, omega) after every `every` steps of `run` in a device ring of `capacity` snapshots (`bb_trace_begin`)."""
+        o = bb_trace_opts()
+        o.every, o.capacity = int(every), int(capacity)
+        self._check(self._lib.bb_trace_begin(self._h, C.byref(o)))
+
+    def trace_end(self):
+        self._check(self._lib.bb_trace_end(self._h))
+
+    def trace_count(self) -> Tuple[int, int]:
+        """(taken, first_live): snapshots recorded since `trace_begin` or the last reset, and the oldest one the ring still holds."""
+        taken, live = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.bb_trace_count(self._h, C.byref(taken), C.byref(live)))
+        return int(taken.value), int(live.value)
+
+    def trace_get(self, first: int, n: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Snapshots first .. first + n - 1 as (mu[n, D], omega[n, D]) in the caller's latent order (`bb_trace_get`)."""
+        mu, om = np.empty((int(n), self.D)), np.empty((int(n), self.D))
+        self._check(self._lib.bb_trace_get(self._h, int(first), int(n), _ptr(mu), _ptr(om)))
+        return mu, om
+
+    def trace_summary(self, first: int, n_chains: int, n_draws: int, max_lag: int = 0, rhat_max: float = 1.1, columns: bool = False,
+                      slab_cols: int = 0, blocks: bool = True, only: Optional[Sequence[str]] = None) -> Dict[str, object]:
+        """Split-R-hat, ESS and MCSE of the window of n_chains * n_draws snapshots from `first`, computed on the ring where it lies
+        (`bb_trace_summary`).  Returns {"blocks": DataFrame}: one row per (layout block, part) -- name, part ("mu" / "omega"), n_cols,
+        n_nonfinite, n_const, n_above, max_rhat, min_ess, max_mcse_rel.  With `columns` also mean, sd, mcse, ess, rhat and n_lags
+        (int32), each [2 D]: mu of the caller's latent i at i, its omega at D + i; `only` names the ones wanted (the others are not
+        downloaded).  `blocks=False` leaves the verdict out."""
+        o = bb_trace_sum_opts()
+        o.first, o.n_chains, o.n_draws, o.max_lag, o.slab_cols, o.rhat_max = int(first), int(n_chains), int(n_draws), int(max_lag), int(slab_cols), float(rhat_max)
+        out = bb_trace_sum_out()
+        res: Dict[str, object] = {}
+        if columns:
+            for k in TRACE_COLS + ("n_lags",):
+                if only is not None and k not in only:
+                    continue
+                if k == "n_lags":
+                    res[k] = np.empty(2 * self.D, dtype=np.int32)
+                    out.n_lags = res[k].ctypes.data_as(C.POINTER(C.c_int32))
+                else:
+                    res[k] = np.empty(2 * self.D)
+                    setattr(out, k, _ptr(res[k]))
+        nb = len(self.layout())
+        vb = (bb_trace_block * (2 * nb))()
+        if blocks:
+            out.blocks = vb
+        self._check(self._lib.bb_trace_summary(self._h, C.byref(o), C.byref(out)))
+        if blocks:
+            import pandas as pd
+            rows = {"name": [vb[i].name.decode() for i in range(2 * nb)], "part": ["omega" if vb[i].part else "mu" for i in range(2 * nb)]}
+            for k in TRACE_BLOCK_COUNTS + TRACE_BLOCK_VALUES:
+                rows[k] = [getattr(vb[i], k) for i in range(2 * nb)]
+            res["blocks"] = pd.DataFrame(rows)
         return res
 
     # ---- cross-GPU leg of the resident launch (include/barbay_hip.h, bb_p2p_*) ----

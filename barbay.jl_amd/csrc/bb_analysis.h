@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
-// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb (bb_rb.h) and bb_chain_summary
-// (bb_chain.h).  None of them touches the step loop.
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb (bb_rb.h), bb_chain_summary
+// (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -811,6 +811,79 @@ extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_
 static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRIDE && BB_CHAIN_LAG_BATCH == BB_CHAIN_LAGS &&
               2 * BB_CHAIN_MAX_Q <= BB_PPC_MAX_TGT, "bb_chain_summary limits");
 
+// What bb_chain_summary and bb_trace_summary share.  chain_plan: the options that shape the statistics into C, the slab width, and the
+// device buffer -- the slab as filled, its transpose, the slab's results (they lie together and come back in one copy: stat | quant |
+// nlags), then whatever `extra` names.  chain_slabs: the loop over slabs of columns, fill(c0) putting columns c0 .. c0 + C.sc into the
+// slab and take(c0) collecting their results; lap(0 .. 4) brackets the four phases of every slab.
+struct ChainSlabs {
+    double* slab = nullptr;        // [K][ld]
+    long long ld = 0;
+    size_t n_stat = 0, n_quant = 0, n_lags = 0, nres = 0;      // doubles of the slab's results
+};
+template <class X>
+static int chain_plan(bb_handle* dh, int W, int N, int max_lag, int nq, const double* probs, long long slab_cols, long long n_cols,
+                      ChainArgs& C, ChainSlabs& L, X&& extra) {
+    const long long K = (long long)W * N;
+    memset(&C, 0, sizeof C);
+    PpcArgs& P = C.P;
+    P.K = (int)K;
+    C.W = W;
+    C.N = N;
+    C.lag_max = max_lag ? std::min(max_lag, N - 1) : N - 1;
+    C.ess_cap = (double)K * log10((double)K);
+    // the select takes the order statistics and forms no bands (n_q = 0): one pair per probability
+    C.nq = nq;
+    quantile_plan(K, probs, nq, P);
+    // slab: the caller's column count, or what BB_CHAIN_SLAB_BYTES of slab rows hold (whole transpose tiles)
+    long long ld = slab_cols;
+    if (!ld) {
+        ld = std::max<long long>(1, (long long)BB_CHAIN_SLAB_BYTES / (8 * K));
+        if (ld >= BB_CHAIN_TILE) ld -= ld % BB_CHAIN_TILE;
+    }
+    ld = std::min<long long>(ld, n_cols);
+    L.ld = ld;
+    L.n_stat = 5 * (size_t)ld;
+    L.n_quant = (size_t)BB_CHAIN_QSTRIDE * ld;
+    L.n_lags = ((size_t)ld + 1) / 2;
+    L.nres = L.n_stat + L.n_quant + L.n_lags;
+    int rc = carve(dh->buf[BUF_CHAIN], [&](Carve& c) {
+        c(L.slab, (size_t)K * ld);                     // [K][ld] as uploaded / gathered
+        c(C.colT, (size_t)K * ld);                     // [ld][K]
+        c(C.stat, L.n_stat);                           // mean, sd, mcse, ess, rhat [5][ld]
+        c(C.quant, L.n_quant);                         // [ld][BB_CHAIN_QSTRIDE]
+        c(C.nlags, L.n_lags);                          // [ld] ints
+        extra(c);
+    });
+    if (rc) return rc;
+    C.slab = L.slab;
+    C.ld = ld;
+    return BB_OK;
+}
+template <class F, class T, class Lap>
+static int chain_slabs(bb_handle* dh, ChainArgs& C, long long n_cols, F&& fill, T&& take, Lap&& lap) {
+    const long long K = C.P.K, ld = C.ld;
+    int rc;
+    for (long long c0 = 0; c0 < n_cols; c0 += ld) {
+        C.sc = std::min<long long>(ld, n_cols - c0);
+        lap(0);
+        if ((rc = fill(c0))) return rc;
+        lap(1);
+        const long long tiles = ((C.sc + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE) * ((K + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE);
+        if ((rc = launch(dh->stream, k_chain_transpose, (int)std::min<long long>(tiles, 1 << 16), BB_CHAIN_TNT, BB_CHAIN_TILE * (BB_CHAIN_TILE + 1), C))) return rc;
+        lap(2);
+        if ((rc = launch(dh->stream, k_chain_stats, (int)std::min<long long>(C.sc, 1 << 20), BB_CHAIN_NT, (size_t)bb_chain_lds_doubles(C.P.K), C))) return rc;
+        lap(3);
+        if ((rc = take(c0))) return rc;
+        lap(4);
+    }
+    return BB_OK;
+}
+// the phase clock of the BB_*_TIMES diagnostics: lap(i) drains the stream and adds the time since the lap before to ms[i - 1]
+#define BB_LAP_CLOCK(stream, n)                                                                                                    \
+    timespec ct[(n) + 1];                                                                                                          \
+    double cms[(n)] = {0};                                                                                                         \
+    auto lap = [&](int i) { (void)dsync(stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; }
+
 extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols, const double* chain, const bb_chain_out* out) {
     if (!h || !o || !chain || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     if (n_cols < 1) return bb_fail(BB_ERR_INVALID, "n_cols must be >= 1");
@@ -825,65 +898,227 @@ extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_
     bb_handle* dh = sampling_handle(h);      // (nothing of the model is read)
     BB_ENTER(dh);
     ChainArgs C;
-    memset(&C, 0, sizeof C);
-    PpcArgs& P = C.P;
-    P.K = (int)K;
-    C.W = o->n_chains;
-    C.N = o->n_draws;
-    C.lag_max = o->max_lag ? std::min(o->max_lag, o->n_draws - 1) : o->n_draws - 1;
-    C.ess_cap = (double)K * log10((double)K);
-    // the select takes the order statistics and forms no bands (n_q = 0): one pair per probability
-    C.nq = nq;
-    quantile_plan(K, o->probs, nq, P);
-    // slab: the caller's column count, or what BB_CHAIN_SLAB_BYTES of uploaded rows hold (whole transpose tiles)
-    long long ld = o->slab_cols;
-    if (!ld) {
-        ld = std::max<long long>(1, (long long)BB_CHAIN_SLAB_BYTES / (8 * K));
-        if (ld >= BB_CHAIN_TILE) ld -= ld % BB_CHAIN_TILE;
-    }
-    ld = std::min<long long>(ld, n_cols);
-    // the slab's results lie together and come back in one copy: stat | quant | nlags
-    const size_t n_stat = 5 * (size_t)ld, n_quant = (size_t)BB_CHAIN_QSTRIDE * ld, n_lags = ((size_t)ld + 1) / 2, nres = n_stat + n_quant + n_lags;
-    double* slab = nullptr;
-    int rc = carve(dh->buf[BUF_CHAIN], [&](Carve& c) {
-        c(slab, (size_t)K * ld);                       // [K][ld] as uploaded
-        c(C.colT, (size_t)K * ld);                     // [ld][K]
-        c(C.stat, n_stat);                             // mean, sd, mcse, ess, rhat [5][ld]
-        c(C.quant, n_quant);                           // [ld][BB_CHAIN_QSTRIDE]
-        c(C.nlags, n_lags);                            // [ld] ints
-    });
+    ChainSlabs L;
+    int rc = chain_plan(dh, o->n_chains, o->n_draws, o->max_lag, nq, o->probs, o->slab_cols, n_cols, C, L, [](Carve&) {});
     if (rc) return rc;
-    C.slab = slab;
-    C.ld = ld;
-    std::vector<double> res(nres);
+    const long long ld = L.ld;
+    std::vector<double> res(L.nres);
     double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
 #ifdef BB_CHAIN_TIMES          // diagnostics (tools/chain_summary_rate.py): the call's phases, each drained before the next starts
-    timespec ct[5];
-    double cms[4] = {0, 0, 0, 0};
-    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+    BB_LAP_CLOCK(dh->stream, 4);
 #else
     auto lap = [](int) {};
 #endif
-    for (long long c0 = 0; c0 < n_cols; c0 += ld) {
-        C.sc = std::min<long long>(ld, n_cols - c0);
-        lap(0);
-        if ((rc = h2d_2d(slab, (size_t)ld * 8, chain + c0, (size_t)n_cols * 8, (size_t)C.sc * 8, (size_t)K, dh->stream))) return rc;
-        lap(1);
-        const long long tiles = ((C.sc + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE) * ((K + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE);
-        if ((rc = launch(dh->stream, k_chain_transpose, (int)std::min<long long>(tiles, 1 << 16), BB_CHAIN_TNT, BB_CHAIN_TILE * (BB_CHAIN_TILE + 1), C))) return rc;
-        lap(2);
-        if ((rc = launch(dh->stream, k_chain_stats, (int)std::min<long long>(C.sc, 1 << 20), BB_CHAIN_NT, (size_t)bb_chain_lds_doubles(P.K), C))) return rc;
-        lap(3);
-        if ((rc = d2h(res.data(), C.stat, nres * 8, dh->stream))) return rc;
-        lap(4);
-        for (int s = 0; s < 5; ++s)
-            if (outs[s]) memcpy(outs[s] + c0, res.data() + (size_t)s * ld, (size_t)C.sc * 8);
-        if (out->quantiles && nq)
-            for (long long c = 0; c < C.sc; ++c) memcpy(out->quantiles + (size_t)(c0 + c) * nq, res.data() + n_stat + c * BB_CHAIN_QSTRIDE, (size_t)nq * 8);
-        if (out->n_lags) memcpy(out->n_lags + c0, res.data() + n_stat + n_quant, (size_t)C.sc * 4);
-    }
+    rc = chain_slabs(dh, C, n_cols,
+        [&](long long c0) { return h2d_2d(L.slab, (size_t)ld * 8, chain + c0, (size_t)n_cols * 8, (size_t)C.sc * 8, (size_t)K, dh->stream); },
+        [&](long long c0) {
+            if (int r = d2h(res.data(), C.stat, L.nres * 8, dh->stream)) return r;
+            for (int s = 0; s < 5; ++s)
+                if (outs[s]) memcpy(outs[s] + c0, res.data() + (size_t)s * ld, (size_t)C.sc * 8);
+            if (out->quantiles && nq)
+                for (long long c = 0; c < C.sc; ++c) memcpy(out->quantiles + (size_t)(c0 + c) * nq, res.data() + L.n_stat + c * BB_CHAIN_QSTRIDE, (size_t)nq * 8);
+            if (out->n_lags) memcpy(out->n_lags + c0, res.data() + L.n_stat + L.n_quant, (size_t)C.sc * 4);
+            return 0;
+        }, lap);
+    if (rc) return rc;
 #ifdef BB_CHAIN_TIMES
     fprintf(stderr, "[bb_chain_summary %lld x %lld, slabs of %lld] upload %.3f ms, transpose %.3f ms, stats %.3f ms, download %.3f ms\n", K, (long long)n_cols, ld, cms[0], cms[1], cms[2], cms[3]);
 #endif
     return BB_OK;
+}
+
+// ---- the iterate trace (bb_trace.h): ring, snapshots, summary ------------------------------------------------------------------------
+static_assert(BB_TRACE_MAX_SNAPSHOTS == BB_CHAIN_MAX_K, "a window of the whole ring is one pooled column");
+
+extern "C" int bb_trace_begin(bb_handle* h, const bb_trace_opts* o) {
+    if (!h || !o) return bb_fail(BB_ERR_INVALID, "null argument");
+    BB_GROUP_UNSUPPORTED(h, "bb_trace_begin");
+    if (h->o.world_size > 1) return bb_fail(BB_ERR_UNSUPPORTED, "bb_trace_begin is not available on a sharded handle (world_size > 1)");
+    if (h->trace_ring) return bb_fail(BB_ERR_INVALID, "an iterate trace is on already (bb_trace_end first)");
+    if (o->every < 1) return bb_fail(BB_ERR_INVALID, "every must be >= 1");
+    if (o->capacity < 8 || o->capacity > BB_TRACE_MAX_SNAPSHOTS) return bb_fail(BB_ERR_INVALID, "capacity = %d is outside 8 .. %d", (int)o->capacity, BB_TRACE_MAX_SNAPSHOTS);
+    BB_ENTER(h);
+    void* p = nullptr;
+    const size_t bytes = (size_t)o->capacity * 2 * (size_t)h->M.D * 8;
+    if (dmalloc(&p, bytes)) {
+        const std::string why(g_err);
+        return bb_fail(BB_ERR_DEVICE, "bb_trace_begin: no room for a ring of %d snapshots (%zu bytes): %s", (int)o->capacity, bytes, why.c_str());
+    }
+    h->trace_ring = (double*)p;
+    h->trace_every = o->every;
+    h->trace_cap = o->capacity;
+    trace_reset(h);
+    return BB_OK;
+}
+
+extern "C" int bb_trace_end(bb_handle* h) {
+    if (!h) return bb_fail(BB_ERR_INVALID, "null handle");
+    if (!h->trace_ring) return BB_OK;
+    BB_ENTER(h);
+    const int rc = dsync(h->stream);
+    dfree(h->trace_ring);
+    h->trace_ring = nullptr;
+    h->trace_every = h->trace_cap = 0;
+    trace_reset(h);
+    return rc;
+}
+
+static long long trace_first_live(const bb_handle* h) { return std::max<long long>(0, h->trace_taken - h->trace_cap); }
+// snapshots first .. first + n - 1 must all be in the ring
+static int trace_live(const bb_handle* h, const char* what, long long first, long long n) {
+    if (!h->trace_ring) return bb_fail(BB_ERR_INVALID, "%s: no iterate trace is on (bb_trace_begin)", what);
+    if (first < trace_first_live(h) || n < 0 || first + n > h->trace_taken)
+        return bb_fail(BB_ERR_INVALID, "%s: snapshots %lld .. %lld are not all live: the ring holds %lld .. %lld (%lld taken, capacity %d)", what, first,
+                       first + n - 1, trace_first_live(h), h->trace_taken - 1, h->trace_taken, h->trace_cap);
+    return BB_OK;
+}
+
+extern "C" int bb_trace_count(bb_handle* h, int64_t* taken, int64_t* first_live) {
+    if (!h) return bb_fail(BB_ERR_INVALID, "null handle");
+    if (!h->trace_ring) return bb_fail(BB_ERR_INVALID, "bb_trace_count: no iterate trace is on (bb_trace_begin)");
+    if (taken) *taken = h->trace_taken;
+    if (first_live) *first_live = trace_first_live(h);
+    return BB_OK;
+}
+
+extern "C" int bb_trace_get(bb_handle* h, int64_t first, int64_t n, double* mu, double* omega) {
+    if (!h) return bb_fail(BB_ERR_INVALID, "null handle");
+    if (int rc = trace_live(h, "bb_trace_get", first, n)) return rc;
+    BB_ENTER(h);
+    const size_t D = (size_t)h->M.D;
+    std::vector<double> row(2 * D);
+    int rc = dsync(h->stream);
+    for (int64_t k = 0; k < n && !rc; ++k) {
+        const size_t slot = (size_t)((first + k) % h->trace_cap);
+        if ((rc = d2h(row.data(), h->trace_ring + slot * 2 * D, 2 * D * 8, h->stream))) break;
+        double* dst[2] = {mu ? mu + (size_t)k * D : nullptr, omega ? omega + (size_t)k * D : nullptr};
+        for (int part = 0; part < 2; ++part) {
+            if (!dst[part]) continue;
+            if (h->cidx.empty()) memcpy(dst[part], row.data() + part * D, D * 8);
+            else perm_scatter(h, row.data() + part * D, dst[part]);
+        }
+    }
+    return rc;
+}
+
+// internal range of layout block b: the handle's order keeps every block whole, so it is the internal block whose first latent the
+// caller's range holds
+static void trace_block_range(const bb_handle* h, size_t b, long long* lo, long long* hi) {
+    const bb_block_range& r = h->blocks[b];
+    *lo = r.lo;
+    *hi = r.hi;
+    if (h->cidx.empty()) return;
+    for (int k = 0; k < BK_COUNT; ++k) {
+        const long long klo = h->M.blk_lo[k], khi = h->M.blk_hi[k];
+        if (khi > klo && h->cidx[(size_t)klo] >= r.lo && h->cidx[(size_t)klo] < r.hi) { *lo = klo; *hi = khi; return; }
+    }
+}
+
+extern "C" int bb_trace_summary(bb_handle* h, const bb_trace_sum_opts* o, const bb_trace_sum_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (!h->trace_ring) return bb_fail(BB_ERR_INVALID, "bb_trace_summary: no iterate trace is on (bb_trace_begin)");
+    if (o->n_chains < 1 || o->n_draws < 4) return bb_fail(BB_ERR_INVALID, "n_chains must be >= 1 and n_draws >= 4");
+    if (o->max_lag < 0 || o->slab_cols < 0) return bb_fail(BB_ERR_INVALID, "max_lag and slab_cols must be >= 0");
+    if (!(std::isfinite(o->rhat_max) && o->rhat_max >= 1.0)) return bb_fail(BB_ERR_INVALID, "rhat_max must be finite and >= 1");
+    const long long K = (long long)o->n_chains * o->n_draws;
+    if (K > BB_CHAIN_MAX_K) return bb_fail(BB_ERR_UNSUPPORTED, "n_chains * n_draws = %lld must be <= %d", K, BB_CHAIN_MAX_K);
+    if (int rc = trace_live(h, "bb_trace_summary", o->first, K)) return rc;
+    const size_t nblk = h->blocks.size();
+    if (nblk > BB_TRACE_MAX_BLOCKS) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    BB_ENTER(h);
+    const size_t D = (size_t)h->M.D, D2 = 2 * D;
+    ChainArgs C;
+    ChainSlabs L;
+    TraceVerdictArgs V;
+    memset(&V, 0, sizeof V);
+    double* all = nullptr;         // the columns' statistics where the verdict reads them and the downloads start
+    int* all_lags = nullptr;
+    int rc = chain_plan(h, o->n_chains, o->n_draws, o->max_lag, 0, nullptr, o->slab_cols, (long long)D2, C, L, [&](Carve& c) {
+        c(all, 5 * D2);                                // mean, sd, mcse, ess, rhat [5][2 D], the handle's internal order
+        c(all_lags, (D2 + 1) / 2);                     // [2 D] ints
+        c(V.val, 6 * nblk);                            // [2 nblk][3]
+        c(V.cnt, 6 * nblk);                            // [2 nblk][3] 64-bit counts
+    });
+    if (rc) return rc;
+    TraceArgs T;
+    memset(&T, 0, sizeof T);
+    T.ring = h->trace_ring;
+    T.D = (long long)D;
+    T.D2 = (long long)D2;
+    T.cap = h->trace_cap;
+    T.slab = L.slab;
+    T.ld = L.ld;
+    T.first = o->first;
+    T.K = (int)K;
+#ifdef BB_TRACE_TIMES          // diagnostics (tools/trace_cost.py): the call's phases, each drained before the next starts
+    BB_LAP_CLOCK(h->stream, 6);
+#else
+    auto lap = [](int) {};
+#endif
+    rc = chain_slabs(h, C, (long long)D2,
+        [&](long long c0) {
+            T.c0 = c0;
+            T.sc = C.sc;
+            const long long runs = (long long)K * ((C.sc + BB_TRACE_NT - 1) / BB_TRACE_NT);
+            return launch(h->stream, k_trace_gather, (int)std::min<long long>(runs, 1 << 16), BB_TRACE_NT, 0, T);
+        },
+        [&](long long c0) {      // the slab's results to their columns' places (they stay on the device)
+            for (size_t s = 0; s < 5; ++s)
+                if (int r = d2d(all + s * D2 + c0, C.stat + s * (size_t)L.ld, (size_t)C.sc * 8, h->stream)) return r;
+            return d2d(all_lags + c0, C.nlags, (size_t)C.sc * 4, h->stream);
+        }, lap);
+    if (rc) return rc;
+    if (out->blocks) {
+        V.stat = all;
+        V.D = (long long)D;
+        V.D2 = (long long)D2;
+        V.nblk = (int)nblk;
+        V.rhat_max = o->rhat_max;
+        for (size_t b = 0; b < nblk; ++b) trace_block_range(h, b, &V.lo[b], &V.hi[b]);
+        if ((rc = launch(h->stream, k_trace_verdict, 2 * (int)nblk, BB_TRACE_VNT, (size_t)bb_trace_verdict_lds_doubles(), V))) return rc;
+    }
+    lap(5);
+    // downloads: only what was asked for, the handle's order -> the caller's per half
+    double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
+    std::vector<double> tmp;
+    for (size_t s = 0; s < 5; ++s) {
+        if (!outs[s]) continue;
+        if (h->cidx.empty()) { if ((rc = d2h(outs[s], all + s * D2, D2 * 8, h->stream))) return rc; continue; }
+        tmp.resize(D2);
+        if ((rc = d2h(tmp.data(), all + s * D2, D2 * 8, h->stream))) return rc;
+        perm_scatter(h, tmp.data(), outs[s]);
+        perm_scatter(h, tmp.data() + D, outs[s] + D);
+    }
+    if (out->n_lags) {
+        if (h->cidx.empty()) { if ((rc = d2h(out->n_lags, all_lags, D2 * 4, h->stream))) return rc; }
+        else {
+            std::vector<int> li(D2);
+            if ((rc = d2h(li.data(), all_lags, D2 * 4, h->stream))) return rc;
+            for (size_t i = 0; i < D; ++i) { out->n_lags[(size_t)h->cidx[i]] = li[i]; out->n_lags[D + (size_t)h->cidx[i]] = li[D + i]; }
+        }
+    }
+    if (out->blocks) {
+        std::vector<double> val(6 * nblk);
+        std::vector<long long> cnt(6 * nblk);
+        if ((rc = d2h(val.data(), V.val, val.size() * 8, h->stream)) || (rc = d2h(cnt.data(), V.cnt, cnt.size() * 8, h->stream))) return rc;
+        for (size_t v = 0; v < 2 * nblk; ++v) {
+            bb_trace_block& B = out->blocks[v];
+            memset(&B, 0, sizeof B);
+            memcpy(B.name, h->blocks[v % nblk].name, sizeof B.name);
+            B.part = (int32_t)(v / nblk);
+            B.n_cols = h->blocks[v % nblk].hi - h->blocks[v % nblk].lo;
+            B.n_nonfinite = cnt[3 * v];
+            B.n_const = cnt[3 * v + 1];
+            B.n_above = cnt[3 * v + 2];
+            B.max_rhat = val[3 * v];
+            B.min_ess = val[3 * v + 1];
+            B.max_mcse_rel = val[3 * v + 2];
+        }
+    }
+    rc = dsync(h->stream);
+    lap(6);
+#ifdef BB_TRACE_TIMES
+    fprintf(stderr, "[bb_trace_summary %lld x %zu, slabs of %lld] gather %.3f ms, transpose %.3f ms, stats %.3f ms, collect %.3f ms, verdict %.3f ms, download %.3f ms\n", K, D2, L.ld, cms[0], cms[1], cms[2], cms[3], cms[4], cms[5]);
+#endif
+    return rc;
 }

@@ -433,6 +433,18 @@ BB_KERNEL(BB_CHAIN_NT, k_chain_stats, ChainArgs C) {
     BB_CTX;
     bb_block_chain_stats(cx, C, BB_GRID);
 }
+BB_KERNEL(BB_TRACE_NT, k_trace_snapshot, TraceArgs T) {
+    BB_CTX;
+    bb_block_trace_snapshot(cx, T, BB_GRID);
+}
+BB_KERNEL(BB_TRACE_NT, k_trace_gather, TraceArgs T) {
+    BB_CTX;
+    bb_block_trace_gather(cx, T, BB_GRID);
+}
+BB_KERNEL(BB_TRACE_VNT, k_trace_verdict, TraceVerdictArgs V) {
+    BB_CTX;
+    bb_block_trace_verdict(cx, V);
+}
 // bb_logdensity_grad_batch (bb_logp.h): grid = tile + n_tiles * point
 template <int KIND>
 BB_KERNEL(1024, k_logp_moments, const DevModel* __restrict__ Mp, LogpArgs B, RunArgs A, int NB) {

@@ -21,6 +21,7 @@
 #include "bb_score.h"
 #include "bb_rb.h"
 #include "bb_chain.h"
+#include "bb_trace.h"
 #include "bb_logp.h"
 #include "bb_mathprobe.h"
 
@@ -176,6 +177,11 @@ struct bb_handle {
     double* bak_om = nullptr;
     DevBuf buf[BUF_COUNT];             // the calls' own device buffers (BUF_*)
     std::vector<double> logp_host;     // bb_logdensity_grad_batch: host staging (rows padded to an even length, the handle's latent order)
+    // the iterate trace (bb_trace_*, bb_trace.h): on while trace_ring is set
+    double* trace_ring = nullptr;      // [trace_cap][2 D], the handle's own allocation (bb_trace_end frees it)
+    int trace_every = 0, trace_cap = 0;
+    long long trace_t = 0;             // steps bb_run has taken since begin / the last reset
+    long long trace_taken = 0;         // snapshots recorded since then
     bbStream stream{};
     bool opened = false;               // the stream is open (bb_create sets it: until then the handle holds nothing on a device)
     double last_run_ms = 0, avg_sample_ms = 0, avg_update_ms = 0;
@@ -586,6 +592,7 @@ extern "C" void bb_destroy(bb_handle* h) {
     hostmap_free(h->hstatus);
     for (void* p : h->owned) dfree(p);
     for (DevBuf& b : h->buf) if (b.p) dfree(b.p);
+    if (h->trace_ring) dfree(h->trace_ring);
     stream_close(h->stream);
     delete h;
 }
@@ -736,6 +743,7 @@ extern "C" int bb_init_meanfield(bb_handle* h) {
     if (!h->shards.empty()) { int rc = 0; for (bb_handle* sh : h->shards) if (!rc) rc = bb_init_meanfield(sh); h->step = 0; return rc; }
     BB_ENTER(h);
     h->theta_stale = false;
+    trace_reset(h);
     const int nb = (int)std::min<long long>(((h->M.D + 1) / 2 + 255) / 256, 1024);
     const int rc = launch(h->stream, k_init, nb, 256, 0, h->M, h->S, h->o.seed);
     return rc ? rc : reset_optimizer(h);
@@ -753,6 +761,7 @@ extern "C" int bb_set_params(bb_handle* h, const double* mu, const double* omega
     BB_ENTER(h);
     int rc;
     h->theta_stale = false;
+    trace_reset(h);
     if ((rc = h2d(h->S.mu, mu, (size_t)h->M.D * 8, h->stream))) return rc;
     if ((rc = h2d(h->S.om, omega, (size_t)h->M.D * 8, h->stream))) return rc;
     return reset_optimizer(h);

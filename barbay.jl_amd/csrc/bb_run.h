@@ -54,20 +54,26 @@ static int run_graphs(bb_handle* h, int64_t n_steps, int64_t& done) {
 static int run_graphs(bb_handle*, int64_t, int64_t&) { return 0; }
 #endif
 
-// bb_run in two halves (a multi-device handle enqueues on all its shards before it waits for any)
-static int run_enqueue(bb_handle* h, int64_t n_steps) {
+// bb_run in two halves (a multi-device handle enqueues on all its shards before it waits for any).  The first half in its parts, for
+// bb_run under a trace (below): run_open -- what must hold, and what is reset, before a call's first launch -- and run_steps, the
+// launches of n_steps steps as one bb_run call makes them.
+static int run_open(bb_handle* h) {
     if (h->sample != 0) return bb_fail(BB_ERR_INVALID, "a split-phase step is in flight");
     int rc = 0;
-    int64_t done = 0;
     if (h->plan.impl == IMPL_TWO_KERNEL && (rc = ensure_scratch(h))) return rc;
     if (h->hstatus) h->hstatus[1] = 0;          // divergence flag of THIS run (nothing of this handle is in flight here)
     if ((rc = timer_start(h->be, h->stream))) return rc;
     h->launches_last_run = 0;
     h->graph_launches = 0;
+    return 0;
+}
+static int run_steps(bb_handle* h, int64_t n_steps) {
+    int rc = 0;
+    int64_t done = 0;
     if (h->plan.impl != IMPL_TWO_KERNEL && n_steps > 0) {
         if ((rc = launch_persistent(h, n_steps))) return rc;
         done = n_steps;
-        h->launches_last_run = (int)((n_steps + 4095) / 4096);
+        h->launches_last_run += (int)((n_steps + 4095) / 4096);
         if (theta_partial(h)) h->theta_stale = true;         // only the owner's theta_g moved (bb_run / group_run gather it afterwards)
     } else if (h->theta_stale && n_steps > 0 && (rc = theta_sync_comm(h))) return rc;
     if ((rc = run_graphs(h, n_steps, done))) return rc;
@@ -75,11 +81,69 @@ static int run_enqueue(bb_handle* h, int64_t n_steps) {
         if ((rc = enqueue_step(h, h->step))) return rc;
         h->step++;
     }
-    return timer_stop(h->be, h->stream);
+    return 0;
+}
+static int run_enqueue(bb_handle* h, int64_t n_steps) {
+    int rc = run_open(h);
+    if (!rc) rc = run_steps(h, n_steps);
+    return rc ? rc : timer_stop(h->be, h->stream);
 }
 static int run_finish(bb_handle* h) {
     int rc = timer_wait(h->be, h->stream, &h->last_run_ms);
     return rc ? rc : check_persistent(h);
+}
+
+// ---- bb_run under an iterate trace (bb_trace.h; the contract: include/barbay_hip.h) ---------------------------------------------
+static void trace_reset(bb_handle* h) { h->trace_t = 0; h->trace_taken = 0; }
+#define BB_TRACE_REFUSED(h, what) \
+    do { if ((h)->trace_ring) return bb_fail(BB_ERR_UNSUPPORTED, what " is not available while an iterate trace is on (bb_trace_end first)"); } while (0)
+
+// (mu, omega) as they stand on the stream into the ring's next row
+static int trace_snapshot(bb_handle* h) {
+    TraceArgs T;
+    memset(&T, 0, sizeof T);
+    T.ring = h->trace_ring;
+    T.D = h->M.D;
+    T.D2 = 2 * T.D;
+    T.cap = h->trace_cap;
+    T.mu = h->S.mu;
+    T.om = h->S.om;
+    T.slot = h->trace_taken % h->trace_cap;
+    const int grid = (int)std::max<long long>(1, std::min<long long>((T.D2 + 4 * BB_TRACE_NT - 1) / (4 * BB_TRACE_NT), 2048));
+    const int rc = launch(h->stream, k_trace_snapshot, grid, BB_TRACE_NT, 0, T);
+    if (!rc) h->trace_taken++;
+    return rc;
+}
+
+// n_steps > 0 steps cut at the trace's boundaries, a snapshot behind every piece that ends on one.  Every piece makes the launches of a
+// bb_run call of its length (run_steps).  The two-kernel step reports through words nobody reads before the stream has drained
+// (check_persistent's non-finite flag), so its pieces and snapshots go out back to back under one run_open / run_finish; a resident
+// launch may time out, and what follows a timed-out launch must not be in flight already: there every piece is waited for.
+static int run_traced(bb_handle* h, int64_t n_steps) {
+    const int64_t every = h->trace_every;
+    const bool chained = h->plan.impl == IMPL_TWO_KERNEL;
+    int rc = 0, nonfinite = 0;
+    std::string why;
+    if (chained && (rc = run_open(h))) return rc;
+    for (int64_t left = n_steps; left > 0;) {
+        const int64_t piece = std::min<int64_t>(left, every - h->trace_t % every);
+        if ((rc = chained ? run_steps(h, piece) : run_enqueue(h, piece))) return rc;
+        h->trace_t += piece;
+        left -= piece;
+        if (h->trace_t % every == 0) rc = trace_snapshot(h);
+        if (!chained) {
+            const int r = run_finish(h);                     // (waits for whatever was launched, also after an error)
+            if (r == BB_ERR_NONFINITE) { if (!nonfinite) why = g_err; nonfinite = r; }      // the steps were taken: the run goes on
+            else if (r && !rc) rc = r;
+        }
+        if (rc) return rc;
+    }
+    if (chained) {
+        if ((rc = timer_stop(h->be, h->stream))) return rc;
+        return run_finish(h);
+    }
+    if (nonfinite) snprintf(g_err, sizeof g_err, "%s", why.c_str());
+    return nonfinite;
 }
 
 static int group_run(bb_handle* g, int64_t n_steps);      // (bb_engine.hip's groups, after this file: group_run needs run_enqueue / run_finish above)
@@ -92,6 +156,7 @@ extern "C" int bb_run(bb_handle* h, int64_t n_steps) {
     clock_gettime(CLOCK_MONOTONIC, &ht0);
 #endif
     BB_ENTER(h);
+    if (h->trace_ring && n_steps > 0) return run_traced(h, n_steps);
 #ifdef BB_HOST_TIMES
     clock_gettime(CLOCK_MONOTONIC, &ht1);
 #endif
@@ -160,6 +225,7 @@ static int run_profiled(bb_handle* h, int64_t n_steps) {
 extern "C" int bb_run_profiled(bb_handle* h, int64_t n_steps) {
     if (!h || n_steps < 0) return bb_fail(BB_ERR_INVALID, "bad argument");
     BB_GROUP_UNSUPPORTED(h, "bb_run_profiled");
+    BB_TRACE_REFUSED(h, "bb_run_profiled");
     BB_ENTER(h);
     return run_profiled(h, n_steps);
 }
@@ -271,6 +337,7 @@ static RunArgs split_phase_args(const bb_handle* h) { return make_args(h, h->ste
 extern "C" int bb_step_moments(bb_handle* h, double* partial) {
     if (!h || !partial) return bb_fail(BB_ERR_INVALID, "null argument");
     BB_GROUP_UNSUPPORTED(h, "bb_step_moments");
+    BB_TRACE_REFUSED(h, "bb_step_moments");
     BB_ENTER(h);
     if (h->M.kind == BB_MODEL_GENOTYPE && h->o.world_size > 1)
         return bb_fail(BB_ERR_UNSUPPORTED, "split-phase stepping of the sharded genotype model needs a second exchange; use bb_comm_init + bb_run");
@@ -283,6 +350,7 @@ extern "C" int bb_step_moments(bb_handle* h, double* partial) {
 extern "C" int bb_step_apply(bb_handle* h, const double* total) {
     if (!h || !total) return bb_fail(BB_ERR_INVALID, "null argument");
     BB_GROUP_UNSUPPORTED(h, "bb_step_apply");
+    BB_TRACE_REFUSED(h, "bb_step_apply");
     BB_ENTER(h);
     const RunArgs A = split_phase_args(h);
     int rc;

@@ -6,6 +6,8 @@ Turing types (`ADVI(samples_per_step, max_iters)`, `TruncatedADAGrad(eta, tau, n
 `DecayedADAGrad(eta, pre, post)`, src/vi.jl:98-99), and `seed`, `device`, `engine_kwargs` (e.g. `n_devices=8`: one
 call, all GPUs of the node -- include/barbay_hip.h bb_advi_opts.n_devices) select the
 Philox key, the GPU and engine options.  Errors the reference raises with `error(...)` are `BarBayError`.
+`convergence` (a `Convergence`, default None: the reference's fixed max_iters steps and last iterate) turns on the
+stopping rule and iterate averaging of Dhaka et al. 2020 on the engine's iterate trace.
 """
 from __future__ import annotations
 
@@ -47,6 +49,58 @@ class DecayedADAGrad:
     post: float = 0.9
 
 
+@dataclass
+class Convergence:
+    """Stopping rule and iterate averaging on the engine's iterate trace (include/barbay_hip.h, bb_trace_*; Dhaka et al. 2020,
+    "Robust, accurate stochastic optimization for variational inference").  (mu, omega) is kept after every `every` steps; the run
+    goes in calls of `check_every` steps up to `advi.max_iters`, and once `window` snapshots exist the last `window` of them, cut
+    into `n_chains` consecutive segments, are summarised after every call.  The run stops when every block of the layout, mu and
+    omega part, has no non-finite column and at most `max_share` of its non-constant columns at a split-R-hat above `rhat_max`
+    (1.1: Dhaka et al.'s threshold; the other defaults are choices nobody has measured at scale -- a wrong one costs a run to
+    max_iters, which is what happens without a `Convergence`).  `average`: report the window mean of (mu, omega) of the last
+    summarised window instead of the last iterate."""
+    every: int = 10
+    window: int = 400
+    n_chains: int = 4
+    check_every: int = 1000
+    rhat_max: float = 1.1
+    max_share: float = 0.0
+    average: bool = True
+
+
+def blocks_within_rule(blocks, max_share: float) -> bool:
+    """The stopping rule on a verdict frame of `Engine.trace_summary`."""
+    return bool(((blocks["n_nonfinite"] == 0) & (blocks["n_above"] <= max_share * (blocks["n_cols"] - blocks["n_const"]))).all())
+
+
+def run_monitored(e: Engine, max_iters: int, c: Convergence) -> Dict:
+    """`e.run` up to `max_iters` steps under the stopping rule `c`; with `c.average` the engine is left at the averaged iterate
+    (through `set_params`, so everything sampled from the handle afterwards is sampled from the averaged q).  Returns the
+    `convergence` record of `advi`'s frame."""
+    if c.n_chains < 1 or c.window % c.n_chains or c.window // c.n_chains < 4:
+        raise BarBayError("Convergence: window must be n_chains segments of at least 4 snapshots")
+    if c.every < 1 or c.check_every < 1:
+        raise BarBayError("Convergence: every and check_every must be >= 1")
+    e.trace_begin(c.every, max(c.window, 8))
+    steps, first, blocks, converged = 0, None, None, False
+    while steps < max_iters and not converged:
+        n = min(c.check_every, max_iters - steps)
+        e.run(n)
+        steps += n
+        taken, _ = e.trace_count()
+        if taken >= c.window:
+            first = taken - c.window
+            blocks = e.trace_summary(first, c.n_chains, c.window // c.n_chains, rhat_max=c.rhat_max)["blocks"]
+            converged = blocks_within_rule(blocks, c.max_share)
+    if c.average and first is not None:
+        mean = e.trace_summary(first, c.n_chains, c.window // c.n_chains, rhat_max=c.rhat_max, columns=True, only=("mean",), blocks=False)["mean"]
+        e.trace_end()
+        e.set_params(mean[:e.D], mean[e.D:])
+    else:
+        e.trace_end()
+    return {"converged": converged, "steps": steps, "window_first_step": None if first is None else (first + 1) * c.every, "blocks": blocks}
+
+
 def make_engine(bayes_model: BayesModel, advi: ADVI, opt, seed: int = 0, device: int = 0, **engine_kwargs) -> Engine:
     pri = {k: (m if m.shape[0] > 1 else float(m[0]), s if s.shape[0] > 1 else float(s[0]))
            for k, (m, s) in bayes_model.priors.items()}
@@ -63,12 +117,17 @@ def make_engine(bayes_model: BayesModel, advi: ADVI, opt, seed: int = 0, device:
 
 
 def vi(bayes_model: BayesModel, advi: ADVI, optimizer=None, seed: int = 0, device: int = 0, hier_samples: int = 10_000,
-       **engine_kwargs):
+       convergence: Optional[Convergence] = None, **engine_kwargs):
     """`Turing.vi(model, advi; optimizer)`: returns q with q.dist.m, q.dist.σ, q.transform.ranges_out --
     the fields `utils.advi_to_df` reads (src/utils.jl:1049, 1060).  For the hierarchical models q.hier holds the
-    device-side `process_hierarchical_samples!` result (n_samples, median, std) that `advi_to_df` appends."""
+    device-side `process_hierarchical_samples!` result (n_samples, median, std) that `advi_to_df` appends.  With a `convergence`
+    q.convergence holds the record of `run_monitored`."""
     with make_engine(bayes_model, advi, optimizer or TruncatedADAGrad(), seed, device, **engine_kwargs) as e:
-        e.run(advi.max_iters)
+        conv = None
+        if convergence is None:
+            e.run(advi.max_iters)
+        else:
+            conv = run_monitored(e, advi.max_iters, convergence)
         m, s = e.posterior()
         ranges = [(lo, hi) for _, lo, hi in e.layout()]
         hier = None
@@ -86,15 +145,16 @@ def vi(bayes_model: BayesModel, advi: ADVI, optimizer=None, seed: int = 0, devic
         elif hier_samples and e.hier_units() > 0:
             hier = (hier_samples,) + tuple(e.hier_fitness(hier_samples, seed=seed))
     dist = SimpleNamespace(m=m, σ=s, sigma=s)
-    return SimpleNamespace(dist=dist, transform=SimpleNamespace(ranges_out=ranges), hier=hier)
+    return SimpleNamespace(dist=dist, transform=SimpleNamespace(ranges_out=ranges), hier=hier, convergence=conv)
 
 
 def advi(*, data, outputname: Optional[str] = None, model: Callable, model_kwargs: Optional[Dict] = None,
          id_col="barcode", time_col="time", count_col="count", neutral_col="neutral", rep_col: Optional[str] = None,
          env_col: Optional[str] = None, genotype_col: Optional[str] = None, advi: Optional[ADVI] = None,
          opt: Union[TruncatedADAGrad, DecayedADAGrad, None] = None, verbose: bool = True, seed: int = 0, device: int = 0,
-         engine_kwargs: Optional[Dict] = None):
-    """src/vi.jl:86-235."""
+         engine_kwargs: Optional[Dict] = None, convergence: Optional[Convergence] = None):
+    """src/vi.jl:86-235.  With a `convergence` the frame carries df.attrs["convergence"] = {converged, steps, window_first_step,
+    blocks (the last verdict)}."""
     advi = advi or ADVI()
     opt = opt or TruncatedADAGrad()
     model_kwargs = dict(model_kwargs or {})
@@ -120,11 +180,13 @@ def advi(*, data, outputname: Optional[str] = None, model: Callable, model_kwarg
     bayes_model = model(arrays.bc_count, arrays.bc_total, arrays.n_neutral, arrays.n_bc, **model_kwargs)   # :172-178
     if not isinstance(bayes_model, BayesModel):
         raise BarBayError("model must be one of barbay model constructors (BarBay.model.*)")
-    q = vi(bayes_model, advi, opt, seed, device, **(engine_kwargs or {}))          # :201
+    q = vi(bayes_model, advi, opt, seed, device, convergence=convergence, **(engine_kwargs or {}))          # :201
     var_names = []                                                                 # :184-198
     for sym, (lo, hi) in zip(bayes_model.var_symbols(), q.transform.ranges_out):
         var_names += [f"{sym}[{x}]" for x in range(1, hi - lo + 1)]
     df = utils.advi_to_df(data, q, var_names, **cols, rng=np.random.default_rng(seed))   # :203-215
+    if q.convergence is not None:
+        df.attrs["convergence"] = q.convergence
     if fname is None:
         return df
     df.to_csv(fname, index=False)                                                  # :218-233

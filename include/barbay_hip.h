@@ -629,6 +629,91 @@ typedef struct bb_chain_out {     /* every pointer may be NULL; [n_cols] unless 
 int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols,
                      const double* chain /* host, [n_chains][n_draws][n_cols] */, const bb_chain_out* out);
 
+/* Convergence monitor: the optimiser's iterates kept as a chain on the device (Dhaka et al. 2020, "Robust, accurate stochastic
+ * optimization for variational inference": the run is stationary when split-R-hat of the iterates is near 1, and the average of
+ * the stationary iterates, with its MCSE, is reported in place of the last one).  No reference counterpart: the reference runs
+ * max_iters steps and reports the last iterate (src/vi.jl:201).  A handle on which no trace was begun behaves as without these calls.
+ *
+ * bb_trace_begin allocates a ring of `capacity` snapshots (8 .. BB_TRACE_MAX_SNAPSHOTS) on the handle's device; a snapshot is the
+ * handle's (mu, omega), 2 D doubles, in the handle's internal order.  every >= 1.  Outside those ranges, or a null h / o:
+ * BB_ERR_INVALID.  What the device cannot allocate is BB_ERR_DEVICE, and no trace is on.  A second begin on a handle under trace is
+ * BB_ERR_INVALID.  Sharded handles (world_size > 1) and multi-device handles (n_devices > 1): BB_ERR_UNSUPPORTED (after a resident
+ * run only the owner's theta is current on them).
+ *
+ * bb_run(h, n) under a trace.  Let t be the steps bb_run has taken since begin (or since the last reset, below).  Snapshot s
+ * (0-based, kept in slot s mod capacity) is (mu, omega) after trace step (s + 1) every.  The call makes exactly the launches that
+ * consecutive bb_run calls make when cut at those boundaries (every = 3, t = 1, n = 6: pieces of 2, 3 and 1 steps), and after a
+ * piece that ends on a boundary a snapshot kernel on the handle's stream copies the two arrays into the ring.  The result is, bit
+ * for bit, what an untraced twin handle holds after the same sequence of bb_run calls: parameters, optimiser state, step counter,
+ * ELBO ring, bb_stats.steps_done.  (A cut run is not promised to equal an uncut one bit for bit: bb_run never promised that.)
+ * BB_ERR_NONFINITE: the steps are taken and the snapshots recorded, non-finite values included.  BB_ERR_DEVICE from a piece ends
+ * the call there.  On the two-kernel step (bb_stats.resident_kernel == 0) the pieces and snapshots are enqueued back to back and
+ * the host waits once; a resident launch reports through status words the host reads after the stream has drained, so there the
+ * host waits after every piece.
+ *
+ * While a trace is on: bb_init_meanfield and bb_set_params discard the snapshots and set t to 0 (the trace stays on);
+ * bb_run_profiled, bb_step_moments and bb_step_apply are refused with BB_ERR_UNSUPPORTED; every other entry point is unaffected and
+ * leaves the trace as it is.  bb_destroy frees the ring.
+ *
+ * bb_trace_end frees the ring; without a trace it is BB_OK.  bb_trace_count: *taken = the snapshots recorded since begin or the
+ * last reset, *first_live = max(0, taken - capacity), the oldest snapshot the ring still holds (either pointer may be NULL; no
+ * trace on: BB_ERR_INVALID).  bb_trace_get returns snapshots first .. first + n - 1 in the caller's latent order (either array may
+ * be NULL); all of them must be live, else BB_ERR_INVALID with a message naming the live range.
+ *
+ * bb_trace_summary runs the statistics of bb_chain_summary on the ring, on the device, with nothing uploaded.  The window is the
+ * W N = n_chains n_draws live snapshots from `first`, chain c the consecutive segment first + c N .. first + (c + 1) N - 1; it may
+ * straddle the ring's wrap.  There are 2 D columns: column i < D is mu of the caller's latent i, column D + i its omega.
+ * max_lag and slab_cols as bb_chain_opts'.  Per-column outputs (each [2 D], each pointer may be NULL; what is NULL is not
+ * downloaded) equal, bit for bit, bb_chain_summary's with the same n_chains, n_draws, max_lag and no quantiles on the host array
+ * [W][N][2 D] built from bb_trace_get: the same two kernels run on slabs a device-side gather fills from the ring (a column's result
+ * does not depend on its position or its slab, so the slabs are cut in the handle's internal order).
+ *
+ * blocks (may be NULL): [2 n_blocks] verdicts, n_blocks that of bb_get_layout: the mu part of every layout block in layout order,
+ * then the omega parts, reduced on the device over the block's columns with integer counts and max / min only (no order matters):
+ *   n_cols        columns of the part (the block's length)
+ *   n_nonfinite   columns whose mean is NaN (a non-finite value in the window)
+ *   n_const       columns with sd == 0
+ *   n_above       columns with a finite rhat > rhat_max
+ *   max_rhat, min_ess   over the columns where they are finite; NaN if there are none
+ *   max_mcse_rel  the MCSE of the averaged iterate in units that mean something, the max over the columns where it is finite
+ *                 (NaN if none): for a mu column i, mcse_i / softplus(mean_{D+i}), the error of the mean in posterior sds; for an
+ *                 omega column, mcse_{D+i} sigmoid(mean_{D+i}) / softplus(mean_{D+i}), the relative error of sigma by the delta
+ *                 method (softplus and sigmoid those of the step kernels).
+ * The handle's mu, omega, optimiser state, step counter and RNG position are untouched, bitwise; so is the ring.
+ * BB_ERR_INVALID: a null h / o / out; no trace on; a window not wholly live (the message names the live range); n_chains < 1;
+ * n_draws < 4; a negative max_lag or slab_cols; rhat_max not finite or < 1.  BB_ERR_UNSUPPORTED: W N > BB_CHAIN_MAX_K. */
+#define BB_TRACE_MAX_SNAPSHOTS 16384            /* == BB_CHAIN_MAX_K */
+typedef struct bb_trace_opts {
+    int32_t every;            /* a snapshot after every `every` steps, >= 1            */
+    int32_t capacity;         /* snapshots the ring holds, 8 .. BB_TRACE_MAX_SNAPSHOTS */
+} bb_trace_opts;
+typedef struct bb_trace_sum_opts {
+    int64_t first;            /* first snapshot of the window                          */
+    int32_t n_chains;         /* W >= 1 consecutive segments                           */
+    int32_t n_draws;          /* N >= 4 snapshots per segment; W N <= BB_CHAIN_MAX_K   */
+    int32_t max_lag;          /* as bb_chain_opts                                      */
+    int32_t reserved0;
+    int64_t slab_cols;        /* as bb_chain_opts                                      */
+    double rhat_max;          /* n_above's threshold, finite and >= 1                  */
+} bb_trace_sum_opts;
+typedef struct bb_trace_block {
+    char name[24];            /* the layout block's name                               */
+    int32_t part;             /* 0 mu, 1 omega                                         */
+    int32_t reserved0;
+    int64_t n_cols, n_nonfinite, n_const, n_above;
+    double max_rhat, min_ess, max_mcse_rel;
+} bb_trace_block;
+typedef struct bb_trace_sum_out {     /* every pointer may be NULL                     */
+    double *mean, *sd, *mcse, *ess, *rhat;      /* [2 D]                               */
+    int32_t* n_lags;                  /* [2 D]                                         */
+    bb_trace_block* blocks;           /* [2 n_blocks]                                  */
+} bb_trace_sum_out;
+int bb_trace_begin(bb_handle* h, const bb_trace_opts* o);
+int bb_trace_end(bb_handle* h);
+int bb_trace_count(bb_handle* h, int64_t* taken, int64_t* first_live);
+int bb_trace_get(bb_handle* h, int64_t first, int64_t n, double* mu /* [n][D] */, double* omega /* [n][D] */);
+int bb_trace_summary(bb_handle* h, const bb_trace_sum_opts* o, const bb_trace_sum_out* out);
+
 /* The engine's normal stream for (step, stream) over latents [lo, hi), for checks. */
 int bb_debug_normals(bb_handle* h, int64_t step, uint32_t stream, int64_t lo, int64_t hi, double* out);
 

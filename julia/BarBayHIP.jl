@@ -487,4 +487,92 @@ function chain_summary(h::Ptr{Cvoid}, chain::AbstractArray{Float64}; probs::Vect
     return (mean=mean, sd=sd, mcse=mcse, ess=ess, rhat=rhat, quantiles=q, n_lags=nl)
 end
 
+# The iterate trace (bb_trace_*, include/barbay_hip.h): (mu, omega) kept after every `every` steps of bb_run in a device ring, and
+# split-R-hat / ESS / MCSE of a window of it computed where it lies, with a verdict per layout block.
+# Field for field the Python binding's `bb_trace_opts` / `bb_trace_sum_opts` / `bb_trace_block` / `bb_trace_sum_out`.
+const BB_TRACE_MAX_SNAPSHOTS = 16384
+struct bb_trace_opts
+    every::Int32
+    capacity::Int32
+end
+struct bb_trace_sum_opts
+    first::Int64
+    n_chains::Int32
+    n_draws::Int32
+    max_lag::Int32
+    reserved0::Int32
+    slab_cols::Int64
+    rhat_max::Float64
+end
+struct bb_trace_block
+    name::NTuple{24,UInt8}
+    part::Int32
+    reserved0::Int32
+    n_cols::Int64
+    n_nonfinite::Int64
+    n_const::Int64
+    n_above::Int64
+    max_rhat::Float64
+    min_ess::Float64
+    max_mcse_rel::Float64
+end
+struct bb_trace_sum_out
+    mean::Ptr{Float64}
+    sd::Ptr{Float64}
+    mcse::Ptr{Float64}
+    ess::Ptr{Float64}
+    rhat::Ptr{Float64}
+    n_lags::Ptr{Int32}
+    blocks::Ptr{bb_trace_block}
+end
+
+trace_begin(h::Ptr{Cvoid}, every::Integer, capacity::Integer) =
+    check(ccall((:bb_trace_begin, LIB), Cint, (Ptr{Cvoid}, Ref{bb_trace_opts}), h, bb_trace_opts(Int32(every), Int32(capacity))))
+trace_end(h::Ptr{Cvoid}) = check(ccall((:bb_trace_end, LIB), Cint, (Ptr{Cvoid},), h))
+
+"`(taken, first_live)`: snapshots recorded since `trace_begin` or the last reset, and the oldest one the ring still holds (0-based)."
+function trace_count(h::Ptr{Cvoid})
+    taken, live = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:bb_trace_count, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), h, taken, live))
+    return (Int(taken[]), Int(live[]))
+end
+
+"Snapshots `first .. first + n - 1` (0-based) as `(mu, omega)`, each D x n, in the caller's latent order."
+function trace_get(h::Ptr{Cvoid}, first::Integer, n::Integer)
+    D = Int(ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h))
+    mu, om = Matrix{Float64}(undef, D, n), Matrix{Float64}(undef, D, n)
+    check(ccall((:bb_trace_get, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}), h, first, n, mu, om))
+    return (mu, om)
+end
+
+"""
+    trace_summary(h, first, n_chains, n_draws; max_lag=0, slab_cols=0, rhat_max=1.1, columns=false) -> NamedTuple
+
+The window of `n_chains * n_draws` snapshots from `first` (0-based), cut into `n_chains` consecutive segments.  Returns `blocks`, a
+vector of `(name, part, n_cols, n_nonfinite, n_const, n_above, max_rhat, min_ess, max_mcse_rel)` -- the mu part of every layout
+block, then the omega parts -- and, with `columns`, `mean, sd, mcse, ess, rhat, n_lags` (2 D each: mu of latent i at i, its omega at
+D + i).
+"""
+function trace_summary(h::Ptr{Cvoid}, first::Integer, n_chains::Integer, n_draws::Integer; max_lag::Integer=0, slab_cols::Integer=0,
+                       rhat_max::Real=1.1, columns::Bool=false)
+    D = Int(ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h))
+    lay = Vector{bb_block_range}(undef, 8)
+    nb = Ref{Int32}(0)
+    check(ccall((:bb_get_layout, LIB), Cint, (Ptr{Cvoid}, Ptr{bb_block_range}, Ref{Int32}), h, lay, nb))
+    n = columns ? 2D : 0
+    mean, sd, mcse, ess, rhat = (Vector{Float64}(undef, n) for _ in 1:5)
+    nl = Vector{Int32}(undef, n)
+    vb = Vector{bb_trace_block}(undef, 2 * nb[])
+    p(v) = columns ? pointer(v) : Ptr{eltype(v)}(C_NULL)
+    GC.@preserve mean sd mcse ess rhat nl vb begin
+        o = bb_trace_sum_opts(Int64(first), Int32(n_chains), Int32(n_draws), Int32(max_lag), Int32(0), Int64(slab_cols), Float64(rhat_max))
+        out = bb_trace_sum_out(p(mean), p(sd), p(mcse), p(ess), p(rhat), p(nl), pointer(vb))
+        check(ccall((:bb_trace_summary, LIB), Cint, (Ptr{Cvoid}, Ref{bb_trace_sum_opts}, Ref{bb_trace_sum_out}), h, o, out))
+    end
+    name(b) = String(UInt8[c for c in b.name if c != 0x00])
+    blocks = [(name=name(b), part=b.part == 0 ? :mu : :omega, n_cols=b.n_cols, n_nonfinite=b.n_nonfinite, n_const=b.n_const,
+               n_above=b.n_above, max_rhat=b.max_rhat, min_ess=b.min_ess, max_mcse_rel=b.max_mcse_rel) for b in vb]
+    return columns ? (blocks=blocks, mean=mean, sd=sd, mcse=mcse, ess=ess, rhat=rhat, n_lags=nl) : (blocks=blocks,)
+end
+
 end # module
