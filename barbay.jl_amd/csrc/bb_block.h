@@ -769,7 +769,7 @@ BB_DEV void bb_put_total(const DevModel& M, const BBLds& L, double* lds, int k, 
     lds[L.wk + k] = s;
     if (L.tmap) {       // (k_res: one LDS read instead of a search through the model record -- a chain of dependent scalar loads per replicate)
         const int j = ((const int*)(lds + L.tmap))[k];
-        if (j >= 0) { lds[L.invS + j] = bb_rcp(s); lds[L.Lt + j] = bb_log(s); }
+        if (j >= 0) lds[L.invS + j] = bb_rcp(s);      // (no L_t: br_finish takes c_t from the totals' ratio, bb_dlog's form)
         return;
     }
     for (int r = 0; r < M.R; ++r) {

@@ -52,7 +52,7 @@ struct BRSeg { long long lo, hi; int tbeg, span, blk, kind, ldsoff, r, lpb, T; d
 #define BR_SEG_DOUBLES 12
 
 struct BRLay {
-    BBLds L;             // what the shared exchange / finish code reads: wk, zgl, Lt, invS, cc, wbar, gglob, Dt, elbt, misc, acc, red
+    BBLds L;             // what the shared exchange / finish code reads: wk, zgl, invS, cc, wbar, gglob, Dt, elbt, misc, acc, red
     int zl, NBT;         // [2][NBT] staged loglambda samples, double-buffered by step parity; replicate r's rows start at zr0[r] and are
     int zr0[BB_MAX_REP]; // T_r + 1 doubles apart: with the natural stride T_r (8: 64 B) the unit threads' walks along their barcodes'
                          // rows (two barcodes per lane) land all 64 lanes in two banks -- measured: the unit waves' G pass took
@@ -67,9 +67,10 @@ struct BRLay {
     int racc_r[BB_MAX_REP], rw[BB_MAX_REP];   // of the replicate's loglambda segment (rw = its lanes, whole waves; + 4: the 12 columns start in different banks)
     int rowmap;          // [K] int pairs: {lanes per barcode | used << 24, LDS offset of the entry's column (value v of time-pair class k of replicate r)}
     int iG, csum;        // [Ttot] G_t / S_t;  [R] sum_t c_t
+    int piv;             // [Ttot] the moment pivot of every time step (DevModel::piv), copied once per launch: the M pass reads it per pair
     int rtab;            // [R] int4: per replicate {first time point (tcum), offset of its rows in zl, time points, -} -- for the unit threads' walks
     int ftab;            // [Ttot] int4: what the F pass needs of time point j -- {LDS offset of its five moment totals or -1 (a replicate's last
-                         // time point), its index inside s_pop, has a time point before it, -}
+                         // time point), its index inside s_pop, has a time point before it, LDS offset of its normaliser S_t}
     int envt;            // [Ttot] ints: environment of every time point (multienv)
     int gas;             // genotype model: [SU] w As of every mutant of the tile, summed per genotype by the theta threads
     int gix;             // genotype model: int tables of the tile -- [SU] genotype of every mutant minus the tile's first, then [SU] per own genotype
@@ -120,7 +121,7 @@ static inline bool br_any_parity(const DevModel& M) {
 // the instances whose time-point count is a template argument -- __builtin_assume on every field, to take ~20 uniform values out of a
 // step loop that holds more of them than there are SGPRs: the spill count did not move, 296 -> 300 v_readlane_b32, C2 11.87 -> 11.95 us,
 // C4 unchanged; profiles/r04d_c2_experiments.)
-struct BRHdr { int rowmap, tmap, wk, zgl, Lt, invS, cc, wbar, gglob, misc, part, Dt, elbt, iG, csum, ftab, rtab, envt, seg, end; };
+struct BRHdr { int rowmap, tmap, wk, zgl, piv, invS, cc, wbar, gglob, misc, part, Dt, elbt, iG, csum, ftab, rtab, envt, seg, end; };
 #ifndef BB_EMU
 __host__ __device__
 #endif
@@ -132,7 +133,7 @@ inline constexpr BRHdr br_header(int K, int nt1, int Ttot, int R) {
     h.tmap = o;    o += (K + 1) / 2 + 1;
     h.wk = o;      o += KK;
     h.zgl = o;     o += 2 * nt1;
-    h.Lt = o;      o += Ttot;
+    h.piv = o;     o += Ttot;               // (the moment pivots, DevModel::piv: where log S_t stood until c_t came from the totals' ratio)
     h.invS = o;    o += Ttot;
     h.cc = o;      o += Ttot + 1;
     h.wbar = o;    o += Ttot + 1;
@@ -174,7 +175,7 @@ BRLay br_layout(const DevModel& M, int NB, int NT, int P, int xg_rows, bool own_
     if (stream) { long long sp = 0; for (int r = 0; r < M.R; ++r) sp += (long long)NB * (M.T[r] / 2); Y.NBT = (int)(2 * sp + 2); }      // ([R][NB][T / 2] pairs)
     {
         const BRHdr H = br_header(M.K, M.nt1, M.Ttot, M.R);
-        Y.rowmap = H.rowmap; L.tmap = H.tmap; L.wk = H.wk; L.zgl = H.zgl; L.Lt = H.Lt; L.invS = H.invS; L.cc = H.cc; L.GG = H.wbar; L.wbar = H.wbar;
+        Y.rowmap = H.rowmap; L.tmap = H.tmap; L.wk = H.wk; L.zgl = H.zgl; Y.piv = H.piv; L.invS = H.invS; L.cc = H.cc; L.GG = H.wbar; L.wbar = H.wbar;
         L.gglob = H.gglob; L.misc = H.misc; L.part = H.part; L.Dt = H.Dt; L.elbt = H.elbt; Y.iG = H.iG; Y.csum = H.csum; Y.ftab = H.ftab;
         Y.rtab = H.rtab; Y.envt = H.envt; Y.seg = H.seg; L.seg = H.seg;
         o = H.end;
@@ -502,7 +503,7 @@ BB_HD void br_table_time(const DevModel& M, const BBLds& L, int j, int* ft) {
     ft[0] = tt < T - 1 ? L.wk + M.kq[r] + T + 5 * tt : -1;
     ft[1] = M.off_t[r] + tt;
     ft[2] = tt > 0 ? 1 : 0;
-    ft[3] = 0;
+    ft[3] = L.wk + M.kq[r] + tt;          // LDS offset of the normaliser S_t (S_{t+1} follows it)
 }
 BB_HD void br_table_rep(const DevModel& M, const BRLay& Y, int r, int* rt) {
     rt[0] = M.tcum[r]; rt[1] = Y.zr0[r]; rt[2] = M.T[r];
@@ -541,6 +542,7 @@ BB_DEV void br_tile_setup(BBCtx& cx, const DevModel& M, const DevState& S, const
         for (int i = tid; i < Y.nst * Y.stw; i += cx.nthr) lds[Y.st[0] + i] = 0.0;
         if (tid <= M.Ttot) { lds[L.cc + tid] = 0.0; lds[L.wbar + tid] = 0.0; lds[L.Dt + tid] = 0.0; }
         if (tid < M.Ttot) ((int*)(lds + Y.envt))[tid] = (KIND == 1 || KIND == 4) ? M.env_idx[tid] : 0;
+        if (tid < M.Ttot) lds[Y.piv + tid] = M.piv[tid];
         // (the per-replicate table here, in front of the barrier: the pair descriptors read it)
         if (S.ldstab) { for (int i = tid; i < 4 * M.R; i += cx.nthr) ((int*)(lds + Y.rtab))[i] = S.ldstab[3 * M.K + 4 * M.Ttot + i]; }
         else for (int rr = tid; rr < M.R; rr += cx.nthr) br_table_rep(M, Y, rr, (int*)(lds + Y.rtab) + 4 * rr);
@@ -845,7 +847,14 @@ BB_DEV void br_row_publish(BBCtx& cx, const DevModel& M, const DevState& S, cons
             const double* col = lds + rm[2 * j + 1];
             double s = 0.0;
 #ifdef BB_EMU
-            if (c == 0 && (code >> 24)) for (int e = 0; e < nbt; ++e) s += col[e * lpb];
+            // (the device's order: 16 strided partial sums, then br_row16_sum's butterfly -- one chain over the column leaves ~ sqrt(n) u / 2 in
+            //  S_t, and c_t's absolute error is what the s_pop gradient is most sensitive to, tests/_accuracy_cases.py)
+            if (c == 0 && (code >> 24)) {
+                double p[16];
+                for (int i = 0; i < 16; ++i) { p[i] = 0.0; for (int e = i; e < nbt; e += 16) p[i] += col[e * lpb]; }
+                for (int h = 8; h >= 1; h >>= 1) { double q[16]; for (int i = 0; i < 16; ++i) q[i] = p[i] + p[(i + h) & 15]; for (int i = 0; i < 16; ++i) p[i] = q[i]; }
+                s = p[0];
+            }
 #else
             // (More reads in flight per lane make this walk SLOWER, three forms tried -- source-level unrolling twice, one asm block of
             //  four ds_read_b64: pub 2.26 k -> 2.71 k cycles, profiles/r03b_tagged_rows/column_walk_*: it is bound by the LDS pipeline
@@ -921,7 +930,10 @@ BB_DEV void br_moments(BBCtx& cx, const DevModel& M, const DevState& S, const BR
             const bool hn = meta & BRM_NEXT, mut = meta & BRM_MUT;
             const double z0 = st.z[k].x, z1 = st.z[k].y;
             const double zn = hn ? zb[2] : z1;
-            double dm = z1 - z0, dn = zn - z1;       // the pair's two forward differences (the backward one of z0 belongs to the previous pair)
+            // the pair's two forward differences (the backward one of z0 belongs to the previous pair), less their steps' pivots: the moments
+            // are then of the residuals' own size and br_finish's polynomials in c_t - piv_t do not cancel (DevModel::piv)
+            const double* pv = lds + Y.piv + st.pt[k];
+            double dm = (z1 - z0) - pv[0], dn = hn ? (zn - z1) - pv[1] : 0.0;
             cv[0] += st.lam[k].x;
             cv[6] += st.lam[k].y;
             if (mut) {
@@ -943,6 +955,9 @@ BB_DEV void br_moments(BBCtx& cx, const DevModel& M, const DevState& S, const BR
 #pragma unroll
                 for (int q = 0; q < BR_NCV; ++q) lds[st.rb[k] + q * stride] = cv[q];
             }
+            // (several slots: one slot's contributions after the other.  With the slots' LDS reads -- z, unit forms, pivots -- hoisted in front
+            //  of all of them, two 512-thread instances of three slots that fitted their 256 registers took 2 and 4 spilled ones.)
+            if (P > 1) BR_SCHED_FENCE();
         }
     }
     BB_SYNC(cx);                     // barrier 2: the contributions are in LDS
@@ -993,13 +1008,18 @@ BB_DEV void br_finish(BBCtx& cx, const DevModel& M, const DevState& S, const BRL
                 const double M0 = mm[0], M1 = mm[1], N1 = mm[3], N2 = mm[4];
                 const double sbar = lds[L.zgl + zo], ls = lds[L.zgl + M.nt1 + zo];
                 wb = bb_exp(-2.0 * ls);
-                c = lds[L.Lt + j + 1] - lds[L.Lt + j] - sbar;
-                const double quadN = N2 - 2.0 * c * N1 + nn * c * c;
-                Dt = (M1 - c * M0) + wb * (N1 - c * nn);
+                // L_{t+1} - L_t as the log of the totals' ratio (bb_dlog: the difference of two logs loses ~ u |L_t| in every residual of the
+                // step alike).  The moments came about the step's pivot, so their polynomials take cp = c_t - piv_t; the G pass forms its
+                // residuals a - c from the plain differences and reads the plain c_t.
+                const double dl = bb_log(lds[ft[3] + 1] * lds[L.invS + j]);
+                const double cp = (dl - lds[Y.piv + j]) - sbar;
+                c = dl - sbar;
+                const double quadN = N2 - 2.0 * cp * N1 + nn * cp * cp;
+                Dt = (M1 - cp * M0) + wb * (N1 - cp * nn);
                 lds[L.gglob + zo] = -Dt;
                 lds[L.gglob + M.nt1 + zo] = wb * quadN - nn;
                 if (MS && want_el) {
-                    const double M2 = mm[2], quadM = M2 - 2.0 * c * M1 + c * c * M0;
+                    const double M2 = mm[2], quadM = M2 - 2.0 * cp * M1 + cp * cp * M0;
                     lds[L.elbt + j] = -0.5 * (quadM + wb * quadN) - nn * ls;
                 }
             } else if (MS && want_el) lds[L.elbt + j] = 0.0;

@@ -341,7 +341,8 @@ BB_DEV void bs_moments(BBCtx& cx, const DevModel& M, const DevState& S, const Ru
                 if ((meta & 15) != SK_L || !(meta & BRM_VALID)) continue;
                 const bb_d2 d = *(const bb_d2*)(lds + Y.zl + st.zoff[0]);
                 const bool hn = meta & BRM_NEXT, mut = meta & BRM_MUT;
-                double dm = d.y - d.x, dn = hn ? lds[Y.zl + st.zoff[0] + 2] - d.y : 0.0;
+                const double* pv = lds + Y.piv + st.pt[0];          // (the differences less their steps' pivots: br_moments)
+                double dm = (d.y - d.x) - pv[0], dn = hn ? (lds[Y.zl + st.zoff[0] + 2] - d.y) - pv[1] : 0.0;
                 if (KIND >= 3) { g.cv[0] += bb_exp(d.x); g.cv[6] += bb_exp(d.y); }
                 if (mut) {
                     double sm, sn, wm, wn;

@@ -12,7 +12,7 @@ def test_mp_literal_agrees_with_the_literal_oracle_on_the_control_point(case):
 
 
 @pytest.mark.parametrize("case", ["fitness_T5_d200", "multienv_d200", "genotype_d200", "replicate_d200", "replicate_ragged_d200",
-                                  "multienv_replicate_d200"])
+                                  "multienv_replicate_d200", "multienv_replicate_T46_d200"])
 def test_mp_literal_runs_every_model_kind(case):
     a.case_mp_literal_runs(case)
 
@@ -52,3 +52,14 @@ def test_trajectory_from_posterior_like_start_emulation(emu_lib, monkeypatch, na
     for k, v in a.TRAJ[name][1].items():
         monkeypatch.setenv(k, v)
     a.case_trajectory(emu_lib, name, S)
+
+
+@pytest.mark.parametrize("case,config", a.resident_cases())
+def test_resident_accuracy_emulation(emu_lib, case, config):
+    """The gradient the resident launches form (k_res, k_stream, k_persist), read back through one linear optimiser step."""
+    a.case_resident_accuracy(emu_lib, case, config)
+
+
+@pytest.mark.parametrize("case", ["fitness_T4_d200", "replicate_d200"])
+def test_resident_probe_is_the_gradient_emulation(emu_lib, case):
+    a.case_probe_selfcheck(emu_lib, case)

@@ -6,8 +6,16 @@
                                                       C port's from the posterior-like start, on the engine's own draws; also
                                                       written to tests/golden/accuracy_trajectories.json, which the tests read
 
+    python tools/accuracy_units.py resident_emulation [commit|parent LIB]     the gradient inside the resident launches
+    python tools/accuracy_units.py resident_device [commit|parent LIB] [out.json]   (tests/_accuracy_cases.py, resident_measure), emulation / GPU;
+                                                      "parent LIB": the same probe on another build's library (the parent
+                                                      commit's libbb_emu.so / libbarbay_hip.so), recorded beside this commit's
+
 units.json: target -> "units": rows [case, geometry, point, quantity, block, oracle units, engine units, bound, entry point of the
 engine's worst, max-norm figure]; "trajectories": name_S -> mode -> [max|dmu|, max|domega|] against the literal oracle's loop.
+"resident_emulation" / "resident_device": "parent" and "commit" -> one row per kernel and model kind, [kernel<kind, quantity, asserted by the
+tests, measured rows, {block: rows over their bound}, then the row nearest its bound: case, config, S, point, block, oracle units, engine
+units, bound].
 Unlike the tests this asserts nothing: a figure over its bound is recorded as it is.
 """
 import ctypes
@@ -48,6 +56,21 @@ def units(lib):
     return rows
 
 
+def resident(lib, device):
+    groups = {}
+    for case, config in a.resident_cases(device):
+        for r in a.resident_measure(lib, case, config, device):
+            key = (r["kernel"].replace("emu:", "").split(",")[0], r["quantity"], r["asserted"])
+            g = groups.setdefault(key, dict(n=0, over={}, worst=None))
+            g["n"] += 1
+            if not r["engine"] <= a.bound(r["oracle"]):
+                g["over"][r["block"]] = g["over"].get(r["block"], 0) + 1
+            if g["worst"] is None or r["engine"] / a.bound(r["oracle"]) > g["worst"][6] / g["worst"][7]:
+                g["worst"] = [case, config, r["S"], r["point"], r["block"], round(r["oracle"], 3), round(r["engine"], 3), round(a.bound(r["oracle"]), 3)]
+    print(sum(g["n"] for g in groups.values()), "rows,", sum(sum(g["over"].values()) for k, g in groups.items() if k[2]), "asserted rows over their bound")
+    return [list(k) + [g["n"], g["over"]] + g["worst"] for k, g in sorted(groups.items())]
+
+
 def trajectories(lib):
     out = {}
     for name in a.TRAJ:
@@ -79,25 +102,44 @@ def yardsticks():
     return out
 
 
-def main(what, out=OUT):
-    doc = json.load(open(OUT)) if os.path.exists(OUT) else {}
-    if what == "yardsticks":
+def main(what, *rest):
+    out = OUT
+    if what.startswith("resident_"):
+        which, path = "commit", None
+        if rest and rest[0] in ("commit", "parent"):
+            which, rest = rest[0], rest[1:]
+            if which == "parent":
+                path, rest = rest[0], rest[1:]
+        out = rest[0] if rest else OUT
+        if what == "resident_emulation":
+            lib = _capi._declare(ctypes.CDLL(path)) if path else emu()
+        else:
+            lib = _capi._declare(ctypes.CDLL(path)) if path else _capi.load_library()
+        doc = json.load(open(out if os.path.exists(out) else OUT))          # (a second run into the same out.json adds to the first)
+        doc.setdefault(what, {})[which] = resident(lib, what == "resident_device")
+        rest = ()
+    elif what == "yardsticks":
+        doc = json.load(open(OUT)) if os.path.exists(OUT) else {}
         y = yardsticks()
         with open(a.YARDSTICKS, "w") as f:
             json.dump(y, f, indent=1, sort_keys=True)
             f.write("\n")
         doc["trajectory_yardsticks"] = y
     else:
+        out = rest[0] if rest else OUT
+        doc = json.load(open(OUT)) if os.path.exists(OUT) else {}
         lib = emu() if what == "emulation" else _capi.load_library()
         doc[what] = dict(units=units(lib), trajectories=trajectories(lib))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         f.write("{\n" + ",\n".join(
             f' {json.dumps(k)}: ' + (json.dumps(v, sort_keys=True) if k == "trajectory_yardsticks" else
+                                    "{" + ",\n  ".join(f'{json.dumps(w)}: [\n   ' + ",\n   ".join(json.dumps(r) for r in rr) + "]"
+                                                        for w, rr in sorted(v.items())) + "}" if k.startswith("resident_") else
                                     '{"trajectories": ' + json.dumps(v["trajectories"], sort_keys=True) + ',\n  "units": [\n   ' +
                                     ",\n   ".join(json.dumps(r) for r in v["units"]) + "]}")
             for k, v in sorted(doc.items())) + "\n}\n")
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:3])
+    main(*sys.argv[1:])
