@@ -28,6 +28,7 @@ BB_SCORE_MAX_SAMPLES = 16384
 BB_RB_MAX_SAMPLES = 8672
 BB_RB_MAX_Q = 8
 BB_THETA_RB_CHUNK = 64
+BB_POPMEAN_RB_CHUNK = 256
 BB_MATH_FN = {"exp": 0, "log": 1, "rcp": 2, "div": 3, "sqrt": 4, "softplus_sigmoid": 5, "sincospi": 6, "exp_nonpos": 7, "log_1to2": 8,
               "box_muller": 9}
 BB_ERR_UNSUPPORTED = -4
@@ -39,7 +40,7 @@ EXPORTS = [
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
-    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb",
+    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
 ]
 
@@ -133,6 +134,10 @@ class bb_rb_out(C.Structure):
 
 class bb_theta_rb_out(C.Structure):
     _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("n_members", C.POINTER(C.c_int32)), ("n_steps", C.POINTER(C.c_int32))]
+
+
+class bb_popmean_rb_out(C.Structure):
+    _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("n_members", C.POINTER(C.c_int32))]
 
 
 class bb_chain_opts(C.Structure):
@@ -242,6 +247,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_theta_rb"):
         lib.bb_theta_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_theta_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_theta_rb_out)]
+    if hasattr(lib, "bb_popmean_rb"):
+        lib.bb_popmean_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
+        lib.bb_popmean_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_popmean_rb_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     if hasattr(lib, "bb_trace_begin"):
@@ -670,6 +678,31 @@ class Engine:
         out.n_steps = res["n_steps"].ctypes.data_as(C.POINTER(C.c_int32))
         out.n_members = res["n_members"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_theta_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def popmean_rb_shape(self) -> int:
+        """Groups of `popmean_rb`: the length of the s_pop block, g = (replicate, step), replicate-major."""
+        n = C.c_int64(0)
+        self._check(self._lib.bb_popmean_rb_shape(self._h, C.byref(n)))
+        return int(n.value)
+
+    def popmean_rb(self, n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
+                   draws=None) -> Dict[str, np.ndarray]:
+        """Rao-Blackwellised marginal of every population mean fitness sbar_g (`bb_popmean_rb`): its exact Gaussian full
+        conditional -- the prior and the log-frequency-ratio terms of every barcode of the replicate at the step, neutrals and
+        mutants -- averaged over the draws of `fitness_rb` (same arguments).  Returns q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg
+        [n_groups], quantiles [n_groups, len(probs)] and n_members (int32: neutrals + mutants)."""
+        n_groups = self.popmean_rb_shape()
+        o, p, _x = self._rb_opts(n_samples, probs, threshold, seed, draws)
+        res = {k: np.empty(n_groups) for k in RB_UNITS}
+        res["quantiles"] = np.empty((n_groups, p.shape[0]))
+        res["n_members"] = np.empty(n_groups, dtype=np.int32)
+        out = bb_popmean_rb_out()
+        for k in RB_UNITS:
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.n_members = res["n_members"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_popmean_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,

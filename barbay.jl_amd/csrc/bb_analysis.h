@@ -807,6 +807,122 @@ extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_
     return rc;
 }
 
+// ---- Rao-Blackwellised population-mean fitness marginals (bb_rb.h) ------------------------------------------------------------------
+static_assert(BB_POPMEAN_RB_CHUNK == BB_POP_CHUNK, "bb_popmean_rb chunk");
+extern "C" int bb_popmean_rb_shape(const bb_handle* h, int64_t* n_groups) {
+    if (!h || !n_groups) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_groups = h->M.blk_hi[BK_SPOP] - h->M.blk_lo[BK_SPOP];
+    return BB_OK;
+}
+
+extern "C" int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    if (int rc = rb_check(o)) return rc;
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    PopArgs H;
+    memset(&H, 0, sizeof H);
+    RbArgs& A = H.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const long long n_groups = M.nt1, nmem = M.nn + M.nb;
+    if (nmem > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_popmean_rb: more than 2^31 members");
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
+    if (rc) return rc;
+    int zb;
+    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    {   // the prior of sbar: the s_pop block is never regrouped, so a Matrix form lies in the handle as the caller gave it, indexed by g
+        const DevPrior& dp = M.pri[BK_SPOP];
+        P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    }
+    A.nq = nq;
+    A.threshold = o->threshold;
+    A.n_units = n_groups;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+    H.nchunks = (int)((nmem + BB_POP_CHUNK - 1) / BB_POP_CHUNK);
+#ifdef BB_RB_TIMES             // diagnostics (tools/popmean_rb_rate.py): the call's phases, each drained before the next starts
+    timespec ct[7];
+    double cms[5] = {0, 0, 0, 0, 0};
+    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int, int) {};
+#endif
+    lap(0, -1);
+    // the ragged method's pairing: neutral member i of group (r, k) is element x = k nn + i of the replicate's time-fastest vector
+    std::vector<int> neu;
+    if (M.quirk) {
+        neu.resize(2 * (size_t)n_groups * (size_t)M.nn);
+        int* nt = neu.data();
+        int* nbv = nt + (size_t)n_groups * (size_t)M.nn;
+        for (int r = 0; r < M.R; ++r)
+            for (int k = 0; k + 1 < M.T[r]; ++k)
+                for (long long i = 0; i < M.nn; ++i) {
+                    const long long x = (long long)k * M.nn + i, at = (long long)(M.off_t[r] + k) * M.nn + i;
+                    nt[at] = (int)(x % (M.T[r] - 1));
+                    nbv[at] = (int)(x / (M.T[r] - 1));
+                }
+    }
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ng = (size_t)n_groups, nch = (size_t)H.nchunks;
+    // the groups in flight: their chunk partials bounded to 256 MiB (a single group is worked whole whatever it takes)
+    const size_t slab = std::min(ng, std::max<size_t>(1, ((size_t)256 << 20) / (nch * 2 * nsz * 8)));
+    const int nblk = (int)std::max<long long>(1, std::min<long long>(n_groups, B.nblk));      // (P.par holds a [nblk][ns] table of sbar_j)
+    double* ddraws = nullptr;
+    int* dneu = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(H.part, slab * nch * 2 * nsz);               // [groups in flight][nchunks][2][ns]
+        c(A.unit, BB_RB_OUT * ng);                     // [6][n_groups]
+        c(A.quant, BB_RB_MAX_Q * ng);                  // [n_groups][8]
+        c(dneu, (neu.size() + 1) / 2);                 // the flagged pairing: ints
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    A.ytab = P.par;
+    if (!neu.empty()) {
+        if ((rc = h2d(dneu, neu.data(), neu.size() * 4, dh->stream))) return rc;
+        H.neu_t = dneu;
+        H.neu_b = dneu + neu.size() / 2;
+    }
+    if (o->draws) {
+        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
+        P.draws = ddraws;
+        P.D = (long long)D;
+    }
+    lap(1, 0);
+    if ((rc = freq_normalisers(dh, F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
+    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
+    lap(2, 1);
+    for (size_t g0 = 0; g0 < ng; g0 += slab) {
+        const size_t g1 = std::min(ng, g0 + slab);
+        H.g0 = (long long)g0; H.g1 = (long long)g1;
+        lap(3, -1);
+        if ((rc = launch(dh->stream, k_rb_pop_part, (int)std::min<size_t>((g1 - g0) * nch, (size_t)1 << 20), BB_SCORE_NT, 0, H))) return rc;
+        lap(4, 2);
+        if ((rc = launch(dh->stream, k_rb_pop, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), H))) return rc;
+        lap(5, 3);
+    }
+    double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
+    for (int k = 0; k < BB_RB_OUT; ++k)
+        if (units[k] && (rc = d2h(units[k], A.unit + (size_t)k * ng, ng * 8, dh->stream))) return rc;
+    if (out->quantiles && nq) {
+        std::vector<double> q(BB_RB_MAX_Q * ng);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
+        for (size_t g = 0; g < ng; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
+    }
+    if (out->n_members) for (size_t g = 0; g < ng; ++g) out->n_members[g] = (int32_t)nmem;
+    rc = dsync(dh->stream);
+    lap(6, 4);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_popmean_rb %lld groups, %lld members, %d chunks each, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, pop %.3f ms, download %.3f ms\n", n_groups, nmem, H.nchunks, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
+}
+
 // ---- chain diagnostics (bb_chain.h) --------------------------------------------------------------------------------------------
 static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRIDE && BB_CHAIN_LAG_BATCH == BB_CHAIN_LAGS &&
               2 * BB_CHAIN_MAX_Q <= BB_PPC_MAX_TGT, "bb_chain_summary limits");

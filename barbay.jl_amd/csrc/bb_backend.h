@@ -425,6 +425,14 @@ BB_KERNEL(BB_SCORE_NT, k_rb_theta, ThetaArgs H) {
     BB_CTX;
     bb_block_theta(cx, H, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_rb_pop_part, PopArgs H) {
+    BB_CTX;
+    bb_block_pop_part(cx, H, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_rb_pop, PopArgs H) {
+    BB_CTX;
+    bb_block_pop(cx, H, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

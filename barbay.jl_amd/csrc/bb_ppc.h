@@ -51,10 +51,10 @@ struct PpcArgs {
     int plo[2 * BB_PPC_MAX_Q];               // band end e (= 2 qi + upper): index into tgt of its lower order statistic (upper: +1)
     double gam[2 * BB_PPC_MAX_Q];            // ... and its interpolation weight
     unsigned long long seed;
-    // bb_fitness_rb / bb_theta_rb (bb_rb.h) only; all zero in every other call, which then runs exactly as before
+    // bb_fitness_rb / bb_theta_rb / bb_popmean_rb (bb_rb.h) only; all zero in every other call, which then runs exactly as before
     const double* draws;      // [n_samples][D] explicit draws in the caller's order, read in place of the Philox draw; nullptr: none
     long long D;              // ... and their row length
-    const double* pri_mean_e; // s_bc prior, Matrix form (device, caller order = the handle's for the blocks that have one): mean,
+    const double* pri_mean_e; // the call's prior (s_bc; bb_popmean_rb: s_pop), Matrix form (device, caller order = the handle's for the blocks that have one): mean,
     const double* pri_ivar_e; // 1 / std^2; nullptr: the Vector form below
     double pri_mean, pri_ivar;
 };

@@ -35,6 +35,20 @@
 //        prior (a, 1 / b^2) added, theta_j, m_j, sd_j written where bb_block_rb writes them; then bb_rb_mixture.
 // The chunk map (group -> first chunk and sum of n_u, chunk -> group and first member, member -> mutant row r nb + m and n_u) is built
 // on the host (bb_analysis.h); the order of every sum is the map's, not the grid's.
+//
+// Entry point bb_popmean_rb: the same for the population mean fitness sbar_g of a group g = (r, k), replicate r and step k, whose
+// conditional sums over every barcode of the replicate: members i < nn the neutral terms, i >= nn the mutants at step k.  No
+// bb_block_ppc_pop (the conditional does not read sbar; its own draws are read from the latent); after the normalisers and
+// bb_block_rb_logz:
+//   bb_block_pop_part   : one workgroup of BB_SCORE_NT threads per (group, chunk of BB_POP_CHUNK consecutive members),
+//        work += nblocks.  Per draw it walks the chunk's members in index order, (SP, SN) in registers: a member's two loglambda
+//        draws of step t and the step's ln Z give gamma; neutral: cP = w, cN = -(w gamma), w = exp(-2 logsigmabar_{g,j}) from the
+//        latent's draw; mutant: its bb_fitness_rb unit u of environment env_r(k + 1), cP = w_u, cN = w_u (s_u - gamma).  A neutral
+//        member is data column i at step k, or under the ragged method's pairing (quirk) the (t, b) the host's table names.
+//        The simple form: a loglambda entry is drawn by both groups whose step it bounds (per-step accumulators of one walk over
+//        the row would be indexed at run time: scratch memory).
+//   bb_block_pop        : one workgroup per group.  Per draw the chunk partials from 0.0 in chunk order (bb_rb_chunk_sum, shared
+//        with bb_block_theta), the prior (a, 1 / b^2) of s_pop[g] added, sbar_j the latent's draw; then bb_rb_mixture.
 #pragma once
 #include "bb_freq.h"
 #include "bb_score.h"
@@ -79,6 +93,18 @@ struct ThetaArgs {
     double* part;             // [c1 - c0][2][n_samples] chunk partials (SP, SN) of the groups in flight
     long long g0, g1;         // the groups in flight
     int c0, c1;               // ... and their chunks: grp_c0[g0], grp_c0[g1]
+};
+
+#define BB_POP_CHUNK 256                    // == BB_POPMEAN_RB_CHUNK of include/barbay_hip.h: members per partial sum of a group
+
+struct PopArgs {
+    RbArgs A;                 // as for bb_block_rb; unit [BB_RB_OUT][n_groups], quant [n_groups][8], n_units = n_groups = F.P.nt1, ytab [gridDim][n_samples]:
+                              // sbar_j of the group being worked; A.F.P.pri_*: the prior of sbar (s_pop_prior), indexed by g
+    const int* neu_t;         // [n_groups][nn] ragged-method pairing: neutral member i of group g -> its step t and data column b;
+    const int* neu_b;         // nullptr: t = k, b = i
+    double* part;             // [(g1 - g0) nchunks][2][n_samples] chunk partials (SP, SN) of the groups in flight
+    long long g0, g1;         // the groups in flight
+    int nchunks;              // chunks of a group: ceil((nn + nb) / BB_POP_CHUNK), the same for every group
 };
 
 // the normalisers F.Z[Ttot][n_samples] replaced by their logarithms, once per call: every mutant row of a replicate reads the same ones
@@ -311,6 +337,16 @@ BB_DEV void bb_block_theta_part(BBCtx& cx, const ThetaArgs& H, int nblocks) {
     }
 }
 
+// a group's (SP, SN) of draw j: its nc chunk partials part[c][2][ns], from 0.0 in chunk order
+BB_DEV void bb_rb_chunk_sum(const double* part, int nc, int ns, int j, double& SP, double& SN) {
+    SP = 0.0;
+    SN = 0.0;
+    for (int c = 0; c < nc; ++c) {
+        SP += part[(long long)c * 2 * ns + j];
+        SN += part[((long long)c * 2 + 1) * ns + j];
+    }
+}
+
 BB_DEV void bb_block_theta(BBCtx& cx, const ThetaArgs& H, int nblocks) {
     const RbArgs& A = H.A;
     const PpcArgs& P = A.F.P;
@@ -324,12 +360,8 @@ BB_DEV void bb_block_theta(BBCtx& cx, const ThetaArgs& H, int nblocks) {
         const int c0 = H.grp_c0[g], c1 = H.grp_c0[g + 1], nst = H.grp_nst[g];
         const double a = P.pri_mean_e ? P.pri_mean_e[g] : P.pri_mean, ib2 = P.pri_ivar_e ? P.pri_ivar_e[g] : P.pri_ivar;
         bb_rb_mixture(cx, ns, A.nq, A.probs, A.threshold, sj, mj, sdj, red, st, A.unit, A.n_units, g, A.quant, [&](int j, double& s, double& mm, double& sd) {
-            double SP = 0.0, SN = 0.0;
-            for (int c = c0; c < c1; ++c) {
-                const double* part = H.part + (long long)(c - H.c0) * 2 * ns;
-                SP += part[j];
-                SN += part[ns + j];
-            }
+            double SP, SN;
+            bb_rb_chunk_sum(H.part + (long long)(c0 - H.c0) * 2 * ns, c1 - c0, ns, j, SP, SN);
             if (nst == 0) {                  // no contributing member: the conditional is the prior
                 mm = a;
                 sd = 1.0 / sqrt(ib2);
@@ -339,6 +371,83 @@ BB_DEV void bb_block_theta(BBCtx& cx, const ThetaArgs& H, int nblocks) {
                 sd = 1.0 / sqrt(Pj);
             }
             s = bb_ppc_param(P, P.lo_s + g, j);
+        });
+    }
+}
+
+BB_DEV void bb_block_pop_part(BBCtx& cx, const PopArgs& H, int nblocks) {
+    const FreqArgs& F = H.A.F;
+    const PpcArgs& P = F.P;
+    const int ns = P.n_samples, E = P.E;
+    const bool hier = P.kind >= 2, menv = P.kind == 1 || P.kind == 4;
+    const long long nn = F.nn, nmem = F.nn + P.nb, nwork = (H.g1 - H.g0) * H.nchunks;
+    for (long long wk = cx.block; wk < nwork; wk += nblocks) {
+        const long long g = H.g0 + wk / H.nchunks;
+        const int c = (int)(wk % H.nchunks);
+        int r = 0;
+        while (r + 1 < P.R && g >= P.off_t[r + 1]) ++r;
+        const int k = (int)(g - P.off_t[r]), T = P.T[r];
+        const int e = menv ? P.env_idx[P.tcum[r] + k + 1] : 0;
+        const long long i0 = (long long)c * BB_POP_CHUNK, i1 = i0 + BB_POP_CHUNK < nmem ? i0 + BB_POP_CHUNK : nmem;
+        const double* Z = F.Z + (long long)P.tcum[r] * ns;      // ln Z (bb_block_rb_logz)
+        double* part = H.part + wk * 2 * ns;
+        BB_PASS(cx, tid) {
+            for (int j = tid; j < ns; j += BB_SCORE_NT) {
+                double SP = 0.0, SN = 0.0;
+                const double wn = i0 < nn ? exp(-2.0 * bb_ppc_param(P, P.lo_lspop + g, j)) : 0.0;
+                for (long long i = i0; i < i1; ++i) {
+                    int t = k;
+                    long long b = i;
+                    if (i < nn && H.neu_t) { t = H.neu_t[g * nn + i]; b = H.neu_b[g * nn + i]; }
+                    const long long ll = F.off_l[r] + b * T + t;
+                    const double l0 = bb_ppc_param(P, ll, j), l1 = bb_ppc_param(P, ll + 1, j);
+                    const double gam = (l1 - l0) - (Z[(long long)(t + 1) * ns + j] - Z[(long long)t * ns + j]);
+                    if (i < nn) {
+                        SP += wn;
+                        SN += -(wn * gam);
+                    } else {
+                        const long long m = i - nn, em = e + (long long)E * m, u = em + (long long)E * P.nb * r;
+                        double s, ls;
+                        if (!hier) {
+                            s = bb_ppc_param(P, P.lo_s + em, j);
+                            ls = bb_ppc_param(P, P.lo_ls + em, j);
+                        } else {
+                            const long long th = P.kind == 2 ? P.geno_idx[m] : em, uu = P.kind == 2 ? m : u;
+                            const double tau = exp(bb_ppc_param(P, P.lo_lt + uu, j));
+                            s = bb_ppc_param(P, P.lo_s + th, j) + tau * bb_ppc_param(P, P.lo_tt + uu, j);
+                            ls = bb_ppc_param(P, P.lo_ls + uu, j);
+                        }
+                        const double w = exp(-2.0 * ls);
+                        SP += w;
+                        SN += w * (s - gam);
+                    }
+                }
+                part[j] = SP;
+                part[ns + j] = SN;
+            }
+        }
+    }
+}
+
+BB_DEV void bb_block_pop(BBCtx& cx, const PopArgs& H, int nblocks) {
+    const RbArgs& A = H.A;
+    const PpcArgs& P = A.F.P;
+    const int ns = P.n_samples;
+    double* mj = cx.lds;
+    double* sdj = cx.lds + ns;
+    double* red = cx.lds + 2 * (long long)ns;
+    double* st = red + 3 * BB_SCORE_NT;
+    double* sj = A.ytab + (long long)cx.block * ns;
+    for (long long g = H.g0 + cx.block; g < H.g1; g += nblocks) {
+        const double* part = H.part + (g - H.g0) * H.nchunks * 2 * ns;
+        const double a = P.pri_mean_e ? P.pri_mean_e[g] : P.pri_mean, ib2 = P.pri_ivar_e ? P.pri_ivar_e[g] : P.pri_ivar;
+        bb_rb_mixture(cx, ns, A.nq, A.probs, A.threshold, sj, mj, sdj, red, st, A.unit, A.n_units, g, A.quant, [&](int j, double& s, double& mm, double& sd) {
+            double SP, SN;
+            bb_rb_chunk_sum(part, H.nchunks, ns, j, SP, SN);
+            const double Pj = ib2 + SP;
+            mm = (a * ib2 + SN) / Pj;
+            sd = 1.0 / sqrt(Pj);
+            s = bb_ppc_param(P, P.lo_spop + g, j);
         });
     }
 }

@@ -24,6 +24,8 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
     hyperfitness_marginals                                        the same for the hyper-fitness theta of the hierarchical models -- a
                                                                   genotype's fitness, a mutant's across its replicates -- whose
                                                                   conditional sums over the group's members (`bb_theta_rb`)
+    popmean_marginals                                             the same for the population mean fitness of every time step, whose
+                                                                  conditional sums over every barcode of the replicate (`bb_popmean_rb`)
 """
 from __future__ import annotations
 
@@ -512,6 +514,48 @@ def hyperfitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, 
     for i, p in enumerate(probs):
         out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
     return pd.DataFrame(out)
+
+
+def popmean_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                      n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
+                      id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                      rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                      device: int = 0, chain=None) -> pd.DataFrame:
+    """`fitness_marginals` for the population mean fitness -- the `pop_mean_fitness` rows of the fit's frame, the quantity every
+    mutant's fitness is relative to and the one latent every barcode's log-frequency-ratio term reads.  q factorises it away from
+    all of them; given everything else its full conditional is exactly Gaussian in every model (the prior and the terms of every
+    barcode of the replicate at the step, neutrals and mutants), and averaging it over n_samples joint draws of everything else
+    gives the Rao-Blackwellised marginal (`bb_popmean_rb`, one device call).  Arguments as for `fitness_marginals`.
+
+    Returns one line per `pop_mean_fitness` row of the frame, in that order and with those rows' own labels (every column of the
+    frame but `mean` and `std`); then `n_members` (neutrals + mutants), `q_mean`, `q_sd`, `rb_mean`, `rb_sd`, `sd_ratio`, `p_pos`,
+    `p_neg` and one column per probability of `probs`, as `hyperfitness_marginals`."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        n_groups = e.popmean_rb_shape()
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        blk = df_advi.iloc[:e.D]
+        blk = blk[blk["vartype"] == "pop_mean_fitness"]
+        if len(blk) != n_groups:
+            raise BarBayError(f"df_advi holds {len(blk)} pop_mean_fitness rows, the model has {n_groups}")
+        res = e.popmean_rb(n_samples=n_samples, probs=probs, threshold=threshold, seed=seed, draws=draws)
+    out = blk.drop(columns=["mean", "std"]).reset_index(drop=True)
+    out["n_members"] = res["n_members"]
+    for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"] / res["q_sd"]
+    out["p_pos"], out["p_neg"] = res["p_pos"], res["p_neg"]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
+    return out
 
 
 def pit_histogram(scores: pd.DataFrame, bins: int = 10) -> pd.DataFrame:

@@ -495,8 +495,9 @@ int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
  * 0 .. 8; probs null with n_quantiles > 0; a prob outside (0, 1) or NaN; a non-finite threshold.  BB_ERR_UNSUPPORTED: n_samples
  * outside its range.  Multi-device and sharded handles: as bb_ppc_bands (the first device works on the gathered posterior; a shard
  * needs bb_set_params first).
- * The conditional of theta, the hyper-fitness of the hierarchical kinds: bb_theta_rb, below.  Out of scope: the conditionals of
- * sbar_t, tau and logsigma; any change to what the fit or an MCMC run report by default. */
+ * The conditional of theta, the hyper-fitness of the hierarchical kinds: bb_theta_rb, below; that of the population mean fitness
+ * sbar_t: bb_popmean_rb, below that.  Out of scope: the conditionals of tau and logsigma; any change to what the fit or an MCMC
+ * run report by default. */
 #define BB_RB_MAX_SAMPLES 8672
 typedef struct bb_rb_opts {
     int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
@@ -559,7 +560,7 @@ int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out);
  * BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb; BB_ERR_UNSUPPORTED, the message naming the model kind, for
  * BB_MODEL_FITNESS / BB_MODEL_MULTIENV.  The chunk partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB
  * (the groups are worked in slabs; a single group is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditionals of sbar_t, tau and logsigma. */
+ * Out of scope: the conditionals of tau and logsigma. */
 #define BB_THETA_RB_CHUNK 64
 typedef struct bb_theta_rb_out {  /* every pointer may be NULL; [n_groups] unless noted */
     double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
@@ -569,6 +570,61 @@ typedef struct bb_theta_rb_out {  /* every pointer may be NULL; [n_groups] unles
 } bb_theta_rb_out;
 int bb_theta_rb_shape(const bb_handle* h, int64_t* n_groups);
 int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out);
+
+/* Rao-Blackwellised marginals of the population mean fitness sbar_t -- the pop_mean_fitness rows of a fit, the quantity every
+ * reported mutant fitness is relative to, and the one latent that every barcode's log-frequency-ratio term reads: q factorises it
+ * away from all of them.  No reference counterpart.  sbar_g enters the log-joint through its Gaussian prior (s_pop_prior, Vector or
+ * Matrix form) and, linearly, through the Gaussian log-frequency-ratio terms of every barcode of its replicate at its step, so its
+ * full conditional given everything else is N(m, sd) in closed form in all five model kinds, and bb_fitness_rb's averaging over
+ * joint draws applies as it stands.
+ *
+ * Groups (bb_popmean_rb_shape: n_groups = the length of the caller's s_pop block; every model kind has groups): g = (r, k),
+ * replicate r and step k < T_r - 1, numbered in the order of that block: replicate-major, k ascending.
+ *
+ * Members of a group, i = 0 .. n_neutral + n_bc - 1 (n_members; the same for every group):
+ *   i < n_neutral   a neutral term.  Without BB_FLAG_RAGGED_METHOD: the neutral data column b = i at step t = k.  With the flag
+ *          (BB_MODEL_REPLICATE only): the neutral data element x = k n_neutral + i of the replicate's time-fastest vector, that
+ *          is t = x mod (T_r - 1), b = x div (T_r - 1) -- the reference's `repeat(.., inner=n_neutral)` pairing
+ *          (model_fitness_normal_hierarchical_replicates.jl:599-605), the one a flagged handle's fit evaluates.
+ *   i >= n_neutral  mutant m = i - n_neutral, in the caller's order, at step t = k.
+ *
+ * Per draw j and member, with gamma_{t,b,j} = (ll_{r,t+1,b,j} - ll_{r,t,b,j}) - (ln Z_{r,t+1,j} - ln Z_{r,t,j}) exactly
+ * bb_fitness_rb's (the same ln Z by the 256-column rule, the same draws):
+ *   neutral term:  w = exp(-2 logsigmabar_{g,j}), the draw of the group's logsigma_pop latent through the platform exp (not the
+ *          clamped table of bb_ppc_bands);  cP = w;  cN = -(w gamma)
+ *   mutant term, u the mutant's bb_fitness_rb unit for environment env_r(k + 1):  s_{u,j} the unit's fitness draw (the s_bc draw,
+ *          or theta_j + exp(logtau_j) theta_tilde_j: bb_fitness_rb's s_j word for word);  w = exp(-2 logsigma_{u,j});  cP = w;
+ *          cN = w (s_{u,j} - gamma)
+ * Order of the sums: the members are cut into chunks of BB_POPMEAN_RB_CHUNK consecutive member indices; a chunk's (SP, SN) start at
+ * 0.0 and take their members' (cP, cN) in index order (every member adds its own cP: the neutral w is not multiplied by a count);
+ * the group's (SP_j, SN_j) start at 0.0 and take the chunks in chunk order.  No atomics on doubles.
+ * Conditional, with (a, 1 / b^2) the s_pop_prior element of the group as the handle holds it (the same for every draw):
+ *   P_j = 1 / b^2 + SP_j;   m_j = (a / b^2 + SN_j) / P_j;   sd_j = 1 / sqrt(P_j)
+ * The conditional does not read sbar_g itself.  The identity all this rests on, at any point z:  P (m - sbar_g) = dlogp/dsbar_g.
+ *
+ * Outputs per group (every pointer may be NULL):
+ *   n_members  n_neutral + n_bc
+ *   q_mean, q_sd     mean and sd of the group's own sbar draws over j, as bb_fitness_rb's of s_j
+ *   rb_mean, rb_sd, p_pos, p_neg, quantiles    from (m_j, sd_j) by bb_fitness_rb's formulas word for word, the 64-step bisection,
+ *              its bracket and its NaN rule included.
+ * Non-finite parameters propagate by IEEE rules into the groups that use them; they disturb no other group and are not an error.
+ *
+ * The options are bb_fitness_rb's, with the same meaning and limits (draws, seed and keying included; BB_RB_MAX_SAMPLES because a
+ * group's (m_j, sd_j) live in LDS as a unit's do).  A group's results are a function of the handle's (mu, sigma) (or the supplied
+ * draws), the s_pop prior, n_samples, seed, threshold and probs: bit-identical whatever the grid, the launch mode, the handle's
+ * internal latent order, the device count or the calls made before.  The handle's mu, omega, optimiser state, step counter and
+ * RNG position are untouched, bitwise.  BB_ERR_INVALID / BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb.  The chunk
+ * partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB (the groups are worked in slabs; a single group
+ * is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
+ * Out of scope: the conditionals of tau and logsigma. */
+#define BB_POPMEAN_RB_CHUNK 256
+typedef struct bb_popmean_rb_out {   /* every pointer may be NULL; [n_groups] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
+    double* quantiles;               /* [n_groups][n_quantiles]                        */
+    int32_t* n_members;              /* n_neutral + n_bc                               */
+} bb_popmean_rb_out;
+int bb_popmean_rb_shape(const bb_handle* h, int64_t* n_groups);
+int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean_rb_out* out);
 
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array

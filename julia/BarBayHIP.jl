@@ -419,6 +419,60 @@ function theta_rb(h::Ptr{Cvoid}; n_samples::Int=1000, probs::Vector{Float64}=[0.
             quantiles=quantiles)
 end
 
+# Rao-Blackwellised marginals of the population mean fitness sbar_g, g = (replicate, step) (bb_popmean_rb, include/barbay_hip.h):
+# the exact Gaussian full conditional of a step's population mean, summed over every barcode of the replicate (neutrals, then
+# mutants) and averaged over the draws of `fitness_rb`.  Field for field the Python binding's `bb_popmean_rb_out`
+# (barbay.jl_amd/_capi.py); the options are `bb_rb_opts`.  Like the rest of this file it remains unexecuted.
+const BB_POPMEAN_RB_CHUNK = 256
+struct bb_popmean_rb_out
+    q_mean::Ptr{Float64}
+    q_sd::Ptr{Float64}
+    rb_mean::Ptr{Float64}
+    rb_sd::Ptr{Float64}
+    p_pos::Ptr{Float64}
+    p_neg::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    n_members::Ptr{Int32}
+end
+
+"""
+    popmean_rb_shape(h) -> Int
+
+Groups of `popmean_rb`: the length of the s_pop block, g = (replicate, step), replicate-major.
+"""
+function popmean_rb_shape(h::Ptr{Cvoid})
+    n = Ref{Int64}(0)
+    check(ccall((:bb_popmean_rb_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), h, n))
+    return Int(n[])
+end
+
+"""
+    popmean_rb(h; n_samples=1000, probs=[0.025, 0.5, 0.975], threshold=0.0, seed=0, draws=nothing) -> NamedTuple
+
+`h` a live `bb_handle` of any model.  Returns `n_members, q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg` (n_groups each) and
+`quantiles` (length(probs) x n_groups).  Arguments as for `fitness_rb`.
+"""
+function popmean_rb(h::Ptr{Cvoid}; n_samples::Int=1000, probs::Vector{Float64}=[0.025, 0.5, 0.975], threshold::Real=0.0,
+                    seed::Integer=0, draws::Union{Nothing,Matrix{Float64}}=nothing)
+    ng, nq = popmean_rb_shape(h), length(probs)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("popmean_rb: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg = (Vector{Float64}(undef, ng) for _ in 1:6)
+    quantiles = Matrix{Float64}(undef, nq, ng)
+    n_members = Vector{Int32}(undef, ng)
+    GC.@preserve probs draws q_mean q_sd rb_mean rb_sd p_pos p_neg quantiles n_members begin
+        o = bb_rb_opts(Int32(n_samples), Int32(nq), nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL), Float64(threshold), UInt64(seed),
+                       draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws))
+        out = bb_popmean_rb_out(pointer(q_mean), pointer(q_sd), pointer(rb_mean), pointer(rb_sd), pointer(p_pos), pointer(p_neg),
+                                nq > 0 ? pointer(quantiles) : Ptr{Float64}(C_NULL), pointer(n_members))
+        check(ccall((:bb_popmean_rb, LIB), Cint, (Ptr{Cvoid}, Ref{bb_rb_opts}, Ref{bb_popmean_rb_out}), h, o, out))
+    end
+    return (n_members=n_members, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, p_pos=p_pos, p_neg=p_neg, quantiles=quantiles)
+end
+
 # Log-joint and gradient at several points in one call (bb_logdensity_grad_batch, include/barbay_hip.h): what a sampler that
 # steps an ensemble of walkers in lock-step asks of the model (`LogDensityProblems.logdensity_and_gradient`, W points at once).
 const BB_LOGP_MAX_BATCH = 64
