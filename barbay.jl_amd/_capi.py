@@ -37,7 +37,7 @@ BB_ERR_NONFINITE = -5
 EXPORTS = [
     "bb_version", "bb_last_error", "bb_default_opts", "bb_create", "bb_destroy", "bb_num_latents",
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
-    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
+    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
@@ -88,6 +88,7 @@ class bb_stats(C.Structure):
         ("geno_lo", C.c_int32), ("geno_hi", C.c_int32),
         ("device_bytes", C.c_int64), ("window_row", C.c_int64),
         ("rows_same_xcd", C.c_int32), ("reserved0", C.c_int32),
+        ("opt_compiled", C.c_int32), ("reserved1", C.c_int32),
     ]
 
 
@@ -220,6 +221,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_kernel_name"):          # (A/B builds of older sources, tools/xp.py)
         lib.bb_kernel_name.argtypes = [vp, C.c_char_p, C.c_int64]
     lib.bb_debug_stamps.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64]
+    if hasattr(lib, "bb_debug_opt_state"):      # (A/B builds of older sources, tools/xp.py)
+        lib.bb_debug_opt_state.argtypes = [vp, _dp, _dp, C.POINTER(C.c_float)]
     lib.bb_debug_graph_launches.argtypes = [vp]
     lib.bb_comm_make_id.argtypes = [C.c_void_p]
     lib.bb_comm_init.argtypes = [vp, C.c_void_p]
@@ -503,6 +506,13 @@ class Engine:
         buf = C.create_string_buffer(128)
         self._check(self._lib.bb_kernel_name(self._h, buf, 128))
         return buf.value.decode()
+
+    def opt_state(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Test hook (`bb_debug_opt_state`): the optimiser's accumulators of mu and omega [D] and the low-order parts of the compensated
+        window sums [D, 2] (float32), in the handle's internal latent order."""
+        am, ao, lo = np.empty(self.D), np.empty(self.D), np.empty((self.D, 2), dtype=np.float32)
+        self._check(self._lib.bb_debug_opt_state(self._h, _ptr(am), _ptr(ao), lo.ctypes.data_as(C.POINTER(C.c_float))))
+        return am, ao, lo
 
     def logdensity_grad(self, z) -> Tuple[float, np.ndarray]:
         """log p(data, z) and its gradient at a point of the flat latent vector (`bb_logdensity_grad`)."""

@@ -369,20 +369,26 @@ BB_DEV int bb_uniform(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 #endif
 }
+// OS (the resident kernels' specialised instances, bb_opt_apply): the launch runs TruncatedADAGrad with resum_every == 0, known at
+// compile time -- the counters carry the window slot and nothing else.
+template <bool OS = false>
 BB_DEV BBSlotCtr bb_slot_init(const RunArgs& A, unsigned long long step) {
     BBSlotCtr c;
-    c.slot = A.opt == 0 ? bb_uniform((int)(step % (unsigned long long)A.W)) : 0;
-    c.rs = (A.opt == 0 && A.resum_every > 1) ? bb_uniform((int)(step % (unsigned long long)A.resum_every)) : 0;
-    c.past0 = bb_uniform(step > 0 ? 1 : 0) != 0;
+    c.slot = (OS || A.opt == 0) ? bb_uniform((int)(step % (unsigned long long)A.W)) : 0;
+    c.rs = (!OS && A.opt == 0 && A.resum_every > 1) ? bb_uniform((int)(step % (unsigned long long)A.resum_every)) : 0;
+    c.past0 = OS || bb_uniform(step > 0 ? 1 : 0) != 0;
     return c;
 }
+template <bool OS = false>
 BB_DEV BBSlot bb_slot_now(const RunArgs& A, const BBSlotCtr& c) {
     BBSlot w;
     w.slot = c.slot;
-    w.resum = A.opt == 0 && (A.resum_every == 1 || (A.resum_every > 1 && c.past0 && c.rs == 0));
+    w.resum = !OS && A.opt == 0 && (A.resum_every == 1 || (A.resum_every > 1 && c.past0 && c.rs == 0));
     return w;
 }
+template <bool OS = false>
 BB_DEV void bb_slot_next(const RunArgs& A, BBSlotCtr& c) {
+    if (OS) { c.slot = c.slot + 1 == A.W ? 0 : c.slot + 1; return; }
     if (A.opt == 0) { c.slot = c.slot + 1 == A.W ? 0 : c.slot + 1; if (A.resum_every > 1) c.rs = c.rs + 1 == A.resum_every ? 0 : c.rs + 1; }
     c.past0 = true;
 }
@@ -407,11 +413,24 @@ BB_DEV void bb_two_sum(double a, double b, double* s, double* e) {
     *s = t;
     *e = (a - (t - bb)) + (b - bb);
 }
+// OPT, RESUM: the optimiser and the re-add schedule where the caller knows them at compile time -- both are fixed for a whole launch, and
+// the resident kernels' default configuration (TruncatedADAGrad, resum_every == 0) is compiled without the other arms: <0, 0> is the
+// compensated running sum and nothing else, no flags to test, no arms to join, the root without branches (bb_sqrt_nonneg).  -1: read
+// A.opt / w.resum.  The arithmetic of the arm taken is the same statements either way, and the same bits.
+template <int OPT = -1, int RESUM = -1>
 BB_DEV void bb_opt_apply(const DevModel& M, const DevState& S, const RunArgs& A, const BBSlot w,
                          int which, long long ih /* the latent's entry in a window row */, double d, double old_slot, double* new_slot, double* p, double* acc, float* lo) {
     double upd;
-    if (A.opt == 0) {   // TruncatedADAGrad: g2[mod(i-1,n)+1] = d^2; s = sum(g2); d *= eta / (tau + sqrt(s))
-        const double n2 = d * d;
+    if (OPT < 0 ? A.opt == 0 : OPT == 0) {   // TruncatedADAGrad: g2[mod(i-1,n)+1] = d^2; s = sum(g2); d *= eta / (tau + sqrt(s))
+        // (d^2 is rounded on its own, as it always was where the re-add branch stood between this multiply and the sums below: with
+        //  the branch compiled out the device compiler would otherwise contract it into acc + d^2 and d^2 - bb, other bits)
+        double n2;
+        {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+            n2 = d * d;
+        }
         *new_slot = n2;
         // Running sum acc + d^2 - (slot leaving the window).  A plain double leaves up to half an ulp of the CURRENT sum behind at
         // every step, and that residue stays while the sum itself falls by orders of magnitude (the first gradients are ~1e6
@@ -427,7 +446,7 @@ BB_DEV void bb_opt_apply(const DevModel& M, const DevState& S, const RunArgs& A,
         // profiles/window_sum_accuracy_10k.json).  A double lo would remove that (+4 VGPRs per pair slot of k_res, +16 B per latent
         // and step in k_stream); resum_every = k bounds it.  No re-adds, no divergence, no window traffic beyond the one slot.
         double s;
-        if (w.resum) {
+        if (RESUM < 0 ? w.resum : RESUM != 0) {
             s = 0.0;
             for (int j = 0; j < A.W; ++j) s += (j == w.slot) ? n2 : S.hist[((long long)j * 2 + which) * M.Dh + ih];
             *lo = 0.f;
@@ -444,14 +463,14 @@ BB_DEV void bb_opt_apply(const DevModel& M, const DevState& S, const RunArgs& A,
         }
         *acc = s;
         bb_cdouble* oc = bb_tab(S.optc);
-        upd = d * (oc[0] * bb_rcp(oc[1] + bb_sqrt(s)));
+        upd = d * (oc[0] * bb_rcp(oc[1] + ((OPT == 0 && RESUM == 0) ? bb_sqrt_nonneg(s) : bb_sqrt(s))));
     } else {            // DecayedADAGrad: acc = post*acc + pre*d^2; d *= eta / (sqrt(acc) + 1e-8)
         bb_cdouble* oc = bb_tab(S.optc);
         const double a = oc[3] * (*acc) + oc[2] * d * d;
         *acc = a;
         upd = d * (oc[0] * bb_rcp(bb_sqrt(a) + 1e-8));
     }
-    *p -= upd;
+    *p -= upd;          // (one fma with the multiply that formed upd on the device, in either form)
 }
 
 // Finish one pair given the likelihood part of d logjoint / d z for its two latents: prior term,

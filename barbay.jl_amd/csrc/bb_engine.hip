@@ -68,7 +68,7 @@ extern "C" const char* bb_version(void) { return BB_BACKEND_VERSION; }
 struct BBTuning {
     bool no_hist_pack, no_host_tables, no_res, no_persist, no_stream, force_stream, any_parity, force_allreduce, p2p_self;
     bool no_graph, graph_collective, no_regroup, no_reorder, nb_set, lead_set;
-    int nb, res_nb, ng, lead, nthr, row_l2;
+    int nb, res_nb, ng, lead, nthr, row_l2, opt_spec;
 };
 
 static BBTuning read_tuning() {
@@ -98,6 +98,7 @@ static BBTuning read_tuning() {
     if (t.lead < 10 || t.lead > 100) t.lead = 100;
     t.nthr = num("BB_TUNE_NTHR", 0) >= 64 ? num("BB_TUNE_NTHR", 0) / 64 * 64 : 0;
     t.row_l2 = num("BB_TUNE_ROW_L2", 1) == 0 ? 0 : 1;   // (odd: any value that reads as 0, "off" too, turns it off)
+    t.opt_spec = num("BB_TUNE_OPT_SPEC", 1) == 0 ? 0 : 1;   // (likewise: 0 keeps the generic resident instances, A/B runs)
     return t;
 }
 
@@ -109,6 +110,7 @@ struct LaunchPlan {
     int NB = 0, NBL = 0, nblk = 0;     // its tile map: barcodes per tile, per leader tile (0: uniform), tiles (k_persist: the two-kernel map)
     int ng = 8, pf = 0;                // k_res / k_stream: groups of the exchange's first hop (RunArgs.ng), window slot fetch (RunArgs.pf: 0 or 1)
     bool ms = false;                   // several samples per step or the ELBO trace (the MS instances)
+    bool os = false;                   // k_res / k_stream: the instance has the optimiser compiled in (bb_stats.opt_compiled)
     const void* fn = nullptr;          // the resident kernel instance (none in the emulation)
     std::string name;                  // ... as bb_kernel_name reports it
     const char* why = nullptr;         // why no resident launch where one was wanted
@@ -304,7 +306,8 @@ static void emu_persist_phase(EmuPersist& E, int phase, long long it, long long 
     }
 }
 
-template <int KIND, int PP, bool AP>
+// (OS: the forms with the optimiser compiled in, where the plan chose them -- the same templates as the product's instances)
+template <int KIND, int PP, bool AP, bool OS = false>
 static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nsteps) {
     bb_handle* h = E.h;
     const RunArgs& A = E.A;
@@ -331,11 +334,11 @@ static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nste
             br_draw_ahead<KIND, PP, AP>(cx, A, Y, sb, (unsigned long long)h->step);
         } else if (phase == 1) {
             if (MSrun) br_sample<KIND, PP, true>(cx, h->M, h->S, A, Y, sb, buf, wslot.slot, last, want_el);
-            else br_sample<KIND, PP, false>(cx, h->M, h->S, A, Y, sb, buf, wslot.slot);
+            else br_sample<KIND, PP, false, false, OS>(cx, h->M, h->S, A, Y, sb, buf, wslot.slot);
             const unsigned epoch = A.xepoch0 + (unsigned)(xc + 1);
             if (MSrun) br_moments<KIND, PP, true>(cx, h->M, h->S, Y, sb, buf, epoch, want_el);
             else br_moments<KIND, PP, false>(cx, h->M, h->S, Y, sb, buf, epoch);
-            br_xchg_publish<KIND, PP, AP>(cx, h->M, h->S, A, Y, sb, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
+            br_xchg_publish<KIND, PP, AP, false, OS>(cx, h->M, h->S, A, Y, sb, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
         } else if (phase == 2) {
             if (xg) br_xchg_lead<true>(cx, h->M, h->S, A, Y, xc, &E.ok);
             else br_xchg_lead<false>(cx, h->M, h->S, A, Y, xc, &E.ok);
@@ -346,16 +349,16 @@ static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nste
             else br_xchg_consume<KIND, PP, false, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
             // (the compile-time-T forms of the G pass where the product has them, so that the emulation covers that code too)
             if (MSrun) br_update<KIND, PP, 0, AP, true>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB, smp, NS);
-            else if (!AP && uniform_T(h->M) == 8) br_update<KIND, PP, 8, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
-            else if (!AP && uniform_T(h->M) == 6) br_update<KIND, PP, 6, false>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
-            else br_update<KIND, PP, 0, AP>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
+            else if (!AP && uniform_T(h->M) == 8) br_update<KIND, PP, 8, false, false, false, OS>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
+            else if (!AP && uniform_T(h->M) == 6) br_update<KIND, PP, 6, false, false, false, OS>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
+            else br_update<KIND, PP, 0, AP, false, false, OS>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB);
         } else {
             br_epilogue<KIND, PP, AP>(cx, h->S, sb, (unsigned long long)(h->step + nsteps), E.ok == 0);
         }
     }
 }
 
-template <int KIND, int TT, bool MS>
+template <int KIND, int TT, bool MS, bool OS = false>
 static void emu_stream_phase(EmuPersist& E, int phase, long long it, long long nsteps) {
     bb_handle* h = E.h;
     const RunArgs& A = E.A;
@@ -388,8 +391,8 @@ static void emu_stream_phase(EmuPersist& E, int phase, long long it, long long n
             br_xchg_lead<false>(cx, h->M, h->S, A, Y, xc, &E.ok);
         } else if (phase == 3) {
             br_xchg_consume<KIND, 1, false, MS>(cx, h->M, h->S, A, Y, nost, xc, &E.ok, want_el, ring, smp);
-            bs_update_l<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
-            bs_update_u<KIND, TT, MS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
+            bs_update_l<KIND, TT, MS, OS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
+            bs_update_u<KIND, TT, MS, OS>(cx, h->M, h->S, A, Y, h->plan.NB, h->plan.P, (unsigned)step, bb_slot_of(A, step), bad_any, gb, ms);
         } else {
             if (*bad_any) h->S.hstatus[1] = 1u;
             if (b == 0) { h->S.ctr[0] = (unsigned long long)(h->step + nsteps); h->S.ctr[1] = h->S.ctr[0]; }
@@ -403,7 +406,12 @@ static void emu_persist_dispatch(EmuPersist& E, int phase, long long it, long lo
         const int T = uniform_T(E.h->M);
         auto byT = [&](auto kindc) {
             constexpr int KIND = decltype(kindc)::value;
-            if (T == 8) p.ms ? emu_stream_phase<KIND, 8, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 8, false>(E, phase, it, nsteps);
+            if (p.os) {          // (one-sample instances only: resident_instance)
+                if (T == 8) emu_stream_phase<KIND, 8, false, true>(E, phase, it, nsteps);
+                else if (T == 6) emu_stream_phase<KIND, 6, false, true>(E, phase, it, nsteps);
+                else emu_stream_phase<KIND, 4, false, true>(E, phase, it, nsteps);
+            }
+            else if (T == 8) p.ms ? emu_stream_phase<KIND, 8, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 8, false>(E, phase, it, nsteps);
             else if (T == 6) p.ms ? emu_stream_phase<KIND, 6, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 6, false>(E, phase, it, nsteps);
             else p.ms ? emu_stream_phase<KIND, 4, true>(E, phase, it, nsteps) : emu_stream_phase<KIND, 4, false>(E, phase, it, nsteps);
         };
@@ -414,7 +422,15 @@ static void emu_persist_dispatch(EmuPersist& E, int phase, long long it, long lo
         const bool ap = br_any_parity(E.h->M);
         auto byP = [&](auto kindc) {
             constexpr int KIND = decltype(kindc)::value;
-            switch (p.P) {
+            if (p.os) {          // (never MS: resident_instance)
+                switch (p.P) {
+                case 1: ap ? emu_res_phase<KIND, 1, true, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 1, false, true>(E, phase, it, nsteps); break;
+                case 2: ap ? emu_res_phase<KIND, 2, true, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 2, false, true>(E, phase, it, nsteps); break;
+                case 3: ap ? emu_res_phase<KIND, 3, true, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 3, false, true>(E, phase, it, nsteps); break;
+                default: ap ? emu_res_phase<KIND, 4, true, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 4, false, true>(E, phase, it, nsteps);
+                }
+            }
+            else switch (p.P) {
             case 1: ap ? emu_res_phase<KIND, 1, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 1, false>(E, phase, it, nsteps); break;
             case 2: ap ? emu_res_phase<KIND, 2, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 2, false>(E, phase, it, nsteps); break;
             case 3: ap ? emu_res_phase<KIND, 3, true>(E, phase, it, nsteps) : emu_res_phase<KIND, 3, false>(E, phase, it, nsteps); break;
@@ -844,6 +860,17 @@ extern "C" int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n) {
     return d2h(out, h->S.stamps, (size_t)std::min(n, have) * 8, h->stream);
 }
 
+// the optimiser's state as the device holds it (the handle's internal latent order, bb_get_permutation)
+extern "C" int bb_debug_opt_state(bb_handle* h, double* acc_mu, double* acc_omega, float* lo) {
+    if (!h || !acc_mu || !acc_omega || !lo) return bb_fail(BB_ERR_INVALID, "null argument");
+    BB_GROUP_UNSUPPORTED(h, "bb_debug_opt_state");
+    BB_ENTER(h);
+    int rc;
+    if ((rc = dsync(h->stream))) return rc;
+    if ((rc = d2h(acc_mu, h->S.acc_mu, (size_t)h->M.D * 8, h->stream)) || (rc = d2h(acc_omega, h->S.acc_om, (size_t)h->M.D * 8, h->stream))) return rc;
+    return d2h(lo, h->S.accl, (size_t)h->M.D * 2 * sizeof(float), h->stream);
+}
+
 extern "C" int bb_debug_graph_launches(bb_handle* h) {
     if (!h) return 0;
     if (!h->shards.empty()) return bb_debug_graph_launches(h->shards[0]);
@@ -978,6 +1005,7 @@ extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
             s->last_run_ms = std::max(s->last_run_ms, t.last_run_ms);
             s->persistent_pairs = std::min(s->persistent_pairs, t.persistent_pairs);
             s->resident_kernel = std::min(s->resident_kernel, t.resident_kernel);
+            s->opt_compiled = std::min(s->opt_compiled, t.opt_compiled);
         }
         s->shard_lo = 0;
         s->shard_hi = h->M.B;
@@ -1007,6 +1035,7 @@ extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
     s->persistent_pairs = h->plan.P;
     s->launches_last_run = h->launches_last_run;
     s->resident_kernel = h->plan.impl;
+    s->opt_compiled = h->plan.os ? 1 : 0;
     if (h->plan.impl >= IMPL_RES) {          // (k_res / k_stream: what the tiles of the last launch decided about their row stores)
         std::vector<int> sel((size_t)h->plan.nblk);
         int rc = d2h(sel.data(), h->S.xsel, sel.size() * sizeof(int), h->stream);

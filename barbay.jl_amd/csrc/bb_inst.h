@@ -22,4 +22,9 @@ BB_INST bb_res_kernel bb_res_instance_k4(int P, int nthr, bool xg, int T, bool a
 BB_INST bb_stream_kernel bb_stream_instance(int kind, int nthr, int T, const char** nm = nullptr);
 // ... their MS form (several MC samples per step and / or the ELBO trace): k_stream<KIND, NT, TT, true>, T = 8 or 6 (fitness model: 4 too)
 BB_INST bb_stream_kernel bb_stream_instance_ms(int kind, int nthr, int T, const char** nm = nullptr);
+// The optimiser compiled in (k_res<.., OS = true>, k_stream<.., false, OS = true>: TruncatedADAGrad with resum_every == 0, bb_opt_apply<0, 0>) for
+// the compile-time-T k_res instances and the one-sample k_stream instances; nullptr where the shape has none (the generic form then).
+// The names are the generic instances': the form is reported as bb_stats.opt_compiled.
+BB_INST bb_res_kernel bb_res_instance_os(int kind, int P, int nthr, bool xg, int T, const char** nm = nullptr);
+BB_INST bb_stream_kernel bb_stream_instance_os(int kind, int nthr, int T, const char** nm = nullptr);
 #endif

@@ -107,6 +107,15 @@ BB_DEV double bb_sqrt(double x) {
     }
     return bb_sqrt_normal(x);
 }
+// bb_sqrt for an argument known to be >= 0 (the optimiser's window sum), without the branches: the same steps on the same
+// numbers, the three cases as selects -- the bits of bb_sqrt for every x >= 0, 0, the subnormals and +inf included.  (In a
+// loop that every lane walks the divergent form costs exec-mask saves, branches and the copies where its arms join.)
+BB_DEV double bb_sqrt_nonneg(double x) {
+    const bool small = !(x >= 0x1.0p-900);
+    const double r = bb_sqrt_normal(small ? 0x1.0p256 * x : x);
+    const double v = small ? 0x1.0p-128 * r : r;
+    return x == 0.0 ? 0.0 : v;
+}
 
 // exp(x): k = rint(x log2 e), r = x - k ln2 (two-piece), degree-13 Taylor on |r| <= 0.347, ldexp.
 BB_DEV double bb_exp(double x) {

@@ -13,10 +13,16 @@ static int uniform_T(const DevModel& M) {
 // (xg: the cross-GPU instances) -- each with three bodies: the emulation runs the block programs as host functions, so it only names
 // the launch (the compile-time T / AP / MS are the product's); experiment builds (tools/xp.py) hold only the instances the C2 / C4
 // workloads use, in this one translation unit; the product looks the instance up in bb_inst_*.hip.
-static const void* resident_instance(const bb_handle* h, bool xg, bool stream, int P, bool ms, std::string& name) {
+// os: the instance has the optimiser compiled in (k_res / k_stream<.., OS = true>, bb_opt_apply<0, 0>) -- wanted where the handle runs
+// TruncatedADAGrad with resum_every == 0 and one sample per step without the ELBO trace (BB_TUNE_OPT_SPEC=0: never), chosen where the
+// shape has such an instance: the compile-time-T k_res instances, k_stream's; the emulation has both forms of every one-sample shape.
+static const void* resident_instance(const bb_handle* h, bool xg, bool stream, int P, bool ms, std::string& name, bool& os) {
     const int kind = h->M.kind, nthr = h->nthr, T = uniform_T(h->M);
     const bool ap = br_any_parity(h->M);
+    const bool want_os = h->tune.opt_spec != 0 && !ms && h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && h->o.resum_every == 0;
+    os = false;
 #if defined(BB_EMU)
+    os = want_os;
     char nm[64];
     if (stream) snprintf(nm, sizeof nm, "emu:k_stream<%d,%d,%d%s>", kind, nthr, T, ms ? ",true" : "");
     else snprintf(nm, sizeof nm, "emu:k_res<%d,%d,%d,%s,*,%s,%s>", kind, P, nthr, xg ? "true" : "false", ap ? "true" : "false", ms ? "true" : "false");
@@ -47,7 +53,9 @@ static const void* resident_instance(const bb_handle* h, bool xg, bool stream, i
 #else
     const char* nm = "";
     const void* k = nullptr;
-    if (stream) k = ms ? (const void*)bb_stream_instance_ms(kind, nthr, T, &nm) : (const void*)bb_stream_instance(kind, nthr, T, &nm);
+    if (want_os) k = stream ? (const void*)bb_stream_instance_os(kind, nthr, T, &nm) : (ap ? nullptr : (const void*)bb_res_instance_os(kind, P, nthr, xg, T, &nm));
+    if (k) os = true;
+    else if (stream) k = ms ? (const void*)bb_stream_instance_ms(kind, nthr, T, &nm) : (const void*)bb_stream_instance(kind, nthr, T, &nm);
     else switch (kind) {
         case 0: k = (const void*)bb_res_instance_k0(P, nthr, xg, T, ap, ms, &nm); break;
         case 1: k = (const void*)bb_res_instance_k1(P, nthr, xg, T, ap, ms, &nm); break;
@@ -276,7 +284,7 @@ static bool window_fetch_layout(const bb_handle* h, Planned& c) {
 
 // the kernel instance, whether its grid fits resident on the device, and the handle's buffers the tile map
 static bool instance_fits(const bb_handle* h, Planned& c) {
-    c.plan.fn = resident_instance(h, c.xg, c.plan.impl == IMPL_STREAM, c.plan.P, c.plan.ms, c.plan.name);
+    c.plan.fn = resident_instance(h, c.xg, c.plan.impl == IMPL_STREAM, c.plan.P, c.plan.ms, c.plan.name, c.plan.os);
     if (resident_fit(c.plan.fn, h->nthr, c.lds_doubles * 8, c.plan.nblk, h->cus)) return false;
     return c.plan.nblk <= h->tile_cap;       // (else: more tiles than the exchange, stamp, xsel and tile-table buffers hold)
 }

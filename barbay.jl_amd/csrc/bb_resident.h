@@ -682,7 +682,8 @@ BB_DEV void br_unit_sw(const double* lds, const BRLay& Y, int buf, int o, int th
 #else
 #define BR_HDELTA(HD, lds, Y, meta) ((HD) ? ((const BRSeg*)((lds) + (Y).seg))[(meta) >> 12].pad : 0)
 #endif
-template <int P, bool HD = false>
+// (OS, here and below: the launch's optimiser is TruncatedADAGrad with resum_every == 0 at compile time -- bb_opt_apply<0, 0>)
+template <int P, bool HD = false, bool OS = false>
 BB_DEV void br_prefetch_slot(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv, int slot);
 template <int KIND, int P> BB_DEV void br_pair_prior(const double* lds, const BRLay& Y, const BRSt<P>& st, int k, bool a0, bool a1, double* pm0, double* iv0, double* pm1, double* iv1);
 // MS (instances that take several MC samples per step and record the ELBO): want_el -- this sample's ELBO terms are gathered
@@ -690,13 +691,13 @@ template <int KIND, int P> BB_DEV void br_pair_prior(const double* lds, const BR
 //   per (b, t)      R z - lambda                                  (Poisson; bb_pass_moments)
 //   per unit        - logsigma_eff x (time steps that use it)      (normaliser of the fitness likelihood; bb_effective_tables)
 // into BRSt.el; br_moments sums them over the tile (row entry K - 2), br_finish adds the per-time terms and stores the estimate.
-template <int KIND, int P, bool MS = false, bool HD = false>
+template <int KIND, int P, bool MS = false, bool HD = false, bool OS = false>
 BB_DEV void br_sample(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv, int buf, int slot, bool prefetch = true, bool want_el = false) {
     double* lds = cx.lds;
     const BBLds& L = Y.L;
     BB_STAMP(cx, S, 20);
     BB_STAMP_WAVE(cx, S, A, 1);
-    if (A.pf == 1 && prefetch) br_prefetch_slot<P, HD>(cx, M, S, A, Y, stv, slot);
+    if (A.pf == 1 && prefetch) br_prefetch_slot<P, HD, OS>(cx, M, S, A, Y, stv, slot);
     BB_PASS(cx, tid) {
         BRSt<P>& st = BB_PSTATE(stv, tid);
 #pragma unroll
@@ -967,9 +968,9 @@ BB_DEV void br_moments(BBCtx& cx, const DevModel& M, const DevState& S, const BR
 // ---- window-slot prefetch (in the exchange's shadow): LDS-DMA, 16 bytes per lane straight into LDS, no register held across the
 // exchange.  Every pair slot fetches both halves of its 16-byte pair (the row is padded: an edge pair's outside half is a
 // neighbour's or the padding, never used). --------------------------------------------------------------------------------------
-template <int P, bool HD>
+template <int P, bool HD, bool OS>
 BB_DEV void br_prefetch_slot(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv, int slot) {
-    if (A.opt != 0) return;
+    if (!OS && A.opt != 0) return;
     BB_PASS(cx, tid) {
         BRSt<P>& st = BB_PSTATE(stv, tid);
 #pragma unroll
@@ -1233,7 +1234,7 @@ BB_DEV void br_l_grad(const double* lds, const BRLay& Y, const BRSt<P>& st, int 
 // for the loglambda waves and the whole tile waited for them).
 // MS instances, NS > 1 MC samples per step (AdvancedVI's ELBO estimator, Turing.ADVI(samples_per_step, ..), src/vi.jl:98): sample smp's
 // gradient joins running sums; the last sample averages them, adds the entropy term and updates -- the arithmetic of bb_update_pair.
-template <int KIND, int P, int TT = 0, bool AP = false, bool MS = false, bool HD = false>
+template <int KIND, int P, int TT = 0, bool AP = false, bool MS = false, bool HD = false, bool OS = false>
 BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv,
                       const BBSlot wslot, int buf, int NBs, int smp = 0, int NS = 1) {
     double* lds = cx.lds;
@@ -1259,7 +1260,7 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
         BRSt<P>& st = BB_PSTATE(stv, tid);
         double* hs_m = nullptr;
         double* hs_o = nullptr;
-        if (A.opt == 0) {
+        if (OS || A.opt == 0) {
             hs_m = S.hist + ((long long)wslot.slot * 2 + 0) * M.Dh;
             hs_o = S.hist + ((long long)wslot.slot * 2 + 1) * M.Dh;
         }
@@ -1378,7 +1379,7 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
                 go0 = go0 * invS + st.h[k].x; go1 = go1 * invS + st.h[k].y;
             } else { go0 = fma(g0, st.a[k].x, st.h[k].x); go1 = fma(g1, st.a[k].y, st.h[k].y); }
             bb_d2 hm{0, 0}, ho{0, 0};
-            if (hs_m) {
+            if (OS || hs_m) {
 #ifndef BB_EMU
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's LDS-DMA of the window slot has landed (br_prefetch_slot)
 #endif
@@ -1386,20 +1387,21 @@ BB_DEV void br_update(BBCtx& cx, const DevModel& M, const DevState& S, const Run
                 ho = ((const bb_d2*)(lds + Y.hbuf))[(k * 2 + 1) * cx.nthr + tid];
             }
             bb_d2 nhm = hm, nho = ho;
+            constexpr int OSK = OS ? 0 : -1;
             const long long ih = st.i0[k] - BR_HDELTA(HD, lds, Y, meta);          // the pair's entry in a row of the window
             if (a0) {
-                bb_opt_apply(M, S, A, wslot, 0, ih, -g0, hm.x, &nhm.x, &st.mu[k].x, &st.am[k].x, &st.lo[k].x);
+                bb_opt_apply<OSK, OSK>(M, S, A, wslot, 0, ih, -g0, hm.x, &nhm.x, &st.mu[k].x, &st.am[k].x, &st.lo[k].x);
                 BR_SCHED_FENCE();
-                bb_opt_apply(M, S, A, wslot, 1, ih, -go0, ho.x, &nho.x, &st.om[k].x, &st.ao[k].x, &st.lo[k].y);
+                bb_opt_apply<OSK, OSK>(M, S, A, wslot, 1, ih, -go0, ho.x, &nho.x, &st.om[k].x, &st.ao[k].x, &st.lo[k].y);
                 BR_SCHED_FENCE();
             }
             if (a1) {
-                bb_opt_apply(M, S, A, wslot, 0, ih + 1, -g1, hm.y, &nhm.y, &st.mu[k].y, &st.am[k].y, &st.lo[k].z);
+                bb_opt_apply<OSK, OSK>(M, S, A, wslot, 0, ih + 1, -g1, hm.y, &nhm.y, &st.mu[k].y, &st.am[k].y, &st.lo[k].z);
                 BR_SCHED_FENCE();
-                bb_opt_apply(M, S, A, wslot, 1, ih + 1, -go1, ho.y, &nho.y, &st.om[k].y, &st.ao[k].y, &st.lo[k].w);
+                bb_opt_apply<OSK, OSK>(M, S, A, wslot, 1, ih + 1, -go1, ho.y, &nho.y, &st.om[k].y, &st.ao[k].y, &st.lo[k].w);
                 BR_SCHED_FENCE();
             }
-            if (hs_m) { br_store_pair_stream<AP>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<AP>(hs_o, ih, a0, a1, nho); }
+            if (OS || hs_m) { br_store_pair_stream<AP>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<AP>(hs_o, ih, a0, a1, nho); }
         }
     }
 #ifndef BB_EMU
@@ -1438,12 +1440,12 @@ BB_DEV void br_epilogue(BBCtx& cx, const DevState& S, BRSt<P>* stv, unsigned lon
 // a tile's step between its moments and its update, in three parts (the emulation runs part 2 of all tiles between parts 1 and 3)
 // `xc` numbers the exchanges of a handle's life: the step, or step x S + sample in the instances that take several samples per
 // step; it gives the parity of the double-buffered tables and rows and the rows' epoch.
-template <int KIND, int P, bool AP = false, bool HD = false>
+template <int KIND, int P, bool AP = false, bool HD = false, bool OS = false>
 BB_DEV void br_xchg_publish(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv, unsigned long long xc, int slot,
                             unsigned long long next_step, unsigned next_stream = 0u, bool prefetch = true) {
     // (the tile's row went out at the end of br_moments)  The window slot first: LDS-DMA is slow to land (~3 k cycles for a
     // tile's 32 KB) and loads return in order, so it must be out of the way before this wave polls and reads the group rows
-    if (A.pf == 0 && prefetch) br_prefetch_slot<P, HD>(cx, M, S, A, Y, stv, slot);
+    if (A.pf == 0 && prefetch) br_prefetch_slot<P, HD, OS>(cx, M, S, A, Y, stv, slot);
     br_grad_pre<KIND, P, AP>(cx, Y, stv, (int)(xc & 1));          // what of this step's gradient needs no totals
     br_theta_sum<KIND, P>(cx, M, Y, stv);          // (genotype model: the theta threads add their members' terms up -- left in front of barrier 2)
     // (replicate model: theta adds R entries at the start of the G pass; its units' terms are formed HERE -- in the M pass they cost C3 more
@@ -1470,7 +1472,9 @@ BB_DEV void br_xchg_consume(BBCtx& cx, const DevModel& M, const DevState& S, con
 #ifndef BB_EMU
 // MS = false: one MC sample per step, no ELBO recording (the lean instances every BASELINE shape runs).  MS = true: A.S >= 1 samples
 // per step (each with its own exchange) and, every A.elbo_every steps, the ELBO estimate into the ring.
-template <int KIND, int P, int NT, bool XG = false, int TT = 0, bool AP = false, bool MS = false>
+// OS = true: TruncatedADAGrad with resum_every == 0 compiled in (the plan launches these only for such a handle, bb_plan.h); the
+// optimiser's launch-uniform choices then cost the step loop nothing.  The BASELINE shapes' compile-time-T instances have both forms.
+template <int KIND, int P, int NT, bool XG = false, int TT = 0, bool AP = false, bool MS = false, bool OS = false>
 __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, const DevState* __restrict__ Sp, const BRLay* __restrict__ Yp,
                                             RunArgs A, int NB, int nsteps) {
     const DevModel& M = *Mp;
@@ -1492,14 +1496,14 @@ __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, con
     if (!dead) {
         br_draw_ahead<KIND, P, AP>(cx, A, Y, &st, step0);
         BB_STAMP_RT(cx, S, 4);
-        BBSlotCtr sc = bb_slot_init(A, step0);
+        BBSlotCtr sc = bb_slot_init<OS>(A, step0);
         const int NS = MS ? A.S : 1;
         // ELBO recording (MS): position inside the recording period and the ring slot, carried like the window slot
         int ec = (MS && A.elbo_every > 0) ? bb_uniform((int)(step0 % (unsigned long long)A.elbo_every)) : 1;
         int ring = (MS && A.elbo_every > 0) ? bb_uniform((int)(((step0 + (unsigned long long)A.elbo_every - 1ull) / (unsigned long long)A.elbo_every) % BB_ELBO_RING)) : 0;      // (of the next recording step)
-        for (; done < nsteps; ++done, bb_slot_next(A, sc)) {
+        for (; done < nsteps; ++done, bb_slot_next<OS>(A, sc)) {
             const unsigned long long step = step0 + (unsigned long long)done;
-            const BBSlot wslot = bb_slot_now(A, sc);
+            const BBSlot wslot = bb_slot_now<OS>(A, sc);
             const bool want_el = MS && A.elbo_every > 0 && ec == 0;
             bool stop = false;
             for (int smp = 0; smp < NS; ++smp) {
@@ -1515,13 +1519,13 @@ __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, con
 #pragma unroll
                     for (int k = 0; k < P; ++k) asm volatile("" : "+v"(st.meta[k]));
                 }
-                br_sample<KIND, P, MS, XG>(cx, M, S, A, Y, &st, buf, wslot.slot, last, want_el);
+                br_sample<KIND, P, MS, XG, OS>(cx, M, S, A, Y, &st, buf, wslot.slot, last, want_el);
                 br_moments<KIND, P, MS>(cx, M, S, Y, &st, buf, A.xepoch0 + (unsigned)(xc + 1), want_el);      // (tagged rows on the first hop of the sharded instances too)
-                br_xchg_publish<KIND, P, AP, XG>(cx, M, S, A, Y, &st, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
+                br_xchg_publish<KIND, P, AP, XG, OS>(cx, M, S, A, Y, &st, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
                 br_xchg_lead<XG>(cx, M, S, A, Y, xc, ok_slot);
                 br_xchg_consume<KIND, P, XG, MS>(cx, M, S, A, Y, &st, xc, ok_slot, want_el, ring, smp);
                 if (*ok_slot == 0) { stop = true; break; }                 // uniform: read after barrier 3
-                br_update<KIND, P, TT, AP, MS, XG>(cx, M, S, A, Y, &st, wslot, buf, NB, smp, NS);
+                br_update<KIND, P, TT, AP, MS, XG, OS>(cx, M, S, A, Y, &st, wslot, buf, NB, smp, NS);
             }
             if (stop) break;
             if (MS && A.elbo_every > 0) {

@@ -407,34 +407,37 @@ BB_DEV void bs_load_state(const DevModel& M, const DevState& S, const double* hs
     }
 }
 // optimiser update of the pair from the likelihood + prior gradient (g0, g1) and the draw's a = eps sigmoid, h = sigmoid / softplus (g.a, g.h); stores
+// (OS, here and in its callers up to k_stream: TruncatedADAGrad with resum_every == 0 at compile time -- bb_opt_apply<0, 0>, as k_res)
+template <bool OS = false>
 BB_DEV bool bs_apply_store(const DevModel& M, const DevState& S, const RunArgs& A, const BBSlot wslot, double* hs_m, double* hs_o,
                            long long i0, long long ih, bool a0, bool a1, double g0, double g1, BSG& g) {
     const double go0 = fma(g0, g.a.x, g.h.x), go1 = fma(g1, g.a.y, g.h.y);
     bb_d2 nhm = g.hm, nho = g.ho;
+    constexpr int OSK = OS ? 0 : -1;
     if (a0) {
-        bb_opt_apply(M, S, A, wslot, 0, ih, -g0, g.hm.x, &nhm.x, &g.mu.x, &g.am.x, &g.lo.x);
-        bb_opt_apply(M, S, A, wslot, 1, ih, -go0, g.ho.x, &nho.x, &g.om.x, &g.ao.x, &g.lo.y);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 0, ih, -g0, g.hm.x, &nhm.x, &g.mu.x, &g.am.x, &g.lo.x);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 1, ih, -go0, g.ho.x, &nho.x, &g.om.x, &g.ao.x, &g.lo.y);
     }
     if (a1) {
-        bb_opt_apply(M, S, A, wslot, 0, ih + 1, -g1, g.hm.y, &nhm.y, &g.mu.y, &g.am.y, &g.lo.z);
-        bb_opt_apply(M, S, A, wslot, 1, ih + 1, -go1, g.ho.y, &nho.y, &g.om.y, &g.ao.y, &g.lo.w);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 0, ih + 1, -g1, g.hm.y, &nhm.y, &g.mu.y, &g.am.y, &g.lo.z);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 1, ih + 1, -go1, g.ho.y, &nho.y, &g.om.y, &g.ao.y, &g.lo.w);
     }
     br_store_pair<false>(S.mu, i0, a0, a1, g.mu);
     br_store_pair<false>(S.om, i0, a0, a1, g.om);
     br_store_pair<false>(S.acc_mu, i0, a0, a1, g.am);
     br_store_pair<false>(S.acc_om, i0, a0, a1, g.ao);
     bb_store_lo(S, i0, a0, a1, g.lo);
-    if (hs_m) { br_store_pair_stream<false>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<false>(hs_o, ih, a0, a1, nho); }
+    if (OS || hs_m) { br_store_pair_stream<false>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<false>(hs_o, ih, a0, a1, nho); }
     const double chk = (a0 ? g.mu.x + g.om.x : 0.0) + (a1 ? g.mu.y + g.om.y : 0.0);
     return !(chk - chk == 0.0);
 }
 
 // MS, NS > 1: sample smp's gradient of the pair (likelihood + prior part gl, and gl a for omega) joins the running sums in memory; the last
 // sample averages them, adds the entropy term and takes the optimiser step (bb_update_pair's arithmetic).  Returns "non-finite".
-template <bool MS>
+template <bool MS, bool OS = false>
 BB_DEV bool bs_finish_pair(const DevModel& M, const DevState& S, const RunArgs& A, const BBSlot wslot, double* hs_m, double* hs_o,
                            long long i0, long long ih, bool a0, bool a1, double gl0, double gl1, BSG& g, const BSMs& ms) {
-    if (!MS || ms.NS == 1) return bs_apply_store(M, S, A, wslot, hs_m, hs_o, i0, ih, a0, a1, gl0, gl1, g);
+    if (!MS || ms.NS == 1) return bs_apply_store<OS>(M, S, A, wslot, hs_m, hs_o, i0, ih, a0, a1, gl0, gl1, g);
     bb_d2 gm{gl0, gl1}, go{gl0 * g.a.x, gl1 * g.a.y};
     if (ms.smp > 0) {
         const bb_d2 pm = br_load_pair<false>(S.gacc_mu, i0, a0, a1), po = br_load_pair<false>(S.gacc_om, i0, a0, a1);
@@ -450,20 +453,21 @@ BB_DEV bool bs_finish_pair(const DevModel& M, const DevState& S, const RunArgs& 
     const double g0 = gm.x * invS, g1 = gm.y * invS;
     const double go0 = go.x * invS + g.h.x, go1 = go.y * invS + g.h.y;
     bb_d2 nhm = g.hm, nho = g.ho;
+    constexpr int OSK = OS ? 0 : -1;
     if (a0) {
-        bb_opt_apply(M, S, A, wslot, 0, ih, -g0, g.hm.x, &nhm.x, &g.mu.x, &g.am.x, &g.lo.x);
-        bb_opt_apply(M, S, A, wslot, 1, ih, -go0, g.ho.x, &nho.x, &g.om.x, &g.ao.x, &g.lo.y);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 0, ih, -g0, g.hm.x, &nhm.x, &g.mu.x, &g.am.x, &g.lo.x);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 1, ih, -go0, g.ho.x, &nho.x, &g.om.x, &g.ao.x, &g.lo.y);
     }
     if (a1) {
-        bb_opt_apply(M, S, A, wslot, 0, ih + 1, -g1, g.hm.y, &nhm.y, &g.mu.y, &g.am.y, &g.lo.z);
-        bb_opt_apply(M, S, A, wslot, 1, ih + 1, -go1, g.ho.y, &nho.y, &g.om.y, &g.ao.y, &g.lo.w);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 0, ih + 1, -g1, g.hm.y, &nhm.y, &g.mu.y, &g.am.y, &g.lo.z);
+        bb_opt_apply<OSK, OSK>(M, S, A, wslot, 1, ih + 1, -go1, g.ho.y, &nho.y, &g.om.y, &g.ao.y, &g.lo.w);
     }
     br_store_pair<false>(S.mu, i0, a0, a1, g.mu);
     br_store_pair<false>(S.om, i0, a0, a1, g.om);
     br_store_pair<false>(S.acc_mu, i0, a0, a1, g.am);
     br_store_pair<false>(S.acc_om, i0, a0, a1, g.ao);
     bb_store_lo(S, i0, a0, a1, g.lo);
-    if (hs_m) { br_store_pair_stream<false>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<false>(hs_o, ih, a0, a1, nho); }
+    if (OS || hs_m) { br_store_pair_stream<false>(hs_m, ih, a0, a1, nhm); br_store_pair_stream<false>(hs_o, ih, a0, a1, nho); }
     const double chk = (a0 ? g.mu.x + g.om.x : 0.0) + (a1 ? g.mu.y + g.om.y : 0.0);
     return !(chk - chk == 0.0);
 }
@@ -475,7 +479,7 @@ BB_DEV void bs_load_mu_om(const DevState& S, long long i0, bool a0, bool a1, BSG
 }
 
 // ---- G-L: every loglambda pair slot -- state in, eps from the kept sample, gradient, the barcode's unit sums, optimiser, out; the next sample ----
-template <int KIND, int TT, bool MS = false>
+template <int KIND, int TT, bool MS = false, bool OS = false>
 BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, int NB, int P, unsigned step, const BBSlot wslot, int* bad_any, BSG* gv,
                         const BSMs ms_ = BSMs{1, 0, -1, true, false, 0u, 0u}) {
     const BSMs ms = (MS && ms_.buf >= 0) ? ms_ : bs_ms_plain(step);
@@ -491,7 +495,7 @@ BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const R
     const int E = (KIND == 1 || KIND == 4) ? M.E : 1;
     double* hs_m = nullptr;
     double* hs_o = nullptr;
-    if (A.opt == 0) {
+    if (OS || A.opt == 0) {
         hs_m = S.hist + ((long long)wslot.slot * 2 + 0) * M.Dh;
         hs_o = S.hist + ((long long)wslot.slot * 2 + 1) * M.Dh;
     }
@@ -583,7 +587,7 @@ BB_DEV void bs_update_l(BBCtx& cx, const DevModel& M, const DevState& S, const R
             g.z = bb_d2{0.0, 0.0};
             if (g.ok) {
                 const long long i0 = g.st.i0[0];
-                if (bs_finish_pair<MS>(M, S, A, wslot, hs_m, hs_o, i0, i0 - sg[g.st.meta[0] >> 12].pad, true, true, g.g0, g.g1, g, ms)) *bad_any = 1;
+                if (bs_finish_pair<MS, OS>(M, S, A, wslot, hs_m, hs_o, i0, i0 - sg[g.st.meta[0] >> 12].pad, true, true, g.g0, g.g1, g, ms)) *bad_any = 1;
                 const bb_d2 en = bs_draw_inline(A.seed, i0, ms.nstep, ms.nstream);
                 g.z = bs_z(g.mu, g.om, en, &g.sp, &g.sg);
                 if (MS && ms.el_next) g.el += bs_el_pair<KIND, TT>(lds, M, Y, A, g.st, g.z, g.sp);
@@ -620,7 +624,7 @@ BB_DEV bool bs_unit_a(const DevModel& M, const DevState& S, const RunArgs& A, co
     return true;
 }
 // part B: gradient from the units' sums and the staged forms of THIS step, optimiser, everything out; the next step's sample, staged
-template <int KIND, int TT, bool MS = false>
+template <int KIND, int TT, bool MS = false, bool OS = false>
 BB_DEV bool bs_unit_b(const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, const BRSeg* sg, double* hs_m, double* hs_o,
                       const BBSlot wslot, unsigned step, double* lds, BSG& g, int NBs, const BSMs& ms) {
     const BBLds& L = Y.L;
@@ -695,14 +699,14 @@ BB_DEV bool bs_unit_b(const DevModel& M, const DevState& S, const RunArgs& A, co
     }
     gl0 -= (zv0 - pm0) * iv0;
     gl1 -= (zv1 - pm1) * iv1;
-    const bool bad = bs_finish_pair<MS>(M, S, A, wslot, hs_m, hs_o, i0, ih, a0, a1, gl0, gl1, g, ms);
+    const bool bad = bs_finish_pair<MS, OS>(M, S, A, wslot, hs_m, hs_o, i0, ih, a0, a1, gl0, gl1, g, ms);
     const bb_d2 en = bs_draw_inline(A.seed, i0, ms.nstep, ms.nstream);
     const bb_d2 zn = bs_z(g.mu, g.om, en, &g.sp, &g.sg);
     bs_put_u<KIND>(lds, M, Y, A, st, nbuf, zn);
     if (MS && ms.el_next) g.el += bs_el_pair<KIND, TT>(lds, M, Y, A, st, zn, g.sp);
     return bad;
 }
-template <int KIND, int TT, bool MS = false>
+template <int KIND, int TT, bool MS = false, bool OS = false>
 BB_DEV void bs_update_u(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, int NB, int P, unsigned step, const BBSlot wslot, int* bad_any, BSG* gv,
                         const BSMs ms_ = BSMs{1, 0, -1, true, false, 0u, 0u}) {
     const BSMs ms = (MS && ms_.buf >= 0) ? ms_ : bs_ms_plain(step);
@@ -715,7 +719,7 @@ BB_DEV void bs_update_u(BBCtx& cx, const DevModel& M, const DevState& S, const R
     const int lspan = bs_lspan(sg, nseg), k0 = lspan / cx.nthr;
     double* hs_m = nullptr;
     double* hs_o = nullptr;
-    if (A.opt == 0) {
+    if (OS || A.opt == 0) {
         hs_m = S.hist + ((long long)wslot.slot * 2 + 0) * M.Dh;
         hs_o = S.hist + ((long long)wslot.slot * 2 + 1) * M.Dh;
     }
@@ -730,10 +734,10 @@ BB_DEV void bs_update_u(BBCtx& cx, const DevModel& M, const DevState& S, const R
     BB_PASS(cx, tid) {
         BSG& g = BB_PSTATE(gv, tid);
         bool bad = false;
-        if (g.ok) bad = bs_unit_b<KIND, TT, MS>(M, S, A, Y, sg, hs_m, hs_o, wslot, step, lds, g, NB, ms);
+        if (g.ok) bad = bs_unit_b<KIND, TT, MS, OS>(M, S, A, Y, sg, hs_m, hs_o, wslot, step, lds, g, NB, ms);
         for (int k = k0 + 1; k < P; ++k)
             if (bs_unit_a<KIND, TT, MS>(M, S, A, Y, t, sg, nseg, g0t, g1t, hs_m, hs_o, tid + k * cx.nthr, lspan, step, lds, g, ms))
-                bad = bs_unit_b<KIND, TT, MS>(M, S, A, Y, sg, hs_m, hs_o, wslot, step, lds, g, NB, ms) || bad;
+                bad = bs_unit_b<KIND, TT, MS, OS>(M, S, A, Y, sg, hs_m, hs_o, wslot, step, lds, g, NB, ms) || bad;
         if (bad) *bad_any = 1;
     }
     BB_SYNC(cx);                     // the next step's tables are complete
@@ -748,7 +752,7 @@ BB_DEV BSMs bs_ms_of(const RunArgs& A, unsigned long long step, int smp, int NS,
 }
 
 #ifndef BB_EMU
-template <int KIND, int NT, int TT, bool MS = false>
+template <int KIND, int NT, int TT, bool MS = false, bool OS = false>
 __global__ void __launch_bounds__(NT) k_stream(const DevModel* __restrict__ Mp, const DevState* __restrict__ Sp, const BRLay* __restrict__ Yp,
                                                RunArgs A, int NB, int nsteps, int P) {
     const DevModel& M = *Mp;
@@ -774,10 +778,10 @@ __global__ void __launch_bounds__(NT) k_stream(const DevModel* __restrict__ Mp, 
         int ec = (MS && A.elbo_every > 0) ? bb_uniform((int)(step0 % (unsigned long long)A.elbo_every)) : 1;
         int ring = (MS && A.elbo_every > 0) ? bb_uniform((int)(((step0 + (unsigned long long)A.elbo_every - 1ull) / (unsigned long long)A.elbo_every) % BB_ELBO_RING)) : 0;
         bs_sample0<KIND, TT, MS>(cx, M, S, A, Y, NB, P, (unsigned)step0, &g, (int)((step0 * (unsigned long long)NS) & 1ull), MS && A.elbo_every > 0 && ec == 0);
-        BBSlotCtr sc = bb_slot_init(A, step0);
-        for (; done < nsteps; ++done, bb_slot_next(A, sc)) {
+        BBSlotCtr sc = bb_slot_init<OS>(A, step0);
+        for (; done < nsteps; ++done, bb_slot_next<OS>(A, sc)) {
             const unsigned long long step = step0 + (unsigned long long)done;
-            const BBSlot wslot = bb_slot_now(A, sc);
+            const BBSlot wslot = bb_slot_now<OS>(A, sc);
             const bool want_el = MS && A.elbo_every > 0 && ec == 0;
             const int ec1 = (MS && A.elbo_every > 0) ? (ec + 1 == A.elbo_every ? 0 : ec + 1) : 1;
             bool stop = false;
@@ -789,8 +793,8 @@ __global__ void __launch_bounds__(NT) k_stream(const DevModel* __restrict__ Mp, 
                 br_xchg_lead<false>(cx, M, S, A, Y, xc, ok_slot);
                 br_xchg_consume<KIND, 1, false, MS>(cx, M, S, A, Y, nost, xc, ok_slot, want_el, ring, smp);
                 if (*ok_slot == 0) { stop = true; break; }
-                bs_update_l<KIND, TT, MS>(cx, M, S, A, Y, NB, P, (unsigned)step, wslot, bad_any, &g, ms);
-                bs_update_u<KIND, TT, MS>(cx, M, S, A, Y, NB, P, (unsigned)step, wslot, bad_any, &g, ms);
+                bs_update_l<KIND, TT, MS, OS>(cx, M, S, A, Y, NB, P, (unsigned)step, wslot, bad_any, &g, ms);
+                bs_update_u<KIND, TT, MS, OS>(cx, M, S, A, Y, NB, P, (unsigned)step, wslot, bad_any, &g, ms);
             }
             if (stop) break;
             if (MS && A.elbo_every > 0) {

@@ -177,6 +177,12 @@ typedef struct bb_stats {
                                   leader's XCD and stored their row through the L2 they share (of n_blocks; 0 with
                                   BB_TUNE_ROW_L2=0 in the environment, which keeps every row store write-through)        */
     int32_t reserved0;
+    int32_t opt_compiled;      /* 1: the resident launch is an instance with the optimiser compiled in (TruncatedADAGrad with
+                                  resum_every == 0: no run-time choice of optimiser or re-add schedule in the step loop); 0: the
+                                  generic instance (resum_every >= 1, DecayedADAGrad, shapes without such an instance,
+                                  BB_TUNE_OPT_SPEC=0 in the environment, no resident launch).  Same results either way;
+                                  bb_kernel_name does not tell the two apart                                             */
+    int32_t reserved1;
 } bb_stats;
 
 const char* bb_version(void);
@@ -800,6 +806,11 @@ int bb_debug_math(bb_handle* h, int32_t fn, int64_t n, const double* x, const do
 /* s_memtime stamps at the pass boundaries of the last launches, [n_blocks][32]; all zero unless
  * the library was built with -DBB_STAMPS (diagnostic build, never the shipped one). */
 int bb_debug_stamps(bb_handle* h, uint64_t* out, int64_t n);
+
+/* Test hook: the optimiser's state beside the parameters, as the device holds it after the last run, in the handle's INTERNAL latent
+ * order (bb_get_permutation) -- acc_mu, acc_omega [D]: TruncatedADAGrad's running window sums / DecayedADAGrad's accumulators;
+ * lo [2 D]: the low-order parts of the compensated window sums, (mu, omega) per latent.  Not on a multi-device handle. */
+int bb_debug_opt_state(bb_handle* h, double* acc_mu, double* acc_omega, float* lo);
 
 /* hipGraphLaunch calls of the last bb_run on this handle: 0 when the run was a resident launch or went eagerly (ELBO recording on,
  * steps_per_graph < 0, fewer steps than one graph, or a capture that failed), and always 0 in the emulation. */
