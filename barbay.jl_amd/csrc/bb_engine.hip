@@ -346,6 +346,9 @@ static void emu_res_phase(EmuPersist& E, int phase, long long it, long long nste
             if (xg && MSrun) br_xchg_consume<KIND, PP, true, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp);
             else if (xg) br_xchg_consume<KIND, PP, true, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
             else if (MSrun) br_xchg_consume<KIND, PP, false, true>(cx, h->M, h->S, A, Y, sb, xc, &E.ok, want_el, ring, smp);
+            // (the one-wave consume + finish where the product's OS instances run it: resident_instance has checked one replicate, ng <= 8)
+            else if (OS && !AP && KIND <= 2 && uniform_T(h->M) == 8) br_xchg_consume<KIND, PP, false, false, br_fin_T<KIND, PP, false, 8, AP, false, OS>()>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
+            else if (OS && !AP && KIND <= 2 && uniform_T(h->M) == 6) br_xchg_consume<KIND, PP, false, false, br_fin_T<KIND, PP, false, 6, AP, false, OS>()>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
             else br_xchg_consume<KIND, PP, false, false>(cx, h->M, h->S, A, Y, sb, xc, &E.ok);
             // (the compile-time-T forms of the G pass where the product has them, so that the emulation covers that code too)
             if (MSrun) br_update<KIND, PP, 0, AP, true>(cx, h->M, h->S, A, Y, sb, wslot, buf, h->plan.NB, smp, NS);

@@ -416,8 +416,10 @@ BB_DEV void bb_gran_st_l2(bb_gran* p, double v, unsigned tag) {
 // per lane: ONE address register for the eight loads in flight (scalar base + 32-bit lane offset, advanced between the loads) --
 // with eight 64-bit lane addresses beside the 32 destination registers the step loop of the 1024-thread instances spilled.  One
 // call per thread with a row entry; the lanes of a wave leave together.  false = gave up.
-template <bool SYS = false>
-BB_DEV bool bb_gran_poll8(const bb_gran* base, unsigned off, unsigned stride, int n, unsigned tag, bool active, unsigned* tmo, unsigned limit, double* out) {
+// FULL: all eight entries count whatever `n_` says (the caller has checked n_ == 8): no per-entry selects behind the poll.
+template <bool SYS = false, bool FULL = false>
+BB_DEV bool bb_gran_poll8(const bb_gran* base, unsigned off, unsigned stride, int n_, unsigned tag, bool active, unsigned* tmo, unsigned limit, double* out) {
+    const int n = FULL ? 8 : n_;
 #ifdef BB_EMU
     (void)tmo; (void)limit;
     bool good = true;

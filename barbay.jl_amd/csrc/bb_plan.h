@@ -16,10 +16,18 @@ static int uniform_T(const DevModel& M) {
 // os: the instance has the optimiser compiled in (k_res / k_stream<.., OS = true>, bb_opt_apply<0, 0>) -- wanted where the handle runs
 // TruncatedADAGrad with resum_every == 0 and one sample per step without the ELBO trace (BB_TUNE_OPT_SPEC=0: never), chosen where the
 // shape has such an instance: the compile-time-T k_res instances, k_stream's; the emulation has both forms of every one-sample shape.
-static const void* resident_instance(const bb_handle* h, bool xg, bool stream, int P, bool ms, std::string& name, bool& os) {
+// The one-GPU OS instances of k_res for the fitness / multienv / genotype kinds with a compile-time T run the one-wave consume + finish
+// (br_consume_finish, k_res's br_fin_T): it is written for ONE replicate and one polling thread group -- `ng` first-hop groups, 8 at most.
+// Where a launch has more of either, the generic instance runs.
+static bool fin_chain_shape(const bb_handle* h, bool xg, bool stream, int P) {
+    const int T = uniform_T(h->M);
+    return !stream && !xg && !br_any_parity(h->M) && h->M.kind <= 2 && P <= 2 && (T == 8 || T == 6);
+}
+static const void* resident_instance(const bb_handle* h, bool xg, bool stream, int P, bool ms, int ng, std::string& name, bool& os) {
     const int kind = h->M.kind, nthr = h->nthr, T = uniform_T(h->M);
     const bool ap = br_any_parity(h->M);
-    const bool want_os = h->tune.opt_spec != 0 && !ms && h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && h->o.resum_every == 0;
+    const bool fin_ok = !fin_chain_shape(h, xg, stream, P) || (h->M.R == 1 && ng <= 8);
+    const bool want_os = h->tune.opt_spec != 0 && !ms && h->o.optimizer == BB_OPT_TRUNCATED_ADAGRAD && h->o.resum_every == 0 && fin_ok;
     os = false;
 #if defined(BB_EMU)
     os = want_os;
@@ -42,6 +50,14 @@ static const void* resident_instance(const bb_handle* h, bool xg, bool stream, i
         if (nthr > 512 && P == 1 && kind == 0) return fn(k_res<0, 1, 1024, false, 0, true>);
         if (nthr > 256 && nthr <= 512 && P == 3 && kind == 3) return fn(k_res<3, 3, 512, false, 0, true>);
         return nullptr;
+    }
+    // (the OS forms of the C2 / C4 / C5-rank instances, so that stamps and A/B runs are of the instance the product launches)
+    if (want_os && nthr > 512 && P == 1) {
+        os = true;
+        if (kind == 0 && T == 8) return fn(k_res<0, 1, 1024, false, 8, false, false, true>);
+        if (kind == 1 && T == 6) return fn(k_res<1, 1, 1024, false, 6, false, false, true>);
+        if (kind == 2 && T == 8) return fn(k_res<2, 1, 1024, false, 8, false, false, true>);
+        os = false;
     }
     if (nthr > 512 && P == 1 && kind == 0) return T == 8 ? fn(k_res<0, 1, 1024, false, 8>) : fn(k_res<0, 1, 1024, false>);
     if (nthr > 512 && P == 1 && kind == 1) return T == 6 ? fn(k_res<1, 1, 1024, false, 6>) : fn(k_res<1, 1, 1024, false>);
@@ -284,7 +300,7 @@ static bool window_fetch_layout(const bb_handle* h, Planned& c) {
 
 // the kernel instance, whether its grid fits resident on the device, and the handle's buffers the tile map
 static bool instance_fits(const bb_handle* h, Planned& c) {
-    c.plan.fn = resident_instance(h, c.xg, c.plan.impl == IMPL_STREAM, c.plan.P, c.plan.ms, c.plan.name, c.plan.os);
+    c.plan.fn = resident_instance(h, c.xg, c.plan.impl == IMPL_STREAM, c.plan.P, c.plan.ms, c.plan.ng, c.plan.name, c.plan.os);
     if (resident_fit(c.plan.fn, h->nthr, c.lds_doubles * 8, c.plan.nblk, h->cus)) return false;
     return c.plan.nblk <= h->tile_cap;       // (else: more tiles than the exchange, stamp, xsel and tile-table buffers hold)
 }

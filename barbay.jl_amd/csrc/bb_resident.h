@@ -1049,6 +1049,86 @@ BB_DEV void br_finish(BBCtx& cx, const DevModel& M, const DevState& S, const BRL
     }
 }
 
+// ---- consume + F as ONE wave's straight line (the one-GPU OS instances of the fitness / multienv / genotype kinds with a compile-time
+// T: k_res's FT template argument) ---------------------------------------------------------------------------------------------
+// From "the eight group rows are there" to barrier 3 every wave of every tile waits for wave 0.  bbp_consume_tg + br_finish spend that
+// stretch on a workgroup barrier nothing crosses (one thread group polls when NG <= 8), on ~40 single scalar loads of descriptor fields
+// (LDS offsets, K, nt1, Ttot: each waited for on the next line, re-issued every step) and on two table reads (tmap, ftab) in front
+// of the arithmetic.  Here the shape is one replicate of TT time points, so K = 6 TT - 3, nt1 = TT - 1, Ttot = TT, the header of the LDS
+// carve-up (br_header) and both tables are compile-time arithmetic (br_table_row / br_table_time with R = 1: tmap[k] = k for k < TT,
+// ftab[j] = {wk + TT + 5 j or -1, j, j > 0, wk + j}); M.nn is read before the poll.  The plan launches these instances only where
+// M.R == 1 and A.ng <= 8 (resident_instance); the other shapes keep the two functions above.
+// The same operations on the same values in the same order as bbp_consume_tg + bb_put_total + br_finish: group rows added from 0.0 in
+// group order, 1/S_t by bb_rcp into invS, the F lane's expressions verbatim.
+// No workgroup barrier between the poll and barrier 3.  Wave 0 writes, in that stretch: wk (the totals), zgl, invS, cc, wbar, Dt, iG,
+// gglob and -- through *ok -- the launch's ok word in misc.  Nobody else touches them between barrier 2 and barrier 3:
+//   br_row_publish  other waves write wk BEFORE its own barrier (2b); behind it only wave 0 reads wk (KK <= 64: the row's stores)
+//   br_prefetch_slot (pf == 0)  LDS-DMA into hbuf       br_grad_pre   reads seg, zl, the unit stage tables; writes registers
+//   br_theta_sum    reads gas; writes registers          br_draw_ahead writes eps
+//   bbp_leader_reduce_tg  red (and its two barriers, kept: every wave of a leader tile runs them before it comes here)
+// and the ok word is read by everybody behind barrier 3 only.  The G pass (cc, wbar, iG, invS, gglob, zgl) ends with a barrier of its own.
+template <int KIND, int TT>
+BB_DEV void br_consume_finish(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, int par, unsigned epoch, int* ok) {
+    static_assert(KIND <= 2 && TT >= 2 && 8 * TT - 5 <= 64, "one replicate whose row and time points fit one wave");
+    constexpr int K = 6 * TT - 3, NT1 = TT - 1, KK = K + 2 * NT1;
+    constexpr BRHdr H = br_header(K, NT1, TT, 1);
+    double* lds = cx.lds;
+    const int NG = bbp_groups(A);
+    double nn = (double)M.nn;
+#ifndef BB_EMU
+    asm volatile("" : "+v"(nn));                 // (read in front of the poll, and it stays there)
+#endif
+    BB_PASS(cx, tid) {
+        if (tid < 64) {                          // (a whole wave: the lanes of a wave poll together)
+            const bool act = tid < KK;
+            const int k = act ? tid : KK - 1;
+            double v[8];
+            bool good;
+            if (NG == 8) good = bb_gran_poll8<false, true>(S.gxrow + (long long)par * NG * KK, (unsigned)k, (unsigned)KK, 8, epoch, act, S.gbar + 1, A.spin_limit, v);
+            else good = bb_gran_poll8(S.gxrow + (long long)par * NG * KK, (unsigned)k, (unsigned)KK, NG, epoch, act, S.gbar + 1, A.spin_limit, v);
+            if (!good) *ok = 0;
+            BB_STAMP(cx, S, 1);
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) s += v[i];
+            if (act) {
+                if (k < K) {
+                    lds[H.wk + k] = s;
+                    if (k < TT) lds[H.invS + k] = bb_rcp(s);
+                } else lds[H.zgl + (k - K)] = s;
+            }
+        }
+    }
+    BB_STAMP(cx, S, 25);
+    BB_STAMP_RT(cx, S, 30);
+    // (wave 0's LDS operations complete in order: the totals above are there for the lanes below -- as between bbp_consume_tg and br_finish)
+    BB_PASS(cx, tid) {
+        if (tid < TT) {
+            const int j = tid;
+            double Dt = 0.0, c = 0.0, wb = 0.0;
+            if (j < TT - 1) {
+                const double* mm = lds + (H.wk + TT + 5 * j);
+                const double M0 = mm[0], M1 = mm[1], N1 = mm[3], N2 = mm[4];
+                const double sbar = lds[H.zgl + j], ls = lds[H.zgl + NT1 + j];
+                wb = bb_exp(-2.0 * ls);
+                const double dl = bb_log(lds[H.wk + j + 1] * lds[H.invS + j]);
+                const double cp = (dl - lds[H.piv + j]) - sbar;
+                c = dl - sbar;
+                const double quadN = N2 - 2.0 * cp * N1 + nn * cp * cp;
+                Dt = (M1 - cp * M0) + wb * (N1 - cp * nn);
+                lds[H.gglob + j] = -Dt;
+                lds[H.gglob + NT1 + j] = wb * quadN - nn;
+            }
+            lds[H.cc + j] = c;
+            lds[H.wbar + j] = wb;
+            lds[H.Dt + j] = Dt;
+            lds[H.iG + j] = ((j > 0 ? lds[H.Dt + j - 1] : 0.0) - Dt) * lds[H.invS + j];
+        }
+    }
+    BB_SYNC(cx);                     // barrier 3
+    BB_STAMP(cx, S, 26);
+}
+
 // ---- G: gradients from registers, prior, optimiser, window slot -----------------------------------------------------------
 // Likelihood gradient of a loglambda pair's two latents, with r = a - c_t, a = dl - s_eff:
 //   d/dl_t = (R_t - lambda_t) + lambda_t G_t / S_t + w r|_t... - prior
@@ -1460,10 +1540,16 @@ BB_DEV void br_xchg_lead(BBCtx& cx, const DevModel& M, const DevState& S, const 
     //  as round 1 had found for k_persist: 7.6 k cycles against 4.8 k for the leader's read + sum + publish)
     if (cx.block < bbp_groups(A)) bbp_leader_reduce_tg<XG>(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
 }
-template <int KIND, int P, bool XG, bool MS = false>
+// FT > 0: the one-wave consume + finish of a one-replicate shape with FT time points (br_consume_finish)
+// the instances that run it: a constexpr of k_res's template arguments -- no new instances, no run-time flag in the step loop.
+// (One or two pair slots: the three-slot 512-thread genotype instance sits on its 256 registers, 33 of its values spilled; with this
+//  leg it spilled 41.  It keeps the general chain.)
+template <int KIND, int P, bool XG, int TT, bool AP, bool MS, bool OS> static inline constexpr int br_fin_T() { return (OS && !XG && !MS && !AP && KIND <= 2 && P <= 2 && TT > 0) ? TT : 0; }
+template <int KIND, int P, bool XG, bool MS = false, int FT = 0>
 BB_DEV void br_xchg_consume(BBCtx& cx, const DevModel& M, const DevState& S, const RunArgs& A, const BRLay& Y, BRSt<P>* stv,
                             unsigned long long xc, int* ok_slot, bool want_el = false, int ring = 0, int smp = 0) {
     const unsigned epoch = A.xepoch0 + (unsigned)(xc + 1);
+    if constexpr (FT > 0 && !XG && !MS && KIND <= 2) { br_consume_finish<KIND, FT>(cx, M, S, A, (int)(xc & 1), epoch, ok_slot); return; }
     if (XG) bbp_consume_tgx(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
     else bbp_consume_tg(cx, M, S, A, Y.L, (int)(xc & 1), epoch, ok_slot);
     br_finish<KIND, MS>(cx, M, S, Y, &A, want_el, ring, smp);
@@ -1523,7 +1609,7 @@ __global__ void __launch_bounds__(NT) k_res(const DevModel* __restrict__ Mp, con
                 br_moments<KIND, P, MS>(cx, M, S, Y, &st, buf, A.xepoch0 + (unsigned)(xc + 1), want_el);      // (tagged rows on the first hop of the sharded instances too)
                 br_xchg_publish<KIND, P, AP, XG, OS>(cx, M, S, A, Y, &st, xc, wslot.slot, last ? step + 1 : step, last ? 0u : (unsigned)(smp + 1), last);
                 br_xchg_lead<XG>(cx, M, S, A, Y, xc, ok_slot);
-                br_xchg_consume<KIND, P, XG, MS>(cx, M, S, A, Y, &st, xc, ok_slot, want_el, ring, smp);
+                br_xchg_consume<KIND, P, XG, MS, br_fin_T<KIND, P, XG, TT, AP, MS, OS>()>(cx, M, S, A, Y, &st, xc, ok_slot, want_el, ring, smp);
                 if (*ok_slot == 0) { stop = true; break; }                 // uniform: read after barrier 3
                 br_update<KIND, P, TT, AP, MS, XG, OS>(cx, M, S, A, Y, &st, wslot, buf, NB, smp, NS);
             }

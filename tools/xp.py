@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Experiment driver for kernel variants (diagnostic).
-   python tools/xp.py build NAME [-DFLAG ...]     here: lib/ab/NAME.so and NAME_st.so (-DBB_STAMPS), only the C2 / C4 instances (-DBB_FAST_BUILD)
+   python tools/xp.py build NAME [-DFLAG ...]     here: lib/ab/NAME.so and NAME_st.so (-DBB_STAMPS), only the C2 / C4 / C5-rank instances
+                                                  (-DBB_FAST_BUILD), generic and with the optimiser compiled in (BB_TUNE_OPT_SPEC=0 runs the generic ones)
    python tools/xp.py run NAME [NAME ...]         on the GPU box: steps/s of C2 (WL=, B=, T= as tools/ab_geom.py) and the stamp shares"""
 import os
 import subprocess
@@ -63,6 +64,10 @@ for rep in range(2):
             line += (f"\n     leaders: own row out -> group row out (poll members' rows + sum + store) {np.median(s[lead, 18] - s[lead, 24]):.0f}, "
                      f"then until the group rows are seen {np.median(s[lead, 1] - s[lead, 18]):.0f}; others: own row out -> group rows seen {np.median(s[~lead, 1] - s[~lead, 24]):.0f}; "
                      f"all: group rows seen -> totals in LDS {np.median(s[:, 25] - s[:, 1]):.0f}")
+            # the last leg of the chain: 1 = this tile's poll has seen the group rows, 25 = F starts, 26 = behind barrier 3
+            leg = s[:, 26] - s[:, 1]
+            line += (f"\n     poll done -> behind barrier 3: median {np.median(leg):.0f} p10 {np.percentile(leg, 10):.0f} p90 {np.percentile(leg, 90):.0f} min {leg.min()} "
+                     f"(poll done -> F start {np.median(s[:, 25] - s[:, 1]):.0f}, F start -> behind barrier 3 {np.median(s[:, 26] - s[:, 25]):.0f}); opt_compiled {st.get('opt_compiled')}")
             # wall-clock stamps (100 MHz): publish and totals-seen over all tiles, in shader cycles at ~2.4 GHz
             for ev, nm in ((29, "publish"), (30, "totals seen")):
                 tt = (s[:, ev] - s[:, ev].min()) * 24
