@@ -29,6 +29,8 @@ BB_RB_MAX_SAMPLES = 8672
 BB_RB_MAX_Q = 8
 BB_THETA_RB_CHUNK = 64
 BB_POPMEAN_RB_CHUNK = 256
+BB_LOGSIGMA_RB_MAX_SAMPLES = 5781
+BB_LOGSIGMA_BLOCKS = {"bc": 0, "pop": 1}
 BB_MATH_FN = {"exp": 0, "log": 1, "rcp": 2, "div": 3, "sqrt": 4, "softplus_sigmoid": 5, "sincospi": 6, "exp_nonpos": 7, "log_1to2": 8,
               "box_muller": 9}
 BB_ERR_UNSUPPORTED = -4
@@ -41,6 +43,7 @@ EXPORTS = [
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
+    "bb_logsigma_rb_shape", "bb_logsigma_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
 ]
 
@@ -139,6 +142,18 @@ class bb_theta_rb_out(C.Structure):
 
 class bb_popmean_rb_out(C.Structure):
     _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("n_members", C.POINTER(C.c_int32))]
+
+
+LS_UNITS = ("q_mean", "q_sd", "rb_mean", "rb_sd", "sigma_mean", "mode_mean")
+
+
+class bb_logsigma_rb_opts(C.Structure):
+    _fields_ = [("block", C.c_int32), ("n_samples", C.c_int32), ("n_quantiles", C.c_int32), ("reserved0", C.c_int32), ("probs", _dp),
+                ("seed", C.c_uint64), ("draws", _dp)]
+
+
+class bb_logsigma_rb_out(C.Structure):
+    _fields_ = [(k, _dp) for k in LS_UNITS] + [("quantiles", _dp), ("n_terms", C.POINTER(C.c_int32))]
 
 
 class bb_chain_opts(C.Structure):
@@ -253,6 +268,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_popmean_rb"):
         lib.bb_popmean_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_popmean_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_popmean_rb_out)]
+    if hasattr(lib, "bb_logsigma_rb"):
+        lib.bb_logsigma_rb_shape.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+        lib.bb_logsigma_rb.argtypes = [vp, C.POINTER(bb_logsigma_rb_opts), C.POINTER(bb_logsigma_rb_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     if hasattr(lib, "bb_trace_begin"):
@@ -713,6 +731,41 @@ class Engine:
         out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
         out.n_members = res["n_members"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_popmean_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    @staticmethod
+    def _logsigma_block(block) -> int:
+        if block not in BB_LOGSIGMA_BLOCKS:
+            raise BarBayHipError(f"block must be one of {sorted(BB_LOGSIGMA_BLOCKS)}, got {block!r}")
+        return BB_LOGSIGMA_BLOCKS[block]
+
+    def logsigma_rb_shape(self, block: str = "bc") -> int:
+        """Entries of `logsigma_rb`: the length of the logsigma_bc ("bc") or logsigma_pop ("pop") block."""
+        n = C.c_int64(0)
+        self._check(self._lib.bb_logsigma_rb_shape(self._h, self._logsigma_block(block), C.byref(n)))
+        return int(n.value)
+
+    def logsigma_rb(self, block: str = "bc", n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
+                    draws=None) -> Dict[str, np.ndarray]:
+        """Rao-Blackwellised marginal of every noise scale of a block (`bb_logsigma_rb`): "bc" the logsigma_bc entries (the units of
+        `fitness_rb`), "pop" the logsigma_pop entries (the groups of `popmean_rb`).  The full conditional of a log-scale is
+        one-dimensional and log-concave; it is integrated numerically per draw and averaged over the draws of `fitness_rb` (same
+        arguments).  Returns q_mean, q_sd, rb_mean, rb_sd, sigma_mean (the RB mean of sigma itself), mode_mean [n_entries],
+        quantiles [n_entries, len(probs)] (of logsigma; their exp are sigma's) and n_terms (int32)."""
+        blk = self._logsigma_block(block)
+        n_entries = self.logsigma_rb_shape(block)
+        ro, p, _x = self._rb_opts(n_samples, probs, 0.0, seed, draws)
+        o = bb_logsigma_rb_opts()
+        o.block, o.n_samples, o.n_quantiles, o.probs, o.seed, o.draws = blk, ro.n_samples, ro.n_quantiles, ro.probs, ro.seed, ro.draws
+        res = {k: np.empty(n_entries) for k in LS_UNITS}
+        res["quantiles"] = np.empty((n_entries, p.shape[0]))
+        res["n_terms"] = np.empty(n_entries, dtype=np.int32)
+        out = bb_logsigma_rb_out()
+        for k in LS_UNITS:
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.n_terms = res["n_terms"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_logsigma_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,

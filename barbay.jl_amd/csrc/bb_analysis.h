@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
-// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb (bb_rb.h), bb_chain_summary
-// (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
+// bb_logsigma_rb (bb_lsrb.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -919,6 +919,152 @@ extern "C" int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean
     lap(6, 4);
 #ifdef BB_RB_TIMES
     fprintf(stderr, "[bb_popmean_rb %lld groups, %lld members, %d chunks each, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, pop %.3f ms, download %.3f ms\n", n_groups, nmem, H.nchunks, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
+}
+
+// ---- Rao-Blackwellised noise-scale marginals (bb_lsrb.h) ----------------------------------------------------------------------------
+static_assert(BB_LOGSIGMA_RB_MAX_SAMPLES == BB_LS_SAMPLES_CAP && BB_LOGSIGMA_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_logsigma_rb limits");
+extern "C" int bb_logsigma_rb_shape(const bb_handle* h, int32_t block, int64_t* n_entries) {
+    if (!h || !n_entries) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (block != BB_LOGSIGMA_BC && block != BB_LOGSIGMA_POP) return bb_fail(BB_ERR_INVALID, "block must be BB_LOGSIGMA_BC or BB_LOGSIGMA_POP");
+    const int k = block == BB_LOGSIGMA_BC ? BK_LS : BK_LSPOP;
+    *n_entries = h->M.blk_hi[k] - h->M.blk_lo[k];
+    return BB_OK;
+}
+
+extern "C" int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const bb_logsigma_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->block != BB_LOGSIGMA_BC && o->block != BB_LOGSIGMA_POP) return bb_fail(BB_ERR_INVALID, "block must be BB_LOGSIGMA_BC or BB_LOGSIGMA_POP");
+    const bool bc = o->block == BB_LOGSIGMA_BC;
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    {   // bb_fitness_rb's option checks (no threshold here), with this call's own cap
+        bb_rb_opts ro;
+        memset(&ro, 0, sizeof ro);
+        ro.n_samples = 2; ro.n_quantiles = nq; ro.probs = o->probs; ro.draws = o->draws;
+        if (int rc = rb_check(&ro)) return rc;
+        const int ns_lo = o->draws ? 1 : 2;
+        if (ns < ns_lo || ns > BB_LOGSIGMA_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_LOGSIGMA_RB_MAX_SAMPLES);
+    }
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    LsArgs L;
+    memset(&L, 0, sizeof L);
+    RbArgs& A = L.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const long long n_entries = bc ? rb_units(h) : M.nt1;
+    if (M.nn > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_logsigma_rb: more than 2^31 neutral members");
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
+    if (rc) return rc;
+    int zb;
+    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    // The block's prior, indexed by entry in the caller's order.  logsigma_pop is never regrouped; a Matrix-form logsigma_bc prior of a
+    // regrouped genotype handle lies in the handle's mutant order and is brought back to the caller's through perm_m.
+    const DevPrior& dp = M.pri[bc ? BK_LS : BK_LSPOP];
+    P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    const bool reorder = bc && dp.mean_e && !h->perm_m.empty();
+    A.nq = nq;
+    A.n_units = n_entries;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+    L.nchunks = (int)((M.nn + BB_POP_CHUNK - 1) / BB_POP_CHUNK);
+#ifdef BB_RB_TIMES             // diagnostics (tools/logsigma_rb_rate.py): the call's phases, each drained before the next starts
+    timespec ct[7];
+    double cms[5] = {0, 0, 0, 0, 0};
+    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int, int) {};
+#endif
+    lap(0, -1);
+    std::vector<int> neu;      // the ragged method's pairing, as bb_popmean_rb builds it
+    if (!bc && M.quirk) {
+        neu.resize(2 * (size_t)n_entries * (size_t)M.nn);
+        int* nt = neu.data();
+        int* nbv = nt + (size_t)n_entries * (size_t)M.nn;
+        for (int r = 0; r < M.R; ++r)
+            for (int k = 0; k + 1 < M.T[r]; ++k)
+                for (long long i = 0; i < M.nn; ++i) {
+                    const long long x = (long long)k * M.nn + i, at = (long long)(M.off_t[r] + k) * M.nn + i;
+                    nt[at] = (int)(x % (M.T[r] - 1));
+                    nbv[at] = (int)(x / (M.T[r] - 1));
+                }
+    }
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ne = (size_t)n_entries, nch = (size_t)L.nchunks;
+    // POP: the groups in flight, their chunk partials bounded to 256 MiB (a single group is worked whole whatever it takes)
+    const size_t slab = bc ? 0 : std::min(ne, std::max<size_t>(1, ((size_t)256 << 20) / (std::max<size_t>(1, nch) * nsz * 8)));
+    // the mixture's grid: as the row program's, its [BB_LS_TAB][ns] tables bounded to 256 MiB
+    long long nblk = std::max<long long>(1, std::min<long long>(bc ? (long long)M.R * M.nb : n_entries, 2LL * dh->cus));
+    while (nblk > 1 && (size_t)nblk * BB_LS_TAB * nsz * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    double* ddraws = nullptr;
+    double* dpri = nullptr;
+    int* dneu = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(A.ytab, (size_t)nblk * BB_LS_TAB * nsz);     // [nblk][5][ns]
+        c(L.part, slab * nch * nsz);                   // [groups in flight][nchunks][ns]
+        c(A.unit, BB_RB_OUT * ne);                     // [6][n_entries]
+        c(A.quant, BB_RB_MAX_Q * ne);                  // [n_entries][8]
+        c(A.n_steps, (ne + 1) / 2);                    // [n_entries] ints
+        c(dpri, reorder ? 2 * ne : 0);                 // the prior in the caller's order: mean | 1 / std^2
+        c(dneu, (neu.size() + 1) / 2);                 // the flagged pairing: ints
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    if (reorder) {
+        std::vector<double> in(2 * ne), cal(2 * ne);
+        if ((rc = d2h(in.data(), dp.mean_e, ne * 8, dh->stream)) || (rc = d2h(in.data() + ne, dp.inv_var_e, ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        for (size_t m = 0; m < ne; ++m) { cal[(size_t)h->perm_m[m]] = in[m]; cal[ne + (size_t)h->perm_m[m]] = in[ne + m]; }
+        if ((rc = h2d(dpri, cal.data(), 2 * ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;      // (cal is this scope's)
+        P.pri_mean_e = dpri;
+        P.pri_ivar_e = dpri + ne;
+    }
+    if (!neu.empty()) {
+        if ((rc = h2d(dneu, neu.data(), neu.size() * 4, dh->stream))) return rc;
+        L.neu_t = dneu;
+        L.neu_b = dneu + neu.size() / 2;
+    }
+    if (o->draws) {
+        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
+        P.draws = ddraws;
+        P.D = (long long)D;
+    }
+    lap(1, 0);
+    if (bc && (rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    if ((rc = freq_normalisers(dh, F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
+    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
+    lap(2, 1);
+    if (bc) {
+        if (n_entries > 0 && (rc = launch(dh->stream, k_ls_bc, (int)nblk, BB_SCORE_NT, (size_t)BB_LS_LDS_DOUBLES(ns), L))) return rc;
+        lap(3, 3);
+        lap(5, -1);
+    } else {
+        for (size_t g0 = 0; g0 < ne; g0 += slab) {
+            const size_t g1 = std::min(ne, g0 + slab);
+            L.g0 = (long long)g0; L.g1 = (long long)g1;
+            lap(3, -1);
+            if (nch && (rc = launch(dh->stream, k_ls_pop_part, (int)std::min<size_t>((g1 - g0) * nch, (size_t)1 << 20), BB_SCORE_NT, 0, L))) return rc;
+            lap(4, 2);
+            if ((rc = launch(dh->stream, k_ls_pop, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_LS_LDS_DOUBLES(ns), L))) return rc;
+            lap(5, 3);
+        }
+    }
+    double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->sigma_mean, out->mode_mean};
+    for (int k = 0; k < BB_RB_OUT; ++k)
+        if (units[k] && ne && (rc = d2h(units[k], A.unit + (size_t)k * ne, ne * 8, dh->stream))) return rc;
+    if (out->quantiles && nq && ne) {
+        std::vector<double> q(BB_RB_MAX_Q * ne);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        for (size_t g = 0; g < ne; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
+    }
+    if (out->n_terms && ne && (rc = d2h(out->n_terms, A.n_steps, ne * 4, dh->stream))) return rc;
+    rc = dsync(dh->stream);
+    lap(6, 4);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_logsigma_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, mixture %.3f ms, download %.3f ms\n", bc ? "bc" : "pop", n_entries, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
 #endif
     return rc;
 }

@@ -433,6 +433,18 @@ BB_KERNEL(BB_SCORE_NT, k_rb_pop, PopArgs H) {
     BB_CTX;
     bb_block_pop(cx, H, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_ls_bc, LsArgs L) {
+    BB_CTX;
+    bb_block_ls_bc(cx, L, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_ls_pop_part, LsArgs L) {
+    BB_CTX;
+    bb_block_ls_pop_part(cx, L, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_ls_pop, LsArgs L) {
+    BB_CTX;
+    bb_block_ls_pop(cx, L, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

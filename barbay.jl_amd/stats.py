@@ -26,6 +26,8 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
                                                                   conditional sums over the group's members (`bb_theta_rb`)
     popmean_marginals                                             the same for the population mean fitness of every time step, whose
                                                                   conditional sums over every barcode of the replicate (`bb_popmean_rb`)
+    noise_marginals                                               the same for the noise scales logsigma of the mutants and of the time
+                                                                  steps, whose conditional is integrated numerically (`bb_logsigma_rb`)
 """
 from __future__ import annotations
 
@@ -555,6 +557,55 @@ def popmean_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model
     out["p_pos"], out["p_neg"] = res["p_pos"], res["p_neg"]
     for i, p in enumerate(probs):
         out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
+    return out
+
+
+def noise_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, block: str = "bc", model_kwargs: Optional[Dict] = None,
+                    n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
+                    id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                    rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                    device: int = 0, chain=None) -> pd.DataFrame:
+    """`fitness_marginals` for the noise scales: `block="bc"` the `bc_std` rows of the fit's frame (logsigma of a mutant's
+    log-frequency-ratio terms), `block="pop"` the `pop_std` rows (logsigma of a time step's neutral terms) -- the numbers that say
+    which barcodes and which time steps are noisy, and the latents where a mean-field Gaussian is at its worst: too narrow, and
+    symmetric on the log scale where the true marginal is skewed.  The full conditional of a log-scale is not Gaussian but
+    one-dimensional and log-concave; it is integrated numerically per draw and averaged over n_samples joint draws of everything
+    else (`bb_logsigma_rb`, one device call; at most 5781 draws).  Arguments as for `fitness_marginals`, without a threshold.
+
+    Returns one line per row of the block, in the frame's order and with those rows' own labels (every column of the frame but
+    `mean` and `std`); then `n_terms` (the terms that inform the scale; 0: its conditional is the prior), `q_mean`, `q_sd` (the
+    draws' own logsigma), `rb_mean`, `rb_sd`, `sd_ratio` = rb_sd / q_sd, `mode_mean`, `sigma_mean` (the RB mean of sigma itself), one
+    column per probability of `probs` named q2.5, q50, ... (quantiles of logsigma) and their exp as sigma_q2.5, sigma_q50, ..."""
+    if block not in ("bc", "pop"):
+        raise BarBayError(f"block must be 'bc' or 'pop', got {block!r}")
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    vartype = "bc_std" if block == "bc" else "pop_std"
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        n_entries = e.logsigma_rb_shape(block)
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        blk = df_advi.iloc[:e.D]
+        blk = blk[blk["vartype"] == vartype]
+        if len(blk) != n_entries:
+            raise BarBayError(f"df_advi holds {len(blk)} {vartype} rows, the model has {n_entries}")
+        res = e.logsigma_rb(block=block, n_samples=n_samples, probs=probs, seed=seed, draws=draws)
+    out = blk.drop(columns=["mean", "std"]).reset_index(drop=True)
+    out["n_terms"] = res["n_terms"]
+    for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"] / res["q_sd"]
+    out["mode_mean"], out["sigma_mean"] = res["mode_mean"], res["sigma_mean"]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
+    for i, p in enumerate(probs):
+        out[f"sigma_q{100.0 * p:g}"] = np.exp(res["quantiles"][:, i])
     return out
 
 

@@ -502,8 +502,8 @@ int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
  * outside its range.  Multi-device and sharded handles: as bb_ppc_bands (the first device works on the gathered posterior; a shard
  * needs bb_set_params first).
  * The conditional of theta, the hyper-fitness of the hierarchical kinds: bb_theta_rb, below; that of the population mean fitness
- * sbar_t: bb_popmean_rb, below that.  Out of scope: the conditionals of tau and logsigma; any change to what the fit or an MCMC
- * run report by default. */
+ * sbar_t: bb_popmean_rb, below that; those of logsigma_bc and logsigma_pop: bb_logsigma_rb.  Out of scope: the conditional of
+ * tau; any change to what the fit or an MCMC run report by default. */
 #define BB_RB_MAX_SAMPLES 8672
 typedef struct bb_rb_opts {
     int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
@@ -566,7 +566,7 @@ int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out);
  * BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb; BB_ERR_UNSUPPORTED, the message naming the model kind, for
  * BB_MODEL_FITNESS / BB_MODEL_MULTIENV.  The chunk partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB
  * (the groups are worked in slabs; a single group is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditionals of tau and logsigma. */
+ * Out of scope: the conditional of tau (logsigma: bb_logsigma_rb). */
 #define BB_THETA_RB_CHUNK 64
 typedef struct bb_theta_rb_out {  /* every pointer may be NULL; [n_groups] unless noted */
     double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
@@ -622,7 +622,7 @@ int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out);
  * RNG position are untouched, bitwise.  BB_ERR_INVALID / BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb.  The chunk
  * partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB (the groups are worked in slabs; a single group
  * is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditionals of tau and logsigma. */
+ * Out of scope: the conditional of tau (logsigma: bb_logsigma_rb). */
 #define BB_POPMEAN_RB_CHUNK 256
 typedef struct bb_popmean_rb_out {   /* every pointer may be NULL; [n_groups] unless noted */
     double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
@@ -631,6 +631,93 @@ typedef struct bb_popmean_rb_out {   /* every pointer may be NULL; [n_groups] un
 } bb_popmean_rb_out;
 int bb_popmean_rb_shape(const bb_handle* h, int64_t* n_groups);
 int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean_rb_out* out);
+
+/* Rao-Blackwellised marginals of the noise scales logsigma_bc and logsigma_pop -- the latents where a mean-field Gaussian is at its
+ * worst (too narrow, and symmetric on the log scale where the true marginal is skewed), and the numbers that say which barcodes and
+ * which time steps are noisy.  No reference counterpart.  Given everything else a log-scale l enters the log-joint through its
+ * Gaussian prior N(a, b) and n Gaussian terms of standard deviation e^l whose residuals do not read l.  The conditional is not
+ * Gaussian, but it is one-dimensional and strictly log-concave, so it is integrated numerically per draw, by the rule below.
+ *
+ * Entries (bb_logsigma_rb_shape: n_entries = the length of the caller's logsigma_bc or logsigma_pop block):
+ *   BB_LOGSIGMA_BC   unit u of bb_fitness_rb, same numbering, same T_u and n_u.  Prior (a, 1 / b^2): the logsigma_bc_prior element
+ *          as the handle holds it (Vector or Matrix form; a Matrix form follows its mutant through the genotype regrouping).
+ *          n = n_u;  SS_j = sum_{t in T_u} d_t^2,  d_t = (gamma_{t,j} + sbar_{r,t,j}) - s_{u,j},  in ascending t from 0.0; gamma,
+ *          ln Z, sbar and s_{u,j} are bb_fitness_rb's word for word.
+ *   BB_LOGSIGMA_POP  group g = (r, k) of bb_popmean_rb, same numbering.  Prior: the logsigma_pop_prior element.  n = n_neutral;
+ *          d_i = gamma_{t,b,j} + sbar_{g,j} over the neutral members i < n_neutral of bb_popmean_rb's group g word for word (the
+ *          BB_FLAG_RAGGED_METHOD pairing included), sbar_g the draw of the group's own s_pop latent; SS_j is summed in chunks of
+ *          BB_POPMEAN_RB_CHUNK consecutive member indices, a chunk from 0.0 in index order, the chunks from 0.0 in chunk order.
+ * No atomics on doubles.  Either way, with ib2 = 1 / b^2, the log conditional density of draw j up to a constant is
+ *   h_j(l)  = -(l - a)^2 ib2 / 2 - n l - (SS_j / 2) e^{-2l}
+ *   h_j'(l) = -(l - a) ib2 - n + SS_j e^{-2l},     -h_j''(l) = ib2 + 2 SS_j e^{-2l} > 0
+ * The identity all this rests on, at any point z: h'(l) at z's own value of the latent = dlogp/dl (bb_logdensity_grad's entry).
+ *
+ * The rule (this is the definition, as the 64-step bisection is bb_fitness_rb's).
+ * Mode l*_j, the root of h_j':  SS_j == 0: l* = a - n / ib2 exactly.  Otherwise c2 = 2 / ib2, lnK = ln SS_j - 2a + c2 n, and
+ *   G(t) = t + c2 e^t - lnK = 0 is solved by Newton from t0 = ln(lnK / c2) if lnK >= c2, else t0 = lnK (G(t0) >= 0, G convex and
+ *   increasing: the iteration descends monotonically): step = G(t) / (1 + c2 e^t), t <- t - step, until |step| <= 2^-40 (1 + |t|)
+ *   with the new t, or 50 steps; then l* = a + (e^t - n) / ib2.  (Newton on h' itself overflows at n = 1000.)
+ * Grid:  W_j = SS_j e^{-2 l*} (0 where SS_j == 0),  delta_j = 1 / sqrt(ib2 + 2 W_j).  With p(u) = exp(h_j(l* + u) - h_j(l*)), the
+ *   exponent evaluated as -u c1 - ib2 u^2 / 2 - (W_j / 2) expm1(-2u), c1 = ib2 (l* - a) + n, which is the same number without the
+ *   cancelling large terms:
+ *   step   s_j = delta_j / (4 m_j),  m_j = max(1, ceil(2 delta_j)), at most 64 (1 for a NaN delta_j): delta / 4 wherever
+ *          delta_j <= 1/2, and never above 1/8 -- the factor exp(-(SS / 2) e^{-2l}) cuts the density off on the left over a width of
+ *          about 1/2 in l whatever delta is, and delta / 4 alone does not resolve that where delta is near a wide prior's b;
+ *   ends   lo_j = l* - 10 delta_j;  hi_j = l* + 22 r_j delta_j, r_j the first of 1, 2, 4 .. 64 with ln p(22 r delta_j) <= -40 (64
+ *          if none; the right tail is the slow one: it decays at the prior's curvature only, and 22 delta is not far enough where
+ *          delta is well below b and n is small);
+ *   nodes  u_k = (k - 40 m_j) s_j about the mode, k = 0 .. (10 + 22 r_j) 4 m_j, so x_k = l* + u_k runs from lo_j to hi_j = l* +
+ *          (88 r_j m_j) s_j and the mode is a node; p_k = p(u_k); trapezoid weights w_k = s_j, halved at both ends.
+ *   For delta_j <= 1/2 with the tail test met at r = 1 this is 129 nodes at delta / 4 on [l* - 10 delta, l* + 22 delta].
+ * Per-draw moments (sums in ascending k; the common factor s_j taken out of the ratios):
+ *   Z_j = sum w p;   E_j = l* + (sum w p u) / Z_j;   V_j = (sum w p u^2) / Z_j - (E_j - l*)^2  (= sum w p (x - E_j)^2 / Z_j);
+ *   S_j = e^{l*} (sum w p e^u) / Z_j, the conditional mean of sigma itself.
+ * Per-draw CDF C_j(x):  0 for x <= lo_j, 1 for x >= hi_j; between them N = max(1, ceil((x - lo_j) / s_j)), s_x = (x - lo_j) / N,
+ *   the trapezoid of p on the N + 1 nodes u = -10 delta_j + i s_x, i < N, and u = x - l* (ends halved, ascending i), less the first
+ *   Euler-Maclaurin end term s_x^2 / 12 (h_j'(x) p(x) - h_j'(lo_j) p(lo_j)), divided by Z_j, clamped to [0, 1].
+ *
+ * Outputs per entry (every pointer may be NULL; sums over the draws in bb_ppc_score's order):
+ *   n_terms    n
+ *   q_mean, q_sd     of the latent's own draws, as bb_fitness_rb's of s_j
+ *   rb_mean    mean_j E_j
+ *   rb_sd      sqrt(mean_j V_j + mean_j (E_j - rb_mean)^2), two-pass and centred
+ *   sigma_mean mean_j S_j
+ *   mode_mean  mean_j l*_j
+ *   quantiles  quantiles[entry][i], the probs[i] quantile of the mixture F(x) = mean_j C_j(x): lo = min_j lo_j, hi = max_j hi_j;
+ *              40 times x = lo + (hi - lo) / 2, F(x) < p ? lo = x : hi = x; the result is the last bracket's midpoint; NaN if any
+ *              l*_j, delta_j or Z_j is non-finite.  Quantiles are of logsigma; their exp are sigma's.
+ * An entry with n = 0 has the prior as its conditional through the same rule (SS = 0: l* = a, delta = b).  Non-finite parameters
+ * propagate by IEEE rules into the entries that use them; they disturb no other entry and are not an error.
+ *
+ * Options: block selects the latent block; draws, seed and the keying are bb_rb_opts' exactly (n_samples = 1 is allowed with
+ * draws).  BB_LOGSIGMA_RB_MAX_SAMPLES is the largest count for which (l*_j, delta_j, Z_j) -- three arrays where bb_fitness_rb has
+ * two -- and the reductions' partials fit the 160 KiB of LDS (derived next to the layout, csrc/bb_lsrb.h).
+ * An entry's results are a function of the handle's (mu, sigma) (or the supplied draws), the two logsigma priors, n_samples, seed
+ * and probs: bit-identical whatever the grid, the launch mode, the handle's internal latent order, the device count or the calls
+ * made before.  The handle's mu, omega, optimiser state, step counter and RNG position are untouched, bitwise.  BB_ERR_INVALID /
+ * BB_ERR_UNSUPPORTED for the options as bb_fitness_rb (there is no threshold), and BB_ERR_INVALID for an unknown block.  The POP
+ * block's chunk partials [chunks][n_samples] of the groups in flight are bounded to 256 MiB (slabs; a single group is worked
+ * whole).  Multi-device and sharded handles: as bb_ppc_bands.
+ * Out of scope: the conditional of logtau, which is not log-concave in logtau and needs another bracket. */
+#define BB_LOGSIGMA_BC 0
+#define BB_LOGSIGMA_POP 1
+#define BB_LOGSIGMA_RB_MAX_SAMPLES 5781
+typedef struct bb_logsigma_rb_opts {
+    int32_t block;            /* BB_LOGSIGMA_BC or BB_LOGSIGMA_POP                     */
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_LOGSIGMA_RB_MAX_SAMPLES */
+    int32_t n_quantiles;      /* 0 .. 8                                                */
+    int32_t reserved0;
+    const double* probs;      /* [n_quantiles] probabilities in (0, 1)                 */
+    uint64_t seed;            /* Philox key (draws == NULL)                            */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL   */
+} bb_logsigma_rb_opts;
+typedef struct bb_logsigma_rb_out {  /* every pointer may be NULL; [n_entries] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *sigma_mean, *mode_mean;
+    double* quantiles;               /* [n_entries][n_quantiles]                       */
+    int32_t* n_terms;                /* n                                              */
+} bb_logsigma_rb_out;
+int bb_logsigma_rb_shape(const bb_handle* h, int32_t block, int64_t* n_entries);
+int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const bb_logsigma_rb_out* out);
 
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array

@@ -473,6 +473,74 @@ function popmean_rb(h::Ptr{Cvoid}; n_samples::Int=1000, probs::Vector{Float64}=[
     return (n_members=n_members, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, p_pos=p_pos, p_neg=p_neg, quantiles=quantiles)
 end
 
+# Rao-Blackwellised marginals of the noise scales logsigma_bc / logsigma_pop (bb_logsigma_rb, include/barbay_hip.h): the
+# one-dimensional, log-concave full conditional of a log-scale integrated numerically per draw and averaged over the draws of
+# `fitness_rb`.  Field for field the Python binding's `bb_logsigma_rb_opts` / `bb_logsigma_rb_out` (barbay.jl_amd/_capi.py).  Like the
+# rest of this file it remains unexecuted.
+const BB_LOGSIGMA_BC = Int32(0)
+const BB_LOGSIGMA_POP = Int32(1)
+const BB_LOGSIGMA_RB_MAX_SAMPLES = 5781
+struct bb_logsigma_rb_opts
+    block::Int32
+    n_samples::Int32
+    n_quantiles::Int32
+    reserved0::Int32
+    probs::Ptr{Float64}
+    seed::UInt64
+    draws::Ptr{Float64}
+end
+struct bb_logsigma_rb_out
+    q_mean::Ptr{Float64}
+    q_sd::Ptr{Float64}
+    rb_mean::Ptr{Float64}
+    rb_sd::Ptr{Float64}
+    sigma_mean::Ptr{Float64}
+    mode_mean::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    n_terms::Ptr{Int32}
+end
+
+logsigma_block(block::Symbol) = block === :bc ? BB_LOGSIGMA_BC : block === :pop ? BB_LOGSIGMA_POP : error("logsigma_rb: block must be :bc or :pop")
+
+"""
+    logsigma_rb_shape(h; block=:bc) -> Int
+
+Entries of `logsigma_rb`: the length of the logsigma_bc (`:bc`) or logsigma_pop (`:pop`) block.
+"""
+function logsigma_rb_shape(h::Ptr{Cvoid}; block::Symbol=:bc)
+    n = Ref{Int64}(0)
+    check(ccall((:bb_logsigma_rb_shape, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int64}), h, logsigma_block(block), n))
+    return Int(n[])
+end
+
+"""
+    logsigma_rb(h; block=:bc, n_samples=1000, probs=[0.025, 0.5, 0.975], seed=0, draws=nothing) -> NamedTuple
+
+`h` a live `bb_handle` of any model.  Returns `n_terms, q_mean, q_sd, rb_mean, rb_sd, sigma_mean, mode_mean` (n_entries each) and
+`quantiles` (length(probs) x n_entries; of logsigma, their `exp` are sigma's).  Arguments as for `fitness_rb`, without a threshold.
+"""
+function logsigma_rb(h::Ptr{Cvoid}; block::Symbol=:bc, n_samples::Int=1000, probs::Vector{Float64}=[0.025, 0.5, 0.975],
+                     seed::Integer=0, draws::Union{Nothing,Matrix{Float64}}=nothing)
+    ne, nq = logsigma_rb_shape(h; block=block), length(probs)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("logsigma_rb: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    q_mean, q_sd, rb_mean, rb_sd, sigma_mean, mode_mean = (Vector{Float64}(undef, ne) for _ in 1:6)
+    quantiles = Matrix{Float64}(undef, nq, ne)
+    n_terms = Vector{Int32}(undef, ne)
+    GC.@preserve probs draws q_mean q_sd rb_mean rb_sd sigma_mean mode_mean quantiles n_terms begin
+        o = bb_logsigma_rb_opts(logsigma_block(block), Int32(n_samples), Int32(nq), Int32(0), nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL),
+                                UInt64(seed), draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws))
+        out = bb_logsigma_rb_out(pointer(q_mean), pointer(q_sd), pointer(rb_mean), pointer(rb_sd), pointer(sigma_mean), pointer(mode_mean),
+                                 nq > 0 ? pointer(quantiles) : Ptr{Float64}(C_NULL), pointer(n_terms))
+        check(ccall((:bb_logsigma_rb, LIB), Cint, (Ptr{Cvoid}, Ref{bb_logsigma_rb_opts}, Ref{bb_logsigma_rb_out}), h, o, out))
+    end
+    return (n_terms=n_terms, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, sigma_mean=sigma_mean, mode_mean=mode_mean,
+            quantiles=quantiles)
+end
+
 # Log-joint and gradient at several points in one call (bb_logdensity_grad_batch, include/barbay_hip.h): what a sampler that
 # steps an ensemble of walkers in lock-step asks of the model (`LogDensityProblems.logdensity_and_gradient`, W points at once).
 const BB_LOGP_MAX_BATCH = 64
