@@ -31,6 +31,8 @@ BB_THETA_RB_CHUNK = 64
 BB_POPMEAN_RB_CHUNK = 256
 BB_LOGSIGMA_RB_MAX_SAMPLES = 5781
 BB_LOGSIGMA_BLOCKS = {"bc": 0, "pop": 1}
+BB_LOGTAU_RB_MAX_SAMPLES = 5781
+BB_LOGTAU_MODES = {"full": 0, "collapsed": 1}
 BB_MATH_FN = {"exp": 0, "log": 1, "rcp": 2, "div": 3, "sqrt": 4, "softplus_sigmoid": 5, "sincospi": 6, "exp_nonpos": 7, "log_1to2": 8,
               "box_muller": 9}
 BB_ERR_UNSUPPORTED = -4
@@ -43,7 +45,7 @@ EXPORTS = [
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
-    "bb_logsigma_rb_shape", "bb_logsigma_rb",
+    "bb_logsigma_rb_shape", "bb_logsigma_rb", "bb_logtau_rb_shape", "bb_logtau_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
 ]
 
@@ -154,6 +156,18 @@ class bb_logsigma_rb_opts(C.Structure):
 
 class bb_logsigma_rb_out(C.Structure):
     _fields_ = [(k, _dp) for k in LS_UNITS] + [("quantiles", _dp), ("n_terms", C.POINTER(C.c_int32))]
+
+
+LT_UNITS = ("q_mean", "q_sd", "rb_mean", "rb_sd", "tau_mean", "pool_mean", "mode_mean")
+
+
+class bb_logtau_rb_opts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("n_samples", C.c_int32), ("n_quantiles", C.c_int32), ("reserved0", C.c_int32), ("probs", _dp),
+                ("seed", C.c_uint64), ("draws", _dp)]
+
+
+class bb_logtau_rb_out(C.Structure):
+    _fields_ = [(k, _dp) for k in LT_UNITS] + [("quantiles", _dp), ("n_terms", C.POINTER(C.c_int32)), ("n_two_modes", C.POINTER(C.c_int32))]
 
 
 class bb_chain_opts(C.Structure):
@@ -271,6 +285,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_logsigma_rb"):
         lib.bb_logsigma_rb_shape.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
         lib.bb_logsigma_rb.argtypes = [vp, C.POINTER(bb_logsigma_rb_opts), C.POINTER(bb_logsigma_rb_out)]
+    if hasattr(lib, "bb_logtau_rb"):
+        lib.bb_logtau_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
+        lib.bb_logtau_rb.argtypes = [vp, C.POINTER(bb_logtau_rb_opts), C.POINTER(bb_logtau_rb_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     if hasattr(lib, "bb_trace_begin"):
@@ -766,6 +783,40 @@ class Engine:
         out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
         out.n_terms = res["n_terms"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_logsigma_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def logtau_rb_shape(self) -> int:
+        """Entries of `logtau_rb`: the length of the logtau block (0 for the kinds that have none)."""
+        n = C.c_int64(0)
+        self._check(self._lib.bb_logtau_rb_shape(self._h, C.byref(n)))
+        return int(n.value)
+
+    def logtau_rb(self, mode: str = "collapsed", n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
+                  draws=None) -> Dict[str, np.ndarray]:
+        """Rao-Blackwellised marginal of every logtau of a hierarchical model (`bb_logtau_rb`; the entries are the units of
+        `fitness_rb`).  `mode="full"`: the full conditional given everything else, theta_tilde included; `mode="collapsed"`: with
+        theta_tilde integrated out against its prior -- the hierarchical-variance posterior.  Neither is log-concave and either can
+        have two modes; it is integrated numerically per draw on one grid over all of them and averaged over the draws of
+        `fitness_rb` (same arguments).  Returns q_mean, q_sd, rb_mean, rb_sd, tau_mean (the RB mean of tau itself), pool_mean (of
+        1 / (1 + n w tau^2): 1 pooled onto the group, 0 on its own), mode_mean [n_entries], quantiles [n_entries, len(probs)] (of
+        logtau; their exp are tau's), n_terms and n_two_modes (int32: the draws whose conditional kept two modes)."""
+        if mode not in BB_LOGTAU_MODES:
+            raise BarBayHipError(f"mode must be one of {sorted(BB_LOGTAU_MODES)}, got {mode!r}")
+        ro, p, _x = self._rb_opts(n_samples, probs, 0.0, seed, draws)
+        o = bb_logtau_rb_opts()
+        o.mode, o.n_samples, o.n_quantiles, o.probs, o.seed, o.draws = BB_LOGTAU_MODES[mode], ro.n_samples, ro.n_quantiles, ro.probs, ro.seed, ro.draws
+        n_entries = self.logtau_rb_shape()
+        res = {k: np.empty(n_entries) for k in LT_UNITS}
+        res["quantiles"] = np.empty((n_entries, p.shape[0]))
+        res["n_terms"] = np.empty(n_entries, dtype=np.int32)
+        res["n_two_modes"] = np.empty(n_entries, dtype=np.int32)
+        out = bb_logtau_rb_out()
+        for k in LT_UNITS:
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.n_terms = res["n_terms"].ctypes.data_as(C.POINTER(C.c_int32))
+        out.n_two_modes = res["n_two_modes"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_logtau_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,

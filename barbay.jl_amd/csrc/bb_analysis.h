@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
 // bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
-// bb_logsigma_rb (bb_lsrb.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
+// bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -1065,6 +1065,110 @@ extern "C" int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const 
     lap(6, 4);
 #ifdef BB_RB_TIMES
     fprintf(stderr, "[bb_logsigma_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, mixture %.3f ms, download %.3f ms\n", bc ? "bc" : "pop", n_entries, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
+}
+
+// ---- Rao-Blackwellised logtau marginals (bb_ltrb.h) ---------------------------------------------------------------------------------
+static_assert(BB_LOGTAU_RB_MAX_SAMPLES == BB_LT_SAMPLES_CAP && BB_LOGTAU_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES && BB_LOGTAU_FULL == BB_LT_FULL &&
+              BB_LOGTAU_COLLAPSED == BB_LT_COLLAPSED, "bb_logtau_rb limits");
+extern "C" int bb_logtau_rb_shape(const bb_handle* h, int64_t* n_entries) {
+    if (!h || !n_entries) return bb_fail(BB_ERR_INVALID, "null argument");
+    *n_entries = h->M.kind < BB_MODEL_GENOTYPE ? 0 : h->M.blk_hi[BK_LT] - h->M.blk_lo[BK_LT];
+    return BB_OK;
+}
+
+extern "C" int bb_logtau_rb(bb_handle* h, const bb_logtau_rb_opts* o, const bb_logtau_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->mode != BB_LOGTAU_FULL && o->mode != BB_LOGTAU_COLLAPSED) return bb_fail(BB_ERR_INVALID, "mode must be BB_LOGTAU_FULL or BB_LOGTAU_COLLAPSED");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    {   // bb_fitness_rb's option checks (no threshold here), with this call's own cap
+        bb_rb_opts ro;
+        memset(&ro, 0, sizeof ro);
+        ro.n_samples = 2; ro.n_quantiles = nq; ro.probs = o->probs; ro.draws = o->draws;
+        if (int rc = rb_check(&ro)) return rc;
+        const int ns_lo = o->draws ? 1 : 2;
+        if (ns < ns_lo || ns > BB_LOGTAU_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_LOGTAU_RB_MAX_SAMPLES);
+    }
+    if (h->M.kind == BB_MODEL_FITNESS || h->M.kind == BB_MODEL_MULTIENV)
+        return bb_fail(BB_ERR_UNSUPPORTED, "bb_logtau_rb applies to the hierarchical models only: model kind %d (%s) has no logtau", (int)h->M.kind,
+                       h->M.kind == BB_MODEL_FITNESS ? "BB_MODEL_FITNESS" : "BB_MODEL_MULTIENV");
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    LtArgs L;
+    memset(&L, 0, sizeof L);
+    RbArgs& A = L.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const long long n_entries = rb_units(h);      // (the logtau block has one entry per unit of bb_fitness_rb)
+    if (n_entries != h->M.blk_hi[BK_LT] - h->M.blk_lo[BK_LT]) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
+    if (rc) return rc;
+    int zb;
+    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    const DevPrior& dp = M.pri[BK_LT];            // Vector form: one (mean, 1 / std^2) for every entry
+    P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = nullptr; P.pri_ivar_e = nullptr;
+    L.mode = o->mode;
+    A.nq = nq;
+    A.n_units = n_entries;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+#ifdef BB_RB_TIMES             // diagnostics (tools/logtau_rb_rate.py): the call's phases, each drained before the next starts
+    timespec ct[5];
+    double cms[4] = {0, 0, 0, 0};
+    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int, int) {};
+#endif
+    lap(0, -1);
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ne = (size_t)n_entries;
+    // the row program's grid: its [BB_LT_TAB][ns] tables bounded to 256 MiB
+    long long nblk = std::max<long long>(1, std::min<long long>((long long)M.R * M.nb, 2LL * dh->cus));
+    while (nblk > 1 && (size_t)nblk * BB_LT_TAB * nsz * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    double* ddraws = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(A.ytab, (size_t)nblk * BB_LT_TAB * nsz);     // [nblk][10][ns]
+        c(A.unit, BB_LT_OUT * ne);                     // [8][n_entries]
+        c(A.quant, BB_RB_MAX_Q * ne);                  // [n_entries][8]
+        c(A.n_steps, (ne + 1) / 2);                    // [n_entries] ints
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    if (o->draws) {
+        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
+        P.draws = ddraws;
+        P.D = (long long)D;
+    }
+    lap(1, 0);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    if ((rc = freq_normalisers(dh, F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
+    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
+    lap(2, 1);
+    if (n_entries > 0 && (rc = o->mode == BB_LOGTAU_FULL ? launch(dh->stream, k_lt_full, (int)nblk, BB_SCORE_NT, (size_t)BB_LT_LDS_DOUBLES(ns), L)
+                                                        : launch(dh->stream, k_lt_collapsed, (int)nblk, BB_SCORE_NT, (size_t)BB_LT_LDS_DOUBLES(ns), L))) return rc;
+    lap(3, 2);
+    double* units[BB_LT_OUT - 1] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->tau_mean, out->pool_mean, out->mode_mean};
+    for (int k = 0; k < BB_LT_OUT - 1; ++k)
+        if (units[k] && ne && (rc = d2h(units[k], A.unit + (size_t)k * ne, ne * 8, dh->stream))) return rc;
+    if (out->n_two_modes && ne) {                      // (counted in a double on the device: exact up to 2^53)
+        std::vector<double> two(ne);
+        if ((rc = d2h(two.data(), A.unit + (size_t)(BB_LT_OUT - 1) * ne, ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        for (size_t g = 0; g < ne; ++g) out->n_two_modes[g] = (int32_t)two[g];
+    }
+    if (out->quantiles && nq && ne) {
+        std::vector<double> q(BB_RB_MAX_Q * ne);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        for (size_t g = 0; g < ne; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
+    }
+    if (out->n_terms && ne && (rc = d2h(out->n_terms, A.n_steps, ne * 4, dh->stream))) return rc;
+    rc = dsync(dh->stream);
+    lap(4, 3);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_logtau_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, mixture %.3f ms, download %.3f ms\n", o->mode == BB_LOGTAU_FULL ? "full" : "collapsed", n_entries, ns, nq, cms[0], cms[1], cms[2], cms[3]);
 #endif
     return rc;
 }

@@ -445,6 +445,14 @@ BB_KERNEL(BB_SCORE_NT, k_ls_pop, LsArgs L) {
     BB_CTX;
     bb_block_ls_pop(cx, L, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_lt_full, LtArgs L) {
+    BB_CTX;
+    bb_block_lt<BB_LT_FULL>(cx, L, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_lt_collapsed, LtArgs L) {
+    BB_CTX;
+    bb_block_lt<BB_LT_COLLAPSED>(cx, L, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

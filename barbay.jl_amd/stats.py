@@ -28,6 +28,8 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
                                                                   conditional sums over every barcode of the replicate (`bb_popmean_rb`)
     noise_marginals                                               the same for the noise scales logsigma of the mutants and of the time
                                                                   steps, whose conditional is integrated numerically (`bb_logsigma_rb`)
+    deviation_marginals                                           the same for logtau, the deviation scale of the hierarchical models,
+                                                                  whose conditional can have two modes (`bb_logtau_rb`)
 """
 from __future__ import annotations
 
@@ -606,6 +608,60 @@ def noise_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, block: 
         out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
     for i, p in enumerate(probs):
         out[f"sigma_q{100.0 * p:g}"] = np.exp(res["quantiles"][:, i])
+    return out
+
+
+def deviation_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, mode: str = "collapsed", model_kwargs: Optional[Dict] = None,
+                        n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
+                        id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                        rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                        device: int = 0, chain=None) -> pd.DataFrame:
+    """`fitness_marginals` for logtau, the deviation scale of the hierarchical models (the `bc_deviations` rows of the fit's frame):
+    how far a barcode or a replicate stands off its group, and the block where a mean-field Gaussian is least trustworthy -- the
+    fitness is theta + exp(logtau) theta_tilde, so logtau and theta_tilde enter the likelihood through their product only.
+    `mode="collapsed"` (the default) integrates theta_tilde out against its prior: the hierarchical-variance posterior;
+    `mode="full"` is the full conditional given everything else, theta_tilde included.  Neither is log-concave and either can have
+    two modes, one at the prior and one at the least-squares tau; the conditional is integrated numerically per draw on one grid
+    over all of them and averaged over n_samples joint draws of everything else (`bb_logtau_rb`, one device call; at most 5781
+    draws).  Arguments as for `fitness_marginals`, without a threshold.  A model without a logtau raises `BarBayError`.
+
+    Returns one line per logtau row, in the frame's order and with those rows' own labels (every column of the frame but `mean`
+    and `std`); then `n_terms` (0: the conditional is the prior), `q_mean`, `q_sd` (the draws' own logtau), `rb_mean`, `rb_sd`,
+    `sd_ratio` = rb_sd / q_sd, `mode_mean`, `tau_mean` (the RB mean of tau itself), `pool_mean` (of 1 / (1 + n w tau^2): 1 the unit
+    sits on its group, 0 it is on its own), `n_two_modes` (the draws whose conditional kept two modes), one column per probability
+    of `probs` named q2.5, q50, ... (quantiles of logtau) and their exp as tau_q2.5, tau_q50, ..."""
+    if mode not in ("full", "collapsed"):
+        raise BarBayError(f"mode must be 'full' or 'collapsed', got {mode!r}")
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        n_entries = e.logtau_rb_shape()
+        if n_entries == 0:
+            raise BarBayError(f"deviation_marginals applies to the hierarchical models only: {mname} has no logtau")
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        blk = df_advi.iloc[:e.D]
+        blk = blk[blk["vartype"] == "bc_deviations"]
+        if len(blk) != n_entries:
+            raise BarBayError(f"df_advi holds {len(blk)} bc_deviations rows, the model has {n_entries}")
+        res = e.logtau_rb(mode=mode, n_samples=n_samples, probs=probs, seed=seed, draws=draws)
+    out = blk.drop(columns=["mean", "std"]).reset_index(drop=True)
+    out["n_terms"] = res["n_terms"]
+    for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"] / res["q_sd"]
+    for k in ("mode_mean", "tau_mean", "pool_mean", "n_two_modes"):
+        out[k] = res[k]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
+    for i, p in enumerate(probs):
+        out[f"tau_q{100.0 * p:g}"] = np.exp(res["quantiles"][:, i])
     return out
 
 

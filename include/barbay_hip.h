@@ -502,8 +502,8 @@ int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
  * outside its range.  Multi-device and sharded handles: as bb_ppc_bands (the first device works on the gathered posterior; a shard
  * needs bb_set_params first).
  * The conditional of theta, the hyper-fitness of the hierarchical kinds: bb_theta_rb, below; that of the population mean fitness
- * sbar_t: bb_popmean_rb, below that; those of logsigma_bc and logsigma_pop: bb_logsigma_rb.  Out of scope: the conditional of
- * tau; any change to what the fit or an MCMC run report by default. */
+ * sbar_t: bb_popmean_rb, below that; those of logsigma_bc and logsigma_pop: bb_logsigma_rb; that of logtau: bb_logtau_rb.  Out of scope:
+ * any change to what the fit or an MCMC run report by default. */
 #define BB_RB_MAX_SAMPLES 8672
 typedef struct bb_rb_opts {
     int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
@@ -566,7 +566,7 @@ int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out);
  * BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb; BB_ERR_UNSUPPORTED, the message naming the model kind, for
  * BB_MODEL_FITNESS / BB_MODEL_MULTIENV.  The chunk partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB
  * (the groups are worked in slabs; a single group is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditional of tau (logsigma: bb_logsigma_rb). */
+ * The conditionals of logsigma: bb_logsigma_rb; of logtau: bb_logtau_rb. */
 #define BB_THETA_RB_CHUNK 64
 typedef struct bb_theta_rb_out {  /* every pointer may be NULL; [n_groups] unless noted */
     double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
@@ -622,7 +622,7 @@ int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out);
  * RNG position are untouched, bitwise.  BB_ERR_INVALID / BB_ERR_UNSUPPORTED for the options exactly as bb_fitness_rb.  The chunk
  * partials [chunks][2][n_samples] of the groups in flight are bounded to 256 MiB (the groups are worked in slabs; a single group
  * is worked whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditional of tau (logsigma: bb_logsigma_rb). */
+ * The conditionals of logsigma: bb_logsigma_rb; of logtau: bb_logtau_rb. */
 #define BB_POPMEAN_RB_CHUNK 256
 typedef struct bb_popmean_rb_out {   /* every pointer may be NULL; [n_groups] unless noted */
     double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
@@ -698,7 +698,7 @@ int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean_rb_out* ou
  * BB_ERR_UNSUPPORTED for the options as bb_fitness_rb (there is no threshold), and BB_ERR_INVALID for an unknown block.  The POP
  * block's chunk partials [chunks][n_samples] of the groups in flight are bounded to 256 MiB (slabs; a single group is worked
  * whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditional of logtau, which is not log-concave in logtau and needs another bracket. */
+ * The conditional of logtau, which is not log-concave in logtau and needs another bracket: bb_logtau_rb, below. */
 #define BB_LOGSIGMA_BC 0
 #define BB_LOGSIGMA_POP 1
 #define BB_LOGSIGMA_RB_MAX_SAMPLES 5781
@@ -718,6 +718,116 @@ typedef struct bb_logsigma_rb_out {  /* every pointer may be NULL; [n_entries] u
 } bb_logsigma_rb_out;
 int bb_logsigma_rb_shape(const bb_handle* h, int32_t block, int64_t* n_entries);
 int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const bb_logsigma_rb_out* out);
+
+/* Rao-Blackwellised marginals of logtau, the deviation scale of the hierarchical kinds (BB_MODEL_GENOTYPE, BB_MODEL_REPLICATE,
+ * BB_MODEL_MULTIENV_REPLICATE) -- the block where a mean-field Gaussian is least trustworthy: the fitness is non-centred,
+ * s_u = theta_g(u) + e^{logtau_u} theta_tilde_u, so logtau_u and theta_tilde_u enter the likelihood through their product only (the
+ * funnel); and the number that says how strongly a replicate or a barcode is pooled towards its group.  No reference counterpart.
+ *
+ * Entries (bb_logtau_rb_shape: n_entries = the length of the caller's logtau block; 0 for BB_MODEL_FITNESS / BB_MODEL_MULTIENV):
+ * unit u of bb_fitness_rb, same numbering, same T_u and n = n_u.  Per draw j: y_j (gamma, ln Z, sbar, ascending t from 0.0, the
+ * later time point's environment), w_j = exp(-2 logsigma_{u,j}), theta_j (the unit's hyper-fitness) and tt_j = theta_tilde_{u,j}
+ * are bb_fitness_rb's word for word; Y_j = y_j - n theta_j.  Prior (a, ib2 = 1 / b^2): the logtau_prior the handle holds (Vector
+ * form).  With x = e^l the log conditional density of draw j up to a constant is, by mode,
+ *   BB_LOGTAU_FULL       given everything else, theta_tilde included:   A = (1/2) (n w) (tt tt),  B = (w tt) Y
+ *       h(l)   = -(l - a)^2 ib2 / 2 - A x^2 + B x
+ *       h'(l)  = -(l - a) ib2 + x (B - 2A x),      h''(l) = -ib2 + x (B - 4A x)
+ *     The identity this rests on, at any point z: h' at z's own logtau_u = dlogp/dlogtau_u (bb_logdensity_grad's entry).
+ *   BB_LOGTAU_COLLAPSED  theta_tilde_u integrated out against its N(0, 1) prior (tt is not read): v = 1 / (n w),  q = (Y / n)^2,
+ *     c = q - v,  k = q + v,  s = x^2,  V = s + v
+ *       h(l)   = -(l - a)^2 ib2 / 2 - ln V / 2 - q / (2V)
+ *       h'(l)  = -(l - a) ib2 + (s / V) ((q - V) / V),      h''(l) = -ib2 + G(s),  G(s) = 2 (s / V) ((c v - s k) / V) / V
+ *     exp(h(l)) = the integral over tt of exp(h_FULL(l; tt)) N(tt; 0, 1), up to a factor free of l.
+ * An entry with n = 0 has the prior as its conditional through the same rule (h = -(l - a)^2 ib2 / 2, the data terms dropped); its
+ * w, tt, theta are not read, so a non-finite logsigma of such a unit does not reach it (bb_theta_rb's skip rule).
+ * Neither h is log-concave (over parameters of use about 60 % of the draws are not), and either can have two modes: one near the
+ * prior and one near the least-squares tau.  h' has at most three zeros.
+ *
+ * The rule (this is the definition, as bb_logsigma_rb's is its own).  Per draw:
+ * Segments.  The zeros l1 < l2 of h'', between which h' rises and outside of which it falls, and bounds L <= every zero of h' <= U:
+ *   FULL       B > 0:  t = ln(B / (2A)), L = min(a, t), U = max(a, t);  disc = B B - 16 A ib2; if disc > 0: r = sqrt(disc),
+ *              l1 = ln(2 ib2 / (B + r)), l2 = ln((B + r) / (8A)) (the roots of 4A x^2 - B x + ib2).  Otherwise (B <= 0, or NaN):
+ *              no l1, l2 (h is strictly log-concave); U = a, L = a - e^a (2A e^a - B) / ib2.
+ *   COLLAPSED  L = a - 1 / ib2 (h' >= -(l - a) ib2 - 1), U = a; if c > 0: U = max(a, ln(c) / 2), and G has its one maximum over
+ *              s > 0 at sp = v c / ((c + k) + sqrt(c c + c k + k k)); if G(sp) > ib2, the two solutions of G(s) = ib2 by 60
+ *              bisection steps each on the geometric mean, mid = sqrt(lo hi): the first from lo = ib2 v v / (2c), hi = sp with
+ *              G(mid) < ib2 ? lo = mid : hi = mid; the second from lo = sp, hi = c v / k with G(mid) > ib2 ? lo = mid : hi = mid;
+ *              l1, l2 = ln(sqrt(lo hi)) / 2 of the final brackets.
+ *   n = 0      one mode, l = a exactly; no iteration.
+ * Modes.  solve(lo, hi, x): up to 100 times  g = h'(x); g == 0 or NaN: done, the mode x + g;  g > 0 ? lo = x : hi = x;  xn = x - g / h''(x), replaced
+ *   by lo + (hi - lo) / 2 unless h''(x) < 0 and lo <= xn <= hi;  step = xn - x, x = xn;  stop once |step| <= 2^-40 (1 + |x|);
+ *   then once more xn = x - h'(x) / h''(x), taken if h''(x) < 0 and lo <= xn <= hi (the last step bounds the error by 2^-40 only).
+ *   With l1, l2: if h'(l1) < 0 the left mode solve(L, l1, L); if h'(l2) > 0 the right mode solve(l2, U, U).  Without them, or if
+ *   neither test holds: the one mode solve(L, U, U).  (The starts are the ends from which Newton on a convex or concave falling h'
+ *   approaches monotonically; the bracket guards the rest.)
+ * Kept modes.  With two modes, d = ln p(right - left) about the left one (p below); the global mode l* is the right one if d > 0,
+ *   else the left; both are kept iff |d| <= 40, else l* alone.  delta of a kept mode: 1 / sqrt(-h''(mode)).
+ * Density about l*:  p(u) = exp(h(l* + u) - h(l*)), the exponent in the form without cancelling large terms, g1 = ib2 (l* - a):
+ *   FULL       -u g1 - ib2 u^2 / 2 + e1 (D1 - A2 e1),   e1 = expm1(u),  A2 = A (x* x*),  D1 = B x* - 2 A2,  x* = e^{l*}
+ *   COLLAPSED  -u g1 - ib2 u^2 / 2 - log1p(y) / 2 + kap (y / (1 + y)),   y = rho expm1(2u),  rho = s* / V*,  kap = q / (2 V*)
+ *   n = 0      -u g1 - ib2 u^2 / 2
+ * Grid, one per draw, over all kept modes:  dmin the smaller delta;  m = max(1, ceil(2 dmin - 2^-20)), at most 64 (1 for a non-finite
+ *   dmin);  s0 = dmin / (4 m): a quarter of the smallest curvature scale, never above 1/8.  Ends: left of the leftmost kept mode ml
+ *   (its delta dl) e0 = ml - 8 r dl, r the first of 1, 2, 4 .. 4096 with ln p(e0 - l*) <= -40 (4096 if none); right of the
+ *   rightmost likewise with its own delta.  nl = ceil((l* - e0) / s0 - 2^-20), nr = ceil((e1 - l*) / s0 - 2^-20), each 1 unless the quotient is within
+ *   1 .. 1e9 (the 2^-20: with one mode the quotients are whole numbers but for rounding, which must not tip them over);
+ *   f = ceil((nl + nr) / 8192) (integer), s = f s0, nleft = ceil(nl / f), nright = ceil(nr / f): at most 8194 nodes per draw, the
+ *   hard cap, f > 1 only where a mode is narrower than about 1e-3 of the span (the step is then wider than a quarter delta and the
+ *   moments lose accuracy; not met in the tests).  Nodes u_k = (k - nleft) s, k = 0 .. nleft + nright, so lo_j = l* - nleft s,
+ *   hi_j = l* + nright s and the GLOBAL mode is a node.  The other kept mode need not be one: the integrand is analytic and has
+ *   decayed to e^-40 at both ends, so the trapezoid's error is set by the step against the narrowest feature, not by where the
+ *   nodes fall.  Weights s, halved at both ends.
+ * Per-draw moments (sums in ascending k):  z = sum w p,  Z_j = s z;  E_j = l* + (sum w p u) / z;  V_j = (sum w p u^2) / z -
+ *   (E_j - l*)^2;  T_j = e^{l*} (sum w p exp(u)) / z;  P_j = (sum w p / (1 + (n w e^{2 l*}) e^{2u})) / z, with e^{2u} = (e1 + 1)^2
+ *   (FULL) or expm1(2u) + 1 (COLLAPSED), and the factor 1 for n = 0 (so P_j = 1 exactly).
+ * Per-draw CDF C_j(x):  0 for x <= lo_j, 1 for x >= hi_j; between them N = max(1, ceil((x - lo_j) / s)), s_x = (x - lo_j) / N, the
+ *   trapezoid of p on the N + 1 nodes u = (lo_j - l*) + i s_x, i < N, and u = x - l* (ends halved, ascending i), less the first
+ *   Euler-Maclaurin end term s_x^2 / 12 (h'(x) p(x) - h'(lo_j) p(lo_j)), divided by Z_j, clamped to [0, 1].
+ *
+ * Outputs per entry (every pointer may be NULL; sums over the draws in bb_ppc_score's order):
+ *   n_terms     n
+ *   q_mean, q_sd     of the latent's own draws, as bb_fitness_rb's of s_j
+ *   rb_mean     mean_j E_j
+ *   rb_sd       sqrt(mean_j V_j + mean_j (E_j - rb_mean)^2), two-pass and centred
+ *   tau_mean    mean_j T_j, the RB mean of tau itself
+ *   pool_mean   mean_j P_j, the pooling factor 1 / (1 + n w tau^2): 1 the unit sits on its group, 0 it is on its own
+ *   mode_mean   mean_j l*_j (the global modes)
+ *   n_two_modes the draws whose conditional kept two modes
+ *   quantiles   quantiles[entry][i], the probs[i] quantile of the mixture F(x) = mean_j C_j(x): lo = min_j lo_j, hi = max_j hi_j;
+ *               40 times x = lo + (hi - lo) / 2, F(x) < p ? lo = x : hi = x; the result is the last bracket's midpoint; NaN if any
+ *               l*_j, s_j or Z_j is non-finite.  Quantiles are of logtau; their exp are tau's.
+ * Non-finite parameters propagate by IEEE rules into the entries that use them; they disturb no other entry and are not an error.
+ * (A finite corner that is not served: tt so small that A underflows to 0 while B > 0 -- |tt| below 1e-150 -- has U = inf.)
+ *
+ * Options: mode selects the conditional; draws, seed and the keying are bb_rb_opts' exactly (n_samples = 1 is allowed with draws).
+ * BB_LOGTAU_RB_MAX_SAMPLES is the largest count for which (l*_j, s_j, Z_j) and the reductions' partials fit the 160 KiB of LDS
+ * (derived next to the layout, csrc/bb_ltrb.h).  An entry's results are a function of the handle's (mu, sigma) (or the supplied
+ * draws), the logtau prior, n_samples, seed, mode and probs: bit-identical whatever the grid, the launch mode, the handle's
+ * internal latent order, the device count or the calls made before.  No atomics on doubles.  The handle's mu, omega, optimiser
+ * state, step counter and RNG position are untouched, bitwise.  BB_ERR_INVALID / BB_ERR_UNSUPPORTED for the options as
+ * bb_logsigma_rb, BB_ERR_INVALID for an unknown mode, BB_ERR_UNSUPPORTED, the message naming the model kind, for BB_MODEL_FITNESS /
+ * BB_MODEL_MULTIENV.  Multi-device and sharded handles: as bb_ppc_bands.
+ * Out of scope: the conditional of loglambda; a Matrix-form logtau_prior (the reference has none). */
+#define BB_LOGTAU_FULL 0
+#define BB_LOGTAU_COLLAPSED 1
+#define BB_LOGTAU_RB_MAX_SAMPLES 5781
+typedef struct bb_logtau_rb_opts {
+    int32_t mode;             /* BB_LOGTAU_FULL or BB_LOGTAU_COLLAPSED                 */
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_LOGTAU_RB_MAX_SAMPLES */
+    int32_t n_quantiles;      /* 0 .. 8                                                */
+    int32_t reserved0;
+    const double* probs;      /* [n_quantiles] probabilities in (0, 1)                 */
+    uint64_t seed;            /* Philox key (draws == NULL)                            */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL   */
+} bb_logtau_rb_opts;
+typedef struct bb_logtau_rb_out {    /* every pointer may be NULL; [n_entries] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *tau_mean, *pool_mean, *mode_mean;
+    double* quantiles;               /* [n_entries][n_quantiles]                       */
+    int32_t* n_terms;                /* n                                              */
+    int32_t* n_two_modes;            /* draws with two kept modes                      */
+} bb_logtau_rb_out;
+int bb_logtau_rb_shape(const bb_handle* h, int64_t* n_entries);
+int bb_logtau_rb(bb_handle* h, const bb_logtau_rb_opts* o, const bb_logtau_rb_out* out);
 
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array

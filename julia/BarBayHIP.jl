@@ -541,6 +541,79 @@ function logsigma_rb(h::Ptr{Cvoid}; block::Symbol=:bc, n_samples::Int=1000, prob
             quantiles=quantiles)
 end
 
+# Rao-Blackwellised marginals of logtau, the deviation scale of the hierarchical models (bb_logtau_rb, include/barbay_hip.h): the
+# one-dimensional conditional of logtau -- not log-concave, up to two modes -- integrated numerically per draw on one grid over all
+# kept modes and averaged over the draws of `fitness_rb`.  Field for field the Python binding's `bb_logtau_rb_opts` /
+# `bb_logtau_rb_out` (barbay.jl_amd/_capi.py).  Like the rest of this file it remains unexecuted.
+const BB_LOGTAU_FULL = Int32(0)
+const BB_LOGTAU_COLLAPSED = Int32(1)
+const BB_LOGTAU_RB_MAX_SAMPLES = 5781
+struct bb_logtau_rb_opts
+    mode::Int32
+    n_samples::Int32
+    n_quantiles::Int32
+    reserved0::Int32
+    probs::Ptr{Float64}
+    seed::UInt64
+    draws::Ptr{Float64}
+end
+struct bb_logtau_rb_out
+    q_mean::Ptr{Float64}
+    q_sd::Ptr{Float64}
+    rb_mean::Ptr{Float64}
+    rb_sd::Ptr{Float64}
+    tau_mean::Ptr{Float64}
+    pool_mean::Ptr{Float64}
+    mode_mean::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    n_terms::Ptr{Int32}
+    n_two_modes::Ptr{Int32}
+end
+
+logtau_mode(mode::Symbol) = mode === :full ? BB_LOGTAU_FULL : mode === :collapsed ? BB_LOGTAU_COLLAPSED : error("logtau_rb: mode must be :full or :collapsed")
+
+"""
+    logtau_rb_shape(h) -> Int
+
+Entries of `logtau_rb`: the length of the logtau block (0 for the models that have none).
+"""
+function logtau_rb_shape(h::Ptr{Cvoid})
+    n = Ref{Int64}(0)
+    check(ccall((:bb_logtau_rb_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), h, n))
+    return Int(n[])
+end
+
+"""
+    logtau_rb(h; mode=:collapsed, n_samples=1000, probs=[0.025, 0.5, 0.975], seed=0, draws=nothing) -> NamedTuple
+
+`h` a live `bb_handle` of a hierarchical model.  `mode=:full`: the full conditional given everything else; `:collapsed`: with
+theta_tilde integrated out against its prior.  Returns `n_terms, n_two_modes, q_mean, q_sd, rb_mean, rb_sd, tau_mean, pool_mean,
+mode_mean` (n_entries each) and `quantiles` (length(probs) x n_entries; of logtau, their `exp` are tau's).  Arguments as for
+`fitness_rb`, without a threshold.
+"""
+function logtau_rb(h::Ptr{Cvoid}; mode::Symbol=:collapsed, n_samples::Int=1000, probs::Vector{Float64}=[0.025, 0.5, 0.975],
+                   seed::Integer=0, draws::Union{Nothing,Matrix{Float64}}=nothing)
+    ne, nq = logtau_rb_shape(h), length(probs)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("logtau_rb: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    q_mean, q_sd, rb_mean, rb_sd, tau_mean, pool_mean, mode_mean = (Vector{Float64}(undef, ne) for _ in 1:7)
+    quantiles = Matrix{Float64}(undef, nq, ne)
+    n_terms = Vector{Int32}(undef, ne)
+    n_two_modes = Vector{Int32}(undef, ne)
+    GC.@preserve probs draws q_mean q_sd rb_mean rb_sd tau_mean pool_mean mode_mean quantiles n_terms n_two_modes begin
+        o = bb_logtau_rb_opts(logtau_mode(mode), Int32(n_samples), Int32(nq), Int32(0), nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL),
+                              UInt64(seed), draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws))
+        out = bb_logtau_rb_out(pointer(q_mean), pointer(q_sd), pointer(rb_mean), pointer(rb_sd), pointer(tau_mean), pointer(pool_mean),
+                               pointer(mode_mean), nq > 0 ? pointer(quantiles) : Ptr{Float64}(C_NULL), pointer(n_terms), pointer(n_two_modes))
+        check(ccall((:bb_logtau_rb, LIB), Cint, (Ptr{Cvoid}, Ref{bb_logtau_rb_opts}, Ref{bb_logtau_rb_out}), h, o, out))
+    end
+    return (n_terms=n_terms, n_two_modes=n_two_modes, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, tau_mean=tau_mean,
+            pool_mean=pool_mean, mode_mean=mode_mean, quantiles=quantiles)
+end
+
 # Log-joint and gradient at several points in one call (bb_logdensity_grad_batch, include/barbay_hip.h): what a sampler that
 # steps an ensemble of walkers in lock-step asks of the model (`LogDensityProblems.logdensity_and_gradient`, W points at once).
 const BB_LOGP_MAX_BATCH = 64
