@@ -33,6 +33,7 @@ BB_LOGSIGMA_RB_MAX_SAMPLES = 5781
 BB_LOGSIGMA_BLOCKS = {"bc": 0, "pop": 1}
 BB_LOGTAU_RB_MAX_SAMPLES = 5781
 BB_LOGTAU_MODES = {"full": 0, "collapsed": 1}
+BB_LOGLAMBDA_RB_MAX_SAMPLES = 5781
 BB_MATH_FN = {"exp": 0, "log": 1, "rcp": 2, "div": 3, "sqrt": 4, "softplus_sigmoid": 5, "sincospi": 6, "exp_nonpos": 7, "log_1to2": 8,
               "box_muller": 9}
 BB_ERR_UNSUPPORTED = -4
@@ -46,6 +47,7 @@ EXPORTS = [
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
     "bb_logsigma_rb_shape", "bb_logsigma_rb", "bb_logtau_rb_shape", "bb_logtau_rb",
+    "bb_loglambda_rb_shape", "bb_loglambda_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
 ]
 
@@ -170,6 +172,18 @@ class bb_logtau_rb_out(C.Structure):
     _fields_ = [(k, _dp) for k in LT_UNITS] + [("quantiles", _dp), ("n_terms", C.POINTER(C.c_int32)), ("n_two_modes", C.POINTER(C.c_int32))]
 
 
+LL_UNITS = ("q_mean", "q_sd", "rb_mean", "rb_sd", "lambda_mean", "mode_mean")
+
+
+class bb_loglambda_rb_opts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("n_quantiles", C.c_int32), ("probs", _dp), ("seed", C.c_uint64), ("draws", _dp),
+                ("rows", C.POINTER(C.c_int64)), ("n_rows", C.c_int64)]
+
+
+class bb_loglambda_rb_out(C.Structure):
+    _fields_ = [(k, _dp) for k in LL_UNITS] + [("quantiles", _dp), ("n_reads", C.POINTER(C.c_int64)), ("n_sides", C.POINTER(C.c_int32))]
+
+
 class bb_chain_opts(C.Structure):
     _fields_ = [
         ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("n_quantiles", C.c_int32), ("max_lag", C.c_int32),
@@ -288,6 +302,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_logtau_rb"):
         lib.bb_logtau_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_logtau_rb.argtypes = [vp, C.POINTER(bb_logtau_rb_opts), C.POINTER(bb_logtau_rb_out)]
+    if hasattr(lib, "bb_loglambda_rb"):
+        lib.bb_loglambda_rb_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.bb_loglambda_rb.argtypes = [vp, C.POINTER(bb_loglambda_rb_opts), C.POINTER(bb_loglambda_rb_out)]
     if hasattr(lib, "bb_chain_summary"):
         lib.bb_chain_summary.argtypes = [vp, C.POINTER(bb_chain_opts), C.c_int64, _dp, C.POINTER(bb_chain_out)]
     if hasattr(lib, "bb_trace_begin"):
@@ -817,6 +834,46 @@ class Engine:
         out.n_terms = res["n_terms"].ctypes.data_as(C.POINTER(C.c_int32))
         out.n_two_modes = res["n_two_modes"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_logtau_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def loglambda_rb_shape(self) -> Tuple[int, int]:
+        """(n_rows, n_cols) of `loglambda_rb`: the rows and time points of `freq_bands`."""
+        n, c = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.bb_loglambda_rb_shape(self._h, C.byref(n), C.byref(c)))
+        return int(n.value), int(c.value)
+
+    def loglambda_rb(self, n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0, draws=None,
+                     rows=None) -> Dict[str, np.ndarray]:
+        """Rao-Blackwellised marginal of the log-rates loglambda (`bb_loglambda_rb`), per (row, time point) of `freq_bands`: the
+        full conditional of a log-rate -- its prior, its Poisson term and the ratio terms of the steps its time point bounds, those
+        of every other barcode through the row normaliser -- is one-dimensional, skewed for low counts and not necessarily
+        log-concave; it is integrated numerically per draw on one grid over all its modes and averaged over the draws of
+        `fitness_rb` (same arguments).  `rows`: the rows wanted, strictly ascending (all).  Returns q_mean, q_sd, rb_mean, rb_sd,
+        lambda_mean (the RB mean of lambda itself), mode_mean [n_rows, n_cols], quantiles [n_rows, n_cols, len(probs)], n_reads
+        (int64, the observed count) and n_sides (int32: the steps bounding the time point); cells past a shorter replicate's last
+        time point are NaN / 0."""
+        ro, p, _x = self._rb_opts(n_samples, probs, 0.0, seed, draws)
+        o = bb_loglambda_rb_opts()
+        o.n_samples, o.n_quantiles, o.probs, o.seed, o.draws = ro.n_samples, ro.n_quantiles, ro.probs, ro.seed, ro.draws
+        n_rows, n_cols = self.loglambda_rb_shape()
+        rr = None
+        if rows is not None:
+            rr = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            o.rows, o.n_rows = rr.ctypes.data_as(C.POINTER(C.c_int64)), rr.shape[0]
+            if rr.shape[0] == 0:                      # (an empty array has no address to give)
+                o.rows = (C.c_int64 * 1)()
+            n_rows = rr.shape[0]
+        res = {k: np.empty((n_rows, n_cols)) for k in LL_UNITS}
+        res["quantiles"] = np.empty((n_rows, n_cols, p.shape[0]))
+        res["n_reads"] = np.empty((n_rows, n_cols), dtype=np.int64)
+        res["n_sides"] = np.empty((n_rows, n_cols), dtype=np.int32)
+        out = bb_loglambda_rb_out()
+        for k in LL_UNITS:
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.n_reads = res["n_reads"].ctypes.data_as(C.POINTER(C.c_int64))
+        out.n_sides = res["n_sides"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_loglambda_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def chain_summary(self, chain, probs: Sequence[float] = (0.025, 0.25, 0.5, 0.75, 0.975), max_lag: int = 0,

@@ -1173,6 +1173,164 @@ extern "C" int bb_logtau_rb(bb_handle* h, const bb_logtau_rb_opts* o, const bb_l
     return rc;
 }
 
+// ---- Rao-Blackwellised loglambda marginals (bb_llrb.h) ------------------------------------------------------------------------------
+static_assert(BB_LOGLAMBDA_RB_MAX_SAMPLES == BB_LL_SAMPLES_CAP && BB_LOGLAMBDA_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_loglambda_rb limits");
+extern "C" int bb_loglambda_rb_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols) { return bb_freq_shape(h, n_rows, n_cols); }
+
+extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, const bb_loglambda_rb_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    {   // bb_fitness_rb's option checks (no threshold here), with this call's own cap
+        bb_rb_opts ro;
+        memset(&ro, 0, sizeof ro);
+        ro.n_samples = 2; ro.n_quantiles = nq; ro.probs = o->probs; ro.draws = o->draws;
+        if (int rc = rb_check(&ro)) return rc;
+        const int ns_lo = o->draws ? 1 : 2;
+        if (ns < ns_lo || ns > BB_LOGLAMBDA_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_LOGLAMBDA_RB_MAX_SAMPLES);
+    }
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    const long long n_all = (long long)M.R * M.B;
+    const int n_cols = freq_cols(h);
+    const long long n_req = o->rows ? o->n_rows : n_all;
+    if (o->rows) {
+        if (n_req < 0) return bb_fail(BB_ERR_INVALID, "n_rows must not be negative");
+        for (long long x = 0; x < n_req; ++x)
+            if (o->rows[x] < 0 || o->rows[x] >= n_all || (x > 0 && o->rows[x] <= o->rows[x - 1]))
+                return bb_fail(BB_ERR_INVALID, "rows must be bb_freq_bands rows in 0..%lld, strictly ascending", n_all - 1);
+    }
+    if (n_req == 0) return BB_OK;
+    LlArgs L;
+    memset(&L, 0, sizeof L);
+    RbArgs& A = L.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
+    if (rc) return rc;
+    int zb;
+    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, nr = (size_t)n_req, ne = nr * (size_t)n_cols, nch = (size_t)F.nchunks, ng = (size_t)M.nt1;
+    A.nq = nq;
+    A.n_units = (long long)ne;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+    L.n_req = n_req;
+    L.n_cols = n_cols;
+    L.quirk = M.quirk;
+#ifdef BB_LLRB_TIMES           // diagnostics (tools/loglambda_rb_rate.py): the call's phases, each drained before the next starts
+    timespec ct[7];
+    double cms[5] = {0, 0, 0, 0, 0};
+    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
+#else
+    auto lap = [](int, int) {};
+#endif
+    lap(0, -1);
+    // The entries' constants, in the order of the result: the prior element and the count of (row, t).  Both lie in the handle in its
+    // own barcode order ([B][T_r] per replicate, the mutants possibly regrouped); the rows are the caller's.
+    const DevPrior& dp = M.pri[BK_L];
+    long long ncnt = 0;
+    for (int r = 0; r < M.R; ++r) ncnt += (long long)M.T[r] * M.B;
+    std::vector<unsigned> cnt((size_t)ncnt);
+    std::vector<double> pri;
+    if ((rc = d2h(cnt.data(), M.counts, (size_t)ncnt * 4, dh->stream))) return rc;
+    if (dp.mean_e) {
+        pri.resize(2 * (size_t)ncnt);
+        if ((rc = d2h(pri.data(), dp.mean_e, (size_t)ncnt * 8, dh->stream)) || (rc = d2h(pri.data() + ncnt, dp.inv_var_e, (size_t)ncnt * 8, dh->stream))) return rc;
+    }
+    if ((rc = dsync(dh->stream))) return rc;
+    std::vector<long long> own((size_t)M.nb);      // the caller's mutant -> the handle's
+    for (long long m = 0; m < M.nb; ++m) own[(size_t)(h->perm_m.empty() ? m : h->perm_m[(size_t)m])] = m;
+    std::vector<double> ent(3 * ne, 0.0);
+    std::vector<int64_t> reads(ne, 0);
+    std::vector<int32_t> sides(ne, 0);
+    std::vector<char> live(ne, 0);                 // 0: a cell t >= T_r of a shorter replicate
+    for (size_t x = 0; x < nr; ++x) {
+        const long long row = o->rows ? o->rows[x] : (long long)x;
+        const int r = (int)(row / M.B), T = M.T[r];
+        const long long b = row % M.B, bc = b < M.nn ? b : M.nn + own[(size_t)(b - M.nn)];
+        for (int t = 0; t < T; ++t) {
+            const size_t e = x * (size_t)n_cols + t, at = (size_t)(M.cnt_off[r] + bc * T + t), pat = (size_t)(M.off_l[r] - M.blk_lo[BK_L] + bc * T + t);
+            ent[e] = dp.mean_e ? pri[pat] : dp.mean;
+            ent[ne + e] = dp.mean_e ? pri[(size_t)ncnt + pat] : dp.inv_var;
+            ent[2 * ne + e] = (double)cnt[at];
+            reads[e] = (int64_t)cnt[at];
+            sides[e] = (t + 1 < T) + (t >= 1);
+            live[e] = 1;
+        }
+    }
+    // the steps in flight: their chunk partials bounded to 256 MiB (a single step is worked whole whatever it takes)
+    const size_t slab = std::min(ng, std::max<size_t>(1, ((size_t)256 << 20) / (nch * 2 * nsz * 8)));
+    // the entry program's grid: as the row program's, its [BB_LL_TAB][ns] tables bounded to 256 MiB
+    long long nblk = std::max<long long>(1, std::min<long long>(n_req, 2LL * dh->cus));
+    while (nblk > 1 && (size_t)nblk * BB_LL_TAB * nsz * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    double* ddraws = nullptr;
+    double* dent = nullptr;
+    long long* drows = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(A.ytab, (size_t)nblk * BB_LL_TAB * nsz);     // [nblk][11][ns]
+        c(L.part, slab * nch * 2 * nsz);               // [steps in flight][nchunks][2][ns]
+        c(L.ab, ng * 2 * nsz);                         // [nt1][2][ns]
+        c(A.unit, BB_RB_OUT * ne);                     // [6][n_entries]
+        c(A.quant, BB_RB_MAX_Q * ne);                  // [n_entries][8]
+        c(dent, 3 * ne);                               // [3][n_entries]: a, 1 / std^2, R
+        c(drows, o->rows ? nr : 0);                    // [n_req] 64-bit rows
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    if ((rc = h2d(dent, ent.data(), 3 * ne * 8, dh->stream))) return rc;
+    L.ent = dent;
+    if (o->rows) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "rows are passed on as they are");
+        if ((rc = h2d(drows, o->rows, nr * 8, dh->stream))) return rc;
+        L.rows = drows;
+    }
+    if (o->draws) {
+        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
+        P.draws = ddraws;
+        P.D = (long long)D;
+    }
+    lap(1, 0);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    if ((rc = freq_normalisers(dh, F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
+    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
+    lap(2, 1);
+    for (size_t g0 = 0; g0 < ng; g0 += slab) {
+        const size_t g1 = std::min(ng, g0 + slab);
+        L.g0 = (long long)g0; L.g1 = (long long)g1;
+        if ((rc = launch(dh->stream, k_ll_part, (int)std::min<size_t>((g1 - g0) * nch, (size_t)1 << 20), BB_SCORE_NT, 0, L))) return rc;
+        const int gs = (int)std::max<size_t>(1, std::min<size_t>(((g1 - g0) * nsz + 255) / 256, 4096));
+        if ((rc = launch(dh->stream, k_ll_sum, gs, 256, 0, L))) return rc;
+    }
+    lap(3, 2);
+    if ((rc = launch(dh->stream, k_ll, (int)nblk, BB_SCORE_NT, (size_t)BB_LL_LDS_DOUBLES(ns), L))) return rc;
+    lap(4, 3);
+    // cells t >= T_r of a shorter replicate: the entry program leaves them alone; NaN here
+    double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->lambda_mean, out->mode_mean};
+    for (int k = 0; k < BB_RB_OUT; ++k) {
+        if (!units[k]) continue;
+        if ((rc = d2h(units[k], A.unit + (size_t)k * ne, ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        for (size_t e = 0; e < ne; ++e) if (!live[e]) units[k][e] = NAN;
+    }
+    if (out->quantiles && nq) {
+        std::vector<double> q(BB_RB_MAX_Q * ne);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        for (size_t e = 0; e < ne; ++e)
+            for (int i = 0; i < nq; ++i) out->quantiles[e * nq + i] = live[e] ? q[e * BB_RB_MAX_Q + i] : NAN;
+    }
+    if (out->n_reads) memcpy(out->n_reads, reads.data(), ne * sizeof(int64_t));
+    if (out->n_sides) memcpy(out->n_sides, sides.data(), ne * sizeof(int32_t));
+    rc = dsync(dh->stream);
+    lap(5, 4);
+#ifdef BB_LLRB_TIMES
+    fprintf(stderr, "[bb_loglambda_rb %lld rows of %lld, %d columns, %d chunks, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, tables %.3f ms, entries %.3f ms, download %.3f ms\n", n_req, n_all, n_cols, F.nchunks, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+#endif
+    return rc;
+}
+
 // ---- chain diagnostics (bb_chain.h) --------------------------------------------------------------------------------------------
 static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRIDE && BB_CHAIN_LAG_BATCH == BB_CHAIN_LAGS &&
               2 * BB_CHAIN_MAX_Q <= BB_PPC_MAX_TGT, "bb_chain_summary limits");

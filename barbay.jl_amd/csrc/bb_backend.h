@@ -453,6 +453,18 @@ BB_KERNEL(BB_SCORE_NT, k_lt_collapsed, LtArgs L) {
     BB_CTX;
     bb_block_lt<BB_LT_COLLAPSED>(cx, L, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_ll_part, LlArgs L) {
+    BB_CTX;
+    bb_block_ll_part(cx, L, BB_GRID);
+}
+BB_KERNEL(256, k_ll_sum, LlArgs L) {
+    BB_CTX;
+    bb_block_ll_sum(cx, L, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_ll, LlArgs L) {
+    BB_CTX;
+    bb_block_ll(cx, L, BB_GRID);
+}
 BB_KERNEL(BB_CHAIN_TNT, k_chain_transpose, ChainArgs C) {
     BB_CTX;
     bb_block_chain_transpose(cx, C, BB_GRID);

@@ -22,6 +22,7 @@
 #include "bb_rb.h"
 #include "bb_lsrb.h"
 #include "bb_ltrb.h"
+#include "bb_llrb.h"
 #include "bb_chain.h"
 #include "bb_trace.h"
 #include "bb_logp.h"

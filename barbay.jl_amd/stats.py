@@ -665,6 +665,70 @@ def deviation_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, mod
     return out
 
 
+def abundance_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, barcodes: Optional[Sequence] = None,
+                        model_kwargs: Optional[Dict] = None, n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
+                        id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                        rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                        device: int = 0, chain=None) -> pd.DataFrame:
+    """`fitness_marginals` for the log-rates loglambda (the `log_poisson` rows of the fit's frame, most of its latents): which
+    low-count trajectories the fit's frequency bands can be trusted for.  For a barcode read a handful of times the full conditional
+    of its log-rate is skewed like a log-gamma density and need not have a single mode; mean-field gives it a symmetric +- and cuts
+    its coupling to the barcode's fitness, to the noise scale and, through the time point's normaliser, to every other barcode.  The
+    conditional is integrated numerically per draw on one grid over all its modes and averaged over n_samples joint draws of
+    everything else (`bb_loglambda_rb`, one device call; at most 5781 draws).  `barcodes`: the ids wanted (every replicate of them;
+    default all) -- the conditionals still read every barcode.  Other arguments as for `noise_marginals`.
+
+    Returns one line per (id, rep, time point), in the frame's order and with those rows' own labels (every column of the frame but
+    `mean` and `std`); then `time` (0-based index of the time point), `n_reads` (the observed count), `n_sides` (the steps that
+    bound the time point), `q_mean`, `q_sd` (the draws' own loglambda), `rb_mean`, `rb_sd`, `sd_ratio` = rb_sd / q_sd,
+    `lambda_mean` (the RB mean of lambda itself), `mode_mean` and one column per probability of `probs` named q2.5, q50, ...
+    (quantiles of loglambda)."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        n_rows, n_cols = e.loglambda_rb_shape()
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        Ts = [np.asarray(c).shape[0] for c in bayes_model.counts]
+        R = len(Ts)
+        B = n_rows // R
+        blk = df_advi.iloc[:e.D]
+        blk = blk[blk["vartype"] == "log_poisson"]
+        if len(blk) != B * sum(Ts):
+            raise BarBayError(f"df_advi holds {len(blk)} log_poisson rows, the model has {B * sum(Ts)}")
+        rows = None
+        if barcodes is not None:
+            ids = list(arrays.neutral_ids) + list(arrays.bc_ids)          # the data columns: neutrals first
+            want = set(barcodes)
+            missing = want - set(ids)
+            if missing:
+                raise BarBayError(f"barcodes not in the data: {sorted(missing, key=str)[:5]}")
+            colsel = [b for b, x in enumerate(ids) if x in want]
+            rows = np.array([r * B + b for r in range(R) for b in colsel], dtype=np.int64)
+        res = e.loglambda_rb(n_samples=n_samples, probs=probs, seed=seed, draws=draws, rows=rows)
+    rr = np.arange(n_rows) if rows is None else rows
+    rep, col = rr // B, rr % B
+    T_of = np.asarray(Ts)[rep]
+    start = np.concatenate([[0], np.cumsum(np.asarray(Ts) * B)])[rep] + col * T_of      # the row's first line in the block
+    live = np.arange(n_cols)[None, :] < T_of[:, None]
+    at = (start[:, None] + np.arange(n_cols)[None, :])[live]
+    out = blk.drop(columns=["mean", "std"]).iloc[at].reset_index(drop=True)
+    out["time"] = np.broadcast_to(np.arange(n_cols)[None, :], live.shape)[live]
+    for k in ("n_reads", "n_sides", "q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k][live]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"][live] / res["q_sd"][live]
+    out["lambda_mean"], out["mode_mean"] = res["lambda_mean"][live], res["mode_mean"][live]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][..., i][live]
+    return out
+
+
 def pit_histogram(scores: pd.DataFrame, bins: int = 10) -> pd.DataFrame:
     """Calibration of the predictive: counts of the `pit` column of `logfreq_ratio_ppc_scores` in `bins` equal bins of [0, 1], for
     the neutral and the mutant barcodes separately (unscored lines left out).  Flat: calibrated; U-shaped: the predictive is too

@@ -502,8 +502,8 @@ int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
  * outside its range.  Multi-device and sharded handles: as bb_ppc_bands (the first device works on the gathered posterior; a shard
  * needs bb_set_params first).
  * The conditional of theta, the hyper-fitness of the hierarchical kinds: bb_theta_rb, below; that of the population mean fitness
- * sbar_t: bb_popmean_rb, below that; those of logsigma_bc and logsigma_pop: bb_logsigma_rb; that of logtau: bb_logtau_rb.  Out of scope:
- * any change to what the fit or an MCMC run report by default. */
+ * sbar_t: bb_popmean_rb, below that; those of logsigma_bc and logsigma_pop: bb_logsigma_rb; that of logtau: bb_logtau_rb; that of
+ * loglambda: bb_loglambda_rb.  Out of scope: any change to what the fit or an MCMC run report by default. */
 #define BB_RB_MAX_SAMPLES 8672
 typedef struct bb_rb_opts {
     int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
@@ -698,7 +698,8 @@ int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean_rb_out* ou
  * BB_ERR_UNSUPPORTED for the options as bb_fitness_rb (there is no threshold), and BB_ERR_INVALID for an unknown block.  The POP
  * block's chunk partials [chunks][n_samples] of the groups in flight are bounded to 256 MiB (slabs; a single group is worked
  * whole).  Multi-device and sharded handles: as bb_ppc_bands.
- * The conditional of logtau, which is not log-concave in logtau and needs another bracket: bb_logtau_rb, below. */
+ * The conditional of logtau, which is not log-concave in logtau and needs another bracket: bb_logtau_rb, below; that of loglambda:
+ * bb_loglambda_rb, below that. */
 #define BB_LOGSIGMA_BC 0
 #define BB_LOGSIGMA_POP 1
 #define BB_LOGSIGMA_RB_MAX_SAMPLES 5781
@@ -807,7 +808,7 @@ int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const bb_logsigma
  * state, step counter and RNG position are untouched, bitwise.  BB_ERR_INVALID / BB_ERR_UNSUPPORTED for the options as
  * bb_logsigma_rb, BB_ERR_INVALID for an unknown mode, BB_ERR_UNSUPPORTED, the message naming the model kind, for BB_MODEL_FITNESS /
  * BB_MODEL_MULTIENV.  Multi-device and sharded handles: as bb_ppc_bands.
- * Out of scope: the conditional of loglambda; a Matrix-form logtau_prior (the reference has none). */
+ * The conditional of loglambda: bb_loglambda_rb, below.  Out of scope: a Matrix-form logtau_prior (the reference has none). */
 #define BB_LOGTAU_FULL 0
 #define BB_LOGTAU_COLLAPSED 1
 #define BB_LOGTAU_RB_MAX_SAMPLES 5781
@@ -828,6 +829,117 @@ typedef struct bb_logtau_rb_out {    /* every pointer may be NULL; [n_entries] u
 } bb_logtau_rb_out;
 int bb_logtau_rb_shape(const bb_handle* h, int64_t* n_entries);
 int bb_logtau_rb(bb_handle* h, const bb_logtau_rb_opts* o, const bb_logtau_rb_out* out);
+
+/* Rao-Blackwellised marginals of loglambda, the log-rates: T B of the D latents, and the block where a Gaussian q is most doubtful
+ * for the barcodes read a handful of times -- the full conditional of such a log-rate is skewed like a log-gamma density, and
+ * mean-field cuts its coupling to the barcode's fitness, to the noise scale and, through the row normaliser, to every other
+ * barcode of the time point.  No reference counterpart (the terms: src/model_fitness_normal.jl:209-270 and its four siblings).
+ *
+ * Entries (bb_loglambda_rb_shape: n_rows, n_cols = bb_freq_shape's): (row, t), row = r B + b the rows of bb_freq_bands (b the data
+ * column, neutrals first, then the mutants in the caller's order), t < T_r the time point.  Per draw j (bb_fitness_rb's draws) let
+ * x0 be the draw of ll_{r,t,b}, L_t = ln Z_{r,t,j} by the 256-column rule of bb_freq_bands (bb_fitness_rb's ln Z word for word) and
+ * f0 = exp(x0 - L_t).  For a candidate x:  xi = x - x0,  delta(xi) = log1p(f0 expm1(xi)) = ln Z_t(x) - L_t.
+ * A step k of the replicate joins the time points k and k + 1.  Every data column i has at step k a weight w_{i,k}, a mean mu_{i,k}
+ * and a residual rho_{i,k} = gamma_{i,k} - mu_{i,k},  gamma_{i,k} = (ll_{k+1,i} - ll_{k,i}) - (L_{k+1} - L_k), bb_fitness_rb's gamma:
+ *   neutral i            w = exp(-2 logsigmabar_g),  rho = gamma + sbar_g,  g the group whose s_pop / logsigma_pop entries
+ *                        bb_popmean_rb's group table pairs with (k, i): g = (r, k); under BB_FLAG_RAGGED_METHOD the group
+ *                        (r, (i (T_r - 1) + k) div n_neutral), the inverse of that table's (t, b) = (x mod (T_r - 1), x div (T_r - 1));
+ *   mutant i = n_neutral + m   its bb_fitness_rb unit u of environment env_r(k + 1):  w = exp(-2 logsigma_u),
+ *                        rho = (gamma + sbar_{r,k}) - s_u,  s_u the unit's fitness draw (theta + exp(logtau) theta_tilde for the
+ *                        hierarchical kinds), the order of operations bb_logsigma_rb's d_t.
+ * Two tables per (r, k, j):  A_k = sum_i w_{i,k},  B_k = sum_i w_{i,k} rho_{i,k}, over all data columns in chunks of 256
+ * consecutive columns, a chunk from 0.0 in index order, the chunks from 0.0 in chunk order.  No atomics on doubles.
+ * With (a, ib2 = 1 / std^2) the loglambda_prior element as the handle holds it (Vector or Matrix form; a Matrix form follows its
+ * latent through any regrouping) and R = counts_{r,t,b}, the log conditional density of draw j is, up to a constant,
+ *   h(x) - h(x0) = -ib2/2 [(x - a)^2 - (x0 - a)^2] + R xi - e^{x0} expm1(xi)
+ *      - 1/2 [  2 B_t delta     + A_t delta^2     + w_{b,t}   (xi^2 - 2 xi (rho_{b,t}   + delta)) ]      (only if t < T_r - 1)
+ *      - 1/2 [ -2 B_{t-1} delta + A_{t-1} delta^2 + w_{b,t-1} (xi^2 + 2 xi (rho_{b,t-1} - delta)) ]      (only if t >= 1)
+ * (the Poisson total and the multinomial collapse exactly to R x - e^x; the terms in delta are the ratio terms of every barcode
+ * of the time point, reached through the normaliser; no "total minus own term" subtraction is needed).
+ * The identity this rests on, at any point z:  h'(x0) = dlogp/dll_{r,t,b} (bb_logdensity_grad's entry)
+ *   = -ib2 (x0 - a) + R - e^{x0} - (B_t f0 - w_{b,t} rho_{b,t}) + (B_{t-1} f0 - w_{b,t-1} rho_{b,t-1}),  the brackets as above.
+ * h is not log-concave in general: the normaliser terms add the curvature -(A delta'^2 + (A delta +- B) delta''), whose second
+ * piece takes the sign of the summed residuals and can rival the Poisson curvature e^x for counts of a few reads.
+ *
+ * The rule (this is the definition, as bb_logtau_rb's is its own).  Per draw:
+ * Folded form.  A missing side contributes exact zeros to  As = A_t + A_{t-1},  Bs = B_t - B_{t-1},  ws = w_{b,t} + w_{b,t-1},
+ *   wr = w_{b,t} rho_{b,t} - w_{b,t-1} rho_{b,t-1}  (each: the t side, then the t - 1 side).  About a base point x (first x0) with
+ *   its f0 = e^x / Z_t(x), u the offset from it, em = expm1(u), delta = log1p(f0 em), f = delta' = f0 (em + 1) / (1 + f0 em):
+ *     g(u)   = -(ib2/2) (u (u + 2 (x - a))) + R u - e^x em - Bs delta - (As/2) delta^2 - (ws/2) u^2 + u wr + ws (u delta)
+ *     g'(u)  = -ib2 (u + (x - a)) + R - e^x (em + 1) - (Bs + As delta) f - ws u + wr + ws (delta + u f)
+ *     g''(u) = -ib2 - e^x (em + 1) - Bs ff - As (f f + delta ff) - ws + ws (2 f + u ff),   ff = f (1 - f)
+ *   which is h(x + u) - h(x) without a difference of large terms.  Moving the base to x + u keeps the form (anchor):
+ *     Bs <- Bs + As delta(u) - ws u,   wr <- wr + ws (delta(u) - u),   f0 <- f(u),   x <- x + u,   e^x recomputed.
+ * Bracket, about x0, holding every zero of g'.  With Bp = max(Bs, 0), Bm = max(-Bs, 0), sl = ib2 + ws (1 - f0),
+ *   C0 = -ib2 (x0 - a) + R + wr + ws log1p(-f0) and  low(L) = (C0 - e^{x0} e^L - Bp f(L)) / sl - L:  for u < L <= 0 one has
+ *   e^u <= e^L, f(u) <= f(L), 1 - f(u) >= 1 - f0, delta >= log1p(-f0), -As delta f >= 0, so g'(u) >= -sl u + sl (low(L) + L) > 0
+ *   wherever low(L) >= 0; low falls as L rises.  l = low(0); if l < 0 (else lo = 0): l is such an L and 0 is not; 30 times
+ *   mid = l + (up - l) / 2 from up = 0, low(mid) >= 0 ? l = mid : up = mid; lo = l - 1/8.  (The end follows e^x down: a draw far
+ *   above its count -- a fit far from converged -- would otherwise put lo at -e^{x0} / sl.)  For u > 0: f <= 1, delta <= u, As >= ws, so
+ *   g'(u) <= K - ib2 u and g'(u) <= K - e^{x0} e^u with K = R + Bm + wr - ib2 (x0 - a):  hi = max(0, min(K / ib2,
+ *   ln(K / e^{x0}))) + 1/8  (K <= 0: hi = 1/8).
+ *   (A frequency f0 of exactly 1 -- a lone barcode -- is not served: lo = -inf and the entry is NaN.)
+ * Mode search.  nc = ceil(8 (hi - lo)) cells, at least 16, at most 1024, of equal width, the last ending at hi exactly; g' at the
+ *   nc + 1 edges in ascending order.  A cell with g' > 0 at its left edge and not at its right holds a mode: solve(e0, e1, the
+ *   cell's midpoint) as bb_logtau_rb's solve word for word (Newton on g' with g'', a bisection step wherever Newton's leaves the
+ *   bracket, 2^-40 (1 + |u|), 100 steps, one more Newton step).  No such cell (rounding at an end): the mode is hi if g'(lo) > 0,
+ *   else lo.  The global mode u* is the first of the highest g(mode).  Kept modes: those with g(u*) - g(mode) <= 40; delta of a
+ *   kept mode: 1 / sqrt(-g''(mode)).  (Two modes inside one cell of 1/8 are taken as the one the iteration reaches; the grid
+ *   below still covers both.)  The base is then moved to x* = x0 + u*.
+ * Grid, one per draw, over all kept modes, as bb_logtau_rb's:  dmin the smallest delta;  m = max(1, ceil(2 dmin - 2^-20)), at
+ *   most 64;  s0 = dmin / (4 m).  Ends: left of the leftmost kept mode ml (its delta dl) e0 = ml - 8 r dl, r the first of 1, 2,
+ *   4 .. 4096 with g(e0) <= -40 about x*; right of the rightmost likewise.  nl = ceil(-e0 / s0 - 2^-20), nr = ceil(e1 / s0 - 2^-20),
+ *   each 1 unless the quotient is within 1 .. 1e9;  f = ceil((nl + nr) / 8192), s = f s0, nleft = ceil(nl / f), nright = ceil(nr / f).
+ *   Nodes u_k = (k - nleft) s, k = 0 .. nleft + nright; p_k = exp(g(u_k)); weights s, halved at both ends; the global mode is a node.
+ * Per-draw moments (sums in ascending k):  z = sum w p,  Z_j = s z;  E_j = x* + (sum w p u) / z;  V_j = (sum w p u^2) / z -
+ *   (E_j - x*)^2;  Lam_j = e^{x*} (sum w p (em + 1)) / z, the conditional mean of lambda = e^x itself.
+ * Per-draw CDF C_j(x): bb_logtau_rb's word for word (lo_j = x* - nleft s, hi_j = x* + nright s; N = max(1, ceil((x - lo_j) / s))
+ *   nodes re-spaced to end at x, less the first Euler-Maclaurin end term s_x^2 / 12 (g'(x) p(x) - g'(lo_j) p(lo_j)), over Z_j,
+ *   clamped to [0, 1]).
+ *
+ * Outputs per entry, [n_rows][n_cols] (every pointer may be NULL; sums over the draws in bb_ppc_score's order):
+ *   n_reads     R;  n_sides  1 or 2: how many steps bound the time point
+ *   q_mean, q_sd     of the latent's own draws, as bb_fitness_rb's of s_j
+ *   rb_mean     mean_j E_j
+ *   rb_sd       sqrt(mean_j V_j + mean_j (E_j - rb_mean)^2), two-pass and centred
+ *   lambda_mean mean_j Lam_j
+ *   mode_mean   mean_j x*_j (the global modes)
+ *   quantiles   quantiles[entry][i], the probs[i] quantile of the mixture F(x) = mean_j C_j(x): lo = min_j lo_j, hi = max_j hi_j;
+ *               40 times x = lo + (hi - lo) / 2, F(x) < p ? lo = x : hi = x; the result is the last bracket's midpoint; NaN if any
+ *               x*_j, s_j or Z_j is non-finite.
+ * Cells with t >= T_r of a shorter replicate are NaN (n_reads, n_sides: 0).  Non-finite parameters propagate by IEEE rules into
+ * the entries that use them and disturb no others: a NaN in one loglambda reaches every entry of its time point (through Z) and
+ * of the time points its steps join, and nothing of another replicate.
+ *
+ * Options: bb_logsigma_rb_opts' fields without block; draws, seed and the keying are bb_rb_opts' exactly (n_samples = 1 is allowed
+ * with draws).  rows == NULL: every row.  Otherwise the n_rows listed bb_freq_bands rows, each in range and strictly ascending
+ * (else BB_ERR_INVALID), and the outputs are [n_rows][n_cols]; the tables always sum over all barcodes, so a row's results do
+ * not depend on which other rows were asked for.  BB_LOGLAMBDA_RB_MAX_SAMPLES is the largest count for which (x*_j, s_j, Z_j) and
+ * the reductions' partials fit the 160 KiB of LDS (derived next to the layout, csrc/bb_llrb.h).  An entry's results are a function
+ * of the handle's (mu, sigma) (or the supplied draws), the priors, the counts, n_samples, seed and probs: bit-identical whatever the
+ * grid, the launch mode, the handle's internal latent order (the genotype regrouping, loglambda in front of theta), the device
+ * count, rows or the calls made before.  The handle's mu, omega, optimiser state, step counter and RNG position are untouched,
+ * bitwise.  The chunk partials [chunks][2][n_samples] of the steps in flight are bounded to 256 MiB (slabs; a single step is
+ * worked whole).  BB_ERR_INVALID / BB_ERR_UNSUPPORTED for the options as bb_logsigma_rb.  Multi-device and sharded handles: as
+ * bb_ppc_bands. */
+#define BB_LOGLAMBDA_RB_MAX_SAMPLES 5781
+typedef struct bb_loglambda_rb_opts {
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_LOGLAMBDA_RB_MAX_SAMPLES */
+    int32_t n_quantiles;      /* 0 .. 8                                                */
+    const double* probs;      /* [n_quantiles] probabilities in (0, 1)                 */
+    uint64_t seed;            /* Philox key (draws == NULL)                            */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL   */
+    const int64_t* rows;      /* [n_rows] bb_freq_bands rows, strictly ascending, or NULL: all */
+    int64_t n_rows;           /* length of rows (ignored when rows == NULL)            */
+} bb_loglambda_rb_opts;
+typedef struct bb_loglambda_rb_out { /* every pointer may be NULL; [n_rows][n_cols] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *lambda_mean, *mode_mean;
+    double* quantiles;               /* [n_rows][n_cols][n_quantiles]                  */
+    int64_t* n_reads;                /* R                                              */
+    int32_t* n_sides;                /* 1 or 2                                         */
+} bb_loglambda_rb_out;
+int bb_loglambda_rb_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols);
+int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, const bb_loglambda_rb_out* out);
 
 /* Chain diagnostics on the device -- what MCMCChains' summarystats / quantile report for the chain the reference's mcmc_sample
  * returns (src/mcmc.jl:151-158): mean, std, MCSE, ESS, R-hat and quantiles of every column of a HOST array
