@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
 // bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
-// bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
+// bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -446,6 +446,46 @@ extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands,
     });
 }
 
+// Phase times of a call (diagnostics, tools/*_rate.py: -DBB_SCORE_TIMES, -DBB_RB_TIMES, -DBB_LLRB_TIMES, -DBB_CHAIN_TIMES, -DBB_TRACE_TIMES): lap(i, into) drains the
+// stream, stamps ct[i] and adds the time since ct[i - 1] to ms[into] (into < 0: the stamp alone).  ON == false: nothing at all.
+template <bool ON>
+struct PhaseTimes {
+    bbStream stream;
+    timespec ct[8];
+    double ms[7] = {0, 0, 0, 0, 0, 0, 0};
+    void lap(int i, int into) {
+        if (!ON) return;
+        (void)dsync(stream);
+        clock_gettime(CLOCK_MONOTONIC, &ct[i]);
+        if (into >= 0) ms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6;
+    }
+};
+#ifdef BB_SCORE_TIMES
+typedef PhaseTimes<true> ScoreTimes;
+#else
+typedef PhaseTimes<false> ScoreTimes;
+#endif
+#ifdef BB_RB_TIMES
+typedef PhaseTimes<true> RbTimes;
+#else
+typedef PhaseTimes<false> RbTimes;
+#endif
+#ifdef BB_LLRB_TIMES
+typedef PhaseTimes<true> LlrbTimes;
+#else
+typedef PhaseTimes<false> LlrbTimes;
+#endif
+#ifdef BB_CHAIN_TIMES
+typedef PhaseTimes<true> ChainTimes;
+#else
+typedef PhaseTimes<false> ChainTimes;
+#endif
+#ifdef BB_TRACE_TIMES
+typedef PhaseTimes<true> TraceTimes;
+#else
+typedef PhaseTimes<false> TraceTimes;
+#endif
+
 // ---- predictive log score and PIT of the observed ratios (bb_score.h) -----------------------------------------------------------
 static_assert(BB_SCORE_MAX_SAMPLES == BB_PPC_MAX_K, "bb_ppc_score limits");
 extern "C" int bb_score_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps) {
@@ -472,14 +512,8 @@ extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score
     B.nbands = 0;
     A.B = M.B;
     A.nn = M.nn;
-#ifdef BB_SCORE_TIMES          // diagnostics (tools/ppc_score_rate.py): the call's phases, each drained before the next starts
-    timespec ct[6];
-    double cms[5] = {0, 0, 0, 0, 0};
-    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] = (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int) {};
-#endif
-    lap(0);
+    ScoreTimes pt{dh->stream};   // tools/ppc_score_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
     // the observed ratios, formed once here exactly as n_outside's walk forms them; NaN: a zero count, or no such step
     const size_t ncell = (size_t)n_rows * n_steps;
     std::vector<double> y(ncell, (double)NAN);
@@ -489,7 +523,7 @@ extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score
             if (c[t] && c[t + 1]) yr[t] = log((double)c[t + 1] / n[t + 1]) - log((double)c[t] / n[t]);
     });
     if (rc) return rc;
-    lap(1);
+    pt.lap(1, 0);
     double* dy = nullptr;
     rc = bands_buffers(h, P, B, [&](Carve& c) {
         c(dy, ncell);                                  // [n_rows][n_steps]
@@ -499,11 +533,11 @@ extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score
     });
     if (rc || (rc = h2d(dy, y.data(), ncell * 8, dh->stream))) return rc;
     A.y = dy;
-    lap(2);
+    pt.lap(2, 1);
     if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
-    lap(3);
+    pt.lap(3, 2);
     if ((rc = launch(dh->stream, k_score, (int)B.nblk, BB_SCORE_NT, (size_t)bb_score_lds_doubles(P.n_samples), A))) return rc;
-    lap(4);
+    pt.lap(4, 3);
     if (out->observed) memcpy(out->observed, y.data(), ncell * 8);
     double* cells[BB_SCORE_CELLS] = {out->pred_mean, out->pred_sd, out->lpd, out->p_waic, out->pit, out->pit_upper};
     for (int k = 0; k < BB_SCORE_CELLS; ++k)
@@ -512,9 +546,9 @@ extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score
     if (out->row_p_waic && (rc = d2h(out->row_p_waic, A.rowsum + n_rows, (size_t)n_rows * 8, dh->stream))) return rc;
     if (out->n_scored && (rc = d2h(out->n_scored, A.n_scored, (size_t)n_rows * 4, dh->stream))) return rc;
     rc = dsync(dh->stream);
-    lap(5);
+    pt.lap(5, 4);
 #ifdef BB_SCORE_TIMES
-    fprintf(stderr, "[bb_ppc_score %lld x %d, %d samples] observed %.3f ms, upload %.3f ms, pop %.3f ms, score %.3f ms, download %.3f ms\n", n_rows, n_steps, (int)o->n_samples, cms[0], cms[1], cms[2], cms[3], cms[4]);
+    fprintf(stderr, "[bb_ppc_score %lld x %d, %d samples] observed %.3f ms, upload %.3f ms, pop %.3f ms, score %.3f ms, download %.3f ms\n", n_rows, n_steps, (int)o->n_samples, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
 #endif
     return rc;
 }
@@ -532,22 +566,100 @@ extern "C" int bb_fitness_rb_shape(const bb_handle* h, int64_t* n_units) {
     return BB_OK;
 }
 
-// the option checks bb_fitness_rb and bb_theta_rb share
-static int rb_check(const bb_rb_opts* o) {
-    const int nq = o->n_quantiles, ns = o->n_samples;
-    if (nq < 0 || nq > BB_RB_MAX_Q || (nq > 0 && !o->probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_RB_MAX_Q);
+// ---- what the six Rao-Blackwellised calls share ----------------------------------------------------------------------------------------
+// the option checks: `cap` the call's largest n_samples, `threshold` nullptr for the calls that take none
+static int rb_check(int nq, const double* probs, const double* draws, int ns, int cap, const double* threshold) {
+    if (nq < 0 || nq > BB_RB_MAX_Q || (nq > 0 && !probs)) return bb_fail(BB_ERR_INVALID, "n_quantiles must be in 0..%d (with probs)", BB_RB_MAX_Q);
     for (int i = 0; i < nq; ++i)
-        if (!(o->probs[i] > 0.0 && o->probs[i] < 1.0)) return bb_fail(BB_ERR_INVALID, "every prob must lie strictly between zero and one");
-    if (!std::isfinite(o->threshold)) return bb_fail(BB_ERR_INVALID, "threshold must be finite");
-    const int ns_lo = o->draws ? 1 : 2;
-    if (ns < ns_lo || ns > BB_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_RB_MAX_SAMPLES);
+        if (!(probs[i] > 0.0 && probs[i] < 1.0)) return bb_fail(BB_ERR_INVALID, "every prob must lie strictly between zero and one");
+    if (threshold && !std::isfinite(*threshold)) return bb_fail(BB_ERR_INVALID, "threshold must be finite");
+    const int ns_lo = draws ? 1 : 2;
+    if (ns < ns_lo || ns > cap) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, cap);
     return BB_OK;
+}
+
+// The start of a call: the draws' plan (bands_prologue without bands: nothing selects here), every normaliser row of the posterior
+// mode's plan, and of A what every call sets the same way.
+static int rb_open(bb_handle* h, BandsCall& B, RbArgs& A, int ns, uint64_t seed, int nq, const double* probs, long long n_units, int* zb) {
+    const DevModel& M = B.dh->M;
+    int rc = bands_prologue(h, ns, 1, 0, nullptr, seed, (long long)M.R * M.nb, ppc_steps(h), A.F.P, B);
+    if (rc || (rc = freq_plan(h, M, BB_FREQ_POSTERIOR, A.F, zb))) return rc;
+    A.nq = nq;
+    A.n_units = n_units;
+    A.n_z = M.Ttot;
+    for (int i = 0; i < nq; ++i) A.probs[i] = probs[i];
+    return BB_OK;
+}
+// the caller's draws, if any, onto the device
+static int rb_draws(bb_handle* dh, PpcArgs& P, double* ddraws, const double* draws, size_t ns, size_t D) {
+    if (!draws) return BB_OK;
+    if (int rc = h2d(ddraws, draws, ns * D * 8, dh->stream)) return rc;
+    P.draws = ddraws;
+    P.D = (long long)D;
+    return BB_OK;
+}
+// the front on the device: sbar_{t,j} for the calls that read it (pop), the normalisers, their logarithms in place
+static int rb_front(bb_handle* dh, const BandsCall& B, RbArgs& A, int zb, bool pop) {
+    int rc;
+    if (pop && (rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, A.F.P))) return rc;
+    if ((rc = freq_normalisers(dh, A.F, zb))) return rc;
+    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)dh->M.Ttot * (size_t)A.F.P.n_samples + 255) / 256, 4096));
+    return launch(dh->stream, k_rb_logz, glz, 256, 0, A);      // (F.Z now holds ln Z: every row of a replicate reads the same ones)
+}
+// the grid of a mixture program of bb_gridmix.h: a block per row, two per CU at most, their [tab][ns] tables bounded to 256 MiB
+static long long rb_mix_blocks(const bb_handle* dh, long long rows, int tab, size_t ns) {
+    long long nblk = std::max<long long>(1, std::min<long long>(rows, 2LL * dh->cus));
+    while (nblk > 1 && (size_t)nblk * tab * ns * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    return nblk;
+}
+// The results back: row k of A.unit [n_rows][n] into units[k] where the caller gave one, A.quant [n][8] as [n][nq], A.n_steps where
+// n_steps is asked for.  live: entries that are no cell of the model are NaN (bb_loglambda_rb: the program leaves them alone).
+// Ends drained, whatever was asked for.
+static int rb_download(bb_handle* dh, const RbArgs& A, size_t n, double* const* units, int n_rows, double* quantiles, int32_t* n_steps,
+                       const char* live = nullptr) {
+    int rc;
+    for (int k = 0; k < n_rows; ++k) {
+        if (!units[k] || !n) continue;
+        if ((rc = d2h(units[k], A.unit + (size_t)k * n, n * 8, dh->stream))) return rc;
+        for (size_t e = 0; live && e < n; ++e) if (!live[e]) units[k][e] = NAN;
+    }
+    if (quantiles && A.nq && n) {
+        std::vector<double> q(BB_RB_MAX_Q * n);
+        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
+        for (size_t e = 0; e < n; ++e)
+            for (int i = 0; i < A.nq; ++i) quantiles[e * A.nq + i] = !live || live[e] ? q[e * BB_RB_MAX_Q + i] : NAN;
+    }
+    if (n_steps && n && (rc = d2h(n_steps, A.n_steps, n * 4, dh->stream))) return rc;
+    return dsync(dh->stream);
+}
+// The ragged method's pairing of the neutral terms, [2][nt1][nn] (t | b), empty where the model has none: neutral member i of group
+// (r, k) is element x = k nn + i of the replicate's time-fastest vector.  ragged_upload: onto the device, the two halves named.
+static std::vector<int> ragged_pairing(const DevModel& M) {
+    std::vector<int> neu;
+    if (!M.quirk) return neu;
+    neu.resize(2 * (size_t)M.nt1 * (size_t)M.nn);
+    int* nt = neu.data();
+    int* nbv = nt + (size_t)M.nt1 * (size_t)M.nn;
+    for (int r = 0; r < M.R; ++r)
+        for (int k = 0; k + 1 < M.T[r]; ++k)
+            for (long long i = 0; i < M.nn; ++i) {
+                const long long x = (long long)k * M.nn + i, at = (long long)(M.off_t[r] + k) * M.nn + i;
+                nt[at] = (int)(x % (M.T[r] - 1));
+                nbv[at] = (int)(x / (M.T[r] - 1));
+            }
+    return neu;
+}
+static int ragged_upload(bb_handle* dh, const std::vector<int>& neu, int* dneu, const int*& neu_t, const int*& neu_b) {
+    if (neu.empty()) return BB_OK;
+    neu_t = dneu;
+    neu_b = dneu + neu.size() / 2;
+    return h2d(dneu, neu.data(), neu.size() * 4, dh->stream);
 }
 
 extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out* out) {
     if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     const int nq = o->n_quantiles, ns = o->n_samples;
-    if (int rc = rb_check(o)) return rc;
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_RB_MAX_SAMPLES, &o->threshold)) return rc;
     BandsCall B(h);
     bb_handle* dh = B.dh;
     const DevModel& M = dh->M;
@@ -556,27 +668,16 @@ extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out*
     FreqArgs& F = A.F;
     PpcArgs& P = F.P;
     const long long n_units = rb_units(h);
-    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
-    if (rc) return rc;
     int zb;
-    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, n_units, &zb);
+    if (rc) return rc;
     if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {         // (no regrouping for these kinds: the handle's order is the caller's)
         const DevPrior& dp = M.pri[BK_S];
         P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
     }
-    A.nq = nq;
     A.threshold = o->threshold;
-    A.n_units = n_units;
-    A.n_z = M.Ttot;
-    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
-#ifdef BB_RB_TIMES             // diagnostics (tools/fitness_rb_rate.py): the call's phases, each drained before the next starts
-    timespec ct[6];
-    double cms[5] = {0, 0, 0, 0, 0};
-    auto lap = [&](int i) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] = (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int) {};
-#endif
-    lap(0);
+    RbTimes pt{dh->stream};      // tools/fitness_rb_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
     const size_t nsz = (size_t)ns, D = (size_t)h->M.D, nu = (size_t)n_units;
     double* ddraws = nullptr;
     rc = bands_buffers(h, P, B, [&](Carve& c) {        // (P.par, [nblk][E][2][ns], holds the [nblk][E + 1][ns] table of bb_block_rb)
@@ -589,33 +690,19 @@ extern "C" int bb_fitness_rb(bb_handle* h, const bb_rb_opts* o, const bb_rb_out*
     });
     if (rc) return rc;
     A.ytab = P.par;
-    if (o->draws) {
-        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
-        P.draws = ddraws;
-        P.D = (long long)D;
-    }
-    lap(1);
+    if ((rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    pt.lap(1, 0);
     if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
-    lap(2);
-    if ((rc = freq_normalisers(dh, F, zb))) return rc;
-    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
-    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z: every row of a replicate reads the same ones)
-    lap(3);
+    pt.lap(2, 1);
+    if ((rc = rb_front(dh, B, A, zb, false))) return rc;
+    pt.lap(3, 2);
     if ((rc = launch(dh->stream, k_rb, (int)B.nblk, BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), A))) return rc;
-    lap(4);
+    pt.lap(4, 3);
     double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
-    for (int k = 0; k < BB_RB_OUT; ++k)
-        if (units[k] && (rc = d2h(units[k], A.unit + (size_t)k * nu, nu * 8, dh->stream))) return rc;
-    if (out->quantiles && nq) {
-        std::vector<double> q(BB_RB_MAX_Q * nu);
-        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
-        for (size_t u = 0; u < nu; ++u) memcpy(out->quantiles + u * nq, q.data() + u * BB_RB_MAX_Q, (size_t)nq * 8);
-    }
-    if (out->n_steps && (rc = d2h(out->n_steps, A.n_steps, nu * 4, dh->stream))) return rc;
-    rc = dsync(dh->stream);
-    lap(5);
+    rc = rb_download(dh, A, nu, units, BB_RB_OUT, out->quantiles, out->n_steps);
+    pt.lap(5, 4);
 #ifdef BB_RB_TIMES
-    fprintf(stderr, "[bb_fitness_rb %lld units, %d samples, %d quantiles] upload %.3f ms, pop %.3f ms, normalisers %.3f ms, rb %.3f ms, download %.3f ms\n", n_units, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+    fprintf(stderr, "[bb_fitness_rb %lld units, %d samples, %d quantiles] upload %.3f ms, pop %.3f ms, normalisers %.3f ms, rb %.3f ms, download %.3f ms\n", n_units, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
 #endif
     return rc;
 }
@@ -695,7 +782,7 @@ static int theta_map(const bb_handle* h, BandsCall& B, int E, ThetaMap& tm) {
 extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out) {
     if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     const int nq = o->n_quantiles, ns = o->n_samples;
-    if (int rc = rb_check(o)) return rc;
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_RB_MAX_SAMPLES, &o->threshold)) return rc;
     if (h->M.kind < BB_MODEL_GENOTYPE)
         return bb_fail(BB_ERR_UNSUPPORTED, "bb_theta_rb applies to the hierarchical models only: model kind %d (%s) has no theta", (int)h->M.kind,
                        h->M.kind == BB_MODEL_FITNESS ? "BB_MODEL_FITNESS" : "BB_MODEL_MULTIENV");
@@ -708,28 +795,17 @@ extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_
     FreqArgs& F = A.F;
     PpcArgs& P = F.P;
     const long long n_groups = theta_groups(h);
-    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
-    if (rc) return rc;
     int zb;
-    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, n_groups, &zb);
+    if (rc) return rc;
     {   // the prior of theta: the block is never regrouped (a genotype keeps its number, the replicate kinds keep the caller's order),
         // so a Matrix form lies in the handle as the caller gave it, indexed by g
         const DevPrior& dp = M.pri[BK_S];
         P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
     }
-    A.nq = nq;
     A.threshold = o->threshold;
-    A.n_units = n_groups;
-    A.n_z = M.Ttot;
-    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
-#ifdef BB_RB_TIMES             // diagnostics (tools/theta_rb_rate.py): the call's phases, each drained before the next starts
-    timespec ct[8];
-    double cms[7] = {0, 0, 0, 0, 0, 0, 0};
-    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int, int) {};
-#endif
-    lap(0, -1);
+    RbTimes pt{dh->stream};      // tools/theta_rb_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
     ThetaMap tm;
     if ((rc = theta_map(h, B, P.E, tm))) return rc;
     const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ng = (size_t)n_groups, nchk = tm.chk_grp.size(), nmem = tm.mem_row.size();
@@ -767,44 +843,32 @@ extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_
         put(H.grp_c0, tm.grp_c0); put(H.grp_nst, tm.grp_nst); put(H.chk_grp, tm.chk_grp); put(H.chk_m0, tm.chk_m0); put(H.mem_row, tm.mem_row); put(H.mem_nu, tm.mem_nu);
         if ((rc = h2d(dmap, hm.data(), nmap * 4, dh->stream))) return rc;
     }
-    if (o->draws) {
-        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
-        P.draws = ddraws;
-        P.D = (long long)D;
-    }
-    lap(1, 0);
+    if ((rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    pt.lap(1, 0);
     if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
-    lap(2, 1);
-    if ((rc = freq_normalisers(dh, F, zb))) return rc;
-    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
-    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
-    lap(3, 2);
+    pt.lap(2, 1);
+    if ((rc = rb_front(dh, B, A, zb, false))) return rc;
+    pt.lap(3, 2);
     for (size_t sl = 0; sl + 1 < cut.size(); ++sl) {
         const size_t g0 = cut[sl], g1 = cut[sl + 1];
         H.g0 = (long long)g0; H.g1 = (long long)g1;
         H.c0 = tm.grp_c0[g0]; H.c1 = tm.grp_c0[g1];
-        lap(4, -1);
+        pt.lap(4, -1);
         if (H.c1 > H.c0 && (rc = launch(dh->stream, k_rb_theta_part, std::min(H.c1 - H.c0, 1 << 20), BB_SCORE_NT, 0, H))) return rc;
-        lap(5, 3);
+        pt.lap(5, 3);
         if ((rc = launch(dh->stream, k_rb_theta, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), H))) return rc;
-        lap(6, 4);
+        pt.lap(6, 4);
     }
     double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
-    for (int k = 0; k < BB_RB_OUT; ++k)
-        if (units[k] && (rc = d2h(units[k], A.unit + (size_t)k * ng, ng * 8, dh->stream))) return rc;
-    if (out->quantiles && nq) {
-        std::vector<double> q(BB_RB_MAX_Q * ng);
-        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
-        for (size_t g = 0; g < ng; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
-    }
+    rc = rb_download(dh, A, ng, units, BB_RB_OUT, out->quantiles, nullptr);
+    if (rc) return rc;
     if (out->n_members) memcpy(out->n_members, tm.grp_nmem.data(), ng * 4);
     if (out->n_steps) memcpy(out->n_steps, tm.grp_nst.data(), ng * 4);
-    rc = dsync(dh->stream);
-    lap(7, 5);
+    pt.lap(7, 5);
 #ifdef BB_RB_TIMES
-    fprintf(stderr, "[bb_theta_rb %lld groups, %zu members, %zu chunks, %d samples, %d quantiles] map+upload %.3f ms, pop %.3f ms, normalisers %.3f ms, part %.3f ms, theta %.3f ms, download %.3f ms\n", n_groups, nmem, nchk, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4], cms[5]);
+    fprintf(stderr, "[bb_theta_rb %lld groups, %zu members, %zu chunks, %d samples, %d quantiles] map+upload %.3f ms, pop %.3f ms, normalisers %.3f ms, part %.3f ms, theta %.3f ms, download %.3f ms\n", n_groups, nmem, nchk, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5]);
 #endif
-    return rc;
+    return BB_OK;
 }
 
 // ---- Rao-Blackwellised population-mean fitness marginals (bb_rb.h) ------------------------------------------------------------------
@@ -818,7 +882,7 @@ extern "C" int bb_popmean_rb_shape(const bb_handle* h, int64_t* n_groups) {
 extern "C" int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean_rb_out* out) {
     if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     const int nq = o->n_quantiles, ns = o->n_samples;
-    if (int rc = rb_check(o)) return rc;
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_RB_MAX_SAMPLES, &o->threshold)) return rc;
     BandsCall B(h);
     bb_handle* dh = B.dh;
     const DevModel& M = dh->M;
@@ -829,42 +893,18 @@ extern "C" int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean
     PpcArgs& P = F.P;
     const long long n_groups = M.nt1, nmem = M.nn + M.nb;
     if (nmem > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_popmean_rb: more than 2^31 members");
-    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
-    if (rc) return rc;
     int zb;
-    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, n_groups, &zb);
+    if (rc) return rc;
     {   // the prior of sbar: the s_pop block is never regrouped, so a Matrix form lies in the handle as the caller gave it, indexed by g
         const DevPrior& dp = M.pri[BK_SPOP];
         P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
     }
-    A.nq = nq;
     A.threshold = o->threshold;
-    A.n_units = n_groups;
-    A.n_z = M.Ttot;
-    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
     H.nchunks = (int)((nmem + BB_POP_CHUNK - 1) / BB_POP_CHUNK);
-#ifdef BB_RB_TIMES             // diagnostics (tools/popmean_rb_rate.py): the call's phases, each drained before the next starts
-    timespec ct[7];
-    double cms[5] = {0, 0, 0, 0, 0};
-    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int, int) {};
-#endif
-    lap(0, -1);
-    // the ragged method's pairing: neutral member i of group (r, k) is element x = k nn + i of the replicate's time-fastest vector
-    std::vector<int> neu;
-    if (M.quirk) {
-        neu.resize(2 * (size_t)n_groups * (size_t)M.nn);
-        int* nt = neu.data();
-        int* nbv = nt + (size_t)n_groups * (size_t)M.nn;
-        for (int r = 0; r < M.R; ++r)
-            for (int k = 0; k + 1 < M.T[r]; ++k)
-                for (long long i = 0; i < M.nn; ++i) {
-                    const long long x = (long long)k * M.nn + i, at = (long long)(M.off_t[r] + k) * M.nn + i;
-                    nt[at] = (int)(x % (M.T[r] - 1));
-                    nbv[at] = (int)(x / (M.T[r] - 1));
-                }
-    }
+    RbTimes pt{dh->stream};      // tools/popmean_rb_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
+    const std::vector<int> neu = ragged_pairing(M);
     const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ng = (size_t)n_groups, nch = (size_t)H.nchunks;
     // the groups in flight: their chunk partials bounded to 256 MiB (a single group is worked whole whatever it takes)
     const size_t slab = std::min(ng, std::max<size_t>(1, ((size_t)256 << 20) / (nch * 2 * nsz * 8)));
@@ -882,49 +922,31 @@ extern "C" int bb_popmean_rb(bb_handle* h, const bb_rb_opts* o, const bb_popmean
     });
     if (rc) return rc;
     A.ytab = P.par;
-    if (!neu.empty()) {
-        if ((rc = h2d(dneu, neu.data(), neu.size() * 4, dh->stream))) return rc;
-        H.neu_t = dneu;
-        H.neu_b = dneu + neu.size() / 2;
-    }
-    if (o->draws) {
-        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
-        P.draws = ddraws;
-        P.D = (long long)D;
-    }
-    lap(1, 0);
-    if ((rc = freq_normalisers(dh, F, zb))) return rc;
-    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
-    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
-    lap(2, 1);
+    if ((rc = ragged_upload(dh, neu, dneu, H.neu_t, H.neu_b)) || (rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    pt.lap(1, 0);
+    if ((rc = rb_front(dh, B, A, zb, false))) return rc;
+    pt.lap(2, 1);
     for (size_t g0 = 0; g0 < ng; g0 += slab) {
         const size_t g1 = std::min(ng, g0 + slab);
         H.g0 = (long long)g0; H.g1 = (long long)g1;
-        lap(3, -1);
+        pt.lap(3, -1);
         if ((rc = launch(dh->stream, k_rb_pop_part, (int)std::min<size_t>((g1 - g0) * nch, (size_t)1 << 20), BB_SCORE_NT, 0, H))) return rc;
-        lap(4, 2);
+        pt.lap(4, 2);
         if ((rc = launch(dh->stream, k_rb_pop, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), H))) return rc;
-        lap(5, 3);
+        pt.lap(5, 3);
     }
     double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
-    for (int k = 0; k < BB_RB_OUT; ++k)
-        if (units[k] && (rc = d2h(units[k], A.unit + (size_t)k * ng, ng * 8, dh->stream))) return rc;
-    if (out->quantiles && nq) {
-        std::vector<double> q(BB_RB_MAX_Q * ng);
-        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream))) return rc;
-        for (size_t g = 0; g < ng; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
-    }
+    if ((rc = rb_download(dh, A, ng, units, BB_RB_OUT, out->quantiles, nullptr))) return rc;
     if (out->n_members) for (size_t g = 0; g < ng; ++g) out->n_members[g] = (int32_t)nmem;
-    rc = dsync(dh->stream);
-    lap(6, 4);
+    pt.lap(6, 4);
 #ifdef BB_RB_TIMES
-    fprintf(stderr, "[bb_popmean_rb %lld groups, %lld members, %d chunks each, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, pop %.3f ms, download %.3f ms\n", n_groups, nmem, H.nchunks, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+    fprintf(stderr, "[bb_popmean_rb %lld groups, %lld members, %d chunks each, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, pop %.3f ms, download %.3f ms\n", n_groups, nmem, H.nchunks, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
 #endif
     return rc;
 }
 
 // ---- Rao-Blackwellised noise-scale marginals (bb_lsrb.h) ----------------------------------------------------------------------------
-static_assert(BB_LOGSIGMA_RB_MAX_SAMPLES == BB_LS_SAMPLES_CAP && BB_LOGSIGMA_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_logsigma_rb limits");
+static_assert(BB_LOGSIGMA_RB_MAX_SAMPLES == BB_GRID_SAMPLES_CAP && BB_LOGSIGMA_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_logsigma_rb limits");
 extern "C" int bb_logsigma_rb_shape(const bb_handle* h, int32_t block, int64_t* n_entries) {
     if (!h || !n_entries) return bb_fail(BB_ERR_INVALID, "null argument");
     if (block != BB_LOGSIGMA_BC && block != BB_LOGSIGMA_POP) return bb_fail(BB_ERR_INVALID, "block must be BB_LOGSIGMA_BC or BB_LOGSIGMA_POP");
@@ -938,14 +960,7 @@ extern "C" int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const 
     if (o->block != BB_LOGSIGMA_BC && o->block != BB_LOGSIGMA_POP) return bb_fail(BB_ERR_INVALID, "block must be BB_LOGSIGMA_BC or BB_LOGSIGMA_POP");
     const bool bc = o->block == BB_LOGSIGMA_BC;
     const int nq = o->n_quantiles, ns = o->n_samples;
-    {   // bb_fitness_rb's option checks (no threshold here), with this call's own cap
-        bb_rb_opts ro;
-        memset(&ro, 0, sizeof ro);
-        ro.n_samples = 2; ro.n_quantiles = nq; ro.probs = o->probs; ro.draws = o->draws;
-        if (int rc = rb_check(&ro)) return rc;
-        const int ns_lo = o->draws ? 1 : 2;
-        if (ns < ns_lo || ns > BB_LOGSIGMA_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_LOGSIGMA_RB_MAX_SAMPLES);
-    }
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_LOGSIGMA_RB_MAX_SAMPLES, nullptr)) return rc;
     BandsCall B(h);
     bb_handle* dh = B.dh;
     const DevModel& M = dh->M;
@@ -956,54 +971,29 @@ extern "C" int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const 
     PpcArgs& P = F.P;
     const long long n_entries = bc ? rb_units(h) : M.nt1;
     if (M.nn > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_logsigma_rb: more than 2^31 neutral members");
-    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
-    if (rc) return rc;
     int zb;
-    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, n_entries, &zb);
+    if (rc) return rc;
     // The block's prior, indexed by entry in the caller's order.  logsigma_pop is never regrouped; a Matrix-form logsigma_bc prior of a
     // regrouped genotype handle lies in the handle's mutant order and is brought back to the caller's through perm_m.
     const DevPrior& dp = M.pri[bc ? BK_LS : BK_LSPOP];
     P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
     const bool reorder = bc && dp.mean_e && !h->perm_m.empty();
-    A.nq = nq;
-    A.n_units = n_entries;
-    A.n_z = M.Ttot;
-    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
     L.nchunks = (int)((M.nn + BB_POP_CHUNK - 1) / BB_POP_CHUNK);
-#ifdef BB_RB_TIMES             // diagnostics (tools/logsigma_rb_rate.py): the call's phases, each drained before the next starts
-    timespec ct[7];
-    double cms[5] = {0, 0, 0, 0, 0};
-    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int, int) {};
-#endif
-    lap(0, -1);
-    std::vector<int> neu;      // the ragged method's pairing, as bb_popmean_rb builds it
-    if (!bc && M.quirk) {
-        neu.resize(2 * (size_t)n_entries * (size_t)M.nn);
-        int* nt = neu.data();
-        int* nbv = nt + (size_t)n_entries * (size_t)M.nn;
-        for (int r = 0; r < M.R; ++r)
-            for (int k = 0; k + 1 < M.T[r]; ++k)
-                for (long long i = 0; i < M.nn; ++i) {
-                    const long long x = (long long)k * M.nn + i, at = (long long)(M.off_t[r] + k) * M.nn + i;
-                    nt[at] = (int)(x % (M.T[r] - 1));
-                    nbv[at] = (int)(x / (M.T[r] - 1));
-                }
-    }
+    RbTimes pt{dh->stream};      // tools/logsigma_rb_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
+    const std::vector<int> neu = bc ? std::vector<int>() : ragged_pairing(M);
     const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ne = (size_t)n_entries, nch = (size_t)L.nchunks;
     // POP: the groups in flight, their chunk partials bounded to 256 MiB (a single group is worked whole whatever it takes)
     const size_t slab = bc ? 0 : std::min(ne, std::max<size_t>(1, ((size_t)256 << 20) / (std::max<size_t>(1, nch) * nsz * 8)));
-    // the mixture's grid: as the row program's, its [BB_LS_TAB][ns] tables bounded to 256 MiB
-    long long nblk = std::max<long long>(1, std::min<long long>(bc ? (long long)M.R * M.nb : n_entries, 2LL * dh->cus));
-    while (nblk > 1 && (size_t)nblk * BB_LS_TAB * nsz * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    const long long nblk = rb_mix_blocks(dh, bc ? (long long)M.R * M.nb : n_entries, BB_LS_TAB, nsz);
     double* ddraws = nullptr;
     double* dpri = nullptr;
     int* dneu = nullptr;
     rc = bands_buffers(h, P, B, [&](Carve& c) {
         c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
         c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
-        c(A.ytab, (size_t)nblk * BB_LS_TAB * nsz);     // [nblk][5][ns]
+        c(A.ytab, (size_t)nblk * BB_LS_TAB * nsz);     // [nblk][BB_LS_TAB][ns]
         c(L.part, slab * nch * nsz);                   // [groups in flight][nchunks][ns]
         c(A.unit, BB_RB_OUT * ne);                     // [6][n_entries]
         c(A.quant, BB_RB_MAX_Q * ne);                  // [n_entries][8]
@@ -1015,62 +1005,42 @@ extern "C" int bb_logsigma_rb(bb_handle* h, const bb_logsigma_rb_opts* o, const 
     if (rc) return rc;
     if (reorder) {
         std::vector<double> in(2 * ne), cal(2 * ne);
-        if ((rc = d2h(in.data(), dp.mean_e, ne * 8, dh->stream)) || (rc = d2h(in.data() + ne, dp.inv_var_e, ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        if ((rc = d2h(in.data(), dp.mean_e, ne * 8, dh->stream)) || (rc = d2h(in.data() + ne, dp.inv_var_e, ne * 8, dh->stream))) return rc;
         for (size_t m = 0; m < ne; ++m) { cal[(size_t)h->perm_m[m]] = in[m]; cal[ne + (size_t)h->perm_m[m]] = in[ne + m]; }
         if ((rc = h2d(dpri, cal.data(), 2 * ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;      // (cal is this scope's)
         P.pri_mean_e = dpri;
         P.pri_ivar_e = dpri + ne;
     }
-    if (!neu.empty()) {
-        if ((rc = h2d(dneu, neu.data(), neu.size() * 4, dh->stream))) return rc;
-        L.neu_t = dneu;
-        L.neu_b = dneu + neu.size() / 2;
-    }
-    if (o->draws) {
-        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
-        P.draws = ddraws;
-        P.D = (long long)D;
-    }
-    lap(1, 0);
-    if (bc && (rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
-    if ((rc = freq_normalisers(dh, F, zb))) return rc;
-    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
-    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
-    lap(2, 1);
+    if ((rc = ragged_upload(dh, neu, dneu, L.neu_t, L.neu_b)) || (rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    pt.lap(1, 0);
+    if ((rc = rb_front(dh, B, A, zb, bc))) return rc;
+    pt.lap(2, 1);
     if (bc) {
-        if (n_entries > 0 && (rc = launch(dh->stream, k_ls_bc, (int)nblk, BB_SCORE_NT, (size_t)BB_LS_LDS_DOUBLES(ns), L))) return rc;
-        lap(3, 3);
-        lap(5, -1);
+        if (n_entries > 0 && (rc = launch(dh->stream, k_ls_bc, (int)nblk, BB_SCORE_NT, (size_t)BB_GRID_LDS_DOUBLES(ns), L))) return rc;
+        pt.lap(3, 3);
+        pt.lap(5, -1);
     } else {
         for (size_t g0 = 0; g0 < ne; g0 += slab) {
             const size_t g1 = std::min(ne, g0 + slab);
             L.g0 = (long long)g0; L.g1 = (long long)g1;
-            lap(3, -1);
+            pt.lap(3, -1);
             if (nch && (rc = launch(dh->stream, k_ls_pop_part, (int)std::min<size_t>((g1 - g0) * nch, (size_t)1 << 20), BB_SCORE_NT, 0, L))) return rc;
-            lap(4, 2);
-            if ((rc = launch(dh->stream, k_ls_pop, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_LS_LDS_DOUBLES(ns), L))) return rc;
-            lap(5, 3);
+            pt.lap(4, 2);
+            if ((rc = launch(dh->stream, k_ls_pop, (int)std::min<long long>((long long)(g1 - g0), nblk), BB_SCORE_NT, (size_t)BB_GRID_LDS_DOUBLES(ns), L))) return rc;
+            pt.lap(5, 3);
         }
     }
     double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->sigma_mean, out->mode_mean};
-    for (int k = 0; k < BB_RB_OUT; ++k)
-        if (units[k] && ne && (rc = d2h(units[k], A.unit + (size_t)k * ne, ne * 8, dh->stream))) return rc;
-    if (out->quantiles && nq && ne) {
-        std::vector<double> q(BB_RB_MAX_Q * ne);
-        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
-        for (size_t g = 0; g < ne; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
-    }
-    if (out->n_terms && ne && (rc = d2h(out->n_terms, A.n_steps, ne * 4, dh->stream))) return rc;
-    rc = dsync(dh->stream);
-    lap(6, 4);
+    rc = rb_download(dh, A, ne, units, BB_RB_OUT, out->quantiles, out->n_terms);
+    pt.lap(6, 4);
 #ifdef BB_RB_TIMES
-    fprintf(stderr, "[bb_logsigma_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, mixture %.3f ms, download %.3f ms\n", bc ? "bc" : "pop", n_entries, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+    fprintf(stderr, "[bb_logsigma_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, part %.3f ms, mixture %.3f ms, download %.3f ms\n", bc ? "bc" : "pop", n_entries, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
 #endif
     return rc;
 }
 
 // ---- Rao-Blackwellised logtau marginals (bb_ltrb.h) ---------------------------------------------------------------------------------
-static_assert(BB_LOGTAU_RB_MAX_SAMPLES == BB_LT_SAMPLES_CAP && BB_LOGTAU_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES && BB_LOGTAU_FULL == BB_LT_FULL &&
+static_assert(BB_LOGTAU_RB_MAX_SAMPLES == BB_GRID_SAMPLES_CAP && BB_LOGTAU_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES && BB_LOGTAU_FULL == BB_LT_FULL &&
               BB_LOGTAU_COLLAPSED == BB_LT_COLLAPSED, "bb_logtau_rb limits");
 extern "C" int bb_logtau_rb_shape(const bb_handle* h, int64_t* n_entries) {
     if (!h || !n_entries) return bb_fail(BB_ERR_INVALID, "null argument");
@@ -1082,14 +1052,7 @@ extern "C" int bb_logtau_rb(bb_handle* h, const bb_logtau_rb_opts* o, const bb_l
     if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     if (o->mode != BB_LOGTAU_FULL && o->mode != BB_LOGTAU_COLLAPSED) return bb_fail(BB_ERR_INVALID, "mode must be BB_LOGTAU_FULL or BB_LOGTAU_COLLAPSED");
     const int nq = o->n_quantiles, ns = o->n_samples;
-    {   // bb_fitness_rb's option checks (no threshold here), with this call's own cap
-        bb_rb_opts ro;
-        memset(&ro, 0, sizeof ro);
-        ro.n_samples = 2; ro.n_quantiles = nq; ro.probs = o->probs; ro.draws = o->draws;
-        if (int rc = rb_check(&ro)) return rc;
-        const int ns_lo = o->draws ? 1 : 2;
-        if (ns < ns_lo || ns > BB_LOGTAU_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_LOGTAU_RB_MAX_SAMPLES);
-    }
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_LOGTAU_RB_MAX_SAMPLES, nullptr)) return rc;
     if (h->M.kind == BB_MODEL_FITNESS || h->M.kind == BB_MODEL_MULTIENV)
         return bb_fail(BB_ERR_UNSUPPORTED, "bb_logtau_rb applies to the hierarchical models only: model kind %d (%s) has no logtau", (int)h->M.kind,
                        h->M.kind == BB_MODEL_FITNESS ? "BB_MODEL_FITNESS" : "BB_MODEL_MULTIENV");
@@ -1103,91 +1066,55 @@ extern "C" int bb_logtau_rb(bb_handle* h, const bb_logtau_rb_opts* o, const bb_l
     PpcArgs& P = F.P;
     const long long n_entries = rb_units(h);      // (the logtau block has one entry per unit of bb_fitness_rb)
     if (n_entries != h->M.blk_hi[BK_LT] - h->M.blk_lo[BK_LT]) return bb_fail(BB_ERR_INVALID, "unexpected block layout");
-    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
-    if (rc) return rc;
     int zb;
-    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, n_entries, &zb);
+    if (rc) return rc;
     const DevPrior& dp = M.pri[BK_LT];            // Vector form: one (mean, 1 / std^2) for every entry
     P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = nullptr; P.pri_ivar_e = nullptr;
     L.mode = o->mode;
-    A.nq = nq;
-    A.n_units = n_entries;
-    A.n_z = M.Ttot;
-    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
-#ifdef BB_RB_TIMES             // diagnostics (tools/logtau_rb_rate.py): the call's phases, each drained before the next starts
-    timespec ct[5];
-    double cms[4] = {0, 0, 0, 0};
-    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int, int) {};
-#endif
-    lap(0, -1);
+    RbTimes pt{dh->stream};      // tools/logtau_rb_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
     const size_t nsz = (size_t)ns, D = (size_t)h->M.D, ne = (size_t)n_entries;
-    // the row program's grid: its [BB_LT_TAB][ns] tables bounded to 256 MiB
-    long long nblk = std::max<long long>(1, std::min<long long>((long long)M.R * M.nb, 2LL * dh->cus));
-    while (nblk > 1 && (size_t)nblk * BB_LT_TAB * nsz * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    const long long nblk = rb_mix_blocks(dh, (long long)M.R * M.nb, BB_LT_TAB, nsz);
     double* ddraws = nullptr;
     rc = bands_buffers(h, P, B, [&](Carve& c) {
         c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
         c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
-        c(A.ytab, (size_t)nblk * BB_LT_TAB * nsz);     // [nblk][10][ns]
+        c(A.ytab, (size_t)nblk * BB_LT_TAB * nsz);     // [nblk][BB_LT_TAB][ns]
         c(A.unit, BB_LT_OUT * ne);                     // [8][n_entries]
         c(A.quant, BB_RB_MAX_Q * ne);                  // [n_entries][8]
         c(A.n_steps, (ne + 1) / 2);                    // [n_entries] ints
         c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
     });
-    if (rc) return rc;
-    if (o->draws) {
-        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
-        P.draws = ddraws;
-        P.D = (long long)D;
-    }
-    lap(1, 0);
-    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
-    if ((rc = freq_normalisers(dh, F, zb))) return rc;
-    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
-    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
-    lap(2, 1);
-    if (n_entries > 0 && (rc = o->mode == BB_LOGTAU_FULL ? launch(dh->stream, k_lt_full, (int)nblk, BB_SCORE_NT, (size_t)BB_LT_LDS_DOUBLES(ns), L)
-                                                        : launch(dh->stream, k_lt_collapsed, (int)nblk, BB_SCORE_NT, (size_t)BB_LT_LDS_DOUBLES(ns), L))) return rc;
-    lap(3, 2);
-    double* units[BB_LT_OUT - 1] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->tau_mean, out->pool_mean, out->mode_mean};
-    for (int k = 0; k < BB_LT_OUT - 1; ++k)
-        if (units[k] && ne && (rc = d2h(units[k], A.unit + (size_t)k * ne, ne * 8, dh->stream))) return rc;
+    if (rc || (rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    pt.lap(1, 0);
+    if ((rc = rb_front(dh, B, A, zb, true))) return rc;
+    pt.lap(2, 1);
+    if (n_entries > 0 && (rc = o->mode == BB_LOGTAU_FULL ? launch(dh->stream, k_lt_full, (int)nblk, BB_SCORE_NT, (size_t)BB_GRID_LDS_DOUBLES(ns), L)
+                                                        : launch(dh->stream, k_lt_collapsed, (int)nblk, BB_SCORE_NT, (size_t)BB_GRID_LDS_DOUBLES(ns), L))) return rc;
+    pt.lap(3, 2);
     if (out->n_two_modes && ne) {                      // (counted in a double on the device: exact up to 2^53)
         std::vector<double> two(ne);
-        if ((rc = d2h(two.data(), A.unit + (size_t)(BB_LT_OUT - 1) * ne, ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
+        if ((rc = d2h(two.data(), A.unit + (size_t)(BB_LT_OUT - 1) * ne, ne * 8, dh->stream))) return rc;
         for (size_t g = 0; g < ne; ++g) out->n_two_modes[g] = (int32_t)two[g];
     }
-    if (out->quantiles && nq && ne) {
-        std::vector<double> q(BB_RB_MAX_Q * ne);
-        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
-        for (size_t g = 0; g < ne; ++g) memcpy(out->quantiles + g * nq, q.data() + g * BB_RB_MAX_Q, (size_t)nq * 8);
-    }
-    if (out->n_terms && ne && (rc = d2h(out->n_terms, A.n_steps, ne * 4, dh->stream))) return rc;
-    rc = dsync(dh->stream);
-    lap(4, 3);
+    double* units[BB_LT_OUT - 1] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->tau_mean, out->pool_mean, out->mode_mean};
+    rc = rb_download(dh, A, ne, units, BB_LT_OUT - 1, out->quantiles, out->n_terms);
+    pt.lap(4, 3);
 #ifdef BB_RB_TIMES
-    fprintf(stderr, "[bb_logtau_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, mixture %.3f ms, download %.3f ms\n", o->mode == BB_LOGTAU_FULL ? "full" : "collapsed", n_entries, ns, nq, cms[0], cms[1], cms[2], cms[3]);
+    fprintf(stderr, "[bb_logtau_rb %s %lld entries, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, mixture %.3f ms, download %.3f ms\n", o->mode == BB_LOGTAU_FULL ? "full" : "collapsed", n_entries, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3]);
 #endif
     return rc;
 }
 
 // ---- Rao-Blackwellised loglambda marginals (bb_llrb.h) ------------------------------------------------------------------------------
-static_assert(BB_LOGLAMBDA_RB_MAX_SAMPLES == BB_LL_SAMPLES_CAP && BB_LOGLAMBDA_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_loglambda_rb limits");
+static_assert(BB_LOGLAMBDA_RB_MAX_SAMPLES == BB_GRID_SAMPLES_CAP && BB_LOGLAMBDA_RB_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_loglambda_rb limits");
 extern "C" int bb_loglambda_rb_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_cols) { return bb_freq_shape(h, n_rows, n_cols); }
 
 extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, const bb_loglambda_rb_out* out) {
     if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     const int nq = o->n_quantiles, ns = o->n_samples;
-    {   // bb_fitness_rb's option checks (no threshold here), with this call's own cap
-        bb_rb_opts ro;
-        memset(&ro, 0, sizeof ro);
-        ro.n_samples = 2; ro.n_quantiles = nq; ro.probs = o->probs; ro.draws = o->draws;
-        if (int rc = rb_check(&ro)) return rc;
-        const int ns_lo = o->draws ? 1 : 2;
-        if (ns < ns_lo || ns > BB_LOGLAMBDA_RB_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in %d..%d", ns_lo, BB_LOGLAMBDA_RB_MAX_SAMPLES);
-    }
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_LOGLAMBDA_RB_MAX_SAMPLES, nullptr)) return rc;
     BandsCall B(h);
     bb_handle* dh = B.dh;
     const DevModel& M = dh->M;
@@ -1206,26 +1133,16 @@ extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, cons
     RbArgs& A = L.A;
     FreqArgs& F = A.F;
     PpcArgs& P = F.P;
-    int rc = bands_prologue(h, ns, 1, 0, nullptr, o->seed, (long long)M.R * M.nb, ppc_steps(h), P, B);      // (no bands: nothing selects here)
-    if (rc) return rc;
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, nr = (size_t)n_req, ne = nr * (size_t)n_cols, ng = (size_t)M.nt1;
     int zb;
-    if ((rc = freq_plan(h, M, BB_FREQ_POSTERIOR, F, &zb))) return rc;
-    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, nr = (size_t)n_req, ne = nr * (size_t)n_cols, nch = (size_t)F.nchunks, ng = (size_t)M.nt1;
-    A.nq = nq;
-    A.n_units = (long long)ne;
-    A.n_z = M.Ttot;
-    for (int i = 0; i < nq; ++i) A.probs[i] = o->probs[i];
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, (long long)ne, &zb);
+    if (rc) return rc;
+    const size_t nch = (size_t)F.nchunks;
     L.n_req = n_req;
     L.n_cols = n_cols;
     L.quirk = M.quirk;
-#ifdef BB_LLRB_TIMES           // diagnostics (tools/loglambda_rb_rate.py): the call's phases, each drained before the next starts
-    timespec ct[7];
-    double cms[5] = {0, 0, 0, 0, 0};
-    auto lap = [&](int i, int into) { (void)dsync(dh->stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (into >= 0) cms[into] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; };
-#else
-    auto lap = [](int, int) {};
-#endif
-    lap(0, -1);
+    LlrbTimes pt{dh->stream};    // tools/loglambda_rb_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
     // The entries' constants, in the order of the result: the prior element and the count of (row, t).  Both lie in the handle in its
     // own barcode order ([B][T_r] per replicate, the mutants possibly regrouped); the rows are the caller's.
     const DevPrior& dp = M.pri[BK_L];
@@ -1238,7 +1155,6 @@ extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, cons
         pri.resize(2 * (size_t)ncnt);
         if ((rc = d2h(pri.data(), dp.mean_e, (size_t)ncnt * 8, dh->stream)) || (rc = d2h(pri.data() + ncnt, dp.inv_var_e, (size_t)ncnt * 8, dh->stream))) return rc;
     }
-    if ((rc = dsync(dh->stream))) return rc;
     std::vector<long long> own((size_t)M.nb);      // the caller's mutant -> the handle's
     for (long long m = 0; m < M.nb; ++m) own[(size_t)(h->perm_m.empty() ? m : h->perm_m[(size_t)m])] = m;
     std::vector<double> ent(3 * ne, 0.0);
@@ -1261,16 +1177,14 @@ extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, cons
     }
     // the steps in flight: their chunk partials bounded to 256 MiB (a single step is worked whole whatever it takes)
     const size_t slab = std::min(ng, std::max<size_t>(1, ((size_t)256 << 20) / (nch * 2 * nsz * 8)));
-    // the entry program's grid: as the row program's, its [BB_LL_TAB][ns] tables bounded to 256 MiB
-    long long nblk = std::max<long long>(1, std::min<long long>(n_req, 2LL * dh->cus));
-    while (nblk > 1 && (size_t)nblk * BB_LL_TAB * nsz * 8 > ((size_t)256 << 20)) nblk = (nblk + 1) / 2;
+    const long long nblk = rb_mix_blocks(dh, n_req, BB_LL_TAB, nsz);
     double* ddraws = nullptr;
     double* dent = nullptr;
     long long* drows = nullptr;
     rc = bands_buffers(h, P, B, [&](Carve& c) {
         c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
         c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
-        c(A.ytab, (size_t)nblk * BB_LL_TAB * nsz);     // [nblk][11][ns]
+        c(A.ytab, (size_t)nblk * BB_LL_TAB * nsz);     // [nblk][BB_LL_TAB][ns]
         c(L.part, slab * nch * 2 * nsz);               // [steps in flight][nchunks][2][ns]
         c(L.ab, ng * 2 * nsz);                         // [nt1][2][ns]
         c(A.unit, BB_RB_OUT * ne);                     // [6][n_entries]
@@ -1287,17 +1201,10 @@ extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, cons
         if ((rc = h2d(drows, o->rows, nr * 8, dh->stream))) return rc;
         L.rows = drows;
     }
-    if (o->draws) {
-        if ((rc = h2d(ddraws, o->draws, nsz * D * 8, dh->stream))) return rc;
-        P.draws = ddraws;
-        P.D = (long long)D;
-    }
-    lap(1, 0);
-    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
-    if ((rc = freq_normalisers(dh, F, zb))) return rc;
-    const int glz = (int)std::max<size_t>(1, std::min<size_t>(((size_t)M.Ttot * nsz + 255) / 256, 4096));
-    if ((rc = launch(dh->stream, k_rb_logz, glz, 256, 0, A))) return rc;      // (F.Z now holds ln Z)
-    lap(2, 1);
+    if ((rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    pt.lap(1, 0);
+    if ((rc = rb_front(dh, B, A, zb, true))) return rc;
+    pt.lap(2, 1);
     for (size_t g0 = 0; g0 < ng; g0 += slab) {
         const size_t g1 = std::min(ng, g0 + slab);
         L.g0 = (long long)g0; L.g1 = (long long)g1;
@@ -1305,28 +1212,16 @@ extern "C" int bb_loglambda_rb(bb_handle* h, const bb_loglambda_rb_opts* o, cons
         const int gs = (int)std::max<size_t>(1, std::min<size_t>(((g1 - g0) * nsz + 255) / 256, 4096));
         if ((rc = launch(dh->stream, k_ll_sum, gs, 256, 0, L))) return rc;
     }
-    lap(3, 2);
-    if ((rc = launch(dh->stream, k_ll, (int)nblk, BB_SCORE_NT, (size_t)BB_LL_LDS_DOUBLES(ns), L))) return rc;
-    lap(4, 3);
-    // cells t >= T_r of a shorter replicate: the entry program leaves them alone; NaN here
+    pt.lap(3, 2);
+    if ((rc = launch(dh->stream, k_ll, (int)nblk, BB_SCORE_NT, (size_t)BB_GRID_LDS_DOUBLES(ns), L))) return rc;
+    pt.lap(4, 3);
     double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->lambda_mean, out->mode_mean};
-    for (int k = 0; k < BB_RB_OUT; ++k) {
-        if (!units[k]) continue;
-        if ((rc = d2h(units[k], A.unit + (size_t)k * ne, ne * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
-        for (size_t e = 0; e < ne; ++e) if (!live[e]) units[k][e] = NAN;
-    }
-    if (out->quantiles && nq) {
-        std::vector<double> q(BB_RB_MAX_Q * ne);
-        if ((rc = d2h(q.data(), A.quant, q.size() * 8, dh->stream)) || (rc = dsync(dh->stream))) return rc;
-        for (size_t e = 0; e < ne; ++e)
-            for (int i = 0; i < nq; ++i) out->quantiles[e * nq + i] = live[e] ? q[e * BB_RB_MAX_Q + i] : NAN;
-    }
+    if ((rc = rb_download(dh, A, ne, units, BB_RB_OUT, out->quantiles, nullptr, live.data()))) return rc;
     if (out->n_reads) memcpy(out->n_reads, reads.data(), ne * sizeof(int64_t));
     if (out->n_sides) memcpy(out->n_sides, sides.data(), ne * sizeof(int32_t));
-    rc = dsync(dh->stream);
-    lap(5, 4);
+    pt.lap(5, 4);
 #ifdef BB_LLRB_TIMES
-    fprintf(stderr, "[bb_loglambda_rb %lld rows of %lld, %d columns, %d chunks, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, tables %.3f ms, entries %.3f ms, download %.3f ms\n", n_req, n_all, n_cols, F.nchunks, ns, nq, cms[0], cms[1], cms[2], cms[3], cms[4]);
+    fprintf(stderr, "[bb_loglambda_rb %lld rows of %lld, %d columns, %d chunks, %d samples, %d quantiles] upload %.3f ms, normalisers %.3f ms, tables %.3f ms, entries %.3f ms, download %.3f ms\n", n_req, n_all, n_cols, F.nchunks, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
 #endif
     return rc;
 }
@@ -1338,7 +1233,7 @@ static_assert(BB_CHAIN_MAX_K == BB_PPC_MAX_K && BB_CHAIN_MAX_Q == BB_CHAIN_QSTRI
 // What bb_chain_summary and bb_trace_summary share.  chain_plan: the options that shape the statistics into C, the slab width, and the
 // device buffer -- the slab as filled, its transpose, the slab's results (they lie together and come back in one copy: stat | quant |
 // nlags), then whatever `extra` names.  chain_slabs: the loop over slabs of columns, fill(c0) putting columns c0 .. c0 + C.sc into the
-// slab and take(c0) collecting their results; lap(0 .. 4) brackets the four phases of every slab.
+// slab and take(c0) collecting their results; pt's laps 0 .. 4 bracket the four phases of every slab.
 struct ChainSlabs {
     double* slab = nullptr;        // [K][ld]
     long long ld = 0;
@@ -1383,31 +1278,25 @@ static int chain_plan(bb_handle* dh, int W, int N, int max_lag, int nq, const do
     C.ld = ld;
     return BB_OK;
 }
-template <class F, class T, class Lap>
-static int chain_slabs(bb_handle* dh, ChainArgs& C, long long n_cols, F&& fill, T&& take, Lap&& lap) {
+template <class F, class T, class PT>
+static int chain_slabs(bb_handle* dh, ChainArgs& C, long long n_cols, F&& fill, T&& take, PT& pt) {
     const long long K = C.P.K, ld = C.ld;
     int rc;
     for (long long c0 = 0; c0 < n_cols; c0 += ld) {
         C.sc = std::min<long long>(ld, n_cols - c0);
-        lap(0);
+        pt.lap(0, -1);
         if ((rc = fill(c0))) return rc;
-        lap(1);
+        pt.lap(1, 0);
         const long long tiles = ((C.sc + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE) * ((K + BB_CHAIN_TILE - 1) / BB_CHAIN_TILE);
         if ((rc = launch(dh->stream, k_chain_transpose, (int)std::min<long long>(tiles, 1 << 16), BB_CHAIN_TNT, BB_CHAIN_TILE * (BB_CHAIN_TILE + 1), C))) return rc;
-        lap(2);
+        pt.lap(2, 1);
         if ((rc = launch(dh->stream, k_chain_stats, (int)std::min<long long>(C.sc, 1 << 20), BB_CHAIN_NT, (size_t)bb_chain_lds_doubles(C.P.K), C))) return rc;
-        lap(3);
+        pt.lap(3, 2);
         if ((rc = take(c0))) return rc;
-        lap(4);
+        pt.lap(4, 3);
     }
     return BB_OK;
 }
-// the phase clock of the BB_*_TIMES diagnostics: lap(i) drains the stream and adds the time since the lap before to ms[i - 1]
-#define BB_LAP_CLOCK(stream, n)                                                                                                    \
-    timespec ct[(n) + 1];                                                                                                          \
-    double cms[(n)] = {0};                                                                                                         \
-    auto lap = [&](int i) { (void)dsync(stream); clock_gettime(CLOCK_MONOTONIC, &ct[i]); if (i) cms[i - 1] += (ct[i].tv_sec - ct[i - 1].tv_sec) * 1e3 + (ct[i].tv_nsec - ct[i - 1].tv_nsec) * 1e-6; }
-
 extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_cols, const double* chain, const bb_chain_out* out) {
     if (!h || !o || !chain || !out) return bb_fail(BB_ERR_INVALID, "null argument");
     if (n_cols < 1) return bb_fail(BB_ERR_INVALID, "n_cols must be >= 1");
@@ -1428,11 +1317,7 @@ extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_
     const long long ld = L.ld;
     std::vector<double> res(L.nres);
     double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
-#ifdef BB_CHAIN_TIMES          // diagnostics (tools/chain_summary_rate.py): the call's phases, each drained before the next starts
-    BB_LAP_CLOCK(dh->stream, 4);
-#else
-    auto lap = [](int) {};
-#endif
+    ChainTimes pt{dh->stream};   // tools/chain_summary_rate.py: the call's phases, each drained before the next starts
     rc = chain_slabs(dh, C, n_cols,
         [&](long long c0) { return h2d_2d(L.slab, (size_t)ld * 8, chain + c0, (size_t)n_cols * 8, (size_t)C.sc * 8, (size_t)K, dh->stream); },
         [&](long long c0) {
@@ -1443,10 +1328,10 @@ extern "C" int bb_chain_summary(bb_handle* h, const bb_chain_opts* o, int64_t n_
                 for (long long c = 0; c < C.sc; ++c) memcpy(out->quantiles + (size_t)(c0 + c) * nq, res.data() + L.n_stat + c * BB_CHAIN_QSTRIDE, (size_t)nq * 8);
             if (out->n_lags) memcpy(out->n_lags + c0, res.data() + L.n_stat + L.n_quant, (size_t)C.sc * 4);
             return 0;
-        }, lap);
+        }, pt);
     if (rc) return rc;
 #ifdef BB_CHAIN_TIMES
-    fprintf(stderr, "[bb_chain_summary %lld x %lld, slabs of %lld] upload %.3f ms, transpose %.3f ms, stats %.3f ms, download %.3f ms\n", K, (long long)n_cols, ld, cms[0], cms[1], cms[2], cms[3]);
+    fprintf(stderr, "[bb_chain_summary %lld x %lld, slabs of %lld] upload %.3f ms, transpose %.3f ms, stats %.3f ms, download %.3f ms\n", K, (long long)n_cols, ld, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3]);
 #endif
     return BB_OK;
 }
@@ -1574,11 +1459,7 @@ extern "C" int bb_trace_summary(bb_handle* h, const bb_trace_sum_opts* o, const 
     T.ld = L.ld;
     T.first = o->first;
     T.K = (int)K;
-#ifdef BB_TRACE_TIMES          // diagnostics (tools/trace_cost.py): the call's phases, each drained before the next starts
-    BB_LAP_CLOCK(h->stream, 6);
-#else
-    auto lap = [](int) {};
-#endif
+    TraceTimes pt{h->stream};    // tools/trace_cost.py: the call's phases, each drained before the next starts
     rc = chain_slabs(h, C, (long long)D2,
         [&](long long c0) {
             T.c0 = c0;
@@ -1590,7 +1471,7 @@ extern "C" int bb_trace_summary(bb_handle* h, const bb_trace_sum_opts* o, const 
             for (size_t s = 0; s < 5; ++s)
                 if (int r = d2d(all + s * D2 + c0, C.stat + s * (size_t)L.ld, (size_t)C.sc * 8, h->stream)) return r;
             return d2d(all_lags + c0, C.nlags, (size_t)C.sc * 4, h->stream);
-        }, lap);
+        }, pt);
     if (rc) return rc;
     if (out->blocks) {
         V.stat = all;
@@ -1601,7 +1482,7 @@ extern "C" int bb_trace_summary(bb_handle* h, const bb_trace_sum_opts* o, const 
         for (size_t b = 0; b < nblk; ++b) trace_block_range(h, b, &V.lo[b], &V.hi[b]);
         if ((rc = launch(h->stream, k_trace_verdict, 2 * (int)nblk, BB_TRACE_VNT, (size_t)bb_trace_verdict_lds_doubles(), V))) return rc;
     }
-    lap(5);
+    pt.lap(5, 4);
     // downloads: only what was asked for, the handle's order -> the caller's per half
     double* outs[5] = {out->mean, out->sd, out->mcse, out->ess, out->rhat};
     std::vector<double> tmp;
@@ -1640,9 +1521,9 @@ extern "C" int bb_trace_summary(bb_handle* h, const bb_trace_sum_opts* o, const 
         }
     }
     rc = dsync(h->stream);
-    lap(6);
+    pt.lap(6, 5);
 #ifdef BB_TRACE_TIMES
-    fprintf(stderr, "[bb_trace_summary %lld x %zu, slabs of %lld] gather %.3f ms, transpose %.3f ms, stats %.3f ms, collect %.3f ms, verdict %.3f ms, download %.3f ms\n", K, D2, L.ld, cms[0], cms[1], cms[2], cms[3], cms[4], cms[5]);
+    fprintf(stderr, "[bb_trace_summary %lld x %zu, slabs of %lld] gather %.3f ms, transpose %.3f ms, stats %.3f ms, collect %.3f ms, verdict %.3f ms, download %.3f ms\n", K, D2, L.ld, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5]);
 #endif
     return rc;
 }

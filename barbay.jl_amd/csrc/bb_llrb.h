@@ -21,40 +21,17 @@
 //        into part[work][2][n_samples].
 //   bb_block_ll_sum  : per (step, draw) the chunk partials from 0.0 in chunk order (bb_rb_chunk_sum) into ab[nt1][2][n_samples].
 //   bb_block_ll      : one workgroup per requested row (r, b), x += nblocks, walking its T_r time points; entry = x n_cols + t.
-//     C  per draw the base point's coefficients (x0, f0, As, Bs, ws, wr) into the block's slice of a global table
-//     A  per draw the modes, the grid, the moments: x*, s, Z into LDS; the anchored coefficients, E, V, Lam, lo, hi into the table
-//        (draw j is lane j mod BB_SCORE_NT's in every sweep, so a lane reads only table entries it wrote)     -> sum x0, E, V
-//     A' (no arithmetic on the grid)                                                        -> sum Lam, sum x*, max hi_j
-//     B  centred second moments                                          -> sum (x0 - q_mean)^2, sum (E - rb_mean)^2, max -lo_j
-//     Q  bisection of the mixture CDF, BB_LL_ITER steps, up to three quantiles per sweep as bb_rb_mixture does; a draw whose
-//        [lo_j, hi_j] does not hold the midpoint adds 0 or 1 and evaluates nothing.
-// The maximum of hi_j takes NaN for a draw whose Z_j is not finite, so that the bracket is finite exactly when every x*_j, s_j and
-// Z_j is.  Sums and maxima in bb_score_reduce's order; exp, expm1, log, log1p, sqrt, ceil are the platform's, as in bb_rb.h.
-// No per-thread array is indexed at run time (that would be scratch memory): per-draw state lives in LDS or in the block's table.
-// Barrier-separated passes, so the host emulation (BB_EMU) runs the same source.
+//     C  per draw the base point's coefficients (x0, f0, As, Bs, ws, wr) into the block's slice of a global table; then
+//        bb_grid_mixture (bb_gridmix.h: the sweeps, the NaN rule, the quantiles) over LlMix, whose extra is lambda.
+// exp, expm1, log, log1p, sqrt, ceil are the platform's, as in bb_rb.h.
 #pragma once
-#include "bb_rb.h"
+#include "bb_gridmix.h"
 
-#define BB_LL_ITER 40                      // bisection steps of a quantile
-#define BB_LL_TAIL (-40.0)                 // a mode is kept, and the grid ends, at exp(BB_LL_TAIL) of the global maximum
-#define BB_LL_REACH 8                      // an end lies 8 r delta beyond its outer mode, r = 1, 2, 4 .. BB_LL_REACH_MAX
-#define BB_LL_REACH_MAX 4096
-#define BB_LL_REFINE_MAX 64                // the step is delta / (4 m), m = ceil(2 delta) up to this
-#define BB_LL_NODES_MAX 8192               // intervals of a draw's grid; beyond it the step is widened by a whole factor
-#define BB_LL_MODE_ITER 100                // steps of the safeguarded iteration of one scan cell
 #define BB_LL_SCAN_MIN 16                  // cells of the mode scan: ceil(8 width) within these, so a cell is 1/8 wide or narrower
 #define BB_LL_SCAN_MAX 1024                //   on a bracket up to 128 wide
 #define BB_LL_PAD 0.125                    // added to either end of the bracket
 #define BB_LL_LOW_ITER 30                  // bisection steps of the bracket's lower end
-#define BB_LL_SLACK 9.5367431640625e-07   // 2^-20, taken off a quotient before ceil (bb_ltrb.h)
 #define BB_LL_TAB 11                       // per-block global table [11][n_samples]: As, ws, Bs, wr, f0, x0, E, V, Lam, lo, hi
-// LDS: x*[n_samples] | s[n_samples] | Z[n_samples] | three arrays of BB_SCORE_NT partials | scalars (bb_rb.h's st[] layout)
-#define BB_LL_LDS_DOUBLES(ns) (3 * (long long)(ns) + 3 * BB_SCORE_NT + BB_RB_SCALARS)
-// the largest n_samples whose layout fits the 160 KiB of LDS a workgroup can have
-#define BB_LL_SAMPLES_CAP ((160 * 1024 / 8 - 3 * BB_SCORE_NT - BB_RB_SCALARS) / 3)
-static_assert(BB_LL_LDS_DOUBLES(BB_LL_SAMPLES_CAP) * 8 <= 160 * 1024 && BB_LL_LDS_DOUBLES(BB_LL_SAMPLES_CAP + 1) * 8 > 160 * 1024,
-              "BB_LL_SAMPLES_CAP is the largest count that fits");
-static_assert(BB_LL_SAMPLES_CAP == 5781, "3 x 5781 doubles of (x*, s, Z) + 24 KiB of partials + 512 B of scalars <= 160 KiB");
 
 struct LlArgs {
     RbArgs A;                 // as for bb_block_rb: F, probs, nq, n_z; unit [BB_RB_OUT][n_entries]: q_mean, q_sd, rb_mean, rb_sd, lambda_mean,
@@ -141,28 +118,10 @@ BB_DEV void bb_ll_bracket(const LlCond& c, double* lo, double* hi) {
     *hi = h + BB_LL_PAD;
 }
 
-// a local maximum of g in [lo, hi], g'(lo) > 0 >= g'(hi), from x: Newton, a bisection step wherever Newton's leaves the bracket
+// a local maximum of g in [lo, hi], g'(lo) > 0 >= g'(hi), from x
 BB_DEV double bb_ll_solve(const LlCond& c, double lo, double hi, double x) {
-    double g, cv;
-    for (int it = 0; it < BB_LL_MODE_ITER; ++it) {
-        bb_ll_d12(c, x, &g, &cv);
-        if (g == 0.0 || g != g) return x + g;      // (a NaN g': the mode is NaN)
-        if (g > 0.0) lo = x;
-        else hi = x;
-        double xn = x - g / cv;
-        if (!(cv < 0.0 && xn >= lo && xn <= hi)) xn = lo + (hi - lo) / 2.0;
-        const double step = xn - x;
-        x = xn;
-        if (fabs(step) <= 9.094947017729282e-13 * (1.0 + fabs(x))) break;      // 2^-40
-    }
-    bb_ll_d12(c, x, &g, &cv);                       // one more Newton step where it stays inside (bb_ltrb.h)
-    const double xn = x - g / cv;
-    return cv < 0.0 && xn >= lo && xn <= hi ? xn : x;
-}
-
-// an interval count from a quotient: ceil(x - 2^-20) where 1 <= x <= 1e9, else 1 (a NaN included)
-BB_DEV long long bb_ll_count(double x) {
-    return (x >= 1.0 && x <= 1e9) ? (long long)ceil(x - BB_LL_SLACK) : 1;
+    double g, cv;                                   // (g' and g'' come together)
+    return bb_grid_solve(lo, hi, x, [&](double u) { bb_ll_d12(c, u, &g, &cv); return g; }, [&](double) { return cv; });
 }
 
 // The modes, the anchor and the grid of one draw; c comes in about the draw x0 and leaves about the global mode x*.  Returns the
@@ -189,7 +148,7 @@ BB_DEV double bb_ll_setup(LlCond& c, int* nleft, int* nright) {
         g0 = g1;
     }
     if (!any) { best = gfirst > 0.0 ? bhi : blo; gbest = bb_ll_lnp(c, best, &e); }      // (no sign change: rounding at an end of the bracket)
-    // second scan: the modes within exp(BB_LL_TAIL) of it -- the outermost two and the smallest curvature scale
+    // second scan: the modes within exp(BB_GRID_TAIL) of it -- the outermost two and the smallest curvature scale
     double left = best, right = best, dl0 = 0.0, dl1 = 0.0, dmin = INFINITY, gg, cv;
     bool kept = false;
     g0 = gfirst;
@@ -197,7 +156,7 @@ BB_DEV double bb_ll_setup(LlCond& c, int* nleft, int* nright) {
         const double e0 = blo + (double)i * cw, e1 = i + 1 < nc ? blo + (double)(i + 1) * cw : bhi, g1 = bb_ll_d1(c, e1);
         if (g0 > 0.0 && !(g1 > 0.0)) {
             const double m = bb_ll_solve(c, e0, e1, e0 + (e1 - e0) / 2.0), v = bb_ll_lnp(c, m, &e);
-            if (gbest - v <= -BB_LL_TAIL) {
+            if (gbest - v <= -BB_GRID_TAIL) {
                 bb_ll_d12(c, m, &gg, &cv);
                 const double d = 1.0 / sqrt(-cv);
                 if (!kept) { left = m; dl0 = d; }
@@ -215,36 +174,8 @@ BB_DEV double bb_ll_setup(LlCond& c, int* nleft, int* nright) {
     left -= best;
     right -= best;
     bb_ll_anchor(c, best);
-    double m = isfinite(dmin) ? ceil(2.0 * dmin - BB_LL_SLACK) : 1.0;
-    m = m >= 1.0 ? (m <= (double)BB_LL_REFINE_MAX ? m : (double)BB_LL_REFINE_MAX) : 1.0;
-    const double s = dmin / (4.0 * m);
-    int r = 1;
-    while (r < BB_LL_REACH_MAX && bb_ll_lnp(c, left - (double)(BB_LL_REACH * r) * dl0, &e) > BB_LL_TAIL) r *= 2;
-    const double end0 = left - (double)(BB_LL_REACH * r) * dl0;
-    r = 1;
-    while (r < BB_LL_REACH_MAX && bb_ll_lnp(c, right + (double)(BB_LL_REACH * r) * dl1, &e) > BB_LL_TAIL) r *= 2;
-    const double end1 = right + (double)(BB_LL_REACH * r) * dl1;
-    const long long nl = bb_ll_count(-end0 / s), nr = bb_ll_count(end1 / s);
-    const long long f = (nl + nr + BB_LL_NODES_MAX - 1) / BB_LL_NODES_MAX;
-    *nleft = (int)((nl + f - 1) / f);
-    *nright = (int)((nr + f - 1) / f);
-    return s * (double)f;
-}
-
-// draw j's CDF at x, times Z_j: the trapezoid on N + 1 equidistant nodes from lo_j to x less the first Euler-Maclaurin end term;
-// lo_j < x < hi_j; c about the global mode
-BB_DEV double bb_ll_cdf_z(const LlCond& c, double s, double lo, double x) {
-    const double r = x - lo, ulo = lo - c.x;
-    double N = ceil(r / s);
-    N = N >= 1.0 ? N : 1.0;
-    const double sx = r / N;
-    const int n = (int)N;
-    double e;
-    const double ux = x - c.x, p0 = exp(bb_ll_lnp(c, ulo, &e)), p1 = exp(bb_ll_lnp(c, ux, &e));
-    double acc = 0.5 * p0;
-    for (int i = 1; i < n; ++i) acc += exp(bb_ll_lnp(c, ulo + (double)i * sx, &e));
-    acc += 0.5 * p1;
-    return sx * acc - sx * sx / 12.0 * (bb_ll_d1(c, ux) * p1 - bb_ll_d1(c, ulo) * p0);
+    // (left, right and the ends as offsets from the global mode)
+    return bb_grid_layout(left, right, dl0, dl1, dmin, 0.0, nleft, nright, [&](double u) { return bb_ll_lnp(c, u, &e); });
 }
 
 // the weight and the residual of data column i at step k of replicate r, draw j (the header's w_{i,k}, rho_{i,k})
@@ -324,29 +255,64 @@ BB_DEV void bb_block_ll_sum(BBCtx& cx, const LlArgs& L, int nblocks) {
     }
 }
 
+// The conditionals of one entry for bb_grid_mixture: rows 0 .. 5 of the block's table hold the draws' coefficients about the draw
+// itself (pass C of bb_block_ll), x0 among them; sweep A puts the ones that move with the base point back about the global mode.
+struct LlMix : GridRows {
+    typedef LlCond Cond;
+    static constexpr int NX = 1;          // lambda_mean
+    static constexpr bool L_KEPT = true;  // pass C put x0 there
+    double a, ib2, R;         // the entry's prior and count
+    const double *Asj, *wsj;
+    double *Bsj, *wrj, *f0j, *loj;
+
+    BB_MEM LlMix(double a_, double ib2_, double R_, double* tab, long long ns) : a(a_), ib2(ib2_), R(R_) {
+        Asj = tab; wsj = tab + ns; Bsj = tab + 2 * ns; wrj = tab + 3 * ns; f0j = tab + 4 * ns;
+        l = tab + 5 * ns; E = tab + 6 * ns; V = tab + 7 * ns; x0 = tab + 8 * ns; loj = tab + 9 * ns; hi = tab + 10 * ns;
+        x1 = two = nullptr;
+    }
+    BB_MEM void cond(LlCond& c, int j, double x) const {
+        c.a = a; c.ib2 = ib2; c.R = R; c.As = Asj[j]; c.ws = wsj[j];
+        c.x = x; c.ex = exp(x); c.f0 = f0j[j]; c.Bs = Bsj[j]; c.wr = wrj[j];
+    }
+    BB_MEM double setup(int j, LlCond& c, double* w, int* nleft, int* nright, bool*) const {
+        cond(c, j, l[j]);
+        const double s = bb_ll_setup(c, nleft, nright);
+        *w = s;
+        return s;
+    }
+    BB_MEM double p(const LlCond& c, double u, double* em) const { return exp(bb_ll_lnp(c, u, em)); }
+    BB_MEM void extras(const LlCond&, double p, double, double em, double* se, double*) const { *se += p * (em + 1.0); }
+    BB_MEM double finish0(const LlCond& c, double z, double se) const { return c.ex * (se / z); }
+    BB_MEM double finish1(const LlCond&, double, double x) const { return x; }
+    BB_MEM double mode(const LlCond& c) const { return c.x; }
+    BB_MEM double latent(int j) const { return l[j]; }
+    BB_MEM void keep(int j, const LlCond& c, double lm, double s, int nleft) const {
+        Bsj[j] = c.Bs; wrj[j] = c.wr; f0j[j] = c.f0;
+        loj[j] = lm - (double)nleft * s;
+    }
+    BB_MEM double lo(int j, double, double) const { return loj[j]; }
+    BB_MEM void reopen(int j, LlCond& c, double lm) const { cond(c, j, lm); }
+    // (h' takes the offset)
+    BB_MEM double cdf_z(const LlCond& c, double s, double lo, double x) const {
+        const double ulo = lo - c.x, ux = x - c.x;
+        return bb_grid_cdf_z(x - lo, s, ulo, ux, [&](double u, double* em) { return exp(bb_ll_lnp(c, u, em)); },
+                             [&](bool upper, double) { return bb_ll_d1(c, upper ? ux : ulo); });
+    }
+};
+
 BB_DEV void bb_block_ll(BBCtx& cx, const LlArgs& L, int nblocks) {
     const RbArgs& A = L.A;
     const FreqArgs& F = A.F;
     const PpcArgs& P = F.P;
-    const int ns = P.n_samples, nq = A.nq;
+    const int ns = P.n_samples;
     const long long n_units = A.n_units;
     double* tab = A.ytab + (long long)cx.block * BB_LL_TAB * ns;
-    double* ms = cx.lds;
-    double* ssj = cx.lds + ns;
-    double* zz = cx.lds + 2 * (long long)ns;
-    double* red = cx.lds + 3 * (long long)ns;
-    double* st = red + 3 * BB_SCORE_NT;
     double* Asj = tab;
     double* wsj = tab + ns;
     double* Bsj = tab + 2 * (long long)ns;
     double* wrj = tab + 3 * (long long)ns;
     double* f0j = tab + 4 * (long long)ns;
     double* lj = tab + 5 * (long long)ns;
-    double* ej = tab + 6 * (long long)ns;
-    double* vj = tab + 7 * (long long)ns;
-    double* lamj = tab + 8 * (long long)ns;
-    double* loj = tab + 9 * (long long)ns;
-    double* hij = tab + 10 * (long long)ns;
     for (long long x = cx.block; x < L.n_req; x += nblocks) {
         const long long row = L.rows ? L.rows[x] : x;
         const int r = (int)(row / F.B);
@@ -377,132 +343,7 @@ BB_DEV void bb_block_ll(BBCtx& cx, const LlArgs& L, int nblocks) {
                     lj[j] = x0;
                 }
             }
-            // sweep A: modes, grid and per-draw moments; first sums
-            BB_PASS(cx, tid) {
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    LlCond c;
-                    const double l = lj[j];
-                    c.a = a; c.ib2 = ib2; c.R = Rc; c.As = Asj[j]; c.ws = wsj[j];
-                    c.x = l; c.ex = exp(l); c.f0 = f0j[j]; c.Bs = Bsj[j]; c.wr = wrj[j];
-                    int nleft = 0, nright = 0;
-                    const double s = bb_ll_setup(c, &nleft, &nright);
-                    const int nodes = nleft + nright;
-                    double z = 0.0, m1 = 0.0, m2 = 0.0, se = 0.0;
-                    for (int k = 0; k <= nodes; ++k) {
-                        const double uk = (double)(k - nleft) * s;
-                        double em;
-                        double p = exp(bb_ll_lnp(c, uk, &em));
-                        if (k == 0 || k == nodes) p *= 0.5;
-                        z += p;
-                        m1 += p * uk;
-                        m2 += p * (uk * uk);
-                        se += p * (em + 1.0);
-                    }
-                    const double Zj = s * z, r1 = m1 / z, Ej = c.x + r1, Vj = m2 / z - r1 * r1, Lj = c.ex * (se / z);
-                    ms[j] = c.x; ssj[j] = s; zz[j] = Zj;
-                    Bsj[j] = c.Bs; wrj[j] = c.wr; f0j[j] = c.f0;
-                    ej[j] = Ej; vj[j] = Vj; lamj[j] = Lj;
-                    loj[j] = c.x - (double)nleft * s; hij[j] = c.x + (double)nright * s;
-                    a0 += l;
-                    a1 += Ej;
-                    a2 += Vj;
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = a2;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st, false);
-            // sweep A': the other first sums; the largest hi_j (NaN where Z_j is not finite)
-            BB_PASS(cx, tid) {
-                double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    a0 += lamj[j];
-                    a1 += ms[j];
-                    mx = bb_score_max(mx, isfinite(zz[j]) ? hij[j] : (double)NAN);
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st + 3, true);
-            // sweep B: centred second moments; the smallest lo_j (as the largest of -lo_j)
-            BB_PASS(cx, tid) {
-                const double qm = st[0] / ns, rm = st[1] / ns;
-                double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    const double d0 = lj[j] - qm, d1 = ej[j] - rm;
-                    a0 += d0 * d0;
-                    a1 += d1 * d1;
-                    mx = bb_score_max(mx, -loj[j]);
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st + 6, true);
-            BB_PASS(cx, tid) {
-                if (tid == 0) {
-                    A.unit[0 * n_units + ent] = st[0] / ns;
-                    A.unit[1 * n_units + ent] = sqrt(st[6] / ns);
-                    A.unit[2 * n_units + ent] = st[1] / ns;
-                    A.unit[3 * n_units + ent] = sqrt(st[2] / ns + st[7] / ns);
-                    A.unit[4 * n_units + ent] = st[3] / ns;
-                    A.unit[5 * n_units + ent] = st[4] / ns;
-                    const double lo = -st[8], hi = st[5];
-                    st[15] = (nq > 0 && isfinite(lo) && isfinite(hi)) ? 1.0 : 0.0;
-                    for (int i = 0; i < nq; ++i) { st[16 + i] = lo; st[24 + i] = hi; }
-                }
-            }
-            BB_SYNC(cx);
-            if (nq > 0 && st[15] == 0.0) {   // a non-finite x*_j, s_j or Z_j: no bracket
-                BB_PASS(cx, tid) { if (tid < nq) A.quant[ent * BB_RB_MAX_Q + tid] = NAN; }
-            } else if (nq > 0) {
-                for (int it = 0; it < BB_LL_ITER; ++it) {
-                    for (int q0 = 0; q0 < nq; q0 += 3) {
-                        // sweep Q: the mixture CDF at the midpoints of up to three brackets
-                        BB_PASS(cx, tid) {
-                            const int nx = nq - q0 < 3 ? nq - q0 : 3;
-                            double acc[3] = {0.0, 0.0, 0.0}, xs[3];
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) {
-                                const int qi = i < nx ? q0 + i : q0;
-                                xs[i] = st[16 + qi] + (st[24 + qi] - st[16 + qi]) / 2.0;
-                            }
-                            for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                                LlCond c;
-                                const double lo = loj[j], hi = hij[j];
-                                bool have = false;
-#pragma unroll
-                                for (int i = 0; i < 3; ++i) {
-                                    if (i >= nx) continue;
-                                    const double xq = xs[i];
-                                    if (xq <= lo) continue;                       // C_j = 0
-                                    if (xq >= hi) { acc[i] += 1.0; continue; }    // C_j = 1
-                                    if (!have) {
-                                        c.a = a; c.ib2 = ib2; c.R = Rc; c.As = Asj[j]; c.ws = wsj[j];
-                                        c.x = ms[j]; c.ex = exp(c.x); c.f0 = f0j[j]; c.Bs = Bsj[j]; c.wr = wrj[j];
-                                        have = true;
-                                    }
-                                    const double Cq = bb_ll_cdf_z(c, ssj[j], lo, xq) / zz[j];
-                                    acc[i] += Cq < 0.0 ? 0.0 : (Cq > 1.0 ? 1.0 : Cq);
-                                }
-                            }
-                            red[tid] = acc[0]; red[BB_SCORE_NT + tid] = acc[1]; red[2 * BB_SCORE_NT + tid] = acc[2];
-                        }
-                        BB_SYNC(cx);
-                        bb_score_reduce(cx, red, st + 12, false);
-                        BB_PASS(cx, tid) {
-                            if (tid < 3 && q0 + tid < nq) {
-                                const int i = q0 + tid;
-                                const double xq = st[16 + i] + (st[24 + i] - st[16 + i]) / 2.0;
-                                if (st[12 + tid] / ns < A.probs[i]) st[16 + i] = xq;
-                                else st[24 + i] = xq;
-                            }
-                        }
-                        BB_SYNC(cx);
-                    }
-                }
-                BB_PASS(cx, tid) { if (tid < nq) A.quant[ent * BB_RB_MAX_Q + tid] = st[16 + tid] + (st[24 + tid] - st[16 + tid]) / 2.0; }
-            }
-            BB_SYNC(cx);
+            bb_grid_mixture(cx, ns, A.nq, A.probs, cx.lds, A.unit, n_units, ent, A.quant, LlMix(a, ib2, Rc, tab, ns));
         }
     }
 }

@@ -13,37 +13,19 @@
 //   BC   bb_block_ls_bc   : one workgroup of BB_SCORE_NT threads per mutant row (r, m), row += nblocks.  Per environment e (entry
 //        u = bb_fitness_rb's unit) one walk over the row's loglambda draws, the unit's s_j in a register (so no accumulator is indexed
 //        by a run-time environment: that would be scratch memory): SS_j += d_t^2 for the steps of e, ascending t, from 0.0, into the
-//        block's slice of a global table; then bb_ls_mixture.
+//        block's slice of a global table; then bb_grid_mixture (bb_gridmix.h: the sweeps, the NaN rule, the quantiles) over LsMix.
 //   POP  bb_block_ls_pop_part : one workgroup per (group g = (r, k), chunk of BB_POP_CHUNK consecutive neutral members),
 //        work += nblocks; per draw the chunk's sum of d_i^2 from 0.0 in index order, the ragged method's pairing as in
 //        bb_block_pop_part, into part[work][n_samples].
-//        bb_block_ls_pop  : one workgroup per group; per draw the chunk partials from 0.0 in chunk order; then bb_ls_mixture.
-//   bb_ls_mixture, shared (draw j is lane j mod BB_SCORE_NT's in every sweep, so a lane reads only table entries it wrote):
-//     A  per draw the mode, delta, the grid: l*, delta, Z into LDS; l, E, V, S, hi into the block's table -> sum l, sum E, sum V
-//     A' (no arithmetic on the grid)                                                                       -> sum S, sum l*, max hi_j
-//     B  centred second moments                                            -> sum (l - q_mean)^2, sum (E - rb_mean)^2, max -lo_j
-//     Q  bisection of the mixture CDF, BB_LS_ITER steps, up to three quantiles per sweep as bb_rb_mixture does; a draw whose
-//        [lo_j, hi_j] does not hold the midpoint adds 0 or 1 and evaluates nothing.
-// The maximum of hi_j takes NaN for a draw whose Z_j is not finite, so that the bracket is finite exactly when every l*_j, delta_j
-// and Z_j is.  Sums and maxima in bb_score_reduce's order; exp, expm1, log, sqrt, ceil are the platform's, as in bb_rb.h.
-// Barrier-separated passes, so the host emulation (BB_EMU) runs the same source.
+//        bb_block_ls_pop  : one workgroup per group; per draw the chunk partials from 0.0 in chunk order; then the same.
+// exp, expm1, log, sqrt, ceil are the platform's, as in bb_rb.h.
 #pragma once
-#include "bb_rb.h"
+#include "bb_gridmix.h"
 
-#define BB_LS_ITER 40                      // bisection steps
 #define BB_LS_LEFT 10                      // the grid starts at lo = l* - 10 delta ...
 #define BB_LS_RIGHT 22                     // ... and ends at hi = l* + 22 r delta, r = 1, 2, 4 .. BB_LS_RIGHT_MAX: the first at which the
-#define BB_LS_RIGHT_MAX 64                 //     density has fallen to exp(BB_LS_TAIL) of its mode's
-#define BB_LS_TAIL (-40.0)
-#define BB_LS_REFINE_MAX 64                // the step is delta / (4 m), m = ceil(2 delta) up to this (a delta of 32 is no log-scale's)
+#define BB_LS_RIGHT_MAX 64                 //     density has fallen to exp(BB_GRID_TAIL) of its mode's
 #define BB_LS_TAB 6                        // per-block global table [6][n_samples]: SS_j, l_j, E_j, V_j, S_j, hi_j
-// LDS: l*[n_samples] | delta[n_samples] | Z[n_samples] | three arrays of BB_SCORE_NT partials | scalars (bb_rb.h's st[] layout)
-#define BB_LS_LDS_DOUBLES(ns) (3 * (long long)(ns) + 3 * BB_SCORE_NT + BB_RB_SCALARS)
-// the largest n_samples whose layout fits the 160 KiB of LDS a workgroup can have
-#define BB_LS_SAMPLES_CAP ((160 * 1024 / 8 - 3 * BB_SCORE_NT - BB_RB_SCALARS) / 3)
-static_assert(BB_LS_LDS_DOUBLES(BB_LS_SAMPLES_CAP) * 8 <= 160 * 1024 && BB_LS_LDS_DOUBLES(BB_LS_SAMPLES_CAP + 1) * 8 > 160 * 1024,
-              "BB_LS_SAMPLES_CAP is the largest count that fits");
-static_assert(BB_LS_SAMPLES_CAP == 5781, "3 x 5781 doubles of (l*, delta, Z) + 24 KiB of partials + 512 B of scalars <= 160 KiB");
 
 struct LsArgs {
     RbArgs A;                 // as for bb_block_rb: F, probs, nq, n_z; unit [BB_RB_OUT][n_entries]: q_mean, q_sd, rb_mean, rb_sd, sigma_mean,
@@ -96,11 +78,8 @@ BB_DEV double bb_ls_mode(LsCond& c, double SS) {
     return 1.0 / sqrt(c.ib2 + 2.0 * c.W);
 }
 
-// m of bb_ls_grid: max(1, ceil(2 delta)), at most BB_LS_REFINE_MAX (and 1 for a NaN delta)
-BB_DEV double bb_ls_refine(double dl) {
-    const double m = ceil(2.0 * dl);
-    return m >= 1.0 ? (m <= (double)BB_LS_REFINE_MAX ? m : (double)BB_LS_REFINE_MAX) : 1.0;
-}
+// m of bb_ls_grid: max(1, ceil(2 delta)), at most BB_GRID_REFINE_MAX (and 1 for a NaN delta)
+BB_DEV double bb_ls_refine(double dl) { return bb_grid_refine(ceil(2.0 * dl)); }
 
 // The grid of one draw: the step s = delta / (4 m), m = max(1, ceil(2 delta)), so that s <= 1/8 whatever delta is -- the factor
 // exp(-(SS / 2) e^{-2l}) cuts the density off on the left over a width of about 1/2 in l, which a step of delta / 4 alone does not
@@ -110,175 +89,60 @@ BB_DEV double bb_ls_grid(const LsCond& c, double dl, int* nleft, int* nright) {
     const double m = bb_ls_refine(dl);
     int r = 1;
     double e;
-    while (r < BB_LS_RIGHT_MAX && log(bb_ls_p(c, (double)(BB_LS_RIGHT * r) * dl, &e)) > BB_LS_TAIL) r *= 2;
+    while (r < BB_LS_RIGHT_MAX && log(bb_ls_p(c, (double)(BB_LS_RIGHT * r) * dl, &e)) > BB_GRID_TAIL) r *= 2;
     const int m4 = 4 * (int)m;
     *nleft = BB_LS_LEFT * m4;
     *nright = BB_LS_RIGHT * r * m4;
     return dl / (double)m4;
 }
 
-// draw j's CDF at x, times Z_j: the trapezoid on N + 1 equidistant nodes from lo_j to x less the first Euler-Maclaurin end term;
-// lo_j < x < hi_j
-BB_DEV double bb_ls_cdf_z(const LsCond& c, double dl, double x) {
-    const double mm = bb_ls_refine(dl);
-    const double ulo = -10.0 * dl, r = x - (c.lm + ulo), s = dl / (4.0 * mm);
-    double N = ceil(r / s);
-    N = N >= 1.0 ? N : 1.0;
-    const double sx = r / N;
-    const int n = (int)N;
-    double e0, e1;
-    const double p0 = bb_ls_p(c, ulo, &e0), ux = x - c.lm, p1 = bb_ls_p(c, ux, &e1);
-    double acc = 0.5 * p0, e;
-    for (int i = 1; i < n; ++i) acc += bb_ls_p(c, ulo + (double)i * sx, &e);
-    acc += 0.5 * p1;
-    return sx * acc - sx * sx / 12.0 * (bb_ls_dh(c, ux, e1) * p1 - bb_ls_dh(c, ulo, e0) * p0);
-}
+// The conditionals of one entry for bb_grid_mixture, shared by both blocks: row 0 of the block's table holds SS_j (the caller's
+// pass, same lane), parameter `own` of the draws is the entry's own l_j.  Nothing but the sweeps' rows is kept: lo_j = l* - 10 delta
+// and the coefficients are formed again from (l*, delta) in LDS and SS_j.
+struct LsMix : GridRows {
+    typedef LsCond Cond;
+    static constexpr int NX = 1;          // sigma_mean
+    static constexpr bool L_KEPT = false;
+    const PpcArgs& P;
+    long long own;
+    double a, ib2;            // the entry's prior
+    int nterms;
+    const double* ss;
 
-// The mixture of an entry's conditionals, shared by both blocks: ss[j] holds SS_j (the caller's pass, same lane), latent(j) gives
-// the entry's own draw l_j; the six results go to unit[k n_units + u], the nq quantiles to quant[u][BB_RB_MAX_Q].  tab: the block's
-// [BB_LS_TAB][ns] table, row 0 == ss.  Ends with a barrier: the next entry's sweep A overwrites what this one read.
-template <class Latent>
-BB_DEV void bb_ls_mixture(BBCtx& cx, int ns, int nq, const double* probs, double a, double ib2, int nterms, double* tab, double* lds,
-                          double* unit, long long n_units, long long u, double* quant, Latent&& latent) {
-    double* ms = lds;
-    double* dls = lds + ns;
-    double* zz = lds + 2 * (long long)ns;
-    double* red = lds + 3 * (long long)ns;
-    double* st = red + 3 * BB_SCORE_NT;
-    const double* ss = tab;
-    double* lj = tab + ns;
-    double* ej = tab + 2 * (long long)ns;
-    double* vj = tab + 3 * (long long)ns;
-    double* sgj = tab + 4 * (long long)ns;
-    double* hij = tab + 5 * (long long)ns;
-    // sweep A: mode, grid and per-draw moments; first sums
-    BB_PASS(cx, tid) {
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-        for (int j = tid; j < ns; j += BB_SCORE_NT) {
-            LsCond c;
-            c.a = a; c.ib2 = ib2; c.n = (double)nterms;
-            const double dl = bb_ls_mode(c, ss[j]);
-            int nleft = 0, nright = 0;
-            const double s = bb_ls_grid(c, dl, &nleft, &nright);
-            const int nodes = nleft + nright;
-            double z = 0.0, m1 = 0.0, m2 = 0.0, se = 0.0;
-            for (int k = 0; k <= nodes; ++k) {
-                const double uk = (double)(k - nleft) * s;
-                double e;
-                double p = bb_ls_p(c, uk, &e);
-                if (k == 0 || k == nodes) p *= 0.5;
-                z += p;
-                m1 += p * uk;
-                m2 += p * (uk * uk);
-                se += p * exp(uk);
-            }
-            const double Z = s * z, r1 = m1 / z, E = c.lm + r1, V = m2 / z - r1 * r1, S = exp(c.lm) * (se / z);
-            const double l = latent(j);
-            ms[j] = c.lm; dls[j] = dl; zz[j] = Z;
-            lj[j] = l; ej[j] = E; vj[j] = V; sgj[j] = S; hij[j] = c.lm + (double)nright * s;
-            a0 += l;
-            a1 += E;
-            a2 += V;
-        }
-        red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = a2;
+    BB_MEM LsMix(const PpcArgs& P_, long long own_, double a_, double ib2_, int nterms_, double* tab) : P(P_), own(own_), a(a_), ib2(ib2_), nterms(nterms_), ss(tab) {
+        const long long ns = P.n_samples;
+        l = tab + ns; E = tab + 2 * ns; V = tab + 3 * ns; x0 = tab + 4 * ns; hi = tab + 5 * ns;
+        x1 = two = nullptr;
     }
-    BB_SYNC(cx);
-    bb_score_reduce(cx, red, st, false);
-    // sweep A': the other first sums; the largest hi_j (NaN where Z_j is not finite)
-    BB_PASS(cx, tid) {
-        double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
-        for (int j = tid; j < ns; j += BB_SCORE_NT) {
-            a0 += sgj[j];
-            a1 += ms[j];
-            mx = bb_score_max(mx, isfinite(zz[j]) ? hij[j] : (double)NAN);
-        }
-        red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
+    BB_MEM double setup(int j, LsCond& c, double* w, int* nleft, int* nright, bool*) const {
+        c.a = a; c.ib2 = ib2; c.n = (double)nterms;
+        const double dl = bb_ls_mode(c, ss[j]);
+        *w = dl;
+        return bb_ls_grid(c, dl, nleft, nright);
     }
-    BB_SYNC(cx);
-    bb_score_reduce(cx, red, st + 3, true);
-    // sweep B: centred second moments; the smallest lo_j (as the largest of -lo_j)
-    BB_PASS(cx, tid) {
-        const double qm = st[0] / ns, rm = st[1] / ns;
-        double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
-        for (int j = tid; j < ns; j += BB_SCORE_NT) {
-            const double d0 = lj[j] - qm, d1 = ej[j] - rm;
-            a0 += d0 * d0;
-            a1 += d1 * d1;
-            mx = bb_score_max(mx, -(ms[j] - 10.0 * dls[j]));
-        }
-        red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
+    BB_MEM double p(const LsCond& c, double u, double* em1) const { return bb_ls_p(c, u, em1); }
+    BB_MEM void extras(const LsCond&, double p, double u, double, double* se, double*) const { *se += p * exp(u); }
+    BB_MEM double finish0(const LsCond& c, double z, double se) const { return exp(c.lm) * (se / z); }
+    BB_MEM double finish1(const LsCond&, double, double x) const { return x; }
+    BB_MEM double mode(const LsCond& c) const { return c.lm; }
+    BB_MEM double latent(int j) const { return bb_ppc_param(P, own, j); }
+    BB_MEM void keep(int, const LsCond&, double, double, int) const {}
+    BB_MEM double lo(int, double lm, double dl) const { return lm - 10.0 * dl; }
+    BB_MEM void reopen(int j, LsCond& c, double lm) const {
+        const double SS = ss[j];
+        c.a = a; c.ib2 = ib2; c.n = (double)nterms;
+        c.lm = lm;
+        c.W = SS == 0.0 ? 0.0 : SS * exp(-2.0 * lm);
+        c.c1 = ib2 * (lm - a) + c.n;
     }
-    BB_SYNC(cx);
-    bb_score_reduce(cx, red, st + 6, true);
-    BB_PASS(cx, tid) {
-        if (tid == 0) {
-            unit[0 * n_units + u] = st[0] / ns;
-            unit[1 * n_units + u] = sqrt(st[6] / ns);
-            unit[2 * n_units + u] = st[1] / ns;
-            unit[3 * n_units + u] = sqrt(st[2] / ns + st[7] / ns);
-            unit[4 * n_units + u] = st[3] / ns;
-            unit[5 * n_units + u] = st[4] / ns;
-            const double lo = -st[8], hi = st[5];
-            st[15] = (nq > 0 && isfinite(lo) && isfinite(hi)) ? 1.0 : 0.0;
-            for (int i = 0; i < nq; ++i) { st[16 + i] = lo; st[24 + i] = hi; }
-        }
+    // (the lower end as an offset, and the step, once more from delta: lo_j is not read here)
+    BB_MEM double cdf_z(const LsCond& c, double dl, double, double x) const {
+        const double mm = bb_ls_refine(dl);
+        const double ulo = -10.0 * dl, r = x - (c.lm + ulo), s = dl / (4.0 * mm), ux = x - c.lm;
+        return bb_grid_cdf_z(r, s, ulo, ux, [&](double u, double* em1) { return bb_ls_p(c, u, em1); },
+                             [&](bool upper, double em1) { return bb_ls_dh(c, upper ? ux : ulo, em1); });
     }
-    BB_SYNC(cx);
-    if (nq > 0 && st[15] == 0.0) {   // a non-finite l*_j, delta_j or Z_j: no bracket
-        BB_PASS(cx, tid) { if (tid < nq) quant[u * BB_RB_MAX_Q + tid] = NAN; }
-    } else if (nq > 0) {
-        for (int it = 0; it < BB_LS_ITER; ++it) {
-            for (int q0 = 0; q0 < nq; q0 += 3) {
-                // sweep Q: the mixture CDF at the midpoints of up to three brackets
-                BB_PASS(cx, tid) {
-                    const int nx = nq - q0 < 3 ? nq - q0 : 3;
-                    double acc[3] = {0.0, 0.0, 0.0}, xs[3];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        const int qi = i < nx ? q0 + i : q0;
-                        xs[i] = st[16 + qi] + (st[24 + qi] - st[16 + qi]) / 2.0;
-                    }
-                    for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                        LsCond c;
-                        c.a = a; c.ib2 = ib2; c.n = (double)nterms;
-                        const double lm = ms[j], dl = dls[j], lo = lm - 10.0 * dl, hi = hij[j];
-                        bool have = false;
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            if (i >= nx) continue;
-                            const double x = xs[i];
-                            if (x <= lo) continue;                       // C_j = 0
-                            if (x >= hi) { acc[i] += 1.0; continue; }    // C_j = 1
-                            if (!have) {
-                                const double SS = ss[j];
-                                c.lm = lm;
-                                c.W = SS == 0.0 ? 0.0 : SS * exp(-2.0 * lm);
-                                c.c1 = ib2 * (lm - a) + c.n;
-                                have = true;
-                            }
-                            const double C = bb_ls_cdf_z(c, dl, x) / zz[j];
-                            acc[i] += C < 0.0 ? 0.0 : (C > 1.0 ? 1.0 : C);
-                        }
-                    }
-                    red[tid] = acc[0]; red[BB_SCORE_NT + tid] = acc[1]; red[2 * BB_SCORE_NT + tid] = acc[2];
-                }
-                BB_SYNC(cx);
-                bb_score_reduce(cx, red, st + 12, false);
-                BB_PASS(cx, tid) {
-                    if (tid < 3 && q0 + tid < nq) {
-                        const int i = q0 + tid;
-                        const double x = st[16 + i] + (st[24 + i] - st[16 + i]) / 2.0;
-                        if (st[12 + tid] / ns < probs[i]) st[16 + i] = x;
-                        else st[24 + i] = x;
-                    }
-                }
-                BB_SYNC(cx);
-            }
-        }
-        BB_PASS(cx, tid) { if (tid < nq) quant[u * BB_RB_MAX_Q + tid] = st[16 + tid] + (st[24 + tid] - st[16 + tid]) / 2.0; }
-    }
-    BB_SYNC(cx);
-}
+};
 
 BB_DEV void bb_block_ls_bc(BBCtx& cx, const LsArgs& L, int nblocks) {
     const RbArgs& A = L.A;
@@ -320,8 +184,7 @@ BB_DEV void bb_block_ls_bc(BBCtx& cx, const LsArgs& L, int nblocks) {
                 }
             }
             const double a = P.pri_mean_e ? P.pri_mean_e[ent] : P.pri_mean, ib2 = P.pri_ivar_e ? P.pri_ivar_e[ent] : P.pri_ivar;
-            bb_ls_mixture(cx, ns, A.nq, A.probs, a, ib2, nu, tab, cx.lds, A.unit, A.n_units, ent, A.quant,
-                          [&](int j) { return bb_ppc_param(P, P.lo_ls + ent, j); });
+            bb_grid_mixture(cx, ns, A.nq, A.probs, cx.lds, A.unit, A.n_units, ent, A.quant, LsMix(P, P.lo_ls + ent, a, ib2, nu, tab));
         }
     }
 }
@@ -375,7 +238,6 @@ BB_DEV void bb_block_ls_pop(BBCtx& cx, const LsArgs& L, int nblocks) {
             }
         }
         const double a = P.pri_mean_e ? P.pri_mean_e[g] : P.pri_mean, ib2 = P.pri_ivar_e ? P.pri_ivar_e[g] : P.pri_ivar;
-        bb_ls_mixture(cx, ns, A.nq, A.probs, a, ib2, (int)A.F.nn, tab, cx.lds, A.unit, A.n_units, g, A.quant,
-                      [&](int j) { return bb_ppc_param(P, P.lo_lspop + g, j); });
+        bb_grid_mixture(cx, ns, A.nq, A.probs, cx.lds, A.unit, A.n_units, g, A.quant, LsMix(P, P.lo_lspop + g, a, ib2, (int)A.F.nn, tab));
     }
 }

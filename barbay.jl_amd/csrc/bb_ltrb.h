@@ -16,39 +16,17 @@
 //   bb_block_lt : one workgroup of BB_SCORE_NT threads per mutant row (r, m), row += nblocks.  Per environment e (entry = the unit's
 //        place in the caller's logtau block) one walk over the row's loglambda draws, y in a register (no accumulator is indexed by a
 //        run-time environment: that would be scratch memory): y_j += gamma_t + sbar_t for the steps of e, ascending t, from 0.0; the
-//        draw's two coefficients (A, B) or (v, q) into the block's slice of a global table; then, draw j being lane j mod
-//        BB_SCORE_NT's in every sweep, so that a lane reads only table entries it wrote:
-//     A  per draw the modes, the grid, the moments: l*, s, Z into LDS; l, E, V, T, P, lo, hi, two into the table -> sum l, E, V
-//     A' (no arithmetic on the grid)                                                            -> sum T, P, l*;  sum two, max hi_j
-//     B  centred second moments                                         -> sum (l - q_mean)^2, sum (E - rb_mean)^2, max -lo_j
-//     Q  bisection of the mixture CDF, BB_LT_ITER steps, up to three quantiles per sweep as bb_rb_mixture does; a draw whose
-//        [lo_j, hi_j] does not hold the midpoint adds 0 or 1 and evaluates nothing.
-// The maximum of hi_j takes NaN for a draw whose Z_j is not finite, so that the bracket is finite exactly when every l*_j, s_j and
-// Z_j is.  Sums and maxima in bb_score_reduce's order; exp, expm1, log, log1p, sqrt, ceil are the platform's, as in bb_rb.h.
-// Barrier-separated passes, so the host emulation (BB_EMU) runs the same source.
+//        draw's two coefficients (A, B) or (v, q) into the block's slice of a global table; then bb_grid_mixture (bb_gridmix.h: the
+//        sweeps, the NaN rule, the quantiles) over LtMix<MODE>, whose two extras are tau and the pooling factor.
+// exp, expm1, log, log1p, sqrt, ceil are the platform's, as in bb_rb.h.
 #pragma once
-#include "bb_rb.h"
+#include "bb_gridmix.h"
 
 #define BB_LT_FULL 0                       // == BB_LOGTAU_FULL / BB_LOGTAU_COLLAPSED of include/barbay_hip.h
 #define BB_LT_COLLAPSED 1
-#define BB_LT_ITER 40                      // bisection steps of a quantile
-#define BB_LT_TAIL (-40.0)                 // a mode is kept, and the grid ends, at exp(BB_LT_TAIL) of the global maximum
-#define BB_LT_REACH 8                      // an end lies 8 r delta beyond its outer mode, r = 1, 2, 4 .. BB_LT_REACH_MAX
-#define BB_LT_REACH_MAX 4096
-#define BB_LT_REFINE_MAX 64                // the step is delta / (4 m), m = ceil(2 delta) up to this
-#define BB_LT_NODES_MAX 8192               // intervals of a draw's grid; beyond it the step is widened by a whole factor
-#define BB_LT_MODE_ITER 100                // steps of the safeguarded iteration of one segment
 #define BB_LT_SEG_ITER 60                  // bisection steps of a zero of h_c''
-#define BB_LT_SLACK 9.5367431640625e-07   // 2^-20, taken off a quotient before ceil: a whole number but for rounding does not tip over
 #define BB_LT_OUT 8                        // per-entry results: q_mean, q_sd, rb_mean, rb_sd, tau_mean, pool_mean, mode_mean, n_two_modes
 #define BB_LT_TAB 10                       // per-block global table [10][n_samples]: c0_j, c1_j, l_j, E_j, V_j, T_j, P_j, lo_j, hi_j, two_j
-// LDS: l*[n_samples] | s[n_samples] | Z[n_samples] | three arrays of BB_SCORE_NT partials | scalars (bb_rb.h's st[] layout)
-#define BB_LT_LDS_DOUBLES(ns) (3 * (long long)(ns) + 3 * BB_SCORE_NT + BB_RB_SCALARS)
-// the largest n_samples whose layout fits the 160 KiB of LDS a workgroup can have
-#define BB_LT_SAMPLES_CAP ((160 * 1024 / 8 - 3 * BB_SCORE_NT - BB_RB_SCALARS) / 3)
-static_assert(BB_LT_LDS_DOUBLES(BB_LT_SAMPLES_CAP) * 8 <= 160 * 1024 && BB_LT_LDS_DOUBLES(BB_LT_SAMPLES_CAP + 1) * 8 > 160 * 1024,
-              "BB_LT_SAMPLES_CAP is the largest count that fits");
-static_assert(BB_LT_SAMPLES_CAP == 5781, "3 x 5781 doubles of (l*, s, Z) + 24 KiB of partials + 512 B of scalars <= 160 KiB");
 
 struct LtArgs {
     RbArgs A;                 // as for bb_block_rb: F, probs, nq, n_z; unit [BB_LT_OUT][n_entries]; quant [n_entries][8]; n_steps [n_entries]:
@@ -95,23 +73,10 @@ BB_DEV double bb_lt_d2(const LtCond& c, double l) {
     return -c.ib2 + bb_lt_G(c, exp(2.0 * l));
 }
 
-// the root of h' in [lo, hi], on which h' falls, from x: Newton, a bisection step wherever Newton's leaves the bracket
+// the root of h' in [lo, hi], on which h' falls, from x
 template <int MODE>
 BB_DEV double bb_lt_solve(const LtCond& c, double lo, double hi, double x) {
-    for (int it = 0; it < BB_LT_MODE_ITER; ++it) {
-        const double g = bb_lt_d1<MODE>(c, x);
-        if (g == 0.0 || g != g) return x + g;      // (a NaN h': the mode is NaN)
-        if (g > 0.0) lo = x;
-        else hi = x;
-        const double cv = bb_lt_d2<MODE>(c, x);
-        double xn = x - g / cv;
-        if (!(cv < 0.0 && xn >= lo && xn <= hi)) xn = lo + (hi - lo) / 2.0;
-        const double step = xn - x;
-        x = xn;
-        if (fabs(step) <= 9.094947017729282e-13 * (1.0 + fabs(x))) break;      // 2^-40
-    }
-    const double g = bb_lt_d1<MODE>(c, x), cv = bb_lt_d2<MODE>(c, x), xn = x - g / cv;      // one more Newton step where it stays inside: the
-    return cv < 0.0 && xn >= lo && xn <= hi ? xn : x;                             // iteration's last step bounds the error by 2^-40 only
+    return bb_grid_solve(lo, hi, x, [&](double l) { return bb_lt_d1<MODE>(c, l); }, [&](double l) { return bb_lt_d2<MODE>(c, l); });
 }
 
 // the local maxima of h, ascending: one or two (the header's segments); returns their number
@@ -214,11 +179,6 @@ BB_DEV double bb_lt_lnp(const LtCond& c, double u, double* e2) {
     return g;
 }
 
-// an interval count from a quotient: ceil(x - 2^-20) where 1 <= x <= 1e9, else 1 (a NaN included)
-BB_DEV long long bb_lt_count(double x) {
-    return (x >= 1.0 && x <= 1e9) ? (long long)ceil(x - BB_LT_SLACK) : 1;
-}
-
 // The modes, the anchor and the grid of one draw: returns the step s; *nleft, *nright: intervals left and right of the global mode,
 // which is a node; *two: two modes kept.
 template <int MODE>
@@ -231,77 +191,81 @@ BB_DEV double bb_lt_setup(LtCond& c, int* nleft, int* nright, bool* two) {
         bb_lt_anchor<MODE>(c, m0);
         const double d = bb_lt_lnp<MODE>(c, m1 - m0, &e);
         glob = d > 0.0 ? m1 : m0;
-        kept2 = fabs(d) <= -BB_LT_TAIL;
+        kept2 = fabs(d) <= -BB_GRID_TAIL;
         left = kept2 ? m0 : glob;
         right = kept2 ? m1 : glob;
     }
     bb_lt_anchor<MODE>(c, glob);
     const double dl0 = 1.0 / sqrt(-bb_lt_d2<MODE>(c, left)), dl1 = kept2 ? 1.0 / sqrt(-bb_lt_d2<MODE>(c, right)) : dl0;
     const double dmin = !kept2 || !(dl1 < dl0) ? dl0 : dl1;
-    double m = isfinite(dmin) ? ceil(2.0 * dmin - BB_LT_SLACK) : 1.0;
-    m = m >= 1.0 ? (m <= (double)BB_LT_REFINE_MAX ? m : (double)BB_LT_REFINE_MAX) : 1.0;
-    const double s = dmin / (4.0 * m);
-    int r = 1;
-    while (r < BB_LT_REACH_MAX && bb_lt_lnp<MODE>(c, (left - (double)(BB_LT_REACH * r) * dl0) - c.lm, &e) > BB_LT_TAIL) r *= 2;
-    const double end0 = left - (double)(BB_LT_REACH * r) * dl0;
-    r = 1;
-    while (r < BB_LT_REACH_MAX && bb_lt_lnp<MODE>(c, (right + (double)(BB_LT_REACH * r) * dl1) - c.lm, &e) > BB_LT_TAIL) r *= 2;
-    const double end1 = right + (double)(BB_LT_REACH * r) * dl1;
-    const long long nl = bb_lt_count((c.lm - end0) / s), nr = bb_lt_count((end1 - c.lm) / s);
-    const long long f = (nl + nr + BB_LT_NODES_MAX - 1) / BB_LT_NODES_MAX;
-    *nleft = (int)((nl + f - 1) / f);
-    *nright = (int)((nr + f - 1) / f);
     *two = kept2;
-    return s * (double)f;
+    // (left, right and the ends in absolute coordinates, the anchor subtracted last)
+    return bb_grid_layout(left, right, dl0, dl1, dmin, c.lm, nleft, nright, [&](double u) { return bb_lt_lnp<MODE>(c, u, &e); });
 }
 
-// draw j's CDF at x, times Z_j: the trapezoid on N + 1 equidistant nodes from lo_j to x less the first Euler-Maclaurin end term;
-// lo_j < x < hi_j
+// The conditionals of one entry for bb_grid_mixture: rows 0 and 1 of the block's table hold the draws' coefficients, row 6 (P_j's)
+// n w until sweep A has read it, same lane (pass Y of bb_block_lt); parameter `own` of the draws is the entry's own l_j.
 template <int MODE>
-BB_DEV double bb_lt_cdf_z(const LtCond& c, double s, double lo, double x) {
-    const double r = x - lo, ulo = lo - c.lm;
-    double N = ceil(r / s);
-    N = N >= 1.0 ? N : 1.0;
-    const double sx = r / N;
-    const int n = (int)N;
-    double e;
-    const double ux = x - c.lm, p0 = exp(bb_lt_lnp<MODE>(c, ulo, &e)), p1 = exp(bb_lt_lnp<MODE>(c, ux, &e));
-    double acc = 0.5 * p0;
-    for (int i = 1; i < n; ++i) acc += exp(bb_lt_lnp<MODE>(c, ulo + (double)i * sx, &e));
-    acc += 0.5 * p1;
-    return sx * acc - sx * sx / 12.0 * (bb_lt_d1<MODE>(c, x) * p1 - bb_lt_d1<MODE>(c, lo) * p0);
-}
+struct LtMix : GridRows {
+    typedef LtCond Cond;
+    static constexpr int NX = 2;          // tau_mean, pool_mean; n_two_modes
+    static constexpr bool L_KEPT = false;
+    const PpcArgs& P;
+    long long own;
+    double a, ib2;            // logtau's prior
+    int nterms;
+    const double *c0j, *c1j;
+    double* loj;
 
-BB_DEV void bb_lt_cond(LtCond& c, int nterms, double a, double ib2, double c0, double c1, double nw) {
-    c.a = a; c.ib2 = ib2; c.prior = nterms == 0;
-    c.c0 = c0; c.c1 = c1; c.nw = nw;
-}
+    BB_MEM LtMix(const PpcArgs& P_, long long own_, double a_, double ib2_, int nterms_, double* tab) : P(P_), own(own_), a(a_), ib2(ib2_), nterms(nterms_) {
+        const long long ns = P.n_samples;
+        c0j = tab; c1j = tab + ns;
+        l = tab + 2 * ns; E = tab + 3 * ns; V = tab + 4 * ns; x0 = tab + 5 * ns; x1 = tab + 6 * ns;
+        loj = tab + 7 * ns; hi = tab + 8 * ns; two = tab + 9 * ns;
+    }
+    BB_MEM void cond(LtCond& c, int j, double nw) const {
+        c.a = a; c.ib2 = ib2; c.prior = nterms == 0;
+        c.c0 = c0j[j]; c.c1 = c1j[j]; c.nw = nw;
+    }
+    BB_MEM double setup(int j, LtCond& c, double* w, int* nleft, int* nright, bool* kept2) const {
+        cond(c, j, nterms > 0 ? x1[j] : 0.0);
+        const double s = bb_lt_setup<MODE>(c, nleft, nright, kept2);
+        *w = s;
+        return s;
+    }
+    BB_MEM double p(const LtCond& c, double u, double* e2) const { return exp(bb_lt_lnp<MODE>(c, u, e2)); }
+    BB_MEM void extras(const LtCond& c, double p, double u, double e2, double* se, double* sp) const {
+        *se += p * exp(u);
+        *sp += p * (c.prior ? 1.0 : 1.0 / (1.0 + c.nws * e2));
+    }
+    BB_MEM double finish0(const LtCond& c, double z, double se) const { return exp(c.lm) * (se / z); }
+    BB_MEM double finish1(const LtCond&, double z, double sp) const { return sp / z; }
+    BB_MEM double mode(const LtCond& c) const { return c.lm; }
+    BB_MEM double latent(int j) const { return bb_ppc_param(P, own, j); }
+    BB_MEM void keep(int j, const LtCond&, double lm, double s, int nleft) const { loj[j] = lm - (double)nleft * s; }
+    BB_MEM double lo(int j, double, double) const { return loj[j]; }
+    BB_MEM void reopen(int j, LtCond& c, double lm) const {
+        cond(c, j, 0.0);      // (n w: the pooling factor's alone)
+        bb_lt_anchor<MODE>(c, lm);
+    }
+    // (h' takes the absolute point)
+    BB_MEM double cdf_z(const LtCond& c, double s, double lo, double x) const {
+        return bb_grid_cdf_z(x - lo, s, lo - c.lm, x - c.lm, [&](double u, double* e2) { return exp(bb_lt_lnp<MODE>(c, u, e2)); },
+                             [&](bool upper, double) { return bb_lt_d1<MODE>(c, upper ? x : lo); });
+    }
+};
 
 template <int MODE>
 BB_DEV void bb_block_lt(BBCtx& cx, const LtArgs& L, int nblocks) {
     const RbArgs& A = L.A;
     const FreqArgs& F = A.F;
     const PpcArgs& P = F.P;
-    const int ns = P.n_samples, E = P.E, nq = A.nq;
-    const long long n_units = A.n_units;
+    const int ns = P.n_samples, E = P.E;
     double* tab = A.ytab + (long long)cx.block * BB_LT_TAB * ns;
-    double* ms = cx.lds;
-    double* ssj = cx.lds + ns;
-    double* zz = cx.lds + 2 * (long long)ns;
-    double* red = cx.lds + 3 * (long long)ns;
-    double* st = red + 3 * BB_SCORE_NT;
     double* c0j = tab;
     double* c1j = tab + ns;
-    double* lj = tab + 2 * (long long)ns;
-    double* ej = tab + 3 * (long long)ns;
-    double* vj = tab + 4 * (long long)ns;
-    double* tj = tab + 5 * (long long)ns;
     double* pj = tab + 6 * (long long)ns;
-    double* loj = tab + 7 * (long long)ns;
-    double* hij = tab + 8 * (long long)ns;
-    double* twoj = tab + 9 * (long long)ns;
     const bool menv = P.kind == 4;
-    const double a = P.pri_mean, ib2 = P.pri_ivar;
     for (long long row = cx.block; row < P.n_rows; row += nblocks) {
         const int r = (int)(row / P.nb);
         const long long m = row % P.nb;
@@ -342,145 +306,7 @@ BB_DEV void bb_block_lt(BBCtx& cx, const LtArgs& L, int nblocks) {
                     c1j[j] = c1;
                 }
             }
-            // sweep A: modes, grid and per-draw moments; first sums
-            BB_PASS(cx, tid) {
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    LtCond c;
-                    bb_lt_cond(c, nu, a, ib2, c0j[j], c1j[j], nu > 0 ? pj[j] : 0.0);
-                    int nleft = 0, nright = 0;
-                    bool two = false;
-                    const double s = bb_lt_setup<MODE>(c, &nleft, &nright, &two);
-                    const int nodes = nleft + nright;
-                    double z = 0.0, m1 = 0.0, m2 = 0.0, se = 0.0, sp = 0.0;
-                    for (int k = 0; k <= nodes; ++k) {
-                        const double uk = (double)(k - nleft) * s;
-                        double e2;
-                        double p = exp(bb_lt_lnp<MODE>(c, uk, &e2));
-                        if (k == 0 || k == nodes) p *= 0.5;
-                        z += p;
-                        m1 += p * uk;
-                        m2 += p * (uk * uk);
-                        se += p * exp(uk);
-                        sp += p * (c.prior ? 1.0 : 1.0 / (1.0 + c.nws * e2));
-                    }
-                    const double Zj = s * z, r1 = m1 / z, Ej = c.lm + r1, Vj = m2 / z - r1 * r1, Tj = exp(c.lm) * (se / z), Pj = sp / z;
-                    const double l = bb_ppc_param(P, P.lo_lt + ent, j);
-                    ms[j] = c.lm; ssj[j] = s; zz[j] = Zj;
-                    lj[j] = l; ej[j] = Ej; vj[j] = Vj; tj[j] = Tj; pj[j] = Pj;
-                    loj[j] = c.lm - (double)nleft * s; hij[j] = c.lm + (double)nright * s; twoj[j] = two ? 1.0 : 0.0;
-                    a0 += l;
-                    a1 += Ej;
-                    a2 += Vj;
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = a2;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st, false);
-            // sweep A': the other first sums
-            BB_PASS(cx, tid) {
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    a0 += tj[j];
-                    a1 += pj[j];
-                    a2 += ms[j];
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = a2;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st + 3, false);
-            // sweep A'': the draws with two modes; the largest hi_j (NaN where Z_j is not finite)
-            BB_PASS(cx, tid) {
-                double a0 = 0.0, mx = -INFINITY;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    a0 += twoj[j];
-                    mx = bb_score_max(mx, isfinite(zz[j]) ? hij[j] : (double)NAN);
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = 0.0; red[2 * BB_SCORE_NT + tid] = mx;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st + 6, true);
-            // sweep B: centred second moments; the smallest lo_j (as the largest of -lo_j)
-            BB_PASS(cx, tid) {
-                const double qm = st[0] / ns, rm = st[1] / ns;
-                double a0 = 0.0, a1 = 0.0, mx = -INFINITY;
-                for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                    const double d0 = lj[j] - qm, d1 = ej[j] - rm;
-                    a0 += d0 * d0;
-                    a1 += d1 * d1;
-                    mx = bb_score_max(mx, -loj[j]);
-                }
-                red[tid] = a0; red[BB_SCORE_NT + tid] = a1; red[2 * BB_SCORE_NT + tid] = mx;
-            }
-            BB_SYNC(cx);
-            bb_score_reduce(cx, red, st + 9, true);
-            BB_PASS(cx, tid) {
-                if (tid == 0) {
-                    A.unit[0 * n_units + ent] = st[0] / ns;
-                    A.unit[1 * n_units + ent] = sqrt(st[9] / ns);
-                    A.unit[2 * n_units + ent] = st[1] / ns;
-                    A.unit[3 * n_units + ent] = sqrt(st[2] / ns + st[10] / ns);
-                    A.unit[4 * n_units + ent] = st[3] / ns;
-                    A.unit[5 * n_units + ent] = st[4] / ns;
-                    A.unit[6 * n_units + ent] = st[5] / ns;
-                    A.unit[7 * n_units + ent] = st[6];
-                    const double lo = -st[11], hi = st[8];
-                    st[15] = (nq > 0 && isfinite(lo) && isfinite(hi)) ? 1.0 : 0.0;
-                    for (int i = 0; i < nq; ++i) { st[16 + i] = lo; st[24 + i] = hi; }
-                }
-            }
-            BB_SYNC(cx);
-            if (nq > 0 && st[15] == 0.0) {   // a non-finite l*_j, s_j or Z_j: no bracket
-                BB_PASS(cx, tid) { if (tid < nq) A.quant[ent * BB_RB_MAX_Q + tid] = NAN; }
-            } else if (nq > 0) {
-                for (int it = 0; it < BB_LT_ITER; ++it) {
-                    for (int q0 = 0; q0 < nq; q0 += 3) {
-                        // sweep Q: the mixture CDF at the midpoints of up to three brackets
-                        BB_PASS(cx, tid) {
-                            const int nx = nq - q0 < 3 ? nq - q0 : 3;
-                            double acc[3] = {0.0, 0.0, 0.0}, xs[3];
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) {
-                                const int qi = i < nx ? q0 + i : q0;
-                                xs[i] = st[16 + qi] + (st[24 + qi] - st[16 + qi]) / 2.0;
-                            }
-                            for (int j = tid; j < ns; j += BB_SCORE_NT) {
-                                LtCond c;
-                                const double lo = loj[j], hi = hij[j];
-                                bool have = false;
-#pragma unroll
-                                for (int i = 0; i < 3; ++i) {
-                                    if (i >= nx) continue;
-                                    const double x = xs[i];
-                                    if (x <= lo) continue;                       // C_j = 0
-                                    if (x >= hi) { acc[i] += 1.0; continue; }    // C_j = 1
-                                    if (!have) {
-                                        bb_lt_cond(c, nu, a, ib2, c0j[j], c1j[j], 0.0);      // (n w: the pooling factor's alone)
-                                        bb_lt_anchor<MODE>(c, ms[j]);
-                                        have = true;
-                                    }
-                                    const double C = bb_lt_cdf_z<MODE>(c, ssj[j], lo, x) / zz[j];
-                                    acc[i] += C < 0.0 ? 0.0 : (C > 1.0 ? 1.0 : C);
-                                }
-                            }
-                            red[tid] = acc[0]; red[BB_SCORE_NT + tid] = acc[1]; red[2 * BB_SCORE_NT + tid] = acc[2];
-                        }
-                        BB_SYNC(cx);
-                        bb_score_reduce(cx, red, st + 12, false);
-                        BB_PASS(cx, tid) {
-                            if (tid < 3 && q0 + tid < nq) {
-                                const int i = q0 + tid;
-                                const double x = st[16 + i] + (st[24 + i] - st[16 + i]) / 2.0;
-                                if (st[12 + tid] / ns < A.probs[i]) st[16 + i] = x;
-                                else st[24 + i] = x;
-                            }
-                        }
-                        BB_SYNC(cx);
-                    }
-                }
-                BB_PASS(cx, tid) { if (tid < nq) A.quant[ent * BB_RB_MAX_Q + tid] = st[16 + tid] + (st[24 + tid] - st[16 + tid]) / 2.0; }
-            }
-            BB_SYNC(cx);
+            bb_grid_mixture(cx, ns, A.nq, A.probs, cx.lds, A.unit, A.n_units, ent, A.quant, LtMix<MODE>(P, P.lo_lt + ent, P.pri_mean, P.pri_ivar, nu, tab));
         }
     }
 }
