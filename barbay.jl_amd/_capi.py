@@ -45,7 +45,7 @@ EXPORTS = [
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
-    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
+    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
     "bb_logsigma_rb_shape", "bb_logsigma_rb", "bb_logtau_rb_shape", "bb_logtau_rb",
     "bb_loglambda_rb_shape", "bb_loglambda_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
@@ -142,6 +142,19 @@ class bb_rb_out(C.Structure):
 
 class bb_theta_rb_out(C.Structure):
     _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("n_members", C.POINTER(C.c_int32)), ("n_steps", C.POINTER(C.c_int32))]
+
+
+BB_CONTRAST_SPACES = {"fitness": 0, "theta": 1}
+
+
+class bb_contrast_opts(C.Structure):
+    _fields_ = [("space", C.c_int32), ("n_samples", C.c_int32), ("n_quantiles", C.c_int32), ("reserved0", C.c_int32), ("probs", _dp),
+                ("threshold", C.c_double), ("seed", C.c_uint64), ("draws", _dp), ("n_contrasts", C.c_int64),
+                ("term_ptr", C.POINTER(C.c_int64)), ("term_idx", C.POINTER(C.c_int64)), ("term_w", _dp)]
+
+
+class bb_contrast_out(C.Structure):
+    _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("min_steps", C.POINTER(C.c_int32))]
 
 
 class bb_popmean_rb_out(C.Structure):
@@ -293,6 +306,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_theta_rb"):
         lib.bb_theta_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_theta_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_theta_rb_out)]
+    if hasattr(lib, "bb_contrast_rb"):
+        lib.bb_contrast_rb.argtypes = [vp, C.POINTER(bb_contrast_opts), C.POINTER(bb_contrast_out)]
     if hasattr(lib, "bb_popmean_rb"):
         lib.bb_popmean_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_popmean_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_popmean_rb_out)]
@@ -697,10 +712,10 @@ class Engine:
         self._check(self._lib.bb_fitness_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
-    def _rb_opts(self, n_samples, probs, threshold, seed, draws):
+    def _rb_opts(self, n_samples, probs, threshold, seed, draws, opts=bb_rb_opts):
         """(bb_rb_opts, probs, draws): the arrays the options point into must outlive the call."""
         p = _f64(np.atleast_1d(probs)).reshape(-1)
-        o = bb_rb_opts()
+        o = opts()
         o.n_samples, o.n_quantiles, o.threshold, o.seed = int(n_samples), int(p.shape[0]), float(threshold), int(seed)
         o.probs = _ptr(p) if p.shape[0] else None
         x = None
@@ -740,6 +755,44 @@ class Engine:
         out.n_steps = res["n_steps"].ctypes.data_as(C.POINTER(C.c_int32))
         out.n_members = res["n_members"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_theta_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def contrast_rb(self, terms, space: str = "fitness", n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975),
+                    threshold: float = 0.0, seed: int = 0, draws=None) -> Dict[str, np.ndarray]:
+        """Rao-Blackwellised marginal of linear contrasts sum_k w_k x_k of distinct fitness units (`space="fitness"`, the units of
+        `fitness_rb`) or distinct hyper-fitnesses (`space="theta"`, the groups of `theta_rb`) (`bb_contrast_rb`): the contrast's exact
+        Gaussian conditional N(sum w m, sqrt(sum w^2 sd^2)) averaged over the draws of `fitness_rb` (same arguments), so that what
+        the terms share -- the population mean fitness above all -- cancels or adds up draw by draw.  `terms`: a sequence of
+        contrasts, each a sequence of (index, weight), or a CSR triple (ptr, idx, w).  Returns what `fitness_rb` returns, per
+        contrast, with min_steps (int32, the smallest n_steps over the contrast's terms) in place of n_steps."""
+        if space not in BB_CONTRAST_SPACES:
+            raise BarBayHipError(f"space must be one of {sorted(BB_CONTRAST_SPACES)}")
+        if isinstance(terms, tuple) and len(terms) == 3 and np.ndim(terms[0]) == 1 and len(terms[0]) > 0:
+            ptr, idx, w = terms                       # (a contrast is a sequence of pairs: two-dimensional, or empty)
+        else:
+            terms = [list(c) for c in terms]
+            ptr = np.cumsum([0] + [len(c) for c in terms])
+            idx = [k for c in terms for k, _ in c]
+            w = [x for c in terms for _, x in c]
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        w = _f64(np.asarray(w, dtype=np.float64)).reshape(-1)
+        if ptr.shape[0] < 1 or idx.shape[0] != w.shape[0] or (ptr.shape[0] > 1 and ptr[-1] != idx.shape[0]):
+            raise BarBayHipError("terms: ptr must have n_contrasts + 1 entries ending at the number of terms, idx and w that many entries")
+        n = ptr.shape[0] - 1
+        o, p, _x = self._rb_opts(n_samples, probs, threshold, seed, draws, opts=bb_contrast_opts)
+        o.space, o.n_contrasts = BB_CONTRAST_SPACES[space], n
+        i64 = C.POINTER(C.c_int64)
+        o.term_ptr, o.term_idx, o.term_w = ptr.ctypes.data_as(i64), idx.ctypes.data_as(i64), _ptr(w)
+        res = {k: np.empty(n) for k in RB_UNITS}
+        res["quantiles"] = np.empty((n, p.shape[0]))
+        res["min_steps"] = np.empty(n, dtype=np.int32)
+        out = bb_contrast_out()
+        for k in RB_UNITS:
+            setattr(out, k, _ptr(res[k]))
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
+        out.min_steps = res["min_steps"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_contrast_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def popmean_rb_shape(self) -> int:

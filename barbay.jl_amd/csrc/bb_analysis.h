@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
 // bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
-// bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
+// bb_contrast_rb (bb_contrast.h), bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -723,21 +723,27 @@ extern "C" int bb_theta_rb_shape(const bb_handle* h, int64_t* n_groups) {
 struct ThetaMap {
     std::vector<int> grp_c0, grp_nst, grp_nmem, chk_grp, chk_m0, mem_row, mem_nu;
 };
+// nu[r E + e] = n_u of (replicate, environment): the replicate's steps whose later time point lies in e
+static int env_steps(bb_handle* dh, int E, std::vector<int>& nu) {
+    const DevModel& M = dh->M;
+    std::vector<int> env;
+    if (E > 1) {
+        env.resize((size_t)M.Ttot);
+        if (int rc = d2h(env.data(), M.env_idx, (size_t)M.Ttot * 4, dh->stream)) return rc;
+    }
+    nu.assign((size_t)M.R * E, 0);
+    for (int r = 0; r < M.R; ++r)
+        for (int t = 0; t + 1 < M.T[r]; ++t) nu[(size_t)r * E + (E > 1 ? env[(size_t)(M.tcum[r] + t + 1)] : 0)]++;
+    return BB_OK;
+}
 static int theta_map(const bb_handle* h, BandsCall& B, int E, ThetaMap& tm) {
     bb_handle* dh = B.dh;
     const DevModel& M = dh->M;
     const long long G = theta_groups(h), nb = M.nb;
     const bool geno = M.kind == BB_MODEL_GENOTYPE;
     int rc;
-    // n_u of (replicate, environment)
-    std::vector<int> env;
-    if (E > 1) {
-        env.resize((size_t)M.Ttot);
-        if ((rc = d2h(env.data(), M.env_idx, (size_t)M.Ttot * 4, dh->stream))) return rc;
-    }
-    std::vector<int> nu((size_t)M.R * E, 0);
-    for (int r = 0; r < M.R; ++r)
-        for (int t = 0; t + 1 < M.T[r]; ++t) nu[(size_t)r * E + (E > 1 ? env[(size_t)(M.tcum[r] + t + 1)] : 0)]++;
+    std::vector<int> nu;
+    if ((rc = env_steps(dh, E, nu))) return rc;
     // members: first member of every group, then the rows
     std::vector<long long> m0((size_t)G + 1, 0);
     if (geno) {
@@ -868,6 +874,128 @@ extern "C" int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_
 #ifdef BB_RB_TIMES
     fprintf(stderr, "[bb_theta_rb %lld groups, %zu members, %zu chunks, %d samples, %d quantiles] map+upload %.3f ms, pop %.3f ms, normalisers %.3f ms, part %.3f ms, theta %.3f ms, download %.3f ms\n", n_groups, nmem, nchk, ns, nq, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5]);
 #endif
+    return BB_OK;
+}
+
+// ---- Rao-Blackwellised fitness contrasts (bb_contrast.h) ------------------------------------------------------------------------------
+// The terms checked: a well-formed CSR, every contrast with terms, every index inside the space and named once per contrast, every
+// weight finite.  *n_terms = term_ptr[n_contrasts].
+static int contrast_check(const bb_contrast_opts* o, long long n_space, const char* what, long long* n_terms) {
+    const long long nc = o->n_contrasts;
+    if (!o->term_ptr || !o->term_idx || !o->term_w) return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: term_ptr, term_idx and term_w must not be null");
+    if (o->term_ptr[0] != 0) return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: term_ptr[0] = %lld, must be 0", (long long)o->term_ptr[0]);
+    if (nc > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_contrast_rb: more than 2^31 - 1 terms");
+    for (long long c = 0; c < nc; ++c) {
+        if (o->term_ptr[c + 1] < o->term_ptr[c])
+            return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: contrast %lld: term_ptr decreases (%lld after %lld)", c, (long long)o->term_ptr[c + 1], (long long)o->term_ptr[c]);
+        if (o->term_ptr[c + 1] == o->term_ptr[c]) return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: contrast %lld has no terms", c);
+    }
+    if (o->term_ptr[nc] > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_contrast_rb: %lld terms, more than 2^31 - 1", (long long)o->term_ptr[nc]);
+    std::vector<long long> seen;
+    for (long long c = 0; c < nc; ++c) {
+        const long long k0 = o->term_ptr[c], k1 = o->term_ptr[c + 1];
+        for (long long k = k0; k < k1; ++k) {
+            if (o->term_idx[k] < 0 || o->term_idx[k] >= n_space)
+                return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: contrast %lld, term %lld: %s %lld outside 0..%lld", c, k - k0, what, (long long)o->term_idx[k], n_space - 1);
+            if (!std::isfinite(o->term_w[k])) return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: contrast %lld, term %lld: the weight is not finite", c, k - k0);
+        }
+        seen.assign(o->term_idx + k0, o->term_idx + k1);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) {
+            long long k = k1 - 1;                      // the later of the two terms that name it
+            while (o->term_idx[k] != *dup) --k;
+            return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: contrast %lld, term %lld: %s %lld is named twice", c, k - k0, what, *dup);
+        }
+    }
+    *n_terms = o->term_ptr[nc];
+    return BB_OK;
+}
+
+extern "C" int bb_contrast_rb(bb_handle* h, const bb_contrast_opts* o, const bb_contrast_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples;
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_RB_MAX_SAMPLES, &o->threshold)) return rc;
+    if (o->space != BB_CONTRAST_FITNESS && o->space != BB_CONTRAST_THETA)
+        return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: unknown space %d", (int)o->space);
+    const bool theta = o->space == BB_CONTRAST_THETA;
+    if (theta && h->M.kind < BB_MODEL_GENOTYPE)
+        return bb_fail(BB_ERR_UNSUPPORTED, "bb_contrast_rb: BB_CONTRAST_THETA applies to the hierarchical models only: model kind %d (%s) has no theta",
+                       (int)h->M.kind, h->M.kind == BB_MODEL_FITNESS ? "BB_MODEL_FITNESS" : "BB_MODEL_MULTIENV");
+    if (o->n_contrasts < 0) return bb_fail(BB_ERR_INVALID, "bb_contrast_rb: n_contrasts = %lld", (long long)o->n_contrasts);
+    if (o->n_contrasts == 0) return BB_OK;
+    long long n_terms = 0;
+    if (int rc = contrast_check(o, theta ? theta_groups(h) : rb_units(h), theta ? "group" : "unit", &n_terms)) return rc;
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    ContrastArgs C;
+    memset(&C, 0, sizeof C);
+    RbArgs& A = C.H.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    int zb;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, o->n_contrasts, &zb);
+    if (rc) return rc;
+    if (theta || M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {      // the s_bc prior, as bb_theta_rb / bb_fitness_rb set it
+        const DevPrior& dp = M.pri[BK_S];
+        P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    }
+    A.threshold = o->threshold;
+    C.space = o->space;
+    // min_steps, and for THETA the chunk map
+    const size_t ncz = (size_t)o->n_contrasts, ntz = (size_t)n_terms;
+    std::vector<int> elem_steps;                       // n_u of every unit, or the groups' n_steps
+    ThetaMap tm;
+    if (theta) {
+        if ((rc = theta_map(h, B, P.E, tm))) return rc;
+        elem_steps = tm.grp_nst;
+    } else {
+        std::vector<int> nu;
+        if ((rc = env_steps(dh, P.E, nu))) return rc;
+        const long long n_units = rb_units(h), per = (long long)P.E * M.nb;
+        elem_steps.resize((size_t)n_units);
+        for (long long u = 0; u < n_units; ++u) elem_steps[(size_t)u] = nu[(size_t)(u / per) * P.E + (size_t)(u % P.E)];
+    }
+    std::vector<int> hm;                               // term_ptr | term_idx | the chunk map
+    hm.reserve(ncz + 1 + ntz);
+    for (size_t c = 0; c <= ncz; ++c) hm.push_back((int)o->term_ptr[c]);
+    for (size_t k = 0; k < ntz; ++k) hm.push_back((int)o->term_idx[k]);
+    const std::vector<int>* maps[5] = {&tm.grp_c0, &tm.grp_nst, &tm.chk_m0, &tm.mem_row, &tm.mem_nu};
+    size_t at[5];
+    for (int i = 0; i < 5; ++i) { at[i] = hm.size(); hm.insert(hm.end(), maps[i]->begin(), maps[i]->end()); }
+    const size_t nsz = (size_t)ns, D = (size_t)h->M.D, nmap = hm.size();
+    const int nblk = (int)std::max<long long>(1, std::min<long long>(o->n_contrasts, B.nblk));      // (P.par holds a [nblk][ns] table of d_j)
+    double* ddraws = nullptr;
+    double* dw = nullptr;
+    int* dmap = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(A.unit, BB_RB_OUT * ncz);                    // [6][n_contrasts]
+        c(A.quant, BB_RB_MAX_Q * ncz);                 // [n_contrasts][8]
+        c(dw, ntz);                                    // [n_terms] weights
+        c(dmap, (nmap + 1) / 2);                       // the CSR arrays and the chunk map: ints
+        c(ddraws, o->draws ? nsz * D : 0);             // [ns][D]
+    });
+    if (rc) return rc;
+    A.ytab = P.par;
+    C.term_ptr = dmap;
+    C.term_idx = dmap + ncz + 1;
+    C.term_w = dw;
+    if (theta) { C.H.grp_c0 = dmap + at[0]; C.H.grp_nst = dmap + at[1]; C.H.chk_m0 = dmap + at[2]; C.H.mem_row = dmap + at[3]; C.H.mem_nu = dmap + at[4]; }
+    if ((rc = h2d(dmap, hm.data(), nmap * 4, dh->stream)) || (rc = h2d(dw, o->term_w, ntz * 8, dh->stream))) return rc;
+    if ((rc = rb_draws(dh, P, ddraws, o->draws, nsz, D))) return rc;
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    if ((rc = rb_front(dh, B, A, zb, false))) return rc;
+    if ((rc = launch(dh->stream, k_rb_contrast, nblk, BB_SCORE_NT, (size_t)BB_RB_LDS_DOUBLES(ns), C))) return rc;
+    double* units[BB_RB_OUT] = {out->q_mean, out->q_sd, out->rb_mean, out->rb_sd, out->p_pos, out->p_neg};
+    if ((rc = rb_download(dh, A, ncz, units, BB_RB_OUT, out->quantiles, nullptr))) return rc;
+    for (size_t c = 0; out->min_steps && c < ncz; ++c) {
+        int lo = elem_steps[(size_t)o->term_idx[o->term_ptr[c]]];
+        for (long long k = o->term_ptr[c] + 1; k < o->term_ptr[c + 1]; ++k) lo = std::min(lo, elem_steps[(size_t)o->term_idx[k]]);
+        out->min_steps[c] = lo;
+    }
     return BB_OK;
 }
 

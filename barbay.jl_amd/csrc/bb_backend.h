@@ -433,6 +433,10 @@ BB_KERNEL(BB_SCORE_NT, k_rb_pop, PopArgs H) {
     BB_CTX;
     bb_block_pop(cx, H, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_rb_contrast, ContrastArgs C) {
+    BB_CTX;
+    bb_block_contrast(cx, C, BB_GRID);
+}
 BB_KERNEL(BB_SCORE_NT, k_ls_bc, LsArgs L) {
     BB_CTX;
     bb_block_ls_bc(cx, L, BB_GRID);

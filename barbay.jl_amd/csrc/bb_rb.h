@@ -28,8 +28,8 @@
 // Entry point bb_theta_rb: the same for the hyper-fitness theta_g of the hierarchical kinds, whose conditional sums over the members
 // of a group g (a genotype's mutants; a mutant's replicates).  After the phases above, in place of bb_block_rb:
 //   bb_block_theta_part : one workgroup of BB_SCORE_NT threads per chunk of BB_THETA_CHUNK consecutive members of a group,
-//        chunk += nblocks.  Per draw it walks the chunk's members in order; a member's loglambda row once (pass Y's body, the steps of
-//        the group's environment only, y in a register), cP = n_u w, cN = w (y - n_u (tau theta_tilde)); a member with n_u = 0 is
+//        chunk += nblocks.  Per draw it walks the chunk's members in order; a member's loglambda row once (bb_rb_member_y: pass Y's body, the
+//        steps of the group's environment only, y in a register), cP = n_u w, cN = w (y - n_u (tau theta_tilde)); a member with n_u = 0 is
 //        skipped.  The chunk's (SP, SN), from 0.0, go to the partial table part[chunk][2][n_samples].
 //   bb_block_theta      : one workgroup per group, g += nblocks.  Per draw the group's chunk partials from 0.0 in chunk order, the
 //        prior (a, 1 / b^2) added, theta_j, m_j, sd_j written where bb_block_rb writes them; then bb_rb_mixture.
@@ -297,6 +297,28 @@ BB_DEV void bb_block_rb(BBCtx& cx, const RbArgs& A, int nblocks) {
     }
 }
 
+// y_j of mutant row (r, m) in environment e, and in nu the steps summed: one walk over the row's loglambda draws (pass Y's body for
+// one environment, y in a register), ascending t, the later time point's environment.  Shared with bb_contrast.h.
+BB_DEV double bb_rb_member_y(const FreqArgs& F, int r, long long m, int e, bool menv, int j, int& nu) {
+    const PpcArgs& P = F.P;
+    const int ns = P.n_samples, T = P.T[r];
+    const long long ll = F.off_l[r] + (F.nn + m) * T;
+    const double* Z = F.Z + (long long)P.tcum[r] * ns;      // ln Z (bb_block_rb_logz)
+    const double* sbar = P.pop + (long long)(2 * P.off_t[r]) * ns;
+    double y = 0.0, l0 = bb_ppc_param(P, ll, j), z0 = Z[j];
+    nu = 0;
+    for (int t = 0; t + 1 < T; ++t) {
+        const double l1 = bb_ppc_param(P, ll + t + 1, j), z1 = Z[(long long)(t + 1) * ns + j];
+        if (!menv || P.env_idx[P.tcum[r] + t + 1] == e) {
+            y += ((l1 - l0) - (z1 - z0)) + sbar[(long long)(2 * t) * ns + j];
+            ++nu;
+        }
+        l0 = l1;
+        z0 = z1;
+    }
+    return y;
+}
+
 BB_DEV void bb_block_theta_part(BBCtx& cx, const ThetaArgs& H, int nblocks) {
     const FreqArgs& F = H.A.F;
     const PpcArgs& P = F.P;
@@ -312,18 +334,10 @@ BB_DEV void bb_block_theta_part(BBCtx& cx, const ThetaArgs& H, int nblocks) {
                     const long long row = H.mem_row[x];
                     const int r = (int)(row / P.nb);
                     const long long m = row % P.nb;
-                    const int T = P.T[r], nu = H.mem_nu[x];
+                    const int nu = H.mem_nu[x];
                     if (nu == 0) continue;       // the log-joint has no term for the member
-                    const long long ll = F.off_l[r] + (F.nn + m) * T;
-                    const double* Z = F.Z + (long long)P.tcum[r] * ns;      // ln Z (bb_block_rb_logz)
-                    const double* sbar = P.pop + (long long)(2 * P.off_t[r]) * ns;
-                    double y = 0.0, l0 = bb_ppc_param(P, ll, j), z0 = Z[j];
-                    for (int t = 0; t + 1 < T; ++t) {
-                        const double l1 = bb_ppc_param(P, ll + t + 1, j), z1 = Z[(long long)(t + 1) * ns + j];
-                        if (!menv || P.env_idx[P.tcum[r] + t + 1] == e) y += ((l1 - l0) - (z1 - z0)) + sbar[(long long)(2 * t) * ns + j];
-                        l0 = l1;
-                        z0 = z1;
-                    }
+                    int walked;                  // (== nu)
+                    const double y = bb_rb_member_y(F, r, m, e, menv, j, walked);
                     const long long uu = P.kind == 2 ? m : e + (long long)E * m + (long long)E * P.nb * r;
                     const double w = exp(-2.0 * bb_ppc_param(P, P.lo_ls + uu, j));
                     const double tau = exp(bb_ppc_param(P, P.lo_lt + uu, j)), tt = bb_ppc_param(P, P.lo_tt + uu, j);

@@ -24,6 +24,8 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
     hyperfitness_marginals                                        the same for the hyper-fitness theta of the hierarchical models -- a
                                                                   genotype's fitness, a mutant's across its replicates -- whose
                                                                   conditional sums over the group's members (`bb_theta_rb`)
+    fitness_contrasts                                             differences and other linear contrasts of fitnesses or hyper-fitnesses
+                                                                  from the joint draws (`bb_contrast_rb`): what the terms share cancels
     popmean_marginals                                             the same for the population mean fitness of every time step, whose
                                                                   conditional sums over every barcode of the replicate (`bb_popmean_rb`)
     noise_marginals                                               the same for the noise scales logsigma of the mutants and of the time
@@ -33,6 +35,7 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
 """
 from __future__ import annotations
 
+import math
 from contextlib import contextmanager
 from typing import Dict, List, Optional, Sequence
 
@@ -518,6 +521,127 @@ def hyperfitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, 
     for i, p in enumerate(probs):
         out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
     return pd.DataFrame(out)
+
+
+def _contrast_pairs(labels: List, between: str, reference) -> List[Dict]:
+    """The contrasts `between` names over the element labels (tuples; the genotype model's hyper level: plain labels)."""
+    from itertools import combinations
+    axis = {"id": 0, "rep": 1, "env": -1, "genotype": None}[between]
+    if axis is None:                                                  # every other genotype minus the reference
+        if reference not in labels:
+            raise BarBayError(f"reference {reference!r} is no genotype of the data")
+        return [{x: 1.0, reference: -1.0} for x in labels if x != reference]
+    cells: Dict = {}                                                  # the other coordinates -> the labels that differ in `axis` only
+    for x in labels:
+        cells.setdefault(x[:axis] + x[axis + 1:] if axis >= 0 else x[:-1], []).append(x)
+    out = []
+    if between == "id":
+        if not any(x[0] == reference for x in labels):
+            raise BarBayError(f"reference {reference!r} is no mutant of the data")
+        for group in cells.values():
+            ref = [x for x in group if x[0] == reference]
+            out += [{x: 1.0, ref[0]: -1.0} for x in group if ref and x[0] != reference]
+    else:
+        for group in cells.values():
+            out += [{b: 1.0, a: -1.0} for a, b in combinations(group, 2)]      # later label minus earlier
+    return out
+
+
+def fitness_contrasts(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, level: str = "fitness", contrasts: Optional[Sequence[Dict]] = None,
+                      between: Optional[str] = None, reference=None, model_kwargs: Optional[Dict] = None,
+                      n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
+                      id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                      rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                      device: int = 0, chain=None) -> pd.DataFrame:
+    """Differences (and any other linear contrasts) of fitnesses with an honest +-: is a mutant fitter in environment B than in A,
+    fitter than the wild type, do two replicates agree?  The difference of two `fitness_marginals` rows with their variances added
+    is wrong: every fitness of a replicate is measured against the same population mean fitness, whose uncertainty each marginal
+    carries and which cancels in a difference of two mutants of one replicate (and adds up in a sum).  Distinct fitnesses are
+    conditionally independent given everything else, so the contrast's full conditional is exactly Gaussian, and averaging it over
+    the joint draws gives its Rao-Blackwellised marginal (`bb_contrast_rb`, one device call).
+
+    level "fitness": the elements are the rows of `fitness_marginals`, labelled (id, rep, env) (env None without environments);
+    level "hyper": those of `hyperfitness_marginals`, labelled genotype (genotype model) or (id, env).  One call serves one level: a
+    fitness and the hyper-fitness of its own group are not conditionally independent.
+
+    Give either `contrasts`, a list of dicts {label: weight} (every label at most once per contrast), or `between`:
+    "env" -- for every (id, rep) (hyper: every id) every pair of environments, later label minus earlier; "rep" -- for every
+    (id, env) every pair of replicates; "id" with `reference` -- every other mutant minus the reference mutant within each
+    (rep, env); "genotype" with `reference` (level "hyper", genotype model) -- every other genotype minus the reference genotype.
+    The remaining arguments as for `fitness_marginals`.  At the hyper level a term re-walks its whole group for every contrast that
+    names it: every genotype against a reference is cheap, all pairs of a thousand genotypes are not.
+
+    Returns one line per contrast: `contrast` (its number), `terms` ("+1 (id, rep, env) -1 (...)"), `n_terms`, `min_steps` (the
+    smallest n_steps over the terms; 0: some term's conditional is its prior), `q_mean`, `q_sd` (the draws' own contrast),
+    `rb_mean`, `rb_sd`, `sd_ratio` = rb_sd / q_sd, `indep_sd` = sqrt(sum w^2 rb_sd_k^2) from the terms' own marginals at the same
+    seed (what adding variances would give), `common_mode` = rb_sd / indep_sd (below 1: shared uncertainty cancels; above: it adds
+    up), `p_pos`, `p_neg` (the RB probability of a contrast above / below `threshold`) and the quantile columns of
+    `fitness_marginals`."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    if level not in ("fitness", "hyper"):
+        raise BarBayError('level must be "fitness" or "hyper"')
+    if (contrasts is None) == (between is None):
+        raise BarBayError("give exactly one of contrasts= and between=")
+    if between is not None and between not in ("env", "rep", "id", "genotype"):
+        raise BarBayError('between must be "env", "rep", "id" or "genotype"')
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        R, nb = len(bayes_model.counts), bayes_model.n_bc
+        has_env, envs = _env_labels(arrays, mname, R)
+        E = max(len(envs), 1) if has_env else 1
+        env_of = lambda x: envs[x] if has_env else None
+        ids = list(arrays.bc_ids)
+        geno = "genotype" in mname
+        if level == "fitness":
+            labels = [(ids[m], f"R{r + 1}", env_of(x)) for r in range(R) for m in range(nb) for x in range(E)]
+        elif e.theta_rb_shape() == 0:
+            raise BarBayError(f'{mname} has no hyper-fitness: level="hyper" applies to the hierarchical models')
+        elif geno:
+            labels = list(dict.fromkeys(arrays.genotypes))
+        else:
+            labels = [(ids[m], env_of(x)) for m in range(nb) for x in range(E)]
+        if between is not None:
+            if (between == "genotype") != (geno and level == "hyper") or (between == "env" and not has_env) or (between == "rep" and (level == "hyper" or R < 2)):
+                raise BarBayError(f'between="{between}" cannot be served at level "{level}" of {mname}')
+            if between in ("id", "genotype") and reference is None:
+                raise BarBayError(f'between="{between}" needs reference=')
+            contrasts = _contrast_pairs(labels, between, reference)
+        index = {x: i for i, x in enumerate(labels)}
+        terms = []
+        for c, con in enumerate(contrasts):
+            for x in con:
+                if x not in index:
+                    form = "genotype" if geno and level == "hyper" else "(id, env)" if level == "hyper" else "(id, rep, env)"
+                    raise BarBayError(f"contrast {c}: unknown label {x!r} (level {level!r}: {form})")
+            terms.append([(index[x], float(w)) for x, w in con.items()])
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        kw = dict(n_samples=n_samples, threshold=threshold, seed=seed, draws=draws)
+        res = e.contrast_rb(terms, space="fitness" if level == "fitness" else "theta", probs=probs, **kw)
+        own = (e.fitness_rb if level == "fitness" else e.theta_rb)(probs=(), **kw)["rb_sd"]
+    fmt = lambda x: "(" + ", ".join(str(v) for v in x) + ")" if isinstance(x, tuple) else str(x)
+    out = {
+        "contrast": np.arange(len(terms)),
+        "terms": [" ".join(f"{w:+g} {fmt(labels[k])}" for k, w in t) for t in terms],
+        "n_terms": [len(t) for t in terms],
+        "min_steps": res["min_steps"],
+    }
+    for k in ("q_mean", "q_sd", "rb_mean", "rb_sd"):
+        out[k] = res[k]
+    out["indep_sd"] = np.asarray([math.sqrt(sum((w * own[k]) ** 2 for k, w in t)) for t in terms], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["sd_ratio"] = res["rb_sd"] / res["q_sd"]
+        out["common_mode"] = res["rb_sd"] / out["indep_sd"]
+    out["p_pos"], out["p_neg"] = res["p_pos"], res["p_neg"]
+    for i, p in enumerate(probs):
+        out[f"q{100.0 * p:g}"] = res["quantiles"][:, i]
+    order = ["contrast", "terms", "n_terms", "min_steps", "q_mean", "q_sd", "rb_mean", "rb_sd", "sd_ratio", "indep_sd", "common_mode", "p_pos", "p_neg"]
+    return pd.DataFrame({k: out[k] for k in order + [k for k in out if k not in order]})
 
 
 def popmean_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,

@@ -577,6 +577,82 @@ typedef struct bb_theta_rb_out {  /* every pointer may be NULL; [n_groups] unles
 int bb_theta_rb_shape(const bb_handle* h, int64_t* n_groups);
 int bb_theta_rb(bb_handle* h, const bb_rb_opts* o, const bb_theta_rb_out* out);
 
+/* Rao-Blackwellised marginals of linear contrasts of fitnesses -- the number a barcode experiment is run for: is mutant m fitter in
+ * environment B than in A, is genotype g fitter than the wild type, do two replicates agree, is one lineage fitter than another on
+ * average.  No reference counterpart.  A contrast cannot be had from two marginals by adding their variances: every fitness of a
+ * replicate is measured against the same population mean sbar_t, whose uncertainty each marginal carries (bb_fitness_rb's sd_ratio)
+ * and which cancels, draw by draw, in a difference of two mutants of one replicate -- and adds up in their sum.
+ *
+ * The fact it rests on.  Given everything else a fitness unit enters the log-joint through its own prior and its own
+ * log-frequency-ratio terms only; no term holds two units.  The joint full conditional of distinct units is therefore the product of
+ * bb_fitness_rb's N(m_{u,j}, sd_{u,j}) (its n_u = 0 rule and the hierarchical kinds' N(theta_j, tau_j) prior included), and the same
+ * holds for distinct groups of bb_theta_rb, whose conditional never reads another theta.  A unit and the theta of its own group
+ * are NOT conditionally independent: one call serves one space.
+ *
+ * Spaces: BB_CONTRAST_FITNESS -- the terms name units u of bb_fitness_rb (0 .. n_units - 1, every model kind);
+ * BB_CONTRAST_THETA -- groups g of bb_theta_rb (0 .. n_groups - 1, the hierarchical kinds).
+ * Contrasts: CSR.  Contrast c has the terms k = term_ptr[c] .. term_ptr[c + 1] - 1, element term_idx[k] with weight term_w[k]; at
+ * least one term, every element named at most once per contrast (a repeated element would make V below wrong), finite weights.
+ *
+ * Per draw j, a term's (s_{k,j}, m_{k,j}, sd_{k,j}) are exactly those of bb_fitness_rb / bb_theta_rb for that unit / group: the same
+ * gamma, the same ln Z by the 256-column rule, ascending t, the later time point's environment, the n_u = 0 rule; for theta the
+ * members in chunks of BB_THETA_RB_CHUNK, a chunk's (SP, SN) from 0.0 in member order, the chunks from 0.0 in chunk order, members
+ * with n_u = 0 skipped.  Then, each sum starting at 0.0 and taking the contrast's terms in the caller's order:
+ *   d_j = sum_k w_k s_{k,j}              the draw's own value of the contrast
+ *   M_j = sum_k w_k m_{k,j}
+ *   V_j = sum_k (w_k sd_{k,j}) (w_k sd_{k,j});   sd_j = sqrt(V_j)
+ * (the term values are w * s, w * m and (w * sd) * (w * sd), as written).  The conditional of the contrast is exactly N(M_j, sd_j).
+ *
+ * Outputs per contrast (every pointer may be NULL), bb_fitness_rb's read for the contrast:
+ *   min_steps  the smallest n_u (THETA: group n_steps) over the terms; 0: some term's conditional is its prior
+ *   q_mean, q_sd     mean and sd of d_j over the draws: two-pass, centred, divisor n
+ *   rb_mean, rb_sd, p_pos, p_neg, quantiles    from (M_j, sd_j) by bb_fitness_rb's formulas word for word, the 64-step bisection,
+ *              its bracket and its NaN rule included.  A one-term contrast of weight 1.0 differs from the unit's own marginal only
+ *              by sqrt(sd * sd) in place of sd: an ulp at most.
+ * Non-finite parameters propagate by IEEE rules into the contrasts that name a unit or group that uses them; they disturb no other
+ * contrast and are not an error.
+ *
+ * Options: n_samples, n_quantiles, probs, threshold, seed and draws are bb_rb_opts' exactly (the keying included: at equal seed the
+ * draws are bb_fitness_rb's; n_samples = 1 is allowed with draws; BB_RB_MAX_SAMPLES because (M_j, sd_j) live in LDS).
+ *
+ * Cost.  One workgroup per contrast; nothing is shared between contrasts.  A FITNESS term walks its unit's loglambda row once per
+ * draw.  A THETA term re-walks the rows of its whole group once per draw, for every contrast that names it: fine for "every
+ * genotype against a reference" (the reference is walked once per contrast), quadratic for "all pairs" of a thousand genotypes.
+ *
+ * A contrast's results are a function of the handle's (mu, sigma) (or the supplied draws), the priors, geno_idx, n_samples, seed,
+ * threshold, probs and that contrast's own terms in their order: bit-identical whatever the grid, the launch mode, the other
+ * contrasts of the call, their number or their order, the device count or the calls made before.  (Permuting the terms within a
+ * contrast reorders three floating-point sums and may change low bits.)  No atomics on doubles.  The handle's mu, omega, optimiser
+ * state, step counter and RNG position are untouched, bitwise.
+ * BB_ERR_INVALID: a null h, o or out; the option errors of bb_fitness_rb; an unknown space; n_contrasts < 0; with n_contrasts > 0 a
+ * null term_ptr, term_idx or term_w, term_ptr[0] != 0 or a decreasing term_ptr, a contrast without terms, an index outside the
+ * space, an element named twice in one contrast, a non-finite weight.  BB_ERR_UNSUPPORTED: n_samples outside its range;
+ * BB_CONTRAST_THETA on BB_MODEL_FITNESS / BB_MODEL_MULTIENV; more than 2^31 - 1 terms.  The message (bb_last_error) names the
+ * contrast and the term within it, both 0-based.  n_contrasts == 0 is BB_OK and computes nothing.  Multi-device and sharded
+ * handles: as bb_ppc_bands.  Out of scope: contrasts that mix the spaces, or over sbar, logsigma, logtau or loglambda. */
+#define BB_CONTRAST_FITNESS 0   /* terms index bb_fitness_rb's units  */
+#define BB_CONTRAST_THETA   1   /* terms index bb_theta_rb's groups   */
+typedef struct bb_contrast_opts {
+    int32_t space;            /* BB_CONTRAST_FITNESS or BB_CONTRAST_THETA              */
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RB_MAX_SAMPLES        */
+    int32_t n_quantiles;      /* 0 .. 8                                                */
+    int32_t reserved0;
+    const double* probs;      /* [n_quantiles] probabilities in (0, 1)                 */
+    double threshold;         /* s0 of p_pos / p_neg                                   */
+    uint64_t seed;            /* Philox key (draws == NULL)                            */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL   */
+    int64_t n_contrasts;
+    const int64_t* term_ptr;  /* [n_contrasts + 1], CSR, term_ptr[0] == 0, non-decreasing */
+    const int64_t* term_idx;  /* [term_ptr[n_contrasts]] unit / group numbers          */
+    const double* term_w;     /* [term_ptr[n_contrasts]] weights                       */
+} bb_contrast_opts;
+typedef struct bb_contrast_out {  /* every pointer may be NULL; [n_contrasts] unless noted */
+    double *q_mean, *q_sd, *rb_mean, *rb_sd, *p_pos, *p_neg;
+    double* quantiles;        /* [n_contrasts][n_quantiles]                            */
+    int32_t* min_steps;       /* smallest n_u (THETA: group n_steps) over the terms    */
+} bb_contrast_out;
+int bb_contrast_rb(bb_handle* h, const bb_contrast_opts* o, const bb_contrast_out* out);
+
 /* Rao-Blackwellised marginals of the population mean fitness sbar_t -- the pop_mean_fitness rows of a fit, the quantity every
  * reported mutant fitness is relative to, and the one latent that every barcode's log-frequency-ratio term reads: q factorises it
  * away from all of them.  No reference counterpart.  sbar_g enters the log-joint through its Gaussian prior (s_pop_prior, Vector or

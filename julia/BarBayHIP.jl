@@ -419,6 +419,73 @@ function theta_rb(h::Ptr{Cvoid}; n_samples::Int=1000, probs::Vector{Float64}=[0.
             quantiles=quantiles)
 end
 
+# Rao-Blackwellised marginals of linear contrasts of fitnesses (bb_contrast_rb, include/barbay_hip.h): distinct fitness units (or
+# distinct hyper-fitnesses) are conditionally independent given everything else, so the contrast's conditional is exactly Gaussian
+# per draw, and what the terms share cancels or adds up draw by draw.  Field for field the Python binding's `bb_contrast_opts` /
+# `bb_contrast_out` (barbay.jl_amd/_capi.py).  Like the rest of this file it remains unexecuted.
+const BB_CONTRAST_FITNESS = Int32(0)
+const BB_CONTRAST_THETA = Int32(1)
+struct bb_contrast_opts
+    space::Int32
+    n_samples::Int32
+    n_quantiles::Int32
+    reserved0::Int32
+    probs::Ptr{Float64}
+    threshold::Float64
+    seed::UInt64
+    draws::Ptr{Float64}
+    n_contrasts::Int64
+    term_ptr::Ptr{Int64}
+    term_idx::Ptr{Int64}
+    term_w::Ptr{Float64}
+end
+struct bb_contrast_out
+    q_mean::Ptr{Float64}
+    q_sd::Ptr{Float64}
+    rb_mean::Ptr{Float64}
+    rb_sd::Ptr{Float64}
+    p_pos::Ptr{Float64}
+    p_neg::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    min_steps::Ptr{Int32}
+end
+
+"""
+    contrast_rb(h, terms; space=:fitness, n_samples=1000, probs=[0.025, 0.5, 0.975], threshold=0.0, seed=0, draws=nothing) -> NamedTuple
+
+`h` a live `bb_handle`.  `terms`: a vector of contrasts, each a vector of `index => weight` pairs with the 0-based unit numbers of
+`fitness_rb` (`space=:fitness`) or group numbers of `theta_rb` (`space=:theta`); every element at most once per contrast.  Returns
+`min_steps, q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg` (one per contrast) and `quantiles` (length(probs) x n_contrasts).  The
+remaining arguments as for `fitness_rb`.
+"""
+function contrast_rb(h::Ptr{Cvoid}, terms::Vector{<:Vector{<:Pair}}; space::Symbol=:fitness, n_samples::Int=1000,
+                     probs::Vector{Float64}=[0.025, 0.5, 0.975], threshold::Real=0.0, seed::Integer=0,
+                     draws::Union{Nothing,Matrix{Float64}}=nothing)
+    space in (:fitness, :theta) || error("contrast_rb: space must be :fitness or :theta")
+    nc, nq = length(terms), length(probs)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("contrast_rb: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    term_ptr = Int64.(cumsum(vcat(0, length.(terms))))
+    term_idx = Int64[first(p) for t in terms for p in t]
+    term_w = Float64[last(p) for t in terms for p in t]
+    q_mean, q_sd, rb_mean, rb_sd, p_pos, p_neg = (Vector{Float64}(undef, nc) for _ in 1:6)
+    quantiles = Matrix{Float64}(undef, nq, nc)
+    min_steps = Vector{Int32}(undef, nc)
+    GC.@preserve probs draws term_ptr term_idx term_w q_mean q_sd rb_mean rb_sd p_pos p_neg quantiles min_steps begin
+        o = bb_contrast_opts(space == :theta ? BB_CONTRAST_THETA : BB_CONTRAST_FITNESS, Int32(n_samples), Int32(nq), Int32(0),
+                             nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL), Float64(threshold), UInt64(seed),
+                             draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws), Int64(nc), pointer(term_ptr), pointer(term_idx),
+                             pointer(term_w))
+        out = bb_contrast_out(pointer(q_mean), pointer(q_sd), pointer(rb_mean), pointer(rb_sd), pointer(p_pos), pointer(p_neg),
+                              nq > 0 ? pointer(quantiles) : Ptr{Float64}(C_NULL), pointer(min_steps))
+        check(ccall((:bb_contrast_rb, LIB), Cint, (Ptr{Cvoid}, Ref{bb_contrast_opts}, Ref{bb_contrast_out}), h, o, out))
+    end
+    return (min_steps=min_steps, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, p_pos=p_pos, p_neg=p_neg, quantiles=quantiles)
+end
+
 # Rao-Blackwellised marginals of the population mean fitness sbar_g, g = (replicate, step) (bb_popmean_rb, include/barbay_hip.h):
 # the exact Gaussian full conditional of a step's population mean, summed over every barcode of the replicate (neutrals, then
 # mutants) and averaged over the draws of `fitness_rb`.  Field for field the Python binding's `bb_popmean_rb_out`
