@@ -35,9 +35,8 @@ BB_DEV void bb_block_hier(BBCtx& cx, const HierArgs& H, int nblocks) {
         const double m_th = H.mean[H.lo_theta + ith], s_th = H.sigma[H.lo_theta + ith];
         const double m_tt = H.mean[H.lo_tt + u], s_tt = H.sigma[H.lo_tt + u];
         const double m_lt = H.mean[H.lo_lt + u], s_lt = H.sigma[H.lo_lt + u];
-        // pass 1: draws, partial sums
+        // pass 1: draws
         BB_PASS(cx, tid) {
-            double acc = 0.0;
             for (int j = tid; j < H.n_pad; j += cx.nthr) {
                 double v = INFINITY;
                 if (j < H.n_samples) {
@@ -46,16 +45,30 @@ BB_DEV void bb_block_hier(BBCtx& cx, const HierArgs& H, int nblocks) {
                     bb_normal_pair(H.seed, ((unsigned long long)ith << 20) | (unsigned long long)(j >> 1), (unsigned)(j & 1), BB_STREAM_HIER_THETA, &n_th, &dummy);
                     if (j & 1) n_th = dummy;
                     bb_normal_pair(H.seed, (unsigned long long)u, (unsigned)j, BB_STREAM_HIER_UNIT, &n_lt, &n_tt);
-                    v = fma(s_th, n_th, m_th) + bb_exp(fma(s_lt, n_lt, m_lt)) * fma(s_tt, n_tt, m_tt);
-                    acc += v;
+                    // (the product and the sum rounded one after the other, as the emulation and the oracle form them: contracted into one
+                    //  fma by the device compiler, a draw is other bits -- an ulp on a quarter of the units of a point posterior)
+                    {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+                        v = fma(s_th, n_th, m_th) + bb_exp(fma(s_lt, n_lt, m_lt)) * fma(s_tt, n_tt, m_tt);
+                    }
                 }
                 smp[j] = v;
             }
+        }
+        BB_SYNC(cx);
+        // the mean about the first draw: the sum of n equal draws over n is not that draw again (n = 3 already misses by an ulp), and a
+        // posterior that has collapsed to a point (sigma = 0) must come out with std == 0, not 1e-13
+        BB_PASS(cx, tid) {
+            const double pv = smp[0];
+            double acc = 0.0;
+            for (int j = tid; j < H.n_samples; j += cx.nthr) acc += smp[j] - pv;
             red[tid] = acc;
         }
         BB_SYNC(cx);
         BB_PASS(cx, tid) {
-            if (tid == 0) { double s = 0.0; for (int i = 0; i < cx.nthr; ++i) s += red[i]; red[cx.nthr] = s / (double)H.n_samples; }
+            if (tid == 0) { double s = 0.0; for (int i = 0; i < cx.nthr; ++i) s += red[i]; red[cx.nthr] = smp[0] + s / (double)H.n_samples; }
         }
         BB_SYNC(cx);
         BB_PASS(cx, tid) {

@@ -700,6 +700,10 @@ BB_DEV void br_sample(BBCtx& cx, const DevModel& M, const DevState& S, const Run
     if (A.pf == 1 && prefetch) br_prefetch_slot<P, HD, OS>(cx, M, S, A, Y, stv, slot);
     BB_PASS(cx, tid) {
         BRSt<P>& st = BB_PSTATE(stv, tid);
+        // (in front of the slots, not inside slot 0: whoever is skipped in slot 0 and works in a later one -- in the emulation any lane
+        //  of a segment's wave-alignment gap, 16 replicates have 16 of them; on the device only a wave that idles as a whole -- would
+        //  keep its terms of the samples before in the sum)
+        if (MS && want_el) st.el = 0.0;
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             // a pair slot that no lane of this wave uses (the tail of the tile's last slot) costs nothing
@@ -716,7 +720,6 @@ BB_DEV void br_sample(BBCtx& cx, const DevModel& M, const DevState& S, const Run
             st.a[k] = bb_d2{e.x * sg0, e.y * sg1};
             st.h[k] = bb_d2{sg0 * bb_rcp(sp0), sg1 * bb_rcp(sp1)};
             if (MS && want_el) {
-                if (k == 0) st.el = 0.0;
                 const int meta = st.meta[k], kd = meta & 15;
                 const bool counted = (meta & BRM_VALID) && (kd < SK_GS || A.count_globals);      // (sharded run: rank 0 counts the replicated blocks)
                 if (counted) {

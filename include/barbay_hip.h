@@ -191,7 +191,12 @@ const char* bb_last_error(void);
 void bb_default_opts(bb_advi_opts* opts);
 
 /* Build device state for one model instance.  Validates the description
- * (shapes, totals == row sums, index ranges) and copies everything it needs. */
+ * (shapes, totals == row sums, index ranges) and copies everything it needs.
+ * Shape limits: n_time[r] outside 2..255 is BB_ERR_INVALID.  A shape whose two-kernel tile of 8 barcodes needs more than the
+ * 160 KiB of LDS of a compute unit (bb_lds_layout: the need grows with n_time x n_rep x n_env) is BB_ERR_UNSUPPORTED, "a tile of 8
+ * barcodes needs N bytes of LDS / n threads (n_time or n_rep too large for this build)".  Largest uniform n_time accepted: fitness
+ * and genotype 96; multienv with 4 environments 95; replicate with 2 / 4 / 8 / 16 replicates 47 / 22 / 9 / 5; multienv_replicate
+ * with 16 replicates 4, with 4 replicates and 4 environments 20 ("Limits the reference does not have"). */
 int bb_create(const bb_model_desc* model, const bb_advi_opts* opts, bb_handle** out);
 void bb_destroy(bb_handle* h);
 
