@@ -29,6 +29,9 @@ BB_RB_MAX_SAMPLES = 8672
 BB_RB_MAX_Q = 8
 BB_THETA_RB_CHUNK = 64
 BB_POPMEAN_RB_CHUNK = 256
+BB_DFE_CHUNK = 128
+BB_DFE_MAX_GRID = 64
+BB_DFE_MAX_SAMPLES = 8672
 BB_LOGSIGMA_RB_MAX_SAMPLES = 5781
 BB_LOGSIGMA_BLOCKS = {"bc": 0, "pop": 1}
 BB_LOGTAU_RB_MAX_SAMPLES = 5781
@@ -45,7 +48,7 @@ EXPORTS = [
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
-    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
+    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_dfe_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
     "bb_logsigma_rb_shape", "bb_logsigma_rb", "bb_logtau_rb_shape", "bb_logtau_rb",
     "bb_loglambda_rb_shape", "bb_loglambda_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
@@ -155,6 +158,20 @@ class bb_contrast_opts(C.Structure):
 
 class bb_contrast_out(C.Structure):
     _fields_ = [(k, _dp) for k in RB_UNITS] + [("quantiles", _dp), ("min_steps", C.POINTER(C.c_int32))]
+
+
+DFE_CELLS = ("below_mean", "above_mean", "between_sd", "within_sd", "q_below_mean", "q_below_sd")
+DFE_BANDS = ("below_bands", "above_bands")
+
+
+class bb_dfe_opts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("n_quantiles", C.c_int32), ("n_grid", C.c_int32), ("reserved0", C.c_int32), ("probs", _dp),
+                ("grid", _dp), ("seed", C.c_uint64), ("draws", _dp), ("n_sets", C.c_int64),
+                ("set_ptr", C.POINTER(C.c_int64)), ("set_idx", C.POINTER(C.c_int64))]
+
+
+class bb_dfe_out(C.Structure):
+    _fields_ = [(k, _dp) for k in DFE_CELLS + DFE_BANDS] + [("n_units", C.POINTER(C.c_int64))]
 
 
 class bb_popmean_rb_out(C.Structure):
@@ -308,6 +325,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.bb_theta_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_theta_rb_out)]
     if hasattr(lib, "bb_contrast_rb"):
         lib.bb_contrast_rb.argtypes = [vp, C.POINTER(bb_contrast_opts), C.POINTER(bb_contrast_out)]
+    if hasattr(lib, "bb_dfe_rb"):
+        lib.bb_dfe_rb.argtypes = [vp, C.POINTER(bb_dfe_opts), C.POINTER(bb_dfe_out)]
     if hasattr(lib, "bb_popmean_rb"):
         lib.bb_popmean_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_popmean_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_popmean_rb_out)]
@@ -716,7 +735,9 @@ class Engine:
         """(bb_rb_opts, probs, draws): the arrays the options point into must outlive the call."""
         p = _f64(np.atleast_1d(probs)).reshape(-1)
         o = opts()
-        o.n_samples, o.n_quantiles, o.threshold, o.seed = int(n_samples), int(p.shape[0]), float(threshold), int(seed)
+        o.n_samples, o.n_quantiles, o.seed = int(n_samples), int(p.shape[0]), int(seed)
+        if threshold is not None:                     # (bb_dfe_opts has none)
+            o.threshold = float(threshold)
         o.probs = _ptr(p) if p.shape[0] else None
         x = None
         if draws is not None:
@@ -793,6 +814,46 @@ class Engine:
         out.quantiles = _ptr(res["quantiles"]) if p.shape[0] else None
         out.min_steps = res["min_steps"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_contrast_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def dfe_rb(self, sets, grid, *, probs: Sequence[float] = (0.025, 0.5, 0.975), n_samples: int = 1000, seed: int = 0, draws=None,
+               _slab_tables: int = 0) -> Dict[str, np.ndarray]:
+        """Posterior of the distribution of fitness effects of sets of fitness units (`bb_dfe_rb`): per set and threshold x of
+        `grid` (finite, strictly ascending, at most BB_DFE_MAX_GRID) the fraction of the set's units at or below (above) x, averaged
+        over the draws of `fitness_rb` (same `n_samples`, `seed`, `draws`) with each unit's exact Gaussian conditional in place of its
+        draw, so that what the units share -- the population mean fitness above all -- moves the whole curve draw by draw.  `sets`:
+        a list of index sequences (the units of `fitness_rb`, each at most once per set), or a CSR pair as a tuple (ptr, idx).  Returns
+        below_mean, above_mean, between_sd (sd over the draws of the conditional fraction below x), within_sd (sqrt of the mean
+        conditional, Poisson-binomial, variance; the total variance of the fraction is between_sd^2 + within_sd^2), q_below_mean,
+        q_below_sd (the draws' own ECDF at x), each [n_sets, n_grid]; below_bands, above_bands [n_sets, n_grid, len(probs)], the
+        `probs` quantiles over the draws of the two conditional fractions; n_units [n_sets] (int64).  `_slab_tables`: tests only."""
+        if isinstance(sets, tuple) and len(sets) == 2:
+            ptr, idx = sets                           # (a tuple is the CSR pair; a list of two index lists is two sets)
+        else:
+            sets = [np.asarray(c, dtype=np.int64).reshape(-1) for c in sets]
+            ptr = np.cumsum([0] + [len(c) for c in sets])
+            idx = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int64)
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        if ptr.shape[0] < 1 or (ptr.shape[0] > 1 and ptr[-1] != idx.shape[0]):
+            raise BarBayHipError("sets: ptr must have n_sets + 1 entries ending at the number of indices")
+        n = ptr.shape[0] - 1
+        x = _f64(np.atleast_1d(grid)).reshape(-1)
+        o, p, _x = self._rb_opts(n_samples, probs, None, seed, draws, opts=bb_dfe_opts)
+        o.n_grid, o.grid, o.n_sets, o.reserved0 = x.shape[0], _ptr(x) if x.shape[0] else None, n, int(_slab_tables)
+        i64 = C.POINTER(C.c_int64)
+        idx_ = idx if idx.shape[0] else np.zeros(1, dtype=np.int64)
+        o.set_ptr, o.set_idx = ptr.ctypes.data_as(i64), idx_.ctypes.data_as(i64)
+        res = {k: np.empty((n, x.shape[0])) for k in DFE_CELLS}
+        res.update({k: np.empty((n, x.shape[0], p.shape[0])) for k in DFE_BANDS})
+        res["n_units"] = np.empty(n, dtype=np.int64)
+        out = bb_dfe_out()
+        for k in DFE_CELLS:
+            setattr(out, k, _ptr(res[k]))
+        for k in DFE_BANDS:
+            setattr(out, k, _ptr(res[k]) if p.shape[0] else None)
+        out.n_units = res["n_units"].ctypes.data_as(i64)
+        self._check(self._lib.bb_dfe_rb(self._h, C.byref(o), C.byref(out)))
         return res
 
     def popmean_rb_shape(self) -> int:

@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
 // bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
-// bb_contrast_rb (bb_contrast.h), bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
+// bb_contrast_rb (bb_contrast.h), bb_dfe_rb (bb_dfe.h), bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -996,6 +996,183 @@ extern "C" int bb_contrast_rb(bb_handle* h, const bb_contrast_opts* o, const bb_
         for (long long k = o->term_ptr[c] + 1; k < o->term_ptr[c + 1]; ++k) lo = std::min(lo, elem_steps[(size_t)o->term_idx[k]]);
         out->min_steps[c] = lo;
     }
+    return BB_OK;
+}
+
+// ---- posterior of the fitness distribution of sets of units (bb_dfe.h) ---------------------------------------------------------------
+static_assert(BB_DFE_CHUNK == BB_DFE_CHUNK_UNITS && BB_DFE_MAX_SAMPLES == BB_DFE_SAMPLES_CAP && BB_DFE_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_dfe_rb limits");
+// The grid and the sets checked: thresholds finite and strictly ascending; a well-formed CSR, every set with units, every index
+// inside the units and named once per set.  *n_idx = set_ptr[n_sets].
+static int dfe_check(const bb_dfe_opts* o, long long n_units, long long* n_idx) {
+    if (o->n_grid < 1 || o->n_grid > BB_DFE_MAX_GRID) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: n_grid = %d, must be in 1..%d", (int)o->n_grid, BB_DFE_MAX_GRID);
+    if (!o->grid) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: grid must not be null");
+    for (int g = 0; g < o->n_grid; ++g) {
+        if (!std::isfinite(o->grid[g])) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: grid point %d is not finite", g);
+        if (g > 0 && !(o->grid[g] > o->grid[g - 1])) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: grid point %d does not lie above grid point %d: the grid must be strictly ascending", g, g - 1);
+    }
+    if (o->reserved0 < 0) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: reserved0 = %d, must be 0", (int)o->reserved0);
+    const long long nc = o->n_sets;
+    if (nc < 0) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: n_sets = %lld", nc);
+    *n_idx = 0;
+    if (nc == 0) return BB_OK;
+    if (!o->set_ptr || !o->set_idx) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set_ptr and set_idx must not be null");
+    if (o->set_ptr[0] != 0) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set_ptr[0] = %lld, must be 0", (long long)o->set_ptr[0]);
+    if (nc > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_dfe_rb: more than 2^31 - 1 indices");
+    for (long long c = 0; c < nc; ++c) {
+        if (o->set_ptr[c + 1] < o->set_ptr[c])
+            return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld: set_ptr decreases (%lld after %lld)", c, (long long)o->set_ptr[c + 1], (long long)o->set_ptr[c]);
+        if (o->set_ptr[c + 1] == o->set_ptr[c]) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld has no units", c);
+    }
+    if (o->set_ptr[nc] > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_dfe_rb: %lld indices, more than 2^31 - 1", (long long)o->set_ptr[nc]);
+    std::vector<long long> seen;
+    for (long long c = 0; c < nc; ++c) {
+        const long long k0 = o->set_ptr[c], k1 = o->set_ptr[c + 1];
+        for (long long k = k0; k < k1; ++k)
+            if (o->set_idx[k] < 0 || o->set_idx[k] >= n_units)
+                return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld, position %lld: unit %lld outside 0..%lld", c, k - k0, (long long)o->set_idx[k], n_units - 1);
+        seen.assign(o->set_idx + k0, o->set_idx + k1);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) {
+            long long k = k1 - 1;                      // the later of the two positions that name it
+            while (o->set_idx[k] != *dup) --k;
+            return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld, position %lld: unit %lld is named twice", c, k - k0, *dup);
+        }
+    }
+    *n_idx = o->set_ptr[nc];
+    return BB_OK;
+}
+
+extern "C" int bb_dfe_rb(bb_handle* h, const bb_dfe_opts* o, const bb_dfe_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples, ngr = o->n_grid;
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_DFE_MAX_SAMPLES, nullptr)) return rc;
+    if (nq > 0 && ns < 2) return bb_fail(BB_ERR_UNSUPPORTED, "bb_dfe_rb: n_quantiles > 0 needs n_samples >= 2: one draw has no quantiles over the draws");
+    long long n_idx = 0;
+    if (int rc = dfe_check(o, rb_units(h), &n_idx)) return rc;
+    if (o->n_sets == 0) return BB_OK;
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    DfeArgs D;
+    memset(&D, 0, sizeof D);
+    RbArgs& A = D.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const size_t nset = (size_t)o->n_sets, nix = (size_t)n_idx, ncell = nset * (size_t)ngr;
+    int zb;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, (long long)ncell, &zb);
+    if (rc) return rc;
+    if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {      // the s_bc prior, as bb_fitness_rb sets it
+        const DevPrior& dp = M.pri[BK_S];
+        P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    }
+    if (nq > 0) quantile_plan(ns, o->probs, nq, P);    // (P.n_q stays 0: the program interpolates per probability, as bb_chain_summary's)
+    D.n_grid = ngr;
+    D.n_cells = (long long)ncell;
+    RbTimes pt{dh->stream};      // tools/dfe_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
+    // the chunk map: set -> first chunk, chunk -> set
+    std::vector<int> hm;                               // set_ptr | set_idx | set_c0 | chk_set
+    hm.reserve(2 * (nset + 1) + nix + nix / BB_DFE_CHUNK + nset);
+    for (size_t c = 0; c <= nset; ++c) hm.push_back((int)o->set_ptr[c]);
+    for (size_t k = 0; k < nix; ++k) hm.push_back((int)o->set_idx[k]);
+    std::vector<int> set_c0(nset + 1, 0), chk_set;
+    for (size_t c = 0; c < nset; ++c) {
+        const long long n = o->set_ptr[c + 1] - o->set_ptr[c], nc = (n + BB_DFE_CHUNK - 1) / BB_DFE_CHUNK;
+        set_c0[c + 1] = set_c0[c] + (int)nc;
+        chk_set.insert(chk_set.end(), (size_t)nc, (int)c);
+    }
+    const size_t at_c0 = hm.size();
+    hm.insert(hm.end(), set_c0.begin(), set_c0.end());
+    const size_t at_cs = hm.size();
+    hm.insert(hm.end(), chk_set.begin(), chk_set.end());
+    // The slabs: sets [cut[s], cut[s + 1]) with all their grid points while their chunk partials, one [4][ns] table per (chunk,
+    // grid point), stay within 256 MiB; a set too large for that takes its grid points grid_width at a time (a single (set, grid
+    // point) is worked whole whatever it takes).
+    const size_t nsz = (size_t)ns, D_ = (size_t)h->M.D, nmap = hm.size();
+    const size_t cap = o->reserved0 > 0 ? (size_t)o->reserved0 : std::max<size_t>(1, ((size_t)256 << 20) / (4 * nsz * 8));
+    auto grid_width = [&](size_t nchk) {               // grid points in flight of a slab of nchk chunks: all, or whole groups of the part program
+        if (nchk * (size_t)ngr <= cap) return (size_t)ngr;
+        const size_t gw = std::max<size_t>(1, cap / nchk);
+        return gw > BB_DFE_GROUP ? gw - gw % BB_DFE_GROUP : gw;
+    };
+    std::vector<size_t> cut{0};
+    size_t slab_tabs = 1, slab_cells = 1, n_slabs = 0;
+    while (cut.back() < nset) {
+        const size_t s0 = cut.back();
+        size_t s1 = s0 + 1;
+        while (s1 < nset && (size_t)(set_c0[s1 + 1] - set_c0[s0]) * (size_t)ngr <= cap) ++s1;
+        const size_t nchk = (size_t)(set_c0[s1] - set_c0[s0]);
+        const size_t gw = grid_width(nchk);
+        n_slabs += ((size_t)ngr + gw - 1) / gw;
+        slab_tabs = std::max(slab_tabs, nchk * gw);
+        slab_cells = std::max(slab_cells, (s1 - s0) * gw);
+        cut.push_back(s1);
+    }
+    const int nblk = (int)std::max<long long>(1, std::min<long long>((long long)slab_cells, 2LL * dh->cus));
+    B.nblk = (3LL * nblk + 2 * P.E - 1) / (2 * P.E);   // (P.par, [B.nblk][E][2][ns], holds the [nblk][3][ns] table of bb_block_dfe and nothing else)
+    double* ddraws = nullptr;
+    double* dgrid = nullptr;
+    int* dmap = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, (size_t)M.Ttot * nsz);                  // [Ttot][ns]
+        c(F.zpart, (size_t)F.nchunks * zb * nsz);      // [nchunks][zb][ns]
+        c(D.part, slab_tabs * 4 * nsz);                // [chunks in flight][grid points in flight][4][ns]
+        c(D.cell, BB_DFE_OUT * ncell);                 // [6][n_sets n_grid]
+        c(D.bands, nq ? 2 * ncell * BB_RB_MAX_Q : 0);  // [2][n_sets n_grid][8]
+        c(dgrid, (size_t)ngr);                         // [n_grid]
+        c(dmap, (nmap + 1) / 2);                       // the CSR arrays and the chunk map: ints
+        c(ddraws, o->draws ? nsz * D_ : 0);            // [ns][D]
+    });
+    if (rc) return rc;
+    A.ytab = P.par;
+    D.set_ptr = dmap;
+    D.set_idx = dmap + nset + 1;
+    D.set_c0 = dmap + at_c0;
+    D.chk_set = dmap + at_cs;
+    D.grid = dgrid;
+    if ((rc = h2d(dmap, hm.data(), nmap * 4, dh->stream)) || (rc = h2d(dgrid, o->grid, (size_t)ngr * 8, dh->stream))) return rc;
+    if ((rc = rb_draws(dh, P, ddraws, o->draws, nsz, D_))) return rc;
+    pt.lap(1, 0);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    pt.lap(2, 1);
+    if ((rc = rb_front(dh, B, A, zb, false))) return rc;
+    pt.lap(3, 2);
+    const long long ntile = ((long long)ns + BB_DFE_PART_NT - 1) / BB_DFE_PART_NT;
+    for (size_t sl = 0; sl + 1 < cut.size(); ++sl) {
+        const size_t s0 = cut[sl], s1 = cut[sl + 1], nchk = (size_t)(set_c0[s1] - set_c0[s0]);
+        const int gw = (int)grid_width(nchk);
+        D.s0 = (long long)s0; D.s1 = (long long)s1;
+        D.c0 = set_c0[s0]; D.c1 = set_c0[s1];
+        for (int g0 = 0; g0 < ngr; g0 += gw) {
+            D.g0 = g0; D.g1 = std::min(g0 + gw, ngr);
+            const long long ngrp = (D.g1 - D.g0 + BB_DFE_GROUP - 1) / BB_DFE_GROUP, ncl = (long long)(s1 - s0) * (D.g1 - D.g0);
+            pt.lap(4, -1);
+            if ((rc = launch(dh->stream, k_dfe_part, (int)std::min<long long>((long long)nchk * ngrp * ntile, 1 << 20), BB_DFE_PART_NT, 0, D))) return rc;
+            pt.lap(5, 3);
+            if ((rc = launch(dh->stream, k_dfe, (int)std::min<long long>(ncl, nblk), BB_SCORE_NT, (size_t)BB_DFE_LDS_DOUBLES(ns, 1), D))) return rc;
+            pt.lap(6, 4);
+        }
+    }
+    double* cells[BB_DFE_OUT] = {out->below_mean, out->above_mean, out->between_sd, out->within_sd, out->q_below_mean, out->q_below_sd};
+    for (int k = 0; k < BB_DFE_OUT; ++k)
+        if (cells[k] && (rc = d2h(cells[k], D.cell + (size_t)k * ncell, ncell * 8, dh->stream))) return rc;
+    double* bands[2] = {out->below_bands, out->above_bands};
+    std::vector<double> q;
+    for (int side = 0; side < 2 && nq; ++side) {
+        if (!bands[side]) continue;
+        q.resize(BB_RB_MAX_Q * ncell);
+        if ((rc = d2h(q.data(), D.bands + (size_t)side * ncell * BB_RB_MAX_Q, q.size() * 8, dh->stream))) return rc;
+        for (size_t e = 0; e < ncell; ++e)
+            for (int i = 0; i < nq; ++i) bands[side][e * nq + i] = q[e * BB_RB_MAX_Q + i];
+    }
+    if ((rc = dsync(dh->stream))) return rc;
+    for (size_t c = 0; out->n_units && c < nset; ++c) out->n_units[c] = o->set_ptr[c + 1] - o->set_ptr[c];
+    pt.lap(7, 5);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_dfe_rb %zu sets, %zu indices, %zu chunks, %d grid points, %d samples, %d quantiles, %zu slabs] map+upload %.3f ms, pop %.3f ms, normalisers %.3f ms, part %.3f ms, dfe %.3f ms, download %.3f ms\n", nset, nix, chk_set.size(), ngr, ns, nq, n_slabs, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5]);
+#endif
     return BB_OK;
 }
 

@@ -437,6 +437,14 @@ BB_KERNEL(BB_SCORE_NT, k_rb_contrast, ContrastArgs C) {
     BB_CTX;
     bb_block_contrast(cx, C, BB_GRID);
 }
+BB_KERNEL(BB_DFE_PART_NT, k_dfe_part, DfeArgs D) {
+    BB_CTX;
+    bb_block_dfe_part(cx, D, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_dfe, DfeArgs D) {
+    BB_CTX;
+    bb_block_dfe(cx, D, BB_GRID);
+}
 BB_KERNEL(BB_SCORE_NT, k_ls_bc, LsArgs L) {
     BB_CTX;
     bb_block_ls_bc(cx, L, BB_GRID);

@@ -243,10 +243,7 @@ BB_DEV void bb_block_chain_stats(BBCtx& cx, const ChainArgs& C, int nblocks) {
             // the order statistics stay in the select's state; the interpolation of bb_ppc_select's bands, fused on both backends
             bb_ppc_select(cx, P, S, col, nullptr);
             BB_PASS(cx, tid) {
-                if (tid < C.nq) {
-                    const double a = S.tval[P.plo[tid]], b = S.tval[P.plo[tid] + 1], gm = P.gam[tid];
-                    C.quant[c * BB_CHAIN_QSTRIDE + tid] = (isfinite(a) && isfinite(b)) ? fma(gm, b - a, a) : (1.0 - gm) * a + gm * b;
-                }
+                if (tid < C.nq) C.quant[c * BB_CHAIN_QSTRIDE + tid] = bb_ppc_interp(P, S, tid);
             }
             BB_SYNC(cx);
         }

@@ -210,6 +210,14 @@ BB_DEV void bb_ppc_select(BBCtx& cx, const PpcArgs& P, const PpcSel& S, const do
     BB_SYNC(cx);
 }
 
+// Probability e's quantile from the order statistics a selection left in S.tval: StatsBase.quantile's interpolation with the
+// product fused on both backends, for the callers that plan per probability and pass bb_ppc_select no `out` (bb_block_chain_stats,
+// bb_block_dfe).  bb_ppc_select's own band ends keep a + gamma (b - a) as written above: their bytes are what they were.
+BB_DEV double bb_ppc_interp(const PpcArgs& P, const PpcSel& S, int e) {
+    const double a = S.tval[P.plo[e]], b = S.tval[P.plo[e] + 1], gm = P.gam[e];
+    return (isfinite(a) && isfinite(b)) ? fma(gm, b - a, a) : (1.0 - gm) * a + gm * b;
+}
+
 // per-sample parameters (s_j, exp(logsigma_j)) of mutant m in replicate r, every environment, into the block's scratch slice par[E][2][n_samples]
 BB_DEV void bb_ppc_row_par(BBCtx& cx, const PpcArgs& P, double* par, int r, long long m) {
     const int ns = P.n_samples, E = P.E;

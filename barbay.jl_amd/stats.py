@@ -644,6 +644,99 @@ def fitness_contrasts(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, level
     return pd.DataFrame({k: out[k] for k in order + [k for k in out if k not in order]})
 
 
+def fitness_distribution(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, by: str = "rep_env", groups: Optional[Dict] = None,
+                         grid: Optional[Sequence[float]] = None, model_kwargs: Optional[Dict] = None,
+                         n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
+                         id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                         rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                         device: int = 0, chain=None) -> pd.DataFrame:
+    """The distribution of fitness effects of a library with an honest +-: which fraction of the lineages of an environment, a
+    replicate, a genotype or a user class has a fitness below (above) x, and how sure is that curve?  It cannot be read off the
+    `fitness_marginals` rows: every fitness of a replicate is measured against the same population mean fitness, whose uncertainty
+    moves the whole curve left or right together -- the coupling mean-field q has cut, and the other side of `fitness_contrasts`'
+    argument: there the common mode cancels, here it adds up over the set.  Per joint draw of everything else the units' exact
+    Gaussian conditionals give the expected fraction below x and its (Poisson-binomial) variance; `bb_dfe_rb` averages both over
+    the draws in one device call.
+
+    `by`: one set of fitness units (the rows of `fitness_marginals`) per "rep_env" (replicate, environment), "env" (over the
+    replicates), "rep" (over the environments), "genotype" (a genotype's mutants, every replicate and environment; needs
+    `genotype_col`) or "all".  `groups`: a dict mutant label -> class; every set is then split by class and mutants it does not name
+    are left out.  `grid`: ascending thresholds x, at most 64; default 32 equally spaced points from min(mean - 3 std) to
+    max(mean + 3 std) over the `bc_fitness` rows of `df_advi`.  The remaining arguments as for `fitness_marginals`.
+
+    Returns one line per (set, grid point): the set's labels `rep`, `env`, `genotype`, `group` (None where the set spans them),
+    `n_units`, `x`, `below_mean`, `above_mean` (the posterior mean of the fraction at or below / above x), `between_sd` (its sd
+    between the draws: what the units share), `within_sd` (sqrt of the mean conditional variance: what each unit's own conditional
+    leaves open), `q_below_mean`, `q_below_sd` (the ECDF of q's own draws at x: mean and sd over the draws), `total_sd` =
+    sqrt(between_sd^2 + within_sd^2), `common_mode` = between_sd / within_sd (above 1: the shared part dominates) and, per
+    probability of `probs`, the quantiles over the draws of the fraction below and above x: below_q2.5, ..., above_q2.5, ..."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    if by not in ("rep_env", "env", "rep", "genotype", "all"):
+        raise BarBayError('by must be "rep_env", "env", "rep", "genotype" or "all"')
+    if grid is None:
+        fit = df_advi[df_advi["vartype"] == "bc_fitness"] if "vartype" in df_advi else df_advi.iloc[:0]
+        if len(fit) == 0:
+            raise BarBayError("df_advi has no bc_fitness rows to span a default grid: give grid=")
+        lo, hi = float((fit["mean"] - 3.0 * fit["std"]).min()), float((fit["mean"] + 3.0 * fit["std"]).max())
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise BarBayError("the bc_fitness rows of df_advi span no finite range: give grid=")
+        grid = np.linspace(lo, hi, 32)
+    grid = np.asarray(grid, dtype=np.float64).reshape(-1)
+    if grid.shape[0] < 1 or grid.shape[0] > 64 or not np.all(np.isfinite(grid)) or not np.all(np.diff(grid) > 0):
+        raise BarBayError("grid must hold 1 to 64 finite, strictly ascending thresholds")
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        R, nb = len(bayes_model.counts), bayes_model.n_bc
+        has_env, envs = _env_labels(arrays, mname, R)
+        E = max(len(envs), 1) if has_env else 1
+        ids = list(arrays.bc_ids)
+        geno = arrays.genotypes if isinstance(arrays.genotypes, list) else None
+        if by == "genotype" and geno is None:
+            raise BarBayError('by="genotype" needs the genotypes of the mutants: give genotype_col=')
+        if by == "env" and not has_env:
+            raise BarBayError(f'by="env" cannot be served by {mname}: it has no environments (by="rep_env", "rep" or "all")')
+        if groups is not None:
+            known = set(ids)
+            unknown = next((k for k in groups if k not in known), None)
+            if unknown is not None:
+                raise BarBayError(f"groups: {unknown!r} is no mutant of the data")
+            if not groups:
+                raise BarBayError("groups names no mutant")
+        sets: Dict = {}                                                # (rep, env, genotype, group) -> units, in unit order
+        for r in range(R):
+            for m in range(nb):
+                if groups is not None and ids[m] not in groups:
+                    continue
+                for x in range(E):
+                    key = (f"R{r + 1}" if by in ("rep_env", "rep") else None,
+                           envs[x] if has_env and by in ("rep_env", "env") else None,
+                           geno[m] if by == "genotype" else None,
+                           groups[ids[m]] if groups is not None else None)
+                    sets.setdefault(key, []).append(x + E * m + E * nb * r)
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        keys = list(sets)
+        res = e.dfe_rb([sets[k] for k in keys], grid, probs=probs, n_samples=n_samples, seed=seed, draws=draws)
+    ns, ng = len(keys), grid.shape[0]
+    out = {name: np.repeat(np.asarray([k[i] for k in keys], dtype=object), ng) for i, name in enumerate(("rep", "env", "genotype", "group"))}
+    out["n_units"] = np.repeat(res["n_units"], ng)
+    out["x"] = np.tile(grid, ns)
+    for k in ("below_mean", "above_mean", "between_sd", "within_sd", "q_below_mean", "q_below_sd"):
+        out[k] = res[k].reshape(-1)
+    out["total_sd"] = np.sqrt(out["between_sd"] ** 2 + out["within_sd"] ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["common_mode"] = out["between_sd"] / out["within_sd"]
+    for side in ("below", "above"):
+        for i, p in enumerate(probs):
+            out[f"{side}_q{100.0 * p:g}"] = res[f"{side}_bands"][:, :, i].reshape(-1)
+    return pd.DataFrame(out)
+
+
 def popmean_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
                       n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), threshold: float = 0.0, seed: int = 0,
                       id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",

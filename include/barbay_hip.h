@@ -658,6 +658,86 @@ typedef struct bb_contrast_out {  /* every pointer may be NULL; [n_contrasts] un
 } bb_contrast_out;
 int bb_contrast_rb(bb_handle* h, const bb_contrast_opts* o, const bb_contrast_out* out);
 
+/* Posterior of the distribution of fitness effects (DFE) of a set of fitness units -- the population-level answer a barcode
+ * experiment is run for: which fraction of a library, an environment, a replicate or a genotype class lies below (above) a fitness
+ * x, and how sure we are of that curve.  No reference counterpart.  It cannot be had from the per-unit marginals: every fitness of
+ * a replicate is measured against the same sbar_t, whose uncertainty moves the whole curve left or right together, and mean-field
+ * q has cut exactly that coupling.  This is bb_contrast_rb's argument on the other side: there the common mode cancels, here it
+ * adds up over the units of the set.
+ *
+ * The fact it rests on is bb_contrast_rb's: given everything else, distinct fitness units are conditionally independent, each
+ * N(m_{u,j}, sd_{u,j}).  Given draw j of the rest, the number of a set's n units at or below x is therefore Poisson-binomial with
+ * mean n L_j and variance n^2 V_j (below), and by the law of total variance the posterior variance of the FRACTION below x is
+ * between_sd^2 + within_sd^2: what the units share (between the draws) and what each unit's own conditional leaves open (within).
+ *
+ * Sets: CSR.  Set c names the units set_idx[set_ptr[c] .. set_ptr[c + 1]) in bb_fitness_rb's numbering (every model kind); at
+ * least one unit, every unit at most once per set (a repeated unit is not independent of itself: V_j would be wrong).
+ * Grid: n_grid (1 .. BB_DFE_MAX_GRID) finite, strictly ascending thresholds x_g.
+ *
+ * Per draw j, a unit's (s_{u,j}, m_{u,j}, sd_{u,j}) are exactly bb_fitness_rb's: the same gamma, the same ln Z by the 256-column
+ * rule, ascending t, the later time point's environment, the n_u = 0 rule, the hierarchical kinds' N(theta_j, tau_j) prior.  Then,
+ * bb_fitness_rb's tails word for word, both through erfc:
+ *   v = (m - x_g) / sd * rsqrt2;   pl = 0.5 erfc(v);   pu = 0.5 erfc(-v);   c = (s <= x_g)
+ * Order of the sums: the set's units, in the caller's order, are cut into chunks of BB_DFE_CHUNK.  A chunk's (SL, SU, SV, SC)
+ * start at 0.0 and take their units' pl, pu, pl pu and c in order (SV = fma(pl, pu, SV): the product is not rounded on its own);
+ * the set's sums start at 0.0 and take the chunks in chunk order.  With n the set's size:
+ *   L_j = SL / n    U_j = SU / n    V_j = SV / (n n)    C_j = SC / n
+ * Outputs per (set, grid point), every sum over j in bb_ppc_score's reduction order, divisor n_samples:
+ *   below_mean, above_mean   mean_j L_j, mean_j U_j: the posterior mean of the fraction at or below (above) x_g
+ *   between_sd               sqrt(mean_j (L_j - below_mean)^2), two-pass, centred
+ *   within_sd                sqrt(mean_j V_j)
+ *   q_below_mean, q_below_sd the same two of C_j: what q's own draws say by themselves (the ECDF of the draws)
+ *   below_bands, above_bands the probs quantiles over j of L_j and of U_j, by the rule of bb_ppc_bands (StatsBase.quantile, type 7:
+ *                            order statistics by selection, a + gamma (b - a)); n_quantiles > 0 needs n_samples >= 2
+ *   n_units [n_sets]         the sets' sizes
+ * total variance of the fraction: between_sd^2 + within_sd^2; between_sd / within_sd > 1 says the shared part dominates.
+ * A non-finite parameter makes the eight Rao-Blackwellised outputs of the sets that name a unit using it NaN (q_below_* stay what
+ * the comparison gives); it disturbs no other set and is not an error.
+ *
+ * Options: n_samples, n_quantiles, probs, seed and draws are bb_rb_opts' exactly (the keying included: at equal seed the draws are
+ * bb_fitness_rb's; n_samples = 1 is allowed with draws and no quantiles).  BB_DFE_MAX_SAMPLES: one workgroup holds the column of
+ * L_j, then of U_j -- one after the other, not both -- in LDS beside the selection's histograms; both at once would cap at 7572.
+ * reserved0: 0.  (Tests: a positive value bounds the chunk partials in flight to that many [4][n_samples] tables in place of
+ * 256 MiB; no result depends on it.)
+ *
+ * Cost: units x draws x grid points x 2 erfc, and a unit's loglambda row walked once per draw and group of 8 grid points.  The
+ * chunk partials [chunks][grid points][4][n_samples] in flight are bounded to 256 MiB by working (sets x grid points) in slabs.
+ *
+ * A cell's results are a function of the handle's (mu, sigma) (or the supplied draws), the priors, geno_idx, the set's own units
+ * in their order, x_g, n_samples, seed and probs: bit-identical whatever the other sets and grid points of the call, their number
+ * or order, the slabs, the launch grid, the launch mode, the device count or the calls made before.  (Permuting the units within a
+ * set reorders floating-point sums and may change low bits.)  No atomics on doubles.  The handle's mu, omega, optimiser state,
+ * step counter and RNG position are untouched, bitwise.
+ * BB_ERR_INVALID: a null h, o or out; the probs / n_quantiles errors of bb_fitness_rb; n_grid outside 1 .. BB_DFE_MAX_GRID; a
+ * null, non-finite or not strictly ascending grid; reserved0 < 0; n_sets < 0; with n_sets > 0 a null set_ptr or set_idx,
+ * set_ptr[0] != 0 or a decreasing set_ptr, an empty set, an index outside the units, a unit named twice in one set.
+ * BB_ERR_UNSUPPORTED: n_samples outside its range; n_quantiles > 0 with one draw; more than 2^31 - 1 indices.  The message
+ * (bb_last_error) names the set and the position within it, both 0-based.  n_sets == 0 is BB_OK and writes nothing.  Multi-device
+ * and sharded handles: as bb_ppc_bands.  Out of scope: quantiles of the DFE itself (invert below_mean along the grid), the set
+ * mean (a bb_contrast_rb with weights 1 / n), sets over theta. */
+#define BB_DFE_CHUNK 128          /* units per partial sum of a set                        */
+#define BB_DFE_MAX_GRID 64
+#define BB_DFE_MAX_SAMPLES 8672   /* <= BB_RB_MAX_SAMPLES                                  */
+typedef struct bb_dfe_opts {
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_DFE_MAX_SAMPLES       */
+    int32_t n_quantiles;      /* 0 .. 8                                                */
+    int32_t n_grid;           /* 1 .. BB_DFE_MAX_GRID                                  */
+    int32_t reserved0;        /* 0                                                     */
+    const double* probs;      /* [n_quantiles], in (0, 1): quantiles over the draws    */
+    const double* grid;       /* [n_grid] finite, strictly ascending thresholds x_g    */
+    uint64_t seed;            /* Philox key (draws == NULL)                            */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL   */
+    int64_t n_sets;
+    const int64_t* set_ptr;   /* [n_sets + 1], CSR, set_ptr[0] == 0, increasing        */
+    const int64_t* set_idx;   /* [set_ptr[n_sets]] units of bb_fitness_rb              */
+} bb_dfe_opts;
+typedef struct bb_dfe_out {   /* every pointer may be NULL; [n_sets][n_grid] unless noted */
+    double *below_mean, *above_mean, *between_sd, *within_sd, *q_below_mean, *q_below_sd;
+    double *below_bands, *above_bands;           /* [n_sets][n_grid][n_quantiles]      */
+    int64_t* n_units;                            /* [n_sets]                           */
+} bb_dfe_out;
+int bb_dfe_rb(bb_handle* h, const bb_dfe_opts* o, const bb_dfe_out* out);
+
 /* Rao-Blackwellised marginals of the population mean fitness sbar_t -- the pop_mean_fitness rows of a fit, the quantity every
  * reported mutant fitness is relative to, and the one latent that every barcode's log-frequency-ratio term reads: q factorises it
  * away from all of them.  No reference counterpart.  sbar_g enters the log-joint through its Gaussian prior (s_pop_prior, Vector or

@@ -486,6 +486,73 @@ function contrast_rb(h::Ptr{Cvoid}, terms::Vector{<:Vector{<:Pair}}; space::Symb
     return (min_steps=min_steps, q_mean=q_mean, q_sd=q_sd, rb_mean=rb_mean, rb_sd=rb_sd, p_pos=p_pos, p_neg=p_neg, quantiles=quantiles)
 end
 
+# Posterior of the distribution of fitness effects of sets of fitness units (bb_dfe_rb, include/barbay_hip.h): per set and
+# threshold x the fraction of the set's units at or below (above) x, the units' exact Gaussian conditionals averaged over the draws
+# of `fitness_rb`, so that what the units share -- the population mean fitness above all -- moves the whole curve draw by draw.
+# Field for field the Python binding's `bb_dfe_opts` / `bb_dfe_out` (barbay.jl_amd/_capi.py).  Like the rest of this file it
+# remains unexecuted.
+const BB_DFE_CHUNK = 128
+const BB_DFE_MAX_GRID = 64
+const BB_DFE_MAX_SAMPLES = 8672
+struct bb_dfe_opts
+    n_samples::Int32
+    n_quantiles::Int32
+    n_grid::Int32
+    reserved0::Int32
+    probs::Ptr{Float64}
+    grid::Ptr{Float64}
+    seed::UInt64
+    draws::Ptr{Float64}
+    n_sets::Int64
+    set_ptr::Ptr{Int64}
+    set_idx::Ptr{Int64}
+end
+struct bb_dfe_out
+    below_mean::Ptr{Float64}
+    above_mean::Ptr{Float64}
+    between_sd::Ptr{Float64}
+    within_sd::Ptr{Float64}
+    q_below_mean::Ptr{Float64}
+    q_below_sd::Ptr{Float64}
+    below_bands::Ptr{Float64}
+    above_bands::Ptr{Float64}
+    n_units::Ptr{Int64}
+end
+
+"""
+    dfe_rb(h, sets, grid; probs=[0.025, 0.5, 0.975], n_samples=1000, seed=0, draws=nothing) -> NamedTuple
+
+`h` a live `bb_handle`.  `sets`: a vector of sets, each a vector of 0-based unit numbers of `fitness_rb`, every unit at most once
+per set; `grid`: finite, strictly ascending thresholds, at most `BB_DFE_MAX_GRID`.  Returns `below_mean, above_mean, between_sd,
+within_sd, q_below_mean, q_below_sd` (n_grid x n_sets), `below_bands, above_bands` (length(probs) x n_grid x n_sets) and `n_units`
+(one per set).  The total variance of the fraction below a threshold is `between_sd^2 + within_sd^2`.  The remaining arguments as
+for `fitness_rb`.
+"""
+function dfe_rb(h::Ptr{Cvoid}, sets::Vector{<:Vector{<:Integer}}, grid::Vector{Float64}; probs::Vector{Float64}=[0.025, 0.5, 0.975],
+                n_samples::Int=1000, seed::Integer=0, draws::Union{Nothing,Matrix{Float64}}=nothing)
+    nc, ng, nq = length(sets), length(grid), length(probs)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("dfe_rb: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    set_ptr = Int64.(cumsum(vcat(0, length.(sets))))
+    set_idx = Int64[u for s in sets for u in s]
+    below_mean, above_mean, between_sd, within_sd, q_below_mean, q_below_sd = (Matrix{Float64}(undef, ng, nc) for _ in 1:6)
+    below_bands, above_bands = (Array{Float64,3}(undef, nq, ng, nc) for _ in 1:2)
+    n_units = Vector{Int64}(undef, nc)
+    GC.@preserve probs grid draws set_ptr set_idx below_mean above_mean between_sd within_sd q_below_mean q_below_sd below_bands above_bands n_units begin
+        o = bb_dfe_opts(Int32(n_samples), Int32(nq), Int32(ng), Int32(0), nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL), pointer(grid),
+                        UInt64(seed), draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws), Int64(nc), pointer(set_ptr), pointer(set_idx))
+        out = bb_dfe_out(pointer(below_mean), pointer(above_mean), pointer(between_sd), pointer(within_sd), pointer(q_below_mean),
+                         pointer(q_below_sd), nq > 0 ? pointer(below_bands) : Ptr{Float64}(C_NULL),
+                         nq > 0 ? pointer(above_bands) : Ptr{Float64}(C_NULL), pointer(n_units))
+        check(ccall((:bb_dfe_rb, LIB), Cint, (Ptr{Cvoid}, Ref{bb_dfe_opts}, Ref{bb_dfe_out}), h, o, out))
+    end
+    return (n_units=n_units, below_mean=below_mean, above_mean=above_mean, between_sd=between_sd, within_sd=within_sd,
+            q_below_mean=q_below_mean, q_below_sd=q_below_sd, below_bands=below_bands, above_bands=above_bands)
+end
+
 # Rao-Blackwellised marginals of the population mean fitness sbar_g, g = (replicate, step) (bb_popmean_rb, include/barbay_hip.h):
 # the exact Gaussian full conditional of a step's population mean, summed over every barcode of the replicate (neutrals, then
 # mutants) and averaged over the draws of `fitness_rb`.  Field for field the Python binding's `bb_popmean_rb_out`
