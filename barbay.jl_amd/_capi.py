@@ -47,7 +47,7 @@ EXPORTS = [
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
-    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_chain_summary",
+    "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_loo_shape", "bb_ppc_loo", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_dfe_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
     "bb_logsigma_rb_shape", "bb_logsigma_rb", "bb_logtau_rb_shape", "bb_logtau_rb",
     "bb_loglambda_rb_shape", "bb_loglambda_rb",
@@ -129,6 +129,19 @@ SCORE_ROWS = ("row_lpd", "row_p_waic")
 
 class bb_score_out(C.Structure):
     _fields_ = [(k, _dp) for k in SCORE_CELLS + SCORE_ROWS] + [("n_scored", C.POINTER(C.c_int32))]
+
+
+class bb_loo_opts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64)]
+
+
+BB_LOO_MAX_SAMPLES = 8192
+LOO_CELLS = ("elpd_loo", "p_loo", "khat", "n_eff", "lpd")
+LOO_ROWS = ("row_elpd_loo", "row_p_loo", "row_khat", "row_n_eff", "row_elpd_cells", "row_khat_max")
+
+
+class bb_loo_out(C.Structure):
+    _fields_ = [(k, _dp) for k in LOO_CELLS + LOO_ROWS] + [("n_scored", C.POINTER(C.c_int32))]
 
 
 RB_UNITS = ("q_mean", "q_sd", "rb_mean", "rb_sd", "p_pos", "p_neg")
@@ -317,6 +330,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "bb_ppc_score"):
         lib.bb_score_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.bb_ppc_score.argtypes = [vp, C.POINTER(bb_score_opts), C.POINTER(bb_score_out)]
+    if hasattr(lib, "bb_ppc_loo"):
+        lib.bb_loo_shape.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.bb_ppc_loo.argtypes = [vp, C.POINTER(bb_loo_opts), C.POINTER(bb_loo_out)]
     if hasattr(lib, "bb_fitness_rb"):
         lib.bb_fitness_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_fitness_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_rb_out)]
@@ -702,6 +718,31 @@ class Engine:
             setattr(out, k, _ptr(res[k]))
         out.n_scored = res["n_scored"].ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.bb_ppc_score(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def loo_shape(self) -> Tuple[int, int]:
+        """(n_rows, n_steps) of `ppc_loo`: those of `ppc_score`."""
+        n, t = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.bb_loo_shape(self._h, C.byref(n), C.byref(t)))
+        return int(n.value), int(t.value)
+
+    def ppc_loo(self, n_samples: int = 1000, seed: int = 0) -> Dict[str, np.ndarray]:
+        """Pareto-smoothed importance-sampling leave-one-out scores of every observed log-frequency ratio (`bb_ppc_loo`), on the
+        draws and log densities of `ppc_score`.  Returns elpd_loo, p_loo, khat, n_eff, lpd, each [n_rows, n_steps] (NaN: no such
+        step, or a zero count; khat = +Inf: too few draws, or too light a tail, to smooth), the barcode's whole trajectory left
+        out: row_elpd_loo, row_p_loo, row_khat, row_n_eff, and row_elpd_cells, row_khat_max, n_scored (int32), each [n_rows].
+        n_samples <= 8192."""
+        n_rows, n_steps = self.loo_shape()
+        o = bb_loo_opts()
+        o.n_samples, o.seed = int(n_samples), int(seed)
+        res = {k: np.empty((n_rows, n_steps)) for k in LOO_CELLS}
+        res.update({k: np.empty(n_rows) for k in LOO_ROWS})
+        res["n_scored"] = np.empty(n_rows, dtype=np.int32)
+        out = bb_loo_out()
+        for k in LOO_CELLS + LOO_ROWS:
+            setattr(out, k, _ptr(res[k]))
+        out.n_scored = res["n_scored"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_ppc_loo(self._h, C.byref(o), C.byref(out)))
         return res
 
     def fitness_rb_shape(self) -> int:

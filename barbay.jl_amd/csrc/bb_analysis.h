@@ -1,5 +1,5 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
-// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
+// bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_ppc_loo (bb_loo.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
 // bb_contrast_rb (bb_contrast.h), bb_dfe_rb (bb_dfe.h), bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
@@ -446,7 +446,7 @@ extern "C" int bb_freq_bands(bb_handle* h, const bb_freq_opts* o, double* bands,
     });
 }
 
-// Phase times of a call (diagnostics, tools/*_rate.py: -DBB_SCORE_TIMES, -DBB_RB_TIMES, -DBB_LLRB_TIMES, -DBB_CHAIN_TIMES, -DBB_TRACE_TIMES): lap(i, into) drains the
+// Phase times of a call (diagnostics, tools/*_rate.py: -DBB_SCORE_TIMES, -DBB_LOO_TIMES, -DBB_RB_TIMES, -DBB_LLRB_TIMES, -DBB_CHAIN_TIMES, -DBB_TRACE_TIMES): lap(i, into) drains the
 // stream, stamps ct[i] and adds the time since ct[i - 1] to ms[into] (into < 0: the stamp alone).  ON == false: nothing at all.
 template <bool ON>
 struct PhaseTimes {
@@ -549,6 +549,73 @@ extern "C" int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score
     pt.lap(5, 4);
 #ifdef BB_SCORE_TIMES
     fprintf(stderr, "[bb_ppc_score %lld x %d, %d samples] observed %.3f ms, upload %.3f ms, pop %.3f ms, score %.3f ms, download %.3f ms\n", n_rows, n_steps, (int)o->n_samples, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
+#endif
+    return rc;
+}
+
+// ---- PSIS leave-one-out predictive scores of the observed ratios (bb_loo.h), in bb_ppc_score's frame ---------------------------------
+static_assert(BB_LOO_MAX_SAMPLES == BB_LOO_NSAMP_CAP && 2 * BB_LOO_MAX_SAMPLES == BB_SCORE_MAX_SAMPLES, "bb_ppc_loo limits");
+#ifdef BB_LOO_TIMES
+typedef PhaseTimes<true> LooTimes;
+#else
+typedef PhaseTimes<false> LooTimes;
+#endif
+extern "C" int bb_loo_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps) { return bb_score_shape(h, n_rows, n_steps); }
+
+extern "C" int bb_ppc_loo(bb_handle* h, const bb_loo_opts* o, const bb_loo_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    if (o->n_samples < 2 || o->n_samples > BB_LOO_MAX_SAMPLES) return bb_fail(BB_ERR_UNSUPPORTED, "n_samples must be in 2..%d", BB_LOO_MAX_SAMPLES);
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    LooArgs A;
+    memset(&A, 0, sizeof A);
+    PpcArgs& P = A.P;
+    const long long n_rows = (long long)M.R * M.B;
+    const int n_steps = ppc_steps(h);
+    const double no_band = 0.0;              // (the shared prologue plans one band; nothing selects here)
+    int rc = bands_prologue(h, o->n_samples, 1, 1, &no_band, o->seed, n_rows, n_steps, P, B);
+    if (rc) return rc;
+    B.nbands = 0;
+    A.B = M.B;
+    A.nn = M.nn;
+    LooTimes pt{dh->stream};     // tools/ppc_loo_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
+    // the observed ratios, formed exactly as bb_ppc_score forms them; NaN: a zero count, or no such step
+    const size_t ncell = (size_t)n_rows * n_steps;
+    std::vector<double> y(ncell, (double)NAN);
+    rc = observed_walk(h, B, P, &no_band, nullptr, [&](int r, int T, long long col, const unsigned* c, const double* n, auto&) {
+        double* yr = y.data() + ((size_t)r * M.B + col) * n_steps;
+        for (int t = 0; t + 1 < T; ++t)
+            if (c[t] && c[t + 1]) yr[t] = log((double)c[t + 1] / n[t + 1]) - log((double)c[t] / n[t]);
+    });
+    if (rc) return rc;
+    pt.lap(1, 0);
+    double* dy = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(dy, ncell);                                  // [n_rows][n_steps]
+        c(A.cell, BB_LOO_CELLS * ncell);               // [5][n_rows][n_steps]
+        c(A.rowv, BB_LOO_ROWS * (size_t)n_rows);       // [6][n_rows]
+        c(A.n_scored, ((size_t)n_rows + 1) / 2);       // [n_rows] ints
+    });
+    if (rc || (rc = h2d(dy, y.data(), ncell * 8, dh->stream))) return rc;
+    A.y = dy;
+    pt.lap(2, 1);
+    if ((rc = launch(dh->stream, k_ppc_pop, B.npop, 256, 0, P))) return rc;
+    pt.lap(3, 2);
+    if ((rc = launch(dh->stream, k_loo, (int)B.nblk, BB_SCORE_NT, (size_t)BB_LOO_LDS_DOUBLES(P.n_samples), A))) return rc;
+    pt.lap(4, 3);
+    double* cells[BB_LOO_CELLS] = {out->elpd_loo, out->p_loo, out->khat, out->n_eff, out->lpd};
+    for (int k = 0; k < BB_LOO_CELLS; ++k)
+        if (cells[k] && (rc = d2h(cells[k], A.cell + (size_t)k * ncell, ncell * 8, dh->stream))) return rc;
+    double* rows[BB_LOO_ROWS] = {out->row_elpd_loo, out->row_p_loo, out->row_khat, out->row_n_eff, out->row_elpd_cells, out->row_khat_max};
+    for (int k = 0; k < BB_LOO_ROWS; ++k)
+        if (rows[k] && (rc = d2h(rows[k], A.rowv + (size_t)k * n_rows, (size_t)n_rows * 8, dh->stream))) return rc;
+    if (out->n_scored && (rc = d2h(out->n_scored, A.n_scored, (size_t)n_rows * 4, dh->stream))) return rc;
+    rc = dsync(dh->stream);
+    pt.lap(5, 4);
+#ifdef BB_LOO_TIMES
+    fprintf(stderr, "[bb_ppc_loo %lld x %d, %d samples] observed %.3f ms, upload %.3f ms, pop %.3f ms, loo %.3f ms, download %.3f ms\n", n_rows, n_steps, (int)o->n_samples, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4]);
 #endif
     return rc;
 }

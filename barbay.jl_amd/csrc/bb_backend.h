@@ -409,6 +409,10 @@ BB_KERNEL(BB_SCORE_NT, k_score, ScoreArgs A) {
     BB_CTX;
     bb_block_score(cx, A, BB_GRID);
 }
+BB_KERNEL(BB_SCORE_NT, k_loo, LooArgs A) {
+    BB_CTX;
+    bb_block_loo(cx, A, BB_GRID);
+}
 BB_KERNEL(256, k_rb_logz, RbArgs A) {
     BB_CTX;
     bb_block_rb_logz(cx, A, BB_GRID);

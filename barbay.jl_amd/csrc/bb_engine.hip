@@ -19,6 +19,7 @@
 #include "bb_ppc.h"
 #include "bb_freq.h"
 #include "bb_score.h"
+#include "bb_loo.h"
 #include "bb_rb.h"
 #include "bb_contrast.h"
 #include "bb_dfe.h"

@@ -18,6 +18,9 @@ The posterior-predictive checks of the reference's guide ("Validating the infere
     logfreq_ratio_ppc_scores, pit_histogram                       the log predictive density and PIT of every observed ratio, the
                                                                   draws averaged in closed form (`bb_ppc_score`), and the calibration
                                                                   histogram of the PITs (no reference counterpart)
+    logfreq_ratio_loo, loo_compare                                Pareto-smoothed leave-one-out scores per barcode with the khat
+                                                                  diagnostic (`bb_ppc_loo`), and the paired comparison of two fits
+                                                                  (no reference counterpart)
     fitness_marginals                                             the Rao-Blackwellised marginal of every mutant's fitness beside the
                                                                   mean-field one (`bb_fitness_rb`): how far the fit's +- can be trusted
                                                                   (no reference counterpart)
@@ -418,6 +421,77 @@ def logfreq_ratio_ppc_scores(data: pd.DataFrame, df_advi: pd.DataFrame, *, model
     out["row_lpd"] = res["row_lpd"][rr]
     out["n_scored"] = res["n_scored"][rr]
     return pd.DataFrame(out)
+
+
+def logfreq_ratio_loo(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,
+                      n_samples: int = 1000, seed: int = 0,
+                      id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                      rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                      device: int = 0) -> pd.DataFrame:
+    """Which barcodes does the fit lean on too hard, and how well would it have predicted each one had it not seen it?  Pareto-
+    smoothed importance-sampling leave-one-out (PSIS-LOO; Vehtari, Gelman, Gabry 2017) on the draws and log densities of
+    `logfreq_ratio_ppc_scores`, in one device call (`bb_ppc_loo`), a barcode's whole trajectory left out at a time.
+    `df_advi` as for `logfreq_ratio_ppc_bands`; n_samples <= 8192.
+
+    Returns one line per barcode and replicate, labelled as `logfreq_ratio_ppc_scores` labels them (`id`, `neutral`, `rep`):
+    `elpd_loo` (the log predictive density of the barcode's scored ratios, jointly, under the fit without them: what
+    `loo_compare` sums), `p_loo` (in-sample minus leave-one-out: the effective number of parameters the barcode takes up), `khat`
+    (the fitted shape of the importance ratios' tail; +Inf: not fitted, too few draws or ratios beyond the range of exp),
+    `n_eff` (the effective number of draws behind the estimate), `khat_max_cell` (the largest khat when a single ratio of the
+    barcode is left out), `n_scored`, and `flag`: khat above min(1 - 1 / log10(n_samples), 0.7) (Vehtari et al. 2024) -- the
+    estimate for that barcode is unreliable and the fit depends on it unduly; a barcode without a scored step (NaN) is not flagged.
+    `.attrs`: "elpd_loo" (the total over the scored barcodes), "se" (sqrt(N var) of the N per-barcode values), "p_loo",
+    "n_flagged" and "khat_threshold"."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        res = e.ppc_loo(n_samples=n_samples, seed=seed)
+    n_rows = res["row_elpd_loo"].shape[0]
+    R, nn = len(bayes_model.counts), arrays.n_neutral
+    B = n_rows // R
+    ids = np.asarray(list(arrays.neutral_ids) + list(arrays.bc_ids), dtype=object)      # the data columns: neutrals first
+    row = np.arange(n_rows)
+    rep, col = row // B, row % B
+    thr = min(1.0 - 1.0 / math.log10(n_samples), 0.7)
+    out = pd.DataFrame({
+        "id": ids[col],
+        "neutral": col < nn,
+        "rep": [f"R{r + 1}" for r in rep],
+        "elpd_loo": res["row_elpd_loo"],
+        "p_loo": res["row_p_loo"],
+        "khat": res["row_khat"],
+        "n_eff": res["row_n_eff"],
+        "khat_max_cell": res["row_khat_max"],
+        "n_scored": res["n_scored"],
+        "flag": res["row_khat"] > thr,
+    })
+    ok = res["n_scored"] > 0
+    v = res["row_elpd_loo"][ok]
+    out.attrs.update({"elpd_loo": float(v.sum()), "se": float(math.sqrt(len(v) * v.var(ddof=1))) if len(v) > 1 else float("nan"),
+                      "p_loo": float(res["row_p_loo"][ok].sum()), "n_flagged": int(out["flag"].sum()), "khat_threshold": thr})
+    return out
+
+
+def loo_compare(a: pd.DataFrame, b: pd.DataFrame, top: int = 10) -> Dict:
+    """Which of two fits predicts the data better?  `a`, `b`: frames of `logfreq_ratio_loo` over the same barcodes (two models, or
+    two settings, on the same data); raises `BarBayError` if their row labels (`id`, `rep`) differ.  The comparison is paired:
+    d_i = elpd_loo(b)_i - elpd_loo(a)_i per barcode, over the barcodes scored in both.  Returns a dict: "elpd_diff" = sum d_i
+    (positive: b predicts better), "se_diff" = sqrt(N var d), "n" = N, "n_flagged" (barcodes flagged in either frame: their d_i are
+    not to be trusted) and "rows": the `top` barcodes with the largest |d_i|, the ones that drive the difference (`id`, `rep`,
+    `elpd_a`, `elpd_b`, `elpd_diff`, `flag`)."""
+    keys = ["id", "rep"]
+    if len(a) != len(b) or any(list(a[k]) != list(b[k]) for k in keys):
+        raise BarBayError("loo_compare: the two frames do not have the same rows (id, rep)")
+    ea, eb = a["elpd_loo"].to_numpy(dtype=np.float64), b["elpd_loo"].to_numpy(dtype=np.float64)
+    ok = ~(np.isnan(ea) | np.isnan(eb))
+    d = eb[ok] - ea[ok]
+    n = int(ok.sum())
+    flag = (a["flag"].to_numpy(dtype=bool) | b["flag"].to_numpy(dtype=bool))[ok]
+    rows = pd.DataFrame({"id": a["id"].to_numpy()[ok], "rep": a["rep"].to_numpy()[ok], "elpd_a": ea[ok], "elpd_b": eb[ok],
+                         "elpd_diff": d, "flag": flag})
+    rows = rows.iloc[np.argsort(-np.abs(d), kind="stable")[:top]].reset_index(drop=True)
+    return {"elpd_diff": float(d.sum()), "se_diff": float(math.sqrt(n * d.var(ddof=1))) if n > 1 else float("nan"), "n": n,
+            "n_flagged": int(flag.sum()), "rows": rows}
 
 
 def fitness_marginals(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, model_kwargs: Optional[Dict] = None,

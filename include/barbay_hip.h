@@ -448,6 +448,65 @@ typedef struct bb_score_out {     /* every pointer may be NULL                  
 int bb_score_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps);
 int bb_ppc_score(bb_handle* h, const bb_score_opts* o, const bb_score_out* out);
 
+/* Pareto-smoothed importance-sampling leave-one-out (PSIS-LOO) predictive scores of the observed log-frequency ratios: what the
+ * fit would have predicted for an observation had it not seen it, and a diagnostic khat per observation that says where that
+ * estimate (and the fit) leans on one observation too hard -- which bb_ppc_score's in-sample lpd and p_waic cannot tell.  Vehtari,
+ * Gelman, Gabry 2017; Vehtari et al. 2024; the generalised Pareto fit is Zhang and Stephens 2009, as the loo package's gpdfit.  No
+ * reference counterpart.
+ *
+ * Rows, steps (bb_loo_shape == bb_score_shape), observed ratios y, draws j < n = n_samples and the log densities l_j of a scored
+ * cell are exactly bb_ppc_score's; an unscored cell is NaN in every output.  At equal seed and n_samples lpd is bb_ppc_score's
+ * lpd, byte for byte.
+ *
+ * PSIS(l), l_j finite:
+ *   1  a_j = -l_j, A = max_j a_j, r_j = a_j - A <= 0.
+ *   2  M = min(floor(n / 5), c), c the smallest integer with c^2 >= 9 n (ceil(3 sqrt n) in integers; r_eff = 1: q's draws are
+ *      independent).
+ *   3  The draws ordered by (r_j, j) ascending: rho_1 <= ... <= rho_M the M largest, c the largest not among them (order
+ *      statistic n - M).
+ *   4  The tail is smoothed iff M >= 5 and c >= -690 and x* > 0, where x_i = exp(rho_i) - exp(c), x* = x_{floor(M / 4 + 1 / 2)}
+ *      (= x_{(M + 2) / 4} in integers).  Otherwise the weights stay raw and khat = +Inf.  (-690 keeps the decision off exp's
+ *      underflow: a 50-digit evaluation and a double decide alike.)
+ *   5  m = 30 + floor(sqrt M);  theta_i = 1 / x_M + (1 - sqrt(m / (i - 1/2))) / (3 x*), i = 1 .. m;
+ *      kappa(theta) = (sum_{k = 1 .. M} log1p(-theta x_k)) / M;  L_i = M ((log(-theta_i / kappa(theta_i)) - kappa(theta_i)) - 1);
+ *      w_i = 1 / sum_{j = 1 .. m} exp(L_j - L_i);  theta^ = sum_i theta_i w_i;  k_raw = kappa(theta^);  sigma^ = -k_raw / theta^;
+ *      khat = (M k_raw + 5) / (M + 10).
+ *   6  The draw of tail rank i gets lw = min(log(sigma^ expm1(-khat log1p(-p_i)) / khat + exp(c)), 0), p_i = (i - 1/2) / M (the
+ *      minimum as "v > 0 ? 0 : v": a NaN stays); every other draw keeps lw_j = r_j.
+ *   7  elpd_loo = LSE_j(lw_j + l_j) - LSE_j(lw_j), LSE(v) = max v + log sum_j exp(v_j - max v);
+ *      n_eff = 1 / sum_j wt_j^2, wt_j = exp(lw_j - LSE(lw));  lpd = LSE(l) - log n as bb_ppc_score forms it;
+ *      p_loo = lpd - elpd_loo;  khat.
+ *   8  A non-finite l_j makes elpd_loo, p_loo, khat and n_eff of that cell NaN and disturbs no other cell; lpd is then what
+ *      bb_ppc_score gives (NaN where an l_j is NaN or +Inf).  Anything else non-finite inside the fit propagates by IEEE rules.
+ * Order of the sums: every sum and maximum over j in bb_ppc_score's reduction order; every sum over the tail (k) or the theta grid
+ * (i, j) starts from its first term and adds the others in ascending index.  No atomics on doubles.
+ *
+ * Per cell (one observation left out), [n_rows][n_steps]: elpd_loo, p_loo, khat, n_eff, lpd = PSIS of the cell's l.
+ * Per row (a barcode's whole trajectory left out), [n_rows]: row_elpd_loo, row_p_loo, row_khat, row_n_eff = PSIS of
+ *   l^row_j = the sum over the row's scored steps, in step order, of l_{t,j} (row_p_loo against the log-mean-exp of l^row) -- "would
+ *   the model have predicted this lineage?", the number model comparison should sum; row_elpd_cells = the sum of the cells'
+ *   elpd_loo in step order; row_khat_max = the largest of the cells' khat (a NaN stays); n_scored.  A row without a scored cell has
+ *   NaN in all six and n_scored = 0; a row with one scored cell has row_* equal to that cell's, byte for byte.
+ *
+ * Results are a function of y, the handle's (mu, sigma), n_samples and seed alone, bit-identical whatever the grid, the launch mode,
+ * the handle's internal latent order, the device count or the calls made on the handle before.  The handle's mu, omega, optimiser
+ * state, step counter and RNG position are untouched, bitwise.  BB_ERR_INVALID: a null h, o or out; BB_ERR_UNSUPPORTED: n_samples
+ * outside 2 .. BB_LOO_MAX_SAMPLES (a cell's l and lw both in LDS: half of bb_ppc_score's cap).  Multi-device and sharded handles as
+ * bb_ppc_score. */
+#define BB_LOO_MAX_SAMPLES 8192
+typedef struct bb_loo_opts {
+    int32_t n_samples;        /* posterior samples j, 2 .. BB_LOO_MAX_SAMPLES          */
+    int32_t reserved0;
+    uint64_t seed;            /* Philox key                                            */
+} bb_loo_opts;
+typedef struct bb_loo_out {       /* every pointer may be NULL                         */
+    double *elpd_loo, *p_loo, *khat, *n_eff, *lpd;                                /* [n_rows][n_steps] */
+    double *row_elpd_loo, *row_p_loo, *row_khat, *row_n_eff, *row_elpd_cells, *row_khat_max;      /* [n_rows] */
+    int32_t* n_scored;        /* [n_rows]                                              */
+} bb_loo_out;
+int bb_loo_shape(const bb_handle* h, int64_t* n_rows, int32_t* n_steps);
+int bb_ppc_loo(bb_handle* h, const bb_loo_opts* o, const bb_loo_out* out);
+
 /* Rao-Blackwellised (RB) marginals of the mutants' fitness -- how far the "+-" of the mean-field posterior can be trusted, per
  * mutant.  No reference counterpart.  Given everything else, a mutant's fitness enters the log-joint only through a Gaussian prior
  * and Gaussian log-frequency-ratio terms (model_fitness_normal.jl:262-270 and its four siblings), so its full conditional is

@@ -296,6 +296,55 @@ function ppc_score(h::Ptr{Cvoid}; n_samples::Int=1000, seed::Integer=0)
             row_lpd=row_lpd, row_p_waic=row_p_waic, n_scored=n_scored)
 end
 
+# Pareto-smoothed importance-sampling leave-one-out scores of the observed log-frequency ratios (bb_ppc_loo, include/barbay_hip.h),
+# per cell and per barcode, with the khat diagnostic.  Field for field the Python binding's `bb_loo_opts` / `bb_loo_out`
+# (barbay.jl_amd/_capi.py).  Like the rest of this file it remains unexecuted (no `julia` where this repository is built and tested).
+const BB_LOO_MAX_SAMPLES = 8192
+struct bb_loo_opts
+    n_samples::Int32
+    reserved0::Int32
+    seed::UInt64
+end
+struct bb_loo_out
+    elpd_loo::Ptr{Float64}
+    p_loo::Ptr{Float64}
+    khat::Ptr{Float64}
+    n_eff::Ptr{Float64}
+    lpd::Ptr{Float64}
+    row_elpd_loo::Ptr{Float64}
+    row_p_loo::Ptr{Float64}
+    row_khat::Ptr{Float64}
+    row_n_eff::Ptr{Float64}
+    row_elpd_cells::Ptr{Float64}
+    row_khat_max::Ptr{Float64}
+    n_scored::Ptr{Int32}
+end
+
+"""
+    ppc_loo(h; n_samples=1000, seed=0) -> NamedTuple
+
+`h` a live `bb_handle`.  Returns `elpd_loo, p_loo, khat, n_eff, lpd` (each n_steps x n_rows: Julia order of the C array [row][t];
+NaN where the cell is unscored; khat = Inf where the tail was not smoothed) and, the barcode's whole trajectory left out,
+`row_elpd_loo, row_p_loo, row_khat, row_n_eff`, with `row_elpd_cells, row_khat_max, n_scored` (n_rows each); rows and draws as
+`ppc_score`, whose `lpd` this call's `lpd` equals byte for byte at equal seed; 2 <= n_samples <= BB_LOO_MAX_SAMPLES.
+"""
+function ppc_loo(h::Ptr{Cvoid}; n_samples::Int=1000, seed::Integer=0)
+    nr, nt = Ref{Int64}(0), Ref{Int32}(0)
+    check(ccall((:bb_loo_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}), h, nr, nt))
+    elpd_loo, p_loo, khat, n_eff, lpd = (Matrix{Float64}(undef, nt[], nr[]) for _ in 1:5)
+    row_elpd_loo, row_p_loo, row_khat, row_n_eff, row_elpd_cells, row_khat_max = (Vector{Float64}(undef, nr[]) for _ in 1:6)
+    n_scored = Vector{Int32}(undef, nr[])
+    GC.@preserve elpd_loo p_loo khat n_eff lpd row_elpd_loo row_p_loo row_khat row_n_eff row_elpd_cells row_khat_max n_scored begin
+        o = bb_loo_opts(Int32(n_samples), Int32(0), UInt64(seed))
+        out = bb_loo_out(pointer(elpd_loo), pointer(p_loo), pointer(khat), pointer(n_eff), pointer(lpd), pointer(row_elpd_loo),
+                         pointer(row_p_loo), pointer(row_khat), pointer(row_n_eff), pointer(row_elpd_cells), pointer(row_khat_max),
+                         pointer(n_scored))
+        check(ccall((:bb_ppc_loo, LIB), Cint, (Ptr{Cvoid}, Ref{bb_loo_opts}, Ref{bb_loo_out}), h, o, out))
+    end
+    return (elpd_loo=elpd_loo, p_loo=p_loo, khat=khat, n_eff=n_eff, lpd=lpd, row_elpd_loo=row_elpd_loo, row_p_loo=row_p_loo,
+            row_khat=row_khat, row_n_eff=row_n_eff, row_elpd_cells=row_elpd_cells, row_khat_max=row_khat_max, n_scored=n_scored)
+end
+
 # Rao-Blackwellised marginals of the mutants' fitness (bb_fitness_rb, include/barbay_hip.h): every unit's exact Gaussian full
 # conditional averaged over joint draws of everything else -- how far the mean-field +- can be trusted, per mutant.  Field for
 # field the Python binding's `bb_rb_opts` / `bb_rb_out` (barbay.jl_amd/_capi.py).
