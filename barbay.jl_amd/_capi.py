@@ -32,6 +32,10 @@ BB_POPMEAN_RB_CHUNK = 256
 BB_DFE_CHUNK = 128
 BB_DFE_MAX_GRID = 64
 BB_DFE_MAX_SAMPLES = 8672
+BB_RANK_SOURCES = {"conditional": 0, "draws": 1}
+BB_RANK_MAX_TOP = 8
+BB_RANK_RUN = 8192
+BB_RANK_MAX_SAMPLES = 8672
 BB_LOGSIGMA_RB_MAX_SAMPLES = 5781
 BB_LOGSIGMA_BLOCKS = {"bc": 0, "pop": 1}
 BB_LOGTAU_RB_MAX_SAMPLES = 5781
@@ -48,7 +52,7 @@ EXPORTS = [
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_loo_shape", "bb_ppc_loo", "bb_chain_summary",
-    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_dfe_rb", "bb_popmean_rb_shape", "bb_popmean_rb",
+    "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_dfe_rb", "bb_fitness_rank", "bb_popmean_rb_shape", "bb_popmean_rb",
     "bb_logsigma_rb_shape", "bb_logsigma_rb", "bb_logtau_rb_shape", "bb_logtau_rb",
     "bb_loglambda_rb_shape", "bb_loglambda_rb",
     "bb_trace_begin", "bb_trace_end", "bb_trace_count", "bb_trace_get", "bb_trace_summary",
@@ -185,6 +189,17 @@ class bb_dfe_opts(C.Structure):
 
 class bb_dfe_out(C.Structure):
     _fields_ = [(k, _dp) for k in DFE_CELLS + DFE_BANDS] + [("n_units", C.POINTER(C.c_int64))]
+
+
+class bb_rank_opts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("n_quantiles", C.c_int32), ("n_top", C.c_int32), ("source", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved1", C.c_int32), ("probs", _dp), ("top", C.POINTER(C.c_int64)), ("seed", C.c_uint64), ("draws", _dp), ("n_sets", C.c_int64),
+                ("set_ptr", C.POINTER(C.c_int64)), ("set_idx", C.POINTER(C.c_int64))]
+
+
+class bb_rank_out(C.Structure):
+    _fields_ = [("rank_mean", _dp), ("rank_sd", _dp), ("p_top", _dp), ("quantiles", _dp), ("ranks", C.POINTER(C.c_int32)),
+                ("n_units", C.POINTER(C.c_int64))]
 
 
 class bb_popmean_rb_out(C.Structure):
@@ -343,6 +358,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.bb_contrast_rb.argtypes = [vp, C.POINTER(bb_contrast_opts), C.POINTER(bb_contrast_out)]
     if hasattr(lib, "bb_dfe_rb"):
         lib.bb_dfe_rb.argtypes = [vp, C.POINTER(bb_dfe_opts), C.POINTER(bb_dfe_out)]
+    if hasattr(lib, "bb_fitness_rank"):
+        lib.bb_fitness_rank.argtypes = [vp, C.POINTER(bb_rank_opts), C.POINTER(bb_rank_out)]
     if hasattr(lib, "bb_popmean_rb"):
         lib.bb_popmean_rb_shape.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.bb_popmean_rb.argtypes = [vp, C.POINTER(bb_rb_opts), C.POINTER(bb_popmean_rb_out)]
@@ -895,6 +912,50 @@ class Engine:
             setattr(out, k, _ptr(res[k]) if p.shape[0] else None)
         out.n_units = res["n_units"].ctypes.data_as(i64)
         self._check(self._lib.bb_dfe_rb(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def fitness_rank(self, sets, *, top: Sequence[int] = (1, 10), probs: Sequence[float] = (0.025, 0.5, 0.975), source: str = "conditional",
+                     n_samples: int = 1000, seed: int = 0, draws=None, want_ranks: bool = False, _run: int = 0,
+                     _bound_kib: int = 0) -> Dict[str, np.ndarray]:
+        """Posterior ranks of the fitness units of sets and their top-k membership (`bb_fitness_rank`): per joint draw of
+        `fitness_rb` (same `n_samples`, `seed`, `draws`) every unit is redrawn from its exact Gaussian conditional
+        (`source="conditional"`: one blocked Gibbs update of the fitness block, so that what the units share moves them together) or
+        taken as the draw's own fitness (`source="draws"`), and ranked within each set: larger is fitter, rank 0 the fittest, a NaN
+        after every number, ties by the caller's order.  `sets` as for `dfe_rb`.  Results are indexed by position in the
+        concatenated sets: rank_mean, rank_sd [n_idx]; p_top [n_idx, len(top)], the fraction of the draws with rank < top[i];
+        quantiles [n_idx, len(probs)] over the draws of the rank; n_units [n_sets] (int64); set_ptr [n_sets + 1] (int64); with
+        `want_ranks` ranks [n_idx, n_samples] (int32).  `_run`, `_bound_kib`: tests only."""
+        if source not in BB_RANK_SOURCES:
+            raise BarBayHipError(f"source must be one of {sorted(BB_RANK_SOURCES)}")
+        if isinstance(sets, tuple) and len(sets) == 2:
+            ptr, idx = sets                           # (a tuple is the CSR pair; a list of two index lists is two sets)
+        else:
+            sets = [np.asarray(c, dtype=np.int64).reshape(-1) for c in sets]
+            ptr = np.cumsum([0] + [len(c) for c in sets])
+            idx = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int64)
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        if ptr.shape[0] < 1 or (ptr.shape[0] > 1 and ptr[-1] != idx.shape[0]):
+            raise BarBayHipError("sets: ptr must have n_sets + 1 entries ending at the number of indices")
+        n, nix = ptr.shape[0] - 1, idx.shape[0]
+        t = np.ascontiguousarray(np.atleast_1d(top), dtype=np.int64).reshape(-1)
+        o, p, _x = self._rb_opts(n_samples, probs, None, seed, draws, opts=bb_rank_opts)
+        i64 = C.POINTER(C.c_int64)
+        o.n_top, o.top, o.source = t.shape[0], t.ctypes.data_as(i64) if t.shape[0] else None, BB_RANK_SOURCES[source]
+        o.reserved0, o.reserved1, o.n_sets = int(_run), int(_bound_kib), n
+        idx_ = idx if nix else np.zeros(1, dtype=np.int64)
+        o.set_ptr, o.set_idx = ptr.ctypes.data_as(i64), idx_.ctypes.data_as(i64)
+        res = {"rank_mean": np.empty(nix), "rank_sd": np.empty(nix), "p_top": np.empty((nix, t.shape[0])), "quantiles": np.empty((nix, p.shape[0])),
+               "n_units": np.empty(n, dtype=np.int64), "set_ptr": ptr.copy()}
+        out = bb_rank_out()
+        out.rank_mean, out.rank_sd = _ptr(res["rank_mean"]), _ptr(res["rank_sd"])
+        out.p_top = _ptr(res["p_top"]) if t.shape[0] and nix else None
+        out.quantiles = _ptr(res["quantiles"]) if p.shape[0] and nix else None
+        out.n_units = res["n_units"].ctypes.data_as(i64)
+        if want_ranks:
+            res["ranks"] = np.empty((nix, int(o.n_samples)), dtype=np.int32)
+            out.ranks = res["ranks"].ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.bb_fitness_rank(self._h, C.byref(o), C.byref(out)))
         return res
 
     def popmean_rb_shape(self) -> int:

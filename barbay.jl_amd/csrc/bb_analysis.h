@@ -1,6 +1,6 @@
 // bb_analysis.h -- host side of the post-fit entry points: bb_hier_fitness (bb_hier.h), bb_logdensity_grad_batch (bb_logp.h),
 // bb_ppc_bands (bb_ppc.h), bb_freq_bands (bb_freq.h), bb_ppc_score (bb_score.h), bb_ppc_loo (bb_loo.h), bb_fitness_rb, bb_theta_rb, bb_popmean_rb (bb_rb.h),
-// bb_contrast_rb (bb_contrast.h), bb_dfe_rb (bb_dfe.h), bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
+// bb_contrast_rb (bb_contrast.h), bb_dfe_rb (bb_dfe.h), bb_fitness_rank (bb_rank.h), bb_logsigma_rb (bb_lsrb.h), bb_logtau_rb (bb_ltrb.h), bb_loglambda_rb (bb_llrb.h; the three over bb_gridmix.h), bb_chain_summary (bb_chain.h) and the iterate trace's bb_trace_* (bb_trace.h).  None of them touches the step loop.
 // Included only by bb_engine.hip, once, after the handle's own entry points, which it uses: the same translation unit, built by
 // hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 
@@ -1068,8 +1068,42 @@ extern "C" int bb_contrast_rb(bb_handle* h, const bb_contrast_opts* o, const bb_
 
 // ---- posterior of the fitness distribution of sets of units (bb_dfe.h) ---------------------------------------------------------------
 static_assert(BB_DFE_CHUNK == BB_DFE_CHUNK_UNITS && BB_DFE_MAX_SAMPLES == BB_DFE_SAMPLES_CAP && BB_DFE_MAX_SAMPLES <= BB_RB_MAX_SAMPLES, "bb_dfe_rb limits");
-// The grid and the sets checked: thresholds finite and strictly ascending; a well-formed CSR, every set with units, every index
-// inside the units and named once per set.  *n_idx = set_ptr[n_sets].
+// The sets of bb_dfe_rb and bb_fitness_rank (`who`) checked: a well-formed CSR, every set with units, every index inside the units
+// and named once per set.  *n_idx = set_ptr[n_sets].
+static int sets_check(const char* who, long long n_sets, const int64_t* set_ptr, const int64_t* set_idx, long long n_units, long long* n_idx) {
+    const long long nc = n_sets;
+    if (nc < 0) return bb_fail(BB_ERR_INVALID, "%s: n_sets = %lld", who, nc);
+    *n_idx = 0;
+    if (nc == 0) return BB_OK;
+    if (!set_ptr || !set_idx) return bb_fail(BB_ERR_INVALID, "%s: set_ptr and set_idx must not be null", who);
+    if (set_ptr[0] != 0) return bb_fail(BB_ERR_INVALID, "%s: set_ptr[0] = %lld, must be 0", who, (long long)set_ptr[0]);
+    if (nc > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 indices", who);
+    for (long long c = 0; c < nc; ++c) {
+        if (set_ptr[c + 1] < set_ptr[c])
+            return bb_fail(BB_ERR_INVALID, "%s: set %lld: set_ptr decreases (%lld after %lld)", who, c, (long long)set_ptr[c + 1], (long long)set_ptr[c]);
+        if (set_ptr[c + 1] == set_ptr[c]) return bb_fail(BB_ERR_INVALID, "%s: set %lld has no units", who, c);
+    }
+    if (set_ptr[nc] > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "%s: %lld indices, more than 2^31 - 1", who, (long long)set_ptr[nc]);
+    std::vector<long long> seen;
+    for (long long c = 0; c < nc; ++c) {
+        const long long k0 = set_ptr[c], k1 = set_ptr[c + 1];
+        for (long long k = k0; k < k1; ++k)
+            if (set_idx[k] < 0 || set_idx[k] >= n_units)
+                return bb_fail(BB_ERR_INVALID, "%s: set %lld, position %lld: unit %lld outside 0..%lld", who, c, k - k0, (long long)set_idx[k], n_units - 1);
+        seen.assign(set_idx + k0, set_idx + k1);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) {
+            long long k = k1 - 1;                      // the later of the two positions that name it
+            while (set_idx[k] != *dup) --k;
+            return bb_fail(BB_ERR_INVALID, "%s: set %lld, position %lld: unit %lld is named twice", who, c, k - k0, *dup);
+        }
+    }
+    *n_idx = set_ptr[nc];
+    return BB_OK;
+}
+
+// The grid and the sets checked: thresholds finite and strictly ascending; the sets by sets_check.
 static int dfe_check(const bb_dfe_opts* o, long long n_units, long long* n_idx) {
     if (o->n_grid < 1 || o->n_grid > BB_DFE_MAX_GRID) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: n_grid = %d, must be in 1..%d", (int)o->n_grid, BB_DFE_MAX_GRID);
     if (!o->grid) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: grid must not be null");
@@ -1078,36 +1112,7 @@ static int dfe_check(const bb_dfe_opts* o, long long n_units, long long* n_idx) 
         if (g > 0 && !(o->grid[g] > o->grid[g - 1])) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: grid point %d does not lie above grid point %d: the grid must be strictly ascending", g, g - 1);
     }
     if (o->reserved0 < 0) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: reserved0 = %d, must be 0", (int)o->reserved0);
-    const long long nc = o->n_sets;
-    if (nc < 0) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: n_sets = %lld", nc);
-    *n_idx = 0;
-    if (nc == 0) return BB_OK;
-    if (!o->set_ptr || !o->set_idx) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set_ptr and set_idx must not be null");
-    if (o->set_ptr[0] != 0) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set_ptr[0] = %lld, must be 0", (long long)o->set_ptr[0]);
-    if (nc > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_dfe_rb: more than 2^31 - 1 indices");
-    for (long long c = 0; c < nc; ++c) {
-        if (o->set_ptr[c + 1] < o->set_ptr[c])
-            return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld: set_ptr decreases (%lld after %lld)", c, (long long)o->set_ptr[c + 1], (long long)o->set_ptr[c]);
-        if (o->set_ptr[c + 1] == o->set_ptr[c]) return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld has no units", c);
-    }
-    if (o->set_ptr[nc] > 2147483647LL) return bb_fail(BB_ERR_UNSUPPORTED, "bb_dfe_rb: %lld indices, more than 2^31 - 1", (long long)o->set_ptr[nc]);
-    std::vector<long long> seen;
-    for (long long c = 0; c < nc; ++c) {
-        const long long k0 = o->set_ptr[c], k1 = o->set_ptr[c + 1];
-        for (long long k = k0; k < k1; ++k)
-            if (o->set_idx[k] < 0 || o->set_idx[k] >= n_units)
-                return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld, position %lld: unit %lld outside 0..%lld", c, k - k0, (long long)o->set_idx[k], n_units - 1);
-        seen.assign(o->set_idx + k0, o->set_idx + k1);
-        std::sort(seen.begin(), seen.end());
-        const auto dup = std::adjacent_find(seen.begin(), seen.end());
-        if (dup != seen.end()) {
-            long long k = k1 - 1;                      // the later of the two positions that name it
-            while (o->set_idx[k] != *dup) --k;
-            return bb_fail(BB_ERR_INVALID, "bb_dfe_rb: set %lld, position %lld: unit %lld is named twice", c, k - k0, *dup);
-        }
-    }
-    *n_idx = o->set_ptr[nc];
-    return BB_OK;
+    return sets_check("bb_dfe_rb", o->n_sets, o->set_ptr, o->set_idx, n_units, n_idx);
 }
 
 extern "C" int bb_dfe_rb(bb_handle* h, const bb_dfe_opts* o, const bb_dfe_out* out) {
@@ -1239,6 +1244,172 @@ extern "C" int bb_dfe_rb(bb_handle* h, const bb_dfe_opts* o, const bb_dfe_out* o
     pt.lap(7, 5);
 #ifdef BB_RB_TIMES
     fprintf(stderr, "[bb_dfe_rb %zu sets, %zu indices, %zu chunks, %d grid points, %d samples, %d quantiles, %zu slabs] map+upload %.3f ms, pop %.3f ms, normalisers %.3f ms, part %.3f ms, dfe %.3f ms, download %.3f ms\n", nset, nix, chk_set.size(), ngr, ns, nq, n_slabs, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5]);
+#endif
+    return BB_OK;
+}
+
+// ---- posterior ranks and top-k membership of the units of sets (bb_rank.h) -------------------------------------------------------------
+static_assert(BB_RANK_RUN == BB_RANK_RUN_KEYS && BB_RANK_MAX_TOP == BB_RANK_TOPS && BB_RANK_MAX_SAMPLES == BB_RANK_SAMPLES_CAP && BB_RANK_MAX_SAMPLES <= BB_RB_MAX_SAMPLES,
+              "bb_fitness_rank limits");
+static_assert(BB_RANK_CONDITIONAL == 0 && BB_RANK_DRAWS == 1, "RankArgs.source");
+#define BB_RANK_BYTES 16                 // per position and draw in flight: a key, a sorted position, a rank
+extern "C" int bb_fitness_rank(bb_handle* h, const bb_rank_opts* o, const bb_rank_out* out) {
+    if (!h || !o || !out) return bb_fail(BB_ERR_INVALID, "null argument");
+    const int nq = o->n_quantiles, ns = o->n_samples, ntop = o->n_top;
+    if (int rc = rb_check(nq, o->probs, o->draws, ns, BB_RANK_MAX_SAMPLES, nullptr)) return rc;
+    if (nq > 0 && ns < 2) return bb_fail(BB_ERR_UNSUPPORTED, "bb_fitness_rank: n_quantiles > 0 needs n_samples >= 2: one draw has no quantiles over the draws");
+    if (o->source != BB_RANK_CONDITIONAL && o->source != BB_RANK_DRAWS) return bb_fail(BB_ERR_INVALID, "bb_fitness_rank: source = %d, must be BB_RANK_CONDITIONAL or BB_RANK_DRAWS", (int)o->source);
+    if (ntop < 0 || ntop > BB_RANK_MAX_TOP) return bb_fail(BB_ERR_INVALID, "bb_fitness_rank: n_top = %d, must be in 0..%d", ntop, BB_RANK_MAX_TOP);
+    if (ntop > 0 && !o->top) return bb_fail(BB_ERR_INVALID, "bb_fitness_rank: top must not be null with n_top > 0");
+    for (int i = 0; i < ntop; ++i)
+        if (o->top[i] < 1 || o->top[i] > 2147483647LL) return bb_fail(BB_ERR_INVALID, "bb_fitness_rank: top[%d] = %lld, must be in 1..2^31 - 1", i, (long long)o->top[i]);
+    if (o->reserved0 < 0 || (o->reserved0 > 0 && (o->reserved0 < 64 || o->reserved0 > BB_RANK_RUN || (o->reserved0 & (o->reserved0 - 1)))))
+        return bb_fail(BB_ERR_INVALID, "bb_fitness_rank: reserved0 = %d, must be 0", (int)o->reserved0);
+    if (o->reserved1 < 0) return bb_fail(BB_ERR_INVALID, "bb_fitness_rank: reserved1 = %d, must be 0", (int)o->reserved1);
+    long long n_idx = 0;
+    if (int rc = sets_check("bb_fitness_rank", o->n_sets, o->set_ptr, o->set_idx, rb_units(h), &n_idx)) return rc;
+    if (o->n_sets == 0) return BB_OK;
+    BandsCall B(h);
+    bb_handle* dh = B.dh;
+    const DevModel& M = dh->M;
+    RankArgs R;
+    memset(&R, 0, sizeof R);
+    RbArgs& A = R.A;
+    FreqArgs& F = A.F;
+    PpcArgs& P = F.P;
+    const size_t nset = (size_t)o->n_sets, nix = (size_t)n_idx;
+    const bool cond = o->source == BB_RANK_CONDITIONAL;
+    int zb;
+    int rc = rb_open(h, B, A, ns, o->seed, nq, o->probs, n_idx, &zb);
+    if (rc) return rc;
+    if (M.kind == BB_MODEL_FITNESS || M.kind == BB_MODEL_MULTIENV) {      // the s_bc prior, as bb_fitness_rb sets it
+        const DevPrior& dp = M.pri[BK_S];
+        P.pri_mean = dp.mean; P.pri_ivar = dp.inv_var; P.pri_mean_e = dp.mean_e; P.pri_ivar_e = dp.inv_var_e;
+    }
+    if (nq > 0) quantile_plan(ns, o->probs, nq, P);    // (P.n_q stays 0: the program interpolates per probability, as bb_dfe_rb's)
+    R.n_idx = n_idx;
+    R.run = o->reserved0 > 0 ? o->reserved0 : BB_RANK_RUN;
+    R.source = o->source;
+    R.n_top = ntop;
+    for (int i = 0; i < ntop; ++i) R.top[i] = (int)o->top[i];
+    RbTimes pt{dh->stream};      // tools/rank_rate.py: the call's phases, each drained before the next starts
+    pt.lap(0, -1);
+    // the run map: set -> first run, run -> set
+    std::vector<int> hm;                               // set_ptr | set_idx | set_r0 | run_set
+    hm.reserve(2 * (nset + 1) + nix + nix / (size_t)R.run + nset);
+    for (size_t c = 0; c <= nset; ++c) hm.push_back((int)o->set_ptr[c]);
+    for (size_t k = 0; k < nix; ++k) hm.push_back((int)o->set_idx[k]);
+    std::vector<int> set_r0(nset + 1, 0), run_set;
+    for (size_t c = 0; c < nset; ++c) {
+        const long long n = o->set_ptr[c + 1] - o->set_ptr[c], nr = (n + R.run - 1) / R.run;
+        set_r0[c + 1] = set_r0[c] + (int)nr;
+        run_set.insert(run_set.end(), (size_t)nr, (int)c);
+    }
+    const size_t at_r0 = hm.size();
+    hm.insert(hm.end(), set_r0.begin(), set_r0.end());
+    const size_t at_rs = hm.size();
+    hm.insert(hm.end(), run_set.begin(), run_set.end());
+    // The slabs: sets [cut[s], cut[s + 1]) with all their draws while their tables, BB_RANK_BYTES per position and draw, stay within
+    // 256 MiB; a set too large for that is worked alone, its keys and sorted positions `width` draws at a time, its ranks whole.
+    const size_t nsz = (size_t)ns, D_ = (size_t)h->M.D, nmap = hm.size();
+    const size_t bound = o->reserved1 > 0 ? (size_t)o->reserved1 << 10 : (size_t)256 << 20;
+    auto width = [&](size_t npos) {                    // draws in flight of a slab of npos positions
+        if (npos * nsz * BB_RANK_BYTES <= bound) return nsz;
+        return std::min(nsz, std::max<size_t>(1, bound / ((BB_RANK_BYTES - 4) * npos)));
+    };
+    std::vector<size_t> cut{0};
+    size_t key_elems = 1, rank_elems = 1, n_slabs = 0;
+    while (cut.back() < nset) {
+        const size_t s0 = cut.back();
+        size_t s1 = s0 + 1;
+        while (s1 < nset && (size_t)(o->set_ptr[s1 + 1] - o->set_ptr[s0]) * nsz * BB_RANK_BYTES <= bound) ++s1;
+        const size_t npos = (size_t)(o->set_ptr[s1] - o->set_ptr[s0]), jw = width(npos);
+        n_slabs += (nsz + jw - 1) / jw;
+        key_elems = std::max(key_elems, npos * jw);
+        rank_elems = std::max(rank_elems, npos * nsz);
+        cut.push_back(s1);
+    }
+    B.nblk = 0;                                        // (no row program: P.par is not used)
+    double* ddraws = nullptr;
+    int* dmap = nullptr;
+    rc = bands_buffers(h, P, B, [&](Carve& c) {
+        c(F.Z, cond ? (size_t)M.Ttot * nsz : 0);       // [Ttot][ns]
+        c(F.zpart, cond ? (size_t)F.nchunks * zb * nsz : 0);      // [nchunks][zb][ns]
+        c(R.key, key_elems);                           // the keys of the positions and draws in flight
+        c(R.spos, (key_elems + 1) / 2);                // ... their sorted positions: ints
+        c(R.rank, (rank_elems + 1) / 2);               // [positions in flight][ns] ints
+        c(R.unit, 2 * nix);                            // [2][n_idx]
+        c(R.ptop, ntop ? BB_RANK_TOPS * nix : 0);      // [n_idx][8]
+        c(R.quant, nq ? BB_RB_MAX_Q * nix : 0);        // [n_idx][8]
+        c(dmap, (nmap + 1) / 2);                       // the CSR arrays and the run map: ints
+        c(ddraws, o->draws ? nsz * D_ : 0);            // [ns][D]
+    });
+    if (rc) return rc;
+    R.set_ptr = dmap;
+    R.set_idx = dmap + nset + 1;
+    R.set_r0 = dmap + at_r0;
+    R.run_set = dmap + at_rs;
+    if ((rc = h2d(dmap, hm.data(), nmap * 4, dh->stream))) return rc;
+    if ((rc = rb_draws(dh, P, ddraws, o->draws, nsz, D_))) return rc;
+    pt.lap(1, 0);
+    if (cond && (rc = rb_front(dh, B, A, zb, true))) return rc;
+    pt.lap(2, 1);
+    for (size_t sl = 0; sl + 1 < cut.size(); ++sl) {
+        const size_t s0 = cut[sl], s1 = cut[sl + 1];
+        R.s0 = (long long)s0; R.s1 = (long long)s1;
+        R.k0 = (int)o->set_ptr[s0]; R.k1 = (int)o->set_ptr[s1];
+        R.r0 = set_r0[s0]; R.r1 = set_r0[s1];
+        const size_t npos = (size_t)(R.k1 - R.k0), jw = width(npos);
+        long long longest = 1;
+        bool several = false;
+        for (size_t c = s0; c < s1; ++c) {
+            longest = std::max<long long>(longest, o->set_ptr[c + 1] - o->set_ptr[c]);
+            several |= set_r0[c + 1] - set_r0[c] > 1;
+        }
+        int p2 = 2;
+        while (p2 < std::min<long long>(longest, R.run)) p2 <<= 1;
+        R.lds_run = p2;
+        const int snt = std::min(BB_RANK_SORT_NT, std::max(64, p2 / 2));
+        for (size_t j0 = 0; j0 < nsz; j0 += jw) {
+            R.j0 = (int)j0; R.j1 = (int)std::min(j0 + jw, nsz);
+            const long long jn = R.j1 - R.j0, nval = (long long)((npos + BB_RANK_VAL_UNITS - 1) / BB_RANK_VAL_UNITS) * ((jn + BB_RANK_VAL_NT - 1) / BB_RANK_VAL_NT);
+            const long long nsort = (long long)(R.r1 - R.r0) * jn;
+            pt.lap(3, -1);
+            if ((rc = launch(dh->stream, k_rank_val, (int)std::min<long long>(nval, 1 << 20), BB_RANK_VAL_NT, 0, R))) return rc;
+            pt.lap(4, 2);
+            if ((rc = launch(dh->stream, k_rank_sort, (int)std::min<long long>(nsort, 1 << 20), snt, (size_t)BB_RANK_SORT_LDS_DOUBLES(p2), R))) return rc;
+            pt.lap(5, 3);
+            if (several && (rc = launch(dh->stream, k_rank_merge, (int)std::min<long long>(nsort, 1 << 20), snt, 0, R))) return rc;
+            pt.lap(6, 4);
+        }
+        pt.lap(3, -1);
+        if ((rc = launch(dh->stream, k_rank_stats, (int)std::min<long long>((long long)npos, 8LL * dh->cus), BB_SCORE_NT, (size_t)BB_RANK_STATS_LDS_DOUBLES(ns), R))) return rc;
+        pt.lap(4, 5);
+        pt.lap(6, -1);
+        if (out->ranks && (rc = d2h(out->ranks + (size_t)R.k0 * nsz, R.rank, npos * nsz * 4, dh->stream))) return rc;
+        pt.lap(7, 6);
+    }
+    pt.lap(6, -1);
+    if (out->rank_mean && (rc = d2h(out->rank_mean, R.unit, nix * 8, dh->stream))) return rc;
+    if (out->rank_sd && (rc = d2h(out->rank_sd, R.unit + nix, nix * 8, dh->stream))) return rc;
+    std::vector<double> q;
+    if (out->p_top && ntop) {
+        q.resize(BB_RANK_TOPS * nix);
+        if ((rc = d2h(q.data(), R.ptop, q.size() * 8, dh->stream))) return rc;
+        for (size_t e = 0; e < nix; ++e)
+            for (int i = 0; i < ntop; ++i) out->p_top[e * ntop + i] = q[e * BB_RANK_TOPS + i];
+    }
+    if (out->quantiles && nq) {
+        q.resize(BB_RB_MAX_Q * nix);
+        if ((rc = d2h(q.data(), R.quant, q.size() * 8, dh->stream))) return rc;
+        for (size_t e = 0; e < nix; ++e)
+            for (int i = 0; i < nq; ++i) out->quantiles[e * nq + i] = q[e * BB_RB_MAX_Q + i];
+    }
+    if ((rc = dsync(dh->stream))) return rc;
+    for (size_t c = 0; out->n_units && c < nset; ++c) out->n_units[c] = o->set_ptr[c + 1] - o->set_ptr[c];
+    pt.lap(7, 6);
+#ifdef BB_RB_TIMES
+    fprintf(stderr, "[bb_fitness_rank source %d, %zu sets, %zu indices, %zu runs of %d, %d samples, %d quantiles, %d tops, %zu slabs] map+upload %.3f ms, front %.3f ms, values %.3f ms, sort %.3f ms, merge %.3f ms, summaries %.3f ms, download %.3f ms\n", (int)o->source, nset, nix, run_set.size(), R.run, ns, nq, ntop, n_slabs, pt.ms[0], pt.ms[1], pt.ms[2], pt.ms[3], pt.ms[4], pt.ms[5], pt.ms[6]);
 #endif
     return BB_OK;
 }

@@ -449,6 +449,22 @@ BB_KERNEL(BB_SCORE_NT, k_dfe, DfeArgs D) {
     BB_CTX;
     bb_block_dfe(cx, D, BB_GRID);
 }
+BB_KERNEL(BB_RANK_VAL_NT, k_rank_val, RankArgs R) {
+    BB_CTX;
+    bb_block_rank_val(cx, R, BB_GRID);
+}
+BB_KERNEL(BB_RANK_SORT_NT, k_rank_sort, RankArgs R) {
+    BB_CTX;
+    bb_block_rank_sort(cx, R, BB_GRID);
+}
+BB_KERNEL(BB_RANK_SORT_NT, k_rank_merge, RankArgs R) {
+    BB_CTX;
+    bb_block_rank_merge(cx, R, BB_GRID);
+}
+BB_KERNEL(BB_SCORE_NT, k_rank_stats, RankArgs R) {
+    BB_CTX;
+    bb_block_rank_stats(cx, R, BB_GRID);
+}
 BB_KERNEL(BB_SCORE_NT, k_ls_bc, LsArgs L) {
     BB_CTX;
     bb_block_ls_bc(cx, L, BB_GRID);

@@ -23,6 +23,7 @@
 #include "bb_rb.h"
 #include "bb_contrast.h"
 #include "bb_dfe.h"
+#include "bb_rank.h"
 #include "bb_lsrb.h"
 #include "bb_ltrb.h"
 #include "bb_llrb.h"

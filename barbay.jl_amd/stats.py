@@ -718,6 +718,39 @@ def fitness_contrasts(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, level
     return pd.DataFrame({k: out[k] for k in order + [k for k in out if k not in order]})
 
 
+def _fitness_sets(bayes_model, arrays, mname: str, by: str, groups: Optional[Dict]):
+    """The sets of `fitness_distribution` and `fitness_ranking`: (rep, env, genotype, group) -> the set's fitness units (the rows of
+    `fitness_marginals`), in unit order; and what labels a unit: (R, nb, E, ids, envs or None, genotypes or None)."""
+    R, nb = len(bayes_model.counts), bayes_model.n_bc
+    has_env, envs = _env_labels(arrays, mname, R)
+    E = max(len(envs), 1) if has_env else 1
+    ids = list(arrays.bc_ids)
+    geno = arrays.genotypes if isinstance(arrays.genotypes, list) else None
+    if by == "genotype" and geno is None:
+        raise BarBayError('by="genotype" needs the genotypes of the mutants: give genotype_col=')
+    if by == "env" and not has_env:
+        raise BarBayError(f'by="env" cannot be served by {mname}: it has no environments (by="rep_env", "rep" or "all")')
+    if groups is not None:
+        known = set(ids)
+        unknown = next((k for k in groups if k not in known), None)
+        if unknown is not None:
+            raise BarBayError(f"groups: {unknown!r} is no mutant of the data")
+        if not groups:
+            raise BarBayError("groups names no mutant")
+    sets: Dict = {}                                                # (rep, env, genotype, group) -> units, in unit order
+    for r in range(R):
+        for m in range(nb):
+            if groups is not None and ids[m] not in groups:
+                continue
+            for x in range(E):
+                key = (f"R{r + 1}" if by in ("rep_env", "rep") else None,
+                       envs[x] if has_env and by in ("rep_env", "env") else None,
+                       geno[m] if by == "genotype" else None,
+                       groups[ids[m]] if groups is not None else None)
+                sets.setdefault(key, []).append(x + E * m + E * nb * r)
+    return sets, (R, nb, E, ids, envs if has_env else None, geno)
+
+
 def fitness_distribution(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, by: str = "rep_env", groups: Optional[Dict] = None,
                          grid: Optional[Sequence[float]] = None, model_kwargs: Optional[Dict] = None,
                          n_samples: int = 1000, probs: Sequence[float] = (0.025, 0.5, 0.975), seed: int = 0,
@@ -761,33 +794,7 @@ def fitness_distribution(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, by
     if grid.shape[0] < 1 or grid.shape[0] > 64 or not np.all(np.isfinite(grid)) or not np.all(np.diff(grid) > 0):
         raise BarBayError("grid must hold 1 to 64 finite, strictly ascending thresholds")
     with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
-        R, nb = len(bayes_model.counts), bayes_model.n_bc
-        has_env, envs = _env_labels(arrays, mname, R)
-        E = max(len(envs), 1) if has_env else 1
-        ids = list(arrays.bc_ids)
-        geno = arrays.genotypes if isinstance(arrays.genotypes, list) else None
-        if by == "genotype" and geno is None:
-            raise BarBayError('by="genotype" needs the genotypes of the mutants: give genotype_col=')
-        if by == "env" and not has_env:
-            raise BarBayError(f'by="env" cannot be served by {mname}: it has no environments (by="rep_env", "rep" or "all")')
-        if groups is not None:
-            known = set(ids)
-            unknown = next((k for k in groups if k not in known), None)
-            if unknown is not None:
-                raise BarBayError(f"groups: {unknown!r} is no mutant of the data")
-            if not groups:
-                raise BarBayError("groups names no mutant")
-        sets: Dict = {}                                                # (rep, env, genotype, group) -> units, in unit order
-        for r in range(R):
-            for m in range(nb):
-                if groups is not None and ids[m] not in groups:
-                    continue
-                for x in range(E):
-                    key = (f"R{r + 1}" if by in ("rep_env", "rep") else None,
-                           envs[x] if has_env and by in ("rep_env", "env") else None,
-                           geno[m] if by == "genotype" else None,
-                           groups[ids[m]] if groups is not None else None)
-                    sets.setdefault(key, []).append(x + E * m + E * nb * r)
+        sets, _labels = _fitness_sets(bayes_model, arrays, mname, by, groups)
         draws = None
         if chain is not None:
             draws = np.asarray(chain, dtype=np.float64)
@@ -808,6 +815,77 @@ def fitness_distribution(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, by
     for side in ("below", "above"):
         for i, p in enumerate(probs):
             out[f"{side}_q{100.0 * p:g}"] = res[f"{side}_bands"][:, :, i].reshape(-1)
+    return pd.DataFrame(out)
+
+
+def fitness_ranking(data: pd.DataFrame, df_advi: pd.DataFrame, *, model, by: str = "rep_env", groups: Optional[Dict] = None,
+                    top: Sequence[int] = (1, 10), probs: Sequence[float] = (0.025, 0.5, 0.975), source: str = "conditional",
+                    model_kwargs: Optional[Dict] = None, n_samples: int = 1000, seed: int = 0,
+                    id_col="barcode", time_col="time", count_col="count", neutral_col="neutral",
+                    rep_col: Optional[str] = None, env_col: Optional[str] = None, genotype_col: Optional[str] = None,
+                    device: int = 0, chain=None) -> pd.DataFrame:
+    """Which lineages are the fittest, and how sure is that list?  A rank is a function of all the fitnesses of a set at once, so
+    it needs joint draws -- and mean-field q's own are the wrong ones: q has cut every coupling, so ranks formed from them are
+    overconfident wherever units share something (a replicate's population mean fitness; theta and tau of the hierarchical models).
+    Given everything else the fitness units are conditionally independent with exactly Gaussian conditionals, so redrawing every
+    unit of a joint draw from its conditional is one exact blocked Gibbs update of the whole fitness block, the joint draw with the
+    shared uncertainty back in it; `bb_fitness_rank` ranks every set on every such draw in one device call.
+
+    `by`, `groups`: the sets, exactly as for `fitness_distribution`.  `top`: list lengths k (at most 8); `probs`: quantiles of the
+    rank over the draws; `source`: "conditional" (the redraw) or "draws" (q's own draws, or the chain's: what the coupling adds is
+    the difference between the two).  The remaining arguments as for `fitness_marginals`.
+
+    Returns one line per (set, unit), the sets in `fitness_distribution`'s order and a set's units in unit order: `id`, `rep`,
+    `env` (the unit's own; None without environments), `genotype` (None without genotypes), `group` (None without `groups`),
+    `n_units` (the size of the set the line belongs to: the one the columns `by` names and `group` identify), `rank` (1-based
+    position within the set by `rank_mean`, ties by unit order), `rank_mean` (1-based: 1 is the fittest), `rank_sd`, one column
+    rank_q2.5, rank_q50, ... per probability (1-based) and one column p_top1, p_top10, ... per k: the posterior probability that
+    the unit is among the k fittest of its set."""
+    cols = dict(id_col=id_col, time_col=time_col, count_col=count_col, neutral_col=neutral_col, rep_col=rep_col,
+                env_col=env_col, genotype_col=genotype_col)
+    probs = [float(p) for p in np.atleast_1d(probs)] if probs is not None else []
+    if by not in ("rep_env", "env", "rep", "genotype", "all"):
+        raise BarBayError('by must be "rep_env", "env", "rep", "genotype" or "all"')
+    if source not in ("conditional", "draws"):
+        raise BarBayError('source must be "conditional" or "draws"')
+    tops = list(np.atleast_1d(top).reshape(-1)) if top is not None else []
+    if any(not isinstance(k, (int, np.integer)) or isinstance(k, (bool, np.bool_)) for k in tops):
+        raise BarBayError("top must hold whole list lengths")
+    tops = [int(k) for k in tops]
+    if len(tops) > 8 or any(k < 1 or k > 2 ** 31 - 1 for k in tops) or len(set(tops)) != len(tops):
+        raise BarBayError("top must hold at most 8 distinct list lengths k, each in 1 .. 2^31 - 1")
+    with _engine_at_fit(data, df_advi, model, model_kwargs, seed, device, cols) as (e, bayes_model, arrays, mname):
+        sets, (R, nb, E, ids, envs, geno) = _fitness_sets(bayes_model, arrays, mname, by, groups)
+        draws = None
+        if chain is not None:
+            draws = np.asarray(chain, dtype=np.float64)
+            if draws.ndim not in (2, 3) or draws.shape[-1] != e.D:
+                raise BarBayError(f"chain must be [walkers, steps, {e.D}] or [draws, {e.D}]")
+            draws = draws.reshape(-1, e.D)
+        keys = list(sets)
+        res = e.fitness_rank([sets[k] for k in keys], top=tops, probs=probs, source=source, n_samples=n_samples, seed=seed, draws=draws)
+    u = np.concatenate([np.asarray(sets[k], dtype=np.int64) for k in keys])
+    rep, m, env = u // (E * nb), (u // E) % nb, u % E
+    ptr = res["set_ptr"]
+    rank = np.empty(u.shape[0], dtype=np.int64)
+    for c in range(len(keys)):
+        a, b = int(ptr[c]), int(ptr[c + 1])
+        rank[a + np.argsort(res["rank_mean"][a:b], kind="stable")] = np.arange(1, b - a + 1)
+    out = {
+        "id": np.asarray(ids, dtype=object)[m],
+        "rep": [f"R{r + 1}" for r in rep],
+        "env": [envs[x] for x in env] if envs is not None else None,
+        "genotype": [geno[x] for x in m] if geno is not None else None,
+        "group": [groups[ids[x]] for x in m] if groups is not None else None,
+        "n_units": np.repeat(res["n_units"], np.diff(ptr)),
+        "rank": rank,
+        "rank_mean": res["rank_mean"] + 1.0,
+        "rank_sd": res["rank_sd"],
+    }
+    for i, p in enumerate(probs):
+        out[f"rank_q{100.0 * p:g}"] = res["quantiles"][:, i] + 1.0
+    for i, k in enumerate(tops):
+        out[f"p_top{k}"] = res["p_top"][:, i]
     return pd.DataFrame(out)
 
 

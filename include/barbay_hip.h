@@ -797,6 +797,89 @@ typedef struct bb_dfe_out {   /* every pointer may be NULL; [n_sets][n_grid] unl
 } bb_dfe_out;
 int bb_dfe_rb(bb_handle* h, const bb_dfe_opts* o, const bb_dfe_out* out);
 
+/* Posterior ranks of the fitness units of a set and top-k membership -- which lineages are the fittest, and how sure are we of
+ * that list: the rank of every unit within its set per joint draw, and over the draws its mean, sd, quantiles and the probability
+ * of lying among the k fittest.  No reference counterpart.  A rank is a function of all the fitnesses of a set at once, so it
+ * needs joint draws; the marginals do not give it, and mean-field q's own joint draws are the wrong ones: q has cut every
+ * coupling, so ranks formed from them are overconfident wherever units share something (a replicate's sbar_t; theta and tau of
+ * the hierarchical kinds).  The repair is bb_contrast_rb's fact: given everything else, distinct fitness units are conditionally
+ * independent, each exactly N(m_{u,j}, sd_{u,j}).  Drawing every unit of draw j from its conditional is therefore one exact
+ * blocked Gibbs update of the whole fitness block -- the joint draw with the shared uncertainty back in it, the sampling
+ * counterpart of what bb_fitness_rb does for the marginals.
+ *
+ * Sets: CSR exactly as bb_dfe_opts (units in bb_fitness_rb's numbering, at least one per set, each at most once per set).
+ * Outputs are indexed by position k in set_idx, since a unit may sit in several sets; n_idx = set_ptr[n_sets].
+ *
+ * Values per draw j.  (s_{u,j}, m_{u,j}, sd_{u,j}) are bb_fitness_rb's exactly: the same draws and keying (stream 0xFFFFFFE0;
+ * draws read in their place), the same gamma, ln Z by the 256-column rule, ascending t, the later time point's environment, the
+ * n_u = 0 rule, the hierarchical kinds' N(theta_j, tau_j) prior.  The value that is ranked:
+ *   BB_RANK_DRAWS        v = s_{u,j}; the normalisers are not formed
+ *   BB_RANK_CONDITIONAL  v = fma(sd_{u,j}, N(u, j >> 1, 0xFFFFFFE3), m_{u,j}); N is the Philox normal pair at `seed` (with explicit
+ *                        draws too), u the unit's number (not its position in a set), an even j the cosine branch and an odd j the
+ *                        sine branch.  A unit has one value per draw whichever sets name it: the sets of a call are ranked on one
+ *                        joint draw.
+ * Order.  Within a set, position a ranks before position b when v_a > v_b; or v_a is a number and v_b is NaN; or neither holds
+ * either way and a < b (equal values, -0.0 and +0.0 being equal, and both NaN).  So a NaN ranks after every number, -Inf after
+ * every finite value, ties go to the caller's order; the ranks r of a (set, draw) are a permutation of 0 .. n - 1 and rank 0 is
+ * the fittest.  Non-finite parameters are not an error: they rank as stated and disturb no set that does not name a unit using them.
+ *
+ * Over the draws, per position (r_j the int32 rank, divisor n_samples):
+ *   rank_mean  (sum_j r_j) / n_samples: the sum of integers is exact, one rounding
+ *   rank_sd    sqrt(mean_j (r_j - rank_mean)^2), two-pass and centred, in bb_ppc_score's reduction order
+ *   p_top      p_top[k][i] = #{j : r_j < top[i]} / n_samples: exact; 1 where top[i] >= n
+ *   quantiles  the probs quantiles over j of r_j as doubles, by the rule of bb_ppc_bands (type 7: exact order statistics by
+ *              selection, a + gamma (b - a)); n_quantiles > 0 needs n_samples >= 2
+ *   ranks      r_j itself, [n_idx][n_samples]
+ *   n_units    [n_sets] the sets' sizes
+ *
+ * Working memory: a set of at most BB_RANK_RUN units is sorted by one workgroup per draw in LDS; a larger one in runs of
+ * BB_RANK_RUN whose sorted keys are then searched for every element (csrc/bb_rank.h).  The tables in flight (per position and
+ * draw a key, a sorted position and a rank: 16 bytes) are bounded to 256 MiB by working the sets in slabs; a set that alone
+ * exceeds the bound is worked alone, its keys in tiles of draws, its int32 rank table whole.  reserved0, reserved1: 0.  (Tests:
+ * reserved0 > 0 replaces the run length by that power of two in 64 .. BB_RANK_RUN; reserved1 > 0 replaces the bound, in KiB.  No
+ * result depends on either.)  BB_RANK_MAX_SAMPLES: one workgroup holds the column of a position's ranks in LDS beside the
+ * selection's histograms (bb_dfe_rb's layout and cap).
+ *
+ * A position's results are a function of the handle's (mu, sigma) (or the supplied draws), the priors, geno_idx, its own set's
+ * units in their order, n_samples, seed, source, top and probs: bit-identical whatever the other sets, their number or order,
+ * the slabs, the run length, the launch grid or mode, the device count or the calls made before.  Ranks are integers defined by a
+ * strict total order: every correct algorithm gives the same ones.  No atomics on doubles.  The handle's mu, omega, optimiser
+ * state, step counter and RNG position are untouched, bitwise.
+ * BB_ERR_INVALID: a null h, o or out; the probs / n_quantiles errors of bb_fitness_rb; an unknown source; n_top outside
+ * 0 .. BB_RANK_MAX_TOP; top null with n_top > 0; a top[i] outside 1 .. 2^31 - 1; a negative reserved0 or reserved1 (or a
+ * reserved0 that is no power of two in 64 .. BB_RANK_RUN); the set errors of bb_dfe_rb, word for word.  BB_ERR_UNSUPPORTED:
+ * n_samples outside its range; n_quantiles > 0 with one draw; more than 2^31 - 1 indices.  n_sets == 0 is BB_OK and writes
+ * nothing.  What the device cannot allocate is BB_ERR_DEVICE, and nothing is computed.  Multi-device and sharded handles: as
+ * bb_ppc_bands.  Out of scope: ranks of theta, Rao-Blackwellised pairwise ordering probabilities (O(n^2)). */
+#define BB_RANK_CONDITIONAL 0     /* s*_{u,j}: every unit redrawn from its conditional  */
+#define BB_RANK_DRAWS       1     /* s_{u,j}: the draws' own fitness                    */
+#define BB_RANK_MAX_TOP     8
+#define BB_RANK_RUN         8192  /* keys one workgroup sorts in LDS                    */
+#define BB_RANK_MAX_SAMPLES 8672  /* <= BB_RB_MAX_SAMPLES                               */
+typedef struct bb_rank_opts {
+    int32_t n_samples;        /* draws j, 2 (1 with draws) .. BB_RANK_MAX_SAMPLES       */
+    int32_t n_quantiles;      /* 0 .. 8                                                 */
+    int32_t n_top;            /* 0 .. BB_RANK_MAX_TOP                                   */
+    int32_t source;           /* BB_RANK_*                                              */
+    int32_t reserved0;        /* 0 (tests: run length, above)                           */
+    int32_t reserved1;        /* 0 (tests: bound of the tables in flight, KiB)          */
+    const double* probs;      /* [n_quantiles], in (0, 1): quantiles over the draws     */
+    const int64_t* top;       /* [n_top] list lengths k, 1 .. 2^31 - 1                  */
+    uint64_t seed;            /* Philox key                                             */
+    const double* draws;      /* host, [n_samples][D] in the caller's order, or NULL    */
+    int64_t n_sets;
+    const int64_t* set_ptr;   /* CSR exactly as bb_dfe_opts                             */
+    const int64_t* set_idx;   /* units of bb_fitness_rb                                 */
+} bb_rank_opts;
+typedef struct bb_rank_out {  /* every pointer may be NULL; n_idx = set_ptr[n_sets]     */
+    double *rank_mean, *rank_sd;   /* [n_idx]                                           */
+    double* p_top;                 /* [n_idx][n_top]                                    */
+    double* quantiles;             /* [n_idx][n_quantiles]                              */
+    int32_t* ranks;                /* [n_idx][n_samples]: the rank draws themselves     */
+    int64_t* n_units;              /* [n_sets]                                          */
+} bb_rank_out;
+int bb_fitness_rank(bb_handle* h, const bb_rank_opts* o, const bb_rank_out* out);
+
 /* Rao-Blackwellised marginals of the population mean fitness sbar_t -- the pop_mean_fitness rows of a fit, the quantity every
  * reported mutant fitness is relative to, and the one latent that every barcode's log-frequency-ratio term reads: q factorises it
  * away from all of them.  No reference counterpart.  sbar_g enters the log-joint through its Gaussian prior (s_pop_prior, Vector or

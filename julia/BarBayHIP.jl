@@ -602,6 +602,77 @@ function dfe_rb(h::Ptr{Cvoid}, sets::Vector{<:Vector{<:Integer}}, grid::Vector{F
             q_below_mean=q_below_mean, q_below_sd=q_below_sd, below_bands=below_bands, above_bands=above_bands)
 end
 
+# Posterior ranks of the fitness units of sets and their top-k membership (bb_fitness_rank, include/barbay_hip.h): per joint draw
+# of `fitness_rb` every unit is redrawn from its exact Gaussian conditional (one blocked Gibbs update of the fitness block, so that
+# what the units share moves them together) or taken as the draw's own fitness, and ranked within each set; rank 0 is the fittest.
+# Field for field the Python binding's `bb_rank_opts` / `bb_rank_out` (barbay.jl_amd/_capi.py).  Like the rest of this file it
+# remains unexecuted.
+const BB_RANK_CONDITIONAL = 0
+const BB_RANK_DRAWS = 1
+const BB_RANK_MAX_TOP = 8
+const BB_RANK_RUN = 8192
+const BB_RANK_MAX_SAMPLES = 8672
+struct bb_rank_opts
+    n_samples::Int32
+    n_quantiles::Int32
+    n_top::Int32
+    source::Int32
+    reserved0::Int32
+    reserved1::Int32
+    probs::Ptr{Float64}
+    top::Ptr{Int64}
+    seed::UInt64
+    draws::Ptr{Float64}
+    n_sets::Int64
+    set_ptr::Ptr{Int64}
+    set_idx::Ptr{Int64}
+end
+struct bb_rank_out
+    rank_mean::Ptr{Float64}
+    rank_sd::Ptr{Float64}
+    p_top::Ptr{Float64}
+    quantiles::Ptr{Float64}
+    ranks::Ptr{Int32}
+    n_units::Ptr{Int64}
+end
+
+"""
+    fitness_rank(h, sets; top=[1, 10], probs=[0.025, 0.5, 0.975], source=BB_RANK_CONDITIONAL, n_samples=1000, seed=0,
+                 draws=nothing, want_ranks=false) -> NamedTuple
+
+`h` a live `bb_handle`.  `sets` as for `dfe_rb`.  Results are indexed by position in the concatenated sets (`set_ptr`, 0-based
+offsets): `rank_mean, rank_sd` (one per position; 0 is the fittest), `p_top` (length(top) x n_idx: the fraction of the draws with
+rank < top[i]), `quantiles` (length(probs) x n_idx, over the draws of the rank), `n_units` (one per set) and, with `want_ranks`,
+`ranks` (n_samples x n_idx, Int32).  The remaining arguments as for `fitness_rb`.
+"""
+function fitness_rank(h::Ptr{Cvoid}, sets::Vector{<:Vector{<:Integer}}; top::Vector{<:Integer}=[1, 10], probs::Vector{Float64}=[0.025, 0.5, 0.975],
+                      source::Integer=BB_RANK_CONDITIONAL, n_samples::Int=1000, seed::Integer=0,
+                      draws::Union{Nothing,Matrix{Float64}}=nothing, want_ranks::Bool=false)
+    nc, nq, nt = length(sets), length(probs), length(top)
+    if draws !== nothing
+        D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+        size(draws, 1) == D || error("fitness_rank: draws must have $D rows")
+        n_samples = size(draws, 2)
+    end
+    set_ptr = Int64.(cumsum(vcat(0, length.(sets))))
+    set_idx = Int64[u for s in sets for u in s]
+    top64 = Int64.(top)
+    nix = length(set_idx)
+    rank_mean, rank_sd = Vector{Float64}(undef, nix), Vector{Float64}(undef, nix)
+    p_top, quantiles = Matrix{Float64}(undef, nt, nix), Matrix{Float64}(undef, nq, nix)
+    ranks = Matrix{Int32}(undef, want_ranks ? n_samples : 0, nix)
+    n_units = Vector{Int64}(undef, nc)
+    GC.@preserve probs top64 draws set_ptr set_idx rank_mean rank_sd p_top quantiles ranks n_units begin
+        o = bb_rank_opts(Int32(n_samples), Int32(nq), Int32(nt), Int32(source), Int32(0), Int32(0),
+                         nq > 0 ? pointer(probs) : Ptr{Float64}(C_NULL), nt > 0 ? pointer(top64) : Ptr{Int64}(C_NULL), UInt64(seed),
+                         draws === nothing ? Ptr{Float64}(C_NULL) : pointer(draws), Int64(nc), pointer(set_ptr), pointer(set_idx))
+        out = bb_rank_out(pointer(rank_mean), pointer(rank_sd), nt > 0 ? pointer(p_top) : Ptr{Float64}(C_NULL),
+                          nq > 0 ? pointer(quantiles) : Ptr{Float64}(C_NULL), want_ranks ? pointer(ranks) : Ptr{Int32}(C_NULL), pointer(n_units))
+        check(ccall((:bb_fitness_rank, LIB), Cint, (Ptr{Cvoid}, Ref{bb_rank_opts}, Ref{bb_rank_out}), h, o, out))
+    end
+    return (set_ptr=set_ptr, n_units=n_units, rank_mean=rank_mean, rank_sd=rank_sd, p_top=p_top, quantiles=quantiles, ranks=ranks)
+end
+
 # Rao-Blackwellised marginals of the population mean fitness sbar_g, g = (replicate, step) (bb_popmean_rb, include/barbay_hip.h):
 # the exact Gaussian full conditional of a step's population mean, summed over every barcode of the replicate (neutrals, then
 # mutants) and averaged over the draws of `fitness_rb`.  Field for field the Python binding's `bb_popmean_rb_out`
