@@ -20,6 +20,10 @@ BB_OPT_DECAYED_ADAGRAD = 1
 BB_COMM_ID_BYTES = 128
 BB_P2P_HANDLE_BYTES = 64
 BB_LOGP_MAX_BATCH = 64
+BB_HMC_MAX_WALKERS = BB_LOGP_MAX_BATCH
+BB_HMC_MAX_LEAPFROG = 1024
+BB_HMC_STREAM0 = 0xFFFFFF00
+BB_HMC_CHUNK = 2048
 BB_CHAIN_MAX_K = 16384
 BB_CHAIN_MAX_Q = 8
 BB_CHAIN_LAG_BATCH = 32
@@ -49,7 +53,7 @@ BB_ERR_NONFINITE = -5
 EXPORTS = [
     "bb_version", "bb_last_error", "bb_default_opts", "bb_create", "bb_destroy", "bb_num_latents",
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
-    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
+    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_hmc_begin", "bb_hmc_step", "bb_hmc_get", "bb_hmc_end", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_loo_shape", "bb_ppc_loo", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_dfe_rb", "bb_fitness_rank", "bb_popmean_rb_shape", "bb_popmean_rb",
@@ -85,6 +89,22 @@ class bb_advi_opts(C.Structure):
         ("steps_per_graph", C.c_int32), ("elbo_every", C.c_int32), ("launch_mode", C.c_int32),
         ("n_devices", C.c_int32), ("device_ids", C.POINTER(C.c_int32)),
     ]
+
+
+class bb_hmc_opts(C.Structure):
+    _fields_ = [("n_walkers", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64), ("inv_mass", _dp)]
+
+
+class bb_hmc_step_opts(C.Structure):
+    _fields_ = [("transition", C.c_uint32), ("reserved0", C.c_int32), ("eps", _dp), ("n_leapfrog", C.POINTER(C.c_int32)), ("log_u", _dp)]
+
+
+class bb_hmc_step_out(C.Structure):
+    _fields_ = [("h0", _dp), ("h1", _dp), ("kinetic0", _dp), ("kinetic1", _dp), ("logp_prop", _dp), ("logp", _dp),
+                ("accepted", C.POINTER(C.c_int32)), ("divergent", C.POINTER(C.c_int32))]
+
+
+HMC_STEP_FIELDS = ("h0", "h1", "kinetic0", "kinetic1", "logp_prop", "logp", "accepted", "divergent")
 
 
 class bb_block_range(C.Structure):
@@ -314,6 +334,11 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     lib.bb_elbo_grad.argtypes = [vp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]
     lib.bb_logdensity_grad.argtypes = [vp, _dp, _dp, _dp]
     lib.bb_logdensity_grad_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    if hasattr(lib, "bb_hmc_begin"):            # (A/B builds of older sources, tools/xp.py)
+        lib.bb_hmc_begin.argtypes = [vp, C.POINTER(bb_hmc_opts), _dp, _dp]
+        lib.bb_hmc_step.argtypes = [vp, C.POINTER(bb_hmc_step_opts), C.POINTER(bb_hmc_step_out)]
+        lib.bb_hmc_get.argtypes = [vp, _dp, _dp, _dp]
+        lib.bb_hmc_end.argtypes = [vp]
     lib.bb_get_elbo_trace.argtypes = [vp, C.c_int64, C.c_int64, _dp]
     lib.bb_debug_normals.argtypes = [vp, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _dp]
     if hasattr(lib, "bb_debug_math"):           # (A/B builds of older sources, tools/xp.py)
@@ -412,6 +437,20 @@ def _f64(a) -> np.ndarray:
 
 def _ptr(a: np.ndarray, ty=_dp):
     return a.ctypes.data_as(ty)
+
+
+class HmcSession:
+    """What `Engine.hmc_begin` returns: `logp` [W] at the start points; ends the session when used as a context manager."""
+
+    def __init__(self, engine: "Engine", logp: np.ndarray):
+        self.engine, self.logp = engine, logp
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        if getattr(self.engine, "_h", None) is not None and self.engine._h.value:
+            self.engine.hmc_end()
 
 
 class Engine:
@@ -654,6 +693,55 @@ class Engine:
         g = np.empty((W, self.D))
         self._check(self._lib.bb_logdensity_grad_batch(self._h, W, _ptr(Z), _ptr(lp), _ptr(g)))
         return lp, g
+
+    def hmc_begin(self, z0, *, seed: int = 0, inv_mass=None) -> "HmcSession":
+        """Opens the device-resident HMC session (`bb_hmc_begin`): z0 is [W, D] (or [D]), W <= BB_HMC_MAX_WALKERS walkers whose position,
+        momentum and gradient stay on the device until `hmc_end`; `inv_mass` [D] is the diagonal metric (None: ones), `seed` the key of the
+        momentum draws.  Returns the session, whose `logp` holds log p at z0 (a non-finite value is reported, not raised); it is a context
+        manager that ends the session on exit.  A second `hmc_begin` replaces the session."""
+        z0 = np.ascontiguousarray(z0, dtype=np.float64)
+        if z0.ndim == 1:
+            z0 = z0[None, :]
+        assert z0.ndim == 2 and z0.shape[1] == self.D
+        o = bb_hmc_opts()
+        o.n_walkers, o.reserved0, o.seed = z0.shape[0], 0, int(seed)
+        if inv_mass is not None:
+            inv_mass = _f64(inv_mass)
+            assert inv_mass.shape == (self.D,)
+            o.inv_mass = _ptr(inv_mass)
+        lp = np.empty(z0.shape[0])
+        self._check(self._lib.bb_hmc_begin(self._h, C.byref(o), _ptr(z0), _ptr(lp)))
+        self._hmc_W = z0.shape[0]
+        return HmcSession(self, lp)
+
+    def hmc_step(self, transition: int, eps, n_leapfrog, log_u) -> Dict[str, np.ndarray]:
+        """One HMC transition of every walker of the session (`bb_hmc_step`): `eps`, `n_leapfrog`, `log_u` are [W] (scalars are
+        broadcast); walker w's momenta are the engine's normals (i, step=transition, stream=BB_HMC_STREAM0 + w).  Returns h0, h1,
+        kinetic0, kinetic1, logp_prop, logp (of the state held after the call), accepted, divergent, each [W]."""
+        W = self._hmc_W
+        eps = _f64(np.broadcast_to(np.asarray(eps, dtype=np.float64), (W,)))
+        nl = np.ascontiguousarray(np.broadcast_to(np.asarray(n_leapfrog), (W,)), dtype=np.int32)
+        lu = _f64(np.broadcast_to(np.asarray(log_u, dtype=np.float64), (W,)))
+        ip = C.POINTER(C.c_int32)
+        o = bb_hmc_step_opts()
+        o.transition, o.reserved0, o.eps, o.n_leapfrog, o.log_u = int(transition), 0, _ptr(eps), _ptr(nl, ip), _ptr(lu)
+        res = {k: np.empty(W, dtype=np.int32 if k in ("accepted", "divergent") else np.float64) for k in HMC_STEP_FIELDS}
+        out = bb_hmc_step_out()
+        for k in HMC_STEP_FIELDS:
+            setattr(out, k, _ptr(res[k], ip if res[k].dtype == np.int32 else _dp))
+        self._check(self._lib.bb_hmc_step(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def hmc_get(self, grad: bool = False):
+        """The walkers' current positions [W, D] and log-densities [W] (`bb_hmc_get`); with `grad`, the gradients [W, D] too."""
+        W = self._hmc_W
+        z, lp = np.empty((W, self.D)), np.empty(W)
+        g = np.empty((W, self.D)) if grad else None
+        self._check(self._lib.bb_hmc_get(self._h, _ptr(z), _ptr(lp), _ptr(g) if grad else None))
+        return (z, lp, g) if grad else (z, lp)
+
+    def hmc_end(self):
+        self._check(self._lib.bb_hmc_end(self._h))
 
     def hier_units(self) -> int:
         """Length of the theta_tilde block (0 for the non-hierarchical models)."""

@@ -119,6 +119,26 @@ extern "C" int bb_hier_fitness(bb_handle* h, int32_t n_samples, uint64_t seed, d
 }
 
 // ---- log-joint and gradient at a batch of points (bb_logp.h) --------------------------------------------------------------------
+// the launches that evaluate B's points (B.W of them) into B.logp and B.grad; shared with the HMC session (bb_hmc_host.h)
+static int logp_launch(bb_handle* h, const LogpArgs& B) {
+    const DevModel& M = h->M;
+    const RunArgs A = make_args(h, 0, 0, 1, false, true);
+    const int grid = h->nblk * B.W;
+    int rc = 0;
+    by_kind(M.kind, [&](auto kindc) {
+        constexpr int KIND = decltype(kindc)::value;
+        rc = launch(h->stream, k_logp_moments<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
+        if (!rc) rc = launch(h->stream, k_logp_grad<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
+    });
+    if (rc) return rc;
+    if (M.kind == BB_MODEL_GENOTYPE) {
+        const int gsb = (int)std::min<long long>((M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block (as k_geno_sum)
+        if ((rc = launch(h->stream, k_logp_geno, gsb * B.W, 256, 256, desc_ptr(h->dM, &h->M), B, gsb))) return rc;
+    }
+    return BB_OK;
+}
+// the constant of the log-joint (the ELBO's constant carries the entropy's: not part of the log-joint)
+static double logp_const(const bb_handle* h) { return h->elbo_const - 0.5 * (double)h->M.D * (1.0 + BB_LOG2PI); }
 // n_points points in one call: three launches on buffers of the handle's own, the variational state untouched.  Caller's order <->
 // the handle's order once per batch, on the host.
 extern "C" int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z, double* logp, double* grad) {
@@ -147,7 +167,7 @@ extern "C" int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const do
     B.z = dz;
     B.Dz = (long long)Dz; B.nbs = (long long)nbs; B.Gs = (long long)Gs;
     B.nt = h->nblk; B.W = n_points;
-    B.c0 = h->elbo_const - 0.5 * (double)M.D * (1.0 + BB_LOG2PI);      // (the ELBO's constant carries the entropy's: not part of the log-joint)
+    B.c0 = logp_const(h);
     const bool direct = h->cidx.empty() && Dz == D;    // rows can be copied as they are
     if (!direct) {
         h->logp_host.resize(W * Dz + Wp);
@@ -159,18 +179,7 @@ extern "C" int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const do
         }
     }
     if ((rc = h2d(dz, direct ? z : h->logp_host.data(), W * Dz * 8, h->stream))) return rc;
-    const RunArgs A = make_args(h, 0, 0, 1, false, true);
-    const int grid = h->nblk * n_points;
-    by_kind(M.kind, [&](auto kindc) {
-        constexpr int KIND = decltype(kindc)::value;
-        rc = launch(h->stream, k_logp_moments<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
-        if (!rc) rc = launch(h->stream, k_logp_grad<KIND>, grid, h->nthr, h->lds_doubles, desc_ptr(h->dM, &h->M), B, A, h->NB);
-    });
-    if (rc) return rc;
-    if (geno) {
-        const int gsb = (int)std::min<long long>((M.G + 31) / 32, 1024);      // 32 genotypes per 256-thread block (as k_geno_sum)
-        if ((rc = launch(h->stream, k_logp_geno, gsb * n_points, 256, 256, desc_ptr(h->dM, &h->M), B, gsb))) return rc;
-    }
+    if ((rc = logp_launch(h, B))) return rc;
     if (!grad) return logp ? d2h(logp, B.logp, W * 8, h->stream) : dsync(h->stream);
     if (direct) {
         if ((rc = d2h(grad, B.grad, W * D * 8, h->stream))) return rc;

@@ -535,6 +535,27 @@ BB_KERNEL(256, k_logp_geno, const DevModel* __restrict__ Mp, LogpArgs B, int gsb
     BB_CTX;
     bb_block_logp_geno(cx, M, B, gsb);
 }
+// bb_hmc_step (bb_hmc.h): grid = chunk + n_chunks * walker; k_hmc_reduce: grid = walkers
+BB_KERNEL(BB_HMC_NT, k_hmc_momentum, HmcArgs H) {
+    BB_CTX;
+    bb_block_hmc_momentum(cx, H);
+}
+BB_KERNEL(BB_HMC_NT, k_hmc_kick_drift, HmcArgs H, int k) {
+    BB_CTX;
+    bb_block_hmc_kick_drift(cx, H, k);
+}
+BB_KERNEL(BB_HMC_NT, k_hmc_kick_energy, HmcArgs H, int k) {
+    BB_CTX;
+    bb_block_hmc_kick_energy(cx, H, k);
+}
+BB_KERNEL(64, k_hmc_reduce, HmcArgs H, int which, int k) {
+    BB_CTX;
+    bb_block_hmc_reduce(cx, H, which, k);
+}
+BB_KERNEL(BB_HMC_NT, k_hmc_keep, HmcArgs H) {
+    BB_CTX;
+    bb_block_hmc_keep(cx, H);
+}
 #ifndef BB_EMU
 // transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
 __global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {

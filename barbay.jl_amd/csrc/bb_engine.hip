@@ -1,6 +1,7 @@
 // bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the resident launchers, groups and the cross-GPU
 // leg; what a step launches is in bb_step.h, the launch plan in bb_plan.h, handle creation in bb_create.h, the run path (bb_run and its
-// kin) in bb_run.h and the post-fit entry points (hier fitness, log-density batch, bands, scores, chain summary) in bb_analysis.h, all included below.
+// kin) in bb_run.h, the post-fit entry points (hier fitness, log-density batch, bands, scores, chain summary) in bb_analysis.h and the HMC
+// session in bb_hmc_host.h, all included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -30,6 +31,7 @@
 #include "bb_chain.h"
 #include "bb_trace.h"
 #include "bb_logp.h"
+#include "bb_hmc.h"
 #include "bb_mathprobe.h"
 
 #include <algorithm>
@@ -144,6 +146,7 @@ enum {
     BUF_BANDS,     // bb_ppc_bands / bb_freq_bands: parameters, tables, scratch and bands of the last call
     BUF_LOGP,      // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
     BUF_CHAIN,     // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
+    BUF_HMC,       // bb_hmc_*: the session's walkers (state, proposal, momentum), metric and evaluation scratch; kept from begin to end
     BUF_COUNT
 };
 
@@ -186,6 +189,12 @@ struct bb_handle {
     double* bak_om = nullptr;
     DevBuf buf[BUF_COUNT];             // the calls' own device buffers (BUF_*)
     std::vector<double> logp_host;     // bb_logdensity_grad_batch: host staging (rows padded to an even length, the handle's latent order)
+    // the HMC session (bb_hmc_*, bb_hmc_host.h): on while hmc_on is set; the device pointers of hmc / hmc_eval lie in buf[BUF_HMC]
+    bool hmc_on = false, hmc_ever = false;      // (hmc_ever: a session was begun at some time -- what bb_hmc_end asks)
+    HmcArgs hmc{};
+    LogpArgs hmc_eval{};               // the evaluation of the proposal rows (its z, grad, logp, lf_* are set per launch)
+    double* hmc_tab = nullptr;         // device: eps [Wp] | n_leapfrog [Wp ints] of the transition; hmc.accept lies behind
+    std::vector<double> hmc_logp;      // host mirror of the walkers' logp
     // the iterate trace (bb_trace_*, bb_trace.h): on while trace_ring is set
     double* trace_ring = nullptr;      // [trace_cap][2 D], the handle's own allocation (bb_trace_end frees it)
     int trace_every = 0, trace_cap = 0;
@@ -999,6 +1008,9 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
 
 // the post-fit entry points: bb_hier_fitness, bb_logdensity_grad_batch, bb_ppc_bands, bb_freq_bands, bb_chain_summary
 #include "bb_analysis.h"
+
+// the HMC session: bb_hmc_begin, bb_hmc_step, bb_hmc_get, bb_hmc_end (bb_hmc.h)
+#include "bb_hmc_host.h"
 
 extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
     if (!h || !s) return bb_fail(BB_ERR_INVALID, "null argument");

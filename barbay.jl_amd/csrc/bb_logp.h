@@ -28,7 +28,12 @@ struct LogpArgs {
     long long Dz, nbs, Gs;    // row strides (even: pairs stay 16-byte aligned)
     int nt, W;                // tiles per point, points
     double c0;                // constant of the log-joint: prior and likelihood normalisers, lgamma terms
+    const int* lf_n;          // nullptr (bb_logdensity_grad_batch), or [W] (bb_hmc.h): point w is evaluated only while lf_k < lf_n[w]
+    int lf_k;
 };
+
+// a point that is not to be evaluated: its blocks leave at once (block-uniform: a block works on one point)
+BB_DEV bool bb_logp_idle(const LogpArgs& B, int w) { return B.lf_n && B.lf_k >= B.lf_n[w]; }
 
 // the view of point w's buffers the block programs of bb_block.h take as their state
 BB_DEV DevState bb_logp_view(const DevModel& M, const LogpArgs& B, int w) {
@@ -56,6 +61,7 @@ BB_DEV double bb_logp_prior_quad(const DevModel& M, int blk, long long i, double
 template <int KIND>
 BB_DEV void bb_block_logp_moments(BBCtx& cx0, const DevModel& M, const LogpArgs& B, const RunArgs& A, int NB) {
     const int w = cx0.block / B.nt;
+    if (bb_logp_idle(B, w)) return;
     BBCtx cx{cx0.nthr, cx0.block - w * B.nt, cx0.lds};
     const BBLds L = bb_lds_layout(M.R, M.E, KIND, M.Ttot, M.nt1, M.K, NB, cx.nthr);
     double* lds = cx.lds;
@@ -111,6 +117,7 @@ BB_DEV void bb_block_logp_moments(BBCtx& cx0, const DevModel& M, const LogpArgs&
 template <int KIND>
 BB_DEV void bb_block_logp_grad(BBCtx& cx0, const DevModel& M, const LogpArgs& B, const RunArgs& A0, int NB) {
     const int w = cx0.block / B.nt;
+    if (bb_logp_idle(B, w)) return;
     BBCtx cx{cx0.nthr, cx0.block - w * B.nt, cx0.lds};
     const BBLds L = bb_lds_layout(M.R, M.E, KIND, M.Ttot, M.nt1, M.K, NB, cx.nthr);
     double* lds = cx.lds;
@@ -168,6 +175,7 @@ BB_DEV void bb_block_logp_grad(BBCtx& cx0, const DevModel& M, const LogpArgs& B,
 // LDS: nthr doubles (bb_block_geno_sum)
 BB_DEV void bb_block_logp_geno(BBCtx& cx0, const DevModel& M, const LogpArgs& B, int gsb) {
     const int w = cx0.block / gsb;
+    if (bb_logp_idle(B, w)) return;
     BBCtx cx{cx0.nthr, cx0.block - w * gsb, cx0.lds};
     const double* z = B.z + (long long)w * B.Dz;
     double* grad = B.grad + (long long)w * B.Dz;

@@ -177,6 +177,94 @@ def nuts_ensemble(fbatch: Callable, z0s, n_steps, n_adapt, *, rngs: Sequence[np.
     return results
 
 
+def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Generator], target_accept: float = 0.65,
+                 minv: Optional[np.ndarray] = None, n_leapfrog=(8, 24), thin: int = 1, seed: int = 0):
+    """len(z0s) <= BB_HMC_MAX_WALKERS chains of Hamiltonian Monte Carlo (diagonal metric `minv`, a fixed number of leapfrogs per
+    transition) whose position, momentum and gradient stay on the device (`Engine.hmc_begin / hmc_step / hmc_get / hmc_end`,
+    csrc/bb_hmc.h): one call makes one transition of every walker, only scalars come back, and positions are downloaded when a draw
+    is kept (every `thin`-th transition after the warm-up).  `engine` is an Engine, or anything with those four methods.
+
+    Per transition walker w draws its number of leapfrogs uniformly from the closed range `n_leapfrog` and log(u) from rngs[w] -- and
+    reads no other generator; the momenta are the engine's own normals (key `seed`, stream BB_HMC_STREAM0 + w, step = the transition's
+    number).  The start step size follows `_find_step`'s doubling rule, run as probes (one leapfrog, never accepted, all on transition
+    0); during the `n_adapt` warm-up transitions, which are discarded, the step size is adapted by dual averaging with `_walker`'s constants
+    on alpha = min(1, exp(h1 - h0)), 0 for a divergent trajectory.  `n_steps` / `n_adapt` may be sequences, one value per walker: a
+    walker that has finished is stepped on as a probe and disturbs no one.  The default range (8, 24) of `n_leapfrog` has been tuned by
+    nobody.
+
+    Returns a list, per walker, of what `nuts` returns: (chain[n_steps, D], logp[n_steps], info), info holding `step_size`, `n_grad`
+    (leapfrogs, probes included), `accept_rate` and `divergences` (both over the transitions after the warm-up) and `mean_leapfrog`."""
+    W = len(z0s)
+    if len(rngs) != W:
+        raise BarBayError("hmc_ensemble needs one random generator per walker")
+    lo_l, hi_l = (int(n_leapfrog), int(n_leapfrog)) if np.ndim(n_leapfrog) == 0 else (int(n_leapfrog[0]), int(n_leapfrog[1]))
+    if not 1 <= lo_l <= hi_l or thin < 1:
+        raise BarBayError(f"n_leapfrog must be a range 1 <= lo <= hi and thin >= 1, not {n_leapfrog!r}, {thin!r}")
+    per = lambda v, w: int(v[w]) if np.ndim(v) else int(v)
+    n_st = np.array([per(n_steps, w) for w in range(W)])
+    n_ad = np.array([per(n_adapt, w) for w in range(W)])
+    Z0 = np.stack([np.asarray(z, dtype=np.float64) for z in z0s])
+    D = Z0.shape[1]
+    session = engine.hmc_begin(Z0, seed=seed, inv_mass=minv)
+    try:
+        if not np.isfinite(session.logp).all():
+            raise BarBayError("log density is not finite at the initial point")
+        n_grad = np.zeros(W, dtype=np.int64)
+        # the start step size: _find_step's rule on probes of one leapfrog, every probe with transition 0's momenta
+        eps = np.ones(W)
+        dh = lambda r: np.where(np.isfinite(r["h1"]), r["h1"] - r["h0"], -np.inf)
+        d = dh(engine.hmc_step(0, eps, 1, np.inf))
+        n_grad += 1
+        a = np.where(d > np.log(0.5), 1.0, -1.0)
+        done = np.zeros(W, dtype=bool)
+        for _ in range(60):
+            done |= a * d <= -a * np.log(2.0)
+            if done.all():
+                break
+            eps = np.where(done, eps, eps * 2.0 ** a)
+            d = np.where(done, d, dh(engine.hmc_step(0, eps, 1, np.inf)))
+            n_grad += ~done
+        mu, eps_bar, h_bar = np.log(10.0 * eps), np.ones(W), np.zeros(W)
+        gamma, t0, kappa = 0.05, 10.0, 0.75
+        chains = [np.empty((n_st[w], D)) for w in range(W)]
+        lps = [np.empty(n_st[w]) for w in range(W)]
+        acc, div, leaps = np.zeros(W), np.zeros(W, dtype=np.int64), np.zeros(W)
+        total = n_ad + n_st * thin
+        for m in range(1, int(total.max()) + 1):
+            live = m <= total
+            L, logu = np.ones(W, dtype=np.int32), np.full(W, np.inf)          # (a finished walker: a probe)
+            for w in np.flatnonzero(live):
+                L[w] = rngs[w].integers(lo_l, hi_l + 1)
+                logu[w] = np.log(rngs[w].random())
+            r = engine.hmc_step(m, eps, L, logu)
+            n_grad += np.where(live, L, 0)
+            alpha = np.where(r["divergent"] != 0, 0.0, np.minimum(1.0, np.exp(np.minimum(0.0, dh(r)))))
+            keep = None
+            for w in np.flatnonzero(live):
+                if m <= n_ad[w]:
+                    h_bar[w] = (1.0 - 1.0 / (m + t0)) * h_bar[w] + (target_accept - alpha[w]) / (m + t0)
+                    eps[w] = float(np.exp(mu[w] - np.sqrt(m) / gamma * h_bar[w]))
+                    x = m ** -kappa
+                    eps_bar[w] = float(np.exp(x * np.log(eps[w]) + (1.0 - x) * np.log(eps_bar[w])))
+                    if m == n_ad[w]:
+                        eps[w] = eps_bar[w]
+                    continue
+                acc[w] += r["accepted"][w]
+                div[w] += r["divergent"][w]
+                leaps[w] += L[w]
+                if (m - n_ad[w]) % thin == 0:
+                    if keep is None:
+                        keep = engine.hmc_get()                               # (one download for all the walkers that keep this draw)
+                    k = (m - n_ad[w]) // thin - 1
+                    chains[w][k] = keep[0][w]
+                    lps[w][k] = keep[1][w]
+    finally:
+        engine.hmc_end()
+    post = np.maximum(n_st * thin, 1)
+    return [(chains[w], lps[w], {"step_size": float(eps[w]), "n_grad": int(n_grad[w]), "accept_rate": float(acc[w] / post[w]),
+                                 "divergences": int(div[w]), "mean_leapfrog": float(leaps[w] / post[w])}) for w in range(W)]
+
+
 SUMMARY_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)                  # MCMCChains.quantile's default q
 _SUMMARY_KEYS = (("mean", "mean"), ("std", "sd"), ("mcse", "mcse"), ("ess", "ess"), ("rhat", "rhat"))
 
@@ -232,7 +320,8 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
                 neutral_col="neutral", rep_col: Optional[str] = None, env_col: Optional[str] = None,
                 genotype_col: Optional[str] = None, rm_T0: bool = False, target_accept: float = 0.65,
                 n_adapt: Optional[int] = None, advi_steps: int = 3000, verbose: bool = True, seed: int = 0, device: int = 0,
-                engine_kwargs: Optional[Dict] = None, ensemble: str = "serial", summary: bool = False):
+                engine_kwargs: Optional[Dict] = None, ensemble: str = "serial", summary: bool = False, sampler: str = "nuts",
+                hmc_kwargs: Optional[Dict] = None):
     """src/mcmc.jl:86-160.  `sampler = Turing.NUTS(0.65)` becomes `target_accept`.  `ensemble` (the reference's
     `MCMCSerial()` / `MCMCThreads()` / `MCMCDistributed()`, all on one device here): "serial" runs the walkers one after another,
     all drawing from `default_rng(seed)`; "batched" steps them in lock-step, walker w drawing from `default_rng([seed, w])`, every
@@ -241,7 +330,13 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
     `summary` adds the chain diagnostics of every parameter (`Engine.chain_summary` on the same handle) to the output under
     `summary_mean, summary_std, summary_mcse, summary_ess, summary_rhat, summary_quantiles` (at `summary_probs`), `summary_n_lags`;
     `summarize` tabulates them.  It needs n_steps >= 4 and n_walkers * n_steps <= 16384 (BB_CHAIN_MAX_K: one pooled column in
-    LDS), which is checked before anything is sampled."""
+    LDS), which is checked before anything is sampled.
+    `sampler`: "nuts" (the default, the paths above) or "hmc": `hmc_ensemble` from the same ADVI start and metric, all walkers in
+    lock-step with their state on the device (chunks of BB_HMC_MAX_WALKERS = 64 walkers; `ensemble` plays no part), walker w drawing from
+    `default_rng([seed, w])`; `hmc_kwargs` go to `hmc_ensemble` (`n_leapfrog`, `thin`).  Its output has the same keys and
+    `accept_rate`, `divergences`, `n_grad` per walker."""
+    if sampler not in ("nuts", "hmc"):
+        raise BarBayError(f"sampler must be 'nuts' or 'hmc', not {sampler!r}")
     if ensemble not in ("serial", "batched"):
         raise BarBayError(f"ensemble must be 'serial' or 'batched', not {ensemble!r}")
     if summary and (n_walkers < 1 or n_steps < 4 or n_walkers * n_steps > BB_CHAIN_MAX_K):
@@ -286,15 +381,20 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
         chains, lps, infos = [], [], []
         spread = 0.1 if advi_steps > 0 else 0.0
         batched = []
-        if ensemble == "batched":
+        lockstep = ensemble == "batched" or sampler == "hmc"
+        if lockstep:
             rngs = [np.random.default_rng([seed, w]) for w in range(n_walkers)]
             z0s = [mean + np.sqrt(minv) * r.standard_normal(mean.shape[0]) * spread for r in rngs]
-            for lo in range(0, n_walkers, BB_LOGP_MAX_BATCH):
+            for lo in range(0, n_walkers, BB_LOGP_MAX_BATCH):                 # (= BB_HMC_MAX_WALKERS)
                 hi = min(lo + BB_LOGP_MAX_BATCH, n_walkers)
-                batched += nuts_ensemble(e.logdensity_grad_batch, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi],
-                                         target_accept=target_accept, minv=minv)
+                if sampler == "hmc":                                          # (a walker's stream is its index in the chunk: a key per chunk)
+                    batched += hmc_ensemble(e, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi], target_accept=target_accept, minv=minv,
+                                            seed=(seed + 0x9E3779B97F4A7C15 * (lo // BB_LOGP_MAX_BATCH)) % 2 ** 64, **(hmc_kwargs or {}))
+                else:
+                    batched += nuts_ensemble(e.logdensity_grad_batch, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi],
+                                             target_accept=target_accept, minv=minv)
         for w in range(n_walkers):
-            if ensemble == "batched":
+            if lockstep:
                 c, lp, info = batched[w]
             else:
                 z0 = mean + np.sqrt(minv) * rng.standard_normal(mean.shape[0]) * spread
@@ -302,7 +402,10 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
             chains.append(c)
             lps.append(lp)
             infos.append(info)
-            if verbose:
+            if verbose and sampler == "hmc":
+                log.info("walker %d: step size %.3g, acceptance %.2f, %d divergences, %d gradients", w + 1, info["step_size"],
+                         info["accept_rate"], info["divergences"], info["n_grad"])
+            elif verbose:
                 log.info("walker %d: step size %.3g, mean tree depth %.2f, %d gradients", w + 1, info["step_size"],
                          info["mean_tree_depth"], info["n_grad"])
         summ = _summary_arrays(e, np.stack(chains), SUMMARY_PROBS) if summary else {}
@@ -311,6 +414,8 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
         var_names += [f"{sym}[{x}]" for x in range(1, hi - lo + 1)]
     out = {"ids": np.asarray(arrays.bc_ids, dtype=object), "var_names": np.asarray(var_names, dtype=object),
            "chain": np.stack(chains), "logp": np.stack(lps), "step_size": np.asarray([i["step_size"] for i in infos]), **summ}
+    if sampler == "hmc":
+        out.update({k: np.asarray([i[k] for i in infos]) for k in ("accept_rate", "divergences", "n_grad")})
     if fname is None:
         return out
     if verbose:

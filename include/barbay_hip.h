@@ -296,6 +296,71 @@ int bb_logdensity_grad(bb_handle* h, const double* z, double* logp, double* grad
 int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z /* [n_points][D], caller's order */,
                              double* logp /* [n_points] or NULL */, double* grad /* [n_points][D] or NULL */);
 
+/* ---- device-resident HMC trajectories (csrc/bb_hmc.h) ---------------------------------------------------------------------------
+ * Hamiltonian Monte Carlo with a diagonal metric and a fixed number of leapfrogs per transition, chosen per walker by the caller.
+ * Position, momentum and gradient of every walker stay on the device from bb_hmc_begin to bb_hmc_end; one bb_hmc_step makes one
+ * transition of all walkers and brings back scalars only; bb_hmc_get downloads the walkers' positions when a draw is kept.  The NUTS
+ * tree of barbay.jl_amd.mcmc stays on the host (bb_logdensity_grad_batch).  No reference counterpart: the reference samples with
+ * Turing.NUTS (src/mcmc.jl:86-160).
+ *
+ * bb_hmc_begin: a session of n_walkers walkers at z0 on a buffer of its own -- a bb_logdensity_grad_batch between two steps does not
+ *  disturb a session, nor a session that call.  Per walker the device holds z, g = d log p / d z, logp, the proposal z', g' and the
+ *  momentum r, rows of even stride in the handle's latent order.  inv_mass (NULL: ones) and 1 / sqrt(inv_mass) -- both formed on the host,
+ *  correctly rounded sqrt, then the division -- are uploaded in that order, and the caller-index map where the handle regrouped
+ *  (bb_get_permutation).  logp and g at z0 come from the kernels of bb_logdensity_grad_batch: logp[w] is what that call returns at z0[w],
+ *  bit for bit.  A start whose logp is not finite is reported in logp and is not an error.  A second bb_hmc_begin replaces the session;
+ *  bb_destroy frees it.
+ * bb_hmc_step: one transition of every walker w, in this arithmetic (fma: one rounding):
+ *  - momentum: the latent with the CALLER's index i draws n = the normal (i, step = transition, stream = BB_HMC_STREAM0 + w) of the engine's
+ *    stream at `seed` (pair q = i >> 1: even i the cosine branch, odd i the sine branch; bb_debug_normals on a handle created with the
+ *    same seed returns it), r_i = n * (1 / sqrt(inv_mass_i)), kinetic0 = 0.5 * sum_i inv_mass_i r_i r_i;
+ *  - trajectory: half = 0.5 * eps[w]; n_leapfrog[w] times { r = fma(half, g, r); z = fma(eps[w] * inv_mass_i, r, z) with the product rounded
+ *    once; logp_prop, g at z; r = fma(half, g, r) };
+ *  - kinetic1 as kinetic0 from the final r; h0 = logp - kinetic0, h1 = logp_prop - kinetic1; divergent = h1 is not finite;
+ *    accepted = h1 is finite && log_u[w] < h1 - h0, decided on the host side of the call from the downloaded scalars.  An accepted walker's
+ *    (z', g', logp_prop) become its state; a rejected walker's state is bitwise what it was.  log_u = +Inf never accepts (a probe),
+ *    -Inf accepts whenever h1 is finite.
+ *  - order of the sums over i: the handle's latent order cut into chunks of BB_HMC_CHUNK (2048) latents.  Thread t of a chunk's 256 starts at
+ *    0.0 and takes latents 2 t + 512 j and 2 t + 512 j + 1 of the chunk, j = 0, 1, ..., as acc = fma(inv_mass_i r_i, r_i, acc); the threads'
+ *    sums are folded by halving (p[t] += p[t + s], s = 128, ..., 1); the chunks are added in chunk order onto 0.0; the total is halved.
+ *    No atomics.
+ *  - a walker whose n_leapfrog is used up takes no part in the further evaluations of the call (its workgroups leave at once).
+ *  - independence: a walker's outputs and new state are a function of its own (z, eps, n_leapfrog, log_u), inv_mass, seed, transition and
+ *    its session index w alone: bit-identical whatever n_walkers, whatever the other walkers' arguments or a non-finite neighbour,
+ *    whatever the handle's launch mode and whatever was called before.  The handle's mu, omega, optimiser state, step counter and RNG
+ *    position are untouched, bitwise.
+ * bb_hmc_get: the walkers' current z, logp and g, caller's order; bb_hmc_get's logp and grad equal bb_logdensity_grad_batch at its z.
+ * bb_hmc_end: closes the session (a second bb_hmc_end: BB_OK); the buffer stays with the handle until bb_destroy.
+ * Errors: BB_ERR_INVALID -- a null h, o or z0; n_walkers outside 1 .. BB_HMC_MAX_WALKERS; an inv_mass entry that is not finite or not > 0
+ *  (the message names its index); an eps that is not finite or not > 0, an n_leapfrog outside 1 .. BB_HMC_MAX_LEAPFROG or a NaN log_u (the
+ *  message names the walker); reserved0 != 0; bb_hmc_step or bb_hmc_get without a session, bb_hmc_end on a handle that never had one.  BB_ERR_UNSUPPORTED -- sharded
+ *  (world_size > 1) and multi-device (n_devices > 1) handles.  BB_ERR_DEVICE -- the device cannot allocate the session: nothing is kept. */
+#define BB_HMC_MAX_WALKERS   BB_LOGP_MAX_BATCH      /* 64 */
+#define BB_HMC_MAX_LEAPFROG  1024
+#define BB_HMC_STREAM0       0xFFFFFF00u            /* walker w draws on stream BB_HMC_STREAM0 + w; 0xFFFFFF00..3F are used by nothing else */
+#define BB_HMC_CHUNK         2048
+typedef struct bb_hmc_opts {
+    int32_t n_walkers;          /* 1 .. BB_HMC_MAX_WALKERS */
+    int32_t reserved0;          /* 0 */
+    uint64_t seed;              /* Philox key of the momentum draws */
+    const double* inv_mass;     /* [D], caller's order, finite and > 0; NULL: ones */
+} bb_hmc_opts;
+typedef struct bb_hmc_step_opts {
+    uint32_t transition;        /* Philox `step` of this transition's momenta */
+    int32_t reserved0;          /* 0 */
+    const double* eps;          /* [W] finite, > 0 */
+    const int32_t* n_leapfrog;  /* [W] 1 .. BB_HMC_MAX_LEAPFROG */
+    const double* log_u;        /* [W]; +Inf: never accept (a probe), -Inf: accept whenever h1 is finite; NaN is invalid */
+} bb_hmc_step_opts;
+typedef struct bb_hmc_step_out {   /* every pointer may be NULL; [W] */
+    double *h0, *h1, *kinetic0, *kinetic1, *logp_prop, *logp;   /* logp: of the state the walker holds AFTER the call */
+    int32_t *accepted, *divergent;                               /* divergent: h1 not finite */
+} bb_hmc_step_out;
+int bb_hmc_begin(bb_handle* h, const bb_hmc_opts* o, const double* z0 /* [W][D] caller's order */, double* logp /* [W] or NULL */);
+int bb_hmc_step(bb_handle* h, const bb_hmc_step_opts* o, const bb_hmc_step_out* out /* or NULL */);
+int bb_hmc_get(bb_handle* h, double* z /* [W][D] or NULL */, double* logp /* [W] or NULL */, double* grad /* [W][D] or NULL */);
+int bb_hmc_end(bb_handle* h);
+
 /* ELBO estimates recorded by bb_run (elbo_every > 0): values of steps
  * first_step, first_step + elbo_every, ... ; NaN where not recorded/kept. */
 int bb_get_elbo_trace(bb_handle* h, int64_t first_step, int64_t n, double* out);

@@ -888,6 +888,89 @@ function logdensity_grad_batch(h::Ptr{Cvoid}, Z::AbstractVecOrMat{Float64})
     return logp, grad
 end
 
+# Device-resident HMC trajectories (bb_hmc_begin / bb_hmc_step / bb_hmc_get / bb_hmc_end, include/barbay_hip.h): position, momentum and
+# gradient of up to BB_HMC_MAX_WALKERS walkers stay on the device between the calls.  Field for field the Python binding's `bb_hmc_opts`,
+# `bb_hmc_step_opts`, `bb_hmc_step_out` (barbay.jl_amd/_capi.py).  Like the rest of this file it has not been executed: no Julia here.
+const BB_HMC_MAX_WALKERS = BB_LOGP_MAX_BATCH
+const BB_HMC_MAX_LEAPFROG = 1024
+const BB_HMC_STREAM0 = 0xFFFFFF00
+struct bb_hmc_opts
+    n_walkers::Int32
+    reserved0::Int32
+    seed::UInt64
+    inv_mass::Ptr{Float64}
+end
+struct bb_hmc_step_opts
+    transition::UInt32
+    reserved0::Int32
+    eps::Ptr{Float64}
+    n_leapfrog::Ptr{Int32}
+    log_u::Ptr{Float64}
+end
+struct bb_hmc_step_out
+    h0::Ptr{Float64}
+    h1::Ptr{Float64}
+    kinetic0::Ptr{Float64}
+    kinetic1::Ptr{Float64}
+    logp_prop::Ptr{Float64}
+    logp::Ptr{Float64}
+    accepted::Ptr{Int32}
+    divergent::Ptr{Int32}
+end
+"""
+    hmc_begin(h, Z0; seed=0, inv_mass=nothing) -> logp
+
+Opens the session at the columns of `Z0` (D x W, W <= BB_HMC_MAX_WALKERS, or a vector); `inv_mass` (D) is the diagonal metric (`nothing`:
+ones).  Returns log p at the start points (a non-finite value is reported, not an error).  A second `hmc_begin` replaces the session.
+"""
+function hmc_begin(h::Ptr{Cvoid}, Z0::AbstractVecOrMat{Float64}; seed::Integer=0, inv_mass::Union{Nothing,AbstractVector{Float64}}=nothing)
+    Zc = Z0 isa AbstractVector ? reshape(collect(Z0), :, 1) : Matrix{Float64}(Z0)
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    size(Zc, 1) == D || error("hmc_begin: Z0 must have $D rows")
+    im = inv_mass === nothing ? Float64[] : Vector{Float64}(inv_mass)
+    inv_mass === nothing || length(im) == D || error("hmc_begin: inv_mass must have $D entries")
+    W = size(Zc, 2)
+    logp = Vector{Float64}(undef, W)
+    GC.@preserve im begin
+        o = bb_hmc_opts(Int32(W), Int32(0), UInt64(seed), inv_mass === nothing ? Ptr{Float64}(C_NULL) : pointer(im))
+        check(ccall((:bb_hmc_begin, LIB), Cint, (Ptr{Cvoid}, Ref{bb_hmc_opts}, Ptr{Float64}, Ptr{Float64}), h, o, Zc, logp))
+    end
+    return logp
+end
+"""
+    hmc_step(h, transition, eps, n_leapfrog, log_u) -> NamedTuple
+
+One transition of every walker of the session; `eps`, `n_leapfrog`, `log_u` have one entry per walker.  Returns `h0, h1, kinetic0, kinetic1,
+logp_prop, logp` (of the state held after the call), `accepted, divergent`.
+"""
+function hmc_step(h::Ptr{Cvoid}, transition::Integer, eps::AbstractVector{Float64}, n_leapfrog::AbstractVector{<:Integer}, log_u::AbstractVector{Float64})
+    W = length(eps)
+    length(n_leapfrog) == W && length(log_u) == W || error("hmc_step: eps, n_leapfrog and log_u need one entry per walker")
+    e, nl, lu = Vector{Float64}(eps), Vector{Int32}(n_leapfrog), Vector{Float64}(log_u)
+    h0, h1, k0, k1, lpp, lp = (Vector{Float64}(undef, W) for _ in 1:6)
+    acc, dvg = Vector{Int32}(undef, W), Vector{Int32}(undef, W)
+    GC.@preserve e nl lu h0 h1 k0 k1 lpp lp acc dvg begin
+        o = bb_hmc_step_opts(UInt32(transition), Int32(0), pointer(e), pointer(nl), pointer(lu))
+        out = bb_hmc_step_out(pointer(h0), pointer(h1), pointer(k0), pointer(k1), pointer(lpp), pointer(lp), pointer(acc), pointer(dvg))
+        check(ccall((:bb_hmc_step, LIB), Cint, (Ptr{Cvoid}, Ref{bb_hmc_step_opts}, Ref{bb_hmc_step_out}), h, o, out))
+    end
+    return (h0=h0, h1=h1, kinetic0=k0, kinetic1=k1, logp_prop=lpp, logp=lp, accepted=acc, divergent=dvg)
+end
+"""
+    hmc_get(h, W; grad=false) -> (Z, logp[, G])
+
+The `W` walkers' current positions (D x W), log-densities and, with `grad`, gradients (D x W).
+"""
+function hmc_get(h::Ptr{Cvoid}, W::Integer; grad::Bool=false)
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    Z, logp = Matrix{Float64}(undef, D, W), Vector{Float64}(undef, W)
+    G = grad ? Matrix{Float64}(undef, D, W) : Matrix{Float64}(undef, 0, 0)
+    check(ccall((:bb_hmc_get, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h, Z, logp, grad ? pointer(G) : Ptr{Float64}(C_NULL)))
+    return grad ? (Z, logp, G) : (Z, logp)
+end
+hmc_end(h::Ptr{Cvoid}) = check(ccall((:bb_hmc_end, LIB), Cint, (Ptr{Cvoid},), h))
+
 # Chain diagnostics (bb_chain_summary, include/barbay_hip.h): MCMCChains' summarystats + quantile of a host chain, on the device.
 # Field for field the Python binding's `bb_chain_opts` / `bb_chain_out` (barbay.jl_amd/_capi.py).
 const BB_CHAIN_MAX_K = 16384
