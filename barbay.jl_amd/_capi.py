@@ -24,6 +24,7 @@ BB_HMC_MAX_WALKERS = BB_LOGP_MAX_BATCH
 BB_HMC_MAX_LEAPFROG = 1024
 BB_HMC_STREAM0 = 0xFFFFFF00
 BB_HMC_CHUNK = 2048
+BB_HMC_MAX_SEGMENTS = 8
 BB_CHAIN_MAX_K = 16384
 BB_CHAIN_MAX_Q = 8
 BB_CHAIN_LAG_BATCH = 32
@@ -53,7 +54,9 @@ BB_ERR_NONFINITE = -5
 EXPORTS = [
     "bb_version", "bb_last_error", "bb_default_opts", "bb_create", "bb_destroy", "bb_num_latents",
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
-    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_hmc_begin", "bb_hmc_step", "bb_hmc_get", "bb_hmc_end", "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
+    "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_hmc_begin", "bb_hmc_step", "bb_hmc_get", "bb_hmc_end",
+    "bb_hmc_accum_begin", "bb_hmc_accum_add", "bb_hmc_accum_reset", "bb_hmc_accum_get", "bb_hmc_accum_stats", "bb_hmc_set_metric", "bb_hmc_get_metric",
+    "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_loo_shape", "bb_ppc_loo", "bb_chain_summary",
     "bb_fitness_rb_shape", "bb_fitness_rb", "bb_theta_rb_shape", "bb_theta_rb", "bb_contrast_rb", "bb_dfe_rb", "bb_fitness_rank", "bb_popmean_rb_shape", "bb_popmean_rb",
@@ -105,6 +108,18 @@ class bb_hmc_step_out(C.Structure):
 
 
 HMC_STEP_FIELDS = ("h0", "h1", "kinetic0", "kinetic1", "logp_prop", "logp", "accepted", "divergent")
+
+
+class bb_hmc_accum_opts(C.Structure):
+    _fields_ = [("n_segments", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class bb_hmc_accum_out(C.Structure):
+    _fields_ = [("mean", _dp), ("sd", _dp), ("mcse", _dp), ("ess", _dp), ("rhat", _dp), ("within", _dp), ("between", _dp),
+                ("n_total", C.POINTER(C.c_int64))]
+
+
+HMC_ACCUM_FIELDS = ("mean", "sd", "mcse", "ess", "rhat", "within", "between")
 
 
 class bb_block_range(C.Structure):
@@ -339,6 +354,14 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.bb_hmc_step.argtypes = [vp, C.POINTER(bb_hmc_step_opts), C.POINTER(bb_hmc_step_out)]
         lib.bb_hmc_get.argtypes = [vp, _dp, _dp, _dp]
         lib.bb_hmc_end.argtypes = [vp]
+    if hasattr(lib, "bb_hmc_accum_begin"):
+        lib.bb_hmc_accum_begin.argtypes = [vp, C.POINTER(bb_hmc_accum_opts)]
+        lib.bb_hmc_accum_add.argtypes = [vp, C.POINTER(C.c_int32)]
+        lib.bb_hmc_accum_reset.argtypes = [vp]
+        lib.bb_hmc_accum_get.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]
+        lib.bb_hmc_accum_stats.argtypes = [vp, C.POINTER(bb_hmc_accum_out)]
+        lib.bb_hmc_set_metric.argtypes = [vp, _dp]
+        lib.bb_hmc_get_metric.argtypes = [vp, _dp]
     lib.bb_get_elbo_trace.argtypes = [vp, C.c_int64, C.c_int64, _dp]
     lib.bb_debug_normals.argtypes = [vp, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _dp]
     if hasattr(lib, "bb_debug_math"):           # (A/B builds of older sources, tools/xp.py)
@@ -742,6 +765,52 @@ class Engine:
 
     def hmc_end(self):
         self._check(self._lib.bb_hmc_end(self._h))
+
+    def hmc_accum_begin(self, n_segments: int = 1):
+        """Running moments of the session's state on the device (`bb_hmc_accum_begin`): per walker and segment < `n_segments`
+        (<= BB_HMC_MAX_SEGMENTS) a mean and an m2 row, zeroed.  A second call replaces them; `hmc_begin` and `hmc_end` drop them."""
+        o = bb_hmc_accum_opts()
+        o.n_segments, o.reserved0 = int(n_segments), 0
+        self._check(self._lib.bb_hmc_accum_begin(self._h, C.byref(o)))
+
+    def hmc_accum_add(self, segment=0):
+        """One Welford step of every walker's current state into its `segment` [W] (a scalar broadcasts; -1: the walker is not added)."""
+        seg = np.ascontiguousarray(np.broadcast_to(np.asarray(segment), (self._hmc_W,)), dtype=np.int32)
+        self._check(self._lib.bb_hmc_accum_add(self._h, _ptr(seg, C.POINTER(C.c_int32))))
+
+    def hmc_accum_reset(self):
+        self._check(self._lib.bb_hmc_accum_reset(self._h))
+
+    def hmc_accum_get(self, w: int, s: int):
+        """(mean [D], m2 [D], n) of walker `w`'s segment `s` (`bb_hmc_accum_get`)."""
+        mean, m2, n = np.empty(self.D), np.empty(self.D), C.c_int64(0)
+        self._check(self._lib.bb_hmc_accum_get(self._h, int(w), int(s), _ptr(mean), _ptr(m2), C.byref(n)))
+        return mean, m2, int(n.value)
+
+    def hmc_accum_stats(self) -> Dict[str, np.ndarray]:
+        """Pooled statistics of everything added (`bb_hmc_accum_stats`): mean, sd, mcse, ess, rhat, within, between, each [D], and n_total.
+        `ess` is a batch-means estimate over the live (walker, segment) chains, not Geyer's (include/barbay_hip.h)."""
+        res = {k: np.empty(self.D) for k in HMC_ACCUM_FIELDS}
+        n = C.c_int64(0)
+        out = bb_hmc_accum_out()
+        for k in HMC_ACCUM_FIELDS:
+            setattr(out, k, _ptr(res[k]))
+        out.n_total = C.pointer(n)
+        self._check(self._lib.bb_hmc_accum_stats(self._h, C.byref(out)))
+        res["n_total"] = int(n.value)
+        return res
+
+    def hmc_set_metric(self, inv_mass=None):
+        """Replaces the session's diagonal metric (`bb_hmc_set_metric`; None: ones); positions, gradients and accumulators stay."""
+        if inv_mass is not None:
+            inv_mass = _f64(inv_mass)
+            assert inv_mass.shape == (self.D,)
+        self._check(self._lib.bb_hmc_set_metric(self._h, _ptr(inv_mass) if inv_mass is not None else None))
+
+    def hmc_get_metric(self) -> np.ndarray:
+        im = np.empty(self.D)
+        self._check(self._lib.bb_hmc_get_metric(self._h, _ptr(im)))
+        return im
 
     def hier_units(self) -> int:
         """Length of the theta_tilde block (0 for the non-hierarchical models)."""

@@ -556,6 +556,15 @@ BB_KERNEL(BB_HMC_NT, k_hmc_keep, HmcArgs H) {
     BB_CTX;
     bb_block_hmc_keep(cx, H);
 }
+// bb_hmc_accum_* (bb_hmc_accum.h): k_hmc_accum on bb_hmc_step's grid; k_hmc_accum_stats: grid = pairs of latents / BB_HMC_NT
+BB_KERNEL(BB_HMC_NT, k_hmc_accum, HmcArgs H, HmcAccArgs A) {
+    BB_CTX;
+    bb_block_hmc_accum(cx, H, A);
+}
+BB_KERNEL(BB_HMC_NT, k_hmc_accum_stats, HmcArgs H, HmcAccArgs A) {
+    BB_CTX;
+    bb_block_hmc_accum_stats(cx, H, A);
+}
 #ifndef BB_EMU
 // transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
 __global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {

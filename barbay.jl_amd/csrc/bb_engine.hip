@@ -1,7 +1,7 @@
 // bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the resident launchers, groups and the cross-GPU
 // leg; what a step launches is in bb_step.h, the launch plan in bb_plan.h, handle creation in bb_create.h, the run path (bb_run and its
 // kin) in bb_run.h, the post-fit entry points (hier fitness, log-density batch, bands, scores, chain summary) in bb_analysis.h and the HMC
-// session in bb_hmc_host.h, all included below.
+// session in bb_hmc_host.h with its streaming moments in bb_hmc_accum_host.h, all included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -32,6 +32,7 @@
 #include "bb_trace.h"
 #include "bb_logp.h"
 #include "bb_hmc.h"
+#include "bb_hmc_accum.h"
 #include "bb_mathprobe.h"
 
 #include <algorithm>
@@ -147,6 +148,7 @@ enum {
     BUF_LOGP,      // bb_logdensity_grad_batch: the points, their gradients and log-joints, partial rows of the last call
     BUF_CHAIN,     // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
     BUF_HMC,       // bb_hmc_*: the session's walkers (state, proposal, momentum), metric and evaluation scratch; kept from begin to end
+    BUF_HMC_ACC,   // bb_hmc_accum_*: the session's running moments per (walker, segment), the tables of a call and the four rows of the statistics
     BUF_COUNT
 };
 
@@ -195,6 +197,10 @@ struct bb_handle {
     LogpArgs hmc_eval{};               // the evaluation of the proposal rows (its z, grad, logp, lf_* are set per launch)
     double* hmc_tab = nullptr;         // device: eps [Wp] | n_leapfrog [Wp ints] of the transition; hmc.accept lies behind
     std::vector<double> hmc_logp;      // host mirror of the walkers' logp
+    // its streaming moments (bb_hmc_accum_*, bb_hmc_accum_host.h): on while acc_on is set; the device pointers of acc lie in buf[BUF_HMC_ACC]
+    bool acc_on = false;
+    HmcAccArgs acc{};
+    std::vector<long long> acc_n;      // [W][S] states added so far
     // the iterate trace (bb_trace_*, bb_trace.h): on while trace_ring is set
     double* trace_ring = nullptr;      // [trace_cap][2 D], the handle's own allocation (bb_trace_end frees it)
     int trace_every = 0, trace_cap = 0;
@@ -1011,6 +1017,8 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
 
 // the HMC session: bb_hmc_begin, bb_hmc_step, bb_hmc_get, bb_hmc_end (bb_hmc.h)
 #include "bb_hmc_host.h"
+// its streaming moments and the metric: bb_hmc_accum_*, bb_hmc_set_metric, bb_hmc_get_metric (bb_hmc_accum.h)
+#include "bb_hmc_accum_host.h"
 
 extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
     if (!h || !s) return bb_fail(BB_ERR_INVALID, "null argument");

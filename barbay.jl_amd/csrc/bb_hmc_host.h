@@ -3,7 +3,8 @@
 // built by hipcc and by g++ -DBB_EMU -x c++ like the rest of the engine.
 //
 // The session lives in buf[BUF_HMC], carved once by bb_hmc_begin: nothing else grows that buffer, so the pointers in h->hmc hold until
-// the next begin or bb_destroy.  Per transition the host link carries eps and n_leapfrog (W entries each) up, 3 W doubles down, W flags up.
+// the next begin or bb_destroy (the streaming moments of bb_hmc_accum_host.h have buf[BUF_HMC_ACC] to themselves).  Per transition the
+// host link carries eps and n_leapfrog (W entries each) up, 3 W doubles down, W flags up.
 
 static int hmc_common_checks(bb_handle* h, const char* what) {
     if (!h->shards.empty()) return bb_fail(BB_ERR_UNSUPPORTED, "%s is not available on a multi-device handle (n_devices > 1)", what);
@@ -25,10 +26,30 @@ static int hmc_rows_out(bb_handle* h, const double* dev, double* out) {
     return BB_OK;
 }
 
+// The metric as the session holds it (bb_hmc_begin, bb_hmc_set_metric): inv_mass [Dz] | 1 / sqrt(inv_mass) [Dz] in the handle's order, from the
+// caller's inv_mass [D] (nullptr: ones), every entry checked first.  1 / sqrt: the correctly rounded sqrt, then the division.  The pad entry
+// of an odd D: inv_mass 1, 1 / sqrt 0 (its momentum is 0 and stays 0).
+static int hmc_metric_rows(const bb_handle* h, const double* inv_mass, std::vector<double>& rows) {
+    const size_t D = (size_t)h->M.D, Dz = (D + 1) & ~(size_t)1;
+    if (inv_mass)
+        for (size_t i = 0; i < D; ++i)
+            if (!(std::isfinite(inv_mass[i]) && inv_mass[i] > 0.0))
+                return bb_fail(BB_ERR_INVALID, "inv_mass[%lld] = %g is not finite and > 0", (long long)i, inv_mass[i]);
+    rows.assign(2 * Dz, 0.0);
+    double *him = rows.data(), *hsd = rows.data() + Dz;
+    for (size_t i = 0; i < D; ++i) {
+        const double v = inv_mass ? inv_mass[h->cidx.empty() ? i : (size_t)h->cidx[i]] : 1.0;
+        him[i] = v;
+        hsd[i] = 1.0 / std::sqrt(v);
+    }
+    if (Dz > D) { him[D] = 1.0; hsd[D] = 0.0; }
+    return BB_OK;
+}
+
 extern "C" int bb_hmc_end(bb_handle* h) {
     if (!h) return bb_fail(BB_ERR_INVALID, "null argument");
     if (!h->hmc_ever) return bb_fail(BB_ERR_INVALID, "bb_hmc_end without a session: bb_hmc_begin comes first");
-    h->hmc_on = false;                 // (a second end: BB_OK)
+    h->hmc_on = h->acc_on = false;     // (a second end: BB_OK)
     return BB_OK;
 }
 
@@ -40,12 +61,10 @@ extern "C" int bb_hmc_begin(bb_handle* h, const bb_hmc_opts* o, const double* z0
     if (o->reserved0 != 0) return bb_fail(BB_ERR_INVALID, "bb_hmc_opts.reserved0 must be 0");
     const DevModel& M = h->M;
     const size_t W = (size_t)o->n_walkers, D = (size_t)M.D, Dz = (D + 1) & ~(size_t)1, Wp = (W + 1) & ~(size_t)1;
-    if (o->inv_mass)
-        for (size_t i = 0; i < D; ++i)
-            if (!(std::isfinite(o->inv_mass[i]) && o->inv_mass[i] > 0.0))
-                return bb_fail(BB_ERR_INVALID, "inv_mass[%lld] = %g is not finite and > 0", (long long)i, o->inv_mass[i]);
+    std::vector<double> metric;
+    if ((rc = hmc_metric_rows(h, o->inv_mass, metric))) return rc;
     BB_ENTER(h);
-    h->hmc_on = false;                 // (a begin that fails leaves no session)
+    h->hmc_on = h->acc_on = false;     // (a begin that fails leaves no session; the accumulators go with the session they were begun on)
     const bool geno = M.kind == BB_MODEL_GENOTYPE;
     const size_t nbs = geno ? ((size_t)M.nb + 1) & ~(size_t)1 : 0, Gs = geno ? ((size_t)M.G + 1) & ~(size_t)1 : 0;
     const size_t nchunk = (Dz + BB_HMC_CHUNK - 1) / BB_HMC_CHUNK;
@@ -72,16 +91,8 @@ extern "C" int bb_hmc_begin(bb_handle* h, const bb_hmc_opts* o, const double* z0
     });
     if (rc) return rc;
     if ((rc = dzero(h->buf[BUF_HMC].p, total * 8, h->stream))) return rc;
-    // the metric, the handle's order; the pad entry of an odd D: inv_mass 1, 1 / sqrt 0 (its momentum is 0 and stays 0)
-    std::vector<double> host(std::max(2 * Dz, W * Dz));
-    double *him = host.data(), *hsd = host.data() + Dz;
-    for (size_t i = 0; i < D; ++i) {
-        const double v = o->inv_mass ? o->inv_mass[h->cidx.empty() ? i : (size_t)h->cidx[i]] : 1.0;
-        him[i] = v;
-        hsd[i] = 1.0 / std::sqrt(v);
-    }
-    if (Dz > D) { him[D] = 1.0; hsd[D] = 0.0; }
-    if ((rc = h2d(im, him, 2 * Dz * 8, h->stream))) return rc;      // (isd lies behind im)
+    if ((rc = h2d(im, metric.data(), 2 * Dz * 8, h->stream))) return rc;      // (isd lies behind im)
+    std::vector<double> host(W * Dz);
     if (!h->cidx.empty() && (rc = h2d(cidx, h->cidx.data(), D * sizeof(long long), h->stream))) return rc;
     for (size_t w = 0; w < W; ++w) {
         double* row = host.data() + w * Dz;

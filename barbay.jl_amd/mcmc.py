@@ -25,7 +25,7 @@ import numpy as np
 
 from . import utils
 from . import vi as _vi
-from ._capi import BB_CHAIN_MAX_K, BB_LOGP_MAX_BATCH, Engine
+from ._capi import BB_CHAIN_MAX_K, BB_HMC_MAX_SEGMENTS, BB_HMC_MAX_WALKERS, BB_LOGP_MAX_BATCH, Engine
 from .model import BarBayError, BayesModel
 
 log = logging.getLogger("barbay")
@@ -177,8 +177,30 @@ def nuts_ensemble(fbatch: Callable, z0s, n_steps, n_adapt, *, rngs: Sequence[np.
     return results
 
 
+def _adapt_windows(n_adapt: int):
+    """Stan's metric windows of a warm-up of n_adapt transitions, as (start, end] pairs of transition numbers (1-based: the window holds
+    the transitions start < m <= end).  Below 20 transitions none; below 150 one window between floor(0.15 n) and n - floor(0.1 n);
+    otherwise an initial buffer of 75, a final buffer of 50, a first window of 25 and each next window twice as long, a window whose
+    successor would not fit before the final buffer being extended to it (1000: windows ending at 100, 150, 250, 450, 950)."""
+    n = int(n_adapt)
+    if n < 20:
+        return []
+    if n < 150:
+        return [(int(0.15 * n), n - int(0.1 * n))]
+    start, size, last = 75, 25, n - 50
+    out = []
+    while start < last:
+        end = start + size
+        if end + 2 * size > last:
+            end = last
+        out.append((start, end))
+        start, size = end, 2 * size
+    return out
+
+
 def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Generator], target_accept: float = 0.65,
-                 minv: Optional[np.ndarray] = None, n_leapfrog=(8, 24), thin: int = 1, seed: int = 0):
+                 minv: Optional[np.ndarray] = None, n_leapfrog=(8, 24), thin: int = 1, seed: int = 0, adapt_metric: bool = False,
+                 segments: int = 0, keep_chain: bool = True):
     """len(z0s) <= BB_HMC_MAX_WALKERS chains of Hamiltonian Monte Carlo (diagonal metric `minv`, a fixed number of leapfrogs per
     transition) whose position, momentum and gradient stay on the device (`Engine.hmc_begin / hmc_step / hmc_get / hmc_end`,
     csrc/bb_hmc.h): one call makes one transition of every walker, only scalars come back, and positions are downloaded when a draw
@@ -192,6 +214,18 @@ def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Gene
     walker that has finished is stepped on as a probe and disturbs no one.  The default range (8, 24) of `n_leapfrog` has been tuned by
     nobody.
 
+    `adapt_metric`: the metric is adapted during the warm-up as Stan does (`n_adapt` must then be one value: the session has one metric).
+    Inside each window of `_adapt_windows(n_adapt)` every walker's state is added, after each transition, to the device's running moments
+    (`Engine.hmc_accum_add`, segment 0); at a window's end the pooled variance v of its K states (`hmc_accum_stats`' sd squared) becomes
+    the metric, regularised as Stan regularises it, inv_mass = v K / (K + 5) + 1e-3 * 5 / (K + 5) (`hmc_set_metric`), the moments are reset
+    and every walker's dual averaging restarts at mu = log(10 eps), h_bar = 0, eps_bar = 1, counter 1.  `info` gains `inv_mass` (the final
+    metric) and `metric_windows`.
+    `segments` = S > 0: after the warm-up the moments are reset and kept draw k of a walker with n kept draws (n >= 2 S) goes to its segment
+    floor(S k / n); `info` gains `stream`, what `hmc_accum_stats` returns at the end (pooled mean, sd, split-R-hat for S = 2, and a
+    batch-means mcse / ess over the W S segments: include/barbay_hip.h) -- the same dict in every walker's info.
+    `keep_chain=False` (needs `segments`): `hmc_get` is never called and the chains come back with 0 rows: nothing of size D crosses the
+    host link per draw.  With the three defaults the engine sees the calls it saw without them.
+
     Returns a list, per walker, of what `nuts` returns: (chain[n_steps, D], logp[n_steps], info), info holding `step_size`, `n_grad`
     (leapfrogs, probes included), `accept_rate` and `divergences` (both over the transitions after the warm-up) and `mean_leapfrog`."""
     W = len(z0s)
@@ -203,12 +237,23 @@ def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Gene
     per = lambda v, w: int(v[w]) if np.ndim(v) else int(v)
     n_st = np.array([per(n_steps, w) for w in range(W)])
     n_ad = np.array([per(n_adapt, w) for w in range(W)])
+    S = int(segments)
+    if adapt_metric and not (n_ad == n_ad[0]).all():
+        raise BarBayError("adapt_metric needs one n_adapt for all walkers: the session has one metric")
+    if not 0 <= S <= BB_HMC_MAX_SEGMENTS or (S > 0 and (n_st < 2 * S).any()):
+        raise BarBayError(f"segments must lie in 0 .. {BB_HMC_MAX_SEGMENTS} and every walker keep at least 2 draws per segment, not "
+                          f"segments = {segments!r} with n_steps = {n_steps!r}")
+    if not keep_chain and S == 0:
+        raise BarBayError("keep_chain=False needs segments > 0: without the chain the streamed summary is all that is returned")
+    windows = _adapt_windows(n_ad[0]) if adapt_metric else []
     Z0 = np.stack([np.asarray(z, dtype=np.float64) for z in z0s])
     D = Z0.shape[1]
     session = engine.hmc_begin(Z0, seed=seed, inv_mass=minv)
     try:
         if not np.isfinite(session.logp).all():
             raise BarBayError("log density is not finite at the initial point")
+        if windows or S > 0:
+            engine.hmc_accum_begin(max(S, 1))
         n_grad = np.zeros(W, dtype=np.int64)
         # the start step size: _find_step's rule on probes of one leapfrog, every probe with transition 0's momenta
         eps = np.ones(W)
@@ -226,10 +271,14 @@ def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Gene
             n_grad += ~done
         mu, eps_bar, h_bar = np.log(10.0 * eps), np.ones(W), np.zeros(W)
         gamma, t0, kappa = 0.05, 10.0, 0.75
-        chains = [np.empty((n_st[w], D)) for w in range(W)]
-        lps = [np.empty(n_st[w]) for w in range(W)]
+        chains = [np.empty((n_st[w] if keep_chain else 0, D)) for w in range(W)]
+        lps = [np.empty(n_st[w] if keep_chain else 0) for w in range(W)]
         acc, div, leaps = np.zeros(W), np.zeros(W, dtype=np.int64), np.zeros(W)
         total = n_ad + n_st * thin
+        da0 = 0                                                              # the transition the dual averaging last restarted behind
+        metric, metric_windows = None, []
+        win_end = {end: start for start, end in windows}
+        in_window = lambda m: any(start < m <= end for start, end in windows)
         for m in range(1, int(total.max()) + 1):
             live = m <= total
             L, logu = np.ones(W, dtype=np.int32), np.full(W, np.inf)          # (a finished walker: a probe)
@@ -240,11 +289,13 @@ def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Gene
             n_grad += np.where(live, L, 0)
             alpha = np.where(r["divergent"] != 0, 0.0, np.minimum(1.0, np.exp(np.minimum(0.0, dh(r)))))
             keep = None
+            seg = np.full(W, -1, dtype=np.int32)                              # where this transition's states go (segments > 0)
+            md = m - da0                                                      # the dual averaging's own counter
             for w in np.flatnonzero(live):
                 if m <= n_ad[w]:
-                    h_bar[w] = (1.0 - 1.0 / (m + t0)) * h_bar[w] + (target_accept - alpha[w]) / (m + t0)
-                    eps[w] = float(np.exp(mu[w] - np.sqrt(m) / gamma * h_bar[w]))
-                    x = m ** -kappa
+                    h_bar[w] = (1.0 - 1.0 / (md + t0)) * h_bar[w] + (target_accept - alpha[w]) / (md + t0)
+                    eps[w] = float(np.exp(mu[w] - np.sqrt(md) / gamma * h_bar[w]))
+                    x = md ** -kappa
                     eps_bar[w] = float(np.exp(x * np.log(eps[w]) + (1.0 - x) * np.log(eps_bar[w])))
                     if m == n_ad[w]:
                         eps[w] = eps_bar[w]
@@ -253,16 +304,42 @@ def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Gene
                 div[w] += r["divergent"][w]
                 leaps[w] += L[w]
                 if (m - n_ad[w]) % thin == 0:
+                    k = (m - n_ad[w]) // thin - 1
+                    if S > 0:
+                        seg[w] = S * k // n_st[w]
+                    if not keep_chain:
+                        continue
                     if keep is None:
                         keep = engine.hmc_get()                               # (one download for all the walkers that keep this draw)
-                    k = (m - n_ad[w]) // thin - 1
                     chains[w][k] = keep[0][w]
                     lps[w][k] = keep[1][w]
+            if (seg >= 0).any():
+                engine.hmc_accum_add(seg)
+            if windows and in_window(m):
+                engine.hmc_accum_add(0)
+                if m in win_end:                                              # the window's variance becomes the metric
+                    st = engine.hmc_accum_stats()
+                    K = float(st["n_total"])
+                    metric = st["sd"] ** 2 * (K / (K + 5.0)) + 1e-3 * (5.0 / (K + 5.0))
+                    engine.hmc_set_metric(metric)
+                    engine.hmc_accum_reset()
+                    metric_windows.append((win_end[m], m))
+                    if m < n_ad[0]:                                           # (a walker whose warm-up ends here keeps its eps_bar)
+                        mu, eps_bar, h_bar, da0 = np.log(10.0 * eps), np.ones(W), np.zeros(W), m
+            if windows and S > 0 and m == n_ad[0]:
+                engine.hmc_accum_reset()
+        stream = engine.hmc_accum_stats() if S > 0 else None
     finally:
         engine.hmc_end()
     post = np.maximum(n_st * thin, 1)
+    extra = {}
+    if adapt_metric:
+        extra.update(inv_mass=np.array(metric if metric is not None else (np.ones(D) if minv is None else minv), dtype=np.float64),
+                     metric_windows=metric_windows)
+    if S > 0:
+        extra.update(stream=stream)
     return [(chains[w], lps[w], {"step_size": float(eps[w]), "n_grad": int(n_grad[w]), "accept_rate": float(acc[w] / post[w]),
-                                 "divergences": int(div[w]), "mean_leapfrog": float(leaps[w] / post[w])}) for w in range(W)]
+                                 "divergences": int(div[w]), "mean_leapfrog": float(leaps[w] / post[w]), **extra}) for w in range(W)]
 
 
 SUMMARY_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)                  # MCMCChains.quantile's default q
@@ -291,13 +368,19 @@ def summarize(out_or_path, engine: Optional[Engine] = None, *, probs: Optional[S
     `.npz` it wrote.  `probs` None: the output's own `summary_probs`, or SUMMARY_PROBS.  The `summary_*` arrays an output carries
     (`mcmc_sample(summary=True)`: `summary_probs`, no lag bound) are tabulated as they are where they answer the call -- `probs` None
     or equal to `summary_probs`, `max_lag` 0; otherwise the statistics are computed from `chain` on the device
-    (`Engine.chain_summary`) through `engine`, or through a minimal handle of its own on `device`."""
+    (`Engine.chain_summary`) through `engine`, or through a minimal handle of its own on `device`.  An output without a chain
+    (`hmc_kwargs={"segments": S, "keep_chain": False}`) is tabulated from its `stream_*` arrays: no quantile columns, and its `ess` /
+    `mcse` are the batch-means estimates of `Engine.hmc_accum_stats`."""
     import pandas as pd
     out = out_or_path
     if isinstance(out, (str, os.PathLike)):
         path = os.fspath(out)
         with np.load(path if os.path.isfile(path) else path + ".npz", allow_pickle=True) as z:
             out = {k: z[k] for k in z.files}
+    if "stream_mean" in out and ("chain" not in out or np.shape(out["chain"])[1] == 0):      # the summary streamed on the device
+        cols = {"parameters": [str(v) for v in out["var_names"]]}
+        cols.update({k: np.asarray(out[f"stream_{src}"]) for k, src in _SUMMARY_KEYS})
+        return pd.DataFrame(cols)
     stored = "summary_mean" in out and max_lag == 0 and (
         probs is None or np.array_equal(np.asarray(probs, dtype=np.float64), np.asarray(out["summary_probs"], dtype=np.float64)))
     probs = SUMMARY_PROBS if probs is None else probs
@@ -333,8 +416,13 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
     LDS), which is checked before anything is sampled.
     `sampler`: "nuts" (the default, the paths above) or "hmc": `hmc_ensemble` from the same ADVI start and metric, all walkers in
     lock-step with their state on the device (chunks of BB_HMC_MAX_WALKERS = 64 walkers; `ensemble` plays no part), walker w drawing from
-    `default_rng([seed, w])`; `hmc_kwargs` go to `hmc_ensemble` (`n_leapfrog`, `thin`).  Its output has the same keys and
-    `accept_rate`, `divergences`, `n_grad` per walker."""
+    `default_rng([seed, w])`; `hmc_kwargs` go to `hmc_ensemble` (`n_leapfrog`, `thin`, `adapt_metric`, `segments`, `keep_chain`).  Its
+    output has the same keys and `accept_rate`, `divergences`, `n_grad` per walker; with `adapt_metric` also `inv_mass` (the adapted
+    metric), with `segments` the summary streamed on the device, `stream_mean, stream_sd, stream_mcse, stream_ess, stream_rhat` [D] and
+    `stream_n` (`Engine.hmc_accum_stats`: `stream_ess` / `stream_mcse` are batch-means estimates over the walkers' segments, not the
+    `summary_*` ones), which `summarize` tabulates when the output has no chain (`keep_chain=False`: `chain` has 0 draws and no position
+    is ever downloaded).  Both need all walkers in one session, n_walkers <= BB_HMC_MAX_WALKERS; `summary=True` needs the chain.  Both
+    are checked before anything is sampled."""
     if sampler not in ("nuts", "hmc"):
         raise BarBayError(f"sampler must be 'nuts' or 'hmc', not {sampler!r}")
     if ensemble not in ("serial", "batched"):
@@ -342,6 +430,12 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
     if summary and (n_walkers < 1 or n_steps < 4 or n_walkers * n_steps > BB_CHAIN_MAX_K):
         raise BarBayError(f"summary=True needs n_walkers >= 1, n_steps >= 4 and n_walkers * n_steps <= {BB_CHAIN_MAX_K}, not "
                           f"{n_walkers} x {n_steps}: sample with summary=False and summarize fewer draws")
+    hk = hmc_kwargs or {}
+    if sampler == "hmc" and (hk.get("segments", 0) or hk.get("adapt_metric", False)) and n_walkers > BB_HMC_MAX_WALKERS:
+        raise BarBayError(f"segments / adapt_metric need all walkers in one session: n_walkers <= BB_HMC_MAX_WALKERS = "
+                          f"{BB_HMC_MAX_WALKERS}, not {n_walkers}")
+    if sampler == "hmc" and summary and not hk.get("keep_chain", True):
+        raise BarBayError("summary=True needs the chain: keep_chain=False returns the streamed summary (stream_*) alone")
     fname = None if outputname is None else f"{outputname}.npz"
     if fname is not None and os.path.isfile(fname):                                # :104-106
         raise BarBayError(f"{fname} was already processed")
@@ -416,6 +510,11 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
            "chain": np.stack(chains), "logp": np.stack(lps), "step_size": np.asarray([i["step_size"] for i in infos]), **summ}
     if sampler == "hmc":
         out.update({k: np.asarray([i[k] for i in infos]) for k in ("accept_rate", "divergences", "n_grad")})
+        if "inv_mass" in infos[0]:
+            out["inv_mass"] = infos[0]["inv_mass"]
+        if "stream" in infos[0]:
+            st = infos[0]["stream"]
+            out.update({f"stream_{k}": st[k] for k in ("mean", "sd", "mcse", "ess", "rhat")}, stream_n=np.int64(st["n_total"]))
     if fname is None:
         return out
     if verbose:

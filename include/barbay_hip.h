@@ -361,6 +361,72 @@ int bb_hmc_step(bb_handle* h, const bb_hmc_step_opts* o, const bb_hmc_step_out* 
 int bb_hmc_get(bb_handle* h, double* z /* [W][D] or NULL */, double* logp /* [W] or NULL */, double* grad /* [W][D] or NULL */);
 int bb_hmc_end(bb_handle* h);
 
+/* ---- streaming moments of the HMC session and its metric (csrc/bb_hmc_accum.h) ---------------------------------------------------
+ * Summaries of the draws and a windowed adaptation of the metric without the draws leaving the device: per walker w and segment
+ * s < n_segments the device keeps the running mean and m2 (sum of squared deviations) of the states ADDED to (w, s), two rows of the
+ * session's stride in the handle's latent order, in a buffer of their own; the counts n[w][s] stay on the host.  Nothing of size D
+ * crosses the host link per draw.  No reference counterpart.
+ *
+ * bb_hmc_accum_begin: needs a session; allocates and zeroes W x n_segments x 2 rows (and four rows for the statistics); a second call
+ *  replaces them.  bb_hmc_begin and bb_hmc_end drop the accumulators; bb_destroy frees the buffer.
+ * bb_hmc_accum_add: walker w's CURRENT state x = z[w] goes to segment[w] (-1: this walker is not added), one Welford step per latent with
+ *  n the new count of (w, segment[w]) and inv_n = 1.0 / n formed on the host:
+ *      d = x - mean;   mean = mean + d * inv_n;   m2 = m2 + d * (x - mean)
+ *  every product and sum rounded on its own (no fused multiply-add), so a host restatement is bit-exact.  The pass reads z, mean, m2 and
+ *  writes mean, m2 (40 B per latent), on the grid of bb_hmc_step's elementwise kernels.
+ * bb_hmc_accum_reset: all counts and rows to zero.   bb_hmc_accum_get: one (walker, segment)'s rows in the caller's order and its count.
+ * bb_hmc_accum_stats: over the live chains c = (w, s) with n_c > 0 -- C of them, K = sum n_c, m_c and M2_c their rows -- the device forms,
+ *  per latent, every sum onto 0.0 over c in the order w ascending then s ascending, every operation rounded on its own:
+ *      mean      = (sum n_c m_c) / K
+ *      m2_pooled = (sum M2_c) + (sum n_c ((m_c - mean) (m_c - mean)))
+ *      within    = (sum M2_c / (n_c - 1)) / C
+ *      between   = (sum (m_c - mbar) (m_c - mbar)) / (C - 1),  mbar = (sum m_c) / C the unweighted mean of the chain means;  0 for C = 1
+ *  (a latent whose chains all hold M2_c = 0 and one and the same mean is constant: mean = that value, the other three rows 0 exactly), and
+ *  the host side of the call derives, in fp64 with std::sqrt:
+ *      sd   = sqrt(m2_pooled / (K - 1))                                  (StatsBase.std of the pooled draws)
+ *      rhat = sqrt(var+ / within),  var+ = (Nbar - 1) / Nbar within + between,  Nbar = K / C
+ *      mcse = sqrt(between / C)
+ *      ess  = min(sd sd / (mcse mcse), K log10 K)
+ *  With n_segments = 2 and equal halves these are the pooled mean, the sd and the split-R-hat of bb_chain_summary.  ess is NOT that call's
+ *  (Geyer's) estimate: it is a batch-means estimate whose batches are the C chains -- the variance of the chain means against the pooled
+ *  variance -- and its own relative error is about sqrt(2 / (C - 1)): with 4 walkers and 2 segments, +-50 %.  It wants chains (segments)
+ *  longer than the autocorrelation time and says nothing about mixing inside a segment.  Quantiles cannot be streamed exactly and are
+ *  not offered.
+ *  One live chain (C = 1): rhat = mcse = ess = NaN.  A constant latent: sd = 0 exactly, rhat = mcse = ess = NaN.  A latent with a
+ *  non-finite accumulator: NaN in mean, sd, mcse, ess and rhat of that latent, no other latent disturbed, no error.  `within` and
+ *  `between` are the raw rows, for callers who combine sessions.
+ * bb_hmc_set_metric: replaces the session's metric in mid-session: inv_mass is validated, turned into 1 / sqrt(inv_mass), permuted and padded
+ *  as by bb_hmc_begin (the same code) and uploaded, 2 x the padded D doubles; z, g, logp and the accumulators are untouched.  A step after
+ *  it equals the step of a session begun at the same z with that inv_mass.   bb_hmc_get_metric: the session's inv_mass, caller's order.
+ *
+ * Invariants: a (walker, segment)'s rows are a function of that walker's added states and their order alone -- bit-identical whatever W,
+ *  whatever the other walkers' segment arguments and whatever the handle's launch mode (no atomics, no cross-lane sums: a latent is one
+ *  lane's).  No call here changes the session's z, g or logp, the later results of bb_hmc_step (bb_hmc_set_metric: but through the
+ *  metric), or the handle's mu, omega, optimiser state, step counter and RNG position, bitwise.
+ * Errors: BB_ERR_INVALID -- a null argument; no session; no accumulators (bb_hmc_accum_add / reset / get / stats before
+ *  bb_hmc_accum_begin, or after a bb_hmc_begin / bb_hmc_end); n_segments outside 1 .. BB_HMC_MAX_SEGMENTS; reserved0 != 0; a segment outside
+ *  -1 .. n_segments - 1 (the message names the walker); a walker or segment of bb_hmc_accum_get out of range; bb_hmc_accum_stats with a live
+ *  chain of n_c = 1 (the message names walker and segment) or with nothing added; an inv_mass entry that is not finite or not > 0 (the
+ *  message names its index).  BB_ERR_UNSUPPORTED -- sharded and multi-device handles, as for bb_hmc_*.  BB_ERR_DEVICE -- the device
+ *  cannot allocate the rows: nothing is kept. */
+#define BB_HMC_MAX_SEGMENTS 8
+typedef struct bb_hmc_accum_opts {
+    int32_t n_segments;         /* 1 .. BB_HMC_MAX_SEGMENTS */
+    int32_t reserved0;          /* 0 */
+} bb_hmc_accum_opts;
+typedef struct bb_hmc_accum_out {      /* every pointer may be NULL; [D], caller's order */
+    double *mean, *sd, *mcse, *ess, *rhat;
+    double *within, *between;          /* the raw rows, for callers who combine sessions */
+    int64_t* n_total;                  /* one value: K */
+} bb_hmc_accum_out;
+int bb_hmc_accum_begin(bb_handle* h, const bb_hmc_accum_opts* o);
+int bb_hmc_accum_add(bb_handle* h, const int32_t* segment /* [W]: 0 .. n_segments - 1, or -1 = this walker is not added */);
+int bb_hmc_accum_reset(bb_handle* h);
+int bb_hmc_accum_get(bb_handle* h, int32_t walker, int32_t segment, double* mean /* [D] or NULL */, double* m2 /* [D] or NULL */, int64_t* n /* or NULL */);
+int bb_hmc_accum_stats(bb_handle* h, const bb_hmc_accum_out* out);
+int bb_hmc_set_metric(bb_handle* h, const double* inv_mass /* [D] caller's order, finite and > 0; NULL: ones */);
+int bb_hmc_get_metric(bb_handle* h, double* inv_mass /* [D] caller's order */);
+
 /* ELBO estimates recorded by bb_run (elbo_every > 0): values of steps
  * first_step, first_step + elbo_every, ... ; NaN where not recorded/kept. */
 int bb_get_elbo_trace(bb_handle* h, int64_t first_step, int64_t n, double* out);

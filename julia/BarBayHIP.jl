@@ -971,6 +971,86 @@ function hmc_get(h::Ptr{Cvoid}, W::Integer; grad::Bool=false)
 end
 hmc_end(h::Ptr{Cvoid}) = check(ccall((:bb_hmc_end, LIB), Cint, (Ptr{Cvoid},), h))
 
+# Streaming moments of the session's state and its metric (bb_hmc_accum_* / bb_hmc_set_metric / bb_hmc_get_metric, include/barbay_hip.h):
+# per walker and segment a running mean and m2 on the device, pooled on request.  Field for field the Python binding's `bb_hmc_accum_opts`,
+# `bb_hmc_accum_out` (barbay.jl_amd/_capi.py).  Like the rest of this file it has not been executed: no Julia here.
+const BB_HMC_MAX_SEGMENTS = 8
+struct bb_hmc_accum_opts
+    n_segments::Int32
+    reserved0::Int32
+end
+struct bb_hmc_accum_out
+    mean::Ptr{Float64}
+    sd::Ptr{Float64}
+    mcse::Ptr{Float64}
+    ess::Ptr{Float64}
+    rhat::Ptr{Float64}
+    within::Ptr{Float64}
+    between::Ptr{Float64}
+    n_total::Ptr{Int64}
+end
+"""
+    hmc_accum_begin(h; n_segments=1)
+
+Allocates and zeroes the running moments of the open session, `n_segments` <= BB_HMC_MAX_SEGMENTS per walker.  `hmc_begin` and `hmc_end`
+drop them.
+"""
+hmc_accum_begin(h::Ptr{Cvoid}; n_segments::Integer=1) =
+    check(ccall((:bb_hmc_accum_begin, LIB), Cint, (Ptr{Cvoid}, Ref{bb_hmc_accum_opts}), h, bb_hmc_accum_opts(Int32(n_segments), Int32(0))))
+"""
+    hmc_accum_add(h, segment)
+
+One Welford step of every walker's current state into `segment[w]` (0-based as in the C ABI; -1: the walker is not added).
+"""
+hmc_accum_add(h::Ptr{Cvoid}, segment::AbstractVector{<:Integer}) =
+    check(ccall((:bb_hmc_accum_add, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}), h, Vector{Int32}(segment)))
+hmc_accum_reset(h::Ptr{Cvoid}) = check(ccall((:bb_hmc_accum_reset, LIB), Cint, (Ptr{Cvoid},), h))
+"""
+    hmc_accum_get(h, walker, segment) -> (mean, m2, n)
+
+The rows of one (walker, segment), both 0-based, in the caller's order, and the number of states added to it.
+"""
+function hmc_accum_get(h::Ptr{Cvoid}, walker::Integer, segment::Integer)
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    mean, m2, n = Vector{Float64}(undef, D), Vector{Float64}(undef, D), Ref{Int64}(0)
+    check(ccall((:bb_hmc_accum_get, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int64}), h, walker, segment, mean, m2, n))
+    return mean, m2, n[]
+end
+"""
+    hmc_accum_stats(h) -> NamedTuple
+
+Pooled `mean, sd, mcse, ess, rhat, within, between` (D each) and `n_total` of everything added.  `ess` is a batch-means estimate over the
+live (walker, segment) chains, not Geyer's: its own relative error is about sqrt(2 / (C - 1)) for C chains (include/barbay_hip.h).
+"""
+function hmc_accum_stats(h::Ptr{Cvoid})
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    mean, sd, mcse, ess, rhat, within, between = (Vector{Float64}(undef, D) for _ in 1:7)
+    n = Ref{Int64}(0)
+    GC.@preserve mean sd mcse ess rhat within between n begin
+        out = bb_hmc_accum_out(pointer(mean), pointer(sd), pointer(mcse), pointer(ess), pointer(rhat), pointer(within), pointer(between),
+                               Base.unsafe_convert(Ptr{Int64}, n))
+        check(ccall((:bb_hmc_accum_stats, LIB), Cint, (Ptr{Cvoid}, Ref{bb_hmc_accum_out}), h, out))
+    end
+    return (mean=mean, sd=sd, mcse=mcse, ess=ess, rhat=rhat, within=within, between=between, n_total=n[])
+end
+"""
+    hmc_set_metric(h, inv_mass=nothing)
+
+Replaces the open session's diagonal metric (`nothing`: ones); positions, gradients and accumulators stay.
+"""
+function hmc_set_metric(h::Ptr{Cvoid}, inv_mass::Union{Nothing,AbstractVector{Float64}}=nothing)
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    im = inv_mass === nothing ? Float64[] : Vector{Float64}(inv_mass)
+    inv_mass === nothing || length(im) == D || error("hmc_set_metric: inv_mass must have $D entries")
+    GC.@preserve im check(ccall((:bb_hmc_set_metric, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), h, inv_mass === nothing ? Ptr{Float64}(C_NULL) : pointer(im)))
+end
+function hmc_get_metric(h::Ptr{Cvoid})
+    D = ccall((:bb_num_latents, LIB), Int64, (Ptr{Cvoid},), h)
+    im = Vector{Float64}(undef, D)
+    check(ccall((:bb_hmc_get_metric, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), h, im))
+    return im
+end
+
 # Chain diagnostics (bb_chain_summary, include/barbay_hip.h): MCMCChains' summarystats + quantile of a host chain, on the device.
 # Field for field the Python binding's `bb_chain_opts` / `bb_chain_out` (barbay.jl_amd/_capi.py).
 const BB_CHAIN_MAX_K = 16384
