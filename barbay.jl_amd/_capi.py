@@ -25,6 +25,9 @@ BB_HMC_MAX_LEAPFROG = 1024
 BB_HMC_STREAM0 = 0xFFFFFF00
 BB_HMC_CHUNK = 2048
 BB_HMC_MAX_SEGMENTS = 8
+BB_NUTS_MAX_DEPTH = 10
+BB_NUTS_EDGE_OPP = -2
+BB_NUTS_TAKE_LEAF, BB_NUTS_TAKE_SUB, BB_NUTS_TAKE_STATE = 1, 2, 4
 BB_CHAIN_MAX_K = 16384
 BB_CHAIN_MAX_Q = 8
 BB_CHAIN_LAG_BATCH = 32
@@ -56,6 +59,7 @@ EXPORTS = [
     "bb_get_layout", "bb_init_meanfield", "bb_set_params", "bb_get_params", "bb_get_permutation", "bb_get_owned", "bb_run", "bb_run_profiled",
     "bb_get_posterior", "bb_elbo_grad", "bb_logdensity_grad", "bb_logdensity_grad_batch", "bb_hmc_begin", "bb_hmc_step", "bb_hmc_get", "bb_hmc_end",
     "bb_hmc_accum_begin", "bb_hmc_accum_add", "bb_hmc_accum_reset", "bb_hmc_accum_get", "bb_hmc_accum_stats", "bb_hmc_set_metric", "bb_hmc_get_metric",
+    "bb_nuts_begin", "bb_nuts_start", "bb_nuts_leaf", "bb_nuts_take",
     "bb_get_elbo_trace", "bb_debug_normals", "bb_debug_math", "bb_debug_stamps", "bb_debug_opt_state", "bb_debug_graph_launches", "bb_get_stats", "bb_kernel_name",
     "bb_comm_make_id", "bb_comm_init", "bb_step_moments", "bb_step_apply", "bb_hier_units", "bb_hier_fitness", "bb_p2p_export", "bb_p2p_import", "bb_p2p_selftest", "bb_p2p_enable",
     "bb_ppc_shape", "bb_ppc_bands", "bb_freq_shape", "bb_freq_bands", "bb_score_shape", "bb_ppc_score", "bb_loo_shape", "bb_ppc_loo", "bb_chain_summary",
@@ -120,6 +124,19 @@ class bb_hmc_accum_out(C.Structure):
 
 
 HMC_ACCUM_FIELDS = ("mean", "sd", "mcse", "ess", "rhat", "within", "between")
+
+
+class bb_nuts_opts(C.Structure):
+    _fields_ = [("max_depth", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class bb_nuts_leaf_opts(C.Structure):
+    _fields_ = [("dir", C.POINTER(C.c_int32)), ("first", C.POINTER(C.c_int32)), ("last", C.POINTER(C.c_int32)), ("store", C.POINTER(C.c_int32)),
+                ("n_check", C.POINTER(C.c_int32)), ("check", C.POINTER(C.c_int32)), ("reserved0", C.c_int32)]
+
+
+class bb_nuts_leaf_out(C.Structure):
+    _fields_ = [("logp_leaf", _dp), ("kinetic", _dp), ("a", _dp), ("b", _dp)]
 
 
 class bb_block_range(C.Structure):
@@ -362,6 +379,11 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.bb_hmc_accum_stats.argtypes = [vp, C.POINTER(bb_hmc_accum_out)]
         lib.bb_hmc_set_metric.argtypes = [vp, _dp]
         lib.bb_hmc_get_metric.argtypes = [vp, _dp]
+    if hasattr(lib, "bb_nuts_begin"):
+        lib.bb_nuts_begin.argtypes = [vp, C.POINTER(bb_nuts_opts)]
+        lib.bb_nuts_start.argtypes = [vp, C.c_uint32, _dp, C.POINTER(C.c_int32), _dp]
+        lib.bb_nuts_leaf.argtypes = [vp, C.POINTER(bb_nuts_leaf_opts), C.POINTER(bb_nuts_leaf_out)]
+        lib.bb_nuts_take.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.bb_get_elbo_trace.argtypes = [vp, C.c_int64, C.c_int64, _dp]
     lib.bb_debug_normals.argtypes = [vp, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _dp]
     if hasattr(lib, "bb_debug_math"):           # (A/B builds of older sources, tools/xp.py)
@@ -811,6 +833,51 @@ class Engine:
         im = np.empty(self.D)
         self._check(self._lib.bb_hmc_get_metric(self._h, _ptr(im)))
         return im
+
+    def nuts_begin(self, max_depth: int = BB_NUTS_MAX_DEPTH):
+        """The rows of a No-U-Turn tree beside the open session (`bb_nuts_begin`): per walker both edges of the trajectory, the subtree's and
+        the transition's candidate and `max_depth` (<= BB_NUTS_MAX_DEPTH) U-turn checkpoints.  `hmc_begin` and `hmc_end` drop them."""
+        o = bb_nuts_opts()
+        o.max_depth, o.reserved0 = int(max_depth), 0
+        self._check(self._lib.bb_nuts_begin(self._h, C.byref(o)))
+        self._nuts_depth = int(max_depth)
+
+    def nuts_start(self, transition: int, eps, live=1) -> np.ndarray:
+        """A NUTS transition begins for the walkers with `live` [W] != 0 (`bb_nuts_start`): `hmc_step`'s momenta of `transition`, the state to
+        both edges.  Returns kinetic0 [W] (0 for a walker that is not live)."""
+        W = self._hmc_W
+        eps = _f64(np.broadcast_to(np.asarray(eps, dtype=np.float64), (W,)))
+        lv = np.ascontiguousarray(np.broadcast_to(np.asarray(live), (W,)), dtype=np.int32)
+        k0 = np.empty(W)
+        self._check(self._lib.bb_nuts_start(self._h, int(transition), _ptr(eps), _ptr(lv, C.POINTER(C.c_int32)), _ptr(k0)))
+        return k0
+
+    def nuts_leaf(self, dir, first, last, store, checks) -> Dict[str, np.ndarray]:
+        """One leaf of every walker with `dir` [W] != 0 (`bb_nuts_leaf`): `first` / `last` [W] flag the ends of its doubling, `store` [W] is -1
+        or the checkpoint slot that takes the leaf, `checks` a list per walker of the stored points to test against (slots, or
+        BB_NUTS_EDGE_OPP).  Returns logp_leaf, kinetic [W] and a, b [W, max_depth + 1] (0 beyond a walker's checks)."""
+        W, ip = self._hmc_W, C.POINTER(C.c_int32)
+        i32 = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v), (W,)), dtype=np.int32)
+        d, f, l, st = i32(dir), i32(first), i32(last), i32(store)
+        nc = np.array([len(c) for c in checks], dtype=np.int32)
+        ck = np.zeros((W, BB_NUTS_MAX_DEPTH + 1), dtype=np.int32)
+        for w, c in enumerate(checks):
+            ck[w, :min(len(c), BB_NUTS_MAX_DEPTH + 1)] = list(c)[:BB_NUTS_MAX_DEPTH + 1]
+        o = bb_nuts_leaf_opts()
+        o.dir, o.first, o.last, o.store, o.n_check, o.check, o.reserved0 = _ptr(d, ip), _ptr(f, ip), _ptr(l, ip), _ptr(st, ip), _ptr(nc, ip), _ptr(ck, ip), 0
+        n = self._nuts_depth + 1
+        res = {"logp_leaf": np.empty(W), "kinetic": np.empty(W), "a": np.empty((W, n)), "b": np.empty((W, n))}
+        out = bb_nuts_leaf_out()
+        for k, v in res.items():
+            setattr(out, k, _ptr(v))
+        self._check(self._lib.bb_nuts_leaf(self._h, C.byref(o), C.byref(out)))
+        return res
+
+    def nuts_take(self, flags):
+        """The copies `flags` [W] ask for (`bb_nuts_take`; BB_NUTS_TAKE_LEAF: leaf -> subtree candidate, BB_NUTS_TAKE_SUB: subtree candidate ->
+        transition candidate, BB_NUTS_TAKE_STATE: transition candidate -> the session's state), applied in that order."""
+        fl = np.ascontiguousarray(np.broadcast_to(np.asarray(flags), (self._hmc_W,)), dtype=np.int32)
+        self._check(self._lib.bb_nuts_take(self._h, _ptr(fl, C.POINTER(C.c_int32))))
 
     def hier_units(self) -> int:
         """Length of the theta_tilde block (0 for the non-hierarchical models)."""

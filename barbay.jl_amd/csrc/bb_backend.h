@@ -565,6 +565,27 @@ BB_KERNEL(BB_HMC_NT, k_hmc_accum_stats, HmcArgs H, HmcAccArgs A) {
     BB_CTX;
     bb_block_hmc_accum_stats(cx, H, A);
 }
+// bb_nuts_* (bb_nuts.h): on bb_hmc_step's grid; k_nuts_reduce: grid = walkers
+BB_KERNEL(BB_HMC_NT, k_nuts_momentum, HmcArgs H, NutsArgs N) {
+    BB_CTX;
+    bb_block_nuts_momentum(cx, H, N);
+}
+BB_KERNEL(BB_HMC_NT, k_nuts_open, HmcArgs H, NutsArgs N) {
+    BB_CTX;
+    bb_block_nuts_open(cx, H, N);
+}
+BB_KERNEL(BB_HMC_NT, k_nuts_close, HmcArgs H, NutsArgs N) {
+    BB_CTX;
+    bb_block_nuts_close(cx, H, N);
+}
+BB_KERNEL(64, k_nuts_reduce, HmcArgs H, NutsArgs N) {
+    BB_CTX;
+    bb_block_nuts_reduce(cx, H, N);
+}
+BB_KERNEL(BB_HMC_NT, k_nuts_take, HmcArgs H, NutsArgs N) {
+    BB_CTX;
+    bb_block_nuts_take(cx, H, N);
+}
 #ifndef BB_EMU
 // transport probe of the cross-GPU leg: this rank's token into every peer's inbox, then every peer's token here
 __global__ void __launch_bounds__(64) k_p2p_probe_seq(DevState S, int rank, int world, size_t probe_words_off, unsigned seq, unsigned* result) {

@@ -1,7 +1,7 @@
 // bb_engine.hip -- host side of the C ABI declared in include/barbay_hip.h: the handle, the resident launchers, groups and the cross-GPU
 // leg; what a step launches is in bb_step.h, the launch plan in bb_plan.h, handle creation in bb_create.h, the run path (bb_run and its
 // kin) in bb_run.h, the post-fit entry points (hier fitness, log-density batch, bands, scores, chain summary) in bb_analysis.h and the HMC
-// session in bb_hmc_host.h with its streaming moments in bb_hmc_accum_host.h, all included below.
+// session in bb_hmc_host.h with its streaming moments in bb_hmc_accum_host.h and its NUTS tree in bb_nuts_host.h, all included below.
 //
 // Owns device memory, the HIP stream, captured hipGraphs of the step loop, and (optionally) an
 // RCCL communicator.  The compute is the block programs of bb_block.h launched as kernels.
@@ -33,6 +33,7 @@
 #include "bb_logp.h"
 #include "bb_hmc.h"
 #include "bb_hmc_accum.h"
+#include "bb_nuts.h"
 #include "bb_mathprobe.h"
 
 #include <algorithm>
@@ -140,6 +141,11 @@ struct DevBuf {
         if (!rc) { p = (double*)q; cap = n; }
         return rc;
     }
+    void release() {                   // (the next grow allocates afresh)
+        if (p) dfree(p);
+        p = nullptr;
+        cap = 0;
+    }
 };
 enum {
     BUF_EPS,       // bb_elbo_grad: device copy of caller-supplied draws
@@ -149,6 +155,7 @@ enum {
     BUF_CHAIN,     // bb_chain_summary: the slab as uploaded, its transpose and the slab's results
     BUF_HMC,       // bb_hmc_*: the session's walkers (state, proposal, momentum), metric and evaluation scratch; kept from begin to end
     BUF_HMC_ACC,   // bb_hmc_accum_*: the session's running moments per (walker, segment), the tables of a call and the four rows of the statistics
+    BUF_NUTS,      // bb_nuts_*: per walker the tree's edges, candidates and checkpoints, the chunk partials, the scalars and the table of a call
     BUF_COUNT
 };
 
@@ -201,6 +208,13 @@ struct bb_handle {
     bool acc_on = false;
     HmcAccArgs acc{};
     std::vector<long long> acc_n;      // [W][S] states added so far
+    // its NUTS tree (bb_nuts_*, bb_nuts_host.h): on while nuts_on is set; the device pointers of nuts lie in buf[BUF_NUTS]
+    bool nuts_on = false, nuts_started = false;      // (nuts_started: a bb_nuts_start since the last bb_nuts_begin / bb_hmc_step)
+    NutsArgs nuts{};
+    int* nuts_lf = nullptr;            // device: [Wp] 1 where the walker takes part in the call (LogpArgs.lf_n); behind nuts.op
+    std::vector<double> nuts_eps;      // [W] of the transition
+    std::vector<char> nuts_live, nuts_moving, nuts_has_sub, nuts_has_cand;      // [W] started; a leaf / a candidate exists since the start
+    std::vector<double> nuts_lp_leaf, nuts_lp_sub, nuts_lp_cand;              // host mirrors of the log-joints that go with those rows
     // the iterate trace (bb_trace_*, bb_trace.h): on while trace_ring is set
     double* trace_ring = nullptr;      // [trace_cap][2 D], the handle's own allocation (bb_trace_end frees it)
     int trace_every = 0, trace_cap = 0;
@@ -1019,6 +1033,8 @@ extern "C" int bb_p2p_enable(bb_handle* h, int32_t on) {
 #include "bb_hmc_host.h"
 // its streaming moments and the metric: bb_hmc_accum_*, bb_hmc_set_metric, bb_hmc_get_metric (bb_hmc_accum.h)
 #include "bb_hmc_accum_host.h"
+// its NUTS tree: bb_nuts_begin, bb_nuts_start, bb_nuts_leaf, bb_nuts_take (bb_nuts.h)
+#include "bb_nuts_host.h"
 
 extern "C" int bb_get_stats(bb_handle* h, bb_stats* s) {
     if (!h || !s) return bb_fail(BB_ERR_INVALID, "null argument");

@@ -49,7 +49,15 @@ static int hmc_metric_rows(const bb_handle* h, const double* inv_mass, std::vect
 extern "C" int bb_hmc_end(bb_handle* h) {
     if (!h) return bb_fail(BB_ERR_INVALID, "null argument");
     if (!h->hmc_ever) return bb_fail(BB_ERR_INVALID, "bb_hmc_end without a session: bb_hmc_begin comes first");
-    h->hmc_on = h->acc_on = false;     // (a second end: BB_OK)
+    h->hmc_on = h->acc_on = h->nuts_on = false;     // (a second end: BB_OK)
+    if (h->buf[BUF_NUTS].p) {                       // the tree's rows are the one large thing a session leaves behind: up to 7.6 GB.  They go now
+        BB_ENTER(h);
+        int rc = dsync(h->stream);
+        h->buf[BUF_NUTS].release();
+        h->nuts = NutsArgs{};
+        h->nuts_lf = nullptr;
+        if (rc) return rc;
+    }
     return BB_OK;
 }
 
@@ -64,7 +72,7 @@ extern "C" int bb_hmc_begin(bb_handle* h, const bb_hmc_opts* o, const double* z0
     std::vector<double> metric;
     if ((rc = hmc_metric_rows(h, o->inv_mass, metric))) return rc;
     BB_ENTER(h);
-    h->hmc_on = h->acc_on = false;     // (a begin that fails leaves no session; the accumulators go with the session they were begun on)
+    h->hmc_on = h->acc_on = h->nuts_on = false;     // (a begin that fails leaves no session; the accumulators and the NUTS rows go with the session they were begun on)
     const bool geno = M.kind == BB_MODEL_GENOTYPE;
     const size_t nbs = geno ? ((size_t)M.nb + 1) & ~(size_t)1 : 0, Gs = geno ? ((size_t)M.G + 1) & ~(size_t)1 : 0;
     const size_t nchunk = (Dz + BB_HMC_CHUNK - 1) / BB_HMC_CHUNK;
@@ -142,6 +150,7 @@ extern "C" int bb_hmc_step(bb_handle* h, const bb_hmc_step_opts* o, const bb_hmc
         lmax = std::max(lmax, (int)o->n_leapfrog[w]);
     }
     BB_ENTER(h);
+    h->nuts_started = false;           // (the travelling rows of a NUTS tree are redrawn: bb_nuts_start comes before its next leaf)
     // the transition's per-walker table: eps | n_leapfrog
     std::vector<double> tab((size_t)(Wp + Wp / 2), 0.0);
     memcpy(tab.data(), o->eps, (size_t)W * 8);

@@ -25,7 +25,8 @@ import numpy as np
 
 from . import utils
 from . import vi as _vi
-from ._capi import BB_CHAIN_MAX_K, BB_HMC_MAX_SEGMENTS, BB_HMC_MAX_WALKERS, BB_LOGP_MAX_BATCH, Engine
+from ._capi import (BB_CHAIN_MAX_K, BB_HMC_MAX_SEGMENTS, BB_HMC_MAX_WALKERS, BB_LOGP_MAX_BATCH, BB_NUTS_EDGE_OPP, BB_NUTS_MAX_DEPTH,
+                    BB_NUTS_TAKE_LEAF, BB_NUTS_TAKE_STATE, BB_NUTS_TAKE_SUB, Engine)
 from .model import BarBayError, BayesModel
 
 log = logging.getLogger("barbay")
@@ -342,6 +343,250 @@ def hmc_ensemble(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Gene
                                  "divergences": int(div[w]), "mean_leapfrog": float(leaps[w] / post[w]), **extra}) for w in range(W)]
 
 
+def nuts_leaf_op(i: int, j: int):
+    """(store, checks) of leaf i = 0 .. 2^j - 1 of a doubling of 2^j leaves, the ops `Engine.nuts_leaf` takes: with
+    idx_max = popcount(i >> 1) and k = the number of trailing one-bits of i, an even leaf is stored in checkpoint slot idx_max and an odd
+    leaf is checked against the slots idx_max down to idx_max - k + 1 -- the first leaves of the sub-subtrees of 2, 4, ..., 2^k leaves
+    that end at i, innermost first: `_build_tree`'s U-turn tests -- and the last leaf, behind them, against the opposite edge
+    (`_walker`'s test of the whole trajectory)."""
+    idx_max = bin(i >> 1).count("1")
+    if i & 1:
+        k = (~i & (i + 1)).bit_length() - 1
+        store, checks = -1, list(range(idx_max, idx_max - k, -1))
+    else:
+        store, checks = idx_max, []
+    if i == (1 << j) - 1:
+        checks.append(BB_NUTS_EDGE_OPP)
+    return store, checks
+
+
+def nuts_device(engine, z0s, n_steps, n_adapt, *, rngs: Sequence[np.random.Generator], target_accept: float = 0.65,
+                minv: Optional[np.ndarray] = None, max_depth: int = 10, thin: int = 1, seed: int = 0, adapt_metric: bool = False,
+                segments: int = 0, keep_chain: bool = True, trace: Optional[list] = None):
+    """len(z0s) <= BB_HMC_MAX_WALKERS NUTS chains (Hoffman & Gelman's algorithm 6 as `_walker` states it: slice variable, position
+    U-turn criterion, dual averaging with the same constants) whose every vector stays on the device: the session's state
+    (`Engine.hmc_begin`), both ends of the trajectory, the U-turn checkpoints and the candidates (`Engine.nuts_begin / nuts_start /
+    nuts_leaf / nuts_take`, csrc/bb_nuts.h).  The tree's decisions are made here, per walker, on the scalars a leaf brings back.  `engine`
+    is an Engine, or anything with those methods and `hmc_step / hmc_get / hmc_end`.
+
+    The walkers run in lock-step: every round issues one leaf for every walker whose tree still grows; a walker whose tree has ended idles
+    until the deepest is done.  Against `_build_tree` two things differ.  (1) A doubling's 2^j leaves are built iteratively, leaf by leaf
+    from the edge of side v; `nuts_leaf_op` says which checkpoint a leaf is stored in and which it is tested against, a test passing when
+    v a >= 0 and v b >= 0; a leaf is divergent when not logu < 1000 + h1 (a non-finite h1 counting as -inf); the first failure of either
+    kind ends the doubling and the transition, as the recursion does: the same leaves are visited and the same leaf stops the tree.
+    (2) The candidate of a doubling is chosen by reservoir: the c-th valid leaf (logu <= h1) is taken at once for c = 1 and otherwise
+    with probability 1 / c -- uniform over the valid leaves, as the recursion's n2 / (n1 + n2) merges are; a doubling that ends with
+    s true hands its candidate to the transition with probability min(1, n1 / n); the last leaf's test against the opposite edge
+    (`_walker`'s test of the whole trajectory) ends the transition without taking that away, as in `_walker`.
+    Walker w reads rngs[w] only, per transition in this order: log(random()) for logu; per doubling random() < 0.5 for v = -1; per valid
+    leaf with c >= 2 one random(), drawn before the leaf's U-turn tests are looked at; per completed doubling with s true one random().
+    A walker that has finished or idles draws nothing.  The momenta are the engine's normals (key `seed`, stream BB_HMC_STREAM0 + w,
+    step = the transition's number), those of `hmc_step`.  The start step size comes from `hmc_ensemble`'s probes (`hmc_step`, one
+    leapfrog, never accepted, transition 0); alpha / n_alpha of the dual averaging is that of the last doubling's leaves.
+
+    `thin`, `adapt_metric`, `segments`, `keep_chain` and a per-walker `n_steps` / `n_adapt`: as in `hmc_ensemble`.  `trace`: a list that
+    receives one dict per transition, {"m", "walkers": {w: {"depth", "leaves", "stop", "valid", "chosen", "divergent", "logu", "dirs"}}}
+    -- stop is "uturn", "divergent" or "depth"; valid and chosen hold (doubling, leaf) pairs, chosen the leaf whose position the
+    transition ended on (None: it stayed).
+
+    Returns a list, per walker, of (chain[n_steps, D], logp[n_steps], info), info holding `step_size`, `mean_tree_depth`, `n_grad`
+    (leaves, probes included), `accept_rate` (the mean alpha / n_alpha after the warm-up), `divergences` (transitions after the warm-up
+    with a divergent leaf) and `hmc_ensemble`'s `inv_mass` / `metric_windows` / `stream` extras."""
+    W = len(z0s)
+    if len(rngs) != W:
+        raise BarBayError("nuts_device needs one random generator per walker")
+    if not 1 <= W <= BB_HMC_MAX_WALKERS:
+        raise BarBayError(f"nuts_device runs 1 .. {BB_HMC_MAX_WALKERS} walkers in one session, not {W}")
+    if not 1 <= int(max_depth) <= BB_NUTS_MAX_DEPTH or thin < 1:
+        raise BarBayError(f"max_depth must lie in 1 .. {BB_NUTS_MAX_DEPTH} and thin be >= 1, not {max_depth!r}, {thin!r}")
+    max_depth = int(max_depth)
+    per = lambda v, w: int(v[w]) if np.ndim(v) else int(v)
+    n_st = np.array([per(n_steps, w) for w in range(W)])
+    n_ad = np.array([per(n_adapt, w) for w in range(W)])
+    S = int(segments)
+    if adapt_metric and not (n_ad == n_ad[0]).all():
+        raise BarBayError("adapt_metric needs one n_adapt for all walkers: the session has one metric")
+    if not 0 <= S <= BB_HMC_MAX_SEGMENTS or (S > 0 and (n_st < 2 * S).any()):
+        raise BarBayError(f"segments must lie in 0 .. {BB_HMC_MAX_SEGMENTS} and every walker keep at least 2 draws per segment, not "
+                          f"segments = {segments!r} with n_steps = {n_steps!r}")
+    if not keep_chain and S == 0:
+        raise BarBayError("keep_chain=False needs segments > 0: without the chain the streamed summary is all that is returned")
+    windows = _adapt_windows(n_ad[0]) if adapt_metric else []
+    Z0 = np.stack([np.asarray(z, dtype=np.float64) for z in z0s])
+    D = Z0.shape[1]
+    session = engine.hmc_begin(Z0, seed=seed, inv_mass=minv)
+    try:
+        lp = np.array(session.logp, dtype=np.float64)
+        if not np.isfinite(lp).all():
+            raise BarBayError("log density is not finite at the initial point")
+        engine.nuts_begin(max_depth)
+        if windows or S > 0:
+            engine.hmc_accum_begin(max(S, 1))
+        n_grad = np.zeros(W, dtype=np.int64)
+        # the start step size: _find_step's rule on probes of one leapfrog, every probe with transition 0's momenta (as hmc_ensemble)
+        eps = np.ones(W)
+        dh = lambda r: np.where(np.isfinite(r["h1"]), r["h1"] - r["h0"], -np.inf)
+        d = dh(engine.hmc_step(0, eps, 1, np.inf))
+        n_grad += 1
+        a = np.where(d > np.log(0.5), 1.0, -1.0)
+        done = np.zeros(W, dtype=bool)
+        for _ in range(60):
+            done |= a * d <= -a * np.log(2.0)
+            if done.all():
+                break
+            eps = np.where(done, eps, eps * 2.0 ** a)
+            d = np.where(done, d, dh(engine.hmc_step(0, eps, 1, np.inf)))
+            n_grad += ~done
+        mu, eps_bar, h_bar = np.log(10.0 * eps), np.ones(W), np.zeros(W)
+        gamma, t0, kappa = 0.05, 10.0, 0.75
+        chains = [np.empty((n_st[w] if keep_chain else 0, D)) for w in range(W)]
+        lps = [np.empty(n_st[w] if keep_chain else 0) for w in range(W)]
+        acc, div, depths = np.zeros(W), np.zeros(W, dtype=np.int64), np.zeros(W)
+        total = n_ad + n_st * thin
+        da0 = 0
+        metric, metric_windows = None, []
+        win_end = {end: start for start, end in windows}
+        in_window = lambda m: any(start < m <= end for start, end in windows)
+        for m in range(1, int(total.max()) + 1):
+            live = m <= total
+            k0 = engine.nuts_start(m, eps, live.astype(np.int32))
+            # per walker: the transition's and the doubling's scalars
+            h0, logu = lp - k0, np.zeros(W)
+            build = live.copy()                                               # the tree still grows
+            j, n, v, i = np.zeros(W, dtype=int), np.ones(W, dtype=int), np.zeros(W, dtype=int), np.zeros(W, dtype=int)
+            c, alpha, n_alpha = np.zeros(W, dtype=int), np.zeros(W), np.zeros(W, dtype=int)
+            lp_leaf, lp_sub, lp_cand = np.zeros(W), np.zeros(W), np.zeros(W)
+            has_cand, diverged = np.zeros(W, dtype=bool), np.zeros(W, dtype=bool)
+            rec = {w: {"depth": 0, "leaves": 0, "stop": None, "valid": [], "chosen": None, "divergent": False, "dirs": [], "_sub": None}
+                   for w in np.flatnonzero(live)}
+            for w in np.flatnonzero(live):
+                logu[w] = h0[w] + np.log(rngs[w].random())
+                rec[w]["logu"] = float(logu[w])
+            while build.any():
+                dirs, first, last, store = (np.zeros(W, dtype=np.int32) for _ in range(4))
+                checks = [[] for _ in range(W)]
+                store[:] = -1
+                for w in np.flatnonzero(build):
+                    if i[w] == 0:                                             # a doubling begins
+                        v[w] = -1 if rngs[w].random() < 0.5 else 1
+                        c[w], alpha[w], n_alpha[w] = 0, 0.0, 0
+                        rec[w]["dirs"].append(int(v[w]))
+                    dirs[w], first[w], last[w] = v[w], i[w] == 0, i[w] == (1 << j[w]) - 1
+                    store[w], checks[w] = nuts_leaf_op(int(i[w]), int(j[w]))
+                r = engine.nuts_leaf(dirs, first, last, store, checks)
+                flags = np.zeros(W, dtype=np.int32)
+                for w in np.flatnonzero(build):
+                    h1 = r["logp_leaf"][w] - r["kinetic"][w]
+                    fin = bool(np.isfinite(h1))
+                    if not fin:
+                        h1 = -np.inf
+                    lp_leaf[w] = r["logp_leaf"][w]
+                    rec[w]["leaves"] += 1
+                    alpha[w] += min(1.0, float(np.exp(min(0.0, h1 - h0[w])))) if fin else 0.0
+                    n_alpha[w] += 1
+                    s = bool(logu[w] < 1000.0 + h1)
+                    if not s:
+                        diverged[w] = True
+                        rec[w]["divergent"], rec[w]["stop"] = True, "divergent"
+                    if logu[w] <= h1:                                         # a valid leaf: the reservoir
+                        c[w] += 1
+                        rec[w]["valid"].append((int(j[w]), int(i[w])))
+                        if c[w] == 1 or rngs[w].random() < 1.0 / c[w]:
+                            flags[w] |= BB_NUTS_TAKE_LEAF
+                            lp_sub[w] = lp_leaf[w]
+                            rec[w]["_sub"] = (int(j[w]), int(i[w]))
+                    whole = True                                              # the test of the whole trajectory (the last leaf's)
+                    if s:
+                        for q, slot in enumerate(checks[w]):
+                            if not (v[w] * r["a"][w][q] >= 0.0 and v[w] * r["b"][w][q] >= 0.0):
+                                if slot == BB_NUTS_EDGE_OPP:
+                                    whole = False
+                                else:
+                                    s = False
+                                rec[w]["stop"] = "uturn"
+                                break
+                    ends = not s or last[w]
+                    if s and last[w]:                                         # the doubling is complete: _walker's s1
+                        if rngs[w].random() < min(1.0, c[w] / n[w]):
+                            if c[w] > 0:
+                                flags[w] |= BB_NUTS_TAKE_SUB
+                                lp_cand[w], has_cand[w] = lp_sub[w], True
+                                rec[w]["chosen"] = rec[w]["_sub"]
+                        n[w] += c[w]
+                    if ends:
+                        n_grad[w] += n_alpha[w]
+                        j[w] += 1
+                        i[w] = 0
+                        if not (s and whole) or j[w] >= max_depth:            # the transition is complete
+                            build[w] = False
+                            rec[w]["depth"] = int(j[w])
+                            if rec[w]["stop"] is None:
+                                rec[w]["stop"] = "depth"
+                            if has_cand[w]:
+                                flags[w] |= BB_NUTS_TAKE_STATE
+                                lp[w] = lp_cand[w]
+                    else:
+                        i[w] += 1
+                if flags.any():
+                    engine.nuts_take(flags)
+            if trace is not None:
+                for x in rec.values():
+                    del x["_sub"]
+                trace.append({"m": m, "walkers": {int(w): x for w, x in rec.items()}})
+            keep = None
+            seg = np.full(W, -1, dtype=np.int32)
+            md = m - da0
+            for w in np.flatnonzero(live):
+                if m <= n_ad[w]:
+                    h_bar[w] = (1.0 - 1.0 / (md + t0)) * h_bar[w] + (target_accept - alpha[w] / max(n_alpha[w], 1)) / (md + t0)
+                    eps[w] = float(np.exp(mu[w] - np.sqrt(md) / gamma * h_bar[w]))
+                    x = md ** -kappa
+                    eps_bar[w] = float(np.exp(x * np.log(eps[w]) + (1.0 - x) * np.log(eps_bar[w])))
+                    if m == n_ad[w]:
+                        eps[w] = eps_bar[w]
+                    continue
+                acc[w] += alpha[w] / max(n_alpha[w], 1)
+                div[w] += diverged[w]
+                depths[w] += j[w]
+                if (m - n_ad[w]) % thin == 0:
+                    k = (m - n_ad[w]) // thin - 1
+                    if S > 0:
+                        seg[w] = S * k // n_st[w]
+                    if not keep_chain:
+                        continue
+                    if keep is None:
+                        keep = engine.hmc_get()                               # (one download for all the walkers that keep this draw)
+                    chains[w][k] = keep[0][w]
+                    lps[w][k] = keep[1][w]
+            if (seg >= 0).any():
+                engine.hmc_accum_add(seg)
+            if windows and in_window(m):
+                engine.hmc_accum_add(0)
+                if m in win_end:                                              # the window's variance becomes the metric
+                    st = engine.hmc_accum_stats()
+                    K = float(st["n_total"])
+                    metric = st["sd"] ** 2 * (K / (K + 5.0)) + 1e-3 * (5.0 / (K + 5.0))
+                    engine.hmc_set_metric(metric)
+                    engine.hmc_accum_reset()
+                    metric_windows.append((win_end[m], m))
+                    if m < n_ad[0]:
+                        mu, eps_bar, h_bar, da0 = np.log(10.0 * eps), np.ones(W), np.zeros(W), m
+            if windows and S > 0 and m == n_ad[0]:
+                engine.hmc_accum_reset()
+        stream = engine.hmc_accum_stats() if S > 0 else None
+    finally:
+        engine.hmc_end()
+    post = np.maximum(n_st * thin, 1)
+    extra = {}
+    if adapt_metric:
+        extra.update(inv_mass=np.array(metric if metric is not None else (np.ones(D) if minv is None else minv), dtype=np.float64),
+                     metric_windows=metric_windows)
+    if S > 0:
+        extra.update(stream=stream)
+    return [(chains[w], lps[w], {"step_size": float(eps[w]), "mean_tree_depth": float(depths[w] / post[w]), "n_grad": int(n_grad[w]),
+                                 "accept_rate": float(acc[w] / post[w]), "divergences": int(div[w]), **extra}) for w in range(W)]
+
+
 SUMMARY_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)                  # MCMCChains.quantile's default q
 _SUMMARY_KEYS = (("mean", "mean"), ("std", "sd"), ("mcse", "mcse"), ("ess", "ess"), ("rhat", "rhat"))
 
@@ -404,7 +649,7 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
                 genotype_col: Optional[str] = None, rm_T0: bool = False, target_accept: float = 0.65,
                 n_adapt: Optional[int] = None, advi_steps: int = 3000, verbose: bool = True, seed: int = 0, device: int = 0,
                 engine_kwargs: Optional[Dict] = None, ensemble: str = "serial", summary: bool = False, sampler: str = "nuts",
-                hmc_kwargs: Optional[Dict] = None):
+                hmc_kwargs: Optional[Dict] = None, nuts_kwargs: Optional[Dict] = None):
     """src/mcmc.jl:86-160.  `sampler = Turing.NUTS(0.65)` becomes `target_accept`.  `ensemble` (the reference's
     `MCMCSerial()` / `MCMCThreads()` / `MCMCDistributed()`, all on one device here): "serial" runs the walkers one after another,
     all drawing from `default_rng(seed)`; "batched" steps them in lock-step, walker w drawing from `default_rng([seed, w])`, every
@@ -422,19 +667,30 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
     `stream_n` (`Engine.hmc_accum_stats`: `stream_ess` / `stream_mcse` are batch-means estimates over the walkers' segments, not the
     `summary_*` ones), which `summarize` tabulates when the output has no chain (`keep_chain=False`: `chain` has 0 draws and no position
     is ever downloaded).  Both need all walkers in one session, n_walkers <= BB_HMC_MAX_WALKERS; `summary=True` needs the chain.  Both
-    are checked before anything is sampled."""
+    are checked before anything is sampled.
+    `ensemble="device"` (with `sampler="nuts"` only): `nuts_device`, the NUTS above with every vector of its tree on the device, from the
+    same ADVI start and metric, in chunks of BB_HMC_MAX_WALKERS walkers with `hmc`'s generators and seed rule per chunk; `nuts_kwargs` go
+    to `nuts_device` (`max_depth`, `thin`, `adapt_metric`, `segments`, `keep_chain`, with `hmc_kwargs`' conditions).  The output has
+    `sampler="hmc"`'s keys and `mean_tree_depth`."""
     if sampler not in ("nuts", "hmc"):
         raise BarBayError(f"sampler must be 'nuts' or 'hmc', not {sampler!r}")
-    if ensemble not in ("serial", "batched"):
-        raise BarBayError(f"ensemble must be 'serial' or 'batched', not {ensemble!r}")
+    if ensemble not in ("serial", "batched", "device"):
+        raise BarBayError(f"ensemble must be 'serial', 'batched' or 'device', not {ensemble!r}")
+    device_nuts = ensemble == "device"
+    if device_nuts and sampler != "nuts":
+        raise BarBayError(f"ensemble='device' is the device-resident NUTS: sampler must be 'nuts', not {sampler!r} (sampler='hmc' is "
+                          f"device-resident whatever `ensemble`)")
+    if nuts_kwargs and not device_nuts:
+        raise BarBayError("nuts_kwargs go to nuts_device: they need sampler='nuts' with ensemble='device'")
     if summary and (n_walkers < 1 or n_steps < 4 or n_walkers * n_steps > BB_CHAIN_MAX_K):
         raise BarBayError(f"summary=True needs n_walkers >= 1, n_steps >= 4 and n_walkers * n_steps <= {BB_CHAIN_MAX_K}, not "
                           f"{n_walkers} x {n_steps}: sample with summary=False and summarize fewer draws")
-    hk = hmc_kwargs or {}
-    if sampler == "hmc" and (hk.get("segments", 0) or hk.get("adapt_metric", False)) and n_walkers > BB_HMC_MAX_WALKERS:
+    hk = (nuts_kwargs if device_nuts else hmc_kwargs) or {}
+    resident = sampler == "hmc" or device_nuts
+    if resident and (hk.get("segments", 0) or hk.get("adapt_metric", False)) and n_walkers > BB_HMC_MAX_WALKERS:
         raise BarBayError(f"segments / adapt_metric need all walkers in one session: n_walkers <= BB_HMC_MAX_WALKERS = "
                           f"{BB_HMC_MAX_WALKERS}, not {n_walkers}")
-    if sampler == "hmc" and summary and not hk.get("keep_chain", True):
+    if resident and summary and not hk.get("keep_chain", True):
         raise BarBayError("summary=True needs the chain: keep_chain=False returns the streamed summary (stream_*) alone")
     fname = None if outputname is None else f"{outputname}.npz"
     if fname is not None and os.path.isfile(fname):                                # :104-106
@@ -475,15 +731,16 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
         chains, lps, infos = [], [], []
         spread = 0.1 if advi_steps > 0 else 0.0
         batched = []
-        lockstep = ensemble == "batched" or sampler == "hmc"
+        lockstep = ensemble == "batched" or resident
         if lockstep:
             rngs = [np.random.default_rng([seed, w]) for w in range(n_walkers)]
             z0s = [mean + np.sqrt(minv) * r.standard_normal(mean.shape[0]) * spread for r in rngs]
             for lo in range(0, n_walkers, BB_LOGP_MAX_BATCH):                 # (= BB_HMC_MAX_WALKERS)
                 hi = min(lo + BB_LOGP_MAX_BATCH, n_walkers)
-                if sampler == "hmc":                                          # (a walker's stream is its index in the chunk: a key per chunk)
-                    batched += hmc_ensemble(e, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi], target_accept=target_accept, minv=minv,
-                                            seed=(seed + 0x9E3779B97F4A7C15 * (lo // BB_LOGP_MAX_BATCH)) % 2 ** 64, **(hmc_kwargs or {}))
+                if resident:                                                  # (a walker's stream is its index in the chunk: a key per chunk)
+                    batched += (nuts_device if device_nuts else hmc_ensemble)(
+                        e, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi], target_accept=target_accept, minv=minv,
+                        seed=(seed + 0x9E3779B97F4A7C15 * (lo // BB_LOGP_MAX_BATCH)) % 2 ** 64, **hk)
                 else:
                     batched += nuts_ensemble(e.logdensity_grad_batch, z0s[lo:hi], n_steps, n_adapt, rngs=rngs[lo:hi],
                                              target_accept=target_accept, minv=minv)
@@ -508,8 +765,8 @@ def mcmc_sample(*, data, n_walkers: int, n_steps: int, outputname: Optional[str]
         var_names += [f"{sym}[{x}]" for x in range(1, hi - lo + 1)]
     out = {"ids": np.asarray(arrays.bc_ids, dtype=object), "var_names": np.asarray(var_names, dtype=object),
            "chain": np.stack(chains), "logp": np.stack(lps), "step_size": np.asarray([i["step_size"] for i in infos]), **summ}
-    if sampler == "hmc":
-        out.update({k: np.asarray([i[k] for i in infos]) for k in ("accept_rate", "divergences", "n_grad")})
+    if resident:
+        out.update({k: np.asarray([i[k] for i in infos]) for k in ("accept_rate", "divergences", "n_grad") + (("mean_tree_depth",) if device_nuts else ())})
         if "inv_mass" in infos[0]:
             out["inv_mass"] = infos[0]["inv_mass"]
         if "stream" in infos[0]:

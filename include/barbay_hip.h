@@ -300,7 +300,8 @@ int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z /* 
  * Hamiltonian Monte Carlo with a diagonal metric and a fixed number of leapfrogs per transition, chosen per walker by the caller.
  * Position, momentum and gradient of every walker stay on the device from bb_hmc_begin to bb_hmc_end; one bb_hmc_step makes one
  * transition of all walkers and brings back scalars only; bb_hmc_get downloads the walkers' positions when a draw is kept.  The NUTS
- * tree of barbay.jl_amd.mcmc stays on the host (bb_logdensity_grad_batch).  No reference counterpart: the reference samples with
+ * tree of barbay.jl_amd.mcmc.nuts_ensemble stays on the host (bb_logdensity_grad_batch); bb_nuts_* below keeps a tree's vectors beside
+ * this session.  No reference counterpart: the reference samples with
  * Turing.NUTS (src/mcmc.jl:86-160).
  *
  * bb_hmc_begin: a session of n_walkers walkers at z0 on a buffer of its own -- a bb_logdensity_grad_batch between two steps does not
@@ -330,7 +331,8 @@ int bb_logdensity_grad_batch(bb_handle* h, int32_t n_points, const double* z /* 
  *    whatever the handle's launch mode and whatever was called before.  The handle's mu, omega, optimiser state, step counter and RNG
  *    position are untouched, bitwise.
  * bb_hmc_get: the walkers' current z, logp and g, caller's order; bb_hmc_get's logp and grad equal bb_logdensity_grad_batch at its z.
- * bb_hmc_end: closes the session (a second bb_hmc_end: BB_OK); the buffer stays with the handle until bb_destroy.
+ * bb_hmc_end: closes the session (a second bb_hmc_end: BB_OK); the session's buffer (40 W D bytes) and the accumulators' stay with the handle
+ *  until bb_destroy, the NUTS tree's rows (bb_nuts_begin below: up to 7.6 GB) are freed here.
  * Errors: BB_ERR_INVALID -- a null h, o or z0; n_walkers outside 1 .. BB_HMC_MAX_WALKERS; an inv_mass entry that is not finite or not > 0
  *  (the message names its index); an eps that is not finite or not > 0, an n_leapfrog outside 1 .. BB_HMC_MAX_LEAPFROG or a NaN log_u (the
  *  message names the walker); reserved0 != 0; bb_hmc_step or bb_hmc_get without a session, bb_hmc_end on a handle that never had one.  BB_ERR_UNSUPPORTED -- sharded
@@ -426,6 +428,74 @@ int bb_hmc_accum_get(bb_handle* h, int32_t walker, int32_t segment, double* mean
 int bb_hmc_accum_stats(bb_handle* h, const bb_hmc_accum_out* out);
 int bb_hmc_set_metric(bb_handle* h, const double* inv_mass /* [D] caller's order, finite and > 0; NULL: ones */);
 int bb_hmc_get_metric(bb_handle* h, double* inv_mass /* [D] caller's order */);
+
+/* ---- the No-U-Turn tree of an HMC session on the device (csrc/bb_nuts.h) ---------------------------------------------------------
+ * Every D-sized object of a NUTS transition (Hoffman & Gelman 2014, algorithm 6) stays on the device, beside the session: both ends of
+ * the trajectory, the U-turn checkpoints of an iteratively built subtree, the subtree's candidate and the transition's candidate.  The
+ * caller keeps the tree's control flow, per walker, on the scalars a leaf brings back (barbay.jl_amd.mcmc.nuts_device is such a caller).
+ * The reference samples with Turing.NUTS (src/mcmc.jl:86-160); it has no counterpart of these calls.
+ *
+ * bb_nuts_begin: needs a session; allocates and zeroes, in a buffer of its own, 10 + 2 max_depth rows per walker of the session's even
+ *  stride, the handle's latent order: the two edges (z, r, g each), the subtree's candidate (z, g), the transition's candidate (z, g),
+ *  max_depth checkpoint slots (z, r each) -- 8 (10 + 2 max_depth) D bytes per walker, 7.6 GB for 64 walkers of D = 498 014 at depth
+ *  10.  A second call replaces them.  bb_hmc_end drops them AND frees their buffer, the one large thing a session would otherwise leave with the
+ *  handle; bb_hmc_begin drops them and keeps the buffer for the next bb_nuts_begin (a handle that never calls bb_hmc_end keeps it until
+ *  bb_destroy).
+ * bb_nuts_start: a transition begins for the walkers with live[w] != 0: the momentum r and kinetic0 of bb_hmc_step at the same
+ *  `transition` (the same normals, products and order of the sum: bit for bit), and (z, r, g) of the session's state written to both
+ *  edges.  The session's z, g and logp are not touched.  kinetic0 of a walker that is not live: 0.
+ * bb_nuts_leaf: one leapfrog of every walker with dir[w] != 0, e = dir[w] * eps[w] (the eps of bb_nuts_start), fma: one rounding:
+ *  - the leaf starts from the edge of side dir[w] where first[w] != 0, else from where the walker's last leaf ended (the travelling rows,
+ *    which are the session's proposal rows);
+ *  - r = fma(e / 2, g, r); z = fma(e * inv_mass_i, r, z), the product rounded once; logp_leaf and g at z by the kernels of
+ *    bb_logdensity_grad_batch; r = fma(e / 2, g, r);
+ *  - kinetic = 0.5 * sum_i inv_mass_i r_i r_i in bb_hmc_step's order;
+ *  - for j < n_check[w], against the stored point (z_c, r_c) = checkpoint slot check[w][j], or the edge of side -dir[w] for
+ *    BB_NUTS_EDGE_OPP:   a[w][j] = sum_i (z_i - z_c,i) * (inv_mass_i * r_c,i),   b[w][j] = sum_i (z_i - z_c,i) * (inv_mass_i * r_i),
+ *    the difference and the product each rounded on their own, then acc = fma(difference, product, acc), in the latent order, fold and
+ *    chunk order of the kinetic sum (bb_hmc_step above).  No atomics;
+ *  - store[w] >= 0: (z, r) of the leaf is written to that checkpoint slot; last[w] != 0: (z, r, g) to the edge of side dir[w].
+ *  A walker with dir[w] == 0 takes no part (its workgroups leave at once) and its outputs are 0; so are a, b beyond n_check[w].
+ * bb_nuts_take: per walker, the copies its flags ask for, in this order: BB_NUTS_TAKE_LEAF the last leaf's (z, g, logp) becomes the
+ *  subtree's candidate; BB_NUTS_TAKE_SUB the subtree's candidate becomes the transition's; BB_NUTS_TAKE_STATE the transition's candidate
+ *  becomes the session's z, g and logp -- what bb_hmc_get, bb_hmc_accum_add and the next bb_nuts_start then read.
+ * Interleaving: a bb_hmc_step between two transitions is legal (it redraws the travelling rows, so a bb_nuts_start must follow it before
+ *  the next leaf); bb_logdensity_grad_batch, bb_hmc_get and the bb_hmc_accum_* calls may come anywhere.
+ * Independence: a walker's leaf outputs and rows are a function of its own state, ops, eps, inv_mass, seed, transition and session index
+ *  alone: bit-identical whatever n_walkers, the other walkers' ops or a non-finite neighbour, the handle's launch mode and what was
+ *  called before.  The handle's mu, omega, optimiser state, step counter and RNG position are untouched, bitwise.
+ * Errors: BB_ERR_INVALID -- a null argument; no session; no bb_nuts_begin (or a bb_hmc_begin / bb_hmc_end since); a leaf or a take before
+ *  bb_nuts_start; max_depth outside 1 .. BB_NUTS_MAX_DEPTH; reserved0 != 0; and, the message naming the walker: an eps of a live walker
+ *  that is not finite or not > 0, a dir outside -1 .. 1, a leaf or take of a walker that was not live, a first leaf without first, a
+ *  store outside -1 .. max_depth - 1, an n_check outside 0 .. max_depth + 1, a check that is neither a slot nor BB_NUTS_EDGE_OPP, a slot
+ *  both stored and checked in one op, flags beyond the three bits, a take of a candidate that does not exist yet.  BB_ERR_UNSUPPORTED --
+ *  sharded and multi-device handles, as for bb_hmc_*.  BB_ERR_DEVICE -- the device cannot allocate the rows: nothing is kept. */
+#define BB_NUTS_MAX_DEPTH   10
+#define BB_NUTS_EDGE_OPP    (-2)
+#define BB_NUTS_TAKE_LEAF   1
+#define BB_NUTS_TAKE_SUB    2
+#define BB_NUTS_TAKE_STATE  4
+typedef struct bb_nuts_opts {
+    int32_t max_depth;          /* 1 .. BB_NUTS_MAX_DEPTH: the number of checkpoint slots */
+    int32_t reserved0;          /* 0 */
+} bb_nuts_opts;
+typedef struct bb_nuts_leaf_opts {
+    const int32_t* dir;         /* [W] -1, +1; 0: the walker is idle */
+    const int32_t* first;       /* [W] != 0: the first leaf of its doubling (start from the edge of side dir) */
+    const int32_t* last;        /* [W] != 0: the last leaf of its doubling (becomes the edge of side dir) */
+    const int32_t* store;       /* [W] -1, or the checkpoint slot that takes the leaf */
+    const int32_t* n_check;     /* [W] 0 .. max_depth + 1 */
+    const int32_t* check;       /* [W][BB_NUTS_MAX_DEPTH + 1]: slots, or BB_NUTS_EDGE_OPP */
+    int32_t reserved0;          /* 0 */
+} bb_nuts_leaf_opts;
+typedef struct bb_nuts_leaf_out {      /* every pointer may be NULL */
+    double *logp_leaf, *kinetic;       /* [W] */
+    double *a, *b;                     /* [W][max_depth + 1] */
+} bb_nuts_leaf_out;
+int bb_nuts_begin(bb_handle* h, const bb_nuts_opts* o);
+int bb_nuts_start(bb_handle* h, uint32_t transition, const double* eps /* [W] */, const int32_t* live /* [W] */, double* kinetic0 /* [W] or NULL */);
+int bb_nuts_leaf(bb_handle* h, const bb_nuts_leaf_opts* o, const bb_nuts_leaf_out* out /* or NULL */);
+int bb_nuts_take(bb_handle* h, const int32_t* flags /* [W]: BB_NUTS_TAKE_* or 0 */);
 
 /* ELBO estimates recorded by bb_run (elbo_every > 0): values of steps
  * first_step, first_step + elbo_every, ... ; NaN where not recorded/kept. */

@@ -1051,6 +1051,91 @@ function hmc_get_metric(h::Ptr{Cvoid})
     return im
 end
 
+# The No-U-Turn tree of the open session on the device (bb_nuts_begin / bb_nuts_start / bb_nuts_leaf / bb_nuts_take, include/barbay_hip.h):
+# both ends of the trajectory, the U-turn checkpoints and the candidates stay on the device; the caller decides on the scalars a leaf
+# brings back.  Field for field the Python binding's `bb_nuts_opts`, `bb_nuts_leaf_opts`, `bb_nuts_leaf_out` (barbay.jl_amd/_capi.py).
+# Like the rest of this file it has not been executed: no Julia here.
+const BB_NUTS_MAX_DEPTH = 10
+const BB_NUTS_EDGE_OPP = Int32(-2)
+const BB_NUTS_TAKE_LEAF = Int32(1)
+const BB_NUTS_TAKE_SUB = Int32(2)
+const BB_NUTS_TAKE_STATE = Int32(4)
+struct bb_nuts_opts
+    max_depth::Int32
+    reserved0::Int32
+end
+struct bb_nuts_leaf_opts
+    dir::Ptr{Int32}
+    first::Ptr{Int32}
+    last::Ptr{Int32}
+    store::Ptr{Int32}
+    n_check::Ptr{Int32}
+    check::Ptr{Int32}
+    reserved0::Int32
+end
+struct bb_nuts_leaf_out
+    logp_leaf::Ptr{Float64}
+    kinetic::Ptr{Float64}
+    a::Ptr{Float64}
+    b::Ptr{Float64}
+end
+
+"""
+    nuts_begin(h; max_depth=BB_NUTS_MAX_DEPTH)
+
+Allocates and zeroes the tree's rows beside the open session: per walker 10 + 2 `max_depth` rows.  `hmc_begin` and `hmc_end` drop them.
+"""
+nuts_begin(h::Ptr{Cvoid}; max_depth::Integer=BB_NUTS_MAX_DEPTH) =
+    check(ccall((:bb_nuts_begin, LIB), Cint, (Ptr{Cvoid}, Ref{bb_nuts_opts}), h, bb_nuts_opts(Int32(max_depth), Int32(0))))
+
+"""
+    nuts_start(h, transition, eps, live) -> kinetic0
+
+A transition begins for the walkers with `live[w] != 0`: `hmc_step`'s momenta of `transition`, the state to both edges.
+"""
+function nuts_start(h::Ptr{Cvoid}, transition::Integer, eps::AbstractVector{Float64}, live::AbstractVector{<:Integer})
+    W = length(eps)
+    length(live) == W || error("nuts_start: eps and live need one entry per walker")
+    e, lv, k0 = Vector{Float64}(eps), Vector{Int32}(live), Vector{Float64}(undef, W)
+    check(ccall((:bb_nuts_start, LIB), Cint, (Ptr{Cvoid}, UInt32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), h, UInt32(transition), e, lv, k0))
+    return k0
+end
+
+"""
+    nuts_leaf(h, max_depth, dir, first, last, store, checks) -> NamedTuple
+
+One leaf of every walker with `dir[w] != 0`; `checks[w]` lists the stored points the leaf is tested against (0-based checkpoint slots, or
+BB_NUTS_EDGE_OPP).  Returns logp_leaf, kinetic (W) and a, b ((max_depth + 1) x W, column w the walker's).
+"""
+function nuts_leaf(h::Ptr{Cvoid}, max_depth::Integer, dir::AbstractVector{<:Integer}, first::AbstractVector{<:Integer},
+                   last::AbstractVector{<:Integer}, store::AbstractVector{<:Integer}, checks::AbstractVector)
+    W = length(dir)
+    length(first) == W && length(last) == W && length(store) == W && length(checks) == W || error("nuts_leaf: one entry per walker")
+    d, f, l, st = Vector{Int32}(dir), Vector{Int32}(first), Vector{Int32}(last), Vector{Int32}(store)
+    nc = Int32[length(c) for c in checks]
+    ck = zeros(Int32, BB_NUTS_MAX_DEPTH + 1, W)
+    for w in 1:W, (j, c) in enumerate(checks[w])
+        j <= BB_NUTS_MAX_DEPTH + 1 && (ck[j, w] = c)
+    end
+    lp, kin = Vector{Float64}(undef, W), Vector{Float64}(undef, W)
+    a, b = Matrix{Float64}(undef, max_depth + 1, W), Matrix{Float64}(undef, max_depth + 1, W)
+    GC.@preserve d f l st nc ck lp kin a b begin
+        o = bb_nuts_leaf_opts(pointer(d), pointer(f), pointer(l), pointer(st), pointer(nc), pointer(ck), Int32(0))
+        out = bb_nuts_leaf_out(pointer(lp), pointer(kin), pointer(a), pointer(b))
+        check(ccall((:bb_nuts_leaf, LIB), Cint, (Ptr{Cvoid}, Ref{bb_nuts_leaf_opts}, Ref{bb_nuts_leaf_out}), h, o, out))
+    end
+    return (logp_leaf=lp, kinetic=kin, a=a, b=b)
+end
+
+"""
+    nuts_take(h, flags)
+
+Per walker the copies its flags ask for, in this order: BB_NUTS_TAKE_LEAF (leaf -> subtree candidate), BB_NUTS_TAKE_SUB (subtree candidate
+-> transition candidate), BB_NUTS_TAKE_STATE (transition candidate -> the session's state).
+"""
+nuts_take(h::Ptr{Cvoid}, flags::AbstractVector{<:Integer}) =
+    check(ccall((:bb_nuts_take, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}), h, Vector{Int32}(flags)))
+
 # Chain diagnostics (bb_chain_summary, include/barbay_hip.h): MCMCChains' summarystats + quantile of a host chain, on the device.
 # Field for field the Python binding's `bb_chain_opts` / `bb_chain_out` (barbay.jl_amd/_capi.py).
 const BB_CHAIN_MAX_K = 16384
